@@ -19,6 +19,12 @@ region itself without the second stream, which is the command the committed rocp
 (profiles/) were taken with.
 `cpu_baseline` times the CPU oracle (PyTorch-CPU/oneDNN restatement of the same step, fp32, with clip+Adam) on
 this box's host cores on a bounded sample: BASELINE configs[0]'s batch of 2, median of 3 steps after one warm-up.
+
+A plain run measures the headline only: set-up, `--warmup` untimed steps, `--steps` timed steps, the result line
+(`ms_per_step` = wall time of the timed steps / --steps).  Everything else runs after the timed steps and only with
+`--full`: the serialized per-kernel replay (`roofline`, `roofline_hbm`), `extra.f32x3`, `north_star_block` with its
+ceiling, `extra_configs` and `cpu_baseline` (each can still be switched off with its --no-* option).
+`--dump-outputs DIR` writes what the last timed step computed to DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -56,7 +62,18 @@ def main():
     ap.add_argument("--dtype", type=str, default="f32", choices=["f32", "bf16", "f32x3"],
                     help="f32 = BASELINE configs[1] (default, the headline line: exact-fp32 MFMA); bf16 = configs[3]/[4] (bf16 MFMA path); f32x3 = fp32 "
                          "tensors with the 3x3 unit-stride convolutions as six bf16 MFMA products of exact three-plane splits (opt-in: wgrad.f32_split, conv.f32_split)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also the per-kernel replay (roofline), f32x3 / bf16 extra configurations, north-star block and "
+                         "ceiling, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, at most 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    # a plain run does what the headline needs and nothing else; --per-shape asks for the per-kernel replay by itself
+    kernel_timer = (args.full and not args.no_kernel_timer) or bool(args.per_shape)
+    extra_configs = args.full and not args.no_extra_configs
+    cpu = args.full and not args.no_cpu_baseline
 
     # Before torch is imported or any torch.cuda function runs (device_count() may already bring HSA up, and HSA reads this at
     # initialisation): the host driver only supports dmabuf IPC, without which RCCL fails with hipIpcGetMemHandle: invalid argument
@@ -160,6 +177,8 @@ def main():
     sync()
     dt = time.perf_counter() - t0
     note(f"timed {args.steps} steps in {dt:.3f}s")
+    if args.dump_outputs and rank == 0:
+        note(f"outputs of the last timed step: {dump_outputs(model, Path(args.dump_outputs), torch, np) / 2**20:.1f} MB in {args.dump_outputs}")
     comm = None
     if world > 1:
         comm = model._reducer.comm_summary(args.steps)
@@ -167,7 +186,7 @@ def main():
     # per-kernel HIP-event pass: serialized replay (single stream) of the same number of steps
     timer = None
     dt_serial = 0.0
-    if not args.no_kernel_timer:               # every rank replays (the steps contain collectives)
+    if kernel_timer:                           # every rank replays (the steps contain collectives)
         lane.stream = None
         if rank == 0:
             timer = ops.KernelTimer()
@@ -287,7 +306,7 @@ def main():
                              tflops=v["flops"] / (v["ms"] * 1e-3) / 1e12) for k, v in ps.items()]
                 rows.sort(key=lambda r: -r["ms_per_step"])
                 Path(args.per_shape).write_text(json.dumps(rows, indent=1))
-        if world == 1 and args.dtype == "f32" and not args.no_extra_configs:
+        if world == 1 and args.dtype == "f32" and extra_configs:
             # the opt-in fp32-from-bf16-planes weight gradient (csrc/conv_wgrad_x3.hip) on the same model, same process:
             # the headline above stays the exact-fp32 MFMA step
             ops.set_tuning("wgrad.f32_split", 1)
@@ -310,9 +329,9 @@ def main():
                                                     "exact-fp32 MFMA",
                                       "losses_finite": bool(all(np.isfinite(v) for k, v in model.losses().items() if k != "ssim"))}}
             note(f"f32x3 (opt-in): {dt3 / args.steps * 1e3:.2f} ms/step")
-        if not args.no_kernel_timer and world == 1:      # a single-GPU property; at N > 1 the other ranks would wait behind it
+        if args.full and not args.no_kernel_timer and world == 1:      # a single-GPU property; at N > 1 the other ranks would wait behind it
             out["north_star_block"] = north_star_block(torch, ops, dev)
-        if world == 1 and not args.no_extra_configs and (S, B, F, args.dtype) == (256, 8, 64, "f32"):
+        if world == 1 and extra_configs and (S, B, F, args.dtype) == (256, 8, 64, "f32"):
             # BASELINE configs[3] and [4] (per GPU) on the same clock as the headline: two more trainers in this process, one after the
             # other, each after the previous arena has been freed
             del inputs, noise_buf, keep_buf
@@ -321,12 +340,43 @@ def main():
             torch.cuda.empty_cache()
             out["extra_configs"] = [extra_config(torch, np, ops, dev, ShmGANwithSSpecSeg, F, *cfg, note)
                                     for cfg in ((512, 4, "BASELINE configs[3]"), (256, 32, "BASELINE configs[4], per GPU"))]
-        if not args.no_cpu_baseline and world == 1:         # reported at N=1 only: the other ranks would idle behind it
+        if cpu and world == 1:         # reported at N=1 only: the other ranks would idle behind it
             out["cpu_baseline"] = cpu_baseline(S, F, args.cpu_steps, note)
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
     return 0
+
+
+DUMP_MAX_ELEMS = 1 << 21          # --dump-outputs: a larger array is written as a sample of this many elements (8 MB in float32)
+
+
+def dump_outputs(model, out_dir, torch, np):
+    """--dump-outputs: what the last timed train_step left for its caller, one out_dir/<name>.npy each -- the named losses
+    (`loss_<name>`, float64), the generated image `gen_rgb` [B,S,S,3], the five cyclic images `cyc_rgb` [5B,S,S,3] (0, 45, 90, 135, ED),
+    the discriminator heads on the generated and on the target image (`realfake_gen_d1`, `label_gen_d1`, `realfake_target_d2`,
+    `label_target_d2`), both models' flat gradients (`grad_g`, `grad_d`) and their weights after the update (`weights_g`, `weights_d`),
+    in float32.  An array of more than DUMP_MAX_ELEMS elements is written flat, as its elements at DUMP_MAX_ELEMS positions drawn with
+    numpy's default_rng(0) from its size alone (sorted, repeats possible): the same arguments give the same positions in every run and
+    every build.  At most six arrays are that large, so the files stay below 64 MB in all.  Returns the bytes written."""
+    out_dir.mkdir(parents=True, exist_ok=True)
+    arrays = {f"loss_{k}": np.asarray(v, dtype=np.float64) for k, v in model.losses().items()}
+    tensors = {"gen_rgb": model.gen_rgb,
+               "cyc_rgb": torch.cat([model.cyc_gen0_rgb, model.cyc_gen45_rgb, model.cyc_gen90_rgb, model.cyc_gen135_rgb, model.cyc_genED_rgb]),
+               "realfake_gen_d1": model.RealFake_gen_D1, "label_gen_d1": model.label_gen_D1,
+               "realfake_target_d2": model.RealFake_target_D2, "label_target_d2": model.label_target_D2,
+               "grad_g": model.G.P.grad, "grad_d": model.D.P.grad, "weights_g": model.G.P.flat, "weights_d": model.D.P.flat}
+    for name, t in tensors.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).integers(0, t.numel(), DUMP_MAX_ELEMS))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        arrays[name] = t.float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, total
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", a)
+    return total
 
 
 def extra_config(torch, np, ops, dev, Model, F, S, B, tag, note, steps=10, warmup=3, replay=3):

@@ -16,7 +16,7 @@ ROOT = Path(__file__).resolve().parent.parent
 
 def test_bench_two_ranks_on_one_gpu_through_the_launcher():
     cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--same-device", "--backend", "gloo", "--steps", "1", "--warmup", "1",
-           "--no-cpu-baseline"]
+           "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=str(ROOT), capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -33,3 +33,28 @@ def test_bench_two_ranks_on_one_gpu_through_the_launcher():
     # the per-kernel replay ran on rank 0 under N = 2 as well (its durations are not asserted: under this host-staged rehearsal
     # backend an event bracket also absorbs collective stalls)
     assert j["roofline"]["kernel"] and j["roofline"]["launches"] > 0
+
+
+def test_bench_plain_run_reports_the_headline_and_dumps_outputs(tmp_path):
+    """A plain `bench.py --gpus 1` run times exactly --steps steps and prints the headline alone (the replay, extra configurations,
+    north-star block and CPU baseline are --full's); --dump-outputs writes the last timed step's outputs as float32 / float64 .npy."""
+    import numpy as np
+    out = tmp_path / "dump"
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--image-size", "64", "--filter-size", "16",
+           "--batch", "2", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, cwd=str(ROOT), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    j = json.loads(lines[0])
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["dtype"] == "f32" and j["higher_is_better"] is True
+    assert abs(j["value"] - 2 / (j["ms_per_step"] * 1e-3)) < 1e-2 * j["value"]
+    for k in ("roofline", "roofline_hbm", "extra", "extra_configs", "north_star_block", "cpu_baseline"):
+        assert k not in j, k
+    files = {p.stem: np.load(p) for p in out.glob("*.npy")}
+    assert {"gen_rgb", "cyc_rgb", "grad_g", "grad_d", "weights_g", "weights_d", "loss_total_Generator_loss"} <= set(files)
+    assert files["gen_rgb"].shape == (2, 64, 64, 3) and files["cyc_rgb"].shape == (10, 64, 64, 3)
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20
+    for name, a in files.items():
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), name
+    assert float(np.abs(files["grad_g"]).max()) > 0

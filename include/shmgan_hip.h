@@ -491,6 +491,27 @@ int shm_image_losses(const float* gen_rgb, const float* cyc_rgb, const float* cy
                      int flags_mask, float style_factor, double* loss, float* dgen_y, float* dcyc_y,
                      void* ws, size_t ws_bytes, int batch, int s, void* stream);
 
+/* ---- image-quality metrics of the reference's test mode (test.py:332-392, --calc_metrics True) ----------------------
+ * pred = gen_rgb (the G1 output in RGB, not clipped), target = the diffuse image, both [batch,s,s,3] fp32.  Per image b,
+ * out[b][0..4] (f64) = {mse, psnr, ssim, de76, de94}:
+ *   mse   mean over s*s*3 of (pred - target)^2                                (test.py:346-347, Keras MeanSquaredError)
+ *   psnr  -10 log10(mse), +inf when mse == 0                                 (test.py:338-342, tf.image.psnr, max_val 1)
+ *   ssim  tf.image.ssim(rescale_01(pred), rescale_01(target), 5): 11-tap gaussian (sigma 1.5), VALID, k1 0.01, k2 0.03,
+ *         mean over (s-10)^2 * 3; rescale_01 (utils.py:190) = (x - min) / (max - min) over the whole image, all three
+ *         channels, divide_no_nan (a constant image becomes 0)                (test.py:336)
+ *   de76  mean over pixels of |Lab(pred) - Lab(target)|_2                     (test.py:351-353, skimage deltaE_cie76)
+ *   de94  mean over pixels of sqrt(max(dL^2 + (dC/(1 + 0.045 C1))^2 + dH^2/(1 + 0.015 C1)^2, 0)), C = hypot(a, b),
+ *         dH^2 = 2 (C1 C2 - a1 a2 - b1 b2), C1 of pred (asymmetric)          (test.py:354, skimage deltaE_ciede94)
+ * Lab = tfio rgb_to_lab (D65, 2 degree observer): x > 0.04045 ? ((x + 0.055)/1.055)^2.4 : x/12.92; the sRGB -> XYZ matrix;
+ * / white (0.95047, 1, 1.08883); f = v > 0.008856 ? cbrt(v) : 7.787 v + 16/116; L = 116 fy - 16, a = 500 (fx - fy),
+ * b = 200 (fy - fz).
+ * Deterministic and batch-invariant: image b's numbers do not depend on batch or on the other images (per-block partials in
+ * workspace slots reduced in a fixed order, no atomics).  ws: shm_image_metrics_workspace() bytes, no initial contents.
+ * SHM_E_SHAPE for s < 11 or batch < 1, SHM_E_WORKSPACE for a short workspace, both before any launch. */
+size_t shm_image_metrics_workspace(int batch, int s);
+int shm_image_metrics(const float* pred, const float* target, double* out, void* ws, size_t ws_bytes, int batch, int s,
+                      void* stream);
+
 /* ---- SpecSeg mask network, inference only (SpecSeg.py:27-98; SpecSeg.predict at SHM.py:492) --
  * Its Conv2D(3x3, relu) layers are shm_conv2d_fwd with slope 0.  The rest: */
 /* dst[p, 0:nc] = src[p, c0:c0+nc], dst[p, nc:lddst] = 0 (the Y plane into a 16-float pitch). */

@@ -5,5 +5,6 @@ the C ABI of libshmgan_hip.so (include/shmgan_hip.h).  There is no CPU / PyTorch
 """
 from .trainer import LOSS_NAMES, KernelAbortError, ShmGANwithSSpecSeg  # noqa: F401
 from .model import Discriminator, Generator  # noqa: F401
+from .evaluate import test  # noqa: F401  (main.py --mode test; shmgan_amd.evaluate.test)
 
 __all__ = ["ShmGANwithSSpecSeg", "Generator", "Discriminator", "LOSS_NAMES"]

@@ -16,7 +16,7 @@ _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ["SHM_LIB_PATH"]) if os.environ.get("SHM_LIB_PATH") else _HERE / "libshmgan_hip.so"
 CSRC = _HERE / "csrc"
 HEADER = _HERE.parent / "include" / "shmgan_hip.h"
-SOURCES = ["conv_igemm.hip", "conv_wreg16.hip", "conv_pingpong.hip", "conv_wgrad.hip", "conv_wgrad_x3.hip", "conv_fwd_x3.hip", "conv_rgb.hip", "norm_elem.hip", "color.hip", "imgloss.hip", "specseg.hip", "data.hip"]
+SOURCES = ["conv_igemm.hip", "conv_wreg16.hip", "conv_pingpong.hip", "conv_wgrad.hip", "conv_wgrad_x3.hip", "conv_fwd_x3.hip", "conv_rgb.hip", "norm_elem.hip", "color.hip", "imgloss.hip", "metrics.hip", "specseg.hip", "data.hip"]
 F32, BF16 = 0, 1                 # SHM_F32 / SHM_BF16 of include/shmgan_hip.h
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-munsafe-fp-atomics",
                "-Wall", "-Wno-unused-function", "-Wno-unused-local-typedef"]
@@ -94,6 +94,8 @@ SIGNATURES = {
     "shm_dhead_losses": (I, [P, P, P, P, P, P, I, I, F, I, P]),
     "shm_image_losses_workspace": (Z, [I, I]),
     "shm_image_losses": (I, [P, P, P, P, P, P, I, F, P, P, P, P, Z, I, I, P]),
+    "shm_image_metrics_workspace": (Z, [I, I]),
+    "shm_image_metrics": (I, [P, P, P, P, Z, I, I, P]),
     "shm_pack_channels": (I, [P, I, I, I, P, I, Z, P]),
     "shm_bn_apply": (I, [P, I, P, P, P, P, F, P, I, Z, I, P]),
     "shm_maxpool2_fwd": (I, [P, I, P, I, I, I, I, I, P]),

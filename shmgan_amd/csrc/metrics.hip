@@ -1,0 +1,323 @@
+// Image-quality metrics of the reference's test mode (test.py:332-392, `--calc_metrics True`):
+// per image, from gen_rgb (the G1 output in RGB, NOT clipped) against the diffuse target, both [B,S,S,3] fp32.
+// Every sample is an independent B=1 reference call.
+//
+//   MSE    test.py:346-347 (Keras MeanSquaredError): mean over H*W*3 of (g-t)^2
+//   PSNR   test.py:338-342 (tf.image.psnr, max_val 1; convert_image_dtype f32->f32 is the identity): -10 log10(MSE), +inf at MSE 0
+//   SSIM   test.py:336 tf.image.ssim(rescale_01(g), rescale_01(t), 5): the loss's SSIM (11-tap gaussian, sigma 1.5, VALID,
+//          k1 0.01, k2 0.03, max_val 5, mean over HO*WO*3); rescale_01 (utils.py:190-195) takes min/max over the whole image,
+//          all three channels, with divide_no_nan (a constant image becomes 0)
+//   dE76   test.py:351-353 (tfio rgb_to_lab, skimage deltaE_cie76): mean over pixels of |Lab(g) - Lab(t)|_2
+//   dE94   test.py:354 (skimage deltaE_ciede94, kL = kC = kH = 1, k1 0.045, k2 0.015): mean over pixels of
+//          sqrt(max(dL^2 + (dC / (1 + k1 C1))^2 + dH^2 / (1 + k2 C1)^2, 0)), C = hypot(a, b), dH^2 = 2 (C1 C2 - a1 a2 - b1 b2),
+//          C1 of the GENERATED image (the metric is asymmetric)
+//
+// Lab: tfio's rgb_to_lab (D65, 2 degree observer), restated here because neither tfio nor skimage is part of this project: the
+// constants below are our restatement, like the rest of the oracle (oracle/, tests/test_eval_cpu.py).  Both branches of tfio's
+// tf.where are evaluated there, but a NaN of the branch not chosen never reaches the result: here they are selects as well.
+//
+// Reproducibility: results are bitwise reproducible and batch-invariant.  The grid per image depends on S only, every block writes
+// its partial into a workspace slot of its own, and the partials are reduced in a fixed slot order (no atomics anywhere).
+//   pixel pass  grid (NP, B): sums of (g-t)^2, dE76, dE94 (per-thread fp32, per-block f64) and min / max of g and of t
+//   ssim pass   grid (tiles, B, 3): reduces the min / max partials, stages the 26x26 halo of one 16x16 output tile in LDS, separable
+//               11-tap gaussian (as ssim_fwd_kernel of imgloss.hip, without the gradient maps), one f64 partial per block
+//   finalize    grid (B): out[b][5] = {mse, psnr, ssim, de76, de94} (f64)
+#include "common.h"
+
+#include <math.h>
+
+namespace {
+
+constexpr int MWIN = 11;
+constexpr int MTILE = 16;
+constexpr int MHALO = MTILE + MWIN - 1;     // 26
+constexpr int NT = 256;                     // threads per block, all three kernels
+
+// blocks per image of the pixel pass: a function of S alone (batch invariance)
+int pixel_blocks(int s) {
+    int n = shm_cdiv((long)s * s, 4 * NT);
+    return n > 256 ? 256 : n;
+}
+
+int ssim_tiles(int s) {
+    const int t = shm_cdiv(s - MWIN + 1, MTILE);
+    return t * t;
+}
+
+struct MetricWs {
+    size_t pix, mm, ssim, total;
+};
+
+size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+MetricWs plan_metric_ws(int batch, int s) {
+    MetricWs w;
+    size_t off = 0;
+    w.pix = off;  off = align256(off + (size_t)batch * pixel_blocks(s) * 3 * sizeof(double));
+    w.mm = off;   off = align256(off + (size_t)batch * pixel_blocks(s) * 4 * sizeof(float));
+    w.ssim = off; off = align256(off + (size_t)batch * 3 * ssim_tiles(s) * sizeof(double));
+    w.total = off;
+    return w;
+}
+
+// sum over the block's 256 threads in a fixed order (wave shuffles, then the four wave sums in wave order)
+__device__ __forceinline__ double block_sum_fixed(double v) {
+    __shared__ double part[NT / 64];
+    v = shm_wave_sum(v);
+    __syncthreads();                          // the previous call's readers are done
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return part[0] + part[1] + part[2] + part[3];
+}
+
+// ---- tfio rgb_to_lab (D65, 2 degree observer), restated
+__device__ __forceinline__ float srgb_linear(float x) {
+    const float hi = powf((x + 0.055f) / 1.055f, 2.4f);     // NaN for x < -0.055: never selected
+    const float lo = x / 12.92f;
+    return x > 0.04045f ? hi : lo;
+}
+
+__device__ __forceinline__ float lab_f(float v) {
+    const float hi = cbrtf(v), lo = 7.787f * v + 16.0f / 116.0f;
+    return v > 0.008856f ? hi : lo;
+}
+
+__device__ __forceinline__ void rgb_to_lab(float r, float g, float b, float& L, float& A, float& Bc) {
+    r = srgb_linear(r);
+    g = srgb_linear(g);
+    b = srgb_linear(b);
+    const float x = (0.412453f * r + 0.357580f * g + 0.180423f * b) / 0.95047f;
+    const float y = (0.212671f * r + 0.715160f * g + 0.072169f * b) / 1.0f;
+    const float z = (0.019334f * r + 0.119193f * g + 0.950227f * b) / 1.08883f;
+    const float fx = lab_f(x), fy = lab_f(y), fz = lab_f(z);
+    L = 116.0f * fy - 16.0f;
+    A = 500.0f * (fx - fy);
+    Bc = 200.0f * (fy - fz);
+}
+
+// ---------------------------------------------------------------------------------- pixel pass
+// grid (NP, B); pix[b][blk][3] = partial sums of (g-t)^2, dE76, dE94; mm[b][blk][4] = min g, max g, min t, max t
+__global__ __launch_bounds__(NT) void metrics_pixel_kernel(const float* __restrict__ g, const float* __restrict__ t, double* __restrict__ pix,
+                                                          float* __restrict__ mm, int s) {
+    const int b = blockIdx.y, np = gridDim.x;
+    const size_t npix = (size_t)s * s;
+    const float* gi = g + (size_t)b * npix * 3;
+    const float* ti = t + (size_t)b * npix * 3;
+    float sq = 0.f, e76 = 0.f, e94 = 0.f;
+    float gmn = INFINITY, gmx = -INFINITY, tmn = INFINITY, tmx = -INFINITY;
+    for (size_t p = (size_t)blockIdx.x * NT + threadIdx.x; p < npix; p += (size_t)np * NT) {
+        const float g0 = gi[p * 3], g1 = gi[p * 3 + 1], g2 = gi[p * 3 + 2];
+        const float t0 = ti[p * 3], t1 = ti[p * 3 + 1], t2 = ti[p * 3 + 2];
+        const float d0 = g0 - t0, d1 = g1 - t1, d2 = g2 - t2;
+        sq += d0 * d0 + d1 * d1 + d2 * d2;
+        gmn = fminf(gmn, fminf(g0, fminf(g1, g2)));
+        gmx = fmaxf(gmx, fmaxf(g0, fmaxf(g1, g2)));
+        tmn = fminf(tmn, fminf(t0, fminf(t1, t2)));
+        tmx = fmaxf(tmx, fmaxf(t0, fmaxf(t1, t2)));
+        float L1, a1, b1, L2, a2, b2;
+        rgb_to_lab(g0, g1, g2, L1, a1, b1);
+        rgb_to_lab(t0, t1, t2, L2, a2, b2);
+        const float dL = L1 - L2, da = a1 - a2, db = b1 - b2;
+        e76 += sqrtf(dL * dL + da * da + db * db);
+        // skimage's dH^2 = 2 (C1 C2 - a1 a2 - b1 b2) cancels for near-identical colours: evaluated in f64 from the fp32 Lab values
+        const double A1 = a1, B1 = b1, A2 = a2, B2 = b2;
+        const double C1 = sqrt(A1 * A1 + B1 * B1), C2 = sqrt(A2 * A2 + B2 * B2);
+        const double dH2 = 2.0 * (C1 * C2 - A1 * A2 - B1 * B2);
+        const double sc = 1.0 + 0.045 * C1, sh = 1.0 + 0.015 * C1, dC = C1 - C2;
+        const double e2 = (double)dL * dL + (dC / sc) * (dC / sc) + dH2 / (sh * sh);
+        e94 += (float)sqrt(e2 > 0.0 ? e2 : 0.0);
+    }
+    const double s0 = block_sum_fixed((double)sq);
+    const double s1 = block_sum_fixed((double)e76);
+    const double s2 = block_sum_fixed((double)e94);
+    gmn = shm_wave_min(gmn);
+    gmx = shm_wave_max(gmx);
+    tmn = shm_wave_min(tmn);
+    tmx = shm_wave_max(tmx);
+    __shared__ float wmm[NT / 64][4];
+    if ((threadIdx.x & 63) == 0) {
+        wmm[threadIdx.x >> 6][0] = gmn;
+        wmm[threadIdx.x >> 6][1] = gmx;
+        wmm[threadIdx.x >> 6][2] = tmn;
+        wmm[threadIdx.x >> 6][3] = tmx;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const size_t slot = (size_t)b * np + blockIdx.x;
+        pix[slot * 3] = s0;
+        pix[slot * 3 + 1] = s1;
+        pix[slot * 3 + 2] = s2;
+        float r[4] = {wmm[0][0], wmm[0][1], wmm[0][2], wmm[0][3]};
+        for (int w = 1; w < NT / 64; ++w) {
+            r[0] = fminf(r[0], wmm[w][0]);
+            r[1] = fmaxf(r[1], wmm[w][1]);
+            r[2] = fminf(r[2], wmm[w][2]);
+            r[3] = fmaxf(r[3], wmm[w][3]);
+        }
+        for (int k = 0; k < 4; ++k) mm[slot * 4 + k] = r[k];
+    }
+}
+
+// ----------------------------------------------------------------------------------- ssim pass
+// 11 taps, sigma 1.5, normalised: the same taps and arithmetic as gauss1d of imgloss.hip
+__device__ __forceinline__ void metrics_gauss1d(float* w) {
+    float s = 0.f;
+    for (int i = 0; i < MWIN; ++i) {
+        float c = (float)i - 5.0f;
+        w[i] = expf(-0.5f * c * c / 2.25f);
+        s += w[i];
+    }
+    for (int i = 0; i < MWIN; ++i) w[i] /= s;
+}
+
+// grid (tiles, B, 3); ssim[b][c][tile] = sum over the tile's valid outputs of luminance * contrast-structure
+__global__ __launch_bounds__(NT) void metrics_ssim_kernel(const float* __restrict__ g, const float* __restrict__ t, const float* __restrict__ mm,
+                                                         double* __restrict__ ssim, int s, int np) {
+    __shared__ float xs[MHALO][MHALO + 1], ys[MHALO][MHALO + 1];
+    __shared__ float hx[MHALO][MTILE + 1], hy[MHALO][MTILE + 1], hxy[MHALO][MTILE + 1], hsq[MHALO][MTILE + 1];
+    __shared__ float w1[MWIN];
+    __shared__ float wmm[NT / 64][4];
+    const int HO = s - MWIN + 1;
+    const int tiles_x = (HO + MTILE - 1) / MTILE, ntiles = tiles_x * tiles_x;
+    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x % tiles_x;
+    const int b = blockIdx.y, c = blockIdx.z;
+    const size_t npix = (size_t)s * s;
+    // rescale_01's min / max of the whole image (min / max are exact: any order gives the same values)
+    float r0 = INFINITY, r1 = -INFINITY, r2 = INFINITY, r3 = -INFINITY;
+    for (int i = threadIdx.x; i < np; i += NT) {
+        const float* m = mm + ((size_t)b * np + i) * 4;
+        r0 = fminf(r0, m[0]);
+        r1 = fmaxf(r1, m[1]);
+        r2 = fminf(r2, m[2]);
+        r3 = fmaxf(r3, m[3]);
+    }
+    r0 = shm_wave_min(r0);
+    r1 = shm_wave_max(r1);
+    r2 = shm_wave_min(r2);
+    r3 = shm_wave_max(r3);
+    if ((threadIdx.x & 63) == 0) {
+        wmm[threadIdx.x >> 6][0] = r0;
+        wmm[threadIdx.x >> 6][1] = r1;
+        wmm[threadIdx.x >> 6][2] = r2;
+        wmm[threadIdx.x >> 6][3] = r3;
+    }
+    if (threadIdx.x == 0) metrics_gauss1d(w1);
+    __syncthreads();
+    float xmn = wmm[0][0], xmx = wmm[0][1], ymn = wmm[0][2], ymx = wmm[0][3];
+    for (int w = 1; w < NT / 64; ++w) {
+        xmn = fminf(xmn, wmm[w][0]);
+        xmx = fmaxf(xmx, wmm[w][1]);
+        ymn = fminf(ymn, wmm[w][2]);
+        ymx = fmaxf(ymx, wmm[w][3]);
+    }
+    const float xr = xmx - xmn, yr = ymx - ymn;       // divide_no_nan below: a zero range maps the image to 0
+    const int oy0 = ty * MTILE, ox0 = tx * MTILE;
+    const float* gi = g + (size_t)b * npix * 3 + c;
+    const float* ti = t + (size_t)b * npix * 3 + c;
+    for (int i = threadIdx.x; i < MHALO * MHALO; i += NT) {
+        const int r = i / MHALO, cc = i % MHALO;
+        const int yy = oy0 + r, xx = ox0 + cc;
+        float xv = 0.f, yv = 0.f;
+        if (yy < s && xx < s) {
+            const size_t p = (size_t)yy * s + xx;
+            xv = xr != 0.f ? (gi[p * 3] - xmn) / xr : 0.f;
+            yv = yr != 0.f ? (ti[p * 3] - ymn) / yr : 0.f;
+        }
+        xs[r][cc] = xv;
+        ys[r][cc] = yv;
+    }
+    __syncthreads();
+    // separable window: row sums of the four moments per (halo row, output column), then eleven taps down the column
+    for (int i = threadIdx.x; i < MHALO * MTILE; i += NT) {
+        const int r = i / MTILE, cx = i % MTILE;
+        float rx = 0.f, ry = 0.f, rxy = 0.f, rsq = 0.f;
+        for (int j = 0; j < MWIN; ++j) {
+            const float xv = xs[r][cx + j], yv = ys[r][cx + j], w = w1[j];
+            rx += w * xv;
+            ry += w * yv;
+            rxy += w * xv * yv;
+            rsq += w * (xv * xv + yv * yv);
+        }
+        hx[r][cx] = rx;
+        hy[r][cx] = ry;
+        hxy[r][cx] = rxy;
+        hsq[r][cx] = rsq;
+    }
+    __syncthreads();
+    const int ly = threadIdx.x / MTILE, lx = threadIdx.x % MTILE;
+    const int oy = oy0 + ly, ox = ox0 + lx;
+    double v = 0.0;
+    if (oy < HO && ox < HO) {
+        float mx_ = 0.f, my_ = 0.f, exy = 0.f, esq = 0.f;
+        for (int i = 0; i < MWIN; ++i) {
+            mx_ += w1[i] * hx[ly + i][lx];
+            my_ += w1[i] * hy[ly + i][lx];
+            exy += w1[i] * hxy[ly + i][lx];
+            esq += w1[i] * hsq[ly + i][lx];
+        }
+        const float c1 = 0.0025f, c2 = 0.0225f;      // (0.01 * 5)^2, (0.03 * 5)^2: max_val = 5 (test.py:336)
+        const float A1 = 2.f * mx_ * my_ + c1, B1 = mx_ * mx_ + my_ * my_ + c1;
+        const float A2 = 2.f * exy - 2.f * mx_ * my_ + c2, B2 = esq - mx_ * mx_ - my_ * my_ + c2;
+        v = (double)((A1 / B1) * (A2 / B2));
+    }
+    v = block_sum_fixed(v);
+    if (threadIdx.x == 0) ssim[((size_t)b * 3 + c) * ntiles + blockIdx.x] = v;
+}
+
+// ------------------------------------------------------------------------------------ finalize
+// grid (B): every thread sums a fixed stride of slots in slot order, then the block sums in thread order
+__global__ __launch_bounds__(NT) void metrics_finalize_kernel(const double* __restrict__ pix, const double* __restrict__ ssim, double* __restrict__ out,
+                                                             int s, int np, int ntiles) {
+    const int b = blockIdx.x;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    for (int i = threadIdx.x; i < np; i += NT) {
+        const double* q = pix + ((size_t)b * np + i) * 3;
+        a0 += q[0];
+        a1 += q[1];
+        a2 += q[2];
+    }
+    for (int i = threadIdx.x; i < 3 * ntiles; i += NT) a3 += ssim[(size_t)b * 3 * ntiles + i];
+    a0 = block_sum_fixed(a0);
+    a1 = block_sum_fixed(a1);
+    a2 = block_sum_fixed(a2);
+    a3 = block_sum_fixed(a3);
+    if (threadIdx.x == 0) {
+        const double npix = (double)s * s, ho = (double)(s - MWIN + 1);
+        const double mse = a0 / (3.0 * npix);
+        double* o = out + (size_t)b * 5;
+        o[0] = mse;
+        o[1] = mse > 0.0 ? -10.0 * log10(mse) : INFINITY;
+        o[2] = a3 / (3.0 * ho * ho);
+        o[3] = a1 / npix;
+        o[4] = a2 / npix;
+    }
+}
+
+}  // namespace
+
+extern "C" size_t shm_image_metrics_workspace(int batch, int s) {
+    if (s < MWIN || batch < 1) return 0;
+    return plan_metric_ws(batch, s).total;
+}
+
+extern "C" int shm_image_metrics(const float* pred, const float* target, double* out, void* ws, size_t ws_bytes, int batch, int s,
+                                 void* stream) {
+    SHM_REQUIRE(s >= MWIN, SHM_E_SHAPE, "shm_image_metrics: image size %d < 11 (ssim window)", s);
+    SHM_REQUIRE(batch >= 1 && batch <= 65535, SHM_E_SHAPE, "shm_image_metrics: bad batch %d", batch);
+    SHM_REQUIRE(pred && target && out, SHM_E_SHAPE, "shm_image_metrics: null pointer");
+    const MetricWs w = plan_metric_ws(batch, s);
+    SHM_REQUIRE(ws && ws_bytes >= w.total, SHM_E_WORKSPACE, "shm_image_metrics: workspace %zu < %zu bytes", ws_bytes, w.total);
+    hipStream_t st = (hipStream_t)stream;
+    char* base = (char*)ws;
+    double* pix = (double*)(base + w.pix);
+    float* mm = (float*)(base + w.mm);
+    double* ssim = (double*)(base + w.ssim);
+    const int np = pixel_blocks(s), nt = ssim_tiles(s);
+    hipLaunchKernelGGL(metrics_pixel_kernel, dim3(np, batch), dim3(NT), 0, st, pred, target, pix, mm, s);
+    SHM_LAUNCH_CHECK("shm_image_metrics(pixel)");
+    hipLaunchKernelGGL(metrics_ssim_kernel, dim3(nt, batch, 3), dim3(NT), 0, st, pred, target, mm, ssim, s, np);
+    SHM_LAUNCH_CHECK("shm_image_metrics(ssim)");
+    hipLaunchKernelGGL(metrics_finalize_kernel, dim3(batch), dim3(NT), 0, st, pix, ssim, out, s, np, nt);
+    SHM_LAUNCH_CHECK("shm_image_metrics(finalize)");
+    return SHM_OK;
+}

@@ -152,3 +152,79 @@ def datasetLoad(trainer, subdirs=PSD_SUBDIRS, flip_ud=True):
     # per-rank length: batches_per_epoch = length // batch_size (SHM.py:957) then counts this rank's batches
     trainer.length_dataset, trainer.loadedDataset = ds.n // ds.world, ds
     return trainer.length_dataset, ds
+
+
+def eval_file_lists(test_dir, diffuse_dir=None):
+    """File lists of the evaluation loader: the sorted flat `test_dir` and, when given, the sorted flat `diffuse_dir`
+    (None otherwise), paired by position.  The reference zips the two datasets (test.py:130), and tf.data's zip stops at the
+    shorter one without a word; a count mismatch here raises instead, since it means the pairs are not what was meant."""
+    test = list_images(test_dir)
+    if not diffuse_dir:
+        return test, None
+    diffuse = list_images(diffuse_dir)
+    if len(diffuse) != len(test):
+        raise ValueError(f"{test_dir} holds {len(test)} images and {diffuse_dir} {len(diffuse)}: the evaluation pairs them by "
+                         f"sorted position and needs the same number in both")
+    return test, diffuse
+
+
+class EvalDataset:
+    """The test-mode loader (test.py:80-137): batches of ([b,S,S,3] test images, [b,S,S,3] diffuse images or None), float32
+    device tensors in [0,1], b = batch_size except for a partial last batch -- every image is yielded once, in sorted order.
+
+    Same decode and resize as PolarDataset (PIL, then shm_resize_bilinear_u8 scaled by 1/255) but NO flip: test.py:93,118 map
+    only x / 255.  Evaluation is not sharded: rank 0 of a world of 1, whatever torch.distributed says.  The next batch is decoded
+    on a worker thread while the current one is consumed; uploads and resizes run on the consumer's current stream."""
+
+    def __init__(self, test_dir, image_size, batch_size=1, diffuse_dir=None, device=None):
+        if batch_size < 1:
+            raise ValueError(f"batch_size {batch_size} < 1")
+        self.S, self.B = int(image_size), int(batch_size)
+        self.test_files, self.diffuse_files = eval_file_lists(test_dir, diffuse_dir)
+        self.n = len(self.test_files)
+        self.rank, self.world = 0, 1
+        self._dev = device
+        self._pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="shm-eval-loader")
+
+    @property
+    def dev(self):
+        if self._dev is None:
+            self._dev = torch.device("cuda", torch.cuda.current_device())
+        return torch.device(self._dev)
+
+    def __len__(self):
+        return (self.n + self.B - 1) // self.B
+
+    def batch_range(self, index):
+        """Dataset positions [lo, hi) of batch `index`."""
+        lo = index * self.B
+        return lo, min(lo + self.B, self.n)
+
+    @staticmethod
+    def _decode(path):
+        from PIL import Image
+        with Image.open(path) as im:
+            return np.array(im.convert("RGB"), dtype=np.uint8)
+
+    def _decode_batch(self, index):
+        lo, hi = self.batch_range(index)
+        test = [self._decode(p) for p in self.test_files[lo:hi]]
+        diffuse = None if self.diffuse_files is None else [self._decode(p) for p in self.diffuse_files[lo:hi]]
+        return test, diffuse
+
+    def _upload(self, decoded):
+        out = torch.empty((len(decoded), self.S, self.S, 3), dtype=torch.float32, device=self.dev)
+        for b, a in enumerate(decoded):
+            ops.resize_bilinear_u8(torch.from_numpy(a).to(self.dev), out[b], 1.0 / 255.0, False)
+        return out
+
+    def batch(self, index, decoded=None):
+        test, diffuse = decoded if decoded is not None else self._decode_batch(index)
+        return self._upload(test), (None if diffuse is None else self._upload(diffuse))
+
+    def __iter__(self):
+        nxt = self._pool.submit(self._decode_batch, 0) if len(self) else None
+        for i in range(len(self)):
+            cur = nxt.result()
+            nxt = self._pool.submit(self._decode_batch, i + 1) if i + 1 < len(self) else None
+            yield self.batch(i, cur)

@@ -549,6 +549,40 @@ def image_losses(gen_rgb, cyc_rgb, cyc_y, cbcr, orig_ptrs, ds_ptrs, flags_mask, 
                                  ws.numel() * ws.element_size(), batch, s, _stream()), "shm_image_losses")
 
 
+# ---- image-quality metrics of the reference's test mode (test.py:332-392) --------------------------------------
+METRIC_NAMES = ("mse", "psnr", "ssim", "de76", "de94")          # the columns of image_metrics' result
+_METRIC_ARENAS = {}
+
+
+def image_metrics_workspace(batch, s):
+    return int(lib().shm_image_metrics_workspace(batch, s))
+
+
+def image_metrics(pred, target, out=None, arena=None):
+    """Per-image {mse, psnr, ssim, de76, de94} of pred (gen_rgb, not clipped) against target, both float32 [B,S,S,3] device
+    tensors (shm_image_metrics, include/shmgan_hip.h, states the definitions).  Returns `out`, a float64 [B,5] device tensor
+    (allocated when not given), filled asynchronously on the current stream.  The workspace comes from `arena` (default: one
+    arena per device held by this module): calls that share an arena must be ordered on one stream."""
+    if pred.dtype != torch.float32 or target.dtype != torch.float32:
+        raise TypeError(f"image_metrics takes float32 images, got {pred.dtype} / {target.dtype}")
+    if pred.dim() != 4 or pred.shape[-1] != 3 or pred.shape[1] != pred.shape[2] or tuple(target.shape) != tuple(pred.shape):
+        raise ValueError(f"image_metrics takes two [B,S,S,3] images of one shape, got {tuple(pred.shape)} / {tuple(target.shape)}")
+    if not (pred.is_contiguous() and target.is_contiguous()):
+        raise ValueError("image_metrics takes contiguous NHWC images")
+    B, S = int(pred.shape[0]), int(pred.shape[1])
+    if out is None:
+        out = torch.empty((B, 5), dtype=torch.float64, device=pred.device)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (B, 5) or not out.is_contiguous():
+        raise ValueError(f"image_metrics: out must be a contiguous float64 [{B},5] tensor")
+    if arena is None:
+        from .model import Arena
+        arena = _METRIC_ARENAS.setdefault(pred.device, Arena(pred.device))
+    n = image_metrics_workspace(B, S)
+    ws = arena.get("metrics/ws", (max(n, 1),), torch.uint8)
+    check(lib().shm_image_metrics(_p(pred), _p(target), _p(out), _p(ws), ws.numel(), B, S, _stream()), "shm_image_metrics")
+    return out
+
+
 def adam_clip(w, m, v, g, n, alpha, beta1, beta2, eps, gscale):
     _timed_bytes("shm_adam_clip", 7.0 * 4 * n, lambda: check(          # read w, m, v, g; write w, m, v
         lib().shm_adam_clip(_p(w), _p(m), _p(v), _p(g), n, alpha, beta1, beta2, eps, gscale, _stream()), "shm_adam_clip"))

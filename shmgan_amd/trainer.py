@@ -51,7 +51,7 @@ class _Optimizer:
 _DEFAULTS = dict(image_size=128, batch_size=1, filter_size=64, g_lr=0.00002, d_lr=0.00002, beta1=0.5, beta2=0.99,
                  c_dim=5, num_epochs=200, num_iteration_decay=100000, n_critic=5, d_repeat_num=6, mode="train",
                  data_dir="", model_save_dir="./models", checkpoint_save_dir="./checkpoints", result_dir="./results",
-                 log_dir="./logs/train", log_step=1, checkpoint_save_step=10)
+                 log_dir="./logs/train", log_step=1, checkpoint_save_step=10, calc_metrics=False, test_dir="", diffuse_dir="")
 
 LOSS_NAMES = ["total_Generator_loss", "total_Discriminator_loss", "total_Classification_loss", "G_gan_loss",
               "G_clsf_loss", "D1_RealFake_loss", "D3_RealFake_cyc", "D2_RealFake_target", "D4_RealFake_cyc",
@@ -585,10 +585,7 @@ class ShmGANwithSSpecSeg:
         if not rank0:
             print_fn = lambda *a, **k: None
         if rank0:
-            os.makedirs(self.log_dir, exist_ok=True)
-            for mdl, fn in ((self.G, "Generator_summary.txt"), (self.D, "Discriminator_summary.txt"), (self.SpecSeg, "SpecSeg_summary.txt")):
-                with open(os.path.join(self.log_dir, fn), "w") as f:           # SHM.py:914-919, 933-935
-                    mdl.summary(print_fn=lambda x: f.write(x + "\n"))
+            self._write_summaries()                                            # SHM.py:914-919, 933-935
             os.makedirs(self.checkpoint_save_dir, exist_ok=True)
         self._barrier()
         latest = self._restore_latest()                                        # SHM.py:949-951 (delete_old_checkpoints is False)
@@ -630,6 +627,14 @@ class ShmGANwithSSpecSeg:
                 break
         print_fn("Saving checkpoint for epoch {} at {}".format(self.epoch + 1, self._save_checkpoint()))   # SHM.py:1133
         return self.batch_step
+
+    def _write_summaries(self):
+        """Generator / Discriminator / SpecSeg summaries into `log_dir` (SHM.py:914-919, 933-935; test.py:142-158)."""
+        import os
+        os.makedirs(self.log_dir, exist_ok=True)
+        for mdl, fn in ((self.G, "Generator_summary.txt"), (self.D, "Discriminator_summary.txt"), (self.SpecSeg, "SpecSeg_summary.txt")):
+            with open(os.path.join(self.log_dir, fn), "w") as f:
+                mdl.summary(print_fn=lambda x: f.write(x + "\n"))
 
     def _checkpoints(self):
         import glob
@@ -760,6 +765,21 @@ class ShmGANwithSSpecSeg:
         outs = [cyc_rgb[k * B:(k + 1) * B] for k in range(5)]
         (self.cyc_gen0_rgb, self.cyc_gen45_rgb, self.cyc_gen90_rgb, self.cyc_gen135_rgb, self.cyc_genED_rgb) = outs
         return gen_rgb, outs
+
+    def evaluate(self, rgb, diffuse=None):
+        """One batch of the reference's test mode (test.py:218-392): `infer(rgb)` and, when the diffuse targets are given
+        ([B,S,S,3] in [0,1]), their image-quality metrics against gen_rgb (ops.image_metrics, on the library's kernels).
+        Returns (gen_rgb, [5 x cyc_rgb], metrics): metrics is a float64 [B,5] device tensor {mse, psnr, ssim, de76, de94} per
+        image (ops.METRIC_NAMES), or None.  Asynchronous like infer; gen_rgb and the metrics live until the next call."""
+        gen_rgb, cyc = self.infer(rgb)
+        metrics = None
+        if diffuse is not None:
+            t = self._dev(diffuse)
+            if tuple(t.shape) != tuple(gen_rgb.shape):
+                raise ValueError(f"diffuse images {tuple(t.shape)} do not match the generated ones {tuple(gen_rgb.shape)}")
+            B = gen_rgb.shape[0]
+            metrics = ops.image_metrics(gen_rgb, t, out=self.arena.get("eval/metrics", (B, 5), torch.float64), arena=self.arena)
+        return gen_rgb, cyc, metrics
 
     # ------------------------------------------------------------------ weights interchange (SURVEY N3)
     def save_npz(self, path):

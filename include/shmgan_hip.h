@@ -559,6 +559,38 @@ int shm_sum_groups(const void* src, void* dst, int nimg, size_t per, int nb, int
 int shm_resize_bilinear_u8(const unsigned char* src, int hin, int win, int c, float* dst, int ho, int wo,
                            float scale, int flip_ud, void* stream);
 
+/* ---- test-mode image export (the images test.py:305-317 logs; test_plot at test.py:410-425) ----------------------------
+ * Batched, ragged float32 -> uint8 export.  One job = one plane of one image: source src[j], float32 [s,s,c] NHWC with channel
+ * pitch ld >= c, c in {1,3}; destination [ho,wo,c] uint8, tightly packed, at byte offset dst_off (a multiple of 4) of dst.
+ * desc holds SHM_EXPORT_DESC size_t per job: {s, c, ld, ho, wo, mode, k, dst_off}.  src and desc are host arrays of up to
+ * SHM_EXPORT_MAX_JOBS jobs, read during the call.  Per output byte of channel ch at (oy, ox):
+ *   v  (ho,wo) = (s,s): the source value at (oy, ox, ch).  Otherwise tf.image.resize(bilinear, half-pixel centres, no
+ *      antialias), the mapping of shm_resize_bilinear_u8, in fp32 on the raw values: fy = (oy + 0.5) s/ho - 0.5,
+ *      y0 = max(floor(fy), 0), y1 = min(ceil(fy), s-1), ly = fy - floor(fy) (x alike); top = tl + (tr - tl) lx,
+ *      bot = bl + (br - bl) lx, v = top + (bot - top) ly
+ *   t  SHM_EXPORT_RESCALE: (v - min) / (max - min), min and max over the whole s*s*c source plane, 0 when max == min
+ *      (rescale_01, utils.py:190-195, divide_no_nan);  SHM_EXPORT_SCALE: v * mul[k] (mul: device float[nmul]; with mul the
+ *      running mean of shm_running_scale_mean this is gen_rgb_output / 255 of test.py:246-250);  SHM_EXPORT_CLIP: v
+ *   q  rint(clamp(t, 0, 1) * 255) in fp32, round half to even; a NaN t gives 0
+ * At most two launches: a min / max pass (only if some job is RESCALE) and the export pass.  A job's bytes depend on that job
+ * alone (not on the other jobs, their order or the launch geometry).  ws: shm_export_u8_workspace(njobs) bytes, 4-byte
+ * aligned, no initial contents; dst 4-byte aligned.  SHM_E_SHAPE for njobs outside [1, SHM_EXPORT_MAX_JOBS], a null pointer,
+ * c, ld, a size outside [1, 32768], an unknown mode, k >= nmul, a destination outside [0, dst_bytes); SHM_E_WORKSPACE for a
+ * short workspace; all before any launch. */
+#define SHM_EXPORT_RESCALE 0
+#define SHM_EXPORT_SCALE 1
+#define SHM_EXPORT_CLIP 2
+#define SHM_EXPORT_DESC 8
+#define SHM_EXPORT_MAX_JOBS 64
+size_t shm_export_u8_workspace(int njobs);
+int shm_export_u8(const float* const* src, const size_t* desc, int njobs, const float* mul, int nmul, unsigned char* dst,
+                  size_t dst_bytes, void* ws, size_t ws_bytes, void* stream);
+/* The reference's running mean of the standardisation scales (test.py:77, 218, 246: stddev_arr is reset once per test run and
+ * grows by one entry per image; each image uses the mean of every scale so far, its own included).  acc = caller-owned device
+ * f64 {sum, count} ({0, 0} at the start of a run).  In image order, one thread: sum += scale[b], count += 1,
+ * mul[b] = (float)(sum / count); acc is updated.  One block, deterministic. */
+int shm_running_scale_mean(const float* scale, int batch, double* acc, float* mul, void* stream);
+
 /* ---- optimizer (SHM.py:169-175, 859-872) ------------------------------------------
  * tf.clip_by_value(g,-1,1) + Keras adam_v2.Adam: m += (g-m)(1-b1); v += (g^2-v)(1-b2);
  * w -= alpha * m / (sqrt(v) + eps); alpha = lr_t*sqrt(1-b2^t)/(1-b1^t) computed by the caller.

@@ -173,7 +173,8 @@ class EvalDataset:
     device tensors in [0,1], b = batch_size except for a partial last batch -- every image is yielded once, in sorted order.
 
     Same decode and resize as PolarDataset (PIL, then shm_resize_bilinear_u8 scaled by 1/255) but NO flip: test.py:93,118 map
-    only x / 255.  Evaluation is not sharded: rank 0 of a world of 1, whatever torch.distributed says.  The next batch is decoded
+    only x / 255.  `sources(index)` gives each test image's path and (h, w) before the resize (the image export writes at that
+    size).  Evaluation is not sharded: rank 0 of a world of 1, whatever torch.distributed says.  The next batch is decoded
     on a worker thread while the current one is consumed; uploads and resizes run on the consumer's current stream."""
 
     def __init__(self, test_dir, image_size, batch_size=1, diffuse_dir=None, device=None):
@@ -185,6 +186,7 @@ class EvalDataset:
         self.rank, self.world = 0, 1
         self._dev = device
         self._pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="shm-eval-loader")
+        self._sizes = {}             # dataset position -> (h, w) of the decoded test image, filled by the decode
 
     @property
     def dev(self):
@@ -209,6 +211,8 @@ class EvalDataset:
     def _decode_batch(self, index):
         lo, hi = self.batch_range(index)
         test = [self._decode(p) for p in self.test_files[lo:hi]]
+        for i, a in enumerate(test):
+            self._sizes[lo + i] = a.shape[:2]
         diffuse = None if self.diffuse_files is None else [self._decode(p) for p in self.diffuse_files[lo:hi]]
         return test, diffuse
 
@@ -216,6 +220,19 @@ class EvalDataset:
         out = torch.empty((len(decoded), self.S, self.S, 3), dtype=torch.float32, device=self.dev)
         for b, a in enumerate(decoded):
             ops.resize_bilinear_u8(torch.from_numpy(a).to(self.dev), out[b], 1.0 / 255.0, False)
+        return out
+
+    def sources(self, index):
+        """(path, (h, w)) of every test image of batch `index`: the file and its size before the resize (the image export
+        writes at that size).  The sizes come from the decode, so this is free once the batch has been loaded."""
+        lo, hi = self.batch_range(index)
+        out = []
+        for i in range(lo, hi):
+            if i not in self._sizes:
+                from PIL import Image
+                with Image.open(self.test_files[i]) as im:
+                    self._sizes[i] = (im.size[1], im.size[0])
+            out.append((self.test_files[i], tuple(int(v) for v in self._sizes[i])))
         return out
 
     def batch(self, index, decoded=None):

@@ -583,6 +583,92 @@ def image_metrics(pred, target, out=None, arena=None):
     return out
 
 
+# ---- test-mode image export (the images test.py:305-317 logs) ----------------------------------------------------------
+EXPORT_MODES = {"rescale": 0, "scale": 1, "clip": 2}     # SHM_EXPORT_RESCALE / _SCALE / _CLIP
+EXPORT_DESC, EXPORT_MAX_JOBS = 8, 64                      # SHM_EXPORT_DESC, SHM_EXPORT_MAX_JOBS
+EXPORT_ALIGN = 16                                         # start of every job's bytes in export_u8's output
+
+
+def export_workspace(njobs):
+    return int(lib().shm_export_u8_workspace(njobs))
+
+
+def export_layout(sizes, channels):
+    """Byte offsets of the jobs in export_u8's output and its total size: job j holds ho*wo*c bytes ([ho,wo,c] uint8, tightly
+    packed) from an offset that is a multiple of EXPORT_ALIGN."""
+    offs, n = [], 0
+    for (ho, wo), c in zip(sizes, channels):
+        offs.append(n)
+        n += (int(ho) * int(wo) * int(c) + EXPORT_ALIGN - 1) // EXPORT_ALIGN * EXPORT_ALIGN
+    return offs, n
+
+
+def export_u8(planes, sizes, modes, mul=None, out=None, arena=None):
+    """float32 planes -> uint8 images (shm_export_u8, include/shmgan_hip.h, states the definitions).  planes: [S,S,C] device
+    tensors, C in {1,3}, channels innermost with unit stride and a pixel pitch ld >= C (a channel slice of a wider NHWC tensor
+    is fine); sizes: (ho, wo) per plane; modes: "rescale", "clip" or ("scale", k) per plane, k indexing `mul` (a float32 device
+    tensor).  The images go into `out` (a flat uint8 device tensor of at least export_layout(...)[1] bytes, allocated when not
+    given) at the offsets of export_layout.  Returns (out, offsets), filled asynchronously on the current stream.  The
+    workspace comes from `arena` (default: one arena per device held by this module).  One shm_export_u8 call per
+    EXPORT_MAX_JOBS planes (two launches at most each): a test-mode batch of 8 images with all 8 planes is one call."""
+    import ctypes as C
+    n = len(planes)
+    if n == 0 or len(sizes) != n or len(modes) != n:
+        raise ValueError(f"export_u8: {n} planes, {len(sizes)} sizes, {len(modes)} modes")
+    desc, chans = [], []
+    for p, (ho, wo), m in zip(planes, sizes, modes):
+        if p.dtype != torch.float32 or not p.is_cuda:
+            raise TypeError(f"export_u8 takes float32 device planes, got {p.dtype} on {p.device}")
+        if p.dim() != 3 or p.shape[0] != p.shape[1] or p.shape[2] not in (1, 3):
+            raise ValueError(f"export_u8 takes [S,S,C] planes with C in {{1,3}}, got {tuple(p.shape)}")
+        S, c = int(p.shape[0]), int(p.shape[2])
+        ld = int(p.stride(1))
+        if p.stride(2) != 1 or ld < c or p.stride(0) != S * ld:
+            raise ValueError(f"export_u8: plane strides {p.stride()} are not [S*ld, ld, 1] with ld >= {c}")
+        if isinstance(m, tuple) and len(m) == 2 and m[0] == "scale":
+            mode, k = EXPORT_MODES["scale"], int(m[1])
+            if mul is None or mul.dtype != torch.float32 or mul.dim() != 1 or not 0 <= k < mul.numel() or not mul.is_contiguous():
+                raise ValueError(f"export_u8: mode {m} needs a contiguous float32 mul with more than {k} elements")
+        elif m in ("rescale", "clip"):
+            mode, k = EXPORT_MODES[m], 0
+        else:
+            raise ValueError(f"export_u8: mode {m!r} is not 'rescale', 'clip' or ('scale', k)")
+        desc.append([S, c, ld, int(ho), int(wo), mode, k, 0])
+        chans.append(c)
+    offs, total = export_layout(sizes, chans)
+    dev = planes[0].device
+    if out is None:
+        out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.numel() < total:
+        raise ValueError(f"export_u8: out must be a contiguous flat uint8 tensor of at least {total} bytes")
+    if arena is None:
+        from .model import Arena
+        arena = _METRIC_ARENAS.setdefault(dev, Arena(dev))
+    need = export_workspace(EXPORT_MAX_JOBS)
+    ws = arena.get("export/ws", (need,), torch.uint8)
+    for d, o in zip(desc, offs):
+        d[7] = o
+    for j0 in range(0, n, EXPORT_MAX_JOBS):
+        part = range(j0, min(n, j0 + EXPORT_MAX_JOBS))
+        src = (C.c_void_p * len(part))(*[planes[j].data_ptr() for j in part])
+        dsc = (C.c_size_t * (EXPORT_DESC * len(part)))(*[v for j in part for v in desc[j]])
+        check(lib().shm_export_u8(src, dsc, len(part), _p(mul), 0 if mul is None else mul.numel(), _p(out), out.numel(),
+                                  _p(ws), need, _stream()), "shm_export_u8")
+    return out, offs
+
+
+def running_scale_mean(scale, acc, mul):
+    """The reference's running mean of the standardisation scales (test.py:77, 218, 246; shm_running_scale_mean): for the
+    batch's scale [B] (float32, what preprocess returns) in image order, acc (float64 [2] device {sum, count}, zero at the
+    start of a test run) takes each scale in and mul[b] (float32 [B]) = the mean of every scale so far, this image's included."""
+    B = int(scale.numel())
+    if scale.dtype != torch.float32 or mul.dtype != torch.float32 or mul.numel() != B or acc.dtype != torch.float64 \
+            or acc.numel() != 2 or not (scale.is_contiguous() and mul.is_contiguous() and acc.is_contiguous()):
+        raise ValueError("running_scale_mean takes float32 scale [B], float64 acc [2] and float32 mul [B], contiguous")
+    check(lib().shm_running_scale_mean(_p(scale), B, _p(acc), _p(mul), _stream()), "shm_running_scale_mean")
+    return mul
+
+
 def adam_clip(w, m, v, g, n, alpha, beta1, beta2, eps, gscale):
     _timed_bytes("shm_adam_clip", 7.0 * 4 * n, lambda: check(          # read w, m, v, g; write w, m, v
         lib().shm_adam_clip(_p(w), _p(m), _p(v), _p(g), n, alpha, beta1, beta2, eps, gscale, _stream()), "shm_adam_clip"))

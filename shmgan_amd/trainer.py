@@ -51,7 +51,8 @@ class _Optimizer:
 _DEFAULTS = dict(image_size=128, batch_size=1, filter_size=64, g_lr=0.00002, d_lr=0.00002, beta1=0.5, beta2=0.99,
                  c_dim=5, num_epochs=200, num_iteration_decay=100000, n_critic=5, d_repeat_num=6, mode="train",
                  data_dir="", model_save_dir="./models", checkpoint_save_dir="./checkpoints", result_dir="./results",
-                 log_dir="./logs/train", log_step=1, checkpoint_save_step=10, calc_metrics=False, test_dir="", diffuse_dir="")
+                 log_dir="./logs/train", log_step=1, checkpoint_save_step=10, calc_metrics=False, test_dir="", diffuse_dir="",
+                 save_images=False, image_values="rescale", image_out_size="source", image_dir="")
 
 LOSS_NAMES = ["total_Generator_loss", "total_Discriminator_loss", "total_Classification_loss", "G_gan_loss",
               "G_clsf_loss", "D1_RealFake_loss", "D3_RealFake_cyc", "D2_RealFake_target", "D4_RealFake_cyc",

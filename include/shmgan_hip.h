@@ -599,6 +599,57 @@ int shm_running_scale_mean(const float* scale, int batch, double* acc, float* mu
 int shm_adam_clip(float* w, float* m, float* v, const float* g, size_t n, float alpha, float beta1,
                   float beta2, float eps, float gscale, void* stream);
 
+/* ---- training telemetry (the reference logs its loss scalars every 25 steps, SHM.py:1035-1053, and a histogram of every clipped
+ * gradient tensor every 100, SHM.py:1085-1091) --------------------------------------------------------------------------------
+ * Segmented statistics of a flat fp32 device buffer x of n floats (P.grad or P.flat of a model).  Segment s is
+ * x[seg_off[s] : seg_off[s] + seg_len[s]], one variable; seg_off and seg_len are host arrays of nseg <= SHM_TSTAT_MAX_SEGS entries
+ * read during the call.  Segments must not overlap (the workspace size assumes it), need not be sorted and need not cover x; an
+ * empty segment gives zeros.  Every value is first scaled as shm_adam_clip scales it, v = x[i] * scale in one fp32 multiply
+ * (denormals kept), so with scale = 1 / world v is the value the optimizer clips.  Per segment:
+ *   stats[s][SHM_TSTAT_N] (f64): SHM_TSTAT_FINITE count of finite v, _NAN count of NaN, _INF count of +-Inf, _MIN / _MAX over the
+ *     finite v (0 when there is none), _SUM / _SUMSQ of the finite v accumulated in f64, _CLIPPED count of finite |v| > 1 (the
+ *     values tf.clip_by_value(g, -1, 1) moves)
+ *   hist[s][2][SHM_THIST_BINS] (u64): counts by sign bit and magnitude class.  The class comes from the bits of v; E = its biased
+ *     exponent field:
+ *       0          E == 0: zeros and subnormals, under sign 0 whatever the sign bit (a flush-to-zero multiply cannot move a value)
+ *       1          normal, |v| < 2^SHM_THIST_EMIN
+ *       2 .. 41    floor(log2 |v|) = e for e in [SHM_THIST_EMIN, -1]: class e - SHM_THIST_EMIN + 2
+ *       42         finite |v| >= 1; with _CLIPPED this gives the histogram AFTER the clip exactly (these values land on +-1)
+ *       43         NaN and Inf, under sign 0
+ * Two launches whatever nseg is: a pass over fixed-size chunks cut relative to each segment's start (bin counts aggregated per
+ * block in LDS; no global atomics) and a per-segment finalize that adds the chunk partials, the f64 sums in chunk order.  A
+ * segment's results are bitwise the same from run to run and depend on that segment alone (not on the other segments or their
+ * order).  x is only read.  ws: shm_tensor_stats_workspace(nseg, n) bytes (enough for any nseg disjoint segments of [0, n)),
+ * 16-byte aligned, no initial contents.  SHM_E_SHAPE for nseg outside [1, SHM_TSTAT_MAX_SEGS], a null pointer, a segment outside
+ * [0, n); SHM_E_WORKSPACE for a short workspace; both before any launch. */
+#define SHM_TSTAT_N 8
+#define SHM_TSTAT_FINITE 0
+#define SHM_TSTAT_NAN 1
+#define SHM_TSTAT_INF 2
+#define SHM_TSTAT_MIN 3
+#define SHM_TSTAT_MAX 4
+#define SHM_TSTAT_SUM 5
+#define SHM_TSTAT_SUMSQ 6
+#define SHM_TSTAT_CLIPPED 7
+#define SHM_THIST_BINS 44
+#define SHM_THIST_EMIN (-40)
+#define SHM_TSTAT_MAX_SEGS 128
+size_t shm_tensor_stats_workspace(int nseg, size_t n);
+int shm_tensor_stats(const float* x, size_t n, const size_t* seg_off, const size_t* seg_len, int nseg, float scale,
+                     double* stats, unsigned long long* hist, void* ws, size_t ws_bytes, void* stream);
+/* One step's raw loss sums into row `row` of a device ring of f64 [rows][SHM_LOSS_ROW], one tiny launch, no host sync:
+ * {dl[SHM_LOSS_ROW_DL] (shm_dhead_losses), il[SHM_LOSS_ROW_IL] (shm_image_losses), sl[SHM_LOSS_ROW_SL] (shm_spec_loss), step,
+ * abort word}, the last two as f64.  abort_word: the device word of shm_set_abort_words (u32) or null (stored as 0).  The caller
+ * chooses the row (the n-th logged step goes to row n % rows) and copies the ring out before a row comes round again. */
+#define SHM_LOSS_ROW_DL 16
+#define SHM_LOSS_ROW_IL 32
+#define SHM_LOSS_ROW_SL 5
+#define SHM_LOSS_ROW_STEP 53
+#define SHM_LOSS_ROW_ABORT 54
+#define SHM_LOSS_ROW 56
+int shm_loss_ring_put(const double* dl, const double* il, const double* sl, const void* abort_word, double* ring, int rows,
+                      int row, long long step, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,7 +16,7 @@ _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ["SHM_LIB_PATH"]) if os.environ.get("SHM_LIB_PATH") else _HERE / "libshmgan_hip.so"
 CSRC = _HERE / "csrc"
 HEADER = _HERE.parent / "include" / "shmgan_hip.h"
-SOURCES = ["conv_igemm.hip", "conv_wreg16.hip", "conv_pingpong.hip", "conv_wgrad.hip", "conv_wgrad_x3.hip", "conv_fwd_x3.hip", "conv_rgb.hip", "norm_elem.hip", "color.hip", "imgloss.hip", "metrics.hip", "specseg.hip", "data.hip", "export.hip"]
+SOURCES = ["conv_igemm.hip", "conv_wreg16.hip", "conv_pingpong.hip", "conv_wgrad.hip", "conv_wgrad_x3.hip", "conv_fwd_x3.hip", "conv_rgb.hip", "norm_elem.hip", "color.hip", "imgloss.hip", "metrics.hip", "specseg.hip", "data.hip", "export.hip", "telemetry.hip"]
 F32, BF16 = 0, 1                 # SHM_F32 / SHM_BF16 of include/shmgan_hip.h
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-munsafe-fp-atomics",
                "-Wall", "-Wno-unused-function", "-Wno-unused-local-typedef"]
@@ -110,6 +110,9 @@ SIGNATURES = {
     "shm_export_u8": (I, [P, P, I, P, I, P, Z, P, Z, P]),
     "shm_running_scale_mean": (I, [P, I, P, P, P]),
     "shm_adam_clip": (I, [P, P, P, P, Z, F, F, F, F, F, P]),
+    "shm_tensor_stats_workspace": (Z, [I, Z]),
+    "shm_tensor_stats": (I, [P, Z, P, P, I, F, P, P, P, Z, P]),
+    "shm_loss_ring_put": (I, [P, P, P, P, P, I, I, C.c_longlong, P]),
 }
 
 def header_functions():

@@ -583,6 +583,66 @@ def image_metrics(pred, target, out=None, arena=None):
     return out
 
 
+# ---- training telemetry (shm_tensor_stats / shm_loss_ring_put, include/shmgan_hip.h) ---------------------------------------
+TSTAT_NAMES = ["finite", "nan", "inf", "min", "max", "sum", "sumsq", "clipped"]     # SHM_TSTAT_* order
+TSTAT_N, THIST_BINS, THIST_EMIN, TSTAT_MAX_SEGS = 8, 44, -40, 128                   # SHM_TSTAT_N, SHM_THIST_BINS, SHM_THIST_EMIN, SHM_TSTAT_MAX_SEGS
+LOSS_ROW_DL, LOSS_ROW_IL, LOSS_ROW_SL, LOSS_ROW_STEP, LOSS_ROW_ABORT, LOSS_ROW = 16, 32, 5, 53, 54, 56     # SHM_LOSS_ROW_*
+
+
+def tensor_stats_workspace(nseg, n):
+    return int(lib().shm_tensor_stats_workspace(nseg, n))
+
+
+class SegmentTable:
+    """Host arrays of shm_tensor_stats' segment table, built once per table (a model's variables never move)."""
+
+    def __init__(self, offsets, sizes):
+        import ctypes as C
+        self.n = len(offsets)
+        if self.n != len(sizes):
+            raise ValueError(f"tensor_stats: {len(offsets)} offsets for {len(sizes)} sizes")
+        self.off = (C.c_size_t * max(self.n, 1))(*[int(o) for o in offsets])
+        self.len = (C.c_size_t * max(self.n, 1))(*[int(z) for z in sizes])
+        self.total = sum(int(z) for z in sizes)
+
+
+def tensor_stats(x, offsets, sizes=None, scale=1.0, out=None, arena=None):
+    """Per-segment statistics and sign / exponent histogram of the flat float32 device tensor x scaled by `scale`
+    (shm_tensor_stats states the definitions): segment s is x[offsets[s] : offsets[s] + sizes[s]].  `offsets` may be a
+    SegmentTable (then `sizes` is not given).  Returns (stats float64 [nseg, 8] in TSTAT_NAMES order, hist int64
+    [nseg, 2, 44]), device tensors filled asynchronously on the current stream; `out` = such a pair to fill.  The workspace
+    comes from `arena` (default: one arena per device held by this module): calls that share an arena must be ordered on
+    one stream."""
+    if x.dtype != torch.float32 or x.dim() != 1 or not x.is_contiguous():
+        raise TypeError(f"tensor_stats takes a flat contiguous float32 tensor, got {x.dtype} {tuple(x.shape)}")
+    tab = offsets if isinstance(offsets, SegmentTable) else SegmentTable(offsets, sizes)
+    nseg, n = tab.n, x.numel()
+    if out is None:
+        out = (torch.empty((nseg, TSTAT_N), dtype=torch.float64, device=x.device),
+               torch.empty((nseg, 2, THIST_BINS), dtype=torch.int64, device=x.device))
+    stats, hist = out
+    if (stats.dtype != torch.float64 or tuple(stats.shape) != (nseg, TSTAT_N) or not stats.is_contiguous()
+            or hist.dtype != torch.int64 or tuple(hist.shape) != (nseg, 2, THIST_BINS) or not hist.is_contiguous()):
+        raise ValueError(f"tensor_stats: out must be contiguous (float64 [{nseg},{TSTAT_N}], int64 [{nseg},2,{THIST_BINS}]) tensors")
+    if arena is None:
+        from .model import Arena
+        arena = _METRIC_ARENAS.setdefault(x.device, Arena(x.device))
+    nb = tensor_stats_workspace(nseg, n)
+    ws = arena.get("tstats/ws", (max((nb + 7) // 8, 1),), torch.int64)
+    _timed_bytes("shm_tensor_stats", 4.0 * tab.total, lambda: check(          # read every segment once
+        lib().shm_tensor_stats(_p(x), n, tab.off, tab.len, nseg, scale, _p(stats), _p(hist), _p(ws), ws.numel() * 8, _stream()),
+        "shm_tensor_stats"))
+    return out
+
+
+def loss_ring_put(dl, il, sl, abort_word, ring, row, step):
+    """shm_loss_ring_put: the step's raw loss vectors, `step` and the abort word into row `row` of ring (float64 [R, LOSS_ROW])."""
+    assert ring.dtype == torch.float64 and ring.dim() == 2 and ring.shape[1] == LOSS_ROW and ring.is_contiguous()
+    assert dl.numel() == LOSS_ROW_DL and il.numel() == LOSS_ROW_IL and sl.numel() == LOSS_ROW_SL
+    check(lib().shm_loss_ring_put(_p(dl), _p(il), _p(sl), _p(abort_word), _p(ring), ring.shape[0], row, step, _stream()),
+          "shm_loss_ring_put")
+
+
 # ---- test-mode image export (the images test.py:305-317 logs) ----------------------------------------------------------
 EXPORT_MODES = {"rescale": 0, "scale": 1, "clip": 2}     # SHM_EXPORT_RESCALE / _SCALE / _CLIP
 EXPORT_DESC, EXPORT_MAX_JOBS = 8, 64                      # SHM_EXPORT_DESC, SHM_EXPORT_MAX_JOBS

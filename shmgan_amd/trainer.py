@@ -28,6 +28,7 @@ from . import ops
 from .dist import GradReducer, exchange_active, world_size
 from .model import Arena, Discriminator, Generator, WgradLane, pad_channels
 from .specseg import SpecSeg
+from .telemetry import LOSS_NAMES, NonFiniteGradientError, Telemetry, compose_losses, telemetry_options  # noqa: F401
 
 
 class _Optimizer:
@@ -52,12 +53,8 @@ _DEFAULTS = dict(image_size=128, batch_size=1, filter_size=64, g_lr=0.00002, d_l
                  c_dim=5, num_epochs=200, num_iteration_decay=100000, n_critic=5, d_repeat_num=6, mode="train",
                  data_dir="", model_save_dir="./models", checkpoint_save_dir="./checkpoints", result_dir="./results",
                  log_dir="./logs/train", log_step=1, checkpoint_save_step=10, calc_metrics=False, test_dir="", diffuse_dir="",
-                 save_images=False, image_values="rescale", image_out_size="source", image_dir="")
-
-LOSS_NAMES = ["total_Generator_loss", "total_Discriminator_loss", "total_Classification_loss", "G_gan_loss",
-              "G_clsf_loss", "D1_RealFake_loss", "D3_RealFake_cyc", "D2_RealFake_target", "D4_RealFake_cyc",
-              "D1_classification_loss", "D3_classification_loss", "D4_classification_loss", "L1_loss_Gen",
-              "ssim_cyc_loss", "content_loss", "style_loss", "total_NST_loss", "Spec_loss"]
+                 save_images=False, image_values="rescale", image_out_size="source", image_dir="",
+                 loss_log_step=0, histogram_step=0, nonfinite=None)
 
 
 class KernelAbortError(RuntimeError):
@@ -138,6 +135,8 @@ class ShmGANwithSSpecSeg:
         # test diagnostics: called with no arguments between the last forward pass and the first backward kernel of a step
         # (tests/test_step_gpu.py pins LeakyReLU signs there; never set on the hot path)
         self.before_backward = None
+        # training telemetry (telemetry.py): None = off, the default; start_telemetry() / train() create it
+        self.telemetry = None
         # SHM_FORWARD_PARTS=2: the two big forward passes (cyclic generator pass on 5B images, discriminator on 12B) as two half
         # batches on the two streams (samples are independent).  Measured in round 3 and NOT the default: in lockstep the halves
         # gain 0.2 ms of a 121 ms fp32 step (within noise), taking turns convolution by convolution (so that one half's normalisation
@@ -202,15 +201,59 @@ class ShmGANwithSSpecSeg:
         if self._lane is not None:
             self._lane.join()
         torch.cuda.synchronize(self.device)
+        try:
+            self.stop_telemetry()        # flushes the logs and ends the writer thread; a writer's error is raised after the buffers are gone
+        finally:
+            self._release_buffers()
+
+    def _release_buffers(self):
         aborted = self._abort_host is not None and (int(self._abort_np[0]) != 0 or int(self._abort_dev.item()) != 0)
         ops.set_abort_words(None, None)
         self._abort_dev = self._abort_host = self._abort_np = None
         self.arena.t.clear()
         self._ws = self._prefetched = self._loss_cache = None
+        self._adhoc_telemetry = None
         self.G = self.D = self.SpecSeg = None
         self.specular_candidate = None
         if aborted:
             raise KernelAbortError("in_bwd_fused8_kernel: a group barrier timed out during this trainer's last steps (seen at release())")
+
+    # ------------------------------------------------------------------ telemetry
+    def start_telemetry(self, log_dir=None, loss_log_step=None, histogram_step=None, nonfinite=None):
+        """Create this trainer's Telemetry (telemetry.py) from the given options, each defaulting to the trainer's `args`
+        (loss_log_step, histogram_step, nonfinite, log_dir).  With both step options 0 nothing is logged by train_step, but
+        grad_stats() / weight_stats() and manual recording work.  Returns it; a running one is flushed and replaced."""
+        if self.G is None:
+            self.build()
+        self.stop_telemetry()
+        a = self.args
+        self.telemetry = Telemetry(self, log_dir=self.log_dir if log_dir is None else log_dir,
+                                   loss_log_step=a.loss_log_step if loss_log_step is None else loss_log_step,
+                                   histogram_step=a.histogram_step if histogram_step is None else histogram_step,
+                                   nonfinite=a.nonfinite if nonfinite is None else nonfinite)
+        return self.telemetry
+
+    def stop_telemetry(self):
+        """Flush the logs and stop the writer thread (release() calls it)."""
+        tel, self.telemetry = self.telemetry, None
+        if tel is not None:
+            tel.close()
+
+    def _stats_now(self, kind, scale):
+        tel = self.telemetry
+        if tel is None:                  # interactive use without logging: a Telemetry with no writer thread and no files
+            tel = self._adhoc_telemetry = getattr(self, "_adhoc_telemetry", None) or Telemetry(self, log_dir=None)
+        return tel.stats_now(kind, scale)
+
+    def grad_stats(self):
+        """{variable name: {"stats", "hist", "shape"}} of the last step's gradients times 1 / world, the values the optimizer
+        clips, as numpy (ops.tensor_stats; names are the save_npz keys G/var00.., D/var00..).  Synchronises: interactive use,
+        train_step never calls it."""
+        return self._stats_now("gradients", 1.0 / self._world())
+
+    def weight_stats(self):
+        """The same of the current weights."""
+        return self._stats_now("weights", 1.0)
 
     def _get_lane(self):
         import os
@@ -360,6 +403,8 @@ class ShmGANwithSSpecSeg:
             self.build()
         self._arm_abort()
         self._check_abort()              # an earlier step's kernel gave up: stop here, before anything else is issued
+        if self.telemetry is not None:
+            self.telemetry.check()       # non-finite gradients in a histogram that has reached the host (nonfinite="raise" / "warn")
         G, D, A = self.G, self.D, self.arena
         S, F = self.image_size, self.filter_size
         orig = [self._dev(t) for t in (orig0, orig45, orig90, orig135, origED)]
@@ -529,13 +574,21 @@ class ShmGANwithSSpecSeg:
             if nb is not None:
                 self._prefetched = self._prologue([self._dev(t) for t in nb], pro.slot ^ 1)
 
-        # ---- clip + Adam  SHM.py:859-872
+        # ---- clip + Adam  SHM.py:859-872.  On a histogram step (telemetry, rank 0 only: the reduced gradient is the same on every rank) the
+        # gradient statistics go beside the Adam launch of the same buffer: both only read the gradient, after its collective
+        tel = self.telemetry if apply and self._rank() == 0 else None
+        step = D.P.iterations + 1
+        hist_now = tel is not None and tel.wants_histograms(step)
         if apply:
             self._reducer.wait_on(ev_d)
+            if hist_now:
+                tel.record_gradients("D", 1.0 / world)
             self.optimizer_D.apply(D.P, 1.0 / world)
             D.weights_dirty = True
             if update_g:
                 self._reducer.wait_on(ev_g)
+                if hist_now:
+                    tel.record_gradients("G", 1.0 / world)
                 self.optimizer_G.apply(G.P, 1.0 / world)
                 G.weights_dirty = True
         elif exchange_active():
@@ -553,6 +606,8 @@ class ShmGANwithSSpecSeg:
         self.stddev_arr = scales          # reference appends forever (a leak); we keep the last step's
         self._last = SimpleNamespace(dl=dl, il=il, sl=sl, npix=npix, B=B, flags=flags, T=T, scales=scales, ds=ds, cbcr=cbcr)
         self._loss_cache = None
+        if tel is not None:
+            tel.after_step(step, self.epoch, T, self._last, hist_now, update_g)
         return None
 
     # ------------------------------------------------------------------ the training loop (SHM.py:889-1139)
@@ -566,8 +621,12 @@ class ShmGANwithSSpecSeg:
         Differences, all outside the arithmetic: checkpoints are the neutral .npz of save_npz (Keras variable order
         and layouts; newest 3 kept, as CheckpointManager(max_to_keep=3)) instead of TF checkpoints; the summaries go
         to `log_dir`; the Comet histogram upload at step 100 (which raises AttributeError in the reference, SURVEY
-        section 3.1) and the per-step gc.collect() are not reproduced.  `max_steps` (tests) stops early.  Returns the
-        number of train_step calls made."""
+        section 3.1) and the per-step gc.collect() are not reproduced.  The monitoring itself is: with `loss_log_step` (reference: 25) the
+        named loss scalars of SHM.py:1035-1053 go to `log_dir`/losses.jsonl, with `histogram_step` (reference: 100) the statistics and
+        sign / exponent histograms of every gradient tensor (gradmapD, gradmapG, SHM.py:1085-1091) and of every weight tensor go to
+        gradients.jsonl / weights.jsonl, computed on the device and written by a thread of their own (telemetry.py; `nonfinite` says what
+        a NaN or Inf gradient does).  Both are off by default; the step counts optimizer updates, so a resumed run appends.  The logs are
+        flushed before every checkpoint.  `max_steps` (tests) stops early.  Returns the number of train_step calls made."""
         import os
         import time
         from .data import datasetLoad
@@ -592,6 +651,21 @@ class ShmGANwithSSpecSeg:
         latest = self._restore_latest()                                        # SHM.py:949-951 (delete_old_checkpoints is False)
         if latest is not None:
             print_fn(f"Latest checkpoint restored!! ({latest})")
+        loss_step, hist_step, _ = telemetry_options(self.args.loss_log_step, self.args.histogram_step, self.args.nonfinite)
+        if rank0 and (loss_step or hist_step):
+            self.start_telemetry()
+        try:
+            return self._train_loop(dataset, max_steps, print_fn, start)
+        except BaseException:
+            if self.telemetry is not None:                                     # what was logged before a step raised is written out;
+                try:                                                           # the step's own error is the one to report
+                    self.telemetry.flush()
+                except Exception:
+                    pass
+            raise
+
+    def _train_loop(self, dataset, max_steps, print_fn, start):
+        import time
         iterator = iter(dataset)                                               # SHM.py:955
         batches_per_epoch = int(self.length_dataset / self.batch_size)         # SHM.py:957
         self.batch_step = 0
@@ -707,6 +781,11 @@ class ShmGANwithSSpecSeg:
         return chosen
 
     def _save_checkpoint(self, max_to_keep=3):
+        if self.telemetry is not None:
+            self.telemetry.flush()       # a log never trails a checkpoint
+        return self._save_checkpoint_file(max_to_keep)
+
+    def _save_checkpoint_file(self, max_to_keep=3):
         """tf.train.CheckpointManager(ckpt, checkpoint_dir, max_to_keep=3).save() (SHM.py:944, 1127).  Rank 0 writes (to a
         temporary name, then an atomic rename) and prunes; every rank leaves through a barrier, so nobody races ahead into a
         collective while the file is still being written and nobody deletes a file another rank is about to open."""
@@ -871,29 +950,7 @@ class ShmGANwithSSpecSeg:
             return self._loss_cache
         L = self._last
         self._check_abort(sync=True)
-        d = (L.dl.cpu().numpy() / L.B).tolist()
-        i = (L.il.cpu().numpy() / L.B).tolist()
-        D1_RF, D3_RF = d[0], d[1]
-        D2_RF = d[4] + d[2]
-        D4_RF = d[5] + d[3] + D2_RF
-        D1_cls, D3_cls, D4_cls = d[6], d[7], d[8]
-        L1 = (i[1] + i[2] + i[3] + i[4] + i[0]) / 5.0 + i[5] * 10.0
-        ssim_loss = (i[11] + i[12] + i[13] + i[14] + i[15] * 10.0) / 5.0
-        content, style = i[16], i[17]
-        nst = 100.0 * style + content
-        sp = (L.sl.cpu().numpy() / (L.B * L.npix * 3.0)).tolist()       # reduce_mean over [B,S,S,3]
-        out = {
-            "total_Generator_loss": (D1_RF + D3_RF) / 6.0 + 10.0 * L1 + 10.0 * ssim_loss + 10.0 * nst,
-            "total_Discriminator_loss": (D1_cls + D3_cls) / 6.0 + (D2_RF + D4_RF) / 6.0 + 0.5 * D4_cls + 10.0 * nst,
-            "total_Classification_loss": (D4_cls + nst) * 10.0,
-            "G_gan_loss": (D3_RF + D1_RF) / 6.0, "G_clsf_loss": (D3_cls + D1_cls) / 6.0,
-            "D1_RealFake_loss": D1_RF, "D3_RealFake_cyc": D3_RF, "D2_RealFake_target": D2_RF,
-            "D4_RealFake_cyc": D4_RF, "D1_classification_loss": D1_cls, "D3_classification_loss": D3_cls,
-            "D4_classification_loss": D4_cls, "L1_loss_Gen": L1, "ssim_cyc_loss": ssim_loss,
-            "content_loss": content, "style_loss": style, "total_NST_loss": nst,
-            "Spec_loss": (sp[0] + sp[1] + sp[2] + sp[3]) / 5.0 + sp[4] * 5.0,
-            "ssim": [i[6 + k] for k in range(5)],
-        }
+        out = compose_losses(L.dl.cpu().numpy(), L.il.cpu().numpy(), L.sl.cpu().numpy(), L.B, L.npix)
         self._loss_cache = out
         return out
 

@@ -16,7 +16,9 @@ _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ["SHM_LIB_PATH"]) if os.environ.get("SHM_LIB_PATH") else _HERE / "libshmgan_hip.so"
 CSRC = _HERE / "csrc"
 HEADER = _HERE.parent / "include" / "shmgan_hip.h"
-SOURCES = ["conv_igemm.hip", "conv_wreg16.hip", "conv_pingpong.hip", "conv_wgrad.hip", "conv_wgrad_x3.hip", "conv_fwd_x3.hip", "conv_rgb.hip", "norm_elem.hip", "color.hip", "imgloss.hip", "metrics.hip", "specseg.hip", "data.hip", "export.hip", "telemetry.hip"]
+SOURCES = ["runtime.hip", "conv_igemm.hip", "conv_wreg16.hip", "conv_pingpong.hip", "conv_wgrad.hip", "conv_wgrad_x3.hip", "conv_fwd_x3.hip", "conv_rgb.hip", "norm_elem.hip", "color.hip", "imgloss.hip", "metrics.hip", "specseg.hip", "data.hip", "export.hip", "telemetry.hip"]
+# headers every source may include: a change of any of them rebuilds every object (tools/sanitize_host.py goes by the same list)
+SHARED_HEADERS = [CSRC / "common.h", CSRC / "ablate.h", CSRC / "tapgemm.h", CSRC / "wgrad.h", CSRC / "x3split.h", HEADER]
 F32, BF16 = 0, 1                 # SHM_F32 / SHM_BF16 of include/shmgan_hip.h
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-munsafe-fp-atomics",
                "-Wall", "-Wno-unused-function", "-Wno-unused-local-typedef"]
@@ -130,7 +132,6 @@ def build(force=False, verbose=False, jobs=None):
     import hashlib
     from concurrent.futures import ThreadPoolExecutor
     srcs = [CSRC / s for s in SOURCES]
-    shared = [CSRC / "common.h", CSRC / "ablate.h", CSRC / "tapgemm.h", CSRC / "wgrad.h", CSRC / "x3split.h", HEADER]
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     cflags = [f for f in HIPCC_FLAGS if f != "-shared"]
     # what the objects were built WITH: compiler, flags and source list (a change of HIPCC_FLAGS must not relink stale objects)
@@ -139,12 +140,12 @@ def build(force=False, verbose=False, jobs=None):
     objdir.mkdir(exist_ok=True)
     stamp = objdir / "flags.sha256"
     same_cmd = stamp.exists() and stamp.read_text().strip() == stamp_txt
-    deps = srcs + shared
+    deps = srcs + SHARED_HEADERS
     if not force and same_cmd and LIB_PATH.exists():
         newest = max(p.stat().st_mtime for p in deps)
         if LIB_PATH.stat().st_mtime >= newest:
             return LIB_PATH
-    hdr_time = max(p.stat().st_mtime for p in shared)
+    hdr_time = max(p.stat().st_mtime for p in SHARED_HEADERS)
     todo = []
     for src in srcs:
         obj = objdir / (src.stem + ".o")

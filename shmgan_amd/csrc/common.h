@@ -22,9 +22,14 @@ int shm_rgb_s2_fwd_launch(const void* x, int ldx, const void* wk, int K, const f
 int shm_rgb_s2_wgrad_launch(const void* x, int ldx, const void* dy, int lddy, float* part, size_t ws_bytes, int batch, int hi, int wi, int cin, int cout,
                             size_t xbytes, size_t dybytes, int dtype, int* nsplit_out, hipStream_t st);
 
+// norm_elem.hip, for the composite convolution entry points of conv_igemm.hip: the finalize pass of the statistics a convolution's epilogue
+// summed (shm_conv2d_in_fwd), and the stand-alone (sum g, sum g * aux) pass behind a kernel without a gsum epilogue (shm_conv2d_*_gsum)
+int shm_in_finalize_internal(double* stats, double* part, int nslot, int total, int hw, double eps, float* nt, const float* beta, int c, hipStream_t st);
+int shm_gsum_reduce_internal(const void* g, int ldg, const void* aux, int ldaux, double* red, int batch, int hw, int c, int dtype, hipStream_t st);
+
 // Dispatch knobs behind shm_set_tuning()/shm_get_tuning() (include/shmgan_hip.h lists the keys).  Process-wide
 // atomics read at every launch; the initial value comes from the environment variable named in the table of
-// norm_elem.hip (so tools/ablate_conv.py keeps working), -1/0 = the built-in choice.
+// runtime.hip (so tools/ablate_conv.py keeps working), -1/0 = the built-in choice.
 enum ShmTune {
     SHM_TUNE_TAPGEMM_VARIANT = 0,     // SHM_TG_* below; 0 = automatic
     SHM_TUNE_TAPGEMM_HALO_MIN,        // fp32: 128-wide halo blocks from which the 128-wide block is taken unconditionally
@@ -54,8 +59,9 @@ enum ShmTune {
     SHM_TUNE_COUNT
 };
 int shm_tune(int id);
-unsigned long long* shm_clock_probe();       // this thread's shm_set_clock_probe buffer (norm_elem.hip), or null
-const unsigned* shm_abort_dev_word();       // this thread's shm_set_abort_words device word (norm_elem.hip), or null
+unsigned long long* shm_clock_probe();       // this thread's shm_set_clock_probe buffer (runtime.hip), or null
+unsigned* shm_abort_dev_word();              // this thread's shm_set_abort_words device word (runtime.hip), or null
+unsigned* shm_abort_host_word();             // ... and its host word
 
 // Barrier of the LDS-DMA pipelines.  A stage is refilled by DMA instructions issued AFTER the barrier that follows its last use, so a
 // wave must not enter that barrier with fragment reads of the stage still queued: the MFMAs that consume them are register-only
@@ -230,6 +236,20 @@ __device__ __forceinline__ float shm_in_norm(float x, float mean, float inv, flo
 // ring = mean - beta / inv, the RAW value whose normalised image is 0 (what an out-of-image tap has to read in SHM_NORM_SCALED mode).
 #define SHM_NT_PLANES 4
 #define SHM_NT_MAXC 256           // normalised channels a folding consumer keeps in LDS
+// The nt_x / nt_x2 / norm_mode arguments of such a consumer's entry point (`who`) as one request: the table, which source it belongs to
+// (part 0 = x, 1 = x2) and that source's channels out of the `c_all` of both.  nt == null: no source is normalised on the fly.
+struct ShmNormReq {
+    const float* nt;
+    int part, c, mode;
+};
+static inline int shm_norm_request(ShmNormReq* q, const char* who, const float* nt_x, const float* nt_x2, int norm_mode, const void* x2, int c1, int c_all) {
+    SHM_REQUIRE(norm_mode == SHM_NORM_EXACT || norm_mode == SHM_NORM_SCALED, SHM_E_SHAPE, "%s: norm_mode %d", who, norm_mode);
+    SHM_REQUIRE(!(nt_x && nt_x2), SHM_E_SHAPE, "%s: at most one source can be normalised on the fly", who);
+    SHM_REQUIRE(!nt_x2 || x2, SHM_E_SHAPE, "%s: nt_x2 without a second source", who);
+    *q = ShmNormReq{};
+    if (nt_x || nt_x2) *q = ShmNormReq{nt_x ? nt_x : nt_x2, nt_x ? 0 : 1, x2 ? (nt_x ? c1 : c_all - c1) : c_all, norm_mode};
+    return SHM_OK;
+}
 
 // wave64 sum via DPP-free shuffles
 __device__ __forceinline__ double shm_wave_sum(double v) {

@@ -2245,32 +2245,27 @@ __global__ __launch_bounds__(512, 2) void tapgemm_phase4_kernel(const TapGemmArg
     }
 }
 
-static thread_local double* g_conv_stats = nullptr;     // set by shm_conv2d_in_fwd around its conv launch
-static thread_local int g_conv_hw = 0, g_conv_slots = 1;
-
-// gsum request of the *_gsum entry points around their launch, and whether the kernel that ran took it (otherwise the entry
-// point follows up with the stand-alone reduce pass, shm_gsum_reduce_internal)
-struct GsumReq {
-    const void* aux[2];
-    int ld[2];
-    double* red[2];
+// What a composite entry point asks of a product beyond the product itself, and what the launcher tells it back
+struct ConvExtras {
+    double* stats = nullptr;            // shm_conv2d_in_fwd: fused forward statistics (TapGemmArgs::stats, hw, stats_slots)
+    int stats_hw = 0, stats_slots = 1;
+    const void* gaux[2] = {};           // the *_gsum entry points (TapGemmArgs::gaux, ldgaux, gred)
+    int ldgaux[2] = {};
+    double* gred[2] = {};
+    ShmNormReq norm = {};               // shm_conv2d_in_fwd_norm (TapGemmArgs::nt, ntpart, ntc, ntmode)
+    // shm_conv2d_norm_supported: the launcher goes through its variant choice as if a SHM_NORM_EXACT request for source norm.part with
+    // norm.c channels had come, reports in norm_ok whether that kernel can normalise its source in LDS, and launches nothing.  A dry
+    // run has no operands (null pointers read as "aligned"); a second source is announced by a non-null x2, which nobody dereferences.
+    bool dry_run = false;
+    // out: the kernel that ran took the gsum request in its epilogue (otherwise the entry point follows up with the stand-alone reduce
+    // pass, shm_gsum_reduce_internal); the dry run's answer
+    bool gsum_fused = false, norm_ok = false;
 };
-static thread_local GsumReq g_gsum = {};
-static thread_local bool g_gsum_fused = false;
-
-// norm request of shm_conv2d_in_fwd_norm around its launch (TapGemmArgs::nt); query = shm_conv2d_norm_supported's dry run: the
-// launcher goes through its variant choice, records whether that kernel can normalise its source in LDS, and launches nothing
-struct NormReq {
-    const float* nt;
-    int part, c, mode;
-    bool query, query_ok;
-};
-static thread_local NormReq g_norm = {};
 
 // Variant choice.  `forced` (shm_set_tuning("tapgemm.variant", SHM_TG_*)) overrides the automatic choice; a forced
 // variant the shape is not eligible for is an error (SHM_E_SHAPE), so a parity test that forces a variant knows it ran.
 template <typename T, typename TO>
-static int launch_tapgemm_t(const TapGemmArgs& a_in, int batch, int nphase, hipStream_t st, const char* who) {
+static int launch_tapgemm_t(const TapGemmArgs& a_in, int batch, int nphase, hipStream_t st, const char* who, ConvExtras& ex) {
     TapGemmArgs a = a_in;
     constexpr int BKE = 64 / (int)sizeof(T);
     const char* tn = sizeof(T) == 4 ? "float" : "__bf16";
@@ -2395,10 +2390,10 @@ static int launch_tapgemm_t(const TapGemmArgs& a_in, int batch, int nphase, hipS
         }
         if (!gs_fused) a.gred[0] = a.gred[1] = nullptr;
     }
-    g_gsum_fused = gs_fused;
+    ex.gsum_fused = gs_fused;
     // norm: the kernels that stage the A operand as a halo image in LDS (static-tap halo blocks, weights-in-registers kernels) can
     // normalise it there; the part's channels must fit the LDS table and be whole 64-byte rows
-    const bool want_nm = a.nt != nullptr;
+    const bool want_nm = a.nt != nullptr || ex.dry_run;
     if (want_nm) {
         const int pc = a.ntpart ? a.K - a.c1 : a.c1;
         bool ok = !want_gs && nphase == 1 && a.ntc == pc && pc % BKE == 0 && pc <= SHM_NT_MAXC && (a.ntpart == 0 || a.x2 != nullptr);
@@ -2412,16 +2407,13 @@ static int launch_tapgemm_t(const TapGemmArgs& a_in, int batch, int nphase, hipS
         default:
             ok = false;
         }
-        if (g_norm.query) {
-            g_norm.query_ok = ok;
+        if (ex.dry_run) {
+            ex.norm_ok = ok;
             return SHM_OK;
         }
         SHM_REQUIRE(ok, SHM_E_SHAPE,
                     "%s: the kernel this shape runs on (tapgemm variant %d) cannot normalise its source in LDS (unit-stride 3x3 on a map that is a "
                     "multiple of 16, normalised part of at most %d channels; ask shm_conv2d_norm_supported) -- use shm_in_apply", who, v, SHM_NT_MAXC);
-    } else if (g_norm.query) {
-        g_norm.query_ok = false;
-        return SHM_OK;
     }
     auto grid1d = [&](int bm, int bn) { return dim3(shm_cdiv(a.M, bm), shm_cdiv(a.nout, bn), nphase); };
     const int npatch = batch * (a.hi / 16) * (a.wi / 16);
@@ -2657,28 +2649,28 @@ static int launch_tapgemm_t(const TapGemmArgs& a_in, int batch, int nphase, hipS
     return SHM_OK;
 }
 
-static int launch_tapgemm(TapGemmArgs& a, int batch, int nphase, int dtype, hipStream_t st, const char* who) {
+// `a`: the product (operands, geometry, phase table) as its entry point filled it; the rest of the block comes from `ex` and from here
+static int launch_tapgemm(TapGemmArgs& a, int batch, int nphase, int dtype, hipStream_t st, const char* who, ConvExtras& ex) {
     SHM_REQUIRE(dtype == SHM_F32 || dtype == SHM_BF16 || dtype == SHM_BF16_GF32, SHM_E_DTYPE,
                 "%s: dtype %d not in {SHM_F32, SHM_BF16, SHM_BF16_GF32}", who, dtype);
-    a.stats = g_conv_stats;
-    a.hw = g_conv_hw;
-    a.stats_slots = g_conv_slots;
+    a.stats = ex.stats;
+    a.hw = ex.stats_hw;
+    a.stats_slots = ex.stats_slots;
     a.stats_stride = (unsigned)batch * (unsigned)a.nout * 2u;
     for (int p = 0; p < 2; ++p) {
-        a.gaux[p] = g_gsum.aux[p];
-        a.ldgaux[p] = g_gsum.ld[p];
-        a.gred[p] = g_gsum.red[p];
+        a.gaux[p] = ex.gaux[p];
+        a.ldgaux[p] = ex.ldgaux[p];
+        a.gred[p] = ex.gred[p];
     }
     a.gslots = SHM_GSUM_SLOTS;
     a.gbatch = batch;
-    a.nt = g_norm.nt;
-    a.ntpart = g_norm.part;
-    a.ntc = g_norm.c;
-    a.ntmode = g_norm.mode;
-    a.ntbytes = (unsigned)((size_t)batch * SHM_NT_PLANES * g_norm.c * sizeof(float));
+    a.nt = ex.norm.nt;
+    a.ntpart = ex.norm.part;
+    a.ntc = ex.norm.c;
+    a.ntmode = ex.norm.mode;
+    a.ntbytes = (unsigned)((size_t)batch * SHM_NT_PLANES * ex.norm.c * sizeof(float));
     a.wimg = 0;
     a.bias_img = 0;
-    g_gsum_fused = false;
     if (a.gred[0] || a.gred[1]) {
         SHM_REQUIRE(a.stats == nullptr, SHM_E_SHAPE, "%s: fused forward statistics and gsum are exclusive", who);
         a.hw = a.hg * a.wg;           // pixels per sample in the M index space of one phase
@@ -2721,7 +2713,7 @@ static int launch_tapgemm(TapGemmArgs& a, int batch, int nphase, int dtype, hipS
     // the 3-channel stride-2 first layer of the discriminator on the compact image layout (conv_rgb.hip); a forced tapgemm.variant keeps
     // the generic kernels (which read K channels per tap from the 16-byte pixels: the neighbours' values times the zero weight columns)
     if (nphase == 1 && a.is == 2 && a.os == 1 && a.ph[0].ntaps == 9 && a.ph[0].dh[0] == 0 && a.ph[0].dw[0] == 0 && !a.x2 && !a.y2 && !a.gred[0] && !a.gred[1] &&
-        !a.nt && !g_norm.query && a.ldx * esz == 16 && a.K * esz == 64 && a.ybytes != 0 && dtype != SHM_BF16_GF32 &&
+        !a.nt && !ex.dry_run && a.ldx * esz == 16 && a.K * esz == 64 && a.ybytes != 0 && dtype != SHM_BF16_GF32 &&
         shm_tune(SHM_TUNE_TAPGEMM_VARIANT) == SHM_TG_AUTO) {
         const int r = shm_rgb_s2_fwd_launch(a.x, a.ldx, a.w, a.K, a.bias, a.y, a.ldy, batch, a.hi, a.wi, a.nout, a.slope, a.stats, a.stats_slots, a.stats_stride,
                                             a.xbytes, a.ybytes, dtype, st);
@@ -2730,13 +2722,12 @@ static int launch_tapgemm(TapGemmArgs& a, int batch, int nphase, int dtype, hipS
     }
     int rc;
     if (dtype == SHM_BF16)
-        rc = launch_tapgemm_t<bf16_t, bf16_t>(a, batch, nphase, st, who);
+        rc = launch_tapgemm_t<bf16_t, bf16_t>(a, batch, nphase, st, who, ex);
     else if (dtype == SHM_BF16_GF32)
-        rc = launch_tapgemm_t<bf16_t, float>(a, batch, nphase, st, who);
+        rc = launch_tapgemm_t<bf16_t, float>(a, batch, nphase, st, who, ex);
     else
-        rc = launch_tapgemm_t<float, float>(a, batch, nphase, st, who);
-    if (rc) return rc;
-    if (g_norm.query) return SHM_OK;
+        rc = launch_tapgemm_t<float, float>(a, batch, nphase, st, who, ex);
+    if (rc || ex.dry_run) return rc;
     SHM_LAUNCH_CHECK(who);
     return SHM_OK;
 }
@@ -2888,51 +2879,66 @@ extern "C" int shm_conv2d_norm_prepare(const void* wk, const float* bias, const 
 }
 
 // ------------------------------------------------------------------------------------
-extern "C" int shm_conv2d_fwd(const void* x, const void* x2, int c1, int ldx, int ldx2, const void* wk,
-                              const float* bias, void* y, int ldy, int batch, int hi, int wi, int cin,
-                              int cout, int ksize, int stride, float slope, int dtype, void* stream) {
-    SHM_REQUIRE(ksize == 1 || ksize == 3, SHM_E_SHAPE, "shm_conv2d_fwd: ksize %d not in {1,3}", ksize);
-    SHM_REQUIRE(stride == 1 || stride == 2, SHM_E_SHAPE, "shm_conv2d_fwd: stride %d not in {1,2}", stride);
-    SHM_REQUIRE(x && wk && y, SHM_E_SHAPE, "shm_conv2d_fwd: null pointer");
+// The part of the argument block the forward forms share: one source of K channels, weights [taps][nout][K], bias and LeakyReLU, one
+// destination of nout channels.  Callers add a second source / destination and the output geometry with its phase table.
+static TapGemmArgs fwd_args(const void* x, int ldx, const void* w, const float* bias, void* y, int ldy, int hi, int wi, int K, int nout, float slope) {
     TapGemmArgs a{};
     a.x = x;
-    a.x2 = x2;
-    a.c1 = x2 ? c1 : cin;
+    a.c1 = K;
     a.ldx = ldx;
-    a.ldx2 = ldx2;
-    a.w = wk;
+    a.w = w;
     a.bias = bias;
     a.y = y;
-    a.y2 = nullptr;
-    a.n1 = cout;
+    a.n1 = nout;
     a.ldy = ldy;
-    a.ldy2 = 0;
     a.hi = hi;
     a.wi = wi;
-    a.K = cin;
-    int ho, wo, pt, pl;
-    shm_same_pad(hi, ksize, stride, &ho, &pt);
-    shm_same_pad(wi, ksize, stride, &wo, &pl);
-    a.hg = a.ho = ho;
-    a.wg = a.wo = wo;
-    a.nout = cout;
-    a.is = stride;
-    a.os = 1;
+    a.K = K;
+    a.nout = nout;
     a.slope = slope;
-    TapPhase& P = a.ph[0];
+    return a;
+}
+
+// One phase of ksize x ksize taps: tap (kh, kw) reads the source at sign * ((kh, kw) - (pt, pl)) from the output pixel
+static void fill_taps(TapPhase& P, int ksize, int pt, int pl, int sign) {
     P.oph = P.opw = 0;
     P.ntaps = ksize * ksize;
     for (int kh = 0; kh < ksize; ++kh)
         for (int kw = 0; kw < ksize; ++kw) {
             int t = kh * ksize + kw;
-            P.dh[t] = kh - pt;
-            P.dw[t] = kw - pl;
+            P.dh[t] = sign * (kh - pt);
+            P.dw[t] = sign * (kw - pl);
             P.widx[t] = t;
         }
-    return launch_tapgemm(a, batch, 1, dtype, (hipStream_t)stream, "shm_conv2d_fwd");
 }
 
-int shm_in_finalize_internal(double* stats, double* part, int nslot, int total, int hw, double eps, float* nt, const float* beta, int c, hipStream_t st);
+// shm_conv2d_fwd and every entry point that is a forward product with extras
+static int conv_fwd_impl(const void* x, const void* x2, int c1, int ldx, int ldx2, const void* wk, const float* bias, void* y, int ldy, int batch, int hi,
+                         int wi, int cin, int cout, int ksize, int stride, float slope, int dtype, void* stream, ConvExtras& ex) {
+    SHM_REQUIRE(ksize == 1 || ksize == 3, SHM_E_SHAPE, "shm_conv2d_fwd: ksize %d not in {1,3}", ksize);
+    SHM_REQUIRE(stride == 1 || stride == 2, SHM_E_SHAPE, "shm_conv2d_fwd: stride %d not in {1,2}", stride);
+    SHM_REQUIRE(ex.dry_run || (x && wk && y), SHM_E_SHAPE, "shm_conv2d_fwd: null pointer");
+    TapGemmArgs a = fwd_args(x, ldx, wk, bias, y, ldy, hi, wi, cin, cout, slope);
+    a.x2 = x2;
+    a.c1 = x2 ? c1 : cin;
+    a.ldx2 = ldx2;
+    int ho, wo, pt, pl;
+    shm_same_pad(hi, ksize, stride, &ho, &pt);
+    shm_same_pad(wi, ksize, stride, &wo, &pl);
+    a.hg = a.ho = ho;
+    a.wg = a.wo = wo;
+    a.is = stride;
+    a.os = 1;
+    fill_taps(a.ph[0], ksize, pt, pl, 1);
+    return launch_tapgemm(a, batch, 1, dtype, (hipStream_t)stream, "shm_conv2d_fwd", ex);
+}
+
+extern "C" int shm_conv2d_fwd(const void* x, const void* x2, int c1, int ldx, int ldx2, const void* wk,
+                              const float* bias, void* y, int ldy, int batch, int hi, int wi, int cin,
+                              int cout, int ksize, int stride, float slope, int dtype, void* stream) {
+    ConvExtras ex;
+    return conv_fwd_impl(x, x2, c1, ldx, ldx2, wk, bias, y, ldy, batch, hi, wi, cin, cout, ksize, stride, slope, dtype, stream, ex);
+}
 
 extern "C" int shm_conv2d_in_fwd(const void* x, const void* x2, int c1, int ldx, int ldx2, const void* wk,
                                  const float* bias, void* y, int ldy, int batch, int hi, int wi, int cin,
@@ -2950,19 +2956,13 @@ extern "C" int shm_conv2d_norm_supported(int batch, int hi, int wi, int cin, int
     if (norm_part != 0 && norm_part != 1) return 0;
     const bool two = c1 > 0 && c1 < cin;
     if (norm_part == 1 && !two) return 0;
-    // operands are never dereferenced in a dry run; any aligned non-null address serves
-    static const __attribute__((aligned(256))) char dummy[256] = {};
-    const void* px = dummy;
-    g_norm.nt = (const float*)dummy;
-    g_norm.part = norm_part;
-    g_norm.c = two ? (norm_part ? cin - c1 : c1) : cin;
-    g_norm.query = true;
-    g_norm.query_ok = false;
-    const int r = shm_conv2d_fwd(px, two ? px : nullptr, two ? c1 : 0, two ? c1 : cin, two ? cin - c1 : 0, px, nullptr, (void*)dummy, cout, batch, hi, wi, cin, cout,
-                                 ksize, stride, 0.2f, dtype, nullptr);
-    const bool ok = r == SHM_OK && g_norm.query_ok;
-    g_norm = NormReq{};
-    return ok ? 1 : 0;
+    ConvExtras ex;
+    ex.dry_run = true;
+    ex.norm.part = norm_part;
+    ex.norm.c = two ? (norm_part ? cin - c1 : c1) : cin;
+    const int r = conv_fwd_impl(nullptr, two ? &ex : nullptr, two ? c1 : 0, two ? c1 : cin, two ? cin - c1 : 0, nullptr, nullptr, nullptr, cout, batch, hi, wi, cin,
+                                cout, ksize, stride, 0.2f, dtype, nullptr, ex);
+    return r == SHM_OK && ex.norm_ok ? 1 : 0;
 }
 
 extern "C" int shm_conv2d_in_fwd_norm(const void* x, const void* x2, int c1, int ldx, int ldx2, const float* nt_x, const float* nt_x2, int norm_mode,
@@ -2970,27 +2970,15 @@ extern "C" int shm_conv2d_in_fwd_norm(const void* x, const void* x2, int c1, int
                                       int stride, float slope, double* stats, double* scratch, float eps, float* nt_out, const float* beta_out, int dtype,
                                       void* stream) {
     SHM_REQUIRE(stats, SHM_E_SHAPE, "shm_conv2d_in_fwd: null stats");
-    SHM_REQUIRE(norm_mode == SHM_NORM_EXACT || norm_mode == SHM_NORM_SCALED, SHM_E_SHAPE, "shm_conv2d_in_fwd_norm: norm_mode %d", norm_mode);
-    SHM_REQUIRE(!(nt_x && nt_x2), SHM_E_SHAPE, "shm_conv2d_in_fwd_norm: at most one source can be normalised on the fly");
-    SHM_REQUIRE(!nt_x2 || x2, SHM_E_SHAPE, "shm_conv2d_in_fwd_norm: nt_x2 without a second source");
+    ConvExtras ex;
+    if (const int r = shm_norm_request(&ex.norm, "shm_conv2d_in_fwd_norm", nt_x, nt_x2, norm_mode, x2, c1, cin)) return r;
     SHM_REQUIRE(!nt_out || beta_out, SHM_E_SHAPE, "shm_conv2d_in_fwd_norm: nt_out needs beta_out");
     int ho, wo, pt;
     shm_same_pad(hi, ksize, stride, &ho, &pt);
     shm_same_pad(wi, ksize, stride, &wo, &pt);
     const int hw = ho * wo;
-    const bool norm_in = nt_x || nt_x2;
-    struct NormScope {             // the request lives for the conv launch of this call only
-        ~NormScope() { g_norm = NormReq{}; }
-    } norm_scope;
-    if (norm_in) {
-        g_norm.nt = nt_x ? nt_x : nt_x2;
-        g_norm.part = nt_x ? 0 : 1;
-        g_norm.c = x2 ? (nt_x ? c1 : cin - c1) : cin;
-        g_norm.mode = norm_mode;
-    }
     if (!shm_tune(SHM_TUNE_STATS_FUSION) || hw % 64 != 0) {       // tiny maps: separate statistics pass
-        int r = shm_conv2d_fwd(x, x2, c1, ldx, ldx2, wk, bias, y, ldy, batch, hi, wi, cin, cout, ksize, stride, slope, dtype, stream);
-        g_norm = NormReq{};
+        int r = conv_fwd_impl(x, x2, c1, ldx, ldx2, wk, bias, y, ldy, batch, hi, wi, cin, cout, ksize, stride, slope, dtype, stream, ex);
         if (r) return r;
         r = shm_in_stats(y, ldy, stats, batch, hw, cout, eps, dtype, stream);
         if (r == SHM_OK && nt_out) r = shm_in_norm_table(stats, beta_out, nt_out, batch, cout, stream);
@@ -3001,18 +2989,13 @@ extern "C" int shm_conv2d_in_fwd_norm(const void* x, const void* x2, int c1, int
     // With `scratch` the chain is cut SHM_STATS_SLOTS-fold and the finalize kernel sums the copies.
     // `scratch` is zero on entry by contract and left zero (the finalize kernel clears what it sums); without it the
     // sums go to `stats`, which is zeroed here.
-    double* acc = scratch ? scratch : stats;
-    const int slots = scratch ? SHM_STATS_SLOTS : 1;
+    ex.stats = scratch ? scratch : stats;
+    ex.stats_slots = scratch ? SHM_STATS_SLOTS : 1;
+    ex.stats_hw = hw;
     int r = scratch ? SHM_OK : shm_zero(stats, (size_t)batch * cout * 2 * sizeof(double), stream);
     if (r) return r;
-    g_conv_stats = acc;
-    g_conv_slots = slots;
-    g_conv_hw = hw;
-    r = shm_conv2d_fwd(x, x2, c1, ldx, ldx2, wk, bias, y, ldy, batch, hi, wi, cin, cout, ksize, stride, slope, dtype, stream);
-    g_conv_stats = nullptr;
-    g_conv_slots = 1;
-    g_norm = NormReq{};
-    if (r == SHM_OK) r = shm_in_finalize_internal(stats, scratch, slots, batch * cout, hw, (double)eps, nt_out, beta_out, cout, (hipStream_t)stream);
+    r = conv_fwd_impl(x, x2, c1, ldx, ldx2, wk, bias, y, ldy, batch, hi, wi, cin, cout, ksize, stride, slope, dtype, stream, ex);
+    if (r == SHM_OK) r = shm_in_finalize_internal(stats, scratch, ex.stats_slots, batch * cout, hw, (double)eps, nt_out, beta_out, cout, (hipStream_t)stream);
     // "zero on entry, zero on return" also on the error path: a failed launch must not leave sums behind
     if (r != SHM_OK && scratch) (void)hipMemsetAsync(scratch, 0, (size_t)SHM_STATS_SLOTS * batch * cout * 2 * sizeof(double), (hipStream_t)stream);
     return r;
@@ -3041,57 +3024,48 @@ static void fill_s2_phases(TapGemmArgs& a, int pt, int pl) {
         }
 }
 
-extern "C" int shm_conv2d_dgrad(const void* dy, int lddy, const void* w, void* dx, void* dx2, int n1,
-                                int lddx, int lddx2, int batch, int hi, int wi, int cin, int cout,
-                                int ksize, int stride, int dtype, void* stream) {
+// 2x upsampling geometry: every pixel of the A map owns a 2 x 2 block of output pixels, one phase each
+static void up2_geometry(TapGemmArgs& a) {
+    a.hg = a.hi;
+    a.wg = a.wi;
+    a.ho = 2 * a.hi;
+    a.wo = 2 * a.wi;
+    a.is = 1;
+    a.os = 2;
+}
+
+// shm_conv2d_dgrad and shm_conv2d_dgrad_gsum
+static int conv_dgrad_impl(const void* dy, int lddy, const void* w, void* dx, void* dx2, int n1, int lddx, int lddx2, int batch, int hi, int wi, int cin,
+                           int cout, int ksize, int stride, int dtype, void* stream, ConvExtras& ex) {
     SHM_REQUIRE(ksize == 1 || ksize == 3, SHM_E_SHAPE, "shm_conv2d_dgrad: ksize %d not in {1,3}", ksize);
     SHM_REQUIRE(stride == 1 || (stride == 2 && ksize == 3), SHM_E_SHAPE, "shm_conv2d_dgrad: stride %d unsupported", stride);
     SHM_REQUIRE(dy && w && dx, SHM_E_SHAPE, "shm_conv2d_dgrad: null pointer");
     int ho, wo, pt, pl;
     shm_same_pad(hi, ksize, stride, &ho, &pt);
     shm_same_pad(wi, ksize, stride, &wo, &pl);
-    TapGemmArgs a{};
-    a.x = dy;
-    a.x2 = nullptr;
-    a.c1 = cout;
-    a.ldx = lddy;
-    a.w = w;            // HWIO [t][cin][cout] == [t][N=cin][K=cout]
-    a.bias = nullptr;
-    a.y = dx;
+    // HWIO [t][cin][cout] == [t][N=cin][K=cout]; no bias, no activation (slope 1)
+    TapGemmArgs a = fwd_args(dy, lddy, w, nullptr, dx, lddx, ho, wo, cout, cin, 1.f);
     a.y2 = dx2;
     a.n1 = dx2 ? n1 : cin;
-    a.ldy = lddx;
     a.ldy2 = lddx2;
-    a.hi = ho;
-    a.wi = wo;
-    a.K = cout;
-    a.ho = hi;
-    a.wo = wi;
-    a.nout = cin;
-    a.is = 1;
-    a.slope = 1.f;
     if (stride == 1) {
-        a.hg = hi;
-        a.wg = wi;
-        a.os = 1;
-        TapPhase& P = a.ph[0];
-        P.oph = P.opw = 0;
-        P.ntaps = ksize * ksize;
-        for (int kh = 0; kh < ksize; ++kh)
-            for (int kw = 0; kw < ksize; ++kw) {
-                int t = kh * ksize + kw;
-                P.dh[t] = pt - kh;   // dx[p] = sum_t dy[p - (k - pad)] * W_t^T
-                P.dw[t] = pl - kw;
-                P.widx[t] = t;
-            }
-        return launch_tapgemm(a, batch, 1, dtype, (hipStream_t)stream, "shm_conv2d_dgrad");
+        a.hg = a.ho = hi;
+        a.wg = a.wo = wi;
+        a.is = a.os = 1;
+        fill_taps(a.ph[0], ksize, pt, pl, -1);      // dx[p] = sum_t dy[p - (k - pad)] * W_t^T
+        return launch_tapgemm(a, batch, 1, dtype, (hipStream_t)stream, "shm_conv2d_dgrad", ex);
     }
     SHM_REQUIRE(hi % 2 == 0 && wi % 2 == 0, SHM_E_SHAPE, "shm_conv2d_dgrad: stride 2 needs even input size");
-    a.hg = hi / 2;
-    a.wg = wi / 2;
-    a.os = 2;
+    up2_geometry(a);            // (hi, wi even: 2 * ho == hi)
     fill_s2_phases(a, pt, pl);
-    return launch_tapgemm(a, batch, 4, dtype, (hipStream_t)stream, "shm_conv2d_dgrad");
+    return launch_tapgemm(a, batch, 4, dtype, (hipStream_t)stream, "shm_conv2d_dgrad", ex);
+}
+
+extern "C" int shm_conv2d_dgrad(const void* dy, int lddy, const void* w, void* dx, void* dx2, int n1,
+                                int lddx, int lddx2, int batch, int hi, int wi, int cin, int cout,
+                                int ksize, int stride, int dtype, void* stream) {
+    ConvExtras ex;
+    return conv_dgrad_impl(dy, lddy, w, dx, dx2, n1, lddx, lddx2, batch, hi, wi, cin, cout, ksize, stride, dtype, stream, ex);
 }
 
 extern "C" int shm_conv2d_transpose_fwd(const void* x, int ldx, const void* w, const float* bias, void* y,
@@ -3102,30 +3076,11 @@ extern "C" int shm_conv2d_transpose_fwd(const void* x, int ldx, const void* w, c
     int ho2, wo2, pt, pl;
     shm_same_pad(2 * hi, 3, 2, &ho2, &pt);
     shm_same_pad(2 * wi, 3, 2, &wo2, &pl);
-    TapGemmArgs a{};
-    a.x = x;
-    a.x2 = nullptr;
-    a.c1 = cin;
-    a.ldx = ldx;
-    a.w = w;            // Keras [t][cout][cin] == [t][N=cout][K=cin]
-    a.bias = bias;
-    a.y = y;
-    a.y2 = nullptr;
-    a.n1 = cout;
-    a.ldy = ldy;
-    a.hi = hi;
-    a.wi = wi;
-    a.K = cin;
-    a.hg = hi;
-    a.wg = wi;
-    a.ho = 2 * hi;
-    a.wo = 2 * wi;
-    a.nout = cout;
-    a.is = 1;
-    a.os = 2;
-    a.slope = slope;
+    TapGemmArgs a = fwd_args(x, ldx, w, bias, y, ldy, hi, wi, cin, cout, slope);       // Keras [t][cout][cin] == [t][N=cout][K=cin]
+    up2_geometry(a);
     fill_s2_phases(a, pt, pl);
-    return launch_tapgemm(a, batch, 4, dtype, (hipStream_t)stream, "shm_conv2d_transpose_fwd");
+    ConvExtras ex;
+    return launch_tapgemm(a, batch, 4, dtype, (hipStream_t)stream, "shm_conv2d_transpose_fwd", ex);
 }
 
 // Keras Conv2DTranspose(k=2, strides=2) (SpecSeg.py:63,69,75,81): non-overlapping, every output
@@ -3134,28 +3089,8 @@ extern "C" int shm_conv2d_transpose2x2_fwd(const void* x, int ldx, const void* w
                                            int ldy, int batch, int hi, int wi, int cin, int cout, float slope,
                                            int dtype, void* stream) {
     SHM_REQUIRE(x && w && y, SHM_E_SHAPE, "shm_conv2d_transpose2x2_fwd: null pointer");
-    TapGemmArgs a{};
-    a.x = x;
-    a.x2 = nullptr;
-    a.c1 = cin;
-    a.ldx = ldx;
-    a.w = w;            // Keras [2][2][cout][cin] == [t][N=cout][K=cin]
-    a.bias = bias;
-    a.y = y;
-    a.y2 = nullptr;
-    a.n1 = cout;
-    a.ldy = ldy;
-    a.hi = hi;
-    a.wi = wi;
-    a.K = cin;
-    a.hg = hi;
-    a.wg = wi;
-    a.ho = 2 * hi;
-    a.wo = 2 * wi;
-    a.nout = cout;
-    a.is = 1;
-    a.os = 2;
-    a.slope = slope;
+    TapGemmArgs a = fwd_args(x, ldx, w, bias, y, ldy, hi, wi, cin, cout, slope);       // Keras [2][2][cout][cin] == [t][N=cout][K=cin]
+    up2_geometry(a);
     for (int p = 0; p < 4; ++p) {
         TapPhase& P = a.ph[p];
         P.oph = p >> 1;
@@ -3164,7 +3099,8 @@ extern "C" int shm_conv2d_transpose2x2_fwd(const void* x, int ldx, const void* w
         P.dh[0] = P.dw[0] = 0;
         P.widx[0] = p;
     }
-    return launch_tapgemm(a, batch, 4, dtype, (hipStream_t)stream, "shm_conv2d_transpose2x2_fwd");
+    ConvExtras ex;
+    return launch_tapgemm(a, batch, 4, dtype, (hipStream_t)stream, "shm_conv2d_transpose2x2_fwd", ex);
 }
 
 // ------------------------------------------------------------------------------------
@@ -3173,8 +3109,6 @@ extern "C" int shm_conv2d_transpose2x2_fwd(const void* x, int ldx, const void* w
 // own over g and the stored activation (shm_in_bwd's reduce pass).  red = f64 [SHM_GSUM_SLOTS][batch][channels][2], zero on entry
 // (slot copies cut the per-address atomic chains; shm_in_bwd_apply sums and clears them).  Kernels that cannot take the sums in
 // their epilogue (launch_tapgemm_t lists which can) are followed by the stand-alone reduce pass: callers always get the sums.
-int shm_gsum_reduce_internal(const void* g, int ldg, const void* aux, int ldaux, double* red, int batch, int hw, int c, int dtype, hipStream_t st);
-
 extern "C" int shm_conv2d_dgrad_gsum(const void* dy, int lddy, const void* w, void* dx, void* dx2, int n1, int lddx, int lddx2, int batch, int hi,
                                      int wi, int cin, int cout, int ksize, int stride, const void* aux, int ldaux, double* red, const void* aux2,
                                      int ldaux2, double* red2, int dtype, void* stream) {
@@ -3182,12 +3116,11 @@ extern "C" int shm_conv2d_dgrad_gsum(const void* dy, int lddy, const void* w, vo
     SHM_REQUIRE((aux != nullptr) == (red != nullptr) && (aux2 != nullptr) == (red2 != nullptr), SHM_E_SHAPE, "%s: aux and red come in pairs", who);
     SHM_REQUIRE(red || red2, SHM_E_SHAPE, "%s: no sums requested (use shm_conv2d_dgrad)", who);
     SHM_REQUIRE(!red2 || dx2, SHM_E_SHAPE, "%s: sums of the second part need dx2", who);
-    g_gsum = GsumReq{{aux, aux2}, {ldaux, ldaux2}, {red, red2}};
-    int r = shm_conv2d_dgrad(dy, lddy, w, dx, dx2, n1, lddx, lddx2, batch, hi, wi, cin, cout, ksize, stride, dtype, stream);
-    const bool fused = g_gsum_fused;
-    g_gsum = GsumReq{};
-    g_gsum_fused = false;
-    if (r == SHM_OK && !fused) {
+    ConvExtras ex;
+    ex.gaux[0] = aux, ex.ldgaux[0] = ldaux, ex.gred[0] = red;
+    ex.gaux[1] = aux2, ex.ldgaux[1] = ldaux2, ex.gred[1] = red2;
+    int r = conv_dgrad_impl(dy, lddy, w, dx, dx2, n1, lddx, lddx2, batch, hi, wi, cin, cout, ksize, stride, dtype, stream, ex);
+    if (r == SHM_OK && !ex.gsum_fused) {
         const int c0 = dx2 ? n1 : cin;
         if (red) r = shm_gsum_reduce_internal(dx, lddx, aux, ldaux, red, batch, hi * wi, c0, dtype, (hipStream_t)stream);
         if (r == SHM_OK && red2) r = shm_gsum_reduce_internal(dx2, lddx2, aux2, ldaux2, red2, batch, hi * wi, cin - n1, dtype, (hipStream_t)stream);
@@ -3202,12 +3135,10 @@ extern "C" int shm_conv2d_fwd_gsum(const void* x, const void* x2, int c1, int ld
                                    double* red, int dtype, void* stream) {
     const char* who = "shm_conv2d_fwd_gsum";
     SHM_REQUIRE(aux && red, SHM_E_SHAPE, "%s: null aux / red", who);
-    g_gsum = GsumReq{{aux, nullptr}, {ldaux, 0}, {red, nullptr}};
-    int r = shm_conv2d_fwd(x, x2, c1, ldx, ldx2, wk, bias, y, ldy, batch, hi, wi, cin, cout, ksize, stride, slope, dtype, stream);
-    const bool fused = g_gsum_fused;
-    g_gsum = GsumReq{};
-    g_gsum_fused = false;
-    if (r == SHM_OK && !fused) {
+    ConvExtras ex;
+    ex.gaux[0] = aux, ex.ldgaux[0] = ldaux, ex.gred[0] = red;
+    int r = conv_fwd_impl(x, x2, c1, ldx, ldx2, wk, bias, y, ldy, batch, hi, wi, cin, cout, ksize, stride, slope, dtype, stream, ex);
+    if (r == SHM_OK && !ex.gsum_fused) {
         int ho, wo, pt;
         shm_same_pad(hi, ksize, stride, &ho, &pt);
         shm_same_pad(wi, ksize, stride, &wo, &pt);

@@ -1439,13 +1439,6 @@ extern "C" size_t shm_conv2d_wgrad_workspace(int batch, int ho, int wo, int cin,
     return (size_t)ns * ksize * ksize * cin * cout * sizeof(float);
 }
 
-// norm request of shm_conv2d_wgrad_norm around its launch (WgradHaloArgs::nt); query = shm_conv2d_wgrad_norm_supported's dry run
-struct WNormReq {
-    const float* nt;
-    int part, c, mode;
-    bool query, query_ok;
-};
-
 // SHM_NORM_SCALED: a block's patches must lie in one sample -- the largest divisor of the patches per image that does not exceed
 // the split the automatic choice would take
 static int wgrad_norm_aligned_pps(int pps, int ppi) {
@@ -1454,18 +1447,19 @@ static int wgrad_norm_aligned_pps(int pps, int ppi) {
     while (ppi % d) --d;
     return d;
 }
-static thread_local WNormReq g_wnorm = {};
 
-// Phase 1 of shm_conv2d_wgrad: the MFMA kernel; *nsplit_out receives the number of partial slabs written.
-extern "C" int shm_conv2d_wgrad_partial(const void* x, const void* x2, int c1, int ldx, int ldx2, const void* dy,
-                                        int lddy, int batch, int hi, int wi, int cin, int cin_ld, int cout,
-                                        int ksize, int stride, void* workspace, size_t ws_bytes, int dtype,
-                                        int* nsplit_out, void* stream) {
+// Phase 1 of shm_conv2d_wgrad: the MFMA kernel; *nsplit_out receives the number of partial slabs written.  nm: the norm request of
+// shm_conv2d_wgrad_norm (WgradHaloArgs::nt).  dry_ok non-null = shm_conv2d_wgrad_norm_supported's dry run: the variant choice as if a
+// SHM_NORM_EXACT request for source nm.part with nm.c channels had come, *dry_ok = that kernel can normalise its source in LDS, nothing
+// is launched.  A dry run has no operands and no workspace; a second source is announced by a non-null x2, which nobody dereferences.
+static int wgrad_partial_impl(const void* x, const void* x2, int c1, int ldx, int ldx2, const void* dy, int lddy, int batch, int hi, int wi, int cin,
+                              int cin_ld, int cout, int ksize, int stride, void* workspace, size_t ws_bytes, int dtype, int* nsplit_out, void* stream,
+                              const ShmNormReq& nm, bool* dry_ok) {
     SHM_REQUIRE(dtype == SHM_F32 || dtype == SHM_BF16, SHM_E_DTYPE, "shm_conv2d_wgrad: dtype %d not in {SHM_F32, SHM_BF16}", dtype);
     const int esz = dtype == SHM_BF16 ? 2 : 4, vec = 16 / esz;      // 16-byte loads: 4 floats / 8 bf16
     SHM_REQUIRE(ksize == 1 || ksize == 3, SHM_E_SHAPE, "shm_conv2d_wgrad: ksize %d not in {1,3}", ksize);
     SHM_REQUIRE(stride == 1 || stride == 2, SHM_E_SHAPE, "shm_conv2d_wgrad: stride %d not in {1,2}", stride);
-    SHM_REQUIRE(x && dy && workspace, SHM_E_SHAPE, "shm_conv2d_wgrad: null pointer");
+    SHM_REQUIRE(dry_ok || (x && dy && workspace), SHM_E_SHAPE, "shm_conv2d_wgrad: null pointer");
     SHM_REQUIRE(cin_ld % vec == 0 && cin_ld >= cin && cout % vec == 0, SHM_E_SHAPE,
                 "shm_conv2d_wgrad: cin_ld %d / cout %d must be multiples of %d", cin_ld, cout, vec);
     SHM_REQUIRE(ldx % vec == 0 && lddy % vec == 0 && (!x2 || (ldx2 % vec == 0 && c1 % vec == 0)), SHM_E_SHAPE,
@@ -1500,7 +1494,7 @@ extern "C" int shm_conv2d_wgrad_partial(const void* x, const void* x2, int c1, i
     a.M = batch * ho * wo;
     int ns = wgrad_splits(batch, ho, wo, cin, cout, esz);
     size_t need = (size_t)ns * a.ntaps * cin * cout * sizeof(float);
-    SHM_REQUIRE(ws_bytes >= need, SHM_E_WORKSPACE, "shm_conv2d_wgrad: workspace %zu < %zu bytes", ws_bytes, need);
+    SHM_REQUIRE(dry_ok || ws_bytes >= need, SHM_E_WORKSPACE, "shm_conv2d_wgrad: workspace %zu < %zu bytes", ws_bytes, need);
     {
         const size_t lim = 0xfffffff0ull;
         size_t xb = (size_t)batch * hi * wi * ldx * esz, x2b = x2 ? (size_t)batch * hi * wi * ldx2 * esz : 0;
@@ -1516,7 +1510,7 @@ extern "C" int shm_conv2d_wgrad_partial(const void* x, const void* x2, int c1, i
     a.pix_per_split = pps;
     hipStream_t st = (hipStream_t)stream;
     // the 3-channel stride-2 first layer on the compact image layout (conv_rgb.hip); wgrad.variant 1 keeps the generic kernel
-    if (ksize == 3 && stride == 2 && !x2 && ldx * esz == 16 && !g_wnorm.nt && !g_wnorm.query && shm_tune(SHM_TUNE_WGRAD_VARIANT) != 1) {
+    if (ksize == 3 && stride == 2 && !x2 && ldx * esz == 16 && !nm.nt && !dry_ok && shm_tune(SHM_TUNE_WGRAD_VARIANT) != 1) {
         const int r = shm_rgb_s2_wgrad_launch(x, ldx, dy, lddy, (float*)workspace, ws_bytes, batch, hi, wi, cin, cout, a.xbytes, a.dybytes, dtype, nsplit_out, st);
         if (r < 0) return r;
         if (r == 1) return SHM_OK;
@@ -1533,12 +1527,12 @@ extern "C" int shm_conv2d_wgrad_partial(const void* x, const void* x2, int c1, i
     const bool halo2_ok = ksize == 3 && stride == 2 && pt == 0 && pl == 0 && hi % 2 == 0 && wi % 2 == 0 && wo % 8 == 0 && ho % 2 == 0 && !straddle &&
                           !no_halo && wv != 3 && !(thin_ok && dtype == SHM_F32);
     // norm: the halo-image kernels normalise their x halo in LDS (a block's 64 input channels lie in one source: no straddle)
-    const bool want_nm = g_wnorm.nt != nullptr;
-    if (want_nm || g_wnorm.query) {
-        const int pc = x2 ? (g_wnorm.part ? cin_ld - c1 : c1) : cin_ld;
-        const bool ok = want_nm && halo_ok && (dtype == SHM_BF16 || !thin_ok) && g_wnorm.c == pc && (g_wnorm.part == 0 || x2 != nullptr) && pc % vec == 0;
-        if (g_wnorm.query) {
-            g_wnorm.query_ok = ok;
+    const bool want_nm = nm.nt != nullptr || dry_ok;
+    if (want_nm) {
+        const int pc = x2 ? (nm.part ? cin_ld - c1 : c1) : cin_ld;
+        const bool ok = halo_ok && (dtype == SHM_BF16 || !thin_ok) && nm.c == pc && (nm.part == 0 || x2 != nullptr) && pc % vec == 0;
+        if (dry_ok) {
+            *dry_ok = ok;
             return SHM_OK;
         }
         SHM_REQUIRE(ok, SHM_E_SHAPE,
@@ -1633,18 +1627,18 @@ extern "C" int shm_conv2d_wgrad_partial(const void* x, const void* x2, int c1, i
         hgs.npatch = batch * (hi / rows) * (wi / 16);
         int nsh = ns < hgs.npatch ? ns : hgs.npatch;
         hgs.patches_per_split = shm_cdiv(hgs.npatch, nsh);
-        if (want_nm && g_wnorm.mode) hgs.patches_per_split = wgrad_norm_aligned_pps(hgs.patches_per_split, (hi / rows) * (wi / 16));
+        if (want_nm && nm.mode) hgs.patches_per_split = wgrad_norm_aligned_pps(hgs.patches_per_split, (hi / rows) * (wi / 16));
         nsh = shm_cdiv(hgs.npatch, hgs.patches_per_split);
         SHM_REQUIRE(ws_bytes >= (size_t)nsh * 9 * cin * cout * sizeof(float), SHM_E_WORKSPACE,
                     "shm_conv2d_wgrad: workspace %zu < %zu bytes (SHM_NORM_SCALED: shm_conv2d_wgrad_norm_workspace)", ws_bytes, (size_t)nsh * 9 * cin * cout * sizeof(float));
         hgs.xbytes = a.xbytes;
         hgs.x2bytes = a.x2bytes;
         hgs.dybytes = a.dybytes;
-        hgs.nt = g_wnorm.nt;
-        hgs.ntpart = g_wnorm.part;
-        hgs.ntc = g_wnorm.c;
+        hgs.nt = nm.nt;
+        hgs.ntpart = nm.part;
+        hgs.ntc = nm.c;
         ns = nsh;
-        const int nmode = want_nm ? 1 + g_wnorm.mode : 0;
+        const int nmode = want_nm ? 1 + nm.mode : 0;
         const dim3 gridb(shm_cdiv(cin, 64), shm_cdiv(cout, 64), nsh);
         if (rows == 4) {
             constexpr unsigned kLds = 3u * (6 * 20 + 4 * 16) * 128u;      // 69 KiB
@@ -1764,7 +1758,7 @@ extern "C" int shm_conv2d_wgrad_partial(const void* x, const void* x2, int c1, i
         hgs.npatch = batch * (hi / 2) * (wi / 16);
         int nsh = ns < hgs.npatch ? ns : hgs.npatch;
         hgs.patches_per_split = shm_cdiv(hgs.npatch, nsh);
-        if (want_nm && g_wnorm.mode) hgs.patches_per_split = wgrad_norm_aligned_pps(hgs.patches_per_split, (hi / 2) * (wi / 16));
+        if (want_nm && nm.mode) hgs.patches_per_split = wgrad_norm_aligned_pps(hgs.patches_per_split, (hi / 2) * (wi / 16));
         nsh = shm_cdiv(hgs.npatch, hgs.patches_per_split);
         SHM_REQUIRE(ws_bytes >= (size_t)nsh * 9 * cin * cout * sizeof(float), SHM_E_WORKSPACE,
                     "shm_conv2d_wgrad: workspace %zu < %zu bytes (SHM_NORM_SCALED: shm_conv2d_wgrad_norm_workspace)", ws_bytes, (size_t)nsh * 9 * cin * cout * sizeof(float));
@@ -1779,10 +1773,10 @@ extern "C" int shm_conv2d_wgrad_partial(const void* x, const void* x2, int c1, i
             shm_set_last_kernel("wgrad_halo_thin_kernel<3, 1>");
         } else {
         dim3 gridh(shm_cdiv(cin, 64), shm_cdiv(cout, 64), nsh);
-        hgs.nt = g_wnorm.nt;
-        hgs.ntpart = g_wnorm.part;
-        hgs.ntc = g_wnorm.c;
-        if ((!want_nm || g_wnorm.mode == 0) && shm_tune(SHM_TUNE_WGRAD_F32_SPLIT) == 1) {        // "wgrad.f32_split": conv_wgrad_x3.hip (plain and SHM_NORM_EXACT sources)
+        hgs.nt = nm.nt;
+        hgs.ntpart = nm.part;
+        hgs.ntc = nm.c;
+        if ((!want_nm || nm.mode == 0) && shm_tune(SHM_TUNE_WGRAD_F32_SPLIT) == 1) {        // "wgrad.f32_split": conv_wgrad_x3.hip (plain and SHM_NORM_EXACT sources)
             // stages of four pixel rows where the map allows ("wgrad.bf16_rows" = 2 keeps two): the patches and the split are re-cut for them
             // (the normalising form keeps two rows: with four its 24 table values spill)
             const int rows = (hi % 4 == 0 && shm_tune(SHM_TUNE_WGRAD_BF16_ROWS) != 2 && !want_nm) ? 4 : 2;
@@ -1797,13 +1791,13 @@ extern "C" int shm_conv2d_wgrad_partial(const void* x, const void* x2, int c1, i
             const int rc = shm_wgrad_x3_launch(hgs, cin, cout, nsh, rows, st);
             if (rc != SHM_OK) return rc;
         } else {
-        if (want_nm && g_wnorm.mode)
+        if (want_nm && nm.mode)
             hipLaunchKernelGGL(wgrad_halo_kernel<2>, gridh, dim3(256), 0, st, hgs);
         else if (want_nm)
             hipLaunchKernelGGL(wgrad_halo_kernel<1>, gridh, dim3(256), 0, st, hgs);
         else
             hipLaunchKernelGGL(wgrad_halo_kernel<0>, gridh, dim3(256), 0, st, hgs);
-        shm_set_last_kernel(want_nm ? (g_wnorm.mode ? "wgrad_halo_kernel<2>" : "wgrad_halo_kernel<1>") : "wgrad_halo_kernel");
+        shm_set_last_kernel(want_nm ? (nm.mode ? "wgrad_halo_kernel<2>" : "wgrad_halo_kernel<1>") : "wgrad_halo_kernel");
         }
         }
     } else {
@@ -1846,19 +1840,11 @@ extern "C" int shm_conv2d_wgrad_norm_supported(int batch, int hi, int wi, int ci
     if (norm_part != 0 && norm_part != 1) return 0;
     const bool two = c1 > 0 && c1 < cin_ld;
     if (norm_part == 1 && !two) return 0;
-    static const __attribute__((aligned(256))) char dummy[256] = {};
-    const size_t ws = shm_conv2d_wgrad_workspace(batch, hi, wi, cin, cout, ksize) * 2;
-    g_wnorm.nt = (const float*)dummy;
-    g_wnorm.part = norm_part;
-    g_wnorm.c = two ? (norm_part ? cin_ld - c1 : c1) : cin_ld;
-    g_wnorm.query = true;
-    g_wnorm.query_ok = false;
-    int ns = 0;
-    const int r = shm_conv2d_wgrad_partial(dummy, two ? dummy : nullptr, two ? c1 : 0, two ? c1 : cin_ld, two ? cin_ld - c1 : 0, dummy, cout, batch, hi, wi, cin,
-                                           cin_ld, cout, ksize, stride, (void*)dummy, ws, dtype, &ns, nullptr);
-    const bool ok = r == SHM_OK && g_wnorm.query_ok;
-    g_wnorm = WNormReq{};
-    return ok ? 1 : 0;
+    const ShmNormReq nm{nullptr, norm_part, two ? (norm_part ? cin_ld - c1 : c1) : cin_ld, SHM_NORM_EXACT};
+    bool ok = false;
+    const int r = wgrad_partial_impl(nullptr, two ? &nm : nullptr, two ? c1 : 0, two ? c1 : cin_ld, two ? cin_ld - c1 : 0, nullptr, cout, batch, hi, wi, cin, cin_ld,
+                                     cout, ksize, stride, nullptr, 0, dtype, nullptr, nullptr, nm, &ok);
+    return r == SHM_OK && ok ? 1 : 0;
 }
 
 // Workspace of shm_conv2d_wgrad_norm(SHM_NORM_SCALED): the splits are cut on sample boundaries, which can take more slabs than
@@ -1919,22 +1905,21 @@ extern "C" int shm_conv2d_wgrad_norm_finish(float* dw, const float* nt, const do
     return SHM_OK;
 }
 
+extern "C" int shm_conv2d_wgrad_partial(const void* x, const void* x2, int c1, int ldx, int ldx2, const void* dy,
+                                        int lddy, int batch, int hi, int wi, int cin, int cin_ld, int cout,
+                                        int ksize, int stride, void* workspace, size_t ws_bytes, int dtype,
+                                        int* nsplit_out, void* stream) {
+    return wgrad_partial_impl(x, x2, c1, ldx, ldx2, dy, lddy, batch, hi, wi, cin, cin_ld, cout, ksize, stride, workspace, ws_bytes, dtype, nsplit_out, stream,
+                              ShmNormReq{}, nullptr);
+}
+
 extern "C" int shm_conv2d_wgrad_partial_norm(const void* x, const void* x2, int c1, int ldx, int ldx2, const float* nt_x, const float* nt_x2, int norm_mode,
                                              const void* dy, int lddy, int batch, int hi, int wi, int cin, int cin_ld, int cout, int ksize, int stride,
                                              void* workspace, size_t ws_bytes, int dtype, int* nsplit_out, void* stream) {
-    SHM_REQUIRE(!(nt_x && nt_x2), SHM_E_SHAPE, "shm_conv2d_wgrad_norm: at most one source can be normalised on the fly");
-    SHM_REQUIRE(!nt_x2 || x2, SHM_E_SHAPE, "shm_conv2d_wgrad_norm: nt_x2 without a second source");
-    SHM_REQUIRE(norm_mode == SHM_NORM_EXACT || norm_mode == SHM_NORM_SCALED, SHM_E_SHAPE, "shm_conv2d_wgrad_norm: norm_mode %d", norm_mode);
-    if (nt_x || nt_x2) {
-        g_wnorm.nt = nt_x ? nt_x : nt_x2;
-        g_wnorm.part = nt_x ? 0 : 1;
-        g_wnorm.c = x2 ? (nt_x ? c1 : cin_ld - c1) : cin_ld;
-        g_wnorm.mode = norm_mode;
-    }
-    const int r = shm_conv2d_wgrad_partial(x, x2, c1, ldx, ldx2, dy, lddy, batch, hi, wi, cin, cin_ld, cout, ksize, stride, workspace, ws_bytes, dtype,
-                                           nsplit_out, stream);
-    g_wnorm = WNormReq{};
-    return r;
+    ShmNormReq nm;
+    if (const int r = shm_norm_request(&nm, "shm_conv2d_wgrad_norm", nt_x, nt_x2, norm_mode, x2, c1, cin_ld)) return r;
+    return wgrad_partial_impl(x, x2, c1, ldx, ldx2, dy, lddy, batch, hi, wi, cin, cin_ld, cout, ksize, stride, workspace, ws_bytes, dtype, nsplit_out, stream, nm,
+                              nullptr);
 }
 
 // shm_conv2d_wgrad on a source that is the UN-normalised activation of an InstanceNorm block (nt_x / nt_x2: that block's table, at
@@ -1942,29 +1927,20 @@ extern "C" int shm_conv2d_wgrad_partial_norm(const void* x, const void* x2, int 
 extern "C" int shm_conv2d_wgrad_norm(const void* x, const void* x2, int c1, int ldx, int ldx2, const float* nt_x, const float* nt_x2, int norm_mode,
                                      const void* dy, int lddy, float* dw, int batch, int hi, int wi, int cin, int cin_ld, int cout, int ksize, int stride,
                                      int accumulate, void* workspace, size_t ws_bytes, int dtype, void* stream) {
-    SHM_REQUIRE(!(nt_x && nt_x2), SHM_E_SHAPE, "shm_conv2d_wgrad_norm: at most one source can be normalised on the fly");
-    SHM_REQUIRE(!nt_x2 || x2, SHM_E_SHAPE, "shm_conv2d_wgrad_norm: nt_x2 without a second source");
-    SHM_REQUIRE(norm_mode == SHM_NORM_EXACT || norm_mode == SHM_NORM_SCALED, SHM_E_SHAPE, "shm_conv2d_wgrad_norm: norm_mode %d", norm_mode);
-    if (nt_x || nt_x2) {
-        g_wnorm.nt = nt_x ? nt_x : nt_x2;
-        g_wnorm.part = nt_x ? 0 : 1;
-        g_wnorm.c = x2 ? (nt_x ? c1 : cin_ld - c1) : cin_ld;
-        g_wnorm.mode = norm_mode;
-    }
-    const int r = shm_conv2d_wgrad(x, x2, c1, ldx, ldx2, dy, lddy, dw, batch, hi, wi, cin, cin_ld, cout, ksize, stride, accumulate, workspace, ws_bytes, dtype,
-                                   stream);
-    g_wnorm = WNormReq{};
-    return r;
+    ShmNormReq nm;
+    if (const int r = shm_norm_request(&nm, "shm_conv2d_wgrad_norm", nt_x, nt_x2, norm_mode, x2, c1, cin_ld)) return r;
+    SHM_REQUIRE(dw, SHM_E_SHAPE, "shm_conv2d_wgrad: null pointer");
+    int ns = 0;
+    const int r = wgrad_partial_impl(x, x2, c1, ldx, ldx2, dy, lddy, batch, hi, wi, cin, cin_ld, cout, ksize, stride, workspace, ws_bytes, dtype, &ns, stream, nm,
+                                     nullptr);
+    if (r) return r;
+    return shm_conv2d_wgrad_reduce(workspace, dw, (size_t)ksize * ksize * cin * cout, ns, accumulate, stream);
 }
 
 extern "C" int shm_conv2d_wgrad(const void* x, const void* x2, int c1, int ldx, int ldx2, const void* dy,
                                 int lddy, float* dw, int batch, int hi, int wi, int cin, int cin_ld,
                                 int cout, int ksize, int stride, int accumulate, void* workspace,
                                 size_t ws_bytes, int dtype, void* stream) {
-    SHM_REQUIRE(dw, SHM_E_SHAPE, "shm_conv2d_wgrad: null pointer");
-    int ns = 0;
-    int r = shm_conv2d_wgrad_partial(x, x2, c1, ldx, ldx2, dy, lddy, batch, hi, wi, cin, cin_ld, cout, ksize, stride, workspace, ws_bytes, dtype,
-                                     &ns, stream);
-    if (r) return r;
-    return shm_conv2d_wgrad_reduce(workspace, dw, (size_t)ksize * ksize * cin * cout, ns, accumulate, stream);
+    return shm_conv2d_wgrad_norm(x, x2, c1, ldx, ldx2, nullptr, nullptr, SHM_NORM_EXACT, dy, lddy, dw, batch, hi, wi, cin, cin_ld, cout, ksize, stride, accumulate,
+                                 workspace, ws_bytes, dtype, stream);
 }

@@ -104,3 +104,42 @@ def test_new_entry_points_check_their_arguments():
     assert rc == -1 and b"outside" in L.shm_last_error()
     rc = L.shm_in_norm_table(None, p, p, 1, 64, None)
     assert rc == -1 and b"null pointer" in L.shm_last_error()
+
+
+def test_a_rejected_call_leaves_no_request_behind():
+    """The norm / gsum requests travel as arguments: an entry point that accepted one and then failed its argument checks (before any
+    launch) reports its error and changes nothing for the calls after it -- the queries answer as they did before."""
+    L = _lib.lib()
+    buf = (ctypes.c_char * 4096)()
+    p = ctypes.addressof(buf)
+    fwd_cases = [(40, 128, 128, 128, 0, 128, 3, 1, 0, F32), (40, 256, 256, 128, 64, 64, 3, 1, 1, BF16), (40, 256, 256, 64, 0, 128, 3, 2, 0, F32),
+                 (2, 32, 32, 128, 0, 128, 3, 1, 0, F32), (40, 16, 16, 512, 0, 512, 1, 1, 0, BF16)]
+    wg_cases = [(40, 256, 256, 64, 64, 0, 64, 3, 1, 0, F32), (40, 128, 128, 256, 256, 128, 128, 3, 1, 1, BF16), (40, 256, 256, 64, 64, 0, 128, 3, 2, 0, F32),
+                (8, 64, 64, 10, 16, 0, 64, 3, 1, 0, F32)]
+
+    def answers():
+        return [fwd_ok(*c) for c in fwd_cases] + [wg_ok(*c) for c in wg_cases]
+
+    before = answers()
+    assert before == [True, True, False, False, False, True, True, False, False]
+    # a valid table for the only source, then a kernel size the convolution does not have (4 x 4 map: the separate-statistics path)
+    for mode in (0, 1):
+        rc = L.shm_conv2d_in_fwd_norm(p, None, 0, 64, 0, p, None, mode, p, p, p, 64, 1, 4, 4, 64, 64, 5, 1, 0.2, p, None, 1e-6, None, None, F32, None)
+        assert rc == -1 and b"ksize 5" in L.shm_last_error()
+        assert answers() == before
+    # sums of both output parts requested, then a stride the input gradient does not have
+    rc = L.shm_conv2d_dgrad_gsum(p, 64, p, p, p, 32, 32, 32, 1, 16, 16, 64, 64, 3, 3, p, 32, p, p, 32, p, F32, None)
+    assert rc == -1 and b"stride 3" in L.shm_last_error()
+    assert answers() == before
+    rc = L.shm_conv2d_fwd_gsum(p, None, 0, 64, 0, p, None, p, 64, 1, 16, 16, 64, 64, 2, 1, 1.0, p, 64, p, F32, None)
+    assert rc == -1 and b"ksize 2" in L.shm_last_error()
+    assert answers() == before
+    # a table for the second source, then a pitch that is not a multiple of 16 bytes
+    for mode in (0, 1):
+        rc = L.shm_conv2d_wgrad_norm(p, p, 64, 66, 64, None, p, mode, p, 64, p, 1, 16, 16, 128, 128, 64, 3, 1, 0, p, 4096, F32, None)
+        assert rc == -1 and b"pitches must be multiples of 4" in L.shm_last_error()
+        assert answers() == before
+    ns = ctypes.c_int(0)
+    rc = L.shm_conv2d_wgrad_partial_norm(p, None, 0, 64, 0, p, None, 1, p, 60, 1, 16, 16, 64, 64, 64, 3, 1, p, 4096, BF16, ctypes.byref(ns), None)
+    assert rc == -1 and b"pitches must be multiples of 8" in L.shm_last_error()
+    assert answers() == before

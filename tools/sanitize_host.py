@@ -35,7 +35,7 @@ def main():
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     san = ["-fsanitize=address,undefined", "-fno-gpu-sanitize", "-fno-sanitize-recover=undefined", "-shared-libsan", "-fno-omit-frame-pointer", "-g"]
     cflags = [f for f in _lib.HIPCC_FLAGS if f not in ("-shared", "-O3")] + ["-O1"] + san
-    shared = max(p.stat().st_mtime for p in [_lib.CSRC / h for h in ("common.h", "ablate.h", "tapgemm.h", "wgrad.h", "x3split.h")] + [_lib.HEADER])
+    shared = max(p.stat().st_mtime for p in _lib.SHARED_HEADERS)
 
     def cc(name):
         src, obj = _lib.CSRC / name, out / (Path(name).stem + ".o")

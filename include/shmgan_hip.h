@@ -81,7 +81,7 @@ const char* shm_last_kernel(void);
  *                               Opt-in: bench.py --dtype f32x3
  *   "conv.f32_split"            fp32 3x3 unit-stride forward / input gradient: 1 = six bf16 MFMA products of exact three-plane splits where
  *                               the shape fits (tapgemm_halo_x3_kernel), 0 (default) = exact-fp32 MFMA.  Opt-in
- *   "elem.fused_bwd"            bf16 shm_in_bwd: 1 (default) = the one-pass form where shm_in_bwd_fused_scratch was given and the shape fits, 0 = two passes
+ *   "elem.fused_bwd"            bf16 shm_in_bwd: 1 (default) = the one-pass form where fused_scratch was given and the shape fits, 0 = two passes
  *   "wgrad.bf16_wide"           bf16 weight gradient, the eight-wave 64 ci x 128 co block (cout >= 128): 0 automatic (= 2), 1 never, 2 at stride 2 only,
  *                               3 at unit stride only, 4 both
  *   "stats.fusion"              1 InstanceNorm statistics in the conv epilogue (default), 0 separate pass
@@ -244,8 +244,7 @@ int shm_conv2d_norm_supported(int batch, int hi, int wi, int cin, int c1, int co
  * inv * sum a_ext * dz (a_ext = a inside the image, `ring` outside) per sample -- the workspace must then hold
  * shm_conv2d_wgrad_norm_workspace() bytes (splits on sample boundaries) -- and the caller completes the gradient with
  * shm_conv2d_wgrad_norm_finish: dw[tap][part_lo + k][co] += sum_n (beta[k] - mean_n[k] * inv_n[k]) * dzsum[n][co], dzsum = float64
- * [batch][cout] per-sample channel sums of dz = what shm_in_bwd_keep_dz_sums(dst) makes the NEXT shm_in_bwd / shm_in_bwd_apply /
- * shm_in_bwd_rank1 call of the thread copy out of its bias-gradient staging (one-shot; that call must take a bias gradient). */
+ * [batch][cout] per-sample channel sums of dz = the `dz_sums` output of shm_in_bwd / shm_in_bwd_apply / shm_in_bwd_rank1. */
 int shm_conv2d_wgrad_norm(const void* x, const void* x2, int c1, int ldx, int ldx2, const float* nt_x, const float* nt_x2,
                           int norm_mode, const void* dy, int lddy, float* dw, int batch, int hi, int wi, int cin, int cin_ld, int cout,
                           int ksize, int stride, int accumulate, void* workspace, size_t ws_bytes, int dtype, void* stream);
@@ -257,12 +256,11 @@ int shm_conv2d_wgrad_norm_supported(int batch, int hi, int wi, int cin, int cin_
 size_t shm_conv2d_wgrad_norm_workspace(int batch, int hi, int wi, int cin, int cout, int ksize, int dtype);
 int shm_conv2d_wgrad_norm_finish(float* dw, const float* nt, const double* dzsum, int batch, int c, int part_lo, int cin, int cout,
                                  int ksize, void* stream);
-int shm_in_bwd_keep_dz_sums(double* dst);
 /* One-pass bf16 form of shm_in_bwd (round 5, in_bwd_fused8_kernel: a block keeps its slice of g1 / g2 / a in registers between the reduce and
- * the apply phase, the blocks of a sample meet at a per-sample barrier; 3 tensor passes over HBM instead of 5).  The NEXT shm_in_bwd call of this
- * thread may use `scratch` = f64 [n_doubles], n_doubles >= SHM_IN_BWD_FUSED_DOUBLES(batch, h * w, c), zero on entry and zero again on return
- * (outside the per-block partial rows at its front, which every launch rewrites in full and which may hold anything).
- * One-shot (NULL disarms).  Taken for dtype SHM_BF16, c in {8, 16, 32} or a multiple of 64 up to 1024, h * w a multiple of the
+ * the apply phase, the blocks of a sample meet at a per-sample barrier; 3 tensor passes over HBM instead of 5).  shm_in_bwd may take it when
+ * it is given `fused_scratch` = f64 [fused_doubles], fused_doubles >= SHM_IN_BWD_FUSED_DOUBLES(batch, h * w, c), zero on entry and zero again on
+ * return (outside the per-block partial rows at its front, which every launch rewrites in full and which may hold anything).
+ * Taken for dtype SHM_BF16, c in {8, 16, 32} or a multiple of 64 up to 1024, h * w a multiple of the
  * 16384 / min(c, 64) pixel slice and at most 256 slices per map ("elem.fused_max_slices"; with a pooled gradient g2: c a multiple of 64 and
  * whole tiles of (256 / Wt) rows x Wt = min(w, 128) columns), tuning
  * "elem.fused_bwd" = 1 (default); every other call runs the two passes.  No float atomics: the sums are added in block order (bitwise
@@ -271,11 +269,10 @@ int shm_in_bwd_keep_dz_sums(double* dst);
 #define SHM_IN_BWD_FUSED_DOUBLES(batch, hw, c)                                                                                      \
     (((size_t)(batch) * ((size_t)(hw) * SHM_IN_BWD_FUSED_CB(c) / 16384) * 3 * (size_t)(c) + 1) / 2 + (size_t)(batch) * (size_t)(c) + \
      (size_t)(batch) * ((size_t)(c) / SHM_IN_BWD_FUSED_CB(c)) * 288 + 1)
-int shm_in_bwd_fused_scratch(double* scratch, size_t n_doubles);
 /* The one-pass form's barrier needs every block of a group resident at once.  The launcher takes it only when TWICE the group's blocks fit the
  * current device (its CU count x hipOccupancyMaxActiveBlocksPerMultiprocessor of the kernel, queried once: a partitioned or smaller part falls
  * back to the two passes), and a barrier that still waits ~1 s gives up instead of hanging: the launch then completes with wrong means, sets the
- * last u32 of `scratch` and the caller's ABORT WORDS:
+ * last u32 of `fused_scratch` and the caller's ABORT WORDS:
  *   dev_word   u32 in device memory, OR-ed to non-zero.  shm_adam_clip reads it ON THE DEVICE and applies nothing while it is set: gradients
  *              built on unfinished sums never reach the weights, however far the host has run ahead of the stream;
  *   host_word  u32 in mapped (pinned) host memory, set to 1: the host sees it without synchronising.
@@ -319,11 +316,12 @@ int shm_in_apply_pool(const void* a, int lda, const double* stats, const float* 
  *   d_out = g1 + 0.25 * g2[h/2][w/2]   (g2 = gradient of AveragePooling2D(2,2), may be NULL)
  *   dz = lrelu'(a) * inv * (d_out - mean(d_out) - xhat * mean(d_out * xhat))
  * red = f64 scratch [batch*c*3], ZERO on entry and zero again on return; dbias = f64 accumulator [c]
- * (NOT zeroed, may be NULL).
+ * (NOT zeroed, may be NULL).  dz_sums (may be NULL; needs dbias) = f64 [batch][c], receives the per-sample channel sums of dz
+ * staged on the way to dbias.  fused_scratch / fused_doubles (may be NULL / 0 = two passes): scratch of the one-pass bf16 form, above.
  * g1, g2 are [G] tensors; a and dz are activation-typed. */
 int shm_in_bwd(const void* g1, int ldg1, const void* g2, int ldg2, const void* a, int lda,
-               const double* stats, double* red, void* dz, int lddz, double* dbias, int batch,
-               int h, int w, int c, float slope, int dtype, void* stream);
+               const double* stats, double* red, void* dz, int lddz, double* dbias, double* dz_sums,
+               double* fused_scratch, size_t fused_doubles, int batch, int h, int w, int c, float slope, int dtype, void* stream);
 
 /* ---- the fused block's backward: InstanceNorm sums in the producing epilogue ("gsum") -------------------------------------
  * The IN backward needs, per (sample, channel), sum(d_out) and sum(d_out * xhat) before it can write dz: shm_in_bwd collects
@@ -344,7 +342,7 @@ int shm_in_bwd(const void* g1, int ldg1, const void* g2, int ldg2, const void* a
  *       the fused four-phase kernel, odd alignments, tiny maps) is the library's business: red is complete on return.
  *   shm_in_bwd_apply = shm_in_bwd without its reduce pass: d_out = g1 + 0.25 * unpool(g2); red = sums of g1 against a,
  *       redp = sums of g2 against the pooled normalised tensor (NULL iff g2 is NULL; needs beta [c]); dstage = f64 [batch*c]
- *       staging of the bias gradient (required with dbias).  red / redp / dstage are zero again on return. */
+ *       staging of the bias gradient (required with dbias).  red / redp / dstage are zero again on return.  dz_sums as for shm_in_bwd. */
 #define SHM_GSUM_SLOTS 8
 int shm_conv2d_dgrad_gsum(const void* dy, int lddy, const void* w, void* dx, void* dx2, int n1, int lddx, int lddx2, int batch,
                           int hi, int wi, int cin, int cout, int ksize, int stride, const void* aux, int ldaux, double* red,
@@ -354,7 +352,7 @@ int shm_conv2d_fwd_gsum(const void* x, const void* x2, int c1, int ldx, int ldx2
                         const void* aux, int ldaux, double* red, int dtype, void* stream);
 int shm_in_bwd_apply(const void* g1, int ldg1, const void* g2, int ldg2, const void* a, int lda, const double* stats,
                      const float* beta, double* red, double* redp, double* dstage, void* dz, int lddz, double* dbias,
-                     int batch, int h, int w, int c, float slope, int dtype, void* stream);
+                     double* dz_sums, int batch, int h, int w, int c, float slope, int dtype, void* stream);
 
 /* Input gradient of a FIRST layer when only its sum over a set of input channels is needed (the step never
  * uses more: d genY sums the cyclic inputs' view channels, SHM.py:576-580; yuv_to_rgb's backward sums r,g,b).
@@ -403,9 +401,9 @@ int shm_head_in_bwd(const void* a, int lda, const double* stats, const float* be
                     int batch, int hw, int c, float slope, int dtype, void* stream);
 /* shm_in_bwd for the block in front of the head: its output gradient is the rank-1 tensor hdz[n*h*w + p] * hw_[ch] (hdz =
  * shm_head_in_bwd's dz_out [batch*h*w] with dx = NULL, hw_ = the head kernel [c]), formed on the fly: the head writes no input
- * gradient and neither pass of the backward reads one.  Otherwise as shm_in_bwd (red, dz, dbias, slope). */
+ * gradient and neither pass of the backward reads one.  Otherwise as shm_in_bwd (red, dz, dbias, dz_sums, slope). */
 int shm_in_bwd_rank1(const float* hdz, const float* hw_, const void* a, int lda, const double* stats, double* red, void* dz,
-                     int lddz, double* dbias, int batch, int h, int w, int c, float slope, int dtype, void* stream);
+                     int lddz, double* dbias, double* dz_sums, int batch, int h, int w, int c, float slope, int dtype, void* stream);
 /* PatchGAN logits Conv2D(1, k=3, no bias) + LeakyReLU (SHM.py:365-369). x [batch,h,w,c]. */
 int shm_patch_fwd(const void* x, int ldx, const float* w, float* y, int batch, int h, int wd, int c,
                   float slope, int dtype, void* stream);

@@ -16,9 +16,9 @@ _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ["SHM_LIB_PATH"]) if os.environ.get("SHM_LIB_PATH") else _HERE / "libshmgan_hip.so"
 CSRC = _HERE / "csrc"
 HEADER = _HERE.parent / "include" / "shmgan_hip.h"
-SOURCES = ["runtime.hip", "conv_igemm.hip", "conv_wreg16.hip", "conv_pingpong.hip", "conv_wgrad.hip", "conv_wgrad_x3.hip", "conv_fwd_x3.hip", "conv_rgb.hip", "norm_elem.hip", "color.hip", "imgloss.hip", "metrics.hip", "specseg.hip", "data.hip", "export.hip", "telemetry.hip"]
+SOURCES = ["runtime.hip", "conv_igemm.hip", "conv_wreg16.hip", "conv_pingpong.hip", "conv_wgrad.hip", "conv_wgrad_x3.hip", "conv_fwd_x3.hip", "conv_rgb.hip", "elem.hip", "instnorm.hip", "instnorm_bwd.hip", "heads.hip", "dgrad_sum1.hip", "color.hip", "imgloss.hip", "metrics.hip", "specseg.hip", "data.hip", "export.hip", "telemetry.hip"]
 # headers every source may include: a change of any of them rebuilds every object (tools/sanitize_host.py goes by the same list)
-SHARED_HEADERS = [CSRC / "common.h", CSRC / "ablate.h", CSRC / "tapgemm.h", CSRC / "wgrad.h", CSRC / "x3split.h", HEADER]
+SHARED_HEADERS = [CSRC / "common.h", CSRC / "elem.h", CSRC / "ablate.h", CSRC / "tapgemm.h", CSRC / "wgrad.h", CSRC / "x3split.h", HEADER]
 F32, BF16 = 0, 1                 # SHM_F32 / SHM_BF16 of include/shmgan_hip.h
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-munsafe-fp-atomics",
                "-Wall", "-Wno-unused-function", "-Wno-unused-local-typedef"]
@@ -58,16 +58,14 @@ SIGNATURES = {
     "shm_conv2d_wgrad_partial_norm": (I, [P, P, I, I, I, P, P, I, P, I, I, I, I, I, I, I, I, I, P, Z, I, P, P]),
     "shm_conv2d_wgrad_norm_workspace": (Z, [I, I, I, I, I, I, I]),
     "shm_conv2d_wgrad_norm_finish": (I, [P, P, P, I, I, I, I, I, I, P]),
-    "shm_in_bwd_keep_dz_sums": (I, [P]),
-    "shm_in_bwd_fused_scratch": (I, [P, Z]),
     "shm_set_abort_words": (I, [P, P]),
     "shm_set_clock_probe": (I, [P]),
     "shm_conv2d_wgrad_norm_supported": (I, [I, I, I, I, I, I, I, I, I, I, I]),
     "shm_in_pool": (I, [P, I, P, P, P, I, I, I, I, I, I, P]),
-    "shm_in_bwd": (I, [P, I, P, I, P, I, P, P, P, I, P, I, I, I, I, F, I, P]),
+    "shm_in_bwd": (I, [P, I, P, I, P, I, P, P, P, I, P, P, P, Z, I, I, I, I, F, I, P]),
     "shm_conv2d_dgrad_gsum": (I, [P, I, P, P, P, I, I, I, I, I, I, I, I, I, I, P, I, P, P, I, P, I, P]),
     "shm_conv2d_fwd_gsum": (I, [P, P, I, I, I, P, P, P, I, I, I, I, I, I, I, I, F, P, I, P, I, P]),
-    "shm_in_bwd_apply": (I, [P, I, P, I, P, I, P, P, P, P, P, P, I, P, I, I, I, I, F, I, P]),
+    "shm_in_bwd_apply": (I, [P, I, P, I, P, I, P, P, P, P, P, P, I, P, P, I, I, I, I, F, I, P]),
     "shm_sum_input_channels": (I, [P, I, I, C.c_uint, P, P]),
     "shm_conv3x3_dgrad_sum1": (I, [P, I, P, P, I, I, I, I, I, I, I, I, P]),
     "shm_lrelu_bwd": (I, [P, I, P, I, P, I, P, P, Z, I, F, I, P]),
@@ -78,7 +76,7 @@ SIGNATURES = {
     "shm_head_bwd": (I, [P, I, P, P, P, P, I, P, P, P, Z, I, F, I, P]),
     "shm_head_in_fwd": (I, [P, I, P, P, P, P, P, I, I, I, F, I, P]),
     "shm_head_in_bwd": (I, [P, I, P, P, P, P, P, P, I, P, P, P, P, I, I, I, F, I, P]),
-    "shm_in_bwd_rank1": (I, [P, P, P, I, P, P, P, I, P, I, I, I, I, F, I, P]),
+    "shm_in_bwd_rank1": (I, [P, P, P, I, P, P, P, I, P, P, I, I, I, I, F, I, P]),
     "shm_patch_fwd": (I, [P, I, P, P, I, I, I, I, F, I, P]),
     "shm_patch_bwd": (I, [P, I, P, P, P, P, P, I, P, I, I, I, I, F, I, P]),
     "shm_dense_fwd": (I, [P, P, P, I, I, I, I, P]),

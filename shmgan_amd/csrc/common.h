@@ -22,7 +22,7 @@ int shm_rgb_s2_fwd_launch(const void* x, int ldx, const void* wk, int K, const f
 int shm_rgb_s2_wgrad_launch(const void* x, int ldx, const void* dy, int lddy, float* part, size_t ws_bytes, int batch, int hi, int wi, int cin, int cout,
                             size_t xbytes, size_t dybytes, int dtype, int* nsplit_out, hipStream_t st);
 
-// norm_elem.hip, for the composite convolution entry points of conv_igemm.hip: the finalize pass of the statistics a convolution's epilogue
+// instnorm.hip / instnorm_bwd.hip, for the composite convolution entry points of conv_igemm.hip: the finalize pass of the statistics a convolution's epilogue
 // summed (shm_conv2d_in_fwd), and the stand-alone (sum g, sum g * aux) pass behind a kernel without a gsum epilogue (shm_conv2d_*_gsum)
 int shm_in_finalize_internal(double* stats, double* part, int nslot, int total, int hw, double eps, float* nt, const float* beta, int c, hipStream_t st);
 int shm_gsum_reduce_internal(const void* g, int ldg, const void* aux, int ldaux, double* red, int batch, int hw, int c, int dtype, hipStream_t st);
@@ -50,7 +50,7 @@ enum ShmTune {
     SHM_TUNE_WGRAD_BF16_WIDE,         // bf16 weight gradient, eight-wave 64 x 128 block: 0 = automatic (stride 2 only), 1 never, 2 stride 2, 3 unit stride, 4 both
     SHM_TUNE_WGRAD_F32_SPLIT,         // fp32 3x3 unit-stride weight gradient: 1 = six bf16 MFMA products of exact three-plane splits (conv_wgrad_x3.hip), 0 = exact-fp32 MFMA (default)
     SHM_TUNE_TAPGEMM_FLAT_EPILOGUE,   // 1 = treat the outputs as larger than 4 GiB (tests: the 64-bit-address epilogues and the kernels that do not need buffer stores)
-    SHM_TUNE_ELEM_FUSED_BWD,          // 1 = bf16 InstanceNorm backward in one pass where eligible and shm_in_bwd_fused_scratch was given (in_bwd_fused8_kernel), 0 = two passes
+    SHM_TUNE_ELEM_FUSED_BWD,          // 1 = bf16 InstanceNorm backward in one pass where eligible and shm_in_bwd was given its fused_scratch (in_bwd_fused8_kernel), 0 = two passes
     SHM_TUNE_ELEM_FUSED_MAX_SLICES,   // in_bwd_fused8_kernel: most slices (= blocks) per sample; a sample's blocks must be resident together (1024 fit an idle chip)
     SHM_TUNE_CONV_F32_SPLIT,          // fp32 3x3 unit-stride forward / input-gradient layers (> 64 output channels): 1 = six bf16 MFMA products of exact three-plane splits (conv_fwd_x3.hip), 0 = exact-fp32 MFMA (default)
     SHM_TUNE_ELEM_FUSED_TEST_STALL,   // tests only: 1 = in_bwd_fused8_kernel's barriers wait for one block more than the grid has (the timeout path)

@@ -1864,7 +1864,7 @@ extern "C" size_t shm_conv2d_wgrad_norm_workspace(int batch, int hi, int wi, int
 
 // SHM_NORM_SCALED, the second term of the weight gradient: dw[tap][part_lo + k][co] += sum_n (beta[k] - mean_n[k] * inv_n[k]) * dzsum[n][co]
 // for every tap (with `ring` in the out-of-image taps the sum over the pixels does not depend on the tap).  dzsum = per-sample channel
-// sums of dz (shm_in_bwd_keep_dz_sums).
+// sums of dz (the dz_sums output of shm_in_bwd and its kin).
 __global__ __launch_bounds__(256) void wgrad_norm_finish_kernel(float* __restrict__ dw, const float* __restrict__ nt, const double* __restrict__ dzsum, int batch,
                                                                 int c, int part_lo, int cin, int cout, int ntaps) {
     // a thread owns one (k, co) pair and walks the samples four at a time (independent loads in flight: as a chain of `batch`

@@ -1,369 +1,7 @@
-// HBM-bound kernels around the convolutions: InstanceNormalization statistics / apply /
-// backward (fused with LeakyReLU' and the AveragePooling2D gradient), pooling, the
-// 1-output-channel layers (generator head, PatchGAN logits, Dense(5)), dropout mask.
-//
-// Layout: NHWC with a channel pitch; every thread moves 16 bytes (4 channels of one
-// pixel); a block covers PP = 256/(C/4) pixels per iteration, so a wave reads whole
-// contiguous channel rows.  Per-(sample,channel) sums are accumulated in fp64 per thread,
-// combined through LDS and added with one f64 atomic per (block, channel).
-#include "common.h"
-
-extern "C" int shm_zero(void* p, size_t bytes, void* stream) {
-    if (bytes == 0) return SHM_OK;
-    hipError_t e = hipMemsetAsync(p, 0, bytes, (hipStream_t)stream);
-    SHM_REQUIRE(e == hipSuccess, SHM_E_HIP, "shm_zero: %s", hipGetErrorString(e));
-    return SHM_OK;
-}
-
-__global__ void cvt_f64_f32_kernel(const double* __restrict__ s, float* __restrict__ d, size_t n, int acc) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) d[i] = (acc ? d[i] : 0.f) + (float)s[i];
-}
-
-extern "C" int shm_cvt_f64_f32(const double* src, float* dst, size_t n, int accumulate, void* stream) {
-    if (n == 0) return SHM_OK;
-    hipLaunchKernelGGL(cvt_f64_f32_kernel, dim3(shm_cdiv((long)n, 256)), dim3(256), 0, (hipStream_t)stream, src, dst, n, accumulate);
-    SHM_LAUNCH_CHECK("shm_cvt_f64_f32");
-    return SHM_OK;
-}
-
-// f32 -> activation dtype copy (bf16 operand copies of the fp32 master weights)
-template <typename T>
-__global__ void cast_f32_kernel(const float* __restrict__ s, T* __restrict__ d, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) d[i] = (T)s[i];
-}
-
-extern "C" int shm_cast_f32(const float* src, void* dst, size_t n, int dtype, void* stream) {
-    if (n == 0) return SHM_OK;
-    long blocks = (long)((n + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    SHM_DISPATCH(dtype, "shm_cast_f32", hipLaunchKernelGGL(cast_f32_kernel<T>, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, src, (T*)dst, n));
-    SHM_LAUNCH_CHECK("shm_cast_f32");
-    return SHM_OK;
-}
-
-// ------------------------------------------------------------------ pixel-chunk skeleton
-// thread -> (pp, cl): pixel slot and 4-channel lane.  PP pixel slots per block iteration.
-struct PixMap {
-    int lanes_c, PP, pp, cl;
-    bool active;
-    __device__ PixMap(int c) {
-        lanes_c = c >> 2;
-        PP = 256 / lanes_c;
-        pp = threadIdx.x / lanes_c;
-        cl = threadIdx.x - pp * lanes_c;
-        active = pp < PP;
-    }
-};
-
-// blocks = 0: the target of the passes without a per-block prologue or reduction (InstanceNorm apply, its pooling forms),
-// "elem.stream_blocks", default 32768: short blocks keep the addresses in flight a narrow band that sweeps through the tensors
-// (tools/probes/elem_probe.hip: a 2-read / 1-write pass over 3 x 671 MB runs at 5.5 TB/s with 4k blocks of 160 KB each and at 7.0 TB/s with
-// 16k blocks of 40 KB; shm_in_apply on the same tensor 5.16 -> 5.85 TB/s in fp32, 5.24 -> 6.01 in bf16).  The passes that start with
-// a per-block prologue and end in an LDS reduction + atomics (InstanceNorm backward) keep 4096: they get SLOWER with more blocks.
-static int pix_chunks(long npix_per_sample, int batch, int c, int blocks = 0) {
-    // enough blocks to fill the chip, but at least 8 (streaming target) / 16 pixel iterations per thread so the
-    // per-block LDS reduction + f64 atomics (one per channel and block) stay a small fraction
-    if (blocks == 0) blocks = shm_tune(SHM_TUNE_ELEM_STREAM_BLOCKS);
-    const int min_iter = blocks > 4096 ? 8 : 16;
-    int lanes_c = c / 4;
-    int PP = 256 / lanes_c;
-    long want = (blocks + batch - 1) / batch;
-    long maxc = npix_per_sample / ((long)PP * min_iter);
-    if (want > maxc) want = maxc;
-    if (want < 1) want = 1;
-    return (int)want;
-}
-
-#define SHM_CHECK_C(c, who) SHM_REQUIRE((c) % 4 == 0 && (c) >= 4 && (c) <= 1024, SHM_E_SHAPE, "%s: channels %d must be a multiple of 4 in [4,1024]", who, (c))
-
-// Combine per-thread double[NV][4] partials over the PP pixel slots, then one atomic per
-// (channel, value).  dst index = base + (ch * NV + v) when interleaved, or v*c + ch otherwise.
-template <int NV>
-__device__ __forceinline__ void block_reduce_atomic(double (&v)[NV][4], const PixMap& pm, double* dst, int c, bool interleaved) {
-    __shared__ double red[256 * 4];
-    for (int q = 0; q < NV; ++q) {
-        __syncthreads();
-        if (pm.active) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) red[(pm.pp * pm.lanes_c + pm.cl) * 4 + e] = v[q][e];
-        }
-        __syncthreads();
-        if (pm.active && pm.pp == 0) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                double s = 0.0;
-                for (int p = 0; p < pm.PP; ++p) s += red[(p * pm.lanes_c + pm.cl) * 4 + e];
-                int ch = pm.cl * 4 + e;
-                if (ch < c) atomicAdd(&dst[interleaved ? ch * NV + q : q * c + ch], s);
-            }
-        }
-    }
-}
-
-// ------------------------------------------------------------------------- IN statistics
-template <typename T>
-__global__ __launch_bounds__(256) void in_stats_kernel(const T* __restrict__ a, int lda, double* __restrict__ stats, int hw, int c, int chunk) {
-    PixMap pm(c);
-    const int n = blockIdx.y;
-    const int p0 = blockIdx.x * chunk, p1 = min(hw, p0 + chunk);
-    double v[2][4] = {};
-    if (pm.active) {
-        const T* base = a + (size_t)n * hw * lda + pm.cl * 4;
-        for (int p = p0 + pm.pp; p < p1; p += pm.PP) {
-            f32x4 x = ld4(base + (size_t)p * lda);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                v[0][e] += (double)x[e];
-                v[1][e] += (double)x[e] * (double)x[e];
-            }
-        }
-    }
-    block_reduce_atomic<2>(v, pm, stats + (size_t)n * c * 2, c, true);
-}
-
-// part != null: the sums were accumulated over `nslot` slot copies part[slot][total][2]; the copies are zeroed
-// again as they are consumed, so the scratch is zero whenever no call is in flight (no memset per launch)
-// nt != null: also the float table [batch][4][c] = (mean, inv, beta, ring) of the consumers that normalise on the fly (common.h)
-__global__ void in_finalize_kernel(double* __restrict__ stats, double* __restrict__ part, int nslot, int total, int hw, double eps, float* __restrict__ nt,
-                                   const float* __restrict__ beta, int c) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    double s, q;
-    if (part) {
-        s = q = 0.0;
-        for (int k = 0; k < nslot; ++k) {
-            double* pk = part + ((size_t)k * total + i) * 2;
-            s += pk[0];
-            q += pk[1];
-            pk[0] = 0.0;
-            pk[1] = 0.0;
-        }
-    } else {
-        s = stats[2 * i];
-        q = stats[2 * i + 1];
-    }
-    double mean = s / hw;
-    double var = q / hw - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const double inv = 1.0 / sqrt(var + eps);
-    stats[2 * i] = mean;
-    stats[2 * i + 1] = inv;
-    if (nt) {
-        const int n = i / c, ch = i - n * c;
-        float* t = nt + (size_t)n * SHM_NT_PLANES * c + ch;
-        t[0] = (float)mean;
-        t[c] = (float)inv;
-        t[2 * c] = beta[ch];
-        t[3 * c] = (float)mean - beta[ch] / (float)inv;
-    }
-}
-
-int shm_in_finalize_internal(double* stats, double* part, int nslot, int total, int hw, double eps, float* nt, const float* beta, int c, hipStream_t st) {
-    hipLaunchKernelGGL(in_finalize_kernel, dim3(shm_cdiv((long)total, 256)), dim3(256), 0, st, stats, part, nslot, total, hw, eps, nt, beta, c);
-    SHM_LAUNCH_CHECK("shm_in_finalize");
-    return SHM_OK;
-}
-
-// the table alone, from finalized statistics (mean, inv)
-__global__ void in_norm_table_kernel(const double* __restrict__ stats, const float* __restrict__ beta, float* __restrict__ nt, int total, int c) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const int n = i / c, ch = i - n * c;
-    float* t = nt + (size_t)n * SHM_NT_PLANES * c + ch;
-    t[0] = (float)stats[2 * i];
-    t[c] = (float)stats[2 * i + 1];
-    t[2 * c] = beta[ch];
-    t[3 * c] = (float)stats[2 * i] - beta[ch] / (float)stats[2 * i + 1];
-}
-
-extern "C" int shm_in_norm_table(const double* stats, const float* beta, float* nt, int batch, int c, void* stream) {
-    SHM_REQUIRE(stats && beta && nt, SHM_E_SHAPE, "shm_in_norm_table: null pointer");
-    SHM_REQUIRE(c % 4 == 0 && c > 0, SHM_E_SHAPE, "shm_in_norm_table: channels %d must be a positive multiple of 4", c);
-    if (batch == 0) return SHM_OK;
-    hipLaunchKernelGGL(in_norm_table_kernel, dim3(shm_cdiv((long)batch * c, 256)), dim3(256), 0, (hipStream_t)stream, stats, beta, nt, batch * c, c);
-    SHM_LAUNCH_CHECK("shm_in_norm_table");
-    return SHM_OK;
-}
-
-extern "C" int shm_in_stats(const void* a, int lda, double* stats, int batch, int hw, int c, float eps, int dtype, void* stream) {
-    SHM_CHECK_C(c, "shm_in_stats");
-    SHM_REQUIRE(lda % 4 == 0 && lda >= c, SHM_E_SHAPE, "shm_in_stats: bad pitch %d", lda);
-    hipStream_t st = (hipStream_t)stream;
-    if (batch == 0 || hw == 0) return SHM_OK;
-    int r = shm_zero(stats, (size_t)batch * c * 2 * sizeof(double), stream);
-    if (r) return r;
-    int nch = pix_chunks(hw, batch, c, 4096);
-    int chunk = shm_cdiv(hw, nch);
-    SHM_DISPATCH(dtype, "shm_in_stats",
-                 hipLaunchKernelGGL(in_stats_kernel<T>, dim3(shm_cdiv(hw, chunk), batch), dim3(256), 0, st, (const T*)a, lda, stats, hw, c, chunk));
-    SHM_LAUNCH_CHECK("shm_in_stats");
-    hipLaunchKernelGGL(in_finalize_kernel, dim3(shm_cdiv((long)batch * c, 256)), dim3(256), 0, st, stats, (double*)nullptr, 0, batch * c, hw, (double)eps,
-                       (float*)nullptr, (const float*)nullptr, c);
-    SHM_LAUNCH_CHECK("shm_in_stats(finalize)");
-    return SHM_OK;
-}
-
-// rev: walk the tensor back to front.  The producing convolution wrote the samples in ascending order, so the LAST ones are
-// still in the 256 MiB Infinity Cache: reading them first turns up to 256 MiB of this pass's reads into cache hits (front to
-// back, an LRU cache smaller than the tensor yields none), and it leaves sample 0 written last -- where the
-// consuming convolution starts.
-template <typename T>
-__global__ __launch_bounds__(256) void in_apply_kernel(const T* __restrict__ a, int lda, const double* __restrict__ stats, const float* __restrict__ beta,
-                                                       T* __restrict__ out, int ldo, int hw, int c, int chunk, int rev) {
-    PixMap pm(c);
-    if (!pm.active) return;
-    const int n = rev ? gridDim.y - 1 - blockIdx.y : blockIdx.y;
-    const int bx = rev ? gridDim.x - 1 - blockIdx.x : blockIdx.x;
-    const int p0 = bx * chunk, p1 = min(hw, p0 + chunk);
-    float mean[4], inv[4], bt[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        int ch = pm.cl * 4 + e;
-        mean[e] = (float)stats[((size_t)n * c + ch) * 2];
-        inv[e] = (float)stats[((size_t)n * c + ch) * 2 + 1];
-        bt[e] = beta[ch];
-    }
-    const T* base = a + (size_t)n * hw * lda + pm.cl * 4;
-    T* ob = out + (size_t)n * hw * ldo + pm.cl * 4;
-    constexpr int U = sizeof(T) == 2 ? 8 : 4;
-    int p = p0 + pm.pp;
-    for (; p + (U - 1) * pm.PP < p1; p += U * pm.PP) {
-        f32x4 x[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) x[u] = ld4(base + (size_t)(p + u * pm.PP) * lda);
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            f32x4 y;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) y[e] = shm_in_norm(x[u][e], mean[e], inv[e], bt[e]);
-            st4(ob + (size_t)(p + u * pm.PP) * ldo, y);
-        }
-    }
-    for (; p < p1; p += pm.PP) {
-        f32x4 x = ld4(base + (size_t)p * lda);
-        f32x4 y;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) y[e] = shm_in_norm(x[e], mean[e], inv[e], bt[e]);
-        st4(ob + (size_t)p * ldo, y);
-    }
-}
-
-extern "C" int shm_in_apply(const void* a, int lda, const double* stats, const float* beta, void* out, int ldo, int batch, int hw, int c, int dtype,
-                            void* stream) {
-    SHM_CHECK_C(c, "shm_in_apply");
-    SHM_REQUIRE(lda % 4 == 0 && ldo % 4 == 0, SHM_E_SHAPE, "shm_in_apply: bad pitch");
-    if (batch == 0 || hw == 0) return SHM_OK;
-    int nch = pix_chunks(hw, batch, c);
-    int chunk = shm_cdiv(hw, nch);
-    SHM_DISPATCH(dtype, "shm_in_apply",
-                 hipLaunchKernelGGL(in_apply_kernel<T>, dim3(shm_cdiv(hw, chunk), batch), dim3(256), 0, (hipStream_t)stream, (const T*)a, lda, stats, beta,
-                                    (T*)out, ldo, hw, c, chunk, shm_tune(SHM_TUNE_ELEM_REVERSE)));
-    SHM_LAUNCH_CHECK("shm_in_apply");
-    return SHM_OK;
-}
-
-// InstanceNorm apply + AveragePooling2D(2) in one pass (the second block of every encoder level feeds both the skip and the
-// pool): a thread normalises the four pixels of a 2 x 2 quad for its four channels, writes them, and writes their mean -- the
-// pooled tensor is formed from the values as stored (rounded to T), in avgpool2_kernel's order, so it is bit-identical to
-// shm_in_apply followed by shm_avgpool2_fwd; the separate pooling pass (a full read of the normalised tensor) is gone.
-// OUT = false (shm_in_pool): only the pooled tensor is written -- the skip connection's consumers normalise the stored activation
-// on the fly (shm_conv2d_in_fwd_norm / shm_conv2d_wgrad_norm); the pooled values are the same bits as with OUT = true.
-template <typename T, bool OUT = true>
-__global__ __launch_bounds__(256) void in_apply_pool_kernel(const T* __restrict__ a, int lda, const double* __restrict__ stats, const float* __restrict__ beta,
-                                                            T* __restrict__ out, int ldo, T* __restrict__ pooled, int ldp, int h, int w, int c, int chunk,
-                                                            int rev) {
-    PixMap pm(c);
-    if (!pm.active) return;
-    const int n = rev ? gridDim.y - 1 - blockIdx.y : blockIdx.y;
-    const int bx = rev ? gridDim.x - 1 - blockIdx.x : blockIdx.x;
-    const int wo = w >> 1, hq = (h >> 1) * wo;
-    const int q0 = bx * chunk, q1 = min(hq, q0 + chunk);
-    float mean[4], inv[4], bt[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        int ch = pm.cl * 4 + e;
-        mean[e] = (float)stats[((size_t)n * c + ch) * 2];
-        inv[e] = (float)stats[((size_t)n * c + ch) * 2 + 1];
-        bt[e] = beta[ch];
-    }
-    const T* base = a + (size_t)n * h * w * lda + pm.cl * 4;
-    T* ob = out + (size_t)n * h * w * ldo + pm.cl * 4;
-    T* pb = pooled + (size_t)n * hq * ldp + pm.cl * 4;
-    constexpr int U = 2;
-    auto quad = [&](int q, f32x4 (&x)[4]) {
-        const int oy = q / wo, ox = q - oy * wo;
-        const size_t p = (size_t)(2 * oy) * w + 2 * ox;
-        x[0] = ld4(base + p * lda);
-        x[1] = ld4(base + (p + 1) * lda);
-        x[2] = ld4(base + (p + w) * lda);
-        x[3] = ld4(base + (p + w + 1) * lda);
-    };
-    auto finish = [&](int q, const f32x4 (&x)[4]) {
-        const int oy = q / wo, ox = q - oy * wo;
-        const size_t p = (size_t)(2 * oy) * w + 2 * ox;
-        f32x4 y[4], s;
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) y[t][e] = rnd_as((const T*)nullptr, shm_in_norm(x[t][e], mean[e], inv[e], bt[e]));
-        if constexpr (OUT) {
-            st4(ob + p * ldo, y[0]);
-            st4(ob + (p + 1) * ldo, y[1]);
-            st4(ob + (p + w) * ldo, y[2]);
-            st4(ob + (p + w + 1) * ldo, y[3]);
-        }
-        s = ((y[0] + y[1]) + y[2]) + y[3];
-        st4(pb + (size_t)q * ldp, s * 0.25f);
-    };
-    int q = q0 + pm.pp;
-    for (; q + (U - 1) * pm.PP < q1; q += U * pm.PP) {
-        f32x4 x[U][4];
-#pragma unroll
-        for (int u = 0; u < U; ++u) quad(q + u * pm.PP, x[u]);
-#pragma unroll
-        for (int u = 0; u < U; ++u) finish(q + u * pm.PP, x[u]);
-    }
-    for (; q < q1; q += pm.PP) {
-        f32x4 x[4];
-        quad(q, x);
-        finish(q, x);
-    }
-}
-
-extern "C" int shm_in_apply_pool(const void* a, int lda, const double* stats, const float* beta, void* out, int ldo, void* pooled, int ldp, int batch,
-                                 int h, int w, int c, int dtype, void* stream) {
-    SHM_CHECK_C(c, "shm_in_apply_pool");
-    SHM_REQUIRE(lda % 4 == 0 && ldo % 4 == 0 && ldp % 4 == 0, SHM_E_SHAPE, "shm_in_apply_pool: bad pitch");
-    SHM_REQUIRE(h % 2 == 0 && w % 2 == 0, SHM_E_SHAPE, "shm_in_apply_pool: odd size %dx%d", h, w);
-    SHM_REQUIRE(a && stats && beta && out && pooled, SHM_E_SHAPE, "shm_in_apply_pool: null pointer");
-    if (batch == 0 || h * w == 0) return SHM_OK;
-    const int hq = (h / 2) * (w / 2);
-    int nch = pix_chunks(hq, batch, c);
-    int chunk = shm_cdiv(hq, nch);
-    SHM_DISPATCH(dtype, "shm_in_apply_pool",
-                 hipLaunchKernelGGL((in_apply_pool_kernel<T, true>), dim3(shm_cdiv(hq, chunk), batch), dim3(256), 0, (hipStream_t)stream, (const T*)a, lda, stats, beta,
-                                    (T*)out, ldo, (T*)pooled, ldp, h, w, c, chunk, shm_tune(SHM_TUNE_ELEM_REVERSE)));
-    SHM_LAUNCH_CHECK("shm_in_apply_pool");
-    return SHM_OK;
-}
-
-extern "C" int shm_in_pool(const void* a, int lda, const double* stats, const float* beta, void* pooled, int ldp, int batch, int h, int w, int c, int dtype,
-                           void* stream) {
-    SHM_CHECK_C(c, "shm_in_pool");
-    SHM_REQUIRE(lda % 4 == 0 && ldp % 4 == 0, SHM_E_SHAPE, "shm_in_pool: bad pitch");
-    SHM_REQUIRE(h % 2 == 0 && w % 2 == 0, SHM_E_SHAPE, "shm_in_pool: odd size %dx%d", h, w);
-    SHM_REQUIRE(a && stats && beta && pooled, SHM_E_SHAPE, "shm_in_pool: null pointer");
-    if (batch == 0 || h * w == 0) return SHM_OK;
-    const int hq = (h / 2) * (w / 2);
-    int nch = pix_chunks(hq, batch, c);
-    int chunk = shm_cdiv(hq, nch);
-    SHM_DISPATCH(dtype, "shm_in_pool",
-                 hipLaunchKernelGGL((in_apply_pool_kernel<T, false>), dim3(shm_cdiv(hq, chunk), batch), dim3(256), 0, (hipStream_t)stream, (const T*)a, lda, stats,
-                                    beta, (T*)nullptr, 0, (T*)pooled, ldp, h, w, c, chunk, shm_tune(SHM_TUNE_ELEM_REVERSE)));
-    SHM_LAUNCH_CHECK("shm_in_pool");
-    return SHM_OK;
-}
+// InstanceNormalization backward, fused with LeakyReLU' and the AveragePooling2D gradient: the reduce + apply passes, the one-pass bf16
+// kernels with their per-sample barrier, the gsum (apply-only) form and the bias-gradient folds; and the LeakyReLU backward of the blocks
+// without a normalisation, which ends in the same bias-gradient fold (dbias_fold_kernel).
+#include "elem.h"
 
 // --------------------------------------------------------------------------- IN backward
 struct InBwdArgs {               // g1, g2, a, dz: tensors of the kernels' element type T
@@ -1299,7 +937,7 @@ __global__ __launch_bounds__(256, BPC) void in_bwd_fusedg_kernel(const InBwdArgs
 
 // shm_in_bwd_apply's last launch: fold the staged bias gradient (dbias[ch] += sum over samples) and clear the gsum slot copies the
 // apply pass consumed -- "zero on entry, zero on return" for every f64 scratch, no memset in front of a launch.
-// keep != null: the per-sample sums are also copied out ([nslot = batch][c]: shm_in_bwd_keep_dz_sums)
+// keep != null: the per-sample sums are also copied out ([nslot = batch][c]: the entry points' dz_sums)
 __global__ __launch_bounds__(256) void gsum_finish_kernel(double* __restrict__ part, double* __restrict__ dbias, int nslot, int c, double* __restrict__ clr1,
                                                           size_t n1, double* __restrict__ clr2, size_t n2, double* __restrict__ keep) {
     __shared__ double red[4][64];
@@ -1379,6 +1017,8 @@ int shm_gsum_reduce_internal(const void* g, int ldg, const void* aux, int ldaux,
 }
 
 // dbias[ch] += sum over slots of part[slot*c + ch]
+// `keep` != null: the slots -- per-sample channel sums of dz, [batch][c] -- are also copied out (the entry points' dz_sums: the second term of a
+// SHM_NORM_SCALED weight gradient needs them per sample)
 // `clear` != null: also zero the 2*nslot*c reduction sums in front of `part` (shm_in_bwd's scratch is zero on return).
 // Block = 64 channels x 4 slot groups (a serial loop over the slots per channel was latency bound: 10 us per launch).
 __global__ __launch_bounds__(256) void dbias_fold_kernel(double* __restrict__ part, double* __restrict__ dbias, int nslot, int c,
@@ -1402,26 +1042,6 @@ __global__ __launch_bounds__(256) void dbias_fold_kernel(double* __restrict__ pa
     __syncthreads();
     if (g == 0 && ch < c) dbias[ch] += (red[0][cl] + red[1][cl]) + (red[2][cl] + red[3][cl]);
 }
-
-// shm_in_bwd_keep_dz_sums: the next shm_in_bwd / shm_in_bwd_apply / shm_in_bwd_rank1 call of this thread also copies out the per-sample
-// channel sums of dz ([batch][c] float64) it stages on the way to the bias gradient (the second term of a SHM_NORM_SCALED weight
-// gradient needs them per sample).  One-shot.
-static thread_local double* g_keep_dzsum = nullptr;
-extern "C" int shm_in_bwd_keep_dz_sums(double* dst) {
-    g_keep_dzsum = dst;
-    return SHM_OK;
-}
-// shm_in_bwd_fused_scratch: scratch of the one-pass bf16 form (in_bwd_fused8_kernel) for the next shm_in_bwd call of this thread: n_doubles >=
-// SHM_IN_BWD_FUSED_DOUBLES(batch, h * w, c) float64 (fused_scratch_doubles above), zero on entry, zero on return.  One-shot; without it (or on shapes the one-pass form does
-// not take) shm_in_bwd runs its two passes.
-static thread_local double* g_fused_scratch = nullptr;
-static thread_local size_t g_fused_doubles = 0;
-extern "C" int shm_in_bwd_fused_scratch(double* scratch, size_t n_doubles) {
-    g_fused_scratch = scratch;
-    g_fused_doubles = scratch ? n_doubles : 0;
-    return SHM_OK;
-}
-
 
 // Blocks of in_bwd_fused8_kernel<G2> the current device holds at once (CUs x occupancy; queried once per device and form).  The kernel's
 // barrier only completes if a whole group is resident, and two such launches may run side by side (two streams), each stuck with LESS than a
@@ -1448,15 +1068,9 @@ static int fused_resident_blocks(int form) {          // 0: in_bwd_fused8_kernel
 }
 
 static int in_bwd_impl(const char* who, const void* g1, int ldg1, const void* g2, int ldg2, const float* r1_dz, const float* r1_w, const void* a, int lda,
-                       const double* stats, double* red, void* dz, int lddz, double* dbias, int batch, int h, int w, int c, float slope, int dtype,
-                       void* stream) {
+                       const double* stats, double* red, void* dz, int lddz, double* dbias, double* keep, double* fscr, size_t fscr_n, int batch, int h,
+                       int w, int c, float slope, int dtype, void* stream) {
     const bool r1 = r1_dz != nullptr;
-    double* const keep = g_keep_dzsum;
-    g_keep_dzsum = nullptr;
-    double* const fscr = g_fused_scratch;
-    const size_t fscr_n = g_fused_doubles;
-    g_fused_scratch = nullptr;
-    g_fused_doubles = 0;
     SHM_REQUIRE(!keep || dbias, SHM_E_SHAPE, "%s: the per-sample dz sums are staged only with a bias gradient", who);
     SHM_CHECK_C(c, who);
     SHM_REQUIRE((r1 || ldg1 % 4 == 0) && lda % 4 == 0 && lddz % 4 == 0 && (!g2 || ldg2 % 4 == 0), SHM_E_SHAPE, "%s: bad pitch", who);
@@ -1499,41 +1113,33 @@ static int in_bwd_impl(const char* who, const void* g1, int ldg1, const void* g2
         // automatic dispatch takes it from 256 slices of the 8-slot kind per group on.
         const int slice16 = 2 * slice;
         const int fgv = shm_tune(SHM_TUNE_ELEM_FUSED_GVARIANT);
-        if (base_ok && hold != 1 && !g2 && hw % slice16 == 0 && (hold == 2 || hw / slice >= 256) && hw / slice16 <= 2 * max_slices &&
-            2 * (hw / slice16) <= fused_resident_blocks(fgv == 1 ? 3 : 2)) {
-            const int bpi = hw / slice16;
-            // ONE scratch layout for both kernels (the caller's buffer is "zero behind the partial rows" whichever kernel ran last): means, counters
-            // and flags sit behind the rows region of the 16384 / CB-pixel slicing; this kernel's rows fill half of it
-            float* const fres = (float*)(fscr + fused_row_doubles(batch, (size_t)hw * cb / 16384, c));
+        // the tail both one-pass forms share: `blocks` per group, scratch carved behind `rows` partial rows per group; then the bias-gradient fold
+        const auto fused = [&](void (*kernel)(const InBwdArgs, float*, float*, unsigned*, unsigned*, unsigned*, unsigned*, const unsigned), const char* name,
+                               int blocks, size_t rows) -> int {
+            float* const fres = (float*)(fscr + fused_row_doubles(batch, rows, c));
             unsigned* const fsync = (unsigned*)(fres + (size_t)batch * c * 2);
             unsigned* const ferr = fsync + (size_t)batch * ncb * SHM_FUSED_SYNC_WORDS;
-            const dim3 gridf(bpi, ncb, batch);
+            const dim3 gridf(blocks, ncb, batch);
             const unsigned arrivals = gridf.x + (shm_tune(SHM_TUNE_ELEM_FUSED_TEST_STALL) ? 1u : 0u);
-            if (fgv == 1) hipLaunchKernelGGL((in_bwd_fusedg_kernel<8, 8, 3>), gridf, dim3(256), 0, st, k, (float*)fscr, fres, fsync, ferr, shm_abort_dev_word(), shm_abort_host_word(), arrivals);
-            else hipLaunchKernelGGL((in_bwd_fusedg_kernel<2, 2, 4>), gridf, dim3(256), 0, st, k, (float*)fscr, fres, fsync, ferr, shm_abort_dev_word(), shm_abort_host_word(), arrivals);
-            shm_set_last_kernel(fgv == 1 ? "in_bwd_fusedg_kernel<8, 8, 3>" : "in_bwd_fusedg_kernel<2, 2, 4>");
-            SHM_LAUNCH_CHECK_CLEAR("shm_in_bwd(fused)", red, red_bytes, st);
-            if (dbias && !k.fold) {
-                hipLaunchKernelGGL(dbias_fold_kernel, dim3(shm_cdiv(c, 64)), dim3(256), 0, st, red + (size_t)batch * c * 2, dbias, batch, c, (double*)nullptr, keep);
-                SHM_LAUNCH_CHECK_CLEAR("shm_in_bwd(fold)", red, red_bytes, st);
-            }
-            return SHM_OK;
-        }
-        if (base_ok && hold != 2 && hw % slice == 0 && hw / slice <= max_slices && (!g2 || g2_tiles) && 2 * (hw / slice) <= fused_resident_blocks(g2 ? 1 : 0)) {
-            float* const fres = (float*)(fscr + fused_row_doubles(batch, hw / slice, c));
-            unsigned* const fsync = (unsigned*)(fres + (size_t)batch * c * 2);
-            unsigned* const ferr = fsync + (size_t)batch * ncb * SHM_FUSED_SYNC_WORDS;
-            const dim3 gridf(hw / slice, ncb, batch);
-            const unsigned arrivals = gridf.x + (shm_tune(SHM_TUNE_ELEM_FUSED_TEST_STALL) ? 1u : 0u);
-            if (g2) hipLaunchKernelGGL((in_bwd_fused8_kernel<true>), gridf, dim3(256), 0, st, k, (float*)fscr, fres, fsync, ferr, shm_abort_dev_word(), shm_abort_host_word(), arrivals);
-            else hipLaunchKernelGGL((in_bwd_fused8_kernel<false>), gridf, dim3(256), 0, st, k, (float*)fscr, fres, fsync, ferr, shm_abort_dev_word(), shm_abort_host_word(), arrivals);
-            shm_set_last_kernel(g2 ? "in_bwd_fused8_kernel<true>" : "in_bwd_fused8_kernel<false>");
+            hipLaunchKernelGGL(kernel, gridf, dim3(256), 0, st, k, (float*)fscr, fres, fsync, ferr, shm_abort_dev_word(), shm_abort_host_word(), arrivals);
+            shm_set_last_kernel("%s", name);
             SHM_LAUNCH_CHECK_CLEAR("shm_in_bwd(fused)", red, red_bytes, st);
             if (dbias && !k.fold) {       // (the two sum planes in front of the staging were not used: nothing to clear)
                 hipLaunchKernelGGL(dbias_fold_kernel, dim3(shm_cdiv(c, 64)), dim3(256), 0, st, red + (size_t)batch * c * 2, dbias, batch, c, (double*)nullptr, keep);
                 SHM_LAUNCH_CHECK_CLEAR("shm_in_bwd(fold)", red, red_bytes, st);
             }
             return SHM_OK;
+        };
+        if (base_ok && hold != 1 && !g2 && hw % slice16 == 0 && (hold == 2 || hw / slice >= 256) && hw / slice16 <= 2 * max_slices &&
+            2 * (hw / slice16) <= fused_resident_blocks(fgv == 1 ? 3 : 2)) {
+            // ONE scratch layout for both kernels (the caller's buffer is "zero behind the partial rows" whichever kernel ran last): means, counters
+            // and flags sit behind the rows region of the 16384 / CB-pixel slicing; this kernel's rows fill half of it
+            return fused(fgv == 1 ? in_bwd_fusedg_kernel<8, 8, 3> : in_bwd_fusedg_kernel<2, 2, 4>,
+                         fgv == 1 ? "in_bwd_fusedg_kernel<8, 8, 3>" : "in_bwd_fusedg_kernel<2, 2, 4>", hw / slice16, (size_t)hw * cb / 16384);
+        }
+        if (base_ok && hold != 2 && hw % slice == 0 && hw / slice <= max_slices && (!g2 || g2_tiles) && 2 * (hw / slice) <= fused_resident_blocks(g2 ? 1 : 0)) {
+            return fused(g2 ? in_bwd_fused8_kernel<true> : in_bwd_fused8_kernel<false>, g2 ? "in_bwd_fused8_kernel<true>" : "in_bwd_fused8_kernel<false>",
+                         hw / slice, hw / slice);
         }
     }
     // Sample chunks ("elem.chunk_mb", round 3): the apply pass re-reads what the reduce pass read.  On tensors larger than the 256 MiB
@@ -1597,21 +1203,20 @@ static int in_bwd_impl(const char* who, const void* g1, int ldg1, const void* g2
 }
 
 extern "C" int shm_in_bwd(const void* g1, int ldg1, const void* g2, int ldg2, const void* a, int lda,
-                          const double* stats, double* red, void* dz, int lddz, double* dbias, int batch,
-                          int h, int w, int c, float slope, int dtype, void* stream) {
+                          const double* stats, double* red, void* dz, int lddz, double* dbias, double* dz_sums, double* fused_scratch,
+                          size_t fused_doubles, int batch, int h, int w, int c, float slope, int dtype, void* stream) {
     SHM_REQUIRE(g1, SHM_E_SHAPE, "shm_in_bwd: null gradient");
-    return in_bwd_impl("shm_in_bwd", g1, ldg1, g2, ldg2, nullptr, nullptr, a, lda, stats, red, dz, lddz, dbias, batch, h, w, c, slope, dtype, stream);
+    return in_bwd_impl("shm_in_bwd", g1, ldg1, g2, ldg2, nullptr, nullptr, a, lda, stats, red, dz, lddz, dbias, dz_sums, fused_scratch, fused_doubles, batch, h,
+                       w, c, slope, dtype, stream);
 }
 
 // InstanceNorm + LeakyReLU backward WITHOUT its reduce pass: the per-(sample, channel) sums were formed in the epilogues of the
 // launches that wrote g1 / g2 (shm_conv2d_dgrad_gsum, shm_conv2d_fwd_gsum), so this is one pass over the tensors -- read g1 [+ g2],
 // read a, write dz -- where shm_in_bwd makes two.
 extern "C" int shm_in_bwd_apply(const void* g1, int ldg1, const void* g2, int ldg2, const void* a, int lda, const double* stats, const float* beta,
-                                double* red, double* redp, double* dstage, void* dz, int lddz, double* dbias, int batch, int h, int w, int c,
+                                double* red, double* redp, double* dstage, void* dz, int lddz, double* dbias, double* keep, int batch, int h, int w, int c,
                                 float slope, int dtype, void* stream) {
     const char* who = "shm_in_bwd_apply";
-    double* const keep = g_keep_dzsum;
-    g_keep_dzsum = nullptr;
     SHM_REQUIRE(!keep || dbias, SHM_E_SHAPE, "%s: the per-sample dz sums are staged only with a bias gradient", who);
     SHM_REQUIRE(g1 && a && stats && red && dz, SHM_E_SHAPE, "%s: null pointer", who);
     SHM_REQUIRE((g2 != nullptr) == (redp != nullptr), SHM_E_SHAPE, "%s: the pooled gradient g2 and its sums redp come together", who);
@@ -1655,9 +1260,10 @@ extern "C" int shm_in_bwd_apply(const void* g1, int ldg1, const void* g2, int ld
 // d_out[n, p, ch] = hdz[n * h * w + p] * hw_[ch] (shm_head_in_bwd's dz_out and the head kernel): formed on the fly, so the head
 // never writes its input gradient and neither pass here reads it (three passes over the largest activation of the network).
 extern "C" int shm_in_bwd_rank1(const float* hdz, const float* hw_, const void* a, int lda, const double* stats, double* red, void* dz, int lddz,
-                                double* dbias, int batch, int h, int w, int c, float slope, int dtype, void* stream) {
+                                double* dbias, double* dz_sums, int batch, int h, int w, int c, float slope, int dtype, void* stream) {
     SHM_REQUIRE(hdz && hw_, SHM_E_SHAPE, "shm_in_bwd_rank1: null gradient");
-    return in_bwd_impl("shm_in_bwd_rank1", nullptr, 0, nullptr, 0, hdz, hw_, a, lda, stats, red, dz, lddz, dbias, batch, h, w, c, slope, dtype, stream);
+    return in_bwd_impl("shm_in_bwd_rank1", nullptr, 0, nullptr, 0, hdz, hw_, a, lda, stats, red, dz, lddz, dbias, dz_sums, nullptr, 0, batch, h, w, c, slope,
+                       dtype, stream);
 }
 
 // ---------------------------------------------------------------------- LeakyReLU backward
@@ -1723,866 +1329,5 @@ extern "C" int shm_lrelu_bwd(const void* dy, int lddy, const void* y, int ldy, v
         hipLaunchKernelGGL(dbias_fold_kernel, dim3(shm_cdiv(c, 64)), dim3(256), 0, (hipStream_t)stream, red, dbias, SHM_LRELU_RED_SLOTS, c, (double*)nullptr, (double*)nullptr);
         SHM_LAUNCH_CHECK_CLEAR("shm_lrelu_bwd(fold)", red, (size_t)SHM_LRELU_RED_SLOTS * c * sizeof(double), (hipStream_t)stream);
     }
-    return SHM_OK;
-}
-
-// -------------------------------------------------------------------------------- pooling
-template <typename T>
-__global__ void avgpool2_kernel(const T* __restrict__ x, int ldx, T* __restrict__ y, int ldy, int h, int w, int c4, size_t total) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    int cl = (int)(i % c4);
-    size_t q = i / c4;                     // output pixel (n, oy, ox)
-    int wo = w >> 1, ho = h >> 1;
-    int ox = (int)(q % wo);
-    size_t t = q / wo;
-    int oy = (int)(t % ho);
-    size_t n = t / ho;
-    const T* b = x + ((n * h + 2 * oy) * w + 2 * ox) * ldx + cl * 4;
-    f32x4 s = ld4(b) + ld4(b + ldx) + ld4(b + (size_t)w * ldx) + ld4(b + (size_t)(w + 1) * ldx);
-    st4(y + q * ldy + cl * 4, s * 0.25f);
-}
-
-extern "C" int shm_avgpool2_fwd(const void* x, int ldx, void* y, int ldy, int batch, int h, int w, int c, int dtype, void* stream) {
-    SHM_REQUIRE(c % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0, SHM_E_SHAPE, "shm_avgpool2_fwd: channels/pitch must be multiples of 4");
-    SHM_REQUIRE(h % 2 == 0 && w % 2 == 0, SHM_E_SHAPE, "shm_avgpool2_fwd: odd size %dx%d", h, w);
-    size_t total = (size_t)batch * (h / 2) * (w / 2) * (c / 4);
-    if (total == 0) return SHM_OK;
-    SHM_DISPATCH(dtype, "shm_avgpool2_fwd",
-                 hipLaunchKernelGGL(avgpool2_kernel<T>, dim3(shm_cdiv((long)total, 256)), dim3(256), 0, (hipStream_t)stream, (const T*)x, ldx, (T*)y, ldy, h, w,
-                                    c / 4, total));
-    SHM_LAUNCH_CHECK("shm_avgpool2_fwd");
-    return SHM_OK;
-}
-
-// -------------------------------------------------------------------------- generator head
-// y[p] = lrelu(sum_c x[p][c] w[c] + b); C/4 lanes per pixel (power of two <= 64).
-// NORM: x is the UN-normalised activation of the last decoder block and the kernel applies its InstanceNorm on the fly
-// (xh = (x - mean) * inv + beta, the expression of in_apply_kernel: identical fp32 values) -- the apply pass of that block and
-// the normalised tensor do not exist.  grid.y = sample, npix = pixels per sample.
-template <typename T, bool NORM>
-__global__ __launch_bounds__(256) void head_fwd_kernel(const T* __restrict__ x, int ldx, const float* __restrict__ w, const float* __restrict__ bias,
-                                                       float* __restrict__ y, size_t npix, int c, float slope, const double* __restrict__ stats,
-                                                       const float* __restrict__ beta) {
-    const int lanes_c = c >> 2, PP = 256 / lanes_c;
-    const int pp = threadIdx.x / lanes_c, cl = threadIdx.x % lanes_c;
-    f32x4 wv = *(const f32x4*)(w + cl * 4);
-    const float b = bias ? bias[0] : 0.f;
-    float mean[4] = {0.f, 0.f, 0.f, 0.f}, inv[4] = {1.f, 1.f, 1.f, 1.f}, bt[4] = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (NORM) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int ch = cl * 4 + e;
-            mean[e] = (float)stats[((size_t)blockIdx.y * c + ch) * 2];
-            inv[e] = (float)stats[((size_t)blockIdx.y * c + ch) * 2 + 1];
-            bt[e] = beta[ch];
-        }
-        x += (size_t)blockIdx.y * npix * ldx;
-        y += (size_t)blockIdx.y * npix;
-    }
-    for (size_t p = (size_t)blockIdx.x * PP + pp; p < npix; p += (size_t)gridDim.x * PP) {
-        f32x4 xv = ld4(x + p * ldx + cl * 4);
-        if constexpr (NORM) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) xv[e] = (xv[e] - mean[e]) * inv[e] + bt[e];
-        }
-        float s = xv[0] * wv[0] + xv[1] * wv[1] + xv[2] * wv[2] + xv[3] * wv[3];
-        for (int o = lanes_c >> 1; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-        if (cl == 0) y[p] = shm_lrelu(s + b, slope);
-    }
-}
-
-static bool pow2_le64(int v) { return v >= 1 && v <= 64 && (v & (v - 1)) == 0; }
-
-extern "C" int shm_head_fwd(const void* x, int ldx, const float* w, const float* bias, float* y, size_t npix, int c, float slope, int dtype, void* stream) {
-    SHM_REQUIRE(c % 4 == 0 && pow2_le64(c / 4) && ldx % 4 == 0, SHM_E_SHAPE, "shm_head_fwd: channels %d unsupported", c);
-    if (npix == 0) return SHM_OK;
-    int PP = 256 / (c / 4);
-    long blocks = ((long)npix + PP - 1) / PP;
-    if (blocks > 8192) blocks = 8192;
-    SHM_DISPATCH(dtype, "shm_head_fwd",
-                 hipLaunchKernelGGL((head_fwd_kernel<T, false>), dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, (const T*)x, ldx, w, bias, y, npix, c, slope,
-                                    (const double*)nullptr, (const float*)nullptr));
-    SHM_LAUNCH_CHECK("shm_head_fwd");
-    return SHM_OK;
-}
-
-template <typename T, typename TG, bool NORM>
-__global__ __launch_bounds__(256) void head_bwd_kernel(const T* __restrict__ x, int ldx, const float* __restrict__ w, const float* __restrict__ y, const float* __restrict__ dy,
-                                                       TG* __restrict__ dx, int lddx, double* dpart, size_t npix, int c, float slope,
-                                                       const double* __restrict__ stats, const float* __restrict__ beta, float* __restrict__ dz_out) {
-    PixMap pm(c);
-    f32x4 wv = *(const f32x4*)(w + pm.cl * 4);
-    // NORM (see head_fwd_kernel): x un-normalised, grid.y = sample, npix = pixels per sample; dx is the gradient at the NORMALISED
-    // activation (what shm_in_bwd takes), the weight gradient uses the normalised value
-    float mean[4] = {0.f, 0.f, 0.f, 0.f}, inv[4] = {1.f, 1.f, 1.f, 1.f}, bt[4] = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (NORM) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int ch = pm.cl * 4 + e;
-            mean[e] = (float)stats[((size_t)blockIdx.y * c + ch) * 2];
-            inv[e] = (float)stats[((size_t)blockIdx.y * c + ch) * 2 + 1];
-            bt[e] = beta[ch];
-        }
-        x += (size_t)blockIdx.y * npix * ldx;
-        y += (size_t)blockIdx.y * npix;
-        dy += (size_t)blockIdx.y * npix;
-        if (dx) dx += (size_t)blockIdx.y * npix * lddx;
-        if (dz_out) dz_out += (size_t)blockIdx.y * npix;
-    }
-    auto norm = [&](f32x4 v) {
-        if constexpr (NORM) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = (v[e] - mean[e]) * inv[e] + bt[e];
-        }
-        return v;
-    };
-    double v[1][4] = {};
-    double dbs = 0.0;
-    constexpr int U = 4;                   // pixels in flight per thread; partial sums in fp32, accumulated in f64
-    const size_t stride = (size_t)gridDim.x * pm.PP;
-    size_t p = (size_t)blockIdx.x * pm.PP + pm.pp;
-    for (; p + (U - 1) * stride < npix; p += U * stride) {
-        float dz[U];
-        f32x4 xv[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const size_t q = p + u * stride;
-            const float g = dy[q];
-            dz[u] = y[q] > 0.f ? g : g * slope;
-            xv[u] = norm(ld4(x + q * ldx + pm.cl * 4));
-        }
-        float sw[4] = {0.f, 0.f, 0.f, 0.f}, sb = 0.f;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if (dx) st4(dx + (p + u * stride) * lddx + pm.cl * 4, wv * dz[u]);
-            if (dz_out && pm.cl == 0) dz_out[p + u * stride] = dz[u];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) sw[e] += xv[u][e] * dz[u];
-            sb += dz[u];
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[0][e] += (double)sw[e];
-        if (pm.cl == 0) dbs += (double)sb;
-    }
-    for (; p < npix; p += stride) {
-        const float g = dy[p];
-        const float dz = y[p] > 0.f ? g : g * slope;
-        const f32x4 xv = norm(ld4(x + p * ldx + pm.cl * 4));
-        if (dx) st4(dx + p * lddx + pm.cl * 4, wv * dz);
-        if (dz_out && pm.cl == 0) dz_out[p] = dz;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[0][e] += (double)xv[e] * (double)dz;
-        if (pm.cl == 0) dbs += (double)dz;
-    }
-    // staged per slot (slot = block % SHM_LRELU_RED_SLOTS): [slot][c] weight-gradient sums, then [slot] bias sums
-    const int slot = (int)((blockIdx.x + blockIdx.y) % SHM_LRELU_RED_SLOTS);
-    double* slotw = dpart + (size_t)slot * c;
-    block_reduce_atomic<1>(v, pm, slotw, c, true);
-    dbs = shm_wave_sum(dbs);
-    if ((threadIdx.x & 63) == 0 && dbs != 0.0) atomicAdd(dpart + (size_t)SHM_LRELU_RED_SLOTS * c + slot, dbs);
-}
-
-__global__ void head_fold_kernel(const double* __restrict__ dpart, double* __restrict__ dw_acc, double* __restrict__ db_acc, int c) {
-    const int ch = blockIdx.x * blockDim.x + threadIdx.x;
-    if (ch > c) return;
-    double s = 0.0;
-    if (ch < c) {
-        for (int i = 0; i < SHM_LRELU_RED_SLOTS; ++i) s += dpart[(size_t)i * c + ch];
-        dw_acc[ch] += s;
-    } else {
-        for (int i = 0; i < SHM_LRELU_RED_SLOTS; ++i) s += dpart[(size_t)SHM_LRELU_RED_SLOTS * c + i];
-        db_acc[0] += s;
-    }
-}
-
-extern "C" int shm_head_bwd(const void* x, int ldx, const float* w, const float* y, const float* dy, void* dx,
-                            int lddx, double* dw_acc, double* db_acc, double* red, size_t npix, int c, float slope, int dtype, void* stream) {
-    SHM_REQUIRE(c % 4 == 0 && pow2_le64(c / 4) && ldx % 4 == 0 && lddx % 4 == 0, SHM_E_SHAPE, "shm_head_bwd: channels %d unsupported", c);
-    SHM_REQUIRE(red && dw_acc && db_acc, SHM_E_SHAPE, "shm_head_bwd: null accumulator / scratch");
-    if (npix == 0) return SHM_OK;
-    int r = shm_zero(red, (size_t)SHM_LRELU_RED_SLOTS * (c + 1) * sizeof(double), stream);
-    if (r) return r;
-    int PP = 256 / (c / 4);
-    long blocks = ((long)npix + (long)PP * 8 - 1) / ((long)PP * 8);
-    if (blocks > 4096) blocks = 4096;
-    if (blocks < 1) blocks = 1;
-    SHM_DISPATCH_G(dtype, "shm_head_bwd",
-                 hipLaunchKernelGGL((head_bwd_kernel<T, TG, false>), dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, (const T*)x, ldx, w, y, dy, (TG*)dx, lddx, red,
-                                    npix, c, slope, (const double*)nullptr, (const float*)nullptr, (float*)nullptr));
-    SHM_LAUNCH_CHECK("shm_head_bwd");
-    hipLaunchKernelGGL(head_fold_kernel, dim3(shm_cdiv(c + 1, 256)), dim3(256), 0, (hipStream_t)stream, (const double*)red, dw_acc, db_acc, c);
-    SHM_LAUNCH_CHECK("shm_head_bwd(fold)");
-    return SHM_OK;
-}
-
-// The generator head on the UN-normalised activation of the last decoder block + that block's InstanceNorm statistics: the
-// block's apply pass (a read and a write of the largest activation of the network) is folded into the head's forward and backward.
-extern "C" int shm_head_in_fwd(const void* a, int lda, const double* stats, const float* beta, const float* w, const float* bias, float* y, int batch,
-                               int hw, int c, float slope, int dtype, void* stream) {
-    SHM_REQUIRE(c % 4 == 0 && pow2_le64(c / 4) && lda % 4 == 0, SHM_E_SHAPE, "shm_head_in_fwd: channels %d unsupported", c);
-    SHM_REQUIRE(a && stats && beta && w && y, SHM_E_SHAPE, "shm_head_in_fwd: null pointer");
-    if (batch == 0 || hw == 0) return SHM_OK;
-    int PP = 256 / (c / 4);
-    long blocks = ((long)hw + PP - 1) / PP;
-    const long cap = 8192 / batch > 1 ? 8192 / batch : 1;
-    if (blocks > cap) blocks = cap;
-    SHM_DISPATCH(dtype, "shm_head_in_fwd",
-                 hipLaunchKernelGGL((head_fwd_kernel<T, true>), dim3((int)blocks, batch), dim3(256), 0, (hipStream_t)stream, (const T*)a, lda, w, bias, y,
-                                    (size_t)hw, c, slope, stats, beta));
-    SHM_LAUNCH_CHECK("shm_head_in_fwd");
-    return SHM_OK;
-}
-
-extern "C" int shm_head_in_bwd(const void* a, int lda, const double* stats, const float* beta, const float* w, const float* y, const float* dy, void* dx,
-                               int lddx, float* dz_out, double* dw_acc, double* db_acc, double* red, int batch, int hw, int c, float slope, int dtype,
-                               void* stream) {
-    SHM_REQUIRE(c % 4 == 0 && pow2_le64(c / 4) && lda % 4 == 0 && (!dx || lddx % 4 == 0), SHM_E_SHAPE, "shm_head_in_bwd: channels %d unsupported", c);
-    SHM_REQUIRE(dx || dz_out, SHM_E_SHAPE, "shm_head_in_bwd: neither dx nor dz_out");
-    SHM_REQUIRE(a && stats && beta && red && dw_acc && db_acc, SHM_E_SHAPE, "shm_head_in_bwd: null pointer");
-    if (batch == 0 || hw == 0) return SHM_OK;
-    int r = shm_zero(red, (size_t)SHM_LRELU_RED_SLOTS * (c + 1) * sizeof(double), stream);
-    if (r) return r;
-    int PP = 256 / (c / 4);
-    long blocks = ((long)hw + (long)PP * 8 - 1) / ((long)PP * 8);
-    const long cap = 4096 / batch > 1 ? 4096 / batch : 1;
-    if (blocks > cap) blocks = cap;
-    if (blocks < 1) blocks = 1;
-    SHM_DISPATCH_G(dtype, "shm_head_in_bwd",
-                 hipLaunchKernelGGL((head_bwd_kernel<T, TG, true>), dim3((int)blocks, batch), dim3(256), 0, (hipStream_t)stream, (const T*)a, lda, w, y, dy, (TG*)dx,
-                                    lddx, red, (size_t)hw, c, slope, stats, beta, dz_out));
-    SHM_LAUNCH_CHECK("shm_head_in_bwd");
-    hipLaunchKernelGGL(head_fold_kernel, dim3(shm_cdiv(c + 1, 256)), dim3(256), 0, (hipStream_t)stream, (const double*)red, dw_acc, db_acc, c);
-    SHM_LAUNCH_CHECK("shm_head_in_bwd(fold)");
-    return SHM_OK;
-}
-
-// ------------------------------------------------------------------------ PatchGAN logits
-__device__ __forceinline__ float block_sum_256(float v) {
-    __shared__ float ws[4];
-    v = shm_wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ws[0] + ws[1] + ws[2] + ws[3];
-}
-
-// one block per output pixel
-template <typename T>
-__global__ __launch_bounds__(256) void patch_fwd_kernel(const T* __restrict__ x, int ldx, const float* __restrict__ w, float* __restrict__ y, int h, int wd, int c, float slope) {
-    const int q = blockIdx.x;              // (n, i, j)
-    const int j = q % wd, t = q / wd;
-    const int i = t % h, n = t / h;
-    const int c4 = c >> 2;
-    float s = 0.f;
-    for (int it = threadIdx.x; it < 9 * c4; it += 256) {
-        int tap = it / c4, cl = it - tap * c4;
-        int ii = i + tap / 3 - 1, jj = j + tap % 3 - 1;
-        if ((unsigned)ii < (unsigned)h && (unsigned)jj < (unsigned)wd) {
-            f32x4 xv = ld4(x + ((size_t)(n * h + ii) * wd + jj) * ldx + cl * 4);
-            f32x4 wv = *(const f32x4*)(w + (size_t)tap * c + cl * 4);
-            s += xv[0] * wv[0] + xv[1] * wv[1] + xv[2] * wv[2] + xv[3] * wv[3];
-        }
-    }
-    s = block_sum_256(s);
-    if (threadIdx.x == 0) y[q] = shm_lrelu(s, slope);
-}
-
-extern "C" int shm_patch_fwd(const void* x, int ldx, const float* w, float* y, int batch, int h, int wd, int c, float slope, int dtype, void* stream) {
-    SHM_REQUIRE(c % 4 == 0 && ldx % 4 == 0, SHM_E_SHAPE, "shm_patch_fwd: channels must be a multiple of 4");
-    int total = batch * h * wd;
-    if (total == 0) return SHM_OK;
-    SHM_DISPATCH(dtype, "shm_patch_fwd", hipLaunchKernelGGL(patch_fwd_kernel<T>, dim3(total), dim3(256), 0, (hipStream_t)stream, (const T*)x, ldx, w, y, h, wd, c, slope));
-    SHM_LAUNCH_CHECK("shm_patch_fwd");
-    return SHM_OK;
-}
-
-__global__ void patch_dz_kernel(const float* __restrict__ y, const float* __restrict__ dy, float* __restrict__ dz, int n, float slope) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dz[i] = y[i] > 0.f ? dy[i] : dy[i] * slope;
-}
-
-// dx[n,i,j,c] = sum_tap dz[n, i-(kh-1), j-(kw-1)] * w[tap][c]
-template <typename T>
-__global__ void patch_dx_kernel(const float* __restrict__ dz, const float* __restrict__ w, T* __restrict__ dx, int lddx, int h, int wd, int c4, size_t total) {
-    size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= total) return;
-    int cl = (int)(idx % c4);
-    size_t q = idx / c4;
-    int j = (int)(q % wd);
-    size_t t = q / wd;
-    int i = (int)(t % h);
-    size_t n = t / h;
-    f32x4 s = {0.f, 0.f, 0.f, 0.f};
-    for (int tap = 0; tap < 9; ++tap) {
-        int ii = i - (tap / 3 - 1), jj = j - (tap % 3 - 1);
-        if ((unsigned)ii < (unsigned)h && (unsigned)jj < (unsigned)wd) {
-            float g = dz[(n * h + ii) * wd + jj];
-            s += *(const f32x4*)(w + (size_t)tap * c4 * 4 + cl * 4) * g;
-        }
-    }
-    st4(dx + q * lddx + cl * 4, s);
-}
-
-// dw[tap][c] = sum_{n,i,j} x[n,i+kh-1,j+kw-1,c] * dz[n,i,j]; block = (tap, 64 channels), 16 pixel groups
-template <typename T>
-__global__ __launch_bounds__(1024) void patch_dw_kernel(const T* __restrict__ x, int ldx, const float* __restrict__ dz, float* __restrict__ dw, int batch, int h, int wd, int c) {
-    __shared__ double red[16][64];
-    const int tap = blockIdx.x, ch = blockIdx.y * 64 + (threadIdx.x & 63), g = threadIdx.x >> 6;
-    const int dh = tap / 3 - 1, dwv = tap % 3 - 1;
-    double s = 0.0;
-    if (ch < c) {
-        // pixel group g takes samples g, g + 16, ...; the tap's valid output window is a rectangle, so the inner loop has no index
-        // division and no branch and its loads are independent (the flat loop over pixels it replaces ran one dependent load per
-        // ~1 us: 193 us for 12.6 MB)
-        const int i0 = dh < 0 ? -dh : 0, i1 = dh > 0 ? h - dh : h;
-        const int j0 = dwv < 0 ? -dwv : 0, j1 = dwv > 0 ? wd - dwv : wd;
-        for (int n = g; n < batch; n += 16) {
-            const T* xn = x + (size_t)n * h * wd * ldx + ch;
-            const float* dzn = dz + (size_t)n * h * wd;
-            for (int i = i0; i < i1; ++i) {
-                const T* xr = xn + (size_t)((i + dh) * wd + dwv) * ldx;
-                const float* dr = dzn + i * wd;
-#pragma unroll 8
-                for (int j = j0; j < j1; ++j) s += (double)(float)xr[(size_t)j * ldx] * (double)dr[j];
-            }
-        }
-    }
-    red[g][threadIdx.x & 63] = s;
-    __syncthreads();
-    if (g == 0 && ch < c) {
-        double t = 0.0;
-        for (int k = 0; k < 16; ++k) t += red[k][threadIdx.x & 63];
-        dw[(size_t)tap * c + ch] = (float)t;
-    }
-}
-
-extern "C" int shm_patch_bwd(const void* x, int ldx, const float* w, const float* y, const float* dy, float* dz,
-                             void* dx, int lddx, float* dw, int batch, int h, int wd, int c, float slope, int dtype, void* stream) {
-    SHM_REQUIRE(c % 4 == 0 && ldx % 4 == 0 && lddx % 4 == 0, SHM_E_SHAPE, "shm_patch_bwd: channels must be a multiple of 4");
-    int npx = batch * h * wd;
-    if (npx == 0) return SHM_OK;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(patch_dz_kernel, dim3(shm_cdiv(npx, 256)), dim3(256), 0, st, y, dy, dz, npx, slope);
-    SHM_LAUNCH_CHECK("shm_patch_bwd(dz)");
-    size_t total = (size_t)npx * (c / 4);
-    SHM_DISPATCH_G(dtype, "shm_patch_bwd",
-                 hipLaunchKernelGGL(patch_dx_kernel<TG>, dim3(shm_cdiv((long)total, 256)), dim3(256), 0, st, (const float*)dz, w, (TG*)dx, lddx, h, wd, c / 4, total));
-    SHM_LAUNCH_CHECK("shm_patch_bwd(dx)");
-    if (dw) {
-        SHM_DISPATCH_G(dtype, "shm_patch_bwd",
-                     hipLaunchKernelGGL(patch_dw_kernel<T>, dim3(9, shm_cdiv(c, 64)), dim3(1024), 0, st, (const T*)x, ldx, (const float*)dz, dw, batch, h, wd, c));
-        SHM_LAUNCH_CHECK("shm_patch_bwd(dw)");
-    }
-    return SHM_OK;
-}
-
-// --------------------------------------------------------------------------------- Dense(5)
-constexpr int DENSE_MAX_OUT = 8;
-
-template <typename T>
-__global__ __launch_bounds__(256) void dense_fwd_kernel(const T* __restrict__ x, const float* __restrict__ w, float* __restrict__ y, int k, int nout) {
-    const int n = blockIdx.x;
-    float acc[DENSE_MAX_OUT] = {};
-    const T* xr = x + (size_t)n * k;
-    if (nout == 5 && (k & 3) == 0 && ((size_t)xr & (4 * sizeof(T) - 1)) == 0 && ((size_t)w & 15) == 0) {
-        // the classifier's shape (Dense(5)): four inputs x five outputs per iteration = one 8/16-byte load of x and five 16-byte
-        // loads of w per lane, eight of them in flight (the scalar loop below is one dependent 4-byte load chain per lane:
-        // 233 us for 96 samples of 65536 inputs, where the data is 14 MB)
-        const int k4 = k >> 2;
-#pragma unroll 2
-        for (int i4 = threadIdx.x; i4 < k4; i4 += 256) {
-            float xv[4];
-            if constexpr (sizeof(T) == 4) {
-                const f32x4 v = *(const f32x4*)(xr + 4 * (size_t)i4);
-                xv[0] = v[0], xv[1] = v[1], xv[2] = v[2], xv[3] = v[3];
-            } else {
-                const uint2 v = *(const uint2*)(xr + 4 * (size_t)i4);
-                xv[0] = __builtin_bit_cast(float, v.x << 16), xv[1] = __builtin_bit_cast(float, v.x & 0xffff0000u);
-                xv[2] = __builtin_bit_cast(float, v.y << 16), xv[3] = __builtin_bit_cast(float, v.y & 0xffff0000u);
-            }
-            const f32x4* wp = (const f32x4*)(w + 20 * (size_t)i4);
-            float wv[20];
-#pragma unroll
-            for (int q = 0; q < 5; ++q) {
-                const f32x4 t = wp[q];
-                wv[4 * q] = t[0], wv[4 * q + 1] = t[1], wv[4 * q + 2] = t[2], wv[4 * q + 3] = t[3];
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int j = 0; j < 5; ++j) acc[j] += xv[e] * wv[5 * e + j];
-        }
-    } else {
-        for (int i = threadIdx.x; i < k; i += 256) {
-            float xv = (float)xr[i];
-            for (int j = 0; j < nout; ++j) acc[j] += xv * w[(size_t)i * nout + j];
-        }
-    }
-    for (int j = 0; j < nout; ++j) {
-        float s = block_sum_256(acc[j]);
-        if (threadIdx.x == 0) y[(size_t)n * nout + j] = s;
-    }
-}
-
-extern "C" int shm_dense_fwd(const void* x, const float* w, float* y, int batch, int k, int nout, int dtype, void* stream) {
-    SHM_REQUIRE(nout >= 1 && nout <= DENSE_MAX_OUT, SHM_E_SHAPE, "shm_dense_fwd: nout %d > %d", nout, DENSE_MAX_OUT);
-    if (batch == 0) return SHM_OK;
-    SHM_DISPATCH(dtype, "shm_dense_fwd", hipLaunchKernelGGL(dense_fwd_kernel<T>, dim3(batch), dim3(256), 0, (hipStream_t)stream, (const T*)x, w, y, k, nout));
-    SHM_LAUNCH_CHECK("shm_dense_fwd");
-    return SHM_OK;
-}
-
-// thread per k: dx[n][k] += sum_j dy[n][j] w[k][j];  dw[k][j] = sum_n x[n][k] dy[n][j]
-template <typename T, typename TG>
-__global__ __launch_bounds__(256) void dense_bwd_kernel(const T* __restrict__ x, const float* __restrict__ w, const float* __restrict__ dy, TG* __restrict__ dx,
-                                                        float* __restrict__ dw, int batch, int k, int nout) {
-    extern __shared__ float sdy[];          // [batch][nout]
-    for (int i = threadIdx.x; i < batch * nout; i += 256) sdy[i] = dy[i];
-    __syncthreads();
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= k) return;
-    float wv[DENSE_MAX_OUT], acc[DENSE_MAX_OUT] = {};
-    for (int j = 0; j < nout; ++j) wv[j] = w[(size_t)i * nout + j];
-    int n = 0;
-    for (; n + 4 <= batch; n += 4) {                  // four samples per iteration: eight independent loads in flight before the stores
-        float xv[4], dv[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            xv[u] = (float)x[(size_t)(n + u) * k + i];
-            dv[u] = (float)dx[(size_t)(n + u) * k + i];
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            float s = 0.f;
-            for (int j = 0; j < nout; ++j) {
-                float g = sdy[(n + u) * nout + j];
-                s += g * wv[j];
-                acc[j] += xv[u] * g;
-            }
-            dx[(size_t)(n + u) * k + i] = (TG)(dv[u] + s);
-        }
-    }
-    for (; n < batch; ++n) {
-        float xv = (float)x[(size_t)n * k + i];
-        float s = 0.f;
-        for (int j = 0; j < nout; ++j) {
-            float g = sdy[n * nout + j];
-            s += g * wv[j];
-            acc[j] += xv * g;
-        }
-        dx[(size_t)n * k + i] = (TG)((float)dx[(size_t)n * k + i] + s);
-    }
-    if (dw)
-        for (int j = 0; j < nout; ++j) dw[(size_t)i * nout + j] = acc[j];
-}
-
-extern "C" int shm_dense_bwd(const void* x, const float* w, const float* dy, void* dx, float* dw, int batch, int k, int nout, int dtype, void* stream) {
-    SHM_REQUIRE(nout >= 1 && nout <= DENSE_MAX_OUT, SHM_E_SHAPE, "shm_dense_bwd: nout %d > %d", nout, DENSE_MAX_OUT);
-    SHM_REQUIRE((size_t)batch * nout * 4 <= 48 * 1024, SHM_E_SHAPE, "shm_dense_bwd: batch %d too large", batch);
-    if (batch == 0 || k == 0) return SHM_OK;
-    SHM_DISPATCH_G(dtype, "shm_dense_bwd",
-                 hipLaunchKernelGGL((dense_bwd_kernel<T, TG>), dim3(shm_cdiv(k, 256)), dim3(256), (size_t)batch * nout * 4, (hipStream_t)stream, (const T*)x, w,
-                                    dy, (TG*)dx, dw, batch, k, nout));
-    SHM_LAUNCH_CHECK("shm_dense_bwd");
-    return SHM_OK;
-}
-
-// --------------------------------------------------------------------------- dropout mask
-template <typename T>
-__global__ void mul_mask_kernel(const T* __restrict__ x, const float* __restrict__ m, T* __restrict__ y, size_t n4, float scale) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n4) return;
-    f32x4 a = ld4(x + i * 4), b = ((const f32x4*)m)[i];
-    st4(y + i * 4, a * b * scale);
-}
-
-extern "C" int shm_mul_mask(const void* x, const float* mask, void* y, size_t n, float scale, int dtype, void* stream) {
-    SHM_REQUIRE(n % 4 == 0, SHM_E_SHAPE, "shm_mul_mask: n must be a multiple of 4");
-    if (n == 0) return SHM_OK;
-    SHM_DISPATCH(dtype, "shm_mul_mask",
-                 hipLaunchKernelGGL(mul_mask_kernel<T>, dim3(shm_cdiv((long)(n / 4), 256)), dim3(256), 0, (hipStream_t)stream, (const T*)x, mask, (T*)y, n / 4, scale));
-    SHM_LAUNCH_CHECK("shm_mul_mask");
-    return SHM_OK;
-}
-
-// ------------------------------------------------------ live attention branch (SHM.py:404-412, 290-293, 359)
-// MaxPooling2D(pool k x k, 'same' on sizes that are multiples of k) of the one-channel mask, written as channel 0 of an
-// activation tensor of pitch ld (the other channels zero): the 1 -> C convolution of attention_layer then runs on the
-// ordinary tap GEMM.  k = 1 copies (attention_layer(pool=False)).
-template <typename T>
-__global__ void mask_pool_pack_kernel(const float* __restrict__ m, T* __restrict__ dst, int ld, int s, int k, size_t total) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;          // output pixel (b, y, x)
-    if (i >= total) return;
-    const int so = s / k;
-    const int x = (int)(i % so), y = (int)((i / so) % so);
-    const size_t b = i / ((size_t)so * so);
-    const float* src = m + (b * s + (size_t)y * k) * s + (size_t)x * k;
-    float v = src[0];
-    for (int dy = 0; dy < k; ++dy)
-        for (int dx = 0; dx < k; ++dx) v = fmaxf(v, src[(size_t)dy * s + dx]);
-    T* o = dst + i * ld;
-    o[0] = (T)v;
-    for (int c = 1; c < ld; ++c) o[c] = (T)0.f;
-}
-
-extern "C" int shm_mask_pool_pack(const float* mask, void* dst, int lddst, int batch, int s, int k, int dtype, void* stream) {
-    SHM_REQUIRE(mask && dst && k >= 1 && s % k == 0 && lddst >= 1, SHM_E_SHAPE, "shm_mask_pool_pack: bad shape (s %d, k %d)", s, k);
-    const size_t total = (size_t)batch * (s / k) * (s / k);
-    if (total == 0) return SHM_OK;
-    SHM_DISPATCH(dtype, "shm_mask_pool_pack",
-                 hipLaunchKernelGGL(mask_pool_pack_kernel<T>, dim3(shm_cdiv((long)total, 256)), dim3(256), 0, (hipStream_t)stream, mask, (T*)dst, lddst, s, k, total));
-    SHM_LAUNCH_CHECK("shm_mask_pool_pack");
-    return SHM_OK;
-}
-
-// out[i] = a[i] + b[(i0 + i) % nb]  over images of `per` elements each: the skip tensor plus the attention map of its sample
-// (`down_k + attn_k`, SHM.py:290-293; `x + attn_disc`, SHM.py:359), the attention map shared by every copy of a sample in the
-// batched plan (image i of the batch belongs to sample (i0 + i) % nb).
-template <typename T>
-__global__ void add_bcast_kernel(const T* __restrict__ a, const T* __restrict__ b, T* __restrict__ out, size_t per4, int nb, int i0, size_t total4) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total4) return;
-    const size_t img = i / per4, r = i - img * per4;
-    const size_t j = ((size_t)i0 + img) % (size_t)nb;
-    st4(out + i * 4, ld4(a + i * 4) + ld4(b + (j * per4 + r) * 4));
-}
-
-extern "C" int shm_add_bcast(const void* a, const void* b, void* out, int nimg, size_t per, int nb, int i0, int dtype, void* stream) {
-    SHM_REQUIRE(a && b && out && per % 4 == 0 && nb >= 1 && i0 >= 0, SHM_E_SHAPE, "shm_add_bcast: bad arguments");
-    const size_t total4 = (size_t)nimg * per / 4;
-    if (total4 == 0) return SHM_OK;
-    SHM_DISPATCH(dtype, "shm_add_bcast",
-                 hipLaunchKernelGGL(add_bcast_kernel<T>, dim3(shm_cdiv((long)total4, 256)), dim3(256), 0, (hipStream_t)stream, (const T*)a, (const T*)b, (T*)out,
-                                    per / 4, nb, i0, total4));
-    SHM_LAUNCH_CHECK("shm_add_bcast");
-    return SHM_OK;
-}
-
-// dst[j] (+)= sum over the images i of src with (i0 + i) % nb == j: the gradient of the broadcast above (fp32 accumulation).
-template <typename T>
-__global__ void sum_groups_kernel(const T* __restrict__ src, T* __restrict__ dst, size_t per4, int nimg, int nb, int i0, int accumulate, size_t total4) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;          // (sample j, element r)
-    if (i >= total4) return;
-    const size_t j = i / per4, r = i - j * per4;
-    f32x4 s = accumulate ? ld4(dst + i * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
-    int first = (int)((j + (size_t)nb - (size_t)(i0 % nb)) % (size_t)nb);
-    for (int img = first; img < nimg; img += nb) s += ld4(src + ((size_t)img * per4 + r) * 4);
-    st4(dst + i * 4, s);
-}
-
-extern "C" int shm_sum_groups(const void* src, void* dst, int nimg, size_t per, int nb, int i0, int accumulate, int dtype, void* stream) {
-    SHM_REQUIRE(src && dst && per % 4 == 0 && nb >= 1 && i0 >= 0, SHM_E_SHAPE, "shm_sum_groups: bad arguments");
-    const size_t total4 = (size_t)nb * per / 4;
-    if (total4 == 0) return SHM_OK;
-    SHM_DISPATCH(dtype, "shm_sum_groups",
-                 hipLaunchKernelGGL(sum_groups_kernel<T>, dim3(shm_cdiv((long)total4, 256)), dim3(256), 0, (hipStream_t)stream, (const T*)src, (T*)dst, per / 4, nimg,
-                                    nb, i0, accumulate, total4));
-    SHM_LAUNCH_CHECK("shm_sum_groups");
-    return SHM_OK;
-}
-
-// ------------------------------------------------ input gradient of a first layer, summed over input channels
-// The step never needs the per-channel input gradient of the two first layers, only sums over input channels:
-//   generator (cyclic pass, SHM.py:576-580): d genY[b,p] = sum_k sum_{j != k, flags[j]} dX_k[b,p,j]
-//   discriminator (yuv_to_rgb backward):      d Y[i,p]   = sum_{c<3} dX[i,p,c]
-// and conv is linear, so summing the WEIGHTS over those input channels first turns a 64 -> 10 (or 3) channel
-// dgrad -- which fills 10 (3) columns of a 64-wide MFMA tile -- into a 64 -> 1 stencil that is HBM-bound:
-//   out[b,y,x] (+)= sum_k sum_{taps} sum_co dz[k*batch+b, oy, ox, co] * weff[k][tap][co]
-__global__ void weff_kernel(const float* __restrict__ w, int cin, int cout, unsigned mask, float* __restrict__ weff) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;       // (tap, co)
-    if (i >= 9 * cout) return;
-    const int t = i / cout, co = i - t * cout;
-    float s = 0.f;
-    for (int j = 0; j < cin; ++j)
-        if ((mask >> j) & 1u) s += w[((size_t)t * cin + j) * cout + co];
-    weff[i] = s;
-}
-
-extern "C" int shm_sum_input_channels(const float* w, int cin, int cout, unsigned mask, float* weff, void* stream) {
-    SHM_REQUIRE(w && weff && cin >= 1 && cin <= 32 && cout >= 1, SHM_E_SHAPE, "shm_sum_input_channels: bad arguments");
-    hipLaunchKernelGGL(weff_kernel, dim3(shm_cdiv(9 * cout, 256)), dim3(256), 0, (hipStream_t)stream, w, cin, cout, mask, weff);
-    SHM_LAUNCH_CHECK("shm_sum_input_channels");
-    return SHM_OK;
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void dgrad_sum1_kernel(const T* __restrict__ dz, int lddz, const float* __restrict__ weff, float* __restrict__ out, int nk,
-                                                         int batch, int hi, int wi, int ho, int wo, int c, int stride, int pt, int pl, int accumulate) {
-    const int lanes_c = c >> 2, PP = 256 / lanes_c;
-    const int pp = threadIdx.x / lanes_c, cl = threadIdx.x - pp * lanes_c;
-    const size_t npx = (size_t)batch * hi * wi;
-    const size_t q = (size_t)blockIdx.x * PP + pp;             // output pixel (b, y, x)
-    const bool live = q < npx && pp < PP;
-    const size_t qq = live ? q : 0;
-    const int x = (int)(qq % wi);
-    const size_t t = qq / wi;
-    const int y = (int)(t % hi), b = (int)(t / hi);
-    float s = 0.f;
-    for (int k = 0; k < nk; ++k) {
-        const T* zi = dz + (size_t)(k * batch + b) * ho * wo * lddz + cl * 4;
-        const float* wk = weff + (size_t)k * 9 * c + cl * 4;
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh) {
-            const int ny = y + pt - kh;
-            if (ny < 0 || (stride == 2 && (ny & 1))) continue;
-            const int oy = stride == 2 ? ny >> 1 : ny;
-            if (oy >= ho) continue;
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw) {
-                const int nx = x + pl - kw;
-                if (nx < 0 || (stride == 2 && (nx & 1))) continue;
-                const int ox = stride == 2 ? nx >> 1 : nx;
-                if (ox >= wo) continue;
-                const f32x4 g = ld4(zi + ((size_t)oy * wo + ox) * lddz);
-                const f32x4 wv = *(const f32x4*)(wk + (kh * 3 + kw) * c);
-                s += g[0] * wv[0] + g[1] * wv[1] + g[2] * wv[2] + g[3] * wv[3];
-            }
-        }
-    }
-    for (int o = lanes_c >> 1; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if (live && cl == 0) out[q] = accumulate ? out[q] + s : s;
-}
-
-// Tiled form (round 2): the pixel-per-thread-group kernel above reads every dz pixel nine times (once per output pixel it
-// contributes to: 0.6 TB/s HBM-side, 290-560 us per launch in the r02 profiles).  Here a block owns a 16 x 16 tile of OUTPUT
-// pixels: phase A turns every dz pixel the tile touches into its nine per-tap dot products P[t] = sum_k sum_c dz_k[.., c] *
-// weff_k[t][c] (each dz pixel read once per block; weights staged in LDS), phase B gathers out[y, x] = sum of the valid taps'
-// P entries from LDS.  Same sums, different order (fp32 accumulation; the parity tests hold it to 1e-5).
-template <typename T>
-__global__ __launch_bounds__(256) void dgrad_sum1_tiled_kernel(const T* __restrict__ dz, int lddz, const float* __restrict__ weff, float* __restrict__ out,
-                                                               int nk, int batch, int hi, int wi, int ho, int wo, int c, int stride, int pt, int pl,
-                                                               int accumulate) {
-    constexpr int TO = 16, RMAX = TO + 2;
-    __shared__ float P[9][RMAX * RMAX];
-    __shared__ __attribute__((aligned(16))) float wl[5 * 9 * 64];
-    const int lanes_c = c >> 2, PP = 256 / lanes_c;
-    const int pp = threadIdx.x / lanes_c, cl = threadIdx.x - pp * lanes_c;
-    const int tiles_x = (wi + TO - 1) / TO, tiles_y = (hi + TO - 1) / TO;
-    const int b = blockIdx.x / (tiles_x * tiles_y), tr = blockIdx.x - b * (tiles_x * tiles_y);
-    const int y0 = (tr / tiles_x) * TO, x0 = (tr % tiles_x) * TO;
-    // dz region the tile's outputs touch: oy = (y + pt - kh) / stride for kh in 0..2
-    auto fdiv = [](int a, int d) { return a >= 0 ? a / d : -((-a + d - 1) / d); };
-    const int oy_lo = fdiv(y0 + pt - 2, stride), oy_hi = fdiv(y0 + TO - 1 + pt, stride);
-    const int ox_lo = fdiv(x0 + pl - 2, stride), ox_hi = fdiv(x0 + TO - 1 + pl, stride);
-    const int R = oy_hi - oy_lo + 1, Cn = ox_hi - ox_lo + 1;             // <= 18 each
-    for (int i = threadIdx.x; i < nk * 9 * c; i += 256) wl[i] = weff[i];
-    __syncthreads();
-    // ---- phase A
-    if (pp < PP) {
-        for (int j = pp; j < R * Cn; j += PP) {
-            const int r = j / Cn, q = j - r * Cn;
-            const int oy = oy_lo + r, ox = ox_lo + q;
-            float s[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            if ((unsigned)oy < (unsigned)ho && (unsigned)ox < (unsigned)wo) {
-                for (int k = 0; k < nk; ++k) {
-                    const f32x4 g = ld4(dz + (((size_t)(k * batch + b) * ho + oy) * wo + ox) * lddz + cl * 4);
-                    const float* wk = wl + k * 9 * c + cl * 4;
-#pragma unroll
-                    for (int t = 0; t < 9; ++t) {
-                        const f32x4 wv = *(const f32x4*)(wk + t * c);
-                        s[t] += g[0] * wv[0] + g[1] * wv[1] + g[2] * wv[2] + g[3] * wv[3];
-                    }
-                }
-            }
-#pragma unroll
-            for (int t = 0; t < 9; ++t) {
-                float v = s[t];
-                for (int o = lanes_c >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-                if (cl == 0) P[t][r * RMAX + q] = v;
-            }
-        }
-    }
-    __syncthreads();
-    // ---- phase B: one output pixel per thread
-    const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
-    const int y = y0 + ty, x = x0 + tx;
-    if (y < hi && x < wi) {
-        float v = 0.f;
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh) {
-            const int ny = y + pt - kh;
-            if (ny < 0 || (stride == 2 && (ny & 1))) continue;
-            const int oy = stride == 2 ? ny >> 1 : ny;
-            if (oy >= ho) continue;
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw) {
-                const int nx = x + pl - kw;
-                if (nx < 0 || (stride == 2 && (nx & 1))) continue;
-                const int ox = stride == 2 ? nx >> 1 : nx;
-                if (ox >= wo) continue;
-                v += P[kh * 3 + kw][(oy - oy_lo) * RMAX + (ox - ox_lo)];
-            }
-        }
-        const size_t qo = ((size_t)b * hi + y) * wi + x;
-        out[qo] = accumulate ? out[qo] + v : v;
-    }
-}
-
-// MFMA form of the tiled kernel's phase A (round 4).  P[pixel][tap] = sum_k sum_c dz_k[pixel][c] * weff_k[tap][c] is a GEMM with M = the dz pixels of
-// the tile (<= 18 x 18), N = 9 taps (16 MFMA columns) and K = nk * c: the phase above spends 36 FMAs and 36 shuffle-adds per lane and pixel on it
-// (150 us in bf16 / 215 us in fp32 for a launch that moves 335 / 671 MB: vector bound, 2.2-3.1 TB/s).  Here a wave takes 16 pixels per step;
-// a lane's 16-byte global load IS its A fragment (bf16: eight channels = one v_mfma_f32_16x16x32_bf16 K block; fp32: four channels = four
-// v_mfma_f32_16x16x4_f32 with the channel permutation of tapgemm_wreg_f32_kernel), the weights sit in registers as the B operand -- in bf16 split
-// into a high and a low bf16 part (two MFMAs), which keeps the fp32 weights' accuracy (2^-17) -- and the accumulator's four pixels of tap l15 go
-// straight into the P image.  Phase B is unchanged.  c % 32 == 0 (bf16) / c % 16 == 0 (fp32), nk * c <= 320.
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-template <typename T, int NKC>          // NKC = nk * c / (sizeof(T) == 2 ? 32 : 16): K blocks, compile time so that the weights stay in registers
-__global__ __launch_bounds__(256) void dgrad_sum1_mfma_kernel(const T* __restrict__ dz, int lddz, const float* __restrict__ weff, float* __restrict__ out,
-                                                              int nk, int batch, int hi, int wi, int ho, int wo, int c, int stride, int pt, int pl,
-                                                              int accumulate) {
-    constexpr int TO = 16, RMAX = TO + 2, KB = sizeof(T) == 2 ? 32 : 16;
-    __shared__ float P[9][RMAX * RMAX];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, lq = lane >> 4;
-    const int tiles_x = (wi + TO - 1) / TO, tiles_y = (hi + TO - 1) / TO;
-    const int b = blockIdx.x / (tiles_x * tiles_y), tr = blockIdx.x - b * (tiles_x * tiles_y);
-    const int y0 = (tr / tiles_x) * TO, x0 = (tr % tiles_x) * TO;
-    auto fdiv = [](int a, int d) { return a >= 0 ? a / d : -((-a + d - 1) / d); };
-    const int oy_lo = fdiv(y0 + pt - 2, stride), oy_hi = fdiv(y0 + TO - 1 + pt, stride);
-    const int ox_lo = fdiv(x0 + pl - 2, stride), ox_hi = fdiv(x0 + TO - 1 + pl, stride);
-    const int R = oy_hi - oy_lo + 1, Cn = ox_hi - ox_lo + 1;             // <= 18 each
-    const int kpc = c / KB;                                               // K blocks per dz tensor
-    // ---- weights -> registers: B[k][n = tap l15]; taps 9..15 are zero columns
-    f32x4 wb[NKC];                       // fp32: four channels 4 lq + e; bf16: the high parts of eight channels 8 lq ..
-    [[maybe_unused]] f32x4 wlo[sizeof(T) == 2 ? NKC : 1];
-#pragma unroll
-    for (int j = 0; j < NKC; ++j) {
-        const int k = j / kpc, cb = (j - k * kpc) * KB;
-        if constexpr (sizeof(T) == 2) {
-            unsigned hi4[4] = {0, 0, 0, 0}, lo4[4] = {0, 0, 0, 0};
-            if (l15 < 9) {
-                const float* wp = weff + ((size_t)k * 9 + l15) * c + cb + lq * 8;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float w = wp[e];
-                    const bf16_t h = (bf16_t)w;
-                    const bf16_t l = (bf16_t)(w - (float)h);
-                    hi4[e >> 1] |= (unsigned)__builtin_bit_cast(unsigned short, h) << (16 * (e & 1));
-                    lo4[e >> 1] |= (unsigned)__builtin_bit_cast(unsigned short, l) << (16 * (e & 1));
-                }
-            }
-            wb[j] = __builtin_bit_cast(f32x4, u32x4_t{hi4[0], hi4[1], hi4[2], hi4[3]});
-            wlo[j] = __builtin_bit_cast(f32x4, u32x4_t{lo4[0], lo4[1], lo4[2], lo4[3]});
-        } else {
-            wb[j] = l15 < 9 ? *(const f32x4*)(weff + ((size_t)k * 9 + l15) * c + cb + lq * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-    }
-    // ---- phase A: 16 dz pixels per wave and step
-    const int npx = R * Cn;
-    for (int g = wave; g * 16 < npx; g += 4) {
-        const int j = g * 16 + l15;
-        const int r = j / Cn, q = j - r * Cn;
-        const int oy = oy_lo + r, ox = ox_lo + q;
-        const bool ok = j < npx && (unsigned)oy < (unsigned)ho && (unsigned)ox < (unsigned)wo;
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        // every lane loads (lanes without a pixel read pixel 0 of their tensor and are zeroed afterwards): a load under a per-lane
-        // condition inside the unrolled loop would be a branch and a full vmcnt drain per K block
-        const size_t pixoff = ok ? ((size_t)oy * wo + ox) * lddz : 0;
-        u32x4_t araw[NKC];
-#pragma unroll
-        for (int jj = 0; jj < NKC; ++jj) {
-            const int k = jj / kpc, cb = (jj - k * kpc) * KB;
-            araw[jj] = *(const u32x4_t*)(dz + (size_t)(k * batch + b) * ho * wo * lddz + pixoff + cb + lq * (sizeof(T) == 2 ? 8 : 4));
-        }
-#pragma unroll
-        for (int jj = 0; jj < NKC; ++jj) {
-            u32x4_t a = araw[jj];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) a[e] = ok ? a[e] : 0u;
-            if constexpr (sizeof(T) == 2) {
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, wb[jj]), acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, wlo[jj]), acc, 0, 0, 0);
-            } else {
-                const f32x4 af = __builtin_bit_cast(f32x4, a);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(af[e], wb[jj][e], acc, 0, 0, 0);
-            }
-        }
-        // accumulator register e = pixel 16 g + 4 lq + e, column l15 = tap
-        if (l15 < 9) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int jp = g * 16 + 4 * lq + e;
-                if (jp < npx) {
-                    const int rp = jp / Cn;
-                    P[l15][rp * RMAX + (jp - rp * Cn)] = acc[e];
-                }
-            }
-        }
-    }
-    __syncthreads();
-    // ---- phase B: one output pixel per thread (as in dgrad_sum1_tiled_kernel)
-    const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
-    const int y = y0 + ty, x = x0 + tx;
-    if (y < hi && x < wi) {
-        float v = 0.f;
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh) {
-            const int ny = y + pt - kh;
-            if (ny < 0 || (stride == 2 && (ny & 1))) continue;
-            const int oy = stride == 2 ? ny >> 1 : ny;
-            if (oy >= ho) continue;
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw) {
-                const int nx = x + pl - kw;
-                if (nx < 0 || (stride == 2 && (nx & 1))) continue;
-                const int ox = stride == 2 ? nx >> 1 : nx;
-                if (ox >= wo) continue;
-                v += P[kh * 3 + kw][(oy - oy_lo) * RMAX + (ox - ox_lo)];
-            }
-        }
-        const size_t qo = ((size_t)b * hi + y) * wi + x;
-        out[qo] = accumulate ? out[qo] + v : v;
-    }
-}
-
-extern "C" int shm_conv3x3_dgrad_sum1(const void* dz, int lddz, const float* weff, float* out, int nk, int batch, int hi, int wi, int c, int stride,
-                                      int accumulate, int dtype, void* stream) {
-    SHM_REQUIRE(dz && weff && out, SHM_E_SHAPE, "shm_conv3x3_dgrad_sum1: null pointer");
-    SHM_REQUIRE(c % 4 == 0 && pow2_le64(c / 4) && lddz % 4 == 0, SHM_E_SHAPE, "shm_conv3x3_dgrad_sum1: channels %d unsupported", c);
-    SHM_REQUIRE(stride == 1 || stride == 2, SHM_E_SHAPE, "shm_conv3x3_dgrad_sum1: stride %d not in {1,2}", stride);
-    int ho, wo, pt, pl;
-    shm_same_pad(hi, 3, stride, &ho, &pt);
-    shm_same_pad(wi, 3, stride, &wo, &pl);
-    const size_t npx = (size_t)batch * hi * wi;
-    if (npx == 0 || nk == 0) return SHM_OK;
-    const int PP = 256 / (c / 4);
-    {                                    // MFMA phase A: the step's shapes (nk = 1 or 5 tensors of 64 channels); K blocks are a template parameter
-        const int kb = dtype == SHM_F32 ? 16 : 32;
-        const int nkc = c % kb == 0 ? nk * c / kb : 0;
-        const int tiles = shm_cdiv(hi, 16) * shm_cdiv(wi, 16);
-        const dim3 grid(batch * tiles);
-#define SHM_SUM1_MFMA(T_, NKC_)                                                                                                                           \
-    hipLaunchKernelGGL((dgrad_sum1_mfma_kernel<T_, NKC_>), grid, dim3(256), 0, (hipStream_t)stream, (const T_*)dz, lddz, weff, out, nk, batch, hi, wi, ho, wo, c, \
-                       stride, pt, pl, accumulate)
-        bool done = true;
-        if (dtype == SHM_F32 && nkc == 4) SHM_SUM1_MFMA(float, 4);
-        else if (dtype == SHM_F32 && nkc == 20) SHM_SUM1_MFMA(float, 20);
-        else if (dtype == SHM_F32 && nkc == 1) SHM_SUM1_MFMA(float, 1);
-        else if (dtype == SHM_F32 && nkc == 5) SHM_SUM1_MFMA(float, 5);
-        else if (dtype == SHM_BF16 && nkc == 2) SHM_SUM1_MFMA(bf16_t, 2);
-        else if (dtype == SHM_BF16 && nkc == 10) SHM_SUM1_MFMA(bf16_t, 10);
-        else if (dtype == SHM_BF16 && nkc == 1) SHM_SUM1_MFMA(bf16_t, 1);
-        else if (dtype == SHM_BF16 && nkc == 5) SHM_SUM1_MFMA(bf16_t, 5);
-        else done = false;
-#undef SHM_SUM1_MFMA
-        if (done) {
-            SHM_LAUNCH_CHECK("shm_conv3x3_dgrad_sum1");
-            return SHM_OK;
-        }
-    }
-    if (nk * c <= 5 * 64) {              // weights fit the tiled kernel's LDS staging
-        const int tiles = shm_cdiv(hi, 16) * shm_cdiv(wi, 16);
-        SHM_DISPATCH(dtype, "shm_conv3x3_dgrad_sum1",
-                     hipLaunchKernelGGL(dgrad_sum1_tiled_kernel<T>, dim3(batch * tiles), dim3(256), 0, (hipStream_t)stream, (const T*)dz, lddz, weff, out, nk,
-                                        batch, hi, wi, ho, wo, c, stride, pt, pl, accumulate));
-        SHM_LAUNCH_CHECK("shm_conv3x3_dgrad_sum1");
-        return SHM_OK;
-    }
-    SHM_DISPATCH(dtype, "shm_conv3x3_dgrad_sum1",
-                 hipLaunchKernelGGL(dgrad_sum1_kernel<T>, dim3(shm_cdiv((long)npx, PP)), dim3(256), 0, (hipStream_t)stream, (const T*)dz, lddz, weff, out, nk,
-                                    batch, hi, wi, ho, wo, c, stride, pt, pl, accumulate));
-    SHM_LAUNCH_CHECK("shm_conv3x3_dgrad_sum1");
     return SHM_OK;
 }

@@ -235,11 +235,6 @@ def conv2d_wgrad_norm_finish(dw, nt, dzsum, batch, c, part_lo, cin, cout, ksize)
     check(lib().shm_conv2d_wgrad_norm_finish(_p(dw), _p(nt), _p(dzsum), batch, c, part_lo, cin, cout, ksize, _stream()), "shm_conv2d_wgrad_norm_finish")
 
 
-def in_bwd_keep_dz_sums(dst):
-    """The next in_bwd / in_bwd_apply / in_bwd_rank1 call also copies its per-sample channel sums of dz ([batch][c] float64) to dst."""
-    check(lib().shm_in_bwd_keep_dz_sums(_p(dst)), "shm_in_bwd_keep_dz_sums")
-
-
 def conv2d_norm_supported(batch, hi, wi, cin, c1, cout, ksize, stride, norm_part, dtype):
     """Would conv2d_in_fwd(nt_x= / nt_x2=) run on a kernel that normalises source `norm_part` in LDS?  (c1: channels of x when
     there are two sources, else 0; dtype: torch dtype of the activations.)"""
@@ -382,9 +377,10 @@ def in_bwd_fused_doubles(batch, hw, c):
     return (batch * (hw * cb // 16384) * 3 * c + 1) // 2 + batch * c + batch * (c // cb) * 288 + 1
 
 
-def in_bwd(g1, ldg1, g2, ldg2, a, lda, stats, red, dz, lddz, dbias, batch, h, w, c, slope, fused=None):
+def in_bwd(g1, ldg1, g2, ldg2, a, lda, stats, red, dz, lddz, dbias, batch, h, w, c, slope, fused=None, dz_sums=None):
     """fused: float64 scratch of in_bwd_fused_doubles(batch, h * w, c) elements (zero on entry, zero on return): the call may run the one-pass
-    bf16 form (shm_in_bwd_fused_scratch); the library falls back to reduce + apply on shapes that form does not take."""
+    bf16 form; the library falls back to reduce + apply on shapes that form does not take.
+    dz_sums (here, in in_bwd_apply and in in_bwd_rank1): float64 [batch][c], receives the per-sample channel sums of dz; needs dbias."""
     e = batch * h * w * c
     rd = _tb(g1, e * (1.25 if g2 is not None else 1.0)) + _tb(a, e)
 
@@ -393,25 +389,18 @@ def in_bwd(g1, ldg1, g2, ldg2, a, lda, stats, red, dz, lddz, dbias, batch, h, w,
         # (round-5 advisor: three passes were counted for every call, understating the two-pass calls)
         return (rd if last_kernel().startswith("in_bwd_fused") else 2 * rd) + _tb(dz, e)
 
-    def run():
-        if fused is not None:
-            check(lib().shm_in_bwd_fused_scratch(_p(fused), fused.numel()), "shm_in_bwd_fused_scratch")
-        try:
-            check(lib().shm_in_bwd(_p(g1), ldg1, _p(g2), ldg2, _p(a), lda, _p(stats), _p(red), _p(dz), lddz, _p(dbias),
-                                   batch, h, w, c, slope, _dtg(a, g1), _stream()), "shm_in_bwd")
-        finally:
-            if fused is not None:               # one-shot state of the library: never left armed behind an error
-                lib().shm_in_bwd_fused_scratch(None, 0)
-    _timed_bytes("shm_in_bwd", nb, run)
+    _timed_bytes("shm_in_bwd", nb, lambda: check(
+        lib().shm_in_bwd(_p(g1), ldg1, _p(g2), ldg2, _p(a), lda, _p(stats), _p(red), _p(dz), lddz, _p(dbias), _p(dz_sums), _p(fused),
+                         0 if fused is None else fused.numel(), batch, h, w, c, slope, _dtg(a, g1), _stream()), "shm_in_bwd"))
 
 
-def in_bwd_apply(g1, ldg1, g2, ldg2, a, lda, stats, beta, red, redp, dstage, dz, lddz, dbias, batch, h, w, c, slope):
+def in_bwd_apply(g1, ldg1, g2, ldg2, a, lda, stats, beta, red, redp, dstage, dz, lddz, dbias, batch, h, w, c, slope, dz_sums=None):
     """shm_in_bwd without its reduce pass: the sums come from the gsum epilogues of the launches that wrote g1 / g2."""
     e = batch * h * w * c
     nb = _tb(g1, e * (1.25 if g2 is not None else 1.0)) + _tb(a, e) + _tb(dz, e)
     _timed_bytes("shm_in_bwd_apply", nb, lambda: check(
         lib().shm_in_bwd_apply(_p(g1), ldg1, _p(g2), ldg2, _p(a), lda, _p(stats), _p(beta), _p(red), _p(redp), _p(dstage), _p(dz), lddz,
-                               _p(dbias), batch, h, w, c, slope, _dtg(a, g1), _stream()), "shm_in_bwd_apply"))
+                               _p(dbias), _p(dz_sums), batch, h, w, c, slope, _dtg(a, g1), _stream()), "shm_in_bwd_apply"))
 
 
 LRELU_RED_SLOTS = 64        # SHM_LRELU_RED_SLOTS
@@ -449,9 +438,9 @@ def head_in_bwd(a, lda, stats, beta, w, y, dy, dx, lddx, dw_acc, db_acc, batch, 
                                 hw, c, slope, _dt(a) if dx is None else _dtg(a, dx), _stream()), "shm_head_in_bwd")
 
 
-def in_bwd_rank1(hdz, hw_, a, lda, stats, red, dz, lddz, dbias, batch, h, w, c, slope):
-    check(lib().shm_in_bwd_rank1(_p(hdz), _p(hw_), _p(a), lda, _p(stats), _p(red), _p(dz), lddz, _p(dbias), batch, h, w, c, slope, _dt(a), _stream()),
-          "shm_in_bwd_rank1")
+def in_bwd_rank1(hdz, hw_, a, lda, stats, red, dz, lddz, dbias, batch, h, w, c, slope, dz_sums=None):
+    check(lib().shm_in_bwd_rank1(_p(hdz), _p(hw_), _p(a), lda, _p(stats), _p(red), _p(dz), lddz, _p(dbias), _p(dz_sums), batch, h, w, c, slope, _dt(a),
+                                 _stream()), "shm_in_bwd_rank1")
 
 
 def head_bwd(x, ldx, w, y, dy, dx, lddx, dw_acc, db_acc, npix, c, slope, red=None):

@@ -44,6 +44,37 @@ def test_version_and_error_string_without_gpu():
     assert L.shm_image_losses_workspace(8, 256) > 0
 
 
+def test_in_bwd_requests_are_arguments_not_thread_state():
+    """The InstanceNorm backward takes its dz_sums / fused scratch as arguments: no kernel source keeps per-thread request state (runtime.hip
+    holds the persistent per-thread configuration), and the entry points that armed it are gone from the header, the table and the library."""
+    csrc = Path(_lib.__file__).resolve().parent / "csrc"
+    for f in sorted([*csrc.glob("*.hip"), *csrc.glob("*.h")]):
+        if f.name != "runtime.hip":
+            assert "thread_local" not in f.read_text(), f.name
+    L = _lib.lib()
+    for name in ("shm_in_bwd_keep_dz_sums", "shm_in_bwd_fused_scratch"):
+        assert name not in _lib.HEADER.read_text() and name not in _lib.SIGNATURES and not hasattr(L, name), name
+
+
+def test_every_source_is_built():
+    csrc = Path(_lib.__file__).resolve().parent / "csrc"
+    assert sorted(f.name for f in csrc.glob("*.hip")) == sorted(_lib.SOURCES)
+    assert all(h.exists() for h in _lib.SHARED_HEADERS)
+
+
+def test_dz_sums_need_a_bias_gradient_without_gpu():
+    """dz_sums are copied out of the bias gradient's staging: asked for without dbias, all three entry points answer SHM_E_SHAPE with the
+    same message, before any launch (and before their other pointer checks)."""
+    L = _lib.lib()
+    p, f32 = 1, _lib.F32            # a non-null pointer nobody dereferences
+    rc = L.shm_in_bwd(p, 64, None, 0, p, 64, p, p, p, 64, None, p, None, 0, 1, 8, 8, 64, 0.2, f32, None)
+    assert rc == -1 and b"bias gradient" in L.shm_last_error()
+    rc = L.shm_in_bwd_apply(None, 64, None, 0, None, 64, None, None, None, None, None, None, 64, None, p, 1, 8, 8, 64, 0.2, f32, None)
+    assert rc == -1 and b"bias gradient" in L.shm_last_error()
+    rc = L.shm_in_bwd_rank1(p, p, p, 64, p, p, p, 64, None, p, 1, 8, 8, 64, 0.2, f32, None)
+    assert rc == -1 and b"bias gradient" in L.shm_last_error()
+
+
 def test_product_refuses_to_run_without_gpu():
     import torch
     if torch.cuda.is_available():

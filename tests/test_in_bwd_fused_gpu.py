@@ -1,4 +1,4 @@
-"""bf16 InstanceNorm backward in one pass (round 5: in_bwd_fused8_kernel, include/shmgan_hip.h: shm_in_bwd_fused_scratch; the backward of
+"""bf16 InstanceNorm backward in one pass (round 5: in_bwd_fused8_kernel, include/shmgan_hip.h: shm_in_bwd's fused_scratch; the backward of
 SHM.py:244-245's Conv -> LeakyReLU -> InstanceNormalization block).
 
 The one-pass form keeps a block's slice of the gradient and of the activation in registers between the reduce and the apply phase; the blocks

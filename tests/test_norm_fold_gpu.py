@@ -363,28 +363,27 @@ def test_in_bwd_keeps_the_per_sample_dz_sums(dt, gsum):
     dz = torch.empty_like(a)
     db = torch.zeros(c, dtype=torch.float64, device="cuda")
     keep = torch.full((n, c), 7.0, dtype=torch.float64, device="cuda")
-    ops.in_bwd_keep_dz_sums(keep)
-    if gsum:
-        red = torch.zeros(ops.GSUM_SLOTS * n * c * 2, dtype=torch.float64, device="cuda")
-        g64, a64 = g.double(), a.double()
-        red.view(ops.GSUM_SLOTS, n, c, 2)[0] = torch.stack([g64.sum(dim=(1, 2)), (g64 * a64).sum(dim=(1, 2))], -1)
-        dstage = torch.zeros(n * c, dtype=torch.float64, device="cuda")
-        ops.in_bwd_apply(g, c, None, 0, a, c, stats, beta, red, None, dstage, dz, c, db, n, h, h, c, 0.2)
-    else:
-        red = torch.zeros(n * c * 3, dtype=torch.float64, device="cuda")
-        ops.in_bwd(g, c, None, 0, a, c, stats, red, dz, c, db, n, h, h, c, 0.2)
-    torch.cuda.synchronize()
+
+    def run(dbias, dz_sums):
+        if gsum:
+            red = torch.zeros(ops.GSUM_SLOTS * n * c * 2, dtype=torch.float64, device="cuda")
+            g64, a64 = g.double(), a.double()
+            red.view(ops.GSUM_SLOTS, n, c, 2)[0] = torch.stack([g64.sum(dim=(1, 2)), (g64 * a64).sum(dim=(1, 2))], -1)
+            dstage = torch.zeros(n * c, dtype=torch.float64, device="cuda")
+            ops.in_bwd_apply(g, c, None, 0, a, c, stats, beta, red, None, dstage, dz, c, dbias, n, h, h, c, 0.2, dz_sums=dz_sums)
+        else:
+            red = torch.zeros(n * c * 3, dtype=torch.float64, device="cuda")
+            ops.in_bwd(g, c, None, 0, a, c, stats, red, dz, c, dbias, n, h, h, c, 0.2, dz_sums=dz_sums)
+        torch.cuda.synchronize()
+    run(db, keep)
     ref = dz.double().sum(dim=(1, 2))
     # (the sums are taken before dz is rounded to its storage type: fp32 partial sums in float32, plus bf16 rounding of the summands in bf16)
     assert float((keep - ref).abs().max()) < (1e-4 if dt == "f32" else 1e-2) * float(ref.abs().max() + 1.0)
     assert float((keep.sum(0) - db).abs().max()) < 1e-9 * float(db.abs().max() + 1.0)
-    # one-shot: a second call leaves the buffer alone
+    # the buffer belongs to the call it was passed to: a following call without the argument leaves it alone
     keep.fill_(7.0)
-    db2 = torch.zeros_like(db)
-    if not gsum:
-        ops.in_bwd(g, c, None, 0, a, c, stats, red, dz, c, db2, n, h, h, c, 0.2)
-        torch.cuda.synchronize()
-        assert float(keep.min()) == 7.0
+    run(torch.zeros_like(db), None)
+    assert float(keep.min()) == 7.0
 
 
 def _step(S, F, B, dt, fold, seed=0, mode=0):

@@ -2,12 +2,12 @@
 """CPU-side sanitizer build of the host half of libshmgan_hip.so ("race detection / sanitizers").
 
 Every csrc/*.hip is compiled with `-fsanitize=address,undefined -fno-gpu-sanitize`: the HOST code (argument validation, dispatch, the launchers'
-arithmetic, the tuning table, error strings, thread-local one-shot state) is instrumented, the device code is built as usual and never runs --
+arithmetic, the tuning table, error strings, the per-thread configuration) is instrumented, the device code is built as usual and never runs --
 GPU AddressSanitizer is not available on this pool and is not attempted.  The instrumented library goes to $SHM_ASAN_DIR (default
 /tmp/shm_asan), never into the tree.  Then the GPU-less tests that drive the C ABI run against it under the ASan runtime:
 
     tests/test_abi.py           header <-> exports <-> ctypes table, every entry point's argument validation and error path, the
-                                thread-local one-shot state, shm_set_tuning / shm_get_tuning bounds
+                                per-thread configuration, shm_set_tuning / shm_get_tuning bounds
     tests/test_norm_queries.py  the launchers' shape arithmetic (workspace sizes, *_supported queries) over a grid of shapes
 
 Usage:  python tools/sanitize_host.py [--jobs N] [--log FILE]     (exit code = pytest's; any ASan / UBSan report fails the run)

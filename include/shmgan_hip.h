@@ -557,6 +557,39 @@ int shm_sum_groups(const void* src, void* dst, int nimg, size_t per, int nb, int
 int shm_resize_bilinear_u8(const unsigned char* src, int hin, int win, int c, float* dst, int ho, int wo,
                            float scale, int flip_ud, void* stream);
 
+/* ---- polarimetry: the estimated-diffuse target and the Stokes maps (utils.py:68-123 calculate_estimate_diffuse, whose imwrite
+ * is commented out; SHM.py:1157-1169 calcDOP; neither is called by the reference's training path, which reads a pre-computed ED/
+ * directory) ---------------------------------------------------------------------------------------------------------------------
+ * The four decoded views of ONE sample -> that sample's five training planes, one launch, one thread per output pixel.
+ * src_ptrs: host array of 4 device pointers to uint8 [hin,win,3] images of the same size; dst_ptrs: host array of 5 device
+ * pointers to float32 [ho,wo,3] planes (the sample's slices of the loader's five [B,S,S,3] tensors); both arrays are read during
+ * the call and the nine pointers travel to the kernel by value.  Per output pixel, channel and tap position t in {tl, tr, bl, br}
+ * (the taps, weights lx / ly and the row flip of shm_resize_bilinear_u8: half-pixel centres, lower = max(floor, 0),
+ * upper = min(ceil, n-1)) the four bytes v0..v3 are read once, and with lerp(q) = (top + (bot - top) ly) * scale,
+ * top = q_tl + (q_tr - q_tl) lx, bot = q_bl + (q_br - q_bl) lx, all in fp32:
+ *   dst[i] = lerp(v_i)        i = 0..3: the arithmetic of shm_resize_bilinear_u8 on view i
+ *   dst[4] = lerp(e)          e_t = e(v0_t, v1_t, v2_t, v3_t): the estimate is made PER TAP, at source resolution, and then
+ *                             resized -- the resize of the reference's estimated-diffuse image, not the estimate of resized views
+ *   SHM_POLAR_MIN      e = min(v0, v1, v2, v3) (the reference's definition); coef is not read and may be null
+ *   SHM_POLAR_STOKES   coef = host float[12], a row-major 3x4 matrix C with (S0, S1, S2) = C (v0..v3);
+ *                      e = clamp(0.5 (S0 - sqrt(S1^2 + S2^2)), 0, 255): the minimum over ALL polariser angles of the fitted
+ *                      I(theta) = 0.5 (S0 + S1 cos 2 theta + S2 sin 2 theta), which the minimum of four samples overestimates
+ * With (ho,wo) = (hin,win) every weight is 0 and dst[i] = v_i * scale, dst[4] = e * scale exactly.  SHM_E_SHAPE for a null
+ * pointer (either array or any entry), a size outside [1, 32768], an unknown mode or SHM_POLAR_STOKES without coef; all before
+ * any launch. */
+#define SHM_POLAR_MIN 0
+#define SHM_POLAR_STOKES 1
+int shm_polar_views_u8(const unsigned char* const* src_ptrs, int hin, int win, const float* coef, int mode,
+                       float* const* dst_ptrs, int ho, int wo, float scale, int flip_ud, void* stream);
+/* Stokes maps of four float32 views of n elements each (any shape: the loaded RGB views or their Y channels).  view_ptrs: host
+ * array of 4 device pointers; coef: host float[12], the 3x4 matrix above.  Per element (S0, S1, S2) = C (v0..v3) and
+ *   s0 = S0;  dop = sqrt(S1^2 + S2^2) / S0, 0 where S0 == 0 (divide_no_nan, as calcDOP);  aolp = 0.5 atan2f(S2, S1)
+ * Each of s0, dop, aolp (device float32 [n]) may be null and is then not written; with all three null nothing is launched.
+ * One grid-stride launch; 16-byte accesses when n % 4 == 0 and every pointer is 16-byte aligned, scalar ones otherwise (same
+ * values).  SHM_E_SHAPE for a null view_ptrs, view or coef, or n == 0, before any launch. */
+int shm_polar_maps(const float* const* view_ptrs, size_t n, const float* coef, float* s0, float* dop, float* aolp,
+                   void* stream);
+
 /* ---- test-mode image export (the images test.py:305-317 logs; test_plot at test.py:410-425) ----------------------------
  * Batched, ragged float32 -> uint8 export.  One job = one plane of one image: source src[j], float32 [s,s,c] NHWC with channel
  * pitch ld >= c, c in {1,3}; destination [ho,wo,c] uint8, tightly packed, at byte offset dst_off (a multiple of 4) of dst.

@@ -16,7 +16,7 @@ _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ["SHM_LIB_PATH"]) if os.environ.get("SHM_LIB_PATH") else _HERE / "libshmgan_hip.so"
 CSRC = _HERE / "csrc"
 HEADER = _HERE.parent / "include" / "shmgan_hip.h"
-SOURCES = ["runtime.hip", "conv_igemm.hip", "conv_wreg16.hip", "conv_pingpong.hip", "conv_wgrad.hip", "conv_wgrad_x3.hip", "conv_fwd_x3.hip", "conv_rgb.hip", "elem.hip", "instnorm.hip", "instnorm_bwd.hip", "heads.hip", "dgrad_sum1.hip", "color.hip", "imgloss.hip", "metrics.hip", "specseg.hip", "data.hip", "export.hip", "telemetry.hip"]
+SOURCES = ["runtime.hip", "conv_igemm.hip", "conv_wreg16.hip", "conv_pingpong.hip", "conv_wgrad.hip", "conv_wgrad_x3.hip", "conv_fwd_x3.hip", "conv_rgb.hip", "elem.hip", "instnorm.hip", "instnorm_bwd.hip", "heads.hip", "dgrad_sum1.hip", "color.hip", "imgloss.hip", "metrics.hip", "specseg.hip", "data.hip", "polar.hip", "export.hip", "telemetry.hip"]
 # headers every source may include: a change of any of them rebuilds every object (tools/sanitize_host.py goes by the same list)
 SHARED_HEADERS = [CSRC / "common.h", CSRC / "elem.h", CSRC / "ablate.h", CSRC / "tapgemm.h", CSRC / "wgrad.h", CSRC / "x3split.h", HEADER]
 F32, BF16 = 0, 1                 # SHM_F32 / SHM_BF16 of include/shmgan_hip.h
@@ -106,6 +106,8 @@ SIGNATURES = {
     "shm_add_bcast": (I, [P, P, P, I, Z, I, I, I, P]),
     "shm_sum_groups": (I, [P, P, I, Z, I, I, I, I, P]),
     "shm_resize_bilinear_u8": (I, [P, I, I, I, P, I, I, F, I, P]),
+    "shm_polar_views_u8": (I, [P, I, I, P, I, P, I, I, F, I, P]),
+    "shm_polar_maps": (I, [P, Z, P, P, P, P, P]),
     "shm_export_u8_workspace": (Z, [I]),
     "shm_export_u8": (I, [P, P, I, P, I, P, Z, P, Z, P]),
     "shm_running_scale_mean": (I, [P, I, P, P, P]),

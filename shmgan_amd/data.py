@@ -12,6 +12,11 @@ with non-blocking copies on the loader's side stream, and the rest is one kernel
 that stream.  The training thread only enqueues the next batch and, when it takes a batch, waits for the worker's
 future and makes its stream wait for the batch's event -- the 5 B decodes of batch j+1 run under step j.
 
+`diffuse_source` says where the fifth tensor comes from.  "dir" (default) is the reference's path above: a fifth directory of
+pre-computed estimated-diffuse images.  "min" / "stokes" need only the four view directories: the worker decodes 4 B files and
+one kernel per SAMPLE (shm_polar_views_u8) writes all five tensors, the diffuse estimate made per source pixel from the four
+decoded views ("Estimated diffuse on the device") -- B launches and 4 B uploads per batch instead of 5 B of each.
+
 Under torch.distributed the loader shards by rank: global batch i of rank r is images [(i*world + r)*B, +B), so N ranks
 consume N*B distinct samples per step (the data-parallel identity of shmgan_amd/dist.py) and len() = n // (B*world).
 """
@@ -28,6 +33,7 @@ from . import ops
 
 PSD_SUBDIRS = ("I0", "I60", "I90", "I150", "ED")          # datasetLoader.py:30-34 (PSD polar dataset)
 SHMGAN_SUBDIRS = ("I0", "I45", "I90", "I135", "ED")       # datasetLoader.py:23-27 (commented alternative)
+DIFFUSE_SOURCES = ("dir", "min", "stokes")                # where the fifth tensor comes from (PolarDataset)
 _EXT = (".bmp", ".gif", ".jpeg", ".jpg", ".png")          # Keras' ALLOWLIST_FORMATS
 
 
@@ -38,15 +44,32 @@ def list_images(directory):
 
 
 class PolarDataset:
-    """Iterable of 5-tuples of [B,S,S,3] float32 device tensors in [0,1]."""
+    """Iterable of 5-tuples of [B,S,S,3] float32 device tensors in [0,1].
+
+    diffuse_source: "dir" = the fifth of `subdirs` holds the estimated-diffuse images (the reference's loader); "min" = the
+    per-channel minimum of the four views (utils.calculate_estimate_diffuse), "stokes" = the fitted minimum over all polariser
+    angles, both computed on the device from the first four `subdirs` alone.  angles: the polariser angles in degrees for
+    "stokes" (default: read from the directory names, polar.angles_from_subdirs)."""
 
     def __init__(self, data_dir, image_size, batch_size=1, subdirs=PSD_SUBDIRS, flip_ud=True, device=None, epochs=1,
-                 rank=None, world=None):
+                 rank=None, world=None, diffuse_source="dir", angles=None):
         self.S, self.B, self.flip_ud, self.epochs = image_size, batch_size, flip_ud, epochs
+        if diffuse_source not in DIFFUSE_SOURCES:
+            raise ValueError(f"diffuse_source {diffuse_source!r} is not one of {DIFFUSE_SOURCES}")
+        self.diffuse_source, self.coef = diffuse_source, None
+        if diffuse_source != "dir":
+            subdirs = tuple(subdirs)[:4]
+            if len(subdirs) != 4:
+                raise ValueError(f"diffuse_source {diffuse_source!r} needs four view directories, got {subdirs}")
+            if diffuse_source == "stokes":
+                from . import polar
+                self.coef = polar.stokes_matrix(angles if angles is not None else polar.angles_from_subdirs(subdirs))
+                if self.coef.shape != (3, 4):
+                    raise ValueError(f"diffuse_source 'stokes' takes four angles, got {angles}")
         self.files = [list_images(os.path.join(data_dir, s)) for s in subdirs]
         n = len(self.files[0])
         if any(len(f) != n for f in self.files):
-            raise ValueError(f"the five view directories hold different numbers of images: {[len(f) for f in self.files]}")
+            raise ValueError(f"the {len(self.files)} view directories hold different numbers of images: {[len(f) for f in self.files]}")
         self.n = n
         if rank is None or world is None:
             import torch.distributed as dist
@@ -96,6 +119,8 @@ class PolarDataset:
         then enqueue copy + resize per image on the loader stream and record the batch's event."""
         if self._gen_event[gen] is not None:         # the copies that last read this generation's staging buffers
             self._gen_event[gen].synchronize()       # (a host wait, but on the loader thread)
+        if self.diffuse_source != "dir":
+            return self._prepare_estimated(index, gen)
         staged = [[self._decode(self.files[v][self.image_index(index, b)], (gen, v, b)) for b in range(self.B)] for v in range(5)]
         with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
             # allocated, filled and consumed on the loader stream: the caching allocator hands a block back to loader-stream
@@ -105,6 +130,24 @@ class PolarDataset:
                 for b in range(self.B):
                     src = staged[v][b].to(self.dev, non_blocking=True)
                     ops.resize_bilinear_u8(src, outs[v][b], 1.0 / 255.0, self.flip_ud)
+            ev = torch.cuda.Event()
+            ev.record(self.stream)
+        self._gen_event[gen] = ev
+        return tuple(outs), ev
+
+    def _prepare_estimated(self, index, gen):
+        """_prepare_worker for diffuse_source "min" / "stokes": 4 B decodes and uploads, then one shm_polar_views_u8 per sample
+        writes that sample's slice of all five tensors."""
+        staged = [[self._decode(self.files[v][self.image_index(index, b)], (gen, v, b)) for b in range(self.B)] for v in range(4)]
+        for b in range(self.B):
+            if any(staged[v][b].shape != staged[0][b].shape for v in range(4)):
+                raise ValueError("the four views of a sample must have the same decoded size: " + ", ".join(
+                    f"{self.files[v][self.image_index(index, b)]} {staged[v][b].shape[0]}x{staged[v][b].shape[1]}" for v in range(4)))
+        with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+            outs = [torch.empty((self.B, self.S, self.S, 3), device=self.dev) for _ in range(5)]       # on the loader stream, as above
+            for b in range(self.B):
+                srcs = [staged[v][b].to(self.dev, non_blocking=True) for v in range(4)]
+                ops.polar_views_u8(srcs, [outs[v][b] for v in range(5)], self.diffuse_source, self.coef, 1.0 / 255.0, self.flip_ud)
             ev = torch.cuda.Event()
             ev.record(self.stream)
         self._gen_event[gen] = ev
@@ -145,9 +188,10 @@ class PolarDataset:
 
 def datasetLoad(trainer, subdirs=PSD_SUBDIRS, flip_ud=True):
     """Reference signature (datasetLoader.py:19): returns (length_dataset, loadedDataset) and sets the same
-    attributes on the trainer object."""
+    attributes on the trainer object.  The trainer's `diffuse_source` option (default "dir") goes to PolarDataset; it is NOT
+    keyed on the reference's `est_diffuse`, which main.py's parser makes True for every run."""
     ds = PolarDataset(trainer.data_dir, trainer.image_size, trainer.batch_size, subdirs, flip_ud, trainer.device,
-                      epochs=trainer.num_epochs)
+                      epochs=trainer.num_epochs, diffuse_source=getattr(trainer.args, "diffuse_source", "dir"))
     trainer.stddev_arr, trainer.mean_arr, trainer.variance_arr = [], [], []
     # per-rank length: batches_per_epoch = length // batch_size (SHM.py:957) then counts this rank's batches
     trainer.length_dataset, trainer.loadedDataset = ds.n // ds.world, ds

@@ -777,6 +777,80 @@ def resize_bilinear_u8(src_u8, dst, scale=1.0 / 255.0, flip_ud=False):
           "shm_resize_bilinear_u8")
 
 
+# ---- polarimetry: estimated-diffuse target and Stokes maps ----------------------------------------
+POLAR_MODES = {"min": 0, "stokes": 1}                    # SHM_POLAR_MIN / SHM_POLAR_STOKES
+
+
+def _polar_coef(coef, who):
+    """A 3x4 Stokes matrix (anything numpy takes: nested lists, an array, a host tensor) as the C ABI's host float[12]."""
+    import ctypes as C
+    import numpy as np
+    a = np.asarray(coef.cpu() if isinstance(coef, torch.Tensor) else coef, dtype=np.float32)
+    if a.size != 12 or a.shape not in ((3, 4), (12,)):
+        raise ValueError(f"{who}: coef must be a 3x4 matrix, got shape {a.shape}")
+    return (C.c_float * 12)(*[float(v) for v in a.reshape(-1)])
+
+
+def polar_views_u8(srcs, dsts, mode="min", coef=None, scale=1.0 / 255.0, flip_ud=False):
+    """The four decoded views of one sample -> its five training planes in one launch (shm_polar_views_u8, include/shmgan_hip.h,
+    states the definitions).  srcs: four uint8 [hin,win,3] device tensors of the same size; dsts: five float32 [ho,wo,3] device
+    tensors, views 0..3 and the estimated diffuse.  mode "min" (the reference's per-channel minimum) or "stokes" (coef = the 3x4
+    matrix of polar.stokes_matrix).  Runs asynchronously on the current stream."""
+    import ctypes as C
+    if len(srcs) != 4 or len(dsts) != 5:
+        raise ValueError(f"polar_views_u8 takes 4 source views and 5 destination planes, got {len(srcs)} and {len(dsts)}")
+    if mode not in POLAR_MODES:
+        raise ValueError(f"polar_views_u8: mode {mode!r} is not 'min' or 'stokes'")
+    if mode == "stokes" and coef is None:
+        raise ValueError("polar_views_u8: mode 'stokes' needs coef (polar.stokes_matrix of the polariser angles)")
+    for s in srcs:
+        if s.dtype != torch.uint8 or not s.is_cuda:
+            raise TypeError(f"polar_views_u8 takes uint8 device views, got {s.dtype} on {s.device}")
+        if s.dim() != 3 or s.shape[2] != 3 or not s.is_contiguous():
+            raise ValueError(f"polar_views_u8 takes contiguous [hin,win,3] views, got {tuple(s.shape)} with strides {s.stride()}")
+    if any(s.shape != srcs[0].shape for s in srcs):
+        raise ValueError(f"polar_views_u8: the four views differ in size: {[tuple(s.shape[:2]) for s in srcs]}")
+    for d in dsts:
+        if d.dtype != torch.float32 or d.device != srcs[0].device:
+            raise TypeError(f"polar_views_u8 writes float32 planes on {srcs[0].device}, got {d.dtype} on {d.device}")
+        if d.dim() != 3 or d.shape[2] != 3 or not d.is_contiguous():
+            raise ValueError(f"polar_views_u8 writes contiguous [ho,wo,3] planes, got {tuple(d.shape)} with strides {d.stride()}")
+    if any(d.shape != dsts[0].shape for d in dsts):
+        raise ValueError(f"polar_views_u8: the five planes differ in size: {[tuple(d.shape[:2]) for d in dsts]}")
+    hin, win, _ = srcs[0].shape
+    ho, wo, _ = dsts[0].shape
+    sp = (C.c_void_p * 4)(*[s.data_ptr() for s in srcs])
+    dp = (C.c_void_p * 5)(*[d.data_ptr() for d in dsts])
+    cf = _polar_coef(coef, "polar_views_u8") if mode == "stokes" else None
+    check(lib().shm_polar_views_u8(sp, hin, win, cf, POLAR_MODES[mode], dp, ho, wo, scale, int(flip_ud), _stream()),
+          "shm_polar_views_u8")
+
+
+def polar_maps(views, coef, want=("s0", "dop", "aolp")):
+    """Stokes maps of four float32 device views of equal element count (shm_polar_maps): with (S0, S1, S2) = coef . views,
+    "s0" = S0, "dop" = sqrt(S1^2 + S2^2) / S0 (0 where S0 == 0), "aolp" = 0.5 atan2(S2, S1).  Returns {name: tensor of views[0]'s
+    shape} for the names in `want`, filled asynchronously on the current stream."""
+    import ctypes as C
+    if len(views) != 4:
+        raise ValueError(f"polar_maps takes 4 views, got {len(views)}")
+    bad = [w for w in want if w not in ("s0", "dop", "aolp")]
+    if bad or not want:
+        raise ValueError(f"polar_maps: want {tuple(want)!r} must name some of 's0', 'dop', 'aolp'")
+    for v in views:
+        if v.dtype != torch.float32 or not v.is_cuda or v.device != views[0].device:
+            raise TypeError(f"polar_maps takes float32 views on one device, got {v.dtype} on {v.device}")
+        if not v.is_contiguous():
+            raise ValueError(f"polar_maps takes contiguous views, got strides {v.stride()} for shape {tuple(v.shape)}")
+    n = int(views[0].numel())
+    if n == 0 or any(int(v.numel()) != n for v in views):
+        raise ValueError(f"polar_maps: the four views must hold the same, non-zero number of elements: {[int(v.numel()) for v in views]}")
+    cf = _polar_coef(coef, "polar_maps")
+    out = {w: torch.empty_like(views[0]) for w in want}
+    vp = (C.c_void_p * 4)(*[v.data_ptr() for v in views])
+    check(lib().shm_polar_maps(vp, n, cf, _p(out.get("s0")), _p(out.get("dop")), _p(out.get("aolp")), _stream()), "shm_polar_maps")
+    return out
+
+
 # ---- first-layer input gradient, summed over input channels -----------------------------------------
 def sum_input_channels(w, cin, cout, mask, weff):
     check(lib().shm_sum_input_channels(_p(w), cin, cout, mask, _p(weff), _stream()), "shm_sum_input_channels")

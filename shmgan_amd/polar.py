@@ -1,0 +1,112 @@
+"""Polarimetry helpers: the Stokes fit behind the loader's estimated-diffuse target and the DoP / AoLP maps.
+
+The reference carries two dead helpers: utils.calculate_estimate_diffuse (utils.py:68-123: per pixel and channel the minimum of
+the four views at source size; its imwrite is commented out) and calcDOP (SHM.py:1157-1169: Stokes parameters from the
+0/45/90/135 views with hard-coded coefficients).  Its training path reads a pre-computed ED/ directory instead.  Here both have a
+device implementation (csrc/polar.hip) and this module holds the host side: the least-squares Stokes matrix for any set of
+polariser angles, the reference's own coefficients, and the `imwrite` the reference left out.
+
+Importing this module needs no GPU; `polar_maps` and `write_estimated_diffuse` run on one.
+
+Model: a linear polariser at angle theta in front of light with Stokes parameters (S0, S1, S2) passes
+    I(theta) = 0.5 * (S0 + S1 cos 2 theta + S2 sin 2 theta)
+whose minimum over theta is 0.5 * (S0 - sqrt(S1^2 + S2^2)): the unpolarised (diffuse) half of the light.  The minimum of four
+sampled angles is an upper bound of it (exact only when one polariser happens to sit at the minimum).
+"""
+from __future__ import annotations
+
+import os
+import re
+from pathlib import Path
+
+import numpy as np
+
+from .data import PSD_SUBDIRS, list_images
+
+# S0 = I0 + I90, S1 = I0 - I90, S2 = I45 - I135: the coefficients calcDOP hard-codes (SHM.py:1158-1160).  Its S0 uses two of the
+# four views; stokes_matrix([0, 45, 90, 135]) gives the least-squares S0 = (I0 + I45 + I90 + I135) / 2 with the same S1, S2.
+REFERENCE_DOP_MATRIX = [[1, 0, 1, 0], [1, 0, -1, 0], [0, 1, 0, -1]]
+
+_ANGLE_NAME = re.compile(r"^I(\d+(?:\.\d+)?)$")
+
+
+def angles_from_subdirs(subdirs=("I0", "I60", "I90", "I150")):
+    """Polariser angles in degrees from view directory names of the form I<degrees> (PSD: I0 I60 I90 I150; SHMGAN: I0 I45 I90
+    I135).  Any other name (such as "ED") raises ValueError: pass `angles` explicitly for directories named otherwise."""
+    out = []
+    for s in subdirs:
+        m = _ANGLE_NAME.match(str(s))
+        if not m:
+            raise ValueError(f"cannot read a polariser angle from the directory name {s!r} (expected I<degrees>, as in I60)")
+        out.append(float(m.group(1)))
+    return out
+
+
+def stokes_matrix(angles_deg):
+    """The least-squares 3 x n matrix C with (S0, S1, S2) = C . (I(theta_1) .. I(theta_n)) for the model above: the
+    pseudo-inverse of A, A[i] = 0.5 * (1, cos 2 theta_i, sin 2 theta_i).  Computed in float64, returned as float32.  The fit
+    needs three angles that are distinct modulo 180 degrees (theta and theta + 180 are the same polariser); fewer raise."""
+    th = np.asarray(angles_deg, dtype=np.float64).reshape(-1)
+    distinct = []
+    for t in np.mod(th, 180.0):
+        if not any(min(abs(t - u), 180.0 - abs(t - u)) < 1e-9 for u in distinct):
+            distinct.append(float(t))
+    if len(distinct) < 3:
+        raise ValueError(f"a Stokes fit needs at least three polariser angles that are distinct modulo 180 degrees, got "
+                         f"{[float(t) for t in th]}")
+    r = np.deg2rad(2.0 * th)
+    # cos / sin of multiples of 90 degrees exactly, so that the textbook angle sets give the textbook matrices
+    A = 0.5 * np.stack([np.ones_like(r), np.round(np.cos(r), 15), np.round(np.sin(r), 15)], axis=1)
+    return np.linalg.solve(A.T @ A, A.T).astype(np.float32)
+
+
+def polar_maps(views, angles, want=("s0", "dop", "aolp")):
+    """Stokes maps of four float32 device views taken at `angles` (degrees): ops.polar_maps with the least-squares matrix."""
+    from . import ops
+    return ops.polar_maps(views, stokes_matrix(angles), want)
+
+
+def _decode(path):
+    from PIL import Image
+    with Image.open(path) as im:
+        return np.array(im.convert("RGB"), dtype=np.uint8)
+
+
+def write_estimated_diffuse(data_dir, out_dir, subdirs=PSD_SUBDIRS, mode="min", angles=None, device=None):
+    """Materialise the estimated-diffuse image of every sample as a PNG at the sample's own size: the imwrite that
+    utils.calculate_estimate_diffuse left commented out.  The first four `subdirs` of `data_dir` are listed as the loader lists
+    them; sample i's estimate (mode "min": per pixel and channel the minimum of the four views, the reference's definition;
+    "stokes": the fitted minimum, with `angles` or the angles read from the directory names) is computed by shm_polar_views_u8 at
+    (ho, wo) = (hin, win), scale 1, no flip, rounded to the nearest byte and written to `out_dir` under the first view's file
+    name (with the extension .png).  The result can go to any other tool, or back to PolarDataset as its ED/ directory.
+    Returns the list of files written."""
+    import torch
+    from PIL import Image
+    from . import ops
+    if mode not in ops.POLAR_MODES:
+        raise ValueError(f"write_estimated_diffuse: mode {mode!r} is not 'min' or 'stokes'")
+    views = tuple(subdirs)[:4]
+    if len(views) != 4:
+        raise ValueError(f"write_estimated_diffuse needs four view directories, got {views}")
+    coef = stokes_matrix(angles if angles is not None else angles_from_subdirs(views)) if mode == "stokes" else None
+    files = [list_images(os.path.join(data_dir, s)) for s in views]
+    n = len(files[0])
+    if any(len(f) != n for f in files):
+        raise ValueError(f"the four view directories hold different numbers of images: {[len(f) for f in files]}")
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    os.makedirs(out_dir, exist_ok=True)
+    written = []
+    for i in range(n):
+        paths = [f[i] for f in files]
+        imgs = [_decode(p) for p in paths]
+        if any(a.shape != imgs[0].shape for a in imgs):
+            raise ValueError(f"the four views of sample {i} differ in size: " + ", ".join(f"{p} {a.shape[0]}x{a.shape[1]}" for p, a in zip(paths, imgs)))
+        h, w, _ = imgs[0].shape
+        srcs = [torch.from_numpy(a).to(dev) for a in imgs]
+        planes = torch.empty((5, h, w, 3), dtype=torch.float32, device=dev)
+        ops.polar_views_u8(srcs, list(planes), mode, coef, 1.0, False)
+        ed = torch.round(planes[4]).clamp_(0, 255).to(torch.uint8).cpu().numpy()
+        out = os.path.join(out_dir, Path(paths[0]).stem + ".png")
+        Image.fromarray(ed).save(out)
+        written.append(out)
+    return written

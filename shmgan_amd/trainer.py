@@ -54,7 +54,7 @@ _DEFAULTS = dict(image_size=128, batch_size=1, filter_size=64, g_lr=0.00002, d_l
                  data_dir="", model_save_dir="./models", checkpoint_save_dir="./checkpoints", result_dir="./results",
                  log_dir="./logs/train", log_step=1, checkpoint_save_step=10, calc_metrics=False, test_dir="", diffuse_dir="",
                  save_images=False, image_values="rescale", image_out_size="source", image_dir="",
-                 loss_log_step=0, histogram_step=0, nonfinite=None)
+                 loss_log_step=0, histogram_step=0, nonfinite=None, diffuse_source="dir")
 
 
 class KernelAbortError(RuntimeError):
@@ -354,6 +354,21 @@ class ShmGANwithSSpecSeg:
         lane.submit(lambda: box.__setitem__("mask", self.SpecSeg.forward_plane(ds[2], 3, 0, B, tag=f"specseg/step{slot}")))
         return SimpleNamespace(slot=slot, key=tuple((t.data_ptr(), tuple(t.shape)) for t in orig), orig=orig, ds=ds,
                                scales=scales, cbcr=cbcr, mask=box["mask"])
+
+    def calcDOP(self, I0_Ych, I45_Ych, I90_Ych, I135_Ych):
+        """SHM.py:1157-1169: the degree-of-polarisation map of four views taken at 0 / 45 / 90 / 135 degrees (any shape: the Y
+        channels, as the reference names them, or whole RGB views), with the reference's coefficients S0 = I0 + I90,
+        S1 = I0 - I90, S2 = I45 - I135 and divide_no_nan -- on the device (shm_polar_maps).  Dead code in the reference (nothing
+        calls it, and its plot_single_image side effect is not reproduced); `polar_maps` is the general form."""
+        from .polar import REFERENCE_DOP_MATRIX
+        views = [self._dev(t) for t in (I0_Ych, I45_Ych, I90_Ych, I135_Ych)]
+        return ops.polar_maps(views, REFERENCE_DOP_MATRIX, ("dop",))["dop"]
+
+    def polar_maps(self, views, angles, want=("s0", "dop", "aolp")):
+        """{"s0", "dop", "aolp"} maps of four views taken at `angles` (degrees), through the least-squares Stokes matrix of
+        polar.stokes_matrix(angles): S0, sqrt(S1^2 + S2^2) / S0 (0 where S0 == 0) and 0.5 atan2(S2, S1) per element."""
+        from .polar import stokes_matrix
+        return ops.polar_maps([self._dev(t) for t in views], stokes_matrix(angles), want)
 
     def gram_matrix(self, x):
         """SHM.py:1176-1180 (host-side convenience on a torch tensor; not on the hot path)."""

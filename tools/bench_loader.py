@@ -1,0 +1,96 @@
+"""Batch preparation of the training loader (shmgan_amd.data.PolarDataset): one batch of B samples at S x S from a synthetic
+capture of HxH PNG files, with the diffuse target read from the ED/ directory (diffuse_source="dir": 5 B decodes, 5 B uploads,
+5 B shm_resize_bilinear_u8 launches) and computed on the device ("min": 4 B decodes, 4 B uploads, B shm_polar_views_u8 launches).
+
+Two figures per source, the two sources alternating within every repeat, median over the repeats after a warm-up:
+  device_ms   HIP events on the loader stream around the uploads and kernels alone: the decoded bytes are already in the pinned
+              staging buffers (the decode is replaced by a lookup), so this is what the GPU side of a batch costs
+  total_ms    host clock around prepare() -> the batch's event has completed, decode included (PIL, one worker thread)
+Launch and upload counts are counted, not assumed.  Prints one JSON line per source.
+python tools/bench_loader.py [--batch 8] [--size 256] [--source-size 1024] [--repeats 20] [--warmup 3]"""
+import argparse
+import json
+import statistics
+import sys
+import tempfile
+import time
+from pathlib import Path
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+import numpy as np
+import torch
+from shmgan_amd import ops
+from shmgan_amd.data import PSD_SUBDIRS, PolarDataset
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--batch", type=int, default=8)
+ap.add_argument("--size", type=int, default=256)
+ap.add_argument("--source-size", type=int, default=1024)
+ap.add_argument("--repeats", type=int, default=20)
+ap.add_argument("--warmup", type=int, default=3)
+ap.add_argument("--seed", type=int, default=0)
+a = ap.parse_args()
+if not torch.cuda.is_available():
+    sys.exit("bench_loader needs a GPU: there is nothing to time without one")
+B, S, H = a.batch, a.size, a.source_size
+
+counts = {"launches": 0, "uploads": 0}
+
+
+def counted(fn):
+    def call(*args, **kw):
+        counts["launches"] += 1
+        return fn(*args, **kw)
+    return call
+
+
+ops.resize_bilinear_u8 = counted(ops.resize_bilinear_u8)
+ops.polar_views_u8 = counted(ops.polar_views_u8)
+
+with tempfile.TemporaryDirectory() as root:
+    from PIL import Image
+    rng = np.random.default_rng(a.seed)
+    for sub in PSD_SUBDIRS:
+        (Path(root) / sub).mkdir()
+        for i in range(B):
+            Image.fromarray(rng.integers(0, 256, (H, H, 3)).astype(np.uint8)).save(Path(root) / sub / f"img_{i:03d}.png", compress_level=1)
+    sets = {src: PolarDataset(root, S, batch_size=B, diffuse_source=src, rank=0, world=1) for src in ("dir", "min")}
+
+    def run(ds):
+        """One batch through the loader's own worker; (host seconds until the batch's event completed, its tensors)."""
+        t0 = time.perf_counter()
+        outs, ev = ds.prepare(0).result()
+        ev.synchronize()
+        return time.perf_counter() - t0, outs
+
+    total = {src: [] for src in sets}
+    for r in range(a.warmup + a.repeats):
+        for src, ds in sets.items():
+            dt, _ = run(ds)
+            if r >= a.warmup:
+                total[src].append(dt * 1e3)
+
+    # the GPU side alone: both staging generations are filled by now, so the decode becomes a lookup (the upload still reads the pinned buffer)
+    device, per_batch = {src: [] for src in sets}, {}
+    for src, ds in sets.items():
+        def staged(path, key, ds=ds):
+            counts["uploads"] += 1
+            return ds._pin[key]
+        ds._decode = staged
+    for r in range(a.warmup + a.repeats):
+        for src, ds in sets.items():
+            counts["launches"] = counts["uploads"] = 0
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(ds.stream)
+            ds.prepare(0).result()
+            e1.record(ds.stream)
+            e1.synchronize()
+            per_batch[src] = dict(counts)
+            if r >= a.warmup:
+                device[src].append(e0.elapsed_time(e1))
+    for src in sets:
+        d, t = sorted(device[src]), sorted(total[src])
+        print(json.dumps({"tool": "bench_loader", "diffuse_source": src, "B": B, "S": S, "source": f"{H}x{H}",
+                          "launches": per_batch[src]["launches"], "uploads": per_batch[src]["uploads"],
+                          "device_ms": round(statistics.median(d), 4), "device_ms_min_max": [round(d[0], 4), round(d[-1], 4)],
+                          "total_ms": round(statistics.median(t), 3), "total_ms_min_max": [round(t[0], 3), round(t[-1], 3)],
+                          "repeats": a.repeats}), flush=True)

@@ -49,6 +49,29 @@ def pad_c(x, c):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# The rectangular-map tests (test_rect_gpu.py on the device, test_rect_cpu.py for the teeth of the checks on the CPU)
+
+RECT_TOL = {"f32": 1e-5, "bf16": 4e-3}          # rel-L2 of one conv op: fp32 / one bf16 rounding (test_variants_gpu.py)
+SENTINEL = 7.0
+
+
+def rect_close(got, ref, dt):
+    """The comparison every convolution case of test_rect_gpu.py makes: rel-L2 against float64."""
+    return rel_l2(got, ref) < RECT_TOL[dt]
+
+
+def guard_elems(shape):
+    """One patch row (16 map rows) of elements behind the logical end of an NHWC tensor."""
+    return 16 * int(shape[-2]) * int(shape[-1])
+
+
+def band_untouched(band, fill=SENTINEL):
+    """band: what lies behind the logical end of a tensor that was allocated with a guard band and filled with `fill`."""
+    b = band.detach().float().cpu().numpy() if isinstance(band, torch.Tensor) else np.asarray(band)
+    return bool((b == fill).all())
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # LeakyReLU kink pinning and gradient fixtures (whole-step tests on the device)
 
 def pin_kinks(m, gold, tile=1):

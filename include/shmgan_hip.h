@@ -511,6 +511,15 @@ int shm_image_losses(const float* gen_rgb, const float* cyc_rgb, const float* cy
 size_t shm_image_metrics_workspace(int batch, int s);
 int shm_image_metrics(const float* pred, const float* target, double* out, void* ws, size_t ws_bytes, int batch, int s,
                       void* stream);
+/* The same five numbers, same definitions, on a window of a padded prediction (native-resolution test mode): pred is
+ * [batch,hp,wp,3], the photo is its window of h x w pixels at (top, left), target is tight [batch,h,w,3].  Every mean, the
+ * rescale_01 min / max and the VALID 11-tap SSIM ((h-10)(w-10)*3 terms) are taken over the window only; nothing outside it is
+ * read.  Deterministic and batch-invariant like the square call; with (hp,wp) = (h,w) = (s,s) and (top,left) = (0,0) it runs the
+ * same kernels in the same order.  ws: shm_image_metrics_hw_workspace(batch, h, w) bytes.  SHM_E_SHAPE for a window side < 11, a
+ * window outside the frame or batch < 1, SHM_E_WORKSPACE for a short workspace, all before any launch. */
+size_t shm_image_metrics_hw_workspace(int batch, int h, int w);
+int shm_image_metrics_hw(const float* pred, int hp, int wp, int top, int left, const float* target, int h, int w, double* out,
+                         void* ws, size_t ws_bytes, int batch, void* stream);
 
 /* ---- SpecSeg mask network, inference only (SpecSeg.py:27-98; SpecSeg.predict at SHM.py:492) --
  * Its Conv2D(3x3, relu) layers are shm_conv2d_fwd with slope 0.  The rest: */
@@ -547,6 +556,8 @@ int shm_spec_loss(const float* cyc_y, const float* cbcr, const float* const* ds,
 /* MaxPooling2D(k x k) of mask [batch,s,s,1] (fp32) into channel 0 of dst [batch,s/k,s/k,lddst] (activation-typed, other
  * channels zeroed); k = 1 copies (attention_layer(pool=False), SHM.py:248). */
 int shm_mask_pool_pack(const float* mask, void* dst, int lddst, int batch, int s, int k, int dtype, void* stream);
+/* The rectangular form: mask [batch,h,w,1] into dst [batch,h/k,w/k,lddst]; h and w multiples of k. */
+int shm_mask_pool_pack_hw(const float* mask, void* dst, int lddst, int batch, int h, int w, int k, int dtype, void* stream);
 /* out[i] = a[i] + b[(i0 + i) % nb] for nimg images of `per` elements (per % 4 == 0): skip + attention map of the image's
  * sample (SHM.py:290-293, 359); in the batched plan image i0 + i of the batch is a copy of sample (i0 + i) % nb. */
 int shm_add_bcast(const void* a, const void* b, void* out, int nimg, size_t per, int nb, int i0, int dtype, void* stream);
@@ -558,6 +569,14 @@ int shm_sum_groups(const void* src, void* dst, int nimg, size_t per, int nb, int
  * float32 [ho,wo,c], times `scale` (1/255), optionally flipped top-to-bottom. */
 int shm_resize_bilinear_u8(const unsigned char* src, int hin, int win, int c, float* dst, int ho, int wo,
                            float scale, int flip_ud, void* stream);
+/* Native-resolution test mode: one decoded uint8 image [h,w,c] into the float32 frame [hp,wp,c] without resampling, the image at
+ * (top, left), the border filled by reflection WITHOUT repeating the edge sample (NumPy's mode="reflect"):
+ *   dst[y][x][k] = (float)src[r(y - top, h)][r(x - left, w)][k] * scale,   r(i, n) = i < 0 ? -i : i >= n ? 2 (n-1) - i : i
+ * One launch; 16-byte stores when dst is 16-byte aligned and hp*wp*c % 4 == 0, scalar stores otherwise (same values).
+ * SHM_E_SHAPE for a null pointer, a size outside [1, 32768], c > 16, an image that does not lie inside the frame or a pad wider
+ * than the image less one (the reflection would leave the image), before any launch. */
+int shm_load_pad_u8(const unsigned char* src, int h, int w, int c, float* dst, int hp, int wp, int top, int left, float scale,
+                    void* stream);
 
 /* ---- polarimetry: the estimated-diffuse target and the Stokes maps (utils.py:68-123 calculate_estimate_diffuse, whose imwrite
  * is commented out; SHM.py:1157-1169 calcDOP; neither is called by the reference's training path, which reads a pre-computed ED/
@@ -618,6 +637,15 @@ int shm_polar_maps(const float* const* view_ptrs, size_t n, const float* coef, f
 size_t shm_export_u8_workspace(int njobs);
 int shm_export_u8(const float* const* src, const size_t* desc, int njobs, const float* mul, int nmul, unsigned char* dst,
                   size_t dst_bytes, void* ws, size_t ws_bytes, void* stream);
+/* The job model of shm_export_u8 with a rectangular source and a source window (native-resolution test mode: the photo inside its
+ * padded frame).  desc holds SHM_EXPORT_HW_DESC size_t per job: {hs, ws, c, ld, y0, x0, hc, wc, ho, wo, mode, k, dst_off}: source
+ * src[j] float32 [hs,ws,c] with channel pitch ld, the window of hc x wc pixels at (y0, x0), destination [ho,wo,c].  RESCALE takes
+ * min and max over the window; the resampling maps the window to (ho,wo) (fy = (oy + 0.5) hc/ho - 0.5 clamped to the window's
+ * rows, x alike); (ho,wo) = (hc,wc) copies.  Nothing outside the window is read.  Value maps, quantisation, workspace
+ * (shm_export_u8_workspace) and argument checks as in shm_export_u8, plus SHM_E_SHAPE for a window outside the source. */
+#define SHM_EXPORT_HW_DESC 13
+int shm_export_u8_hw(const float* const* src, const size_t* desc, int njobs, const float* mul, int nmul, unsigned char* dst,
+                     size_t dst_bytes, void* ws, size_t ws_bytes, void* stream);
 /* The reference's running mean of the standardisation scales (test.py:77, 218, 246: stddev_arr is reset once per test run and
  * grows by one entry per image; each image uses the mean of every scale so far, its own included).  acc = caller-owned device
  * f64 {sum, count} ({0, 0} at the start of a run).  In image order, one thread: sum += scale[b], count += 1,

@@ -96,6 +96,8 @@ SIGNATURES = {
     "shm_image_losses": (I, [P, P, P, P, P, P, I, F, P, P, P, P, Z, I, I, P]),
     "shm_image_metrics_workspace": (Z, [I, I]),
     "shm_image_metrics": (I, [P, P, P, P, Z, I, I, P]),
+    "shm_image_metrics_hw_workspace": (Z, [I, I, I]),
+    "shm_image_metrics_hw": (I, [P, I, I, I, I, P, I, I, P, P, Z, I, P]),
     "shm_pack_channels": (I, [P, I, I, I, P, I, Z, P]),
     "shm_bn_apply": (I, [P, I, P, P, P, P, F, P, I, Z, I, P]),
     "shm_maxpool2_fwd": (I, [P, I, P, I, I, I, I, I, P]),
@@ -103,13 +105,16 @@ SIGNATURES = {
     "shm_head_sigmoid_fwd": (I, [P, I, P, P, P, Z, I, P]),
     "shm_spec_loss": (I, [P, P, P, P, P, I, Z, P]),
     "shm_mask_pool_pack": (I, [P, P, I, I, I, I, I, P]),
+    "shm_mask_pool_pack_hw": (I, [P, P, I, I, I, I, I, I, P]),
     "shm_add_bcast": (I, [P, P, P, I, Z, I, I, I, P]),
     "shm_sum_groups": (I, [P, P, I, Z, I, I, I, I, P]),
     "shm_resize_bilinear_u8": (I, [P, I, I, I, P, I, I, F, I, P]),
+    "shm_load_pad_u8": (I, [P, I, I, I, P, I, I, I, I, F, P]),
     "shm_polar_views_u8": (I, [P, I, I, P, I, P, I, I, F, I, P]),
     "shm_polar_maps": (I, [P, Z, P, P, P, P, P]),
     "shm_export_u8_workspace": (Z, [I]),
     "shm_export_u8": (I, [P, P, I, P, I, P, Z, P, Z, P]),
+    "shm_export_u8_hw": (I, [P, P, I, P, I, P, Z, P, Z, P]),
     "shm_running_scale_mean": (I, [P, I, P, P, P]),
     "shm_adam_clip": (I, [P, P, P, P, Z, F, F, F, F, F, P]),
     "shm_tensor_stats_workspace": (Z, [I, Z]),

@@ -85,18 +85,18 @@ extern "C" int shm_mul_mask(const void* x, const float* mask, void* y, size_t n,
 // ------------------------------------------------------ live attention branch (SHM.py:404-412, 290-293, 359)
 // MaxPooling2D(pool k x k, 'same' on sizes that are multiples of k) of the one-channel mask, written as channel 0 of an
 // activation tensor of pitch ld (the other channels zero): the 1 -> C convolution of attention_layer then runs on the
-// ordinary tap GEMM.  k = 1 copies (attention_layer(pool=False)).
+// ordinary tap GEMM.  k = 1 copies (attention_layer(pool=False)).  The mask is [batch,h,w,1]: the square call has h = w = s.
 template <typename T>
-__global__ void mask_pool_pack_kernel(const float* __restrict__ m, T* __restrict__ dst, int ld, int s, int k, size_t total) {
+__global__ void mask_pool_pack_kernel(const float* __restrict__ m, T* __restrict__ dst, int ld, int h, int w, int k, size_t total) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;          // output pixel (b, y, x)
     if (i >= total) return;
-    const int so = s / k;
-    const int x = (int)(i % so), y = (int)((i / so) % so);
-    const size_t b = i / ((size_t)so * so);
-    const float* src = m + (b * s + (size_t)y * k) * s + (size_t)x * k;
+    const int ho = h / k, wo = w / k;
+    const int x = (int)(i % wo), y = (int)((i / wo) % ho);
+    const size_t b = i / ((size_t)ho * wo);
+    const float* src = m + (b * h + (size_t)y * k) * w + (size_t)x * k;
     float v = src[0];
     for (int dy = 0; dy < k; ++dy)
-        for (int dx = 0; dx < k; ++dx) v = fmaxf(v, src[(size_t)dy * s + dx]);
+        for (int dx = 0; dx < k; ++dx) v = fmaxf(v, src[(size_t)dy * w + dx]);
     T* o = dst + i * ld;
     o[0] = (T)v;
     for (int c = 1; c < ld; ++c) o[c] = (T)0.f;
@@ -107,8 +107,19 @@ extern "C" int shm_mask_pool_pack(const float* mask, void* dst, int lddst, int b
     const size_t total = (size_t)batch * (s / k) * (s / k);
     if (total == 0) return SHM_OK;
     SHM_DISPATCH(dtype, "shm_mask_pool_pack",
-                 hipLaunchKernelGGL(mask_pool_pack_kernel<T>, dim3(shm_cdiv((long)total, 256)), dim3(256), 0, (hipStream_t)stream, mask, (T*)dst, lddst, s, k, total));
+                 hipLaunchKernelGGL(mask_pool_pack_kernel<T>, dim3(shm_cdiv((long)total, 256)), dim3(256), 0, (hipStream_t)stream, mask, (T*)dst, lddst, s, s, k, total));
     SHM_LAUNCH_CHECK("shm_mask_pool_pack");
+    return SHM_OK;
+}
+
+extern "C" int shm_mask_pool_pack_hw(const float* mask, void* dst, int lddst, int batch, int h, int w, int k, int dtype, void* stream) {
+    SHM_REQUIRE(mask && dst && k >= 1 && h >= 1 && w >= 1 && h % k == 0 && w % k == 0 && lddst >= 1 && batch >= 0, SHM_E_SHAPE,
+                "shm_mask_pool_pack_hw: bad shape (h %d, w %d, k %d)", h, w, k);
+    const size_t total = (size_t)batch * (h / k) * (w / k);
+    if (total == 0) return SHM_OK;
+    SHM_DISPATCH(dtype, "shm_mask_pool_pack_hw",
+                 hipLaunchKernelGGL(mask_pool_pack_kernel<T>, dim3(shm_cdiv((long)total, 256)), dim3(256), 0, (hipStream_t)stream, mask, (T*)dst, lddst, h, w, k, total));
+    SHM_LAUNCH_CHECK("shm_mask_pool_pack_hw");
     return SHM_OK;
 }
 

@@ -14,6 +14,10 @@
 //                   block first reduces its plane's partials
 // A job's bytes are a function of that job alone: batch composition, job order and launch geometry do not enter.
 // The job table travels as a kernel argument (SHM_EXPORT_MAX_JOBS jobs); the library allocates nothing and keeps no pointers.
+//
+// shm_export_u8_hw is the same two kernels on a window (y0, x0, hc, wc) of a rectangular source [hs,ws,C] (native-resolution test
+// mode: the photo inside its padded frame): a job carries the pointer to the window's first pixel, the window's size and the
+// frame's row pitch, so min / max and the resampling see the window only.  The square call is the window (0, 0, s, s) of pitch s.
 #include "common.h"
 
 #include <limits.h>
@@ -32,7 +36,8 @@ struct ExJob {
     unsigned long long dst;                     // byte offset of the job's output in dst
     int blk0;                                   // first export block
     int mblk0;                                  // first min / max block (RESCALE jobs only own any)
-    int s, ho, wo, ld;
+    int pitch, hc, wc;                          // the source window: hc x wc pixels, rows `pitch` pixels apart; src is its first pixel
+    int ho, wo, ld;
     int k;                                      // SCALE: index into mul
     int cmn;                                    // c | mode << 2 | nmm << 4
 };
@@ -59,9 +64,12 @@ __device__ __forceinline__ int find_job(const ExArgs& a, int bid, bool mm) {
     return j;
 }
 
-__device__ __forceinline__ float load_elem(const float* src, int e, int c, int ld) {
+// element e of the hc x wc x c window, rows `pitch` pixels apart
+__device__ __forceinline__ float load_elem(const float* src, int e, int c, int ld, int wc, int pitch) {
     const int p = c == 1 ? e : e / 3;
-    return src[(size_t)p * ld + (e - p * c)];
+    if (pitch == wc) return src[(size_t)p * ld + (e - p * c)];          // whole rows (always in the square call): no second division
+    const int y = p / wc;
+    return src[((size_t)y * pitch + (p - y * wc)) * ld + (e - p * c)];
 }
 
 __global__ void __launch_bounds__(EX_NT) export_minmax_kernel(const ExArgs a) {
@@ -70,10 +78,10 @@ __global__ void __launch_bounds__(EX_NT) export_minmax_kernel(const ExArgs a) {
     const ExJob& jb = a.job[j];
     const int c = jb.cmn & 3, nmm = jb.cmn >> 4;
     const int b = blockIdx.x - jb.mblk0;
-    const int n = jb.s * jb.s * c;
+    const int n = jb.hc * jb.wc * c;
     float lo = INFINITY, hi = -INFINITY;
     for (int e = b * EX_NT + threadIdx.x; e < n; e += nmm * EX_NT) {
-        const float v = load_elem(jb.src, e, c, jb.ld);
+        const float v = load_elem(jb.src, e, c, jb.ld, jb.wc, jb.pitch);
         lo = fminf(lo, v);
         hi = fmaxf(hi, v);
     }
@@ -102,7 +110,7 @@ __global__ void __launch_bounds__(EX_NT) export_u8_kernel(const ExArgs a) {
     const int j = find_job(a, blockIdx.x, false);
     const ExJob& jb = a.job[j];
     const int c = jb.cmn & 3, mode = (jb.cmn >> 2) & 3;
-    const int s = jb.s, ho = jb.ho, wo = jb.wo, ld = jb.ld;
+    const int hc = jb.hc, wc = jb.wc, pitch = jb.pitch, ho = jb.ho, wo = jb.wo, ld = jb.ld;
     const float* src = jb.src;
     float lo = 0.f, rng = 0.f, mul = 1.f;
     if (mode == SHM_EXPORT_RESCALE) {
@@ -127,8 +135,8 @@ __global__ void __launch_bounds__(EX_NT) export_u8_kernel(const ExArgs a) {
     } else if (mode == SHM_EXPORT_SCALE) {
         mul = a.mul[jb.k];
     }
-    const bool resample = ho != s || wo != s;
-    const float hs = (float)s / (float)ho, ws = (float)s / (float)wo;
+    const bool resample = ho != hc || wo != wc;
+    const float hs = (float)hc / (float)ho, ws = (float)wc / (float)wo;
     const int nbytes = ho * wo * c;
     unsigned char* out = a.dst + jb.dst;
     const int w0 = (blockIdx.x - jb.blk0) * (EX_NT * EX_WORDS) + threadIdx.x;
@@ -147,15 +155,15 @@ __global__ void __launch_bounds__(EX_NT) export_u8_kernel(const ExArgs a) {
                 // ResizeBilinear with half_pixel_centers, as resize_bilinear_u8_kernel (data.hip)
                 const float fy = ((float)oy + 0.5f) * hs - 0.5f, fx = ((float)ox + 0.5f) * ws - 0.5f;
                 const float fly = floorf(fy), flx = floorf(fx);
-                const int y0 = max((int)fly, 0), y1 = min((int)ceilf(fy), s - 1);
-                const int x0 = max((int)flx, 0), x1 = min((int)ceilf(fx), s - 1);
+                const int y0 = max((int)fly, 0), y1 = min((int)ceilf(fy), hc - 1);
+                const int x0 = max((int)flx, 0), x1 = min((int)ceilf(fx), wc - 1);
                 const float ly = fy - fly, lx = fx - flx;
-                const float tl = src[((size_t)y0 * s + x0) * ld + ch], tr = src[((size_t)y0 * s + x1) * ld + ch];
-                const float bl = src[((size_t)y1 * s + x0) * ld + ch], br = src[((size_t)y1 * s + x1) * ld + ch];
+                const float tl = src[((size_t)y0 * pitch + x0) * ld + ch], tr = src[((size_t)y0 * pitch + x1) * ld + ch];
+                const float bl = src[((size_t)y1 * pitch + x0) * ld + ch], br = src[((size_t)y1 * pitch + x1) * ld + ch];
                 const float top = tl + (tr - tl) * lx, bot = bl + (br - bl) * lx;
                 v = top + (bot - top) * ly;
             } else {
-                v = src[((size_t)oy * s + ox) * ld + ch];
+                v = src[((size_t)oy * pitch + ox) * ld + ch];
             }
             const float t = mode == SHM_EXPORT_RESCALE ? (rng != 0.f ? (v - lo) / rng : 0.f)
                           : mode == SHM_EXPORT_SCALE   ? v * mul
@@ -188,6 +196,38 @@ __global__ void __launch_bounds__(64) running_scale_mean_kernel(const float* __r
     }
     acc[0] = sum;
     acc[1] = cnt;
+}
+
+// one job's checked fields into the table; blk / mblk: the running block prefixes of the two passes
+void add_job(ExArgs& a, int j, const float* window, int pitch, int hc, int wc, int c, int ld, int ho, int wo, int mode, int k, size_t off,
+             int& blk, int& mblk) {
+    ExJob& jb = a.job[j];
+    jb.src = window;
+    jb.dst = off;
+    jb.pitch = pitch;
+    jb.hc = hc;
+    jb.wc = wc;
+    jb.ho = ho;
+    jb.wo = wo;
+    jb.ld = ld;
+    jb.k = mode == SHM_EXPORT_SCALE ? k : 0;
+    const int nmm = mode == SHM_EXPORT_RESCALE ? nmm_blocks((long)hc * wc * c) : 0;
+    jb.cmn = c | mode << 2 | nmm << 4;
+    jb.blk0 = blk;
+    jb.mblk0 = mblk;
+    blk += shm_cdiv((long)ho * wo * c, EX_BLOCK_BYTES);
+    mblk += nmm;
+}
+
+int export_launch(const ExArgs& a, int blk, int mblk, void* stream, const char* who) {
+    hipStream_t st = (hipStream_t)stream;
+    if (mblk > 0) {
+        hipLaunchKernelGGL(export_minmax_kernel, dim3(mblk), dim3(EX_NT), 0, st, a);
+        SHM_LAUNCH_CHECK(who);
+    }
+    hipLaunchKernelGGL(export_u8_kernel, dim3(blk), dim3(EX_NT), 0, st, a);
+    SHM_LAUNCH_CHECK(who);
+    return SHM_OK;
 }
 
 }  // namespace
@@ -225,32 +265,53 @@ extern "C" int shm_export_u8(const float* const* src, const size_t* desc, int nj
         SHM_REQUIRE((off & 3) == 0, SHM_E_SHAPE, "shm_export_u8: job %d: destination offset %zu not a multiple of 4", j, off);
         SHM_REQUIRE(off <= dst_bytes && nbytes <= dst_bytes - off, SHM_E_SHAPE,
                     "shm_export_u8: job %d: destination [%zu, %zu) outside dst_bytes %zu", j, off, off + nbytes, dst_bytes);
-        ExJob& jb = a.job[j];
-        jb.src = src[j];
-        jb.dst = off;
-        jb.s = (int)s;
-        jb.ho = (int)ho;
-        jb.wo = (int)wo;
-        jb.ld = (int)ld;
-        jb.k = mode == SHM_EXPORT_SCALE ? (int)k : 0;
-        const int nmm = mode == SHM_EXPORT_RESCALE ? nmm_blocks((long)(s * s * c)) : 0;
-        jb.cmn = (int)c | (int)mode << 2 | nmm << 4;
-        jb.blk0 = blk;
-        jb.mblk0 = mblk;
-        blk += shm_cdiv((long)nbytes, EX_BLOCK_BYTES);
-        mblk += nmm;
+        add_job(a, j, src[j], (int)s, (int)s, (int)s, (int)c, (int)ld, (int)ho, (int)wo, (int)mode, (int)k, off, blk, mblk);
     }
     const size_t need = shm_export_u8_workspace(njobs);
     SHM_REQUIRE(ws && ((uintptr_t)ws & 3) == 0 && ws_bytes >= need, SHM_E_WORKSPACE,
                 "shm_export_u8: workspace of %zu bytes (4-byte aligned) needed, %zu given", need, ws ? ws_bytes : 0);
-    hipStream_t st = (hipStream_t)stream;
-    if (mblk > 0) {
-        hipLaunchKernelGGL(export_minmax_kernel, dim3(mblk), dim3(EX_NT), 0, st, a);
-        SHM_LAUNCH_CHECK("shm_export_u8 (min / max)");
+    return export_launch(a, blk, mblk, stream, "shm_export_u8");
+}
+
+extern "C" int shm_export_u8_hw(const float* const* src, const size_t* desc, int njobs, const float* mul, int nmul, unsigned char* dst,
+                                size_t dst_bytes, void* ws, size_t ws_bytes, void* stream) {
+    SHM_REQUIRE(njobs >= 1 && njobs <= SHM_EXPORT_MAX_JOBS, SHM_E_SHAPE, "shm_export_u8_hw: njobs %d outside [1, %d]", njobs,
+                SHM_EXPORT_MAX_JOBS);
+    SHM_REQUIRE(src && desc && dst, SHM_E_SHAPE, "shm_export_u8_hw: null pointer (src, desc or dst)");
+    SHM_REQUIRE(((uintptr_t)dst & 3) == 0, SHM_E_SHAPE, "shm_export_u8_hw: dst is not 4-byte aligned");
+    ExArgs a;
+    a.dst = dst;
+    a.mul = mul;
+    a.mm = (float*)ws;
+    a.njobs = njobs;
+    int blk = 0, mblk = 0;
+    for (int j = 0; j < njobs; ++j) {
+        const size_t* d = desc + (size_t)j * SHM_EXPORT_HW_DESC;
+        const size_t hs = d[0], wsrc = d[1], c = d[2], ld = d[3], y0 = d[4], x0 = d[5], hc = d[6], wc = d[7], ho = d[8], wo = d[9], mode = d[10],
+                     k = d[11], off = d[12];
+        SHM_REQUIRE(src[j], SHM_E_SHAPE, "shm_export_u8_hw: job %d: null pointer (source plane)", j);
+        SHM_REQUIRE(c == 1 || c == 3, SHM_E_SHAPE, "shm_export_u8_hw: job %d: c %zu not in {1, 3}", j, c);
+        SHM_REQUIRE(hs >= 1 && hs <= EX_DIM_MAX && wsrc >= 1 && wsrc <= EX_DIM_MAX && ho >= 1 && ho <= EX_DIM_MAX && wo >= 1 && wo <= EX_DIM_MAX,
+                    SHM_E_SHAPE, "shm_export_u8_hw: job %d: sizes hs %zu, ws %zu, ho %zu, wo %zu outside [1, %d]", j, hs, wsrc, ho, wo, EX_DIM_MAX);
+        SHM_REQUIRE(hc >= 1 && wc >= 1 && y0 <= hs && hc <= hs - y0 && x0 <= wsrc && wc <= wsrc - x0, SHM_E_SHAPE,
+                    "shm_export_u8_hw: job %d: window (%zu, %zu, %zu, %zu) outside the %zu x %zu source", j, y0, x0, hc, wc, hs, wsrc);
+        SHM_REQUIRE(ld >= c && ld <= 65536, SHM_E_SHAPE, "shm_export_u8_hw: job %d: ld %zu outside [c, 65536]", j, ld);
+        const size_t nbytes = ho * wo * c;
+        SHM_REQUIRE(nbytes <= (size_t)INT_MAX - EX_BLOCK_BYTES && hc * wc * c <= (size_t)INT_MAX, SHM_E_SHAPE,
+                    "shm_export_u8_hw: job %d: plane too large", j);
+        SHM_REQUIRE(mode <= SHM_EXPORT_CLIP, SHM_E_SHAPE, "shm_export_u8_hw: job %d: mode %zu unknown", j, mode);
+        SHM_REQUIRE(mode != SHM_EXPORT_SCALE || (mul && nmul > 0 && k < (size_t)nmul), SHM_E_SHAPE,
+                    "shm_export_u8_hw: job %d: SCALE needs mul and k %zu < nmul %d", j, k, nmul);
+        SHM_REQUIRE((off & 3) == 0, SHM_E_SHAPE, "shm_export_u8_hw: job %d: destination offset %zu not a multiple of 4", j, off);
+        SHM_REQUIRE(off <= dst_bytes && nbytes <= dst_bytes - off, SHM_E_SHAPE,
+                    "shm_export_u8_hw: job %d: destination [%zu, %zu) outside dst_bytes %zu", j, off, off + nbytes, dst_bytes);
+        add_job(a, j, src[j] + (y0 * wsrc + x0) * ld, (int)wsrc, (int)hc, (int)wc, (int)c, (int)ld, (int)ho, (int)wo, (int)mode, (int)k, off, blk,
+                mblk);
     }
-    hipLaunchKernelGGL(export_u8_kernel, dim3(blk), dim3(EX_NT), 0, st, a);
-    SHM_LAUNCH_CHECK("shm_export_u8");
-    return SHM_OK;
+    const size_t need = shm_export_u8_workspace(njobs);
+    SHM_REQUIRE(ws && ((uintptr_t)ws & 3) == 0 && ws_bytes >= need, SHM_E_WORKSPACE,
+                "shm_export_u8_hw: workspace of %zu bytes (4-byte aligned) needed, %zu given", need, ws ? ws_bytes : 0);
+    return export_launch(a, blk, mblk, stream, "shm_export_u8_hw");
 }
 
 extern "C" int shm_running_scale_mean(const float* scale, int batch, double* acc, float* mul, void* stream) {

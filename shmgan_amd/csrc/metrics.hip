@@ -22,6 +22,10 @@
 //   ssim pass   grid (tiles, B, 3): reduces the min / max partials, stages the 26x26 halo of one 16x16 output tile in LDS, separable
 //               11-tap gaussian (as ssim_fwd_kernel of imgloss.hip, without the gradient maps), one f64 partial per block
 //   finalize    grid (B): out[b][5] = {mse, psnr, ssim, de76, de94} (f64)
+//
+// shm_image_metrics_hw is the same three kernels on a window (top, left, h, w) of a padded prediction [B,Hp,Wp,3] against a tight
+// target [B,h,w,3] (native-resolution test mode): every sum, the min / max and the SSIM run over the window's pixels only, in the
+// window's own row-major order -- nothing outside the window is read.  The square call is the window (0, 0, s, s) of an s x s frame.
 #include "common.h"
 
 #include <math.h>
@@ -33,15 +37,19 @@ constexpr int MTILE = 16;
 constexpr int MHALO = MTILE + MWIN - 1;     // 26
 constexpr int NT = 256;                     // threads per block, all three kernels
 
-// blocks per image of the pixel pass: a function of S alone (batch invariance)
-int pixel_blocks(int s) {
-    int n = shm_cdiv((long)s * s, 4 * NT);
+// the window of the prediction frame the metrics are taken on: frame pitch pw (pixels per row), origin (top, left), size h x w
+struct MetricWin {
+    int pw, top, left, h, w;
+};
+
+// blocks per image of the pixel pass: a function of the window's size alone (batch invariance)
+int pixel_blocks(int h, int w) {
+    int n = shm_cdiv((long)h * w, 4 * NT);
     return n > 256 ? 256 : n;
 }
 
-int ssim_tiles(int s) {
-    const int t = shm_cdiv(s - MWIN + 1, MTILE);
-    return t * t;
+int ssim_tiles(int h, int w) {
+    return shm_cdiv(h - MWIN + 1, MTILE) * shm_cdiv(w - MWIN + 1, MTILE);
 }
 
 struct MetricWs {
@@ -50,12 +58,12 @@ struct MetricWs {
 
 size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
-MetricWs plan_metric_ws(int batch, int s) {
+MetricWs plan_metric_ws(int batch, int h, int wd) {
     MetricWs w;
     size_t off = 0;
-    w.pix = off;  off = align256(off + (size_t)batch * pixel_blocks(s) * 3 * sizeof(double));
-    w.mm = off;   off = align256(off + (size_t)batch * pixel_blocks(s) * 4 * sizeof(float));
-    w.ssim = off; off = align256(off + (size_t)batch * 3 * ssim_tiles(s) * sizeof(double));
+    w.pix = off;  off = align256(off + (size_t)batch * pixel_blocks(h, wd) * 3 * sizeof(double));
+    w.mm = off;   off = align256(off + (size_t)batch * pixel_blocks(h, wd) * 4 * sizeof(float));
+    w.ssim = off; off = align256(off + (size_t)batch * 3 * ssim_tiles(h, wd) * sizeof(double));
     w.total = off;
     return w;
 }
@@ -98,15 +106,22 @@ __device__ __forceinline__ void rgb_to_lab(float r, float g, float b, float& L, 
 // ---------------------------------------------------------------------------------- pixel pass
 // grid (NP, B); pix[b][blk][3] = partial sums of (g-t)^2, dE76, dE94; mm[b][blk][4] = min g, max g, min t, max t
 __global__ __launch_bounds__(NT) void metrics_pixel_kernel(const float* __restrict__ g, const float* __restrict__ t, double* __restrict__ pix,
-                                                          float* __restrict__ mm, int s) {
+                                                          float* __restrict__ mm, const MetricWin win, size_t frame) {
     const int b = blockIdx.y, np = gridDim.x;
-    const size_t npix = (size_t)s * s;
-    const float* gi = g + (size_t)b * npix * 3;
+    const size_t npix = (size_t)win.h * win.w;
+    const float* gi = g + ((size_t)b * frame + (size_t)win.top * win.pw + win.left) * 3;      // the window's first pixel
     const float* ti = t + (size_t)b * npix * 3;
     float sq = 0.f, e76 = 0.f, e94 = 0.f;
     float gmn = INFINITY, gmx = -INFINITY, tmn = INFINITY, tmx = -INFINITY;
     for (size_t p = (size_t)blockIdx.x * NT + threadIdx.x; p < npix; p += (size_t)np * NT) {
-        const float g0 = gi[p * 3], g1 = gi[p * 3 + 1], g2 = gi[p * 3 + 2];
+        // p in the frame's pitch: p itself when the window spans whole rows (always in the square call); otherwise one 32-bit
+        // division (a padded frame has sides <= 32768: p < 2^30)
+        size_t gp = p;
+        if (win.pw != win.w) {
+            const unsigned y = (unsigned)p / (unsigned)win.w;
+            gp = (size_t)y * win.pw + ((unsigned)p - y * (unsigned)win.w);
+        }
+        const float g0 = gi[gp * 3], g1 = gi[gp * 3 + 1], g2 = gi[gp * 3 + 2];
         const float t0 = ti[p * 3], t1 = ti[p * 3 + 1], t2 = ti[p * 3 + 2];
         const float d0 = g0 - t0, d1 = g1 - t1, d2 = g2 - t2;
         sq += d0 * d0 + d1 * d1 + d2 * d2;
@@ -172,16 +187,16 @@ __device__ __forceinline__ void metrics_gauss1d(float* w) {
 
 // grid (tiles, B, 3); ssim[b][c][tile] = sum over the tile's valid outputs of luminance * contrast-structure
 __global__ __launch_bounds__(NT) void metrics_ssim_kernel(const float* __restrict__ g, const float* __restrict__ t, const float* __restrict__ mm,
-                                                         double* __restrict__ ssim, int s, int np) {
+                                                         double* __restrict__ ssim, const MetricWin win, size_t frame, int np) {
     __shared__ float xs[MHALO][MHALO + 1], ys[MHALO][MHALO + 1];
     __shared__ float hx[MHALO][MTILE + 1], hy[MHALO][MTILE + 1], hxy[MHALO][MTILE + 1], hsq[MHALO][MTILE + 1];
     __shared__ float w1[MWIN];
     __shared__ float wmm[NT / 64][4];
-    const int HO = s - MWIN + 1;
-    const int tiles_x = (HO + MTILE - 1) / MTILE, ntiles = tiles_x * tiles_x;
+    const int HO = win.h - MWIN + 1, WO = win.w - MWIN + 1;
+    const int tiles_x = (WO + MTILE - 1) / MTILE, ntiles = tiles_x * ((HO + MTILE - 1) / MTILE);
     const int ty = blockIdx.x / tiles_x, tx = blockIdx.x % tiles_x;
     const int b = blockIdx.y, c = blockIdx.z;
-    const size_t npix = (size_t)s * s;
+    const size_t npix = (size_t)win.h * win.w;
     // rescale_01's min / max of the whole image (min / max are exact: any order gives the same values)
     float r0 = INFINITY, r1 = -INFINITY, r2 = INFINITY, r3 = -INFINITY;
     for (int i = threadIdx.x; i < np; i += NT) {
@@ -212,15 +227,15 @@ __global__ __launch_bounds__(NT) void metrics_ssim_kernel(const float* __restric
     }
     const float xr = xmx - xmn, yr = ymx - ymn;       // divide_no_nan below: a zero range maps the image to 0
     const int oy0 = ty * MTILE, ox0 = tx * MTILE;
-    const float* gi = g + (size_t)b * npix * 3 + c;
+    const float* gi = g + ((size_t)b * frame + (size_t)win.top * win.pw + win.left) * 3 + c;
     const float* ti = t + (size_t)b * npix * 3 + c;
     for (int i = threadIdx.x; i < MHALO * MHALO; i += NT) {
         const int r = i / MHALO, cc = i % MHALO;
         const int yy = oy0 + r, xx = ox0 + cc;
         float xv = 0.f, yv = 0.f;
-        if (yy < s && xx < s) {
-            const size_t p = (size_t)yy * s + xx;
-            xv = xr != 0.f ? (gi[p * 3] - xmn) / xr : 0.f;
+        if (yy < win.h && xx < win.w) {
+            const size_t gp = (size_t)yy * win.pw + xx, p = (size_t)yy * win.w + xx;
+            xv = xr != 0.f ? (gi[gp * 3] - xmn) / xr : 0.f;
             yv = yr != 0.f ? (ti[p * 3] - ymn) / yr : 0.f;
         }
         xs[r][cc] = xv;
@@ -247,7 +262,7 @@ __global__ __launch_bounds__(NT) void metrics_ssim_kernel(const float* __restric
     const int ly = threadIdx.x / MTILE, lx = threadIdx.x % MTILE;
     const int oy = oy0 + ly, ox = ox0 + lx;
     double v = 0.0;
-    if (oy < HO && ox < HO) {
+    if (oy < HO && ox < WO) {
         float mx_ = 0.f, my_ = 0.f, exy = 0.f, esq = 0.f;
         for (int i = 0; i < MWIN; ++i) {
             mx_ += w1[i] * hx[ly + i][lx];
@@ -267,7 +282,7 @@ __global__ __launch_bounds__(NT) void metrics_ssim_kernel(const float* __restric
 // ------------------------------------------------------------------------------------ finalize
 // grid (B): every thread sums a fixed stride of slots in slot order, then the block sums in thread order
 __global__ __launch_bounds__(NT) void metrics_finalize_kernel(const double* __restrict__ pix, const double* __restrict__ ssim, double* __restrict__ out,
-                                                             int s, int np, int ntiles) {
+                                                             int h, int w, int np, int ntiles) {
     const int b = blockIdx.x;
     double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
     for (int i = threadIdx.x; i < np; i += NT) {
@@ -282,22 +297,40 @@ __global__ __launch_bounds__(NT) void metrics_finalize_kernel(const double* __re
     a2 = block_sum_fixed(a2);
     a3 = block_sum_fixed(a3);
     if (threadIdx.x == 0) {
-        const double npix = (double)s * s, ho = (double)(s - MWIN + 1);
+        const double npix = (double)h * w, nssim = (double)(h - MWIN + 1) * (double)(w - MWIN + 1);
         const double mse = a0 / (3.0 * npix);
         double* o = out + (size_t)b * 5;
         o[0] = mse;
         o[1] = mse > 0.0 ? -10.0 * log10(mse) : INFINITY;
-        o[2] = a3 / (3.0 * ho * ho);
+        o[2] = a3 / (3.0 * nssim);
         o[3] = a1 / npix;
         o[4] = a2 / npix;
     }
+}
+
+// the three launches of both entry points; frame = pixels per image of pred
+int metrics_launch(const float* pred, const float* target, double* out, void* ws, const MetricWs& w, int batch, const MetricWin& win, size_t frame,
+                   void* stream, const char* who) {
+    hipStream_t st = (hipStream_t)stream;
+    char* base = (char*)ws;
+    double* pix = (double*)(base + w.pix);
+    float* mm = (float*)(base + w.mm);
+    double* ssim = (double*)(base + w.ssim);
+    const int np = pixel_blocks(win.h, win.w), nt = ssim_tiles(win.h, win.w);
+    hipLaunchKernelGGL(metrics_pixel_kernel, dim3(np, batch), dim3(NT), 0, st, pred, target, pix, mm, win, frame);
+    SHM_LAUNCH_CHECK(who);
+    hipLaunchKernelGGL(metrics_ssim_kernel, dim3(nt, batch, 3), dim3(NT), 0, st, pred, target, mm, ssim, win, frame, np);
+    SHM_LAUNCH_CHECK(who);
+    hipLaunchKernelGGL(metrics_finalize_kernel, dim3(batch), dim3(NT), 0, st, pix, ssim, out, win.h, win.w, np, nt);
+    SHM_LAUNCH_CHECK(who);
+    return SHM_OK;
 }
 
 }  // namespace
 
 extern "C" size_t shm_image_metrics_workspace(int batch, int s) {
     if (s < MWIN || batch < 1) return 0;
-    return plan_metric_ws(batch, s).total;
+    return plan_metric_ws(batch, s, s).total;
 }
 
 extern "C" int shm_image_metrics(const float* pred, const float* target, double* out, void* ws, size_t ws_bytes, int batch, int s,
@@ -305,19 +338,26 @@ extern "C" int shm_image_metrics(const float* pred, const float* target, double*
     SHM_REQUIRE(s >= MWIN, SHM_E_SHAPE, "shm_image_metrics: image size %d < 11 (ssim window)", s);
     SHM_REQUIRE(batch >= 1 && batch <= 65535, SHM_E_SHAPE, "shm_image_metrics: bad batch %d", batch);
     SHM_REQUIRE(pred && target && out, SHM_E_SHAPE, "shm_image_metrics: null pointer");
-    const MetricWs w = plan_metric_ws(batch, s);
+    const MetricWs w = plan_metric_ws(batch, s, s);
     SHM_REQUIRE(ws && ws_bytes >= w.total, SHM_E_WORKSPACE, "shm_image_metrics: workspace %zu < %zu bytes", ws_bytes, w.total);
-    hipStream_t st = (hipStream_t)stream;
-    char* base = (char*)ws;
-    double* pix = (double*)(base + w.pix);
-    float* mm = (float*)(base + w.mm);
-    double* ssim = (double*)(base + w.ssim);
-    const int np = pixel_blocks(s), nt = ssim_tiles(s);
-    hipLaunchKernelGGL(metrics_pixel_kernel, dim3(np, batch), dim3(NT), 0, st, pred, target, pix, mm, s);
-    SHM_LAUNCH_CHECK("shm_image_metrics(pixel)");
-    hipLaunchKernelGGL(metrics_ssim_kernel, dim3(nt, batch, 3), dim3(NT), 0, st, pred, target, mm, ssim, s, np);
-    SHM_LAUNCH_CHECK("shm_image_metrics(ssim)");
-    hipLaunchKernelGGL(metrics_finalize_kernel, dim3(batch), dim3(NT), 0, st, pix, ssim, out, s, np, nt);
-    SHM_LAUNCH_CHECK("shm_image_metrics(finalize)");
-    return SHM_OK;
+    const MetricWin win = {s, 0, 0, s, s};
+    return metrics_launch(pred, target, out, ws, w, batch, win, (size_t)s * s, stream, "shm_image_metrics");
+}
+
+extern "C" size_t shm_image_metrics_hw_workspace(int batch, int h, int w) {
+    if (h < MWIN || w < MWIN || batch < 1) return 0;
+    return plan_metric_ws(batch, h, w).total;
+}
+
+extern "C" int shm_image_metrics_hw(const float* pred, int hp, int wp, int top, int left, const float* target, int h, int w, double* out,
+                                    void* ws, size_t ws_bytes, int batch, void* stream) {
+    SHM_REQUIRE(h >= MWIN && w >= MWIN, SHM_E_SHAPE, "shm_image_metrics_hw: window %d x %d has a side < 11 (ssim window)", h, w);
+    SHM_REQUIRE(top >= 0 && left >= 0 && hp >= 1 && wp >= 1 && hp <= 32768 && wp <= 32768 && top <= hp - h && left <= wp - w, SHM_E_SHAPE,
+                "shm_image_metrics_hw: window (%d, %d, %d, %d) outside the %d x %d frame", top, left, h, w, hp, wp);
+    SHM_REQUIRE(batch >= 1 && batch <= 65535, SHM_E_SHAPE, "shm_image_metrics_hw: bad batch %d", batch);
+    SHM_REQUIRE(pred && target && out, SHM_E_SHAPE, "shm_image_metrics_hw: null pointer");
+    const MetricWs pl = plan_metric_ws(batch, h, w);
+    SHM_REQUIRE(ws && ws_bytes >= pl.total, SHM_E_WORKSPACE, "shm_image_metrics_hw: workspace %zu < %zu bytes", ws_bytes, pl.total);
+    const MetricWin win = {wp, top, left, h, w};
+    return metrics_launch(pred, target, out, ws, pl, batch, win, (size_t)hp * wp, stream, "shm_image_metrics_hw");
 }

@@ -116,7 +116,7 @@ extern "C" int shm_get_tuning(const char* key, int* value) {
 
 extern "C" const char* shm_last_error(void) { return g_err; }
 extern "C" const char* shm_last_kernel(void) { return g_kernel; }
-extern "C" int shm_version(void) { return 201; }
+extern "C" int shm_version(void) { return 202; }
 
 // shm_set_abort_words: where a kernel that had to give up (today: a barrier of in_bwd_fused8_kernel that timed out) says so for THIS thread's
 // later calls.  dev_word: u32 in device memory, OR-ed to non-zero; shm_adam_clip reads it on the device and applies NOTHING while it is set, so a

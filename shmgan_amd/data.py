@@ -289,3 +289,89 @@ class EvalDataset:
             cur = nxt.result()
             nxt = self._pool.submit(self._decode_batch, i + 1) if i + 1 < len(self) else None
             yield self.batch(i, cur)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Native-resolution test mode (evaluate.test(eval_size="native")): a photo runs at its own h x w.  The networks pool four times,
+# so the frame they see has sides that are multiples of 16; THIS is the one place that says how a photo becomes such a frame.
+FRAME_MULTIPLE = 16          # four 2 x 2 pools (generator and SpecSeg)
+MIN_NATIVE_SIDE = 32         # the deepest map is then 2 x 2, and a pad of at most 15 stays inside the image (reflection needs pad <= side - 1)
+
+
+def pad_geometry(h, w):
+    """(Hp, Wp, top, left) of the frame of an h x w photo: Hp = ceil16(h), Wp = ceil16(w), the photo centred with the odd pixel
+    of the pad below / to the right: top = (Hp - h) // 2, left = (Wp - w) // 2.  The border is filled by reflection without
+    repeating the edge sample (NumPy's mode="reflect"; shm_load_pad_u8).  Standardisation, SpecSeg and the generator see the
+    frame; metrics and export see the window (top, left, h, w).  A side below MIN_NATIVE_SIDE raises ValueError."""
+    h, w = int(h), int(w)
+    if h < MIN_NATIVE_SIDE or w < MIN_NATIVE_SIDE:
+        raise ValueError(f"native-resolution evaluation takes images of at least {MIN_NATIVE_SIDE} x {MIN_NATIVE_SIDE} pixels, got {h} x {w}")
+    m = FRAME_MULTIPLE
+    hp, wp = (h + m - 1) // m * m, (w + m - 1) // m * m
+    return hp, wp, (hp - h) // 2, (wp - w) // 2
+
+
+class NativeEvalDataset:
+    """The test-mode loader at each photo's own resolution: per image (frame [1,Hp,Wp,3], target [1,h,w,3] or None, window
+    (top, left, h, w)), float32 device tensors in [0,1].  Same file listing and pairing as EvalDataset (eval_file_lists), same
+    decode (PIL on a worker thread, one image ahead); the frame is ONE shm_load_pad_u8 call on the decoded bytes (pad_geometry),
+    the diffuse target is uploaded tight (the same call without a pad).  Batch size is 1: sizes differ per image.
+    check(path, h, w): called after the decode and before anything is allocated or launched for the image (evaluate.test refuses
+    images over its limits there).  A diffuse partner of another size than its test image raises ValueError naming both files."""
+
+    def __init__(self, test_dir, diffuse_dir=None, device=None, check=None):
+        self.B = 1
+        self.test_files, self.diffuse_files = eval_file_lists(test_dir, diffuse_dir)
+        self.n = len(self.test_files)
+        self.rank, self.world = 0, 1
+        self._dev, self._check = device, check
+        self._pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="shm-eval-loader")
+        self._sizes = {}
+
+    dev = EvalDataset.dev
+    _decode = staticmethod(EvalDataset._decode)
+
+    def __len__(self):
+        return self.n
+
+    def batch_range(self, index):
+        return index, index + 1
+
+    def _decode_pair(self, index):
+        test = self._decode(self.test_files[index])
+        self._sizes[index] = test.shape[:2]
+        diffuse = None if self.diffuse_files is None else self._decode(self.diffuse_files[index])
+        return test, diffuse
+
+    def sources(self, index):
+        """[(path, (h, w))] of image `index`, as EvalDataset.sources."""
+        if index not in self._sizes:
+            from PIL import Image
+            with Image.open(self.test_files[index]) as im:
+                self._sizes[index] = (im.size[1], im.size[0])
+        return [(self.test_files[index], tuple(int(v) for v in self._sizes[index]))]
+
+    def _upload(self, a, hp, wp, top, left):
+        out = torch.empty((1, hp, wp, 3), dtype=torch.float32, device=self.dev)
+        ops.load_pad_u8(torch.from_numpy(a).to(self.dev), out[0], top, left, 1.0 / 255.0)
+        return out
+
+    def batch(self, index, decoded=None):
+        test, diffuse = decoded if decoded is not None else self._decode_pair(index)
+        h, w = (int(v) for v in test.shape[:2])
+        if diffuse is not None and tuple(diffuse.shape[:2]) != (h, w):
+            raise ValueError(f"native-resolution evaluation compares a test image with its diffuse partner pixel by pixel: "
+                             f"{self.test_files[index]} is {h} x {w}, {self.diffuse_files[index]} is {diffuse.shape[0]} x {diffuse.shape[1]}")
+        hp, wp, top, left = pad_geometry(h, w)
+        if self._check is not None:
+            self._check(self.test_files[index], h, w)
+        frame = self._upload(test, hp, wp, top, left)
+        target = None if diffuse is None else self._upload(diffuse, h, w, 0, 0)
+        return frame, target, (top, left, h, w)
+
+    def __iter__(self):
+        nxt = self._pool.submit(self._decode_pair, 0) if self.n else None
+        for i in range(self.n):
+            cur = nxt.result()
+            nxt = self._pool.submit(self._decode_pair, i + 1) if i + 1 < self.n else None
+            yield self.batch(i, cur)

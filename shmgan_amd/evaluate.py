@@ -24,6 +24,17 @@ gen_rgb_output / 255, and clips.  The mask is always clipped.  `image_out_size` 
 (bilinear, half-pixel centres: the inverse direction of the loader's resize), "model" writes S x S.  `image_dir` defaults to
 `<result_dir>/images`.  The bytes come from the library's exporter (ops.export_u8, one call per batch); PNG encoding runs on a
 pool of writer threads while the next batch is evaluated.
+
+Native resolution (`eval_size`: "model", the default, is everything above; "native"): every test image and its diffuse partner
+are loaded at their own h x w, padded by reflection to multiples of 16 (data.pad_geometry: the one place that states the rule),
+standardised, segmented and generated on that frame, and scored and exported on the photo's window of it -- no resize anywhere.
+G1 always runs; the five cyclic passes run only with `save_images="all"` (nothing else uses them), one after the other.
+`image_out_size` is ignored: the output is the photo's size.  `eval_batch_size` must be 1 (sizes differ per image).  The
+per-image "Time" covers whatever passes were run (G1, or G1 and the cyclic passes), SpecSeg and the metrics.  An image is
+refused with ValueError, before anything is allocated or launched for it, when a tensor of its frame would pass
+MAX_TENSOR_BYTES or MAX_FRAME_SIDE, or when native_frame_bytes() of its frame does not fit the free device memory
+(MEMORY_HEADROOM); the message names the file and points to eval_size="model".  InstanceNorm statistics are per whole image,
+so a frame is never tiled.
 """
 from __future__ import annotations
 
@@ -36,7 +47,9 @@ from concurrent.futures import ThreadPoolExecutor
 import torch
 
 from . import ops
-from .data import EvalDataset
+from .data import EvalDataset, NativeEvalDataset, pad_geometry
+from .model import generator_layers, pad_channels
+from .specseg import WIDTHS as SPECSEG_WIDTHS
 
 TABLE_HEADERS = ["Image#", "Time", "MSE", "SSIM", "PSNR", "delE76", "delE94"]                  # test.py:371
 MEAN_HEADERS = ["Mean MSE", "Mean SSIM", "Mean PSNR", "Mean dleE76", "Mean delE94"]           # test.py:381 (sic)
@@ -46,6 +59,17 @@ SAVE_IMAGES = {"g1": IMAGE_TAGS[:1], "all": IMAGE_TAGS}
 IMAGE_VALUES = ("rescale", "output")
 IMAGE_OUT_SIZES = ("source", "model")
 IMAGE_WRITERS = 4                                             # PNG encoder threads (at most 16)
+EVAL_SIZES = ("model", "native")
+# Largest per-tensor extent, in bytes, the native path supports: every convolution of the generator and of SpecSeg goes through
+# launch_tapgemm (csrc/conv_igemm.hip), whose kernels address their operands with 32-bit byte offsets into buffer descriptors
+# (0xffffffff is the "outside the image" offset) and which therefore requires `xb < lim`, xb = batch * hi * wi * ldx * esz and
+# lim = 0xfffffff0, for every operand.  The widest tensors of a frame are the level-0 activations (filter_size channels) and
+# the 64-byte-per-pixel network inputs (native_max_tensor_bytes).  The elementwise, InstanceNorm, head and colour kernels index
+# with size_t; the pixel count (int32 in the launcher) and the exporter's 2^31 elements per plane bind later than this.
+# A module attribute on purpose: tests lower it instead of allocating a huge image.
+MAX_TENSOR_BYTES = 0xfffffff0
+MAX_FRAME_SIDE = 32768                                        # shm_load_pad_u8, shm_image_metrics_hw, shm_export_u8_hw: sides in [1, 32768]
+MEMORY_HEADROOM = 0.9                                         # fraction of the free device memory a frame's buffers may take
 
 
 def format_table(rows, headers):
@@ -105,12 +129,90 @@ def image_options(save, values, out_size):
     return tags
 
 
+def _esz(dtype):
+    return torch.empty((), dtype=dtype).element_size()
+
+
+def native_max_tensor_bytes(hp, wp, filter_size, dtype=torch.float32):
+    """Bytes of the largest single tensor a batch-1 native forward on an hp x wp frame hands a kernel: the level-0 activations
+    [hp,wp,filter_size] in the activation dtype, or the 64-byte-per-pixel inputs (the generator's padded input, SpecSeg's
+    float32 [hp,wp,16]), whichever is wider.  Deeper levels have twice the channels on a quarter of the pixels."""
+    return int(hp) * int(wp) * max(int(filter_size) * _esz(dtype), pad_channels(dtype) * _esz(dtype), 16 * 4)
+
+
+def native_frame_bytes(hp, wp, filter_size, dtype=torch.float32, cyclic=True, attention=False):
+    """Device bytes the buffers of one native-resolution image on an hp x wp frame (multiples of 16) take, counted from the layer
+    tables (model.generator_layers, specseg.WIDTHS) exactly as trainer.infer / Generator.forward / SpecSeg.forward_plane name
+    them: every buffer proportional to the frame (per-channel statistics and workspaces, some kilobytes, are left out), no
+    InstanceNorm folding (folding only removes buffers).  Linear in hp * wp.  The cyclic passes reuse the G1 pass's activations:
+    `cyclic` adds only their 5 inputs and 5 outputs."""
+    hp, wp, F = int(hp), int(wp), int(filter_size)
+    if hp % 16 or wp % 16:
+        raise ValueError(f"a frame has sides that are multiples of 16, got {hp} x {wp}")
+    e, pad = _esz(dtype), pad_channels(dtype)
+    px = hp * wp
+
+    def lvl(l):
+        return (hp >> l) * (wp >> l)
+    n = 0
+    # ---- loader and trainer.infer: frame + tight target (float32 RGB), yuv, cbcr, generator input, gen_rgb
+    n += px * (12 + 12 + 12 + 8 + pad * e + 12)
+    if cyclic:
+        n += px * (4 + 4 + 5 * pad * e + 5 * 12)                  # orig_Ych, G1's Y kept beside the cyclic passes, cyc_in, cyc_rgb
+    # ---- Generator.forward ("inf1"): per Conv -> LeakyReLU -> InstanceNorm block the conv output and the normalised tensor
+    L = generator_layers(F)
+    for l in range(4):                                            # encoder level l: two blocks, the pooled tensor
+        c = L[2 * l][4]
+        n += lvl(l) * c * e * 4 + lvl(l + 1) * c * e
+        if attention:                                             # skip + attention map, and the branch's mask / y1 / y2
+            n += lvl(l) * e * (c + pad + 2 * c)
+    n += lvl(4) * L[8][4] * e * 4                                 # the two 1x1 blocks
+    for j in range(4):                                            # decoder level 3 - j: Conv2DTranspose output, two blocks
+        l, li = 3 - j, 10 + 3 * j
+        n += lvl(l) * e * (L[li][4] + 2 * L[li + 1][4] + 2 * L[li + 2][4])
+    n -= px * L[21][4] * e                                        # the last block is normalised by the head on the fly
+    n += px * 4                                                   # gen_Y
+    # ---- SpecSeg.forward_plane (float32): packed input, per level two conv outputs + BN, pooled; decoder: up + two convs; mask
+    n += px * 16 * 4
+    for l, w in enumerate(SPECSEG_WIDTHS):
+        n += lvl(l) * w * 4 * 3 + (lvl(l + 1) * w * 4 if l < 4 else 0)
+    for l in (3, 2, 1, 0):
+        n += lvl(l) * SPECSEG_WIDTHS[l] * 4 * 3
+    n += px * 4
+    # ---- image export: up to 8 planes of bytes (6 RGB, 2 single-channel) on the device
+    n += px * (6 * 3 + 2)
+    return n
+
+
+def check_native_limits(path, h, w, filter_size, dtype=torch.float32, cyclic=True, attention=False, free_bytes=None):
+    """Raise ValueError if the native path cannot take the h x w image `path`: a frame side over MAX_FRAME_SIDE, a tensor over
+    MAX_TENSOR_BYTES, or (free_bytes given) native_frame_bytes over MEMORY_HEADROOM * free_bytes.  Host arithmetic only."""
+    hp, wp, _, _ = pad_geometry(h, w)
+    why = None
+    big = native_max_tensor_bytes(hp, wp, filter_size, dtype)
+    need = native_frame_bytes(hp, wp, filter_size, dtype, cyclic, attention)
+    if max(hp, wp) > MAX_FRAME_SIDE:
+        why = f"a side of its {hp} x {wp} frame is over {MAX_FRAME_SIDE}"
+    elif big >= MAX_TENSOR_BYTES:
+        why = (f"the largest tensor of its {hp} x {wp} frame takes {big} bytes, and the convolution kernels address a tensor with "
+               f"32-bit byte offsets (limit {MAX_TENSOR_BYTES})")
+    elif free_bytes is not None and need > MEMORY_HEADROOM * free_bytes:
+        why = (f"its {hp} x {wp} frame needs {need / 2**30:.2f} GiB of device buffers and {free_bytes / 2**30:.2f} GiB are free "
+               f"(headroom {MEMORY_HEADROOM})")
+    if why is not None:
+        raise ValueError(f"{path} ({h} x {w}) is too large for eval_size='native': {why}.  Evaluate it with eval_size='model' "
+                         f"(resized to image_size x image_size), or downscale the file")
+    return need
+
+
 class ImageExporter:
     """Writes a batch's images after its evaluation: one ops.export_u8 call on the current stream into a device byte buffer, a
     copy into one of two pinned staging generations, an event, then the PNG encode and write on a pool of writer threads.
     The main thread blocks only when the generation it is about to fill is still being written by the batch before last."""
 
     def __init__(self, image_dir, tags, values, out_size, device, workers=IMAGE_WRITERS):
+        """out_size "native": submit() is given each image's window of the frame and writes exactly that window
+        (ops.export_u8_hw: min / max of "rescale" over the window, no resampling)."""
         self.dir, self.tags, self.values, self.out_size = image_dir, tuple(tags), values, out_size
         os.makedirs(image_dir, exist_ok=True)
         self.pool = ThreadPoolExecutor(max_workers=max(1, min(int(workers), 16)), thread_name_prefix="shm-png")
@@ -133,9 +235,12 @@ class ImageExporter:
             return mask[b]
         return cyc[IMAGE_TAGS.index(tag) - 2][b]
 
-    def submit(self, shmgan, gen_rgb, cyc, sources):
-        """Enqueue batch `sources` ((path, (h, w)) per image, in batch order) of the evaluation just issued."""
+    def submit(self, shmgan, gen_rgb, cyc, sources, windows=None):
+        """Enqueue batch `sources` ((path, (h, w)) per image, in batch order) of the evaluation just issued.  windows (out_size
+        "native"): (top, left, h, w) per image, the photo inside the frame."""
         B, S = int(gen_rgb.shape[0]), int(gen_rgb.shape[1])
+        native = self.out_size == "native"
+        wins = []
         mul = None
         if self.values == "output":
             if self.mul is None or self.mul.numel() < B:
@@ -144,8 +249,9 @@ class ImageExporter:
             ops.running_scale_mean(shmgan.stddev_arr[0], self.acc, mul)
         planes, sizes, modes, jobs = [], [], [], []
         for b, (path, hw) in enumerate(sources):
-            size = tuple(hw) if self.out_size == "source" else (S, S)
+            size = tuple(windows[b][2:]) if native else tuple(hw) if self.out_size == "source" else (S, S)
             for tag in self.tags:
+                wins.append(tuple(windows[b]) if native else None)
                 p = self._plane(tag, b, gen_rgb, cyc, shmgan.gen_Y, shmgan.specular_candidate)
                 planes.append(p)
                 sizes.append(size)
@@ -156,7 +262,10 @@ class ImageExporter:
             self.buf = torch.empty(total, dtype=torch.uint8, device=self.dev)
         # gen_rgb, the cyclic images, gen_Y and the mask are arena tensors that the next evaluate() overwrites: the export
         # reads them before that only because both are ordered on this one stream.  The same holds for self.buf and the copy.
-        ops.export_u8(planes, sizes, modes, mul, self.buf, arena=shmgan.arena)
+        if native:
+            ops.export_u8_hw(planes, wins, sizes, modes, mul, self.buf, arena=shmgan.arena)
+        else:
+            ops.export_u8(planes, sizes, modes, mul, self.buf, arena=shmgan.arena)
         g = self.gen
         self._wait(g)                       # the batch before last: its writers read this generation
         if self.stage[g] is None or self.stage[g].numel() < total:
@@ -193,7 +302,10 @@ def _write_png(ev, stage, off, size, c, path):
 
 def test(shmgan, args, *, print_fn=print):
     """main.py:110 `test(shmgan, args)`.  Reads args.test_dir, args.diffuse_dir, args.calc_metrics and args.eval_batch_size
-    (default 1), and the image export's args.save_images, image_values, image_out_size, image_dir (module docstring); model
+    (default 1), args.eval_size ("model", the default: every image resized to image_size x image_size; "native": every image at
+    its own size -- eval_batch_size must then be 1, image_out_size is ignored, and "Time" covers the passes that were run: G1,
+    plus the five cyclic passes with save_images="all"; module docstring), and the image export's args.save_images, image_values,
+    image_out_size, image_dir (module docstring); model
     and folder settings come from the trainer (`image_size`, `checkpoint_save_dir`, `log_dir`, `result_dir`).  Returns a
     dict: "index" (1-based image numbers), "time" (seconds per image), "images" and "files" (the exported image paths, in
     batch order; empty without save_images); with calc_metrics also the per-image lists "MSE", "SSIM", "PSNR", "delE76",
@@ -202,6 +314,12 @@ def test(shmgan, args, *, print_fn=print):
     calc = bool(_arg(shmgan, args, "calc_metrics", False))
     diffuse_dir = _arg(shmgan, args, "diffuse_dir", "") if calc else None
     B = int(_arg(shmgan, args, "eval_batch_size", 1) or 1)
+    eval_size = _arg(shmgan, args, "eval_size", "model") or "model"
+    if eval_size not in EVAL_SIZES:
+        raise ValueError(f"eval_size {eval_size!r} is not one of {EVAL_SIZES}")
+    native = eval_size == "native"
+    if native and B != 1:
+        raise ValueError(f"eval_size='native' evaluates one image at a time (sizes differ per image): eval_batch_size must be 1, got {B}")
     if not test_dir:
         raise ValueError("test mode needs args.test_dir")
     if calc and not diffuse_dir:
@@ -209,7 +327,23 @@ def test(shmgan, args, *, print_fn=print):
     tags = image_options(_arg(shmgan, args, "save_images", False), _arg(shmgan, args, "image_values", "rescale"),
                          _arg(shmgan, args, "image_out_size", "source"))
     shmgan.random_flip, shmgan.TARGET_LABELS = 0.0, 1.0                        # test.py:65-67
-    dataset = EvalDataset(test_dir, shmgan.image_size, B, diffuse_dir, shmgan.device)
+    cyclic = not native or len(tags) > 1                                       # native: the cyclic images are only ever exported
+
+    def check(path, h, w):
+        """Before anything is allocated or launched for an image: the derived size limit, then the device memory.  The frame
+        buffers the arena already holds are reused (same frame shape) or dropped (trainer._frame_changed: any other shape, the
+        model-size one included) for this image, so they count as free."""
+        free, _ = torch.cuda.mem_get_info(shmgan.device)
+        held = sum(t.numel() * t.element_size() for k, t in shmgan.arena.t.items()
+                   if isinstance(k[0], str) and k[0].startswith(shmgan._FRAME_BUFFERS))
+        cached = torch.cuda.memory_reserved(shmgan.device) - torch.cuda.memory_allocated(shmgan.device)
+        check_native_limits(path, h, w, shmgan.filter_size, shmgan.compute_dtype, cyclic, shmgan.attention == "live",
+                            free_bytes=free + cached + held)
+
+    if native:
+        dataset = NativeEvalDataset(test_dir, diffuse_dir, shmgan.device, check=check)
+    else:
+        dataset = EvalDataset(test_dir, shmgan.image_size, B, diffuse_dir, shmgan.device)
     if tags:
         check_stems(dataset.test_files)
     shmgan.number_of_test_images = dataset.n                                   # test.py:123
@@ -226,21 +360,22 @@ def test(shmgan, args, *, print_fn=print):
     if tags:
         image_dir = _arg(shmgan, args, "image_dir", "") or os.path.join(shmgan.result_dir, "images")
         exporter = ImageExporter(image_dir, tags, _arg(shmgan, args, "image_values", "rescale"),
-                                 _arg(shmgan, args, "image_out_size", "source"), shmgan.device)
+                                 "native" if native else _arg(shmgan, args, "image_out_size", "source"), shmgan.device)
     index, times, rows = [], [], []
     cols = {k: [] for k in METRIC_KEYS}
     stream = torch.cuda.current_stream()
     try:
-        for bi, (rgb, diffuse) in enumerate(dataset):
+        for bi, item in enumerate(dataset):
+            rgb, diffuse, window = item if native else (*item, None)
             stream.synchronize()                         # the batch's upload and resize are not part of its time
             t0 = time.perf_counter()
-            gen_rgb, cyc, m = shmgan.evaluate(rgb, diffuse)
+            gen_rgb, cyc, m = shmgan.evaluate_frame(rgb, diffuse, window, cyclic) if native else shmgan.evaluate(rgb, diffuse)
             m = None if m is None else m.cpu().tolist()  # a synchronising copy (without metrics: the synchronize below)
             stream.synchronize()
             n = rgb.shape[0]
             dt = (time.perf_counter() - t0) / n
             if exporter is not None:                     # after the timing window: the export is not part of "Time"
-                exporter.submit(shmgan, gen_rgb, cyc, dataset.sources(bi))
+                exporter.submit(shmgan, gen_rgb, cyc, dataset.sources(bi), [window] if native else None)
             lo, _ = dataset.batch_range(bi)
             for b in range(n):
                 index.append(lo + b + 1)

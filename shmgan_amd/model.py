@@ -114,6 +114,15 @@ class Arena:
                 t[-1:].zero_()
         return [name for name, _ in hit]
 
+    def drop(self, *prefixes):
+        """Forget every buffer whose name starts with one of `prefixes` (the memory goes back to torch's allocator); returns the
+        bytes dropped.  The caller makes sure nothing queued still uses them (native-resolution inference synchronises first: it keeps
+        buffers for one frame shape at a time, model.py is otherwise a static plan that never frees)."""
+        before = self.nbytes()
+        for k in [k for k in self.t if isinstance(k[0], str) and k[0].startswith(tuple(prefixes))]:
+            del self.t[k]
+        return before - self.nbytes()
+
     def nbytes(self):
         # a get_slack tensor is a view of its "storage" entry: count the storage
         return sum(t.numel() * t.element_size() for k, t in self.t.items() if not (len(k) == 4 and isinstance(k[3], int)))
@@ -301,17 +310,22 @@ class AttentionBranch:
         for it in self.transpose_items():
             ops.transpose_taps(*it)
 
-    def forward(self, mask, B, S):
-        """mask [B,S,S,1] fp32 -> attention map [B, S/pool, S/pool, C] (activation dtype)."""
+    def forward(self, mask, B, H, W=None):
+        """mask [B,H,W,1] fp32 (W defaults to H: the square training shape) -> attention map [B, H/pool, W/pool, C] (activation
+        dtype).  The backward pass is the training path's and takes the square shape."""
         o, c, A = self.o, self.c, self.o.arena
-        h = S // self.pool
-        m = A.get(f"{self.tag}/m", (B, h, h, o.pad), o.adt)
-        y1 = A.get(f"{self.tag}/y1", (B, h, h, c), o.adt)
-        y2 = A.get(f"{self.tag}/y2", (B, h, h, c), o.adt)
-        ops.mask_pool_pack(mask, m, B, S, self.pool)
-        ops.conv2d_fwd(m, None, 0, o.pad, 0, self.wk1, o.P.vars[self.vi + 1], y1, c, B, h, h, o.pad, c, 3, 1, LRELU, cin_real=1)
-        ops.conv2d_fwd(y1, None, 0, c, 0, self.wk2, o.P.vars[self.vi + 3], y2, c, B, h, h, c, c, 3, 1, LRELU)
-        self.ctx = dict(B=B, h=h, m=m, y1=y1, y2=y2)
+        W = H if W is None else W
+        h, w = H // self.pool, W // self.pool
+        m = A.get(f"{self.tag}/m", (B, h, w, o.pad), o.adt)
+        y1 = A.get(f"{self.tag}/y1", (B, h, w, c), o.adt)
+        y2 = A.get(f"{self.tag}/y2", (B, h, w, c), o.adt)
+        if H == W:
+            ops.mask_pool_pack(mask, m, B, H, self.pool)
+        else:
+            ops.mask_pool_pack_hw(mask, m, B, H, W, self.pool)
+        ops.conv2d_fwd(m, None, 0, o.pad, 0, self.wk1, o.P.vars[self.vi + 1], y1, c, B, h, w, o.pad, c, 3, 1, LRELU, cin_real=1)
+        ops.conv2d_fwd(y1, None, 0, c, 0, self.wk2, o.P.vars[self.vi + 3], y2, c, B, h, w, c, c, 3, 1, LRELU)
+        self.ctx = dict(B=B, h=h, w=w, m=m, y1=y1, y2=y2)
         return y2
 
     def backward(self, dattn):
@@ -319,6 +333,7 @@ class AttentionBranch:
         weight gradients (kernels by the MFMA wgrad, biases through the owner's f64 accumulators)."""
         o, c, A, x = self.o, self.c, self.o.arena, self.ctx
         B, h = x["B"], x["h"]
+        assert x["w"] == h, "the attention backward is the training path's: square maps only"
         dz2 = A.get(f"{self.tag}/dz2", (B, h, h, c), o.adt)
         dz1 = A.get(f"{self.tag}/dz1", (B, h, h, c), o.adt)
         dy1 = A.get(f"{self.tag}/dy1", (B, h, h, c), o.gdt)
@@ -450,10 +465,11 @@ class Generator(_ModelBase):
 
     # -- live attention branch ---------------------------------------------------------------
     def attention_forward(self, mask, B):
-        """attn_1..attn_4 (SHM.py:248,257,266,275) of the step's SpecSeg mask [B,S,S,1]; pass the result to forward(attn=)."""
+        """attn_1..attn_4 (SHM.py:248,257,266,275) of the step's SpecSeg mask [B,H,W,1] ((H, W) = (S, S) in training; any frame of
+        forward() in inference); pass the result to forward(attn=)."""
         self.prepare_weights()
         self._attn_B = B
-        return [br.forward(mask, B, self.S) for br in self.attn]
+        return [br.forward(mask, B, int(mask.shape[1]), int(mask.shape[2])) for br in self.attn]
 
     def attention_masks(self):
         """Sign patterns of the eight attention LeakyReLUs of the last attention_forward (test diagnostics, see lrelu_masks)."""
@@ -470,7 +486,7 @@ class Generator(_ModelBase):
         ops.cvt_f64_f32(self.acc, self.P.grad[self.acc_off:], self.acc_n, 0)
 
     # -- forward --------------------------------------------------------------------------
-    def _fold_plan(self, nb, n, attn):
+    def _fold_plan(self, nb, n, attn, H=None, W=None):
         """{layer index of an InstanceNorm block: True} for the blocks whose normalisation is applied by their consumers: every
         convolution that reads the block's output, and that convolution's weight gradient, must run on a kernel that normalises its
         operand in LDS for this batch (the launcher's variant choice depends on it: ops.conv2d_norm_supported).  Encoder block 1 of a
@@ -478,7 +494,8 @@ class Generator(_ModelBase):
         (its second source); the Concatenate block feeds the decoder level's second block.  That block's own output goes to a
         Conv2DTranspose (or the head, which has normalised on the fly since round 2) and the bottleneck is 1x1: not folded.
         Live attention adds its maps to the normalised skips, which therefore have to exist: nothing is folded."""
-        key = (nb, n, bool(attn), self.fold)            # nb: samples per forward launch (a part of a two-part forward), n: per backward launch
+        H, W = self.S if H is None else H, self.S if W is None else W       # the map the pass runs on: (S, S) in training
+        key = (nb, n, bool(attn), self.fold, H, W)      # nb: samples per forward launch (a part of a two-part forward), n: per backward launch
         plan = self._plans.get(key)
         if plan is not None:
             return plan
@@ -486,20 +503,20 @@ class Generator(_ModelBase):
         if self.fold and not attn:
             dt, L = self.adt, self.layers
 
-            def ok(h, cin, c1, cout, part):
+            def ok(h, w, cin, c1, cout, part):
                 cin_p = _padk(cin, self.pad)
                 if self.fold != "all" and not (dt == torch.float32 and c1 == 0 and cin_p <= 64):
                     return False                               # "auto": only where it is measured to pay
-                return (ops.conv2d_norm_supported(nb, h, h, cin_p, c1, cout, 3, 1, part, dt) and
-                        ops.conv2d_wgrad_norm_supported(n, h, h, cin, cin_p, c1, cout, 3, 1, part, dt))
+                return (ops.conv2d_norm_supported(nb, h, w, cin_p, c1, cout, 3, 1, part, dt) and
+                        ops.conv2d_wgrad_norm_supported(n, h, w, cin, cin_p, c1, cout, 3, 1, part, dt))
             for lvl in range(4):
-                h = self.S >> lvl
+                h, w = H >> lvl, W >> lvl
                 li0, li1 = 2 * lvl, 2 * lvl + 1
-                plan[li0] = ok(h, L[li0][4], 0, L[li1][4], 0)
+                plan[li0] = ok(h, w, L[li0][4], 0, L[li1][4], 0)
                 lic = 11 + 3 * (3 - lvl)                       # the decoder level's Concatenate convolution: sources [u, skip]
                 cu = L[lic - 1][4]
-                plan[li1] = ok(h, L[lic][3], cu, L[lic][4], 1)
-                plan[lic] = ok(h, L[lic][4], 0, L[lic + 1][4], 0)
+                plan[li1] = ok(h, w, L[lic][3], cu, L[lic][4], 1)
+                plan[lic] = ok(h, w, L[lic][4], 0, L[lic + 1][4], 0)
         self._plans[key] = plan
         return plan
 
@@ -553,7 +570,8 @@ class Generator(_ModelBase):
         return ahat, rec
 
     def forward(self, x16, tag, attn=None, parts=1):
-        """x16: [N,S,S,pad] (10 real channels, zero padded to the 64-byte pitch).  Returns gen_Y [N,S,S,1].
+        """x16: [N,H,W,pad] (10 real channels, zero padded to the 64-byte pitch), H and W multiples of 16: (S, S) in training, any
+        frame in inference (the network is fully convolutional; backward() takes the square training shape).  Returns gen_Y [N,H,W,1].
         attn: attention_forward()'s maps ([B,...], N a multiple of B: image i is a copy of sample i % B): added to the four
         skip tensors, `down_k + attn_k` (SHM.py:290-293); the pooled path keeps the un-augmented tensor.
         parts = 2 (experiment, not the trainer's default): the batch is evaluated as two halves, the second one on the second
@@ -562,8 +580,9 @@ class Generator(_ModelBase):
         2 ms of a 121 ms fp32 step are normalisation passes with no MFMA kernel running); the idea was to run one half's
         normalisation pass under the other half's convolution.  Measured: +2 ms -- the halves' convolutions no longer overlap
         and the half-size grids are less efficient than the hidden passes are long."""
-        n, S = x16.shape[0], self.S
-        assert tuple(x16.shape) == (n, S, S, self.pad) and x16.dtype == self.adt
+        n, H, W = (int(v) for v in x16.shape[:3])
+        assert x16.dim() == 4 and x16.shape[3] == self.pad and x16.dtype == self.adt and x16.is_contiguous(), (tuple(x16.shape), x16.dtype)
+        assert H >= 16 and W >= 16 and H % 16 == 0 and W % 16 == 0, f"the generator takes maps whose sides are multiples of 16, got {H} x {W}"
         self.prepare_weights()
         if parts == 2 and self.lane.stream is not None and n >= 4 and (attn is None or (n // 2) % self._attn_B == 0):
             # two half batches, ALTERNATING: a half launches its next convolution only when the other half's previous one has
@@ -598,20 +617,20 @@ class Generator(_ModelBase):
 
     def _forward_rows(self, x16, tag, attn, r0, r1, part, sync):
         """Generator: one step = one convolution of the samples [r0, r1) with the elementwise passes behind it."""
-        n, S, F = x16.shape[0], self.S, self.F
+        n, H, W = (int(v) for v in x16.shape[:3])
         nb = r1 - r0
         A = self.arena
         recs = []
-        plan = self._fold_plan(nb, n, attn is not None)
-        cur, cur_nt, ld, h = x16, None, self.pad, S      # cur_nt: cur is the un-normalised output of a folded block, with this table
+        plan = self._fold_plan(nb, n, attn is not None, H, W)
+        cur, cur_nt, ld, h, w = x16, None, self.pad, H, W      # cur_nt: cur is the un-normalised output of a folded block, with this table
         li = bi = 0
         downs = []
         for lvl in range(4):
             pooled = None
             for j in range(2):
                 if j == 1:            # the level's second block: its normalisation pass also writes the pooled tensor
-                    pooled = A.get(f"{tag}/p{lvl}", (n, h // 2, h // 2, self.layers[li][4]), self.adt)
-                cur, r = self._cnl_fwd(tag, li, bi, cur, None, 0, ld, 0, n, h, h, r0, r1, part, pooled=pooled, sync=sync, ntx=cur_nt,
+                    pooled = A.get(f"{tag}/p{lvl}", (n, h // 2, w // 2, self.layers[li][4]), self.adt)
+                cur, r = self._cnl_fwd(tag, li, bi, cur, None, 0, ld, 0, n, h, w, r0, r1, part, pooled=pooled, sync=sync, ntx=cur_nt,
                                        fold=plan.get(li, False))
                 cur_nt = r["nt"]
                 r["pooled"] = pooled
@@ -621,14 +640,14 @@ class Generator(_ModelBase):
                 li += 1
                 bi += 1
             if attn is not None:
-                skip = A.get(f"{tag}/skip{lvl}", (n, h, h, ld), self.adt)
-                ops.add_bcast(cur[r0:r1], attn[lvl], skip[r0:r1], nb, h * h * ld, self._attn_B, r0)
+                skip = A.get(f"{tag}/skip{lvl}", (n, h, w, ld), self.adt)
+                ops.add_bcast(cur[r0:r1], attn[lvl], skip[r0:r1], nb, h * w * ld, self._attn_B, r0)
                 downs.append((skip, ld, h, None))
             else:
                 downs.append((cur, ld, h, cur_nt))
-            cur, cur_nt, h = pooled, None, h // 2
+            cur, cur_nt, h, w = pooled, None, h // 2, w // 2
         for _ in range(2):                       # the two 1x1 blocks
-            cur, r = self._cnl_fwd(tag, li, bi, cur, None, 0, ld, 0, n, h, h, r0, r1, part, sync=sync)
+            cur, r = self._cnl_fwd(tag, li, bi, cur, None, 0, ld, 0, n, h, w, r0, r1, part, sync=sync)
             recs.append(r)
             li += 1
             bi += 1
@@ -636,20 +655,20 @@ class Generator(_ModelBase):
         ups = []
         for lvl in range(4):
             _, _, _, cin, cout = self.layers[li]
-            u = A.get(f"{tag}/u{lvl}", (n, 2 * h, 2 * h, cout), self.adt)
+            u = A.get(f"{tag}/u{lvl}", (n, 2 * h, 2 * w, cout), self.adt)
             if sync is not None:
                 sync.before(part)
-            ops.conv2d_transpose_fwd(cur[r0:r1], ld, self.P.op_vars[2 * li], self.P.vars[2 * li + 1], u[r0:r1], cout, nb, h, h, cin,
+            ops.conv2d_transpose_fwd(cur[r0:r1], ld, self.P.op_vars[2 * li], self.P.vars[2 * li + 1], u[r0:r1], cout, nb, h, w, cin,
                                      cout, LRELU)
             if sync is not None:
                 sync.after(part)
             yield
             ups.append(dict(li=li, x=cur, ldx=ld, u=u, h=h))
             li += 1
-            h *= 2
+            h, w = 2 * h, 2 * w
             skip, sld, sh, skip_nt = downs[3 - lvl]
             assert sh == h
-            cur, r = self._cnl_fwd(tag, li, bi, u, skip, cout, cout, sld, n, h, h, r0, r1, part, sync=sync, ntx2=skip_nt,
+            cur, r = self._cnl_fwd(tag, li, bi, u, skip, cout, cout, sld, n, h, w, r0, r1, part, sync=sync, ntx2=skip_nt,
                                    fold=plan.get(li, False))                                                  # concat [u, skip]
             cur_nt = r["nt"]
             recs.append(r)
@@ -658,14 +677,14 @@ class Generator(_ModelBase):
             bi += 1
             yield
             # the last block's InstanceNorm is applied by the head kernels (forward and backward) on the fly
-            cur, r = self._cnl_fwd(tag, li, bi, cur, None, 0, ld, 0, n, h, h, r0, r1, part, apply=lvl < 3, sync=sync, ntx=cur_nt)
+            cur, r = self._cnl_fwd(tag, li, bi, cur, None, 0, ld, 0, n, h, w, r0, r1, part, apply=lvl < 3, sync=sync, ntx=cur_nt)
             recs.append(r)
             li += 1
             bi += 1
             yield
-        y = A.get(f"{tag}/y", (n, S, S, 1))
+        y = A.get(f"{tag}/y", (n, H, W, 1))
         ops.head_in_fwd(cur[r0:r1], ld, r["stats"][r0 * ld * 2:r1 * ld * 2], self.betas[r["bi"]], self.P.vars[2 * li], self.P.vars[2 * li + 1], y[r0:r1],
-                        nb, S * S, ld, LRELU)
+                        nb, H * W, ld, LRELU)
         if part == 0:                 # the records describe full-batch tensors: identical whichever part builds them
             self.ctx[tag] = dict(n=n, recs=recs, ups=ups, head_x=cur, head_rec=r, y=y, x16=x16, attn=attn is not None)
         return y
@@ -753,6 +772,7 @@ class Generator(_ModelBase):
         n, recs, ups = c["n"], c["recs"], c["ups"]
         A = self.arena
         S, F = self.S, self.F
+        assert tuple(c["y"].shape[1:3]) == (S, S), f"backward takes the square training shape {S} x {S}, the forward ran on {tuple(c['y'].shape[1:3])}"
         nl = len(self.layers)
         self._on_wgrad = on_wgrad
         try:

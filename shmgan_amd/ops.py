@@ -572,6 +572,35 @@ def image_metrics(pred, target, out=None, arena=None):
     return out
 
 
+def image_metrics_hw_workspace(batch, h, w):
+    return int(lib().shm_image_metrics_hw_workspace(batch, h, w))
+
+
+def image_metrics_hw(pred, window, target, out=None, arena=None):
+    """image_metrics on a window of a padded prediction (shm_image_metrics_hw): pred float32 [B,Hp,Wp,3], window = (top, left, h, w)
+    the photo inside the frame, target tight float32 [B,h,w,3].  Same result tensor, workspace rule and ordering as image_metrics."""
+    top, left, h, w = (int(v) for v in window)
+    if pred.dtype != torch.float32 or target.dtype != torch.float32:
+        raise TypeError(f"image_metrics_hw takes float32 images, got {pred.dtype} / {target.dtype}")
+    if pred.dim() != 4 or pred.shape[-1] != 3 or tuple(target.shape) != (pred.shape[0], h, w, 3):
+        raise ValueError(f"image_metrics_hw takes pred [B,Hp,Wp,3] and target [B,{h},{w},3], got {tuple(pred.shape)} / {tuple(target.shape)}")
+    if not (pred.is_contiguous() and target.is_contiguous()):
+        raise ValueError("image_metrics_hw takes contiguous NHWC images")
+    B, hp, wp = int(pred.shape[0]), int(pred.shape[1]), int(pred.shape[2])
+    if out is None:
+        out = torch.empty((B, 5), dtype=torch.float64, device=pred.device)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (B, 5) or not out.is_contiguous():
+        raise ValueError(f"image_metrics_hw: out must be a contiguous float64 [{B},5] tensor")
+    if arena is None:
+        from .model import Arena
+        arena = _METRIC_ARENAS.setdefault(pred.device, Arena(pred.device))
+    n = image_metrics_hw_workspace(B, h, w)
+    ws = arena.get("metrics/ws", (max(n, 1),), torch.uint8)
+    check(lib().shm_image_metrics_hw(_p(pred), hp, wp, top, left, _p(target), h, w, _p(out), _p(ws), ws.numel(), B, _stream()),
+          "shm_image_metrics_hw")
+    return out
+
+
 # ---- training telemetry (shm_tensor_stats / shm_loss_ring_put, include/shmgan_hip.h) ---------------------------------------
 TSTAT_NAMES = ["finite", "nan", "inf", "min", "max", "sum", "sumsq", "clipped"]     # SHM_TSTAT_* order
 TSTAT_N, THIST_BINS, THIST_EMIN, TSTAT_MAX_SEGS = 8, 44, -40, 128                   # SHM_TSTAT_N, SHM_THIST_BINS, SHM_THIST_EMIN, SHM_TSTAT_MAX_SEGS
@@ -706,6 +735,63 @@ def export_u8(planes, sizes, modes, mul=None, out=None, arena=None):
     return out, offs
 
 
+EXPORT_HW_DESC = 13                                       # SHM_EXPORT_HW_DESC
+
+
+def export_u8_hw(planes, windows, sizes, modes, mul=None, out=None, arena=None):
+    """export_u8 with rectangular planes and a source window per plane (shm_export_u8_hw): planes [Hs,Ws,C] float32 device tensors
+    (C in {1,3}, pixel pitch ld >= C), windows (y0, x0, hc, wc) per plane -- the part that is exported: RESCALE takes its min / max
+    there and the resampling maps it to the plane's (ho, wo) of `sizes`.  modes, mul, out, arena, the output layout (export_layout)
+    and the return value are export_u8's."""
+    import ctypes as C
+    n = len(planes)
+    if n == 0 or len(sizes) != n or len(modes) != n or len(windows) != n:
+        raise ValueError(f"export_u8_hw: {n} planes, {len(windows)} windows, {len(sizes)} sizes, {len(modes)} modes")
+    desc, chans = [], []
+    for p, win, (ho, wo), m in zip(planes, windows, sizes, modes):
+        if p.dtype != torch.float32 or not p.is_cuda:
+            raise TypeError(f"export_u8_hw takes float32 device planes, got {p.dtype} on {p.device}")
+        if p.dim() != 3 or p.shape[2] not in (1, 3):
+            raise ValueError(f"export_u8_hw takes [Hs,Ws,C] planes with C in {{1,3}}, got {tuple(p.shape)}")
+        hs, ws_, c = int(p.shape[0]), int(p.shape[1]), int(p.shape[2])
+        ld = int(p.stride(1))
+        if p.stride(2) != 1 or ld < c or p.stride(0) != ws_ * ld:
+            raise ValueError(f"export_u8_hw: plane strides {p.stride()} are not [Ws*ld, ld, 1] with ld >= {c}")
+        if isinstance(m, tuple) and len(m) == 2 and m[0] == "scale":
+            mode, k = EXPORT_MODES["scale"], int(m[1])
+            if mul is None or mul.dtype != torch.float32 or mul.dim() != 1 or not 0 <= k < mul.numel() or not mul.is_contiguous():
+                raise ValueError(f"export_u8_hw: mode {m} needs a contiguous float32 mul with more than {k} elements")
+        elif m in ("rescale", "clip"):
+            mode, k = EXPORT_MODES[m], 0
+        else:
+            raise ValueError(f"export_u8_hw: mode {m!r} is not 'rescale', 'clip' or ('scale', k)")
+        y0, x0, hc, wc = (int(v) for v in win)
+        if min(y0, x0) < 0 or min(hc, wc) < 1 or y0 + hc > hs or x0 + wc > ws_:
+            raise ValueError(f"export_u8_hw: window {tuple(win)} outside the {hs} x {ws_} plane")
+        desc.append([hs, ws_, c, ld, y0, x0, hc, wc, int(ho), int(wo), mode, k, 0])
+        chans.append(c)
+    offs, total = export_layout(sizes, chans)
+    dev = planes[0].device
+    if out is None:
+        out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.numel() < total:
+        raise ValueError(f"export_u8_hw: out must be a contiguous flat uint8 tensor of at least {total} bytes")
+    if arena is None:
+        from .model import Arena
+        arena = _METRIC_ARENAS.setdefault(dev, Arena(dev))
+    need = export_workspace(EXPORT_MAX_JOBS)
+    ws = arena.get("export/ws", (need,), torch.uint8)
+    for d, o in zip(desc, offs):
+        d[12] = o
+    for j0 in range(0, n, EXPORT_MAX_JOBS):
+        part = range(j0, min(n, j0 + EXPORT_MAX_JOBS))
+        src = (C.c_void_p * len(part))(*[planes[j].data_ptr() for j in part])
+        dsc = (C.c_size_t * (EXPORT_HW_DESC * len(part)))(*[v for j in part for v in desc[j]])
+        check(lib().shm_export_u8_hw(src, dsc, len(part), _p(mul), 0 if mul is None else mul.numel(), _p(out), out.numel(),
+                                     _p(ws), need, _stream()), "shm_export_u8_hw")
+    return out, offs
+
+
 def running_scale_mean(scale, acc, mul):
     """The reference's running mean of the standardisation scales (test.py:77, 218, 246; shm_running_scale_mean): for the
     batch's scale [B] (float32, what preprocess returns) in image order, acc (float64 [2] device {sum, count}, zero at the
@@ -760,6 +846,11 @@ def mask_pool_pack(mask, dst, batch, s, k):
     check(lib().shm_mask_pool_pack(_p(mask), _p(dst), dst.shape[-1], batch, s, k, _dt(dst), _stream()), "shm_mask_pool_pack")
 
 
+def mask_pool_pack_hw(mask, dst, batch, h, w, k):
+    """mask_pool_pack on a rectangular mask [batch,h,w,1] -> dst [batch,h/k,w/k,ld]."""
+    check(lib().shm_mask_pool_pack_hw(_p(mask), _p(dst), dst.shape[-1], batch, h, w, k, _dt(dst), _stream()), "shm_mask_pool_pack_hw")
+
+
 def add_bcast(a, b, out, nimg, per, nb, i0=0):
     check(lib().shm_add_bcast(_p(a), _p(b), _p(out), nimg, per, nb, i0, _dt(a), _stream()), "shm_add_bcast")
 
@@ -775,6 +866,17 @@ def resize_bilinear_u8(src_u8, dst, scale=1.0 / 255.0, flip_ud=False):
     ho, wo, _ = dst.shape
     check(lib().shm_resize_bilinear_u8(_p(src_u8), hin, win, c, _p(dst), ho, wo, scale, int(flip_ud), _stream()),
           "shm_resize_bilinear_u8")
+
+
+def load_pad_u8(src_u8, dst, top, left, scale=1.0 / 255.0):
+    """src_u8 [h,w,c] uint8 device tensor -> dst [hp,wp,c] float32: the image at (top, left), times scale, the border filled by
+    reflection without the edge sample (shm_load_pad_u8; NumPy's mode="reflect")."""
+    h, w, c = src_u8.shape
+    hp, wp, c2 = dst.shape
+    if src_u8.dtype != torch.uint8 or dst.dtype != torch.float32 or c2 != c or not (src_u8.is_contiguous() and dst.is_contiguous()):
+        raise ValueError(f"load_pad_u8 takes contiguous uint8 [h,w,c] and float32 [hp,wp,c], got {src_u8.dtype} {tuple(src_u8.shape)} / "
+                         f"{dst.dtype} {tuple(dst.shape)}")
+    check(lib().shm_load_pad_u8(_p(src_u8), h, w, c, _p(dst), hp, wp, int(top), int(left), scale, _stream()), "shm_load_pad_u8")
 
 
 # ---- polarimetry: estimated-diffuse target and Stokes maps ----------------------------------------

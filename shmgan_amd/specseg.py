@@ -119,50 +119,53 @@ class SpecSeg:
         self.weights_dirty = False
 
     # ---- forward ------------------------------------------------------------------------
-    def _conv(self, tag, i, x, x2, c1, ldx, ldx2, n, h):
+    def _conv(self, tag, i, x, x2, c1, ldx, ldx2, n, h, w):
         k, _, cin, cout = self.spec[i][2]
-        y = self.arena.get(f"{tag}/c{i}", (n, h, h, cout))
-        ops.conv2d_fwd(x, x2, c1, ldx, ldx2, self.wk[i], self.vars[i + 1], y, cout, n, h, h, _pad16(cin), cout, k, 1, 0.0,
+        y = self.arena.get(f"{tag}/c{i}", (n, h, w, cout))
+        ops.conv2d_fwd(x, x2, c1, ldx, ldx2, self.wk[i], self.vars[i + 1], y, cout, n, h, w, _pad16(cin), cout, k, 1, 0.0,
                        cin_real=cin)
         return y
 
     def forward_plane(self, src, ldsrc, c0, n, tag="specseg"):
-        """Mask of channel c0 of `src` ([n,S,S,ldsrc]); returns [n,S,S,1] in (0,1)."""
-        S, A = self.S, self.arena
+        """Mask of channel c0 of `src` ([n,H,W,ldsrc], H and W multiples of 16: the network is fully convolutional, (S, S) in
+        training); returns [n,H,W,1] in (0,1)."""
+        A = self.arena
+        H, W = int(src.shape[1]), int(src.shape[2])
+        assert src.dim() == 4 and H >= 16 and W >= 16 and H % 16 == 0 and W % 16 == 0, f"SpecSeg takes maps whose sides are multiples of 16, got {tuple(src.shape)}"
         self.prepare_weights()
-        x16 = A.get(f"{tag}/x16", (n, S, S, PAD_C))
-        ops.pack_channels(src, ldsrc, c0, 1, x16, PAD_C, n * S * S)
-        cur, ld, h = x16, PAD_C, S
+        x16 = A.get(f"{tag}/x16", (n, H, W, PAD_C))
+        ops.pack_channels(src, ldsrc, c0, 1, x16, PAD_C, n * H * W)
+        cur, ld, h, wd = x16, PAD_C, H, W
         i = 0
         skips = []
         for l, w in enumerate(WIDTHS):
-            a = self._conv(tag, i, cur, None, 0, ld, 0, n, h)
-            b = self._conv(tag, i + 2, a, None, 0, w, 0, n, h)
-            c = A.get(f"{tag}/bn{l}", (n, h, h, w))
+            a = self._conv(tag, i, cur, None, 0, ld, 0, n, h, wd)
+            b = self._conv(tag, i + 2, a, None, 0, w, 0, n, h, wd)
+            c = A.get(f"{tag}/bn{l}", (n, h, wd, w))
             g, be, mu, var = self.vars[i + 4:i + 8]
-            ops.bn_apply(b, w, g, be, mu, var, BN_EPS, c, w, n * h * h, w)
+            ops.bn_apply(b, w, g, be, mu, var, BN_EPS, c, w, n * h * wd, w)
             i += 8
             if l < 4:
                 skips.append((c, w, h))
-                p = A.get(f"{tag}/p{l}", (n, h // 2, h // 2, w))
-                ops.maxpool2_fwd(c, w, p, w, n, h, h, w)
-                cur, ld, h = p, w, h // 2
+                p = A.get(f"{tag}/p{l}", (n, h // 2, wd // 2, w))
+                ops.maxpool2_fwd(c, w, p, w, n, h, wd, w)
+                cur, ld, h, wd = p, w, h // 2, wd // 2
             else:
                 cur, ld = c, w
         for l in (3, 2, 1, 0):
             w = WIDTHS[l]
-            u = A.get(f"{tag}/u{l}", (n, 2 * h, 2 * h, w))
-            ops.conv2d_transpose2x2_fwd(cur, ld, self.vars[i], self.vars[i + 1], u, w, n, h, h, 2 * w, w, 1.0)
+            u = A.get(f"{tag}/u{l}", (n, 2 * h, 2 * wd, w))
+            ops.conv2d_transpose2x2_fwd(cur, ld, self.vars[i], self.vars[i + 1], u, w, n, h, wd, 2 * w, w, 1.0)
             i += 2
-            h *= 2
+            h, wd = 2 * h, 2 * wd
             skip, sw, sh = skips[l]
             assert sh == h and sw == w
-            a = self._conv(tag, i, u, skip, w, w, w, n, h)            # Concatenate([up, skip])
-            b = self._conv(tag, i + 2, a, None, 0, w, 0, n, h)
+            a = self._conv(tag, i, u, skip, w, w, w, n, h, wd)        # Concatenate([up, skip])
+            b = self._conv(tag, i + 2, a, None, 0, w, 0, n, h, wd)
             i += 4
             cur, ld = b, w
-        y = A.get(f"{tag}/mask", (n, S, S, 1))
-        ops.head_sigmoid_fwd(cur, ld, self.vars[i], self.vars[i + 1], y, n * S * S, ld)
+        y = A.get(f"{tag}/mask", (n, H, W, 1))
+        ops.head_sigmoid_fwd(cur, ld, self.vars[i], self.vars[i + 1], y, n * H * W, ld)
         return y
 
     def predict(self, x, verbose=0):

@@ -53,7 +53,7 @@ _DEFAULTS = dict(image_size=128, batch_size=1, filter_size=64, g_lr=0.00002, d_l
                  c_dim=5, num_epochs=200, num_iteration_decay=100000, n_critic=5, d_repeat_num=6, mode="train",
                  data_dir="", model_save_dir="./models", checkpoint_save_dir="./checkpoints", result_dir="./results",
                  log_dir="./logs/train", log_step=1, checkpoint_save_step=10, calc_metrics=False, test_dir="", diffuse_dir="",
-                 save_images=False, image_values="rescale", image_out_size="source", image_dir="",
+                 save_images=False, image_values="rescale", image_out_size="source", image_dir="", eval_size="model",
                  loss_log_step=0, histogram_step=0, nonfinite=None, diffuse_source="dir")
 
 
@@ -283,6 +283,11 @@ class ShmGANwithSSpecSeg:
         """Build G, D and SpecSeg and give G/D the synthetic init of SURVEY 8(d): weights N(0,0.02) from
         default_rng(seed) (RandomNormal(0,0.02), SHM.py:200), biases 0, IN beta N(0,0.02); the live attention branch's
         kernels N(0,0.02) from default_rng(attention_seed), generator levels first, then the discriminator's."""
+        # A trainer is a web of reference cycles (closures over it, records of full-batch tensors), so a dropped trainer keeps its device
+        # buffers until Python's cycle collector happens to run.  A process that builds one trainer after another (bench.py's extra
+        # configurations, a test session) can pile up hundreds of GiB of dead arenas that way: collect before allocating the next one.
+        import gc
+        gc.collect()
         self.G = self.build_generator()
         self.D = self.build_discriminator()
         if self.SpecSeg is None:
@@ -324,11 +329,11 @@ class ShmGANwithSSpecSeg:
 
     def preprocess(self, rgb, name):
         """tf.image.rgb_to_yuv + custom_per_image_standardization (SHM.py:480-484, 1271-1309)."""
-        B, S = rgb.shape[0], self.image_size
-        yuv = self.arena.get(f"pre/yuv/{name}", (B, S, S, 3))
+        B, H, W = (int(v) for v in rgb.shape[:3])            # the frame is the input's: (S, S) in training, any frame in inference
+        yuv = self.arena.get(f"pre/yuv/{name}", (B, H, W, 3))
         acc = self.arena.get(f"pre/acc/{name}", (B * 2,), torch.float64)
         scale = self.arena.get(f"pre/scale/{name}", (B,))
-        ops.rgb2yuv_std(rgb, yuv, acc, scale, B, S * S)
+        ops.rgb2yuv_std(rgb, yuv, acc, scale, B, H * W)
         return yuv, scale
 
     def _prologue(self, orig, slot):
@@ -823,18 +828,50 @@ class ShmGANwithSSpecSeg:
         return path
 
     # ------------------------------------------------------------------ inference (test.py:218-297)
-    def infer(self, rgb):
+    # arena names that hold one frame's worth of inference buffers (dropped when the frame shape changes, _frame_changed)
+    # (of the live attention branch only the forward's mask / y1 / y2: its backward buffers belong to training)
+    _FRAME_BUFFERS = ("inf", "specseg/inf", "pre/yuv/inf", "metrics/ws") + tuple(f"g/attn{lvl}/{n}" for lvl in range(4) for n in ("m", "y1", "y2"))
+
+    def _frame_changed(self, H, W):
+        """Inference keeps buffers for ONE frame shape: when (H, W) differs from the frame of the last infer() (square or not),
+        that frame's buffers leave the arena -- after a device synchronise, because queued kernels may still read them: the
+        metrics, and the image exporter's launch over the planes it was handed (evaluate.ImageExporter reads them on this
+        stream into a buffer of its own, so nothing outlives the synchronise).  A run that stays at image_size x image_size
+        never gets here with a changed shape: its buffers are allocated once, as before."""
+        last = getattr(self, "_inf_frame", None)
+        if last is not None and last != (H, W):
+            torch.cuda.synchronize(self.device)
+            for br in self.G.attn:                 # the branches' records hold the old frame's maps
+                br.ctx = None
+            self.gen_input = self.gen_Y = self.gen_rgb = self.specular_candidate = None
+            self.cyc_gen0_rgb = self.cyc_gen45_rgb = self.cyc_gen90_rgb = self.cyc_gen135_rgb = self.cyc_genED_rgb = None
+            self.G.ctx.pop("inf1", None)
+            self.G.ctx.pop("inf5", None)
+            self.arena.drop(*self._FRAME_BUFFERS)
+        self._inf_frame = (H, W)
+
+    def infer(self, rgb, cyclic=True):
         """Forward-only path of the reference's evaluation script (/root/reference/test.py:218-297):
         standardised YUV of ONE rgb image -> G once with only view 0 populated (target ED) -> the
-        generated RGB, whose channel 0 feeds five cyclic G calls.  rgb [B,S,S,3] in [0,1].
-        Returns (gen_rgb [B,S,S,3], [5 x cyc_rgb [B,S,S,3]]); sets the same attributes as test.py."""
+        generated RGB, whose channel 0 feeds five cyclic G calls.  rgb [B,H,W,3] in [0,1], H and W multiples of 16 and at least 32
+        (the networks are fully convolutional): (H, W) = (image_size, image_size) is the reference's shape and runs the five cyclic
+        passes as one batch of 5 B; any other frame runs them one after the other through one set of buffers (samples are
+        independent under InstanceNorm: the same arithmetic per sample, a sixth of the activation memory) and keeps arena buffers
+        for that one frame shape (_frame_changed).  cyclic=False stops after G1: the cyclic images are then None.
+        Returns (gen_rgb [B,H,W,3], [5 x cyc_rgb [B,H,W,3]]); sets the same attributes as test.py."""
         if self.G is None:
             self.build()
         G, A = self.G, self.arena
         S = self.image_size
         x = self._dev(rgb)
-        B = x.shape[0]
-        npix = S * S
+        if x.dim() != 4 or x.shape[3] != 3:
+            raise ValueError(f"infer takes [B,H,W,3] images, got {tuple(x.shape)}")
+        B, H, W = (int(v) for v in x.shape[:3])
+        if min(H, W) < 32 or H % 16 or W % 16:
+            raise ValueError(f"infer takes frames whose sides are multiples of 16 and at least 32, got {H} x {W}")
+        square = (H, W) == (S, S)
+        self._frame_changed(H, W)
+        npix = H * W
         G.prepare_weights()
         yuv, scale = self.preprocess(x, "inf")
         if self.SpecSeg is None:
@@ -843,37 +880,70 @@ class ShmGANwithSSpecSeg:
         cbcr = yuv[..., 1:].contiguous()                       # averageCbCr = the input's own CbCr (test.py:224)
         ys = [yuv] * 5
         adt, PAD_C = self.compute_dtype, self.pad
-        gen_in = A.get("inf/in", (B, S, S, PAD_C), adt)
+        gen_in = A.get("inf/in", (B, H, W, PAD_C), adt)
         ops.build_gen_input(ys, None, 0b11110, 0, gen_in, B, npix)          # views 1..4 zero, one-hot = ED
         attn = G.attention_forward(self.specular_candidate, B) if self.attention == "live" else None
         gen_Y = G.forward(gen_in, "inf1", attn=attn)
-        gen_rgb = A.get("inf/rgb", (B, S, S, 3))
+        gen_rgb = A.get("inf/rgb", (B, H, W, 3))
         ops.yuv2rgb(gen_Y, cbcr, None, gen_rgb, None, B, B, npix)
-        orig_Ych = gen_rgb[..., 0:1].contiguous()              # test.py:252
-        cyc_in = A.get("inf/cyc_in", (5 * B, S, S, PAD_C), adt)
-        ops.build_gen_input(ys, orig_Ych, 0b11111, 1, cyc_in, B, npix)      # view k zero, the others = orig_Ych
-        cyc_Y = G.forward(cyc_in, "inf5", attn=attn, parts=self.forward_parts)
-        cyc_rgb = A.get("inf/cyc_rgb", (5 * B, S, S, 3))
-        ops.yuv2rgb(cyc_Y, cbcr, None, cyc_rgb, None, 5 * B, B, npix)
+        outs = [None] * 5
+        if cyclic:
+            orig_Ych = gen_rgb[..., 0:1].contiguous()              # test.py:252
+            cyc_in = A.get("inf/cyc_in", (5 * B, H, W, PAD_C), adt)
+            ops.build_gen_input(ys, orig_Ych, 0b11111, 1, cyc_in, B, npix)      # view k zero, the others = orig_Ych
+            cyc_rgb = A.get("inf/cyc_rgb", (5 * B, H, W, 3))
+            if square:
+                cyc_Y = G.forward(cyc_in, "inf5", attn=attn, parts=self.forward_parts)
+                ops.yuv2rgb(cyc_Y, cbcr, None, cyc_rgb, None, 5 * B, B, npix)
+            else:
+                # one pass at a time through the buffers of "inf1", its output plane included: G1's Y moves to a buffer of its own
+                gen_Y = A.get("inf/gen_y", (B, H, W, 1)).copy_(gen_Y)
+                for k in range(5):
+                    cyc_Y = G.forward(cyc_in[k * B:(k + 1) * B], "inf1", attn=attn)
+                    ops.yuv2rgb(cyc_Y, cbcr, None, cyc_rgb[k * B:(k + 1) * B], None, B, B, npix)
+                G.ctx.pop("inf1", None)                        # it would describe the last cyclic pass, not G1
+            outs = [cyc_rgb[k * B:(k + 1) * B] for k in range(5)]
         self.gen_input, self.gen_Y, self.gen_rgb = gen_in, gen_Y, gen_rgb
         self.stddev_arr = [scale]
-        outs = [cyc_rgb[k * B:(k + 1) * B] for k in range(5)]
         (self.cyc_gen0_rgb, self.cyc_gen45_rgb, self.cyc_gen90_rgb, self.cyc_gen135_rgb, self.cyc_genED_rgb) = outs
         return gen_rgb, outs
 
     def evaluate(self, rgb, diffuse=None):
         """One batch of the reference's test mode (test.py:218-392): `infer(rgb)` and, when the diffuse targets are given
-        ([B,S,S,3] in [0,1]), their image-quality metrics against gen_rgb (ops.image_metrics, on the library's kernels).
+        ([B,H,W,3] in [0,1], the shape of rgb), their image-quality metrics against gen_rgb (ops.image_metrics, on the library's
+        kernels; a frame other than a square one is scored whole by ops.image_metrics_hw).  `evaluate_frame` is the same with a
+        window and without the cyclic passes.
         Returns (gen_rgb, [5 x cyc_rgb], metrics): metrics is a float64 [B,5] device tensor {mse, psnr, ssim, de76, de94} per
         image (ops.METRIC_NAMES), or None.  Asynchronous like infer; gen_rgb and the metrics live until the next call."""
-        gen_rgb, cyc = self.infer(rgb)
+        return self.evaluate_frame(rgb, diffuse)
+
+    def evaluate_frame(self, rgb, diffuse=None, window=None, cyclic=True):
+        """`evaluate` for the native-resolution test mode: `infer(rgb, cyclic)` and, when the diffuse targets are given
+        (in [0,1]), their image-quality metrics against gen_rgb (on the library's kernels).  window = (top, left, h, w): the part
+        of the frame that is the photo (native-resolution test mode pads a photo to multiples of 16, data.pad_geometry); the
+        targets are then tight [B,h,w,3] and the metrics are taken on the window only (ops.image_metrics_hw).  Without a window
+        the targets have the frame's shape (ops.image_metrics on a square frame).
+        Returns (gen_rgb, [5 x cyc_rgb], metrics): metrics is a float64 [B,5] device tensor {mse, psnr, ssim, de76, de94} per
+        image (ops.METRIC_NAMES), or None.  Asynchronous like infer; gen_rgb and the metrics live until the next call."""
+        gen_rgb, cyc = self.infer(rgb, cyclic)
+        B, H, W = (int(v) for v in gen_rgb.shape[:3])
+        if window is not None:
+            top, left, h, w = (int(v) for v in window)
+            if min(top, left) < 0 or min(h, w) < 1 or top + h > H or left + w > W:
+                raise ValueError(f"window {tuple(window)} does not lie inside the {H} x {W} frame")
         metrics = None
         if diffuse is not None:
             t = self._dev(diffuse)
-            if tuple(t.shape) != tuple(gen_rgb.shape):
-                raise ValueError(f"diffuse images {tuple(t.shape)} do not match the generated ones {tuple(gen_rgb.shape)}")
-            B = gen_rgb.shape[0]
-            metrics = ops.image_metrics(gen_rgb, t, out=self.arena.get("eval/metrics", (B, 5), torch.float64), arena=self.arena)
+            out = self.arena.get("eval/metrics", (B, 5), torch.float64)
+            if window is None and H == W:
+                if tuple(t.shape) != tuple(gen_rgb.shape):
+                    raise ValueError(f"diffuse images {tuple(t.shape)} do not match the generated ones {tuple(gen_rgb.shape)}")
+                metrics = ops.image_metrics(gen_rgb, t, out=out, arena=self.arena)
+            else:
+                win = (0, 0, H, W) if window is None else (top, left, h, w)
+                if tuple(t.shape) != (B, win[2], win[3], 3):
+                    raise ValueError(f"diffuse images {tuple(t.shape)} do not match the window {win[2]} x {win[3]} of the generated ones")
+                metrics = ops.image_metrics_hw(gen_rgb, win, t, out=out, arena=self.arena)
         return gen_rgb, cyc, metrics
 
     # ------------------------------------------------------------------ weights interchange (SURVEY N3)

@@ -86,14 +86,15 @@ const char* shm_last_kernel(void);
  *                               3 at unit stride only, 4 both
  *   "stats.fusion"              1 InstanceNorm statistics in the conv epilogue (default), 0 separate pass
  *   "elem.fused_max_slices"     the one-pass form: most slices (= blocks that must be resident together) per barrier group, default 256, at most 512; the launcher also
- *                               requires twice the group's blocks to fit the device (shm_set_abort_words below)
+ *                               requires twice the group's blocks to fit the device (the one-pass form of shm_in_bwd below)
  *   "elem.fused_hold"           the one-pass form's kernel: 0 automatic (in_bwd_fusedg_kernel -- the gradient held in registers, the activation streamed
  *                               twice, slices of 32768 / min(c, 64) pixels, up to 2 x "elem.fused_max_slices" blocks per group -- on maps of at least
  *                               256 x 16384 / min(c, 64) pixels without a pooled gradient, where it is measured faster; in_bwd_fused8_kernel otherwise),
  *                               1 in_bwd_fused8_kernel only, 2 in_bwd_fusedg_kernel wherever the map has whole slices
  *   "elem.fused_gvariant"       in_bwd_fusedg_kernel's register-budget form: 0 <2, 2, 4> (four blocks per CU; default), 1 <8, 8, 3>
  *   "elem.fused_test_stall"     tests only: 1 = the one-pass form's barriers wait for one block more than the grid has, i.e. every barrier
- *                               times out (~1 s per resident generation of blocks) and the abort words are set; default 0
+ *                               times out (this form gives up after 2^10 polls, ~1 ms per resident generation of blocks, where a real launch waits
+ *                               ~1 s) and the abort words given to the call are set; default 0
  *   "elem.reverse"              1 InstanceNorm apply / backward-reduce passes walk the tensor back to front (default: the tail the
  *                               producer just wrote is still in the Infinity Cache), 0 front to back
  *   "elem.reduce_blocks"        block target of the InstanceNorm-backward reduce pass, 0 automatic (1024 fp32 / 512 bf16: every block ends
@@ -274,12 +275,14 @@ int shm_conv2d_wgrad_norm_finish(float* dw, const float* nt, const double* dzsum
 /* The one-pass form's barrier needs every block of a group resident at once.  The launcher takes it only when TWICE the group's blocks fit the
  * current device (its CU count x hipOccupancyMaxActiveBlocksPerMultiprocessor of the kernel, queried once: a partitioned or smaller part falls
  * back to the two passes), and a barrier that still waits ~1 s gives up instead of hanging: the launch then completes with wrong means, sets the
- * last u32 of `fused_scratch` and the caller's ABORT WORDS:
- *   dev_word   u32 in device memory, OR-ed to non-zero.  shm_adam_clip reads it ON THE DEVICE and applies nothing while it is set: gradients
- *              built on unfinished sums never reach the weights, however far the host has run ahead of the stream;
- *   host_word  u32 in mapped (pinned) host memory, set to 1: the host sees it without synchronising.
- * Both stay set until the caller clears them; NULLs disarm.  Persistent per calling thread (configuration, like the tuning table). */
-int shm_set_abort_words(unsigned* dev_word, unsigned* host_word);
+ * last u32 of `fused_scratch` and the ABORT WORDS the call was given, shm_in_bwd's two arguments behind the scratch:
+ *   abort_dev   u32 in device memory, OR-ed to non-zero.  shm_adam_clip, given the same word as its `abort_word`, reads it ON THE DEVICE and
+ *               applies nothing while it is set: gradients built on unfinished sums never reach the weights, however far the host has run
+ *               ahead of the stream;
+ *   abort_host  u32 in mapped (pinned) host memory, set to 1: the host sees it without synchronising.
+ * Both stay set until the caller clears them.  Either may be NULL: a timeout is then recorded in the words that were given, with NULL / NULL
+ * in the scratch's own last word only.  The library keeps neither pointer beyond the launch it is passed to: the caller owns the pair, and
+ * its lifetime has to cover the launches that were given it (one pair per trainer, whichever thread steps it). */
 /* Measurement hook (bench.py, north_star_block.ceiling): while dev2 (two u64 in device memory) is set on the calling thread, one wave of the
  * middle block of every tapgemm_pp_bf16_kernel launch writes dev2[0] = shader-clock ticks (s_memtime) and dev2[1] = 100 MHz ticks (s_memrealtime)
  * of its patch loop: the clock the kernel actually held = dev2[0] / dev2[1] x 0.1 GHz.  NULL disarms (default). */
@@ -319,11 +322,13 @@ int shm_in_apply_pool(const void* a, int lda, const double* stats, const float* 
  *   dz = lrelu'(a) * inv * (d_out - mean(d_out) - xhat * mean(d_out * xhat))
  * red = f64 scratch [batch*c*3], ZERO on entry and zero again on return; dbias = f64 accumulator [c]
  * (NOT zeroed, may be NULL).  dz_sums (may be NULL; needs dbias) = f64 [batch][c], receives the per-sample channel sums of dz
- * staged on the way to dbias.  fused_scratch / fused_doubles (may be NULL / 0 = two passes): scratch of the one-pass bf16 form, above.
+ * staged on the way to dbias.  fused_scratch / fused_doubles (may be NULL / 0 = two passes): scratch of the one-pass bf16 form, above;
+ * abort_dev / abort_host (may be NULL): the abort words of that form, ignored by the two passes.
  * g1, g2 are [G] tensors; a and dz are activation-typed. */
 int shm_in_bwd(const void* g1, int ldg1, const void* g2, int ldg2, const void* a, int lda,
                const double* stats, double* red, void* dz, int lddz, double* dbias, double* dz_sums,
-               double* fused_scratch, size_t fused_doubles, int batch, int h, int w, int c, float slope, int dtype, void* stream);
+               double* fused_scratch, size_t fused_doubles, unsigned* abort_dev, unsigned* abort_host, int batch, int h, int w, int c,
+               float slope, int dtype, void* stream);
 
 /* ---- the fused block's backward: InstanceNorm sums in the producing epilogue ("gsum") -------------------------------------
  * The IN backward needs, per (sample, channel), sum(d_out) and sum(d_out * xhat) before it can write dz: shm_in_bwd collects
@@ -655,10 +660,10 @@ int shm_running_scale_mean(const float* scale, int batch, double* acc, float* mu
 /* ---- optimizer (SHM.py:169-175, 859-872) ------------------------------------------
  * tf.clip_by_value(g,-1,1) + Keras adam_v2.Adam: m += (g-m)(1-b1); v += (g^2-v)(1-b2);
  * w -= alpha * m / (sqrt(v) + eps); alpha = lr_t*sqrt(1-b2^t)/(1-b1^t) computed by the caller.
- * gscale multiplies g before the clip (1/world_size for data parallel).  With shm_set_abort_words armed on this thread the
- * kernel checks the device word first and leaves w, m, v untouched while it is non-zero. */
+ * gscale multiplies g before the clip (1/world_size for data parallel).  abort_word (may be NULL): the device abort word of the
+ * step's shm_in_bwd calls; the kernel checks it first and leaves w, m, v untouched while it is non-zero. */
 int shm_adam_clip(float* w, float* m, float* v, const float* g, size_t n, float alpha, float beta1,
-                  float beta2, float eps, float gscale, void* stream);
+                  float beta2, float eps, float gscale, const unsigned* abort_word, void* stream);
 
 /* ---- training telemetry (the reference logs its loss scalars every 25 steps, SHM.py:1035-1053, and a histogram of every clipped
  * gradient tensor every 100, SHM.py:1085-1091) --------------------------------------------------------------------------------
@@ -700,7 +705,7 @@ int shm_tensor_stats(const float* x, size_t n, const size_t* seg_off, const size
                      double* stats, unsigned long long* hist, void* ws, size_t ws_bytes, void* stream);
 /* One step's raw loss sums into row `row` of a device ring of f64 [rows][SHM_LOSS_ROW], one tiny launch, no host sync:
  * {dl[SHM_LOSS_ROW_DL] (shm_dhead_losses), il[SHM_LOSS_ROW_IL] (shm_image_losses), sl[SHM_LOSS_ROW_SL] (shm_spec_loss), step,
- * abort word}, the last two as f64.  abort_word: the device word of shm_set_abort_words (u32) or null (stored as 0).  The caller
+ * abort word}, the last two as f64.  abort_word: the device abort word of shm_in_bwd / shm_adam_clip (u32) or null (stored as 0).  The caller
  * chooses the row (the n-th logged step goes to row n % rows) and copies the ring out before a row comes round again. */
 #define SHM_LOSS_ROW_DL 16
 #define SHM_LOSS_ROW_IL 32

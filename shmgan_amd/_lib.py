@@ -58,11 +58,10 @@ SIGNATURES = {
     "shm_conv2d_wgrad_partial_norm": (I, [P, P, I, I, I, P, P, I, P, I, I, I, I, I, I, I, I, I, P, Z, I, P, P]),
     "shm_conv2d_wgrad_norm_workspace": (Z, [I, I, I, I, I, I, I]),
     "shm_conv2d_wgrad_norm_finish": (I, [P, P, P, I, I, I, I, I, I, P]),
-    "shm_set_abort_words": (I, [P, P]),
     "shm_set_clock_probe": (I, [P]),
     "shm_conv2d_wgrad_norm_supported": (I, [I, I, I, I, I, I, I, I, I, I, I]),
     "shm_in_pool": (I, [P, I, P, P, P, I, I, I, I, I, I, P]),
-    "shm_in_bwd": (I, [P, I, P, I, P, I, P, P, P, I, P, P, P, Z, I, I, I, I, F, I, P]),
+    "shm_in_bwd": (I, [P, I, P, I, P, I, P, P, P, I, P, P, P, Z, P, P, I, I, I, I, F, I, P]),
     "shm_conv2d_dgrad_gsum": (I, [P, I, P, P, P, I, I, I, I, I, I, I, I, I, I, P, I, P, P, I, P, I, P]),
     "shm_conv2d_fwd_gsum": (I, [P, P, I, I, I, P, P, P, I, I, I, I, I, I, I, I, F, P, I, P, I, P]),
     "shm_in_bwd_apply": (I, [P, I, P, I, P, I, P, P, P, P, P, P, I, P, P, I, I, I, I, F, I, P]),
@@ -116,7 +115,7 @@ SIGNATURES = {
     "shm_export_u8": (I, [P, P, I, P, I, P, Z, P, Z, P]),
     "shm_export_u8_hw": (I, [P, P, I, P, I, P, Z, P, Z, P]),
     "shm_running_scale_mean": (I, [P, I, P, P, P]),
-    "shm_adam_clip": (I, [P, P, P, P, Z, F, F, F, F, F, P]),
+    "shm_adam_clip": (I, [P, P, P, P, Z, F, F, F, F, F, P, P]),
     "shm_tensor_stats_workspace": (Z, [I, Z]),
     "shm_tensor_stats": (I, [P, Z, P, P, I, F, P, P, P, Z, P]),
     "shm_loss_ring_put": (I, [P, P, P, P, P, I, I, C.c_longlong, P]),

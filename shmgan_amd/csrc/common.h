@@ -60,8 +60,6 @@ enum ShmTune {
 };
 int shm_tune(int id);
 unsigned long long* shm_clock_probe();       // this thread's shm_set_clock_probe buffer (runtime.hip), or null
-unsigned* shm_abort_dev_word();              // this thread's shm_set_abort_words device word (runtime.hip), or null
-unsigned* shm_abort_host_word();             // ... and its host word
 
 // Barrier of the LDS-DMA pipelines.  A stage is refilled by DMA instructions issued AFTER the barrier that follows its last use, so a
 // wave must not enter that barrier with fragment reads of the stage still queued: the MFMAs that consume them are register-only

@@ -627,7 +627,7 @@ __global__ __launch_bounds__(256, G2 ? 3 : 4) void in_bwd_fused8_kernel(const In
                 __builtin_amdgcn_s_sleep(16);
                 if (++spins > (arrivals == gridDim.x ? 1 << 20 : 1 << 10)) {          // (the stalled test form gives up after ~1 ms)
                     // gave up: this launch goes on with wrong means.  The scratch's own word names the buffer; the caller's abort words
-                    // (shm_set_abort_words) make it fatal: shm_adam_clip applies nothing while the device word is set, and the host word
+                    // (shm_in_bwd's abort_dev / abort_host) make it fatal: shm_adam_clip applies nothing while the device word is set, and the host word
                     // (mapped host memory) lets the trainer see it without a synchronisation
                     __hip_atomic_fetch_or(ferr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     if (abort_dev) __hip_atomic_fetch_or(abort_dev, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1068,8 +1068,8 @@ static int fused_resident_blocks(int form) {          // 0: in_bwd_fused8_kernel
 }
 
 static int in_bwd_impl(const char* who, const void* g1, int ldg1, const void* g2, int ldg2, const float* r1_dz, const float* r1_w, const void* a, int lda,
-                       const double* stats, double* red, void* dz, int lddz, double* dbias, double* keep, double* fscr, size_t fscr_n, int batch, int h,
-                       int w, int c, float slope, int dtype, void* stream) {
+                       const double* stats, double* red, void* dz, int lddz, double* dbias, double* keep, double* fscr, size_t fscr_n, unsigned* abort_dev,
+                       unsigned* abort_host, int batch, int h, int w, int c, float slope, int dtype, void* stream) {
     const bool r1 = r1_dz != nullptr;
     SHM_REQUIRE(!keep || dbias, SHM_E_SHAPE, "%s: the per-sample dz sums are staged only with a bias gradient", who);
     SHM_CHECK_C(c, who);
@@ -1121,7 +1121,7 @@ static int in_bwd_impl(const char* who, const void* g1, int ldg1, const void* g2
             unsigned* const ferr = fsync + (size_t)batch * ncb * SHM_FUSED_SYNC_WORDS;
             const dim3 gridf(blocks, ncb, batch);
             const unsigned arrivals = gridf.x + (shm_tune(SHM_TUNE_ELEM_FUSED_TEST_STALL) ? 1u : 0u);
-            hipLaunchKernelGGL(kernel, gridf, dim3(256), 0, st, k, (float*)fscr, fres, fsync, ferr, shm_abort_dev_word(), shm_abort_host_word(), arrivals);
+            hipLaunchKernelGGL(kernel, gridf, dim3(256), 0, st, k, (float*)fscr, fres, fsync, ferr, abort_dev, abort_host, arrivals);
             shm_set_last_kernel("%s", name);
             SHM_LAUNCH_CHECK_CLEAR("shm_in_bwd(fused)", red, red_bytes, st);
             if (dbias && !k.fold) {       // (the two sum planes in front of the staging were not used: nothing to clear)
@@ -1204,10 +1204,11 @@ static int in_bwd_impl(const char* who, const void* g1, int ldg1, const void* g2
 
 extern "C" int shm_in_bwd(const void* g1, int ldg1, const void* g2, int ldg2, const void* a, int lda,
                           const double* stats, double* red, void* dz, int lddz, double* dbias, double* dz_sums, double* fused_scratch,
-                          size_t fused_doubles, int batch, int h, int w, int c, float slope, int dtype, void* stream) {
+                          size_t fused_doubles, unsigned* abort_dev, unsigned* abort_host, int batch, int h, int w, int c, float slope, int dtype,
+                          void* stream) {
     SHM_REQUIRE(g1, SHM_E_SHAPE, "shm_in_bwd: null gradient");
-    return in_bwd_impl("shm_in_bwd", g1, ldg1, g2, ldg2, nullptr, nullptr, a, lda, stats, red, dz, lddz, dbias, dz_sums, fused_scratch, fused_doubles, batch, h,
-                       w, c, slope, dtype, stream);
+    return in_bwd_impl("shm_in_bwd", g1, ldg1, g2, ldg2, nullptr, nullptr, a, lda, stats, red, dz, lddz, dbias, dz_sums, fused_scratch, fused_doubles, abort_dev,
+                       abort_host, batch, h, w, c, slope, dtype, stream);
 }
 
 // InstanceNorm + LeakyReLU backward WITHOUT its reduce pass: the per-(sample, channel) sums were formed in the epilogues of the
@@ -1262,8 +1263,8 @@ extern "C" int shm_in_bwd_apply(const void* g1, int ldg1, const void* g2, int ld
 extern "C" int shm_in_bwd_rank1(const float* hdz, const float* hw_, const void* a, int lda, const double* stats, double* red, void* dz, int lddz,
                                 double* dbias, double* dz_sums, int batch, int h, int w, int c, float slope, int dtype, void* stream) {
     SHM_REQUIRE(hdz && hw_, SHM_E_SHAPE, "shm_in_bwd_rank1: null gradient");
-    return in_bwd_impl("shm_in_bwd_rank1", nullptr, 0, nullptr, 0, hdz, hw_, a, lda, stats, red, dz, lddz, dbias, dz_sums, nullptr, 0, batch, h, w, c, slope,
-                       dtype, stream);
+    return in_bwd_impl("shm_in_bwd_rank1", nullptr, 0, nullptr, 0, hdz, hw_, a, lda, stats, red, dz, lddz, dbias, dz_sums, nullptr, 0, nullptr, nullptr, batch, h, w, c,
+                       slope, dtype, stream);
 }
 
 // ---------------------------------------------------------------------- LeakyReLU backward

@@ -1,5 +1,7 @@
 // The library's runtime, host code only: this thread's error string and last-kernel name, the process-wide tuning table behind
-// shm_set_tuning / shm_get_tuning, the version, and the per-thread configuration the launchers read (abort words, clock probe).
+// shm_set_tuning / shm_get_tuning, the version, and the clock probe.  The clock probe is the one per-thread pointer a launcher still reads
+// implicitly: it is a measurement hook that bench.py arms through shm_set_clock_probe, not data-path state (the abort words are arguments
+// of shm_in_bwd and shm_adam_clip).
 #include "common.h"
 
 #include <stdarg.h>
@@ -116,22 +118,8 @@ extern "C" int shm_get_tuning(const char* key, int* value) {
 
 extern "C" const char* shm_last_error(void) { return g_err; }
 extern "C" const char* shm_last_kernel(void) { return g_kernel; }
-extern "C" int shm_version(void) { return 202; }
+extern "C" int shm_version(void) { return 203; }
 
-// shm_set_abort_words: where a kernel that had to give up (today: a barrier of in_bwd_fused8_kernel that timed out) says so for THIS thread's
-// later calls.  dev_word: u32 in device memory, OR-ed to non-zero; shm_adam_clip reads it on the device and applies NOTHING while it is set, so a
-// gradient built on unfinished sums never reaches the weights, however far the host has run ahead.  host_word: u32 in mapped (pinned) host
-// memory, set to 1 by the same kernel: the caller polls it without a device synchronisation.  Both stay set until the caller clears them.
-// NULLs disarm.  Persistent per thread (like the tuning table this is configuration, not data-path state).
-static thread_local unsigned* g_abort_dev = nullptr;
-static thread_local unsigned* g_abort_host = nullptr;
-extern "C" int shm_set_abort_words(unsigned* dev_word, unsigned* host_word) {
-    g_abort_dev = dev_word;
-    g_abort_host = host_word;
-    return SHM_OK;
-}
-unsigned* shm_abort_dev_word() { return g_abort_dev; }
-unsigned* shm_abort_host_word() { return g_abort_host; }
 // shm_set_clock_probe: measurement hook (bench.py's north-star ceiling).  While set on this thread, the ping-pong convolution kernel
 // (tapgemm_pp_bf16_kernel) writes, from one wave of its middle block, dev2[0] = s_memtime ticks (shader clock) and dev2[1] = s_memrealtime ticks
 // (100 MHz) spent in its patch loop: dev2[0] / dev2[1] x 0.1 = the clock in GHz the kernel held.  NULL (default) disarms; no other kernel reads it.

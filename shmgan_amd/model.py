@@ -59,11 +59,14 @@ def _padk(c, g):
 
 class Arena:
     """Named, shape-keyed tensor cache: every activation buffer is allocated once and reused
-    on the next step (the step has a static memory plan; 288 GB of HBM is not the limit)."""
+    on the next step (the step has a static memory plan; 288 GB of HBM is not the limit).
+    `abort`: the ops.AbortWords of every launch that works on this arena's buffers (the one-pass InstanceNorm backward sets them, the
+    optimizer kernel checks them); they live and die with the arena, like the scratches whose barriers report to them."""
 
     def __init__(self, device):
         self.device = device
         self.t = {}
+        self.abort = ops.AbortWords(device) if torch.device(device).type == "cuda" else None
 
     def get(self, name, shape, dtype=torch.float32):
         key = (name, tuple(shape), dtype)
@@ -728,7 +731,7 @@ class Generator(_ModelBase):
         else:
             red = A.get(f"bwd/red/{n * cout}", (n * cout * 3,), torch.float64)
             ops.in_bwd(g1, cout, g2, cout, rec["a"], cout, rec["stats"], red, dz, cout, self._acc_slice(2 * li + 1), n,
-                       h, w, cout, LRELU, fused=_fused_scratch(A, self.adt, n, h * w, cout), dz_sums=dzsum)
+                       h, w, cout, LRELU, fused=_fused_scratch(A, self.adt, n, h * w, cout), dz_sums=dzsum, abort=A.abort)
         if self.debug is not None:           # test diagnostics: keep the per-layer gradients
             if g1 is None:
                 g1 = rank1[0].reshape(n, h, w, 1) * rank1[1].reshape(1, 1, 1, -1)
@@ -1091,7 +1094,7 @@ class Discriminator(_ModelBase):
             else:
                 red = A.get(f"d/bwd/red{i}/{n}", (n * cout * 3,), torch.float64)
                 ops.in_bwd(dcur, cout, None, 0, rec["a"], cout, rec["stats"], red, dz, cout, None, n, ho, ho, cout, LRELU,
-                           fused=_fused_scratch(A, self.adt, n, ho * ho, cout))
+                           fused=_fused_scratch(A, self.adt, n, ho * ho, cout), abort=A.abort)
             gred = None
             if params:
                 ws = self.ws_provider(ops.conv2d_wgrad_workspace(n, ho, ho, cin, cout, 3))

@@ -358,12 +358,29 @@ def in_apply(a, lda, stats, beta, out, ldo, batch, hw, c):
         lib().shm_in_apply(_p(a), lda, _p(stats), _p(beta), _p(out), ldo, batch, hw, c, _dt(a), _stream()), "shm_in_apply"))
 
 
-def set_abort_words(dev_word, host_word):
-    """shm_set_abort_words: dev_word a uint32 / int32 CUDA tensor of one element, host_word a PINNED host tensor of one element (ROCm maps
-    pinned host memory into the device's address space at the same address); None, None disarms."""
-    if host_word is not None:
-        assert host_word.is_pinned() and not host_word.is_cuda and dev_word.is_cuda
-    check(lib().shm_set_abort_words(_p(dev_word), _p(host_word)), "shm_set_abort_words")
+class AbortWords:
+    """The pair of words a kernel that had to give up reports to (include/shmgan_hip.h, the one-pass form of shm_in_bwd): `dev`, an int32 CUDA
+    tensor of one element that in_bwd(abort=) sets and adam_clip(abort=) checks on the device, and `host`, a PINNED host tensor of one element
+    (ROCm maps pinned host memory into the device's address space at the same address) that the kernel sets to 1 itself.  The library keeps
+    no pointer to either: whoever owns the pair (model.Arena) outlives the launches it is handed to."""
+
+    def __init__(self, device):
+        self.dev = torch.zeros(1, dtype=torch.int32, device=device)
+        self.host = torch.zeros(1, dtype=torch.int32).pin_memory()
+        assert self.host.is_pinned() and not self.host.is_cuda and self.dev.is_cuda
+        self.np = self.host.numpy()
+
+    def tripped(self, sync=False):
+        """One read of host memory; sync=True waits for the device first and reads its word too (exact)."""
+        if sync:
+            torch.cuda.synchronize(self.dev.device)
+        return int(self.np[0]) != 0 or (sync and int(self.dev.item()) != 0)
+
+    def clear(self):
+        torch.cuda.synchronize(self.dev.device)
+        self.dev.zero_()
+        self.np[0] = 0
+        torch.cuda.synchronize(self.dev.device)
 
 
 def set_clock_probe(dev2):
@@ -377,9 +394,10 @@ def in_bwd_fused_doubles(batch, hw, c):
     return (batch * (hw * cb // 16384) * 3 * c + 1) // 2 + batch * c + batch * (c // cb) * 288 + 1
 
 
-def in_bwd(g1, ldg1, g2, ldg2, a, lda, stats, red, dz, lddz, dbias, batch, h, w, c, slope, fused=None, dz_sums=None):
+def in_bwd(g1, ldg1, g2, ldg2, a, lda, stats, red, dz, lddz, dbias, batch, h, w, c, slope, fused=None, dz_sums=None, abort=None):
     """fused: float64 scratch of in_bwd_fused_doubles(batch, h * w, c) elements (zero on entry, zero on return): the call may run the one-pass
     bf16 form; the library falls back to reduce + apply on shapes that form does not take.
+    abort: the AbortWords a barrier of that form sets when it gives up (None: only the scratch's own last word records it).
     dz_sums (here, in in_bwd_apply and in in_bwd_rank1): float64 [batch][c], receives the per-sample channel sums of dz; needs dbias."""
     e = batch * h * w * c
     rd = _tb(g1, e * (1.25 if g2 is not None else 1.0)) + _tb(a, e)
@@ -391,7 +409,7 @@ def in_bwd(g1, ldg1, g2, ldg2, a, lda, stats, red, dz, lddz, dbias, batch, h, w,
 
     _timed_bytes("shm_in_bwd", nb, lambda: check(
         lib().shm_in_bwd(_p(g1), ldg1, _p(g2), ldg2, _p(a), lda, _p(stats), _p(red), _p(dz), lddz, _p(dbias), _p(dz_sums), _p(fused),
-                         0 if fused is None else fused.numel(), batch, h, w, c, slope, _dtg(a, g1), _stream()), "shm_in_bwd"))
+                         0 if fused is None else fused.numel(), _p(abort and abort.dev), _p(abort and abort.host), batch, h, w, c, slope, _dtg(a, g1), _stream()), "shm_in_bwd"))
 
 
 def in_bwd_apply(g1, ldg1, g2, ldg2, a, lda, stats, beta, red, redp, dstage, dz, lddz, dbias, batch, h, w, c, slope, dz_sums=None):
@@ -804,9 +822,10 @@ def running_scale_mean(scale, acc, mul):
     return mul
 
 
-def adam_clip(w, m, v, g, n, alpha, beta1, beta2, eps, gscale):
+def adam_clip(w, m, v, g, n, alpha, beta1, beta2, eps, gscale, abort=None):
+    """abort: the step's AbortWords; the kernel applies nothing while their device word is set."""
     _timed_bytes("shm_adam_clip", 7.0 * 4 * n, lambda: check(          # read w, m, v, g; write w, m, v
-        lib().shm_adam_clip(_p(w), _p(m), _p(v), _p(g), n, alpha, beta1, beta2, eps, gscale, _stream()), "shm_adam_clip"))
+        lib().shm_adam_clip(_p(w), _p(m), _p(v), _p(g), n, alpha, beta1, beta2, eps, gscale, _p(abort and abort.dev), _stream()), "shm_adam_clip"))
 
 
 # ---- SpecSeg (inference only) ----------------------------------------------------------------

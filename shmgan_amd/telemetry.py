@@ -155,7 +155,7 @@ class Telemetry:
         self.loss_log_step, self.histogram_step, self.nonfinite = telemetry_options(loss_log_step, histogram_step, nonfinite)
         self.log_dir = log_dir
         self.dev = trainer.device
-        self.abort_dev = trainer._abort_dev
+        self.abort_dev = trainer.arena.abort.dev
         self.tables = {"G": _Table(trainer.G, "G"), "D": _Table(trainer.D, "D")}
         self.models = {"G": trainer.G, "D": trainer.D}
         self.arena = trainer.arena

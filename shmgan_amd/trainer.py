@@ -43,9 +43,10 @@ class _Optimizer:
         lr = self.lr0 * 0.95 ** (iterations / 10000.0)
         return lr * math.sqrt(1.0 - self.beta_2 ** t) / (1.0 - self.beta_1 ** t)
 
-    def apply(self, P, gscale=1.0):
+    def apply(self, P, gscale=1.0, abort=None):
+        """abort: the ops.AbortWords of the step that made P.grad: no update while their device word is set."""
         ops.adam_clip(P.flat, P.m, P.v, P.grad, P.n, self.alpha(P.iterations), self.beta_1, self.beta_2,
-                      self.epsilon, gscale)
+                      self.epsilon, gscale, abort=abort)
         P.iterations += 1
 
 
@@ -59,7 +60,7 @@ _DEFAULTS = dict(image_size=128, batch_size=1, filter_size=64, g_lr=0.00002, d_l
 
 class KernelAbortError(RuntimeError):
     """A kernel of an earlier step gave up (a barrier of the one-pass InstanceNorm backward timed out) and went on with wrong numbers.
-    The optimizer kernels refused every update from that moment on (shm_set_abort_words), so the weights are those of the last good
+    The optimizer kernels refused every update from that moment on (the arena's abort words), so the weights are those of the last good
     step; the run must not continue."""
 
 
@@ -115,6 +116,8 @@ class ShmGANwithSSpecSeg:
         # both optimisers use the schedule built from g_lr (SHM.py:169-174; d_lr is unused there)
         self.optimizer_G = _Optimizer(self.g_lr, self.beta1, self.beta2)
         self.optimizer_D = _Optimizer(self.g_lr, self.beta1, self.beta2)
+        # the arena also owns the abort words (ops.AbortWords): a device word the optimizer kernel checks before it touches the weights, and a
+        # word in pinned host memory the host polls without synchronising (_check_abort)
         self.arena = Arena(self.device)
         self._ws = None
         self._lane = None
@@ -127,11 +130,6 @@ class ShmGANwithSSpecSeg:
         self._reducer = GradReducer(self.device)
         self._prefetched = None          # _prologue() of the next batch, issued by train_step(next_batch=)
         self._loss_cache = None
-        # abort words (include/shmgan_hip.h, shm_set_abort_words): a device word the optimizer kernel checks before it touches the
-        # weights, and a word in pinned host memory the host polls without synchronising (_check_abort)
-        self._abort_dev = torch.zeros(1, dtype=torch.int32, device=self.device)
-        self._abort_host = torch.zeros(1, dtype=torch.int32).pin_memory()
-        self._abort_np = self._abort_host.numpy()
         # test diagnostics: called with no arguments between the last forward pass and the first backward kernel of a step
         # (tests/test_step_gpu.py pins LeakyReLU signs there; never set on the hot path)
         self.before_backward = None
@@ -163,34 +161,25 @@ class ShmGANwithSSpecSeg:
             self._ws = torch.empty(max(n, 32 << 20), dtype=torch.float32, device=self.device)
         return self._ws
 
-    def _arm_abort(self):
-        """Point the library's abort words at this trainer's pair (per-thread state of the library: several trainers may live in
-        one process, the one that steps owns them)."""
-        ops.set_abort_words(self._abort_dev, self._abort_host)
-
     def _check_abort(self, sync=False):
         """Raise KernelAbortError if a kernel of this trainer gave up.  Without `sync` this is one read of host memory (the kernel
         wrote the pinned word itself), so it costs the step nothing; it sees every abort whose kernel has finished -- the host runs
         ahead of the device, so an abort of step t may only be seen at the top of step t + 2, and the device-side check in
         shm_adam_clip is what keeps the weights clean in between.  sync=True (losses(), checkpoints, release()) waits for the device
         first and is exact."""
-        if self._abort_host is None:
+        if self.arena.abort is None:
             return
-        if sync:
-            torch.cuda.synchronize(self.device)
-        if int(self._abort_np[0]) != 0 or (sync and int(self._abort_dev.item()) != 0):
+        if self.arena.abort.tripped(sync):
             names = self.arena.fused_timeouts()
             raise KernelAbortError(
                 f"in_bwd_fused8_kernel: a group barrier timed out (scratch {names or 'unknown'}): the step's gradients are built on "
                 "unfinished sums.  No optimizer update has been applied since (shm_adam_clip checks the abort word on the device); "
                 "the weights are those of the last good step.  Set SHM_ELEM_FUSED_BWD=0 (two-pass InstanceNorm backward) and report; "
-                "clear_abort() re-arms this trainer")
+                "clear_abort() clears the words")
 
     def clear_abort(self):
         """Clear the abort words (after a KernelAbortError, once its cause is dealt with)."""
-        torch.cuda.synchronize(self.device)
-        self._abort_dev.zero_()
-        self._abort_np[0] = 0
+        self.arena.abort.clear()
         self.arena.fused_timeouts()
         torch.cuda.synchronize(self.device)
 
@@ -207,9 +196,8 @@ class ShmGANwithSSpecSeg:
             self._release_buffers()
 
     def _release_buffers(self):
-        aborted = self._abort_host is not None and (int(self._abort_np[0]) != 0 or int(self._abort_dev.item()) != 0)
-        ops.set_abort_words(None, None)
-        self._abort_dev = self._abort_host = self._abort_np = None
+        aborted = self.arena.abort is not None and self.arena.abort.tripped(sync=True)
+        self.arena.abort = None
         self.arena.t.clear()
         self._ws = self._prefetched = self._loss_cache = None
         self._adhoc_telemetry = None
@@ -421,7 +409,6 @@ class ShmGANwithSSpecSeg:
         between) picks the result up instead of recomputing it."""
         if self.G is None:
             self.build()
-        self._arm_abort()
         self._check_abort()              # an earlier step's kernel gave up: stop here, before anything else is issued
         if self.telemetry is not None:
             self.telemetry.check()       # non-finite gradients in a histogram that has reached the host (nonfinite="raise" / "warn")
@@ -603,13 +590,13 @@ class ShmGANwithSSpecSeg:
             self._reducer.wait_on(ev_d)
             if hist_now:
                 tel.record_gradients("D", 1.0 / world)
-            self.optimizer_D.apply(D.P, 1.0 / world)
+            self.optimizer_D.apply(D.P, 1.0 / world, abort=self.arena.abort)
             D.weights_dirty = True
             if update_g:
                 self._reducer.wait_on(ev_g)
                 if hist_now:
                     tel.record_gradients("G", 1.0 / world)
-                self.optimizer_G.apply(G.P, 1.0 / world)
+                self.optimizer_G.apply(G.P, 1.0 / world, abort=self.arena.abort)
                 G.weights_dirty = True
         elif exchange_active():
             for ev in (ev_d, ev_g):

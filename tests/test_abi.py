@@ -9,6 +9,14 @@ import pytest
 from shmgan_amd import _lib
 
 
+def exported_functions(lib):
+    """The unmangled shm_* functions in the dynamic symbol table of `lib`: its C ABI as the linker sees it."""
+    import subprocess
+    out = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readelf", "--dyn-syms", "--wide", str(lib)], check=True, capture_output=True, text=True).stdout
+    rows = [ln.split() for ln in out.splitlines()]
+    return {r[7] for r in rows if len(r) == 8 and r[3] == "FUNC" and r[4] in ("GLOBAL", "WEAK") and r[6] != "UND" and re.fullmatch(r"shm_[a-z0-9_]+", r[7])}
+
+
 def test_header_table_and_exports_agree():
     hdr = _lib.header_functions()
     assert len(hdr) == len(set(hdr)), "duplicate declaration in the header"
@@ -17,6 +25,9 @@ def test_header_table_and_exports_agree():
     L = _lib.lib()
     for name in hdr:
         assert hasattr(L, name), f"{name} not exported by libshmgan_hip.so"
+    # ... and nothing else: an entry point that left the header (the per-thread request and abort-word setters did) has left the library too
+    exports = exported_functions(_lib.LIB_PATH)
+    assert exports == set(hdr), (exports ^ set(hdr))
 
 
 def test_argument_counts_match_header():
@@ -45,12 +56,15 @@ def test_version_and_error_string_without_gpu():
 
 
 def test_in_bwd_requests_are_arguments_not_thread_state():
-    """The InstanceNorm backward takes its dz_sums / fused scratch as arguments: no kernel source keeps per-thread request state (runtime.hip
-    holds the persistent per-thread configuration), and the entry points that armed it are gone from the header, the table and the library."""
+    """The InstanceNorm backward takes its dz_sums / fused scratch / abort words as arguments: no kernel source keeps per-thread request state
+    (runtime.hip holds the error string, the last kernel's name and the clock probe, its one per-thread pointer), and the entry points that
+    armed it are gone from the header, the table and the library."""
     csrc = Path(_lib.__file__).resolve().parent / "csrc"
     for f in sorted([*csrc.glob("*.hip"), *csrc.glob("*.h")]):
         if f.name != "runtime.hip":
             assert "thread_local" not in f.read_text(), f.name
+    runtime = re.sub(r"//.*", "", (csrc / "runtime.hip").read_text())
+    assert re.findall(r"thread_local[^;=]*\*\s*(\w+)", runtime) == ["g_clock_probe"]
     L = _lib.lib()
     for name in ("shm_in_bwd_keep_dz_sums", "shm_in_bwd_fused_scratch"):
         assert name not in _lib.HEADER.read_text() and name not in _lib.SIGNATURES and not hasattr(L, name), name
@@ -67,7 +81,7 @@ def test_dz_sums_need_a_bias_gradient_without_gpu():
     same message, before any launch (and before their other pointer checks)."""
     L = _lib.lib()
     p, f32 = 1, _lib.F32            # a non-null pointer nobody dereferences
-    rc = L.shm_in_bwd(p, 64, None, 0, p, 64, p, p, p, 64, None, p, None, 0, 1, 8, 8, 64, 0.2, f32, None)
+    rc = L.shm_in_bwd(p, 64, None, 0, p, 64, p, p, p, 64, None, p, None, 0, None, None, 1, 8, 8, 64, 0.2, f32, None)
     assert rc == -1 and b"bias gradient" in L.shm_last_error()
     rc = L.shm_in_bwd_apply(None, 64, None, 0, None, 64, None, None, None, None, None, None, 64, None, p, 1, 8, 8, 64, 0.2, f32, None)
     assert rc == -1 and b"bias gradient" in L.shm_last_error()

@@ -1,8 +1,10 @@
 """A barrier of the one-pass bf16 InstanceNorm backward that gives up must be fatal in the step that tripped it (round 6; VERDICT r5 item 3,
-advisor r5 "medium").  include/shmgan_hip.h: shm_set_abort_words, shm_adam_clip; the step is SHM.py:859-872 (gradients -> clip -> Adam).
+advisor r5 "medium").  include/shmgan_hip.h: the abort words of shm_in_bwd and shm_adam_clip; the step is SHM.py:859-872 (gradients -> clip -> Adam).
 
   * "elem.fused_test_stall" = 1 makes every barrier of in_bwd_fused8_kernel wait for a block that does not exist: the launch times out, sets the
     scratch's word, the device abort word and the pinned host word; shm_adam_clip then leaves w, m, v bit for bit;
+  * the words are arguments, not state of the library or of the calling thread: a timeout sets the pair its call was given and no other, from
+    whichever thread the call is made, and a trainer that is dropped without release() leaves nothing behind that a later optimizer call reads;
   * a trainer whose step tripped keeps the weights of the last good step, raises KernelAbortError at the next train_step / losses() /
     checkpoint, and works again after clear_abort();
   * the launcher takes the one-pass form only when twice a group's blocks fit the device;
@@ -10,15 +12,19 @@ advisor r5 "medium").  include/shmgan_hip.h: shm_set_abort_words, shm_adam_clip;
     (one-rank group, SHM_DP_FORCE=1: an RCCL kernel co-resident with the barrier kernels) -- no timeout, the kernel's outputs equal the two passes' to 2e-3 and the
     step's gradients to the bf16 tolerance per tensor, and the kernel on fixed operands gives the same bits on a third stream while steps are running.
 """
+import gc
 import multiprocessing as mp
 import os
 import socket
+import threading
 
 import numpy as np
 import pytest
 import torch
 
 from oracle import step_torch as st
+from oracle import tf_ops_np as tn
+from util import dev as to_dev, host as to_host, rel_l2
 
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
@@ -33,16 +39,19 @@ def _ops():
 def _reset():
     yield
     _ops().set_tuning("reset", 0)
-    _ops().set_abort_words(None, None)
 
 
 def _words():
-    dev = torch.zeros(1, dtype=torch.int32, device="cuda")
-    host = torch.zeros(1, dtype=torch.int32).pin_memory()
-    return dev, host, host.numpy()
+    return _ops().AbortWords(torch.device("cuda"))
 
 
-def _fused_call(n=2, h=32, c=64, stall=0):
+def _adam_operands(n=4096):
+    rng = np.random.default_rng(0)
+    w, m, v, g = (torch.from_numpy(rng.standard_normal(n).astype(np.float32)).cuda() for _ in range(4))
+    return w, m, v.abs(), g
+
+
+def _fused_call(n=2, h=32, c=64, stall=0, abort=None):
     ops = _ops()
     rng = np.random.default_rng(5)
     a = torch.from_numpy(rng.standard_normal((n, h, h, c)).astype(np.float32)).cuda().to(BF)
@@ -54,7 +63,7 @@ def _fused_call(n=2, h=32, c=64, stall=0):
     red = torch.zeros(n * c * 3, dtype=torch.float64, device="cuda")
     scr = torch.zeros(ops.in_bwd_fused_doubles(n, h * h, c), dtype=torch.float64, device="cuda")
     ops.set_tuning("elem.fused_test_stall", stall)
-    ops.in_bwd(g, c, None, 0, a, c, stats, red, dz, c, db, n, h, h, c, 0.2, fused=scr)
+    ops.in_bwd(g, c, None, 0, a, c, stats, red, dz, c, db, n, h, h, c, 0.2, fused=scr, abort=abort)
     kern = ops.last_kernel()
     ops.set_tuning("elem.fused_test_stall", 0)
     return scr, dz, kern
@@ -62,24 +71,22 @@ def _fused_call(n=2, h=32, c=64, stall=0):
 
 def test_timeout_sets_the_words_and_adam_refuses():
     ops = _ops()
-    dev, host, hnp = _words()
-    ops.set_abort_words(dev, host)
+    words = _words()
+    dev, hnp = words.dev, words.np
     n = 4096
-    rng = np.random.default_rng(0)
-    w, m, v, g = (torch.from_numpy(rng.standard_normal(n).astype(np.float32)).cuda() for _ in range(4))
-    v = v.abs()
-    # armed and clean: the update is applied
+    w, m, v, g = _adam_operands(n)
+    # given clean words: the update is applied
     w0 = w.clone()
-    ops.adam_clip(w, m, v, g, n, 1e-3, 0.5, 0.99, 1e-7, 1.0)
+    ops.adam_clip(w, m, v, g, n, 1e-3, 0.5, 0.99, 1e-7, 1.0, abort=words)
     torch.cuda.synchronize()
     assert not torch.equal(w, w0) and int(hnp[0]) == 0 and int(dev.item()) == 0
     # a clean fused call leaves the words alone
-    scr, _, kern = _fused_call(stall=0)
+    scr, _, kern = _fused_call(stall=0, abort=words)
     torch.cuda.synchronize()
     assert kern.startswith("in_bwd_fused8_kernel") and int(hnp[0]) == 0 and int(dev.item()) == 0
     assert int(scr[-1:].view(torch.int64).item()) == 0
     # every barrier times out: all three words are set -- the host word without any device-to-host copy
-    scr, dz, kern = _fused_call(stall=1)
+    scr, dz, kern = _fused_call(stall=1, abort=words)
     torch.cuda.synchronize()
     assert kern.startswith("in_bwd_fused8_kernel")
     assert int(hnp[0]) == 1, "the pinned host word is written by the kernel itself"
@@ -90,19 +97,92 @@ def test_timeout_sets_the_words_and_adam_refuses():
     assert int(scr[rows:-1].view(torch.int64).abs().sum().item()) == 0
     # the optimizer kernel applies nothing while the device word is set
     w1, m1, v1 = w.clone(), m.clone(), v.clone()
-    ops.adam_clip(w, m, v, g, n, 1e-3, 0.5, 0.99, 1e-7, 1.0)
+    ops.adam_clip(w, m, v, g, n, 1e-3, 0.5, 0.99, 1e-7, 1.0, abort=words)
     torch.cuda.synchronize()
     assert torch.equal(w, w1) and torch.equal(m, m1) and torch.equal(v, v1)
     dev.zero_()
-    ops.adam_clip(w, m, v, g, n, 1e-3, 0.5, 0.99, 1e-7, 1.0)
+    ops.adam_clip(w, m, v, g, n, 1e-3, 0.5, 0.99, 1e-7, 1.0, abort=words)
     torch.cuda.synchronize()
     assert not torch.equal(w, w1)
-    # disarmed: a timeout is only recorded in the scratch's own word
-    ops.set_abort_words(None, None)
+    # called without words: a timeout is only recorded in the scratch's own word
     hnp[0] = 0
     scr, _, _ = _fused_call(stall=1)
     torch.cuda.synchronize()
     assert int(hnp[0]) == 0 and int(dev.item()) == 0 and int(scr[-1:].view(torch.int64).item()) != 0
+
+
+def test_a_timeout_reaches_only_the_words_its_call_was_given():
+    """Two owners in one process: a stalled call given A's words sets A's three words and none of B's; the optimizer kernel given B's word
+    applies its update, given A's it leaves w, m, v bit for bit."""
+    ops = _ops()
+    A, B = _words(), _words()
+    scr, _, kern = _fused_call(stall=1, abort=A)
+    torch.cuda.synchronize()
+    assert kern.startswith("in_bwd_fused8_kernel")
+    assert int(A.np[0]) == 1 and int(A.dev.item()) != 0 and int(scr[-1:].view(torch.int64).item()) != 0
+    assert int(B.np[0]) == 0 and int(B.dev.item()) == 0
+    assert A.tripped() and not B.tripped(sync=True)
+    n = 4096
+    w, m, v, g = _adam_operands(n)
+    w0, m0, v0 = w.clone(), m.clone(), v.clone()
+    ops.adam_clip(w, m, v, g, n, 1e-3, 0.5, 0.99, 1e-7, 1.0, abort=B)
+    torch.cuda.synchronize()
+    assert not torch.equal(w, w0) and not torch.equal(m, m0) and not torch.equal(v, v0)
+    w1, m1, v1 = w.clone(), m.clone(), v.clone()
+    ops.adam_clip(w, m, v, g, n, 1e-3, 0.5, 0.99, 1e-7, 1.0, abort=A)
+    torch.cuda.synchronize()
+    assert torch.equal(w, w1) and torch.equal(m, m1) and torch.equal(v, v1)
+
+
+def test_the_words_do_not_depend_on_the_calling_thread():
+    """The same stalled call from a thread that never touched the library before: the words it was given are set all the same."""
+    A = _words()
+    out = []
+    torch.cuda.synchronize()
+    dev = torch.cuda.current_device()
+
+    def call():
+        torch.cuda.set_device(dev)
+        out.append(_fused_call(stall=1, abort=A))
+    t = threading.Thread(target=call)
+    t.start()
+    t.join()
+    torch.cuda.synchronize()
+    assert len(out) == 1, "the call raised in its thread"
+    scr, _, kern = out[0]
+    assert kern.startswith("in_bwd_fused8_kernel")
+    assert int(A.np[0]) == 1, "the launch from the second thread ran without its abort words"
+    assert int(A.dev.item()) != 0 and int(scr[-1:].view(torch.int64).item()) != 0
+
+
+def test_a_dropped_trainer_leaves_nothing_behind():
+    """A trainer that goes away without release() (garbage collection, an exception path): the library holds no pointer to its freed words,
+    so a plain optimizer call on memory the allocator hands out again -- non-zero here -- applies its update (tests/test_ops_gpu.py::test_adam_clip)."""
+    from shmgan_amd import ShmGANwithSSpecSeg
+    ops = _ops()
+    S, F, B = 64, 32, 1
+    m = ShmGANwithSSpecSeg(image_size=S, filter_size=F, batch_size=B, compute_dtype="bfloat16").build()
+    m.train_step(*st.make_inputs(B, S), draws=st.make_draws(0, B, S, F), style_factor=st.style_factor_intended(S))
+    torch.cuda.synchronize()
+    del m
+    gc.collect()
+    torch.cuda.empty_cache()
+    ones = [torch.ones(k, dtype=torch.int32, device="cuda") for k in (1, 1, 1, 1, 16, 128)]     # what was freed is handed out again, non-zero
+    torch.cuda.synchronize()
+    # the body of tests/test_ops_gpu.py::test_adam_clip
+    rng = np.random.default_rng(12)
+    n = 10007
+    w, mm, v = rng.standard_normal(n), rng.standard_normal(n) * 0.1, rng.random(n) * 0.01
+    g = rng.standard_normal(n) * 2
+    rw, rm, rv = tn.adam_update(w, mm, v, g * 0.5, 3, 2e-5, 0.5, 0.99)
+    alpha = tn.exp_decay_lr(2e-5, 3) * np.sqrt(1 - 0.99 ** 4) / (1 - 0.5 ** 4)
+    wd, md, vd = to_dev(w), to_dev(mm), to_dev(v)
+    w0 = wd.clone()
+    ops.adam_clip(wd, md, vd, to_dev(g), n, float(alpha), 0.5, 0.99, 1e-7, 0.5)
+    torch.cuda.synchronize()
+    assert all(int(t.min().item()) == 1 for t in ones)
+    assert not torch.equal(wd, w0), "the optimizer kernel applied nothing"
+    assert rel_l2(to_host(wd), rw) < 1e-6 and rel_l2(to_host(md), rm) < 1e-6 and rel_l2(to_host(vd), rv) < 1e-6
 
 
 def test_trainer_keeps_the_last_good_weights_and_raises():
@@ -259,7 +339,7 @@ def _stress_worker(port, q, steps):
         torch.cuda.synchronize()
         m._check_abort(sync=True)
         bitwise = all(torch.equal(dz, ref[0]) and torch.equal(db, ref[1]) for dz, db in outs)
-        q.put(("ok", bitwise, repeat, (worst, op_rel), tripped, float(loss), comm, kinds, int(m._abort_np[0])))
+        q.put(("ok", bitwise, repeat, (worst, op_rel), tripped, float(loss), comm, kinds, int(m.arena.abort.np[0])))
         dist.barrier()
         dist.destroy_process_group()
     except Exception as e:       # the parent asserts on the message

@@ -1,6 +1,7 @@
 // The bf16 weights-in-registers tap GEMM (K <= 64 input channels, 3x3, unit stride): BASELINE.json's north-star block -- conv 64 -> 64 at 256 x 256
 // + bias + LeakyReLU + InstanceNorm statistics (ShmGANwithSSpecSeg.py:244-245), its input gradient, and the generator's first layer.  A translation
-// unit of its own since round 5 (it is the kernel that gets rebuilt most; conv_igemm.hip takes 90 s to compile).
+// unit of its own since round 5 (it is the kernel that gets rebuilt most); every other tap-GEMM kernel family has one too now, behind the launch
+// functions of tapgemm.h, so that no single compile bounds the build.
 #include "tapgemm.h"
 
 // ------------------------------------------------------------------------------------------

@@ -1,4 +1,6 @@
-// Argument block and vector types of the tap-GEMM kernel family (conv_igemm.hip, conv_wreg16.hip): see conv_igemm.hip's header comment.
+// Argument block and vector types of the tap-GEMM kernels, the launcher's plan, and the launch function each kernel family's translation unit
+// sits behind (conv_dma.hip, conv_halo.hip, conv_wreg.hip, conv_wreg_f32.hip, conv_phase4.hip, conv_wreg16.hip, conv_pingpong.hip, conv_fwd_x3.hip).
+// conv_igemm.hip has the entry points, the plan and the launcher: see its header comment.  Device helpers the families share: tapgemm_dev.h.
 #pragma once
 #include "common.h"
 #include "ablate.h"
@@ -59,16 +61,39 @@ struct TapGemmArgs {            // x, x2, w, y, y2 are float or bf16 tensors (ke
     TapPhase ph[4];
 };
 
-// conv_wreg16.hip: the bf16 weights-in-registers kernel of the K <= 64, unit-stride 3x3 layers (the north star's 64 -> 64 block); the caller
-// (launch_tapgemm_t's SHM_TG_WREG case) has checked eligibility.  np8 = batch * (hi / 8) * (wi / 16) patches, ncu = compute units.
+// What conv_igemm.hip's tapgemm_plan decided for one product.  The launches below read no tuning knob and test no shape beyond their grid and
+// LDS sizing; the eligibility facts are here for the checks that reject a forced variant on a shape it cannot take.
+struct TapGemmPlan {
+    int variant;                  // SHM_TG_*: forced ("tapgemm.variant") or chosen
+    bool gs_fused, norm_ok;       // that kernel takes the gsum request in its epilogue / can normalise its source in LDS
+    bool halo_ok, bk32_ok, wreg_ok, wreg32_ok, phase4_ok;
+    int wreg32_wn;                // tapgemm_wreg_f32_kernel: 16-column wave tiles per block (4, 2 or 1; 0 = not that kernel's shape)
+    bool x3;                      // "conv.f32_split": shm_x3_fwd_launch in place of the variant's own kernel
+    int wreg16;                   // SHM_TG_WREG, bf16 -> bf16: 2 = shm_pp_launch, 1 = shm_wreg16_launch, 0 = the four-wave shm_wreg_launch
+};
+
+// element type as the profiler's kernel names spell it (shm_set_last_kernel)
+template <typename T>
+constexpr const char* shm_tg_name() { return sizeof(T) == 4 ? "float" : "__bf16"; }
+
+// One kernel family each, launching the form the plan chose (a.gred is null unless p.gs_fused; a.nt != null: the norm form).  dtype picks
+// the (operand, output) types: SHM_F32, SHM_BF16 or SHM_BF16_GF32.  np8 = batch * (hi / 8) * (wi / 16) patches, ncu = compute units.
+int shm_dma_launch(const TapGemmArgs& a, const TapGemmPlan& p, int nphase, int dtype, hipStream_t st, const char* who);             // conv_dma.hip: SHM_TG_DMA_*
+int shm_halo_launch(const TapGemmArgs& a, const TapGemmPlan& p, int batch, int dtype, hipStream_t st, const char* who);             // conv_halo.hip: SHM_TG_HALO*
+int shm_phase4_launch(const TapGemmArgs& a, const TapGemmPlan& p, int batch, int dtype, hipStream_t st, const char* who);           // conv_phase4.hip: SHM_TG_PHASE4
+int shm_wreg_launch(const TapGemmArgs& a, const TapGemmPlan& p, int np8, int ncu, int dtype, hipStream_t st, const char* who);      // conv_wreg.hip: SHM_TG_WREG, bf16 operands
+int shm_wreg_f32_launch(const TapGemmArgs& a, const TapGemmPlan& p, int batch, int ncu, hipStream_t st, const char* who);           // conv_wreg_f32.hip: SHM_TG_WREG, fp32
+
+// conv_wreg16.hip: the bf16 weights-in-registers kernel of the K <= 64, unit-stride 3x3 layers (the north star's 64 -> 64 block); the plan
+// (TapGemmPlan::wreg16) has checked eligibility.  np8 = batch * (hi / 8) * (wi / 16) patches, ncu = compute units.
 int shm_wreg16_launch(const TapGemmArgs& a, int np8, int ncu, hipStream_t st, const char* who);
 
 // conv_fwd_x3.hip ("conv.f32_split"): fp32 unit-stride 3x3 layers of more than 64 output channels as six bf16 MFMA products of exact three-plane
-// splits; the caller (launch_tapgemm_t) has chosen a static-tap halo variant and decided whether the gsum sums are fused
+// splits; the plan (TapGemmPlan::x3) has chosen a static-tap halo variant and decided whether the gsum sums are fused
 int shm_x3_fwd_eligible(const TapGemmArgs& a);
 int shm_x3_fwd_launch(const TapGemmArgs& a, int batch, bool gs_fused, hipStream_t st, const char* who);
 
 // conv_pingpong.hip: the K = 64 layers as a one-block-per-CU ping-pong kernel (two wave groups alternating between the MFMA segment and the
-// load / epilogue / store segment); shm_pp_eligible checks the shape, the caller that no gsum / norm form is wanted.
+// load / epilogue / store segment); shm_pp_eligible checks the shape, the plan that no gsum / norm form is wanted.
 int shm_pp_eligible(const TapGemmArgs& a);
 int shm_pp_launch(const TapGemmArgs& a, int batch, int ncu, hipStream_t st, const char* who);

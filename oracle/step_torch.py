@@ -173,8 +173,13 @@ def conv2d_transpose_same(x, w_hwoi, stride=2):
     return y[:, :, pt:pt + H, pl:pl + W]
 
 
+_IN_LOG = None         # active list (set by train_step(in_log=...)): receives every InstanceNorm block's pre-normalisation activation
+
+
 def instance_norm(x, beta):
     """tfa InstanceNormalization op chain (Generator_summary.txt:9-36), gamma == 1."""
+    if _IN_LOG is not None:
+        _IN_LOG.append(x.detach())
     mean = x.mean(dim=(2, 3), keepdim=True)
     var = ((x - mean.detach()) ** 2).mean(dim=(2, 3), keepdim=True)
     inv = torch.rsqrt(var + IN_EPS)
@@ -483,7 +488,7 @@ def _mslice(masks, lo, hi):
 
 def train_step(gvars, dvars, gbetas, dbetas, inputs, draws: StepDraws, style_factor,
                filter_size=64, dtype=torch.float64, need_grads=True, masks=None, specseg=None, attention=None,
-               xent_mode="executed", kinks=None):
+               xent_mode="executed", kinks=None, in_log=None):
     """One SHM.py:467-875 forward + both tape.gradient calls (no optimizer apply).
 
     gvars/dvars/gbetas/dbetas: lists of numpy arrays or tensors (TF layouts).
@@ -499,14 +504,17 @@ def train_step(gvars, dvars, gbetas, dbetas, inputs, draws: StepDraws, style_fac
     xent_mode: "executed" (default) = the class-logit gradient of TF's fused softmax-cross-entropy kernel
     (softmax - labels, see _XentTFFused); "intended" = the true derivative.  Only D1's label row [0,0,0,0,T] tells them apart.
     kinks: optional KinkRecorder that receives the near-kink pre-activations of every LeakyReLU of the step.
+    in_log: optional list that receives, in call order, the pre-normalisation activation (NCHW) of every InstanceNorm block of the step.
     """
-    global _KINKS
+    global _KINKS, _IN_LOG
     _KINKS = kinks
+    _IN_LOG = in_log
     try:
         return _train_step(gvars, dvars, gbetas, dbetas, inputs, draws, style_factor, filter_size, dtype, need_grads, masks,
                            specseg, attention, xent_mode, kinks)
     finally:
         _KINKS = None
+        _IN_LOG = None
 
 
 def _train_step(gvars, dvars, gbetas, dbetas, inputs, draws, style_factor, filter_size, dtype, need_grads, masks, specseg,

@@ -516,7 +516,7 @@ int shm_pp_eligible(const TapGemmArgs& a) {
 
 int shm_pp_launch(const TapGemmArgs& a, int batch, int ncu, hipStream_t st, const char* who) {
     const int npatch = batch * (a.hi / PP_PH) * (a.wi / PP_PW), nyw = a.nout / 64;
-    int gx = ncu / nyw;                  // one eight-wave block per CU
+    int gx = ncu / nyw;                  // one eight-wave block per CU.  tests/stats_ref.py (pp_per) mirrors this grid: a group adds one 256-pixel sum per patch to its fp32 statistics
     if (gx < 1) gx = 1;
     if (gx > (npatch + 1) / 2) gx = (npatch + 1) / 2;
     const bool epi = a.slope != 1.f || a.stats != nullptr || a.bias != nullptr;

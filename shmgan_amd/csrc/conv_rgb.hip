@@ -307,7 +307,7 @@ int shm_rgb_s2_fwd_launch(const void* x, int ldx, const void* wk, int K, const f
     if (gpi % unr) return 0;
     // a wave walks a run of 16-pixel groups of one image: the largest power of two up to 32 that divides the groups of an image and leaves
     // 4096 waves (four blocks per CU)
-    int gpw = unr;
+    int gpw = unr;                       // tests/stats_ref.py (rgb_groups_per_wave) mirrors this rule: the length of the fp32 statistics chain
     while (gpw < 32 && gpi % (2 * gpw) == 0 && (long)batch * (gpi / (2 * gpw)) >= 4096) gpw *= 2;
     a.groups_per_wave = gpw;
     const long waves = (long)batch * (gpi / gpw);

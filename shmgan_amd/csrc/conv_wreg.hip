@@ -463,7 +463,7 @@ static void wreg_launch_t(const TapGemmArgs& a, const TapGemmPlan& p, dim3 grid,
 
 int shm_wreg_launch(const TapGemmArgs& a, const TapGemmPlan& p, int np8, int ncu, int dtype, hipStream_t st, const char* who) {
     const int ny = shm_cdiv(a.nout, 64);
-    int gx = 2 * ncu / ny;             // two 4-wave blocks per CU (LDS, VGPRs)
+    int gx = 2 * ncu / ny;             // two 4-wave blocks per CU (LDS, VGPRs).  tests/stats_ref.py (wreg_per) mirrors this grid: a lane adds one 32-value sum per patch to its fp32 statistics
     if (gx < 1) gx = 1;
     if (gx > np8) gx = np8;
     const dim3 grid(gx, ny, 1);

@@ -289,7 +289,7 @@ __global__ __launch_bounds__(512, 4) void tapgemm_wreg16_bf16_kernel(const TapGe
 
 int shm_wreg16_launch(const TapGemmArgs& a, int np8, int ncu, hipStream_t st, const char* who) {
     const int nyw = a.nout / 64;
-    int gxw = 2 * ncu / nyw;            // two eight-wave blocks per CU (68 KiB of LDS, 128 VGPRs each)
+    int gxw = 2 * ncu / nyw;            // two eight-wave blocks per CU (68 KiB of LDS, 128 VGPRs each).  tests/stats_ref.py (wreg_per) mirrors this grid: patches per block = length of the fp32 statistics chain
     if (gxw < 1) gxw = 1;
     if (gxw > np8) gxw = np8;
     static const hipError_t at16 = [] {

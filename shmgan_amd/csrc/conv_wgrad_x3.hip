@@ -271,10 +271,11 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo_x3_kernel(const WgradHaloAr
     }
 }
 
-int shm_wgrad_x3_launch(const WgradHaloArgs& hgs, int cin, int cout, int nsplit, int rows, hipStream_t st, bool stride2) {
-    const dim3 grid(shm_cdiv(cin, 64), shm_cdiv(cout, 64), nsplit);
+int shm_wgrad_x3_launch(const WgradHaloArgs& hgs, const WgradPlan& p, hipStream_t st) {
+    const dim3 grid(shm_cdiv(hgs.cin, 64), shm_cdiv(hgs.cout, 64), p.splits);
+    const int rows = p.rows;
     const bool nm = hgs.nt != nullptr;               // SHM_NORM_EXACT source
-    if (stride2) {
+    if (p.stride2) {
         constexpr unsigned kLds = (3u * 180 + 3u * 32) * 128u;       // 79.5 KiB: two blocks per CU, just
         SHM_REQUIRE(!nm && rows == 2, SHM_E_SHAPE, "shm_conv2d_wgrad: the stride-2 x3 form takes plain sources and stages of two rows");
         static const hipError_t attr = hipFuncSetAttribute((const void*)wgrad_halo_x3_kernel<2, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);

@@ -1,5 +1,6 @@
-// Shared pieces of the weight-gradient kernels (conv_wgrad.hip, conv_wgrad_x3.hip): block order, the halo kernels' argument block, the
-// transposed bf16 fragment read.  See conv_wgrad.hip for the kernels' descriptions.
+// Shared pieces of the weight-gradient kernels: block order, the argument blocks, the transposed bf16 fragment read, the launcher's plan, and
+// the launch function each kernel family's translation unit sits behind (conv_wgrad_gen.hip, conv_wgrad_halo.hip, conv_wgrad_halo16.hip,
+// conv_wgrad_halo8.hip, conv_wgrad_x3.hip).  conv_wgrad.hip has the entry points, the plan (wgrad_plan) and the launcher: see its header comment.
 #pragma once
 #include "common.h"
 #include "ablate.h"
@@ -26,6 +27,21 @@ __device__ __forceinline__ Blk3 xcd_block_order() {
 }
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+struct WgradArgs {            // x, x2, dy: float (wgrad_kernel) or bf16 (wgrad_bf16_kernel) tensors
+    const void* x;
+    const void* x2;
+    int c1, ldx, ldx2;
+    const void* dy;
+    int lddy;
+    float* part;
+    int hi, wi, ho, wo;
+    int cin_ld, cin, cout;
+    int is, ntaps;
+    int dh[9], dw[9];
+    int M, pix_per_split;
+    unsigned xbytes, x2bytes, dybytes;
+};
 
 struct WgradHaloArgs {
     const void* x;
@@ -60,8 +76,63 @@ __device__ __forceinline__ bf16x8 tr_frag(const unsigned short* base) {
     return __builtin_bit_cast(bf16x8, v);
 }
 
+// A 16-byte global load the COMPILER does not see as a vector-memory operation (inline asm, drained on the spot).  The table
+// registers of the NM kernels are re-read when a block moves on to the next image, i.e. under a branch: as plain loads hipcc has
+// to assume them outstanding at every later use and puts s_waitcnt vmcnt(0) in front of each normalisation -- which also waits
+// for the LDS-DMA of the stage just issued, in the middle of the MFMA stream (measured: +6-10 % on the kernel).
+__device__ __forceinline__ f32x4 load16_drained(const float* p) {
+    f32x4 v;
+    asm volatile("global_load_dwordx4 %0, %1, off\n\ts_waitcnt vmcnt(0)" : "=&v"(v) : "v"(p) : "memory");
+    return v;
+}
+
+// What the shape-only sizing of shm_conv2d_wgrad_workspace allows for beside the split-K target (the plan uses the same constants)
+constexpr int kWgradThinRows = 96;          // wgrad_halo_thin_kernel: 9 * cin packed MFMA rows at most ...
+constexpr int kWgradThinSlabs = 2;          // ... and two slabs per split (one per patch row)
+constexpr int kWgradRgbRows = 32;           // conv3x3s2_rgb_wgrad_kernel (conv_rgb.hip): 9 * cin at most ...
+constexpr int kWgradRgbSlabs = 1024;        // ... and one slab per block, streaming -- blocks are what it needs
+constexpr int kWgradHalo8CoTiles = 2;       // wgrad_halo8_bf16_kernel: a block owns two 64-wide co tiles -- half as many (ci, co) tiles, twice the splits for a given block target
+
+enum {
+    SHM_WG_GEN,           // wgrad_kernel / wgrad_bf16_kernel <ntaps, straddle>
+    SHM_WG_HALO,          // wgrad_halo_kernel <nmode> or, stride2, <0, true>
+    SHM_WG_THIN,          // wgrad_halo_thin_kernel <thin_nrt, thin_is>
+    SHM_WG_HALO16,        // wgrad_halo_bf16_kernel <rows, nmode>
+    SHM_WG_HALO8,         // wgrad_halo8_bf16_kernel <mode8>
+    SHM_WG_X3,            // wgrad_halo_x3_kernel <rows, nmode == 1, stride2>
+};
+
+// What conv_wgrad.hip's wgrad_plan decided for one weight gradient.  The launches below read no tuning knob and test no shape beyond their grid.
+struct WgradPlan {
+    int family;                   // SHM_WG_*
+    bool bf16;                    // operand type (SHM_WG_GEN: which of the two kernels)
+    int ntaps;                    // ksize * ksize
+    bool straddle;                // a 64-channel ci tile holds channels of both concat sources (generic kernels only)
+    int rows;                     // pixel rows per stage (SHM_WG_HALO16, SHM_WG_X3: 2 or 4)
+    int nmode;                    // 0 = plain source, 1 + SHM_NORM_* = the source is normalised in LDS
+    bool stride2;                 // SHM_WG_HALO, SHM_WG_X3: the stride-2 form
+    int mode8;                    // SHM_WG_HALO8: MODE
+    int thin_nrt, thin_is;        // SHM_WG_THIN: row tiles, conv stride
+    bool try_rgb;                 // shm_rgb_s2_wgrad_launch (conv_rgb.hip) is tried first; it has its own eligibility and split
+    // the split: patches of prow x pcol pixels of the output map (over_out) or the input map; the generic kernels cut pixels (1 x 1 "patches",
+    // patches_per_split = WgradArgs::pix_per_split)
+    int prow, pcol;
+    bool over_out;
+    int npatch, patches_per_split;
+    int splits;                   // grid z
+    int nsplit;                   // slabs written = what *nsplit_out receives (SHM_WG_THIN: kWgradThinSlabs per split)
+    size_t early_bytes;           // the workspace of the uncut split-K target: asked of every call, before the RGB kernel is tried
+    size_t ws_bytes;              // workspace the launch needs: max(early_bytes, nsplit slabs)
+    bool norm_ok;                 // this shape's kernel can normalise its source in LDS
+};
+
+// One kernel family each, launching the form the plan chose on a grid of (cin / 64, cout / 64 or 128, p.splits) blocks
+int shm_wgrad_gen_launch(const WgradArgs& a, const WgradPlan& p, hipStream_t st);             // conv_wgrad_gen.hip: SHM_WG_GEN
+int shm_wgrad_halo_launch(const WgradHaloArgs& a, const WgradPlan& p, hipStream_t st);        // conv_wgrad_halo.hip: SHM_WG_HALO, SHM_WG_THIN
+int shm_wgrad_halo16_launch(const WgradHaloArgs& a, const WgradPlan& p, hipStream_t st);      // conv_wgrad_halo16.hip: SHM_WG_HALO16
+int shm_wgrad_halo8_launch(const WgradHaloArgs& a, const WgradPlan& p, hipStream_t st);       // conv_wgrad_halo8.hip: SHM_WG_HALO8
 
 // conv_wgrad_x3.hip ("wgrad.f32_split" = 1): the fp32 3x3 unit-stride weight gradient as six bf16 MFMA products of three-plane splits of x and dY.
-// hgs as for wgrad_halo_kernel<0> with patches of rows x 16 pixels (rows = 2 or 4); grid = (cin / 64, cout / 64, splits).
-// stride2: patches of 2 x 16 OUTPUT pixels of a 3x3 stride-2 layer on an even map (hgs as for wgrad_halo_kernel<0, true>, re-cut to that patch)
-int shm_wgrad_x3_launch(const WgradHaloArgs& hgs, int cin, int cout, int nsplit, int rows, hipStream_t st, bool stride2 = false);
+// hgs as for wgrad_halo_kernel<0> with patches of p.rows x 16 pixels (2 or 4); grid = (cin / 64, cout / 64, p.splits).
+// p.stride2: patches of 2 x 16 OUTPUT pixels of a 3x3 stride-2 layer on an even map (hgs as for wgrad_halo_kernel<0, true>, cut to that patch)
+int shm_wgrad_x3_launch(const WgradHaloArgs& hgs, const WgradPlan& p, hipStream_t st);        // SHM_WG_X3

@@ -1,5 +1,5 @@
-"""Host-side logic of the consumer-side InstanceNorm fold that needs no GPU: the eligibility queries are dry runs of the launchers'
-variant choice (include/shmgan_hip.h: shm_conv2d_norm_supported, shm_conv2d_wgrad_norm_supported), the scaled mode's workspace query
+"""Host-side logic of the consumer-side InstanceNorm fold that needs no GPU: the eligibility queries ask the launchers'
+plans (tapgemm_plan, wgrad_plan) (include/shmgan_hip.h: shm_conv2d_norm_supported, shm_conv2d_wgrad_norm_supported), the scaled mode's workspace query
 and the argument checks of the new entry points.  (What the kernels compute is tests/test_norm_fold_gpu.py.)"""
 import ctypes
 

@@ -22,7 +22,7 @@ int shm_rgb_s2_fwd_launch(const void* x, int ldx, const void* wk, int K, const f
 int shm_rgb_s2_wgrad_launch(const void* x, int ldx, const void* dy, int lddy, float* part, size_t ws_bytes, int batch, int hi, int wi, int cin, int cout,
                             size_t xbytes, size_t dybytes, int dtype, int* nsplit_out, hipStream_t st);
 
-// instnorm.hip / instnorm_bwd.hip, for the composite convolution entry points of conv_igemm.hip: the finalize pass of the statistics a convolution's epilogue
+// instnorm.hip / grad_sums.hip, for the composite convolution entry points of conv_igemm.hip: the finalize pass of the statistics a convolution's epilogue
 // summed (shm_conv2d_in_fwd), and the stand-alone (sum g, sum g * aux) pass behind a kernel without a gsum epilogue (shm_conv2d_*_gsum)
 int shm_in_finalize_internal(double* stats, double* part, int nslot, int total, int hw, double eps, float* nt, const float* beta, int c, hipStream_t st);
 int shm_gsum_reduce_internal(const void* g, int ldg, const void* aux, int ldaux, double* red, int batch, int hw, int c, int dtype, hipStream_t st);

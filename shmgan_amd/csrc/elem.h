@@ -1,4 +1,5 @@
-// Helpers shared by the HBM-bound kernels around the convolutions (elem.hip, instnorm.hip, instnorm_bwd.hip, heads.hip, dgrad_sum1.hip).
+// Helpers shared by the HBM-bound kernels around the convolutions (elem.hip, instnorm.hip, the InstanceNorm-backward
+// families behind in_bwd.h -- instnorm_bwd_2pass.hip, instnorm_bwd_fused8.hip, instnorm_bwd_fusedg.hip, grad_sums.hip --, heads.hip, dgrad_sum1.hip).
 //
 // Layout: NHWC with a channel pitch; every thread moves 16 bytes (4 channels of one
 // pixel); a block covers PP = 256/(C/4) pixels per iteration, so a wave reads whole

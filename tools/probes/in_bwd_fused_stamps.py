@@ -1,4 +1,4 @@
-"""Phase stamps of in_bwd_fused8_kernel (timing-only build of instnorm_bwd.hip with -DSHM_FUSED_STAMP, loaded through SHM_LIB_PATH): per block
+"""Phase stamps of in_bwd_fused8_kernel (timing-only build of instnorm_bwd_fused8.hip with -DSHM_FUSED_STAMP, loaded through SHM_LIB_PATH): per block
 start, slices loaded, rows written, arrival counted, released, phase 2 stores issued, departure counted, end -- microseconds from the first start.
 
     python tools/probes/in_bwd_fused_stamps.py [n,h,c]"""
@@ -11,13 +11,13 @@ sys.path.insert(0, str(ROOT))
 so = ROOT / "build_ab" / "libshm_fused_stamp.so"
 if "SHM_LIB_PATH" not in os.environ:
     from shmgan_amd import _lib
-    if not so.exists() or so.stat().st_mtime < (_lib.CSRC / "instnorm_bwd.hip").stat().st_mtime:
+    if not so.exists() or so.stat().st_mtime < (_lib.CSRC / "instnorm_bwd_fused8.hip").stat().st_mtime:
         so.parent.mkdir(exist_ok=True)
         _lib.build()
         obj = so.parent / (so.stem + ".o")
         flags = [f for f in _lib.HIPCC_FLAGS if f != "-shared"]
-        subprocess.run(["/opt/rocm/bin/hipcc", *flags, "-DSHM_FUSED_STAMP", "-c", str(_lib.CSRC / "instnorm_bwd.hip"), "-o", str(obj)], check=True)
-        objs = [str(obj) if s == "instnorm_bwd.hip" else str(_lib.CSRC / "_obj" / (Path(s).stem + ".o")) for s in _lib.SOURCES]
+        subprocess.run(["/opt/rocm/bin/hipcc", *flags, "-DSHM_FUSED_STAMP", "-c", str(_lib.CSRC / "instnorm_bwd_fused8.hip"), "-o", str(obj)], check=True)
+        objs = [str(obj) if s == "instnorm_bwd_fused8.hip" else str(_lib.CSRC / "_obj" / (Path(s).stem + ".o")) for s in _lib.SOURCES]
         subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-fPIC", "-shared", *objs, "-o", str(so)], check=True)
     if "--build-only" in sys.argv:
         sys.exit(0)

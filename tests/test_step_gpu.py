@@ -8,6 +8,7 @@ import torch
 
 from oracle import specseg_torch as sp
 from oracle import step_torch as st
+from loss_edge_ref import dhead_oracle, image_inputs_random, image_oracle
 from util import check_grad_fixture as _check_grad_fixture, pin_kinks as _pin_kinks, cosine, dev, host, rel_l2, t64
 
 pytestmark = pytest.mark.gpu
@@ -22,25 +23,8 @@ def test_dhead_losses(mode):
     B, npatch, T = 3, 4, 1.07
     rf = rng.standard_normal((12 * B, npatch))
     cls = rng.standard_normal((12 * B, 5))
-    rft, clst = t64(rf).requires_grad_(True), t64(cls).requires_grad_(True)
-    sl = lambda g, k=0: slice((g + k) * B, (g + k + 1) * B)       # group start in units of B
-    mse = lambda a, t: ((a - t) ** 2).mean(dim=1)
-    def xent(lg, k, w=1.0):
-        lab = torch.zeros_like(lg)
-        lab[:, k] = w
-        return st.softmax_xent(lg, lab, mode)
-    D1, D2 = sl(0), sl(6)
-    D3 = [sl(1, k) for k in range(5)]
-    D4 = [sl(7, k) for k in range(5)]
-    D1_RF, D3_RF = mse(rft[D1], T), sum(mse(rft[s], T) for s in D3)
-    D2_RF = mse(rft[D2], T) + (rft[D1] ** 2).mean(dim=1)
-    D4_RF = sum(mse(rft[D4[k]], T) + (rft[D3[k]] ** 2).mean(dim=1) for k in range(5)) + D2_RF
-    D1_c, D3_c = xent(clst[D1], 4, T), sum(xent(clst[D3[k]], k) for k in range(5))
-    D4_c = sum(xent(clst[D4[k]], k) for k in range(5))
-    tot_d = ((D1_c + D3_c) / 6 + (D2_RF + D4_RF) / 6 + 0.5 * D4_c + 10 * D4_c).mean()
-    tot_g = ((D1_RF + D3_RF) / 6).mean()
-    gd_rf, gd_cls = torch.autograd.grad(tot_d, [rft, clst], retain_graph=True)
-    gg_rf, = torch.autograd.grad(tot_g, [rft])
+    o = dhead_oracle(rf, cls, B, T, mode)          # the oracle's composition of the head losses (loss_edge_ref.py)
+    gd_rf, gd_cls, gg_rf = t64(o.gd_rf), t64(o.gd_cls), t64(o.gg_rf)
     loss = torch.empty(16, dtype=torch.float64, device="cuda")
     drf_d = torch.empty((12 * B, npatch), device="cuda")
     dcls_d = torch.empty((12 * B, 5), device="cuda")
@@ -59,37 +43,20 @@ def test_dhead_losses(mode):
     assert np.abs(diff[:B] - want).max() < 1e-6 and np.abs(diff[B:]).max() == 0.0
     with pytest.raises(RuntimeError):
         ops.dhead_losses(dev(rf), dev(cls), loss, drf_d, other, drf_g, B, npatch, T, 7)
-    assert rel_l2(host(drf_g), gg_rf.numpy()[:6 * B]) < 1e-5
+    assert rel_l2(host(drf_g), gg_rf.numpy()) < 1e-5
     L = host(loss)
-    ref = [D1_RF.sum(), D3_RF.sum(), (rft[D1] ** 2).mean(dim=1).sum(),
-           sum((rft[s] ** 2).mean(dim=1) for s in D3).sum(), mse(rft[D2], T).sum(),
-           sum(mse(rft[s], T) for s in D4).sum(), D1_c.sum(), D3_c.sum(), D4_c.sum()]
-    assert rel_l2(L[:9], [float(r.detach()) for r in ref]) < 1e-5
+    assert rel_l2(L[:9], o.slots) < 1e-5
 
 
 @pytest.mark.parametrize("B,S,flags", [(1, 32, (False, True, False, False, False)), (2, 48, (True, False, False, True, False))])
 def test_image_losses(B, S, flags):
     from shmgan_amd import ops
-    rng = np.random.default_rng(21)
-    npix = S * S
-    orig = [rng.random((B, S, S, 3)) for _ in range(5)]
-    ds = [st.per_image_standardization(st.rgb_to_yuv(t64(o)))[0] for o in orig]
-    cbcr = sum(d[..., 1:] for d in ds) / 5.0
-    gen_y = t64(rng.standard_normal((B, S, S, 1)) * 0.5 + 1.0).requires_grad_(True)
-    cyc_y = t64(rng.standard_normal((5 * B, S, S, 1)) * 0.5 + 1.0).requires_grad_(True)
-    gen_rgb = st.yuv_to_rgb(torch.cat([gen_y, cbcr], 3))
-    cyuv = [torch.cat([cyc_y[k * B:(k + 1) * B], cbcr], 3) for k in range(5)]
-    crgb = [st.yuv_to_rgb(c) for c in cyuv]
+    # the inputs and the oracle's composition of the image losses (loss_edge_ref.py)
+    inp = image_inputs_random(B, S, seed=21)
+    o = image_oracle(inp, flags, sf=3.0e-3)          # a style factor large enough that the style term is visible in the gradient
+    orig, ds, cbcr, cyc_y, sf = inp.orig, inp.ds, inp.cbcr, o.cyc_y, 3.0e-3
+    gen_rgb, crgb, ssims, sl, content, style, rg, rc = o.gen_rgb, o.crgb, o.ssims, o.sl, o.content, o.style, o.rg, o.rc
     l1 = lambda a, b: (a - b).abs().mean(dim=(1, 2, 3))
-    L1 = (sum(l1(crgb[k], t64(orig[k])) for k in range(4)) + l1(gen_rgb, t64(orig[4]))) / 5 + 10 * l1(crgb[4], t64(orig[4]))
-    ssims = [st.ssim(st.rescale_01(cyuv[k]), st.rescale_01(ds[k])) for k in range(5)]
-    sl = [torch.zeros(B, dtype=torch.float64) if flags[k] else -torch.log((1 + ssims[k]) / 2) for k in range(5)]
-    ssim_loss = (sl[0] + sl[1] + sl[2] + sl[3] + 10 * sl[4]) / 5
-    sf = 3.0e-3          # large enough that the style term is visible in the gradient
-    content = ((cyuv[4] - ds[0]) ** 2).mean(dim=(1, 2, 3))
-    style = sf * ((st.gram_matrix(cyuv[4]) - st.gram_matrix(ds[4])) ** 2).mean(dim=(1, 2))
-    tot = (10 * L1 + 10 * ssim_loss + 10 * (100 * style + content)).mean()
-    rg, rc = torch.autograd.grad(tot, [gen_y, cyc_y])
 
     fmask = sum(1 << k for k in range(5) if flags[k])
     od = [dev(o) for o in orig]

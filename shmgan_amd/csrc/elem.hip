@@ -10,7 +10,7 @@ extern "C" int shm_zero(void* p, size_t bytes, void* stream) {
 
 __global__ void cvt_f64_f32_kernel(const double* __restrict__ s, float* __restrict__ d, size_t n, int acc) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) d[i] = (acc ? d[i] : 0.f) + (float)s[i];
+    if (i < n) d[i] = acc ? d[i] + (float)s[i] : (float)s[i];          // not 0.f + v: that would turn v = -0.0 into +0.0
 }
 
 extern "C" int shm_cvt_f64_f32(const double* src, float* dst, size_t n, int accumulate, void* stream) {

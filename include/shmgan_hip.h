@@ -716,6 +716,64 @@ int shm_tensor_stats(const float* x, size_t n, const size_t* seg_off, const size
 int shm_loss_ring_put(const double* dl, const double* il, const double* sl, const void* abort_word, double* ring, int rows,
                       int row, long long step, void* stream);
 
+/* ---- training the SpecSeg mask network (specseg_train.hip) -----------------------------------------------------------------------
+ * The reference builds SpecSeg's optimiser (SHM.py:175) and a Dice + focal loss with IoU / F-score metrics (SpecSeg.py:92-96) and
+ * runs neither; its checkpoint is not available, so the weights are made here.  fp32 tensors only.  The 3x3 convolutions' gradients
+ * are shm_conv2d_dgrad / shm_conv2d_wgrad, ReLU's is shm_lrelu_bwd at slope 0, Dropout is shm_keep_mask / shm_mul_mask.  Every
+ * reduction below keeps f64 partial sums in a workspace slot per block and adds the slots in a fixed order: no global atomics, results
+ * bitwise the same from run to run.  Workspaces need no initial contents and are 16-byte aligned.  All shape errors are SHM_E_SHAPE
+ * and a short workspace SHM_E_WORKSPACE, before any launch. */
+#define SHM_SST_MAX_BLOCKS 256
+/* f64 elements of the workspace of shm_bn_train_fwd / shm_bn_train_bwd / shm_head_logit_bwd on c channels */
+#define SHM_BN_TRAIN_WS_DOUBLES(c) ((size_t)SHM_SST_MAX_BLOCKS * 2 * (c) + 2 * (size_t)(c))
+/* Keras BatchNormalization(axis=-1) in training mode over the npix = N*H*W pixels of a [npix, c] (pitch lda): per channel
+ * mean and the biased variance var, in two passes (sum, then sum of squared deviations from the f64 mean: data with |mean| >> std
+ * does not cancel); out = (a - mean) * gamma / sqrt(var + eps) + beta.  save (f64 [2c]) receives mean [c] and 1 / sqrt(var + eps) [c]
+ * for the backward.  moving_mean / moving_var (may be NULL) are updated in place: moving = moving * momentum + value * (1 - momentum),
+ * where the variance's value is the unbiased estimate var * npix / max(npix - 1, 1) (TensorFlow's fused kernel).  c a power of two
+ * in 16..256, pitches multiples of 4. */
+int shm_bn_train_fwd(const float* a, int lda, const float* gamma, const float* beta, float* moving_mean, float* moving_var,
+                     float momentum, float eps, float* out, int ldo, double* save, double* ws, size_t ws_bytes, size_t npix, int c,
+                     void* stream);
+/* Its backward, with xhat = (a - mean) * inv_std from `save`: dbeta = sum dy, dgamma = sum dy * xhat (both overwritten),
+ * dx = gamma * inv_std * (dy - mean(dy) - xhat * mean(dy * xhat)).  dx may be dy when their pitches agree. */
+int shm_bn_train_bwd(const float* dy, int lddy, const float* a, int lda, const float* gamma, const double* save, float* dx, int lddx,
+                     float* dgamma, float* dbeta, double* ws, size_t ws_bytes, size_t npix, int c, void* stream);
+/* MaxPooling2D((2,2)) backward on even sizes: x [batch,h,w,c] is the pool's input, dy [batch,h/2,w/2,c] its output gradient.  The
+ * gradient of each window goes to the window's FIRST maximum in row-major order ((0,0), (0,1), (1,0), (1,1)), recomputed from x;
+ * the other three positions get 0.  accumulate != 0: dx += (the skip gradient is already there), else dx is overwritten. */
+int shm_maxpool2_bwd(const float* x, int ldx, const float* dy, int lddy, float* dx, int lddx, int batch, int h, int w, int c,
+                     int accumulate, void* stream);
+/* Conv2DTranspose(k=2, strides=2) backward; w = Keras layout [2][2][cout][cin] as stored, dy [batch,2hi,2wi,cout], x and dx
+ * [batch,hi,wi,cin]; cout a multiple of 16, cin a multiple of 32, any hi, wi >= 1.  v_mfma_f32_16x16x4_f32 GEMMs, LDS-staged.
+ *   dgrad  dx[a,b,ci] = sum_{p,q,co} dy[2a+p,2b+q,co] * w[p,q,co,ci]
+ *   wgrad  dw[p,q,co,ci] = sum_{n,a,b} dy[n,2a+p,2b+q,co] * x[n,a,b,ci] (split over the pixels, the splits added in split order);
+ *          dbias[co] (may be NULL; cout a power of two in 16..256) = sum over every pixel of dy.  Both overwritten. */
+int shm_conv2d_transpose2x2_dgrad(const float* dy, int lddy, const float* w, float* dx, int lddx, int batch, int hi, int wi,
+                                  int cin, int cout, void* stream);
+size_t shm_conv2d_transpose2x2_wgrad_workspace(int batch, int hi, int wi, int cin, int cout);
+int shm_conv2d_transpose2x2_wgrad(const float* x, int ldx, const float* dy, int lddy, float* dw, float* dbias, void* ws,
+                                  size_t ws_bytes, int batch, int hi, int wi, int cin, int cout, void* stream);
+/* The head Conv2D(1, (1,1)) without its sigmoid: z[p] = sum_c x[p,c] w[c] + bias (shm_head_sigmoid_fwd stays what predict uses). */
+int shm_head_logit_fwd(const float* x, int ldx, const float* w, const float* bias, float* z, size_t npix, int c, void* stream);
+/* Its backward: dx[p,c] = dz[p] w[c], dw[c] = sum_p dz[p] x[p,c], db = sum_p dz[p] (all overwritten);
+ * ws = SHM_BN_TRAIN_WS_DOUBLES(c) f64. */
+int shm_head_logit_bwd(const float* x, int ldx, const float* w, const float* dz, float* dx, int lddx, float* dw, float* db,
+                       double* ws, size_t ws_bytes, size_t npix, int c, void* stream);
+/* Dice + binary focal loss of the logits z [npix] against the target g [npix] in [0, 1], over the whole batch, p = sigmoid(z):
+ *   dice  = 1 - (2 sum(g p) + s) / (sum(p) + sum(g) + s),  s = 1e-5
+ *   focal = mean(-g 0.25 (1-p)^2 log p - (1-g) 0.75 p^2 log(1-p)),  log p = -softplus(-z), log(1-p) = -softplus(z)
+ *   tp = sum g [z > 0], fp = sum (1-g) [z > 0], fn = sum g [z <= 0]  (p > 0.5 <=> z > 0);
+ *   iou = (tp + s) / (tp + fp + fn + s), f1 = (2 tp + s) / (2 tp + fp + fn + s)
+ * out (f64 [SHM_SEG_LOSS_OUT]) = {dice + focal, dice, focal, iou, f1, tp, fp, fn}; dz (may be NULL: evaluation) = d(dice + focal)/dz.
+ * Per-pixel arithmetic in f64: finite values and gradients at |z| = 40.  ws = SHM_SEG_LOSS_WS_DOUBLES f64. */
+#define SHM_SEG_LOSS_OUT 8
+#define SHM_SEG_LOSS_WS_DOUBLES ((size_t)SHM_SST_MAX_BLOCKS * 7 + 8)
+int shm_seg_loss(const float* z, const float* g, float* dz, double* out, double* ws, size_t ws_bytes, size_t npix, void* stream);
+/* shm_adam_clip with the clip bound as an argument (clip <= 0: no clip) and no abort word; clip = 1 gives shm_adam_clip's bits. */
+int shm_adam(float* w, float* m, float* v, const float* g, size_t n, float alpha, float beta1, float beta2, float eps,
+             float gscale, float clip, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

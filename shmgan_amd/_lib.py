@@ -16,7 +16,7 @@ _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ["SHM_LIB_PATH"]) if os.environ.get("SHM_LIB_PATH") else _HERE / "libshmgan_hip.so"
 CSRC = _HERE / "csrc"
 HEADER = _HERE.parent / "include" / "shmgan_hip.h"
-SOURCES = ["runtime.hip", "conv_igemm.hip", "conv_dma.hip", "conv_halo.hip", "conv_wreg.hip", "conv_wreg_f32.hip", "conv_phase4.hip", "conv_wreg16.hip", "conv_pingpong.hip", "conv_wgrad.hip", "conv_wgrad_gen.hip", "conv_wgrad_halo.hip", "conv_wgrad_halo16.hip", "conv_wgrad_halo8.hip", "conv_wgrad_x3.hip", "conv_fwd_x3.hip", "conv_rgb.hip", "elem.hip", "instnorm.hip", "instnorm_bwd.hip", "instnorm_bwd_2pass.hip", "instnorm_bwd_fused8.hip", "instnorm_bwd_fusedg.hip", "grad_sums.hip", "heads.hip", "dgrad_sum1.hip", "color.hip", "imgloss.hip", "metrics.hip", "specseg.hip", "data.hip", "polar.hip", "export.hip", "telemetry.hip"]
+SOURCES = ["runtime.hip", "conv_igemm.hip", "conv_dma.hip", "conv_halo.hip", "conv_wreg.hip", "conv_wreg_f32.hip", "conv_phase4.hip", "conv_wreg16.hip", "conv_pingpong.hip", "conv_wgrad.hip", "conv_wgrad_gen.hip", "conv_wgrad_halo.hip", "conv_wgrad_halo16.hip", "conv_wgrad_halo8.hip", "conv_wgrad_x3.hip", "conv_fwd_x3.hip", "conv_rgb.hip", "elem.hip", "instnorm.hip", "instnorm_bwd.hip", "instnorm_bwd_2pass.hip", "instnorm_bwd_fused8.hip", "instnorm_bwd_fusedg.hip", "grad_sums.hip", "heads.hip", "dgrad_sum1.hip", "color.hip", "imgloss.hip", "metrics.hip", "specseg.hip", "data.hip", "polar.hip", "export.hip", "telemetry.hip", "specseg_train.hip"]
 # headers every source may include: a change of any of them rebuilds every object (tools/sanitize_host.py goes by the same list)
 SHARED_HEADERS = [CSRC / "common.h", CSRC / "elem.h", CSRC / "ablate.h", CSRC / "tapgemm.h", CSRC / "tapgemm_dev.h", CSRC / "wgrad.h", CSRC / "in_bwd.h", CSRC / "x3split.h", HEADER]
 F32, BF16 = 0, 1                 # SHM_F32 / SHM_BF16 of include/shmgan_hip.h
@@ -119,6 +119,16 @@ SIGNATURES = {
     "shm_tensor_stats_workspace": (Z, [I, Z]),
     "shm_tensor_stats": (I, [P, Z, P, P, I, F, P, P, P, Z, P]),
     "shm_loss_ring_put": (I, [P, P, P, P, P, I, I, C.c_longlong, P]),
+    "shm_bn_train_fwd": (I, [P, I, P, P, P, P, F, F, P, I, P, P, Z, Z, I, P]),
+    "shm_bn_train_bwd": (I, [P, I, P, I, P, P, P, I, P, P, P, Z, Z, I, P]),
+    "shm_maxpool2_bwd": (I, [P, I, P, I, P, I, I, I, I, I, I, P]),
+    "shm_conv2d_transpose2x2_dgrad": (I, [P, I, P, P, I, I, I, I, I, I, P]),
+    "shm_conv2d_transpose2x2_wgrad_workspace": (Z, [I, I, I, I, I]),
+    "shm_conv2d_transpose2x2_wgrad": (I, [P, I, P, I, P, P, P, Z, I, I, I, I, I, P]),
+    "shm_head_logit_fwd": (I, [P, I, P, P, P, Z, I, P]),
+    "shm_head_logit_bwd": (I, [P, I, P, P, P, I, P, P, P, Z, Z, I, P]),
+    "shm_seg_loss": (I, [P, P, P, P, P, Z, Z, P]),
+    "shm_adam": (I, [P, P, P, P, Z, F, F, F, F, F, F, P]),
 }
 
 def header_functions():

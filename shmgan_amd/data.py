@@ -198,6 +198,62 @@ def datasetLoad(trainer, subdirs=PSD_SUBDIRS, flip_ud=True):
     return trainer.length_dataset, ds
 
 
+class MaskDataset:
+    """Image / mask pairs for SpecSeg training (SpecSeg.fit, trainer.train_specseg): the files of `image_dir` and `mask_dir` are
+    paired by name (the stem, whatever the extension; a file without its partner raises).  Images are decoded to RGB, resized with
+    shm_resize_bilinear_u8 (the training loader's kernel), and go through shm_rgb2yuv_std; the standardised Y plane is kept --
+    exactly what train_step feeds `SpecSeg.predict`.  Masks are decoded to one channel, resized the same way and divided by 255:
+    soft values at the resized edges, not thresholded.  flip_ud flips image and mask alike.  The whole set is held on the device
+    ([N,S,S,1] each): mask sets are small next to the polarimetric data."""
+
+    def __init__(self, image_dir, mask_dir, image_size, batch_size=1, flip_ud=False, device=None):
+        imgs = {Path(p).stem: p for p in list_images(image_dir)}
+        masks = {Path(p).stem: p for p in list_images(mask_dir)}
+        if set(imgs) != set(masks) or not imgs:
+            raise ValueError(f"{image_dir} and {mask_dir} must hold the same, non-empty set of names; without a partner: "
+                             f"{sorted(set(imgs) ^ set(masks))[:8]}")
+        self.names = sorted(imgs)
+        self.files = [(imgs[n], masks[n]) for n in self.names]
+        self.S, self.B, self.flip_ud, self._dev, self._xy = int(image_size), int(batch_size), bool(flip_ud), device, None
+
+    @property
+    def dev(self):
+        if self._dev is None:
+            self._dev = torch.device("cuda", torch.cuda.current_device())
+        return torch.device(self._dev)
+
+    def __len__(self):
+        return -(-len(self.files) // self.B)
+
+    @staticmethod
+    def _decode(path, mode):
+        from PIL import Image
+        with Image.open(path) as im:
+            a = np.asarray(im.convert(mode), dtype=np.uint8)
+        return torch.from_numpy(np.ascontiguousarray(a.reshape(a.shape[0], a.shape[1], -1)))
+
+    def tensors(self):
+        """(x, y): the standardised Y planes and the masks, float32 [N,S,S,1] on the device (loaded once)."""
+        if self._xy is None:
+            N, S = len(self.files), self.S
+            rgb = torch.empty((N, S, S, 3), device=self.dev)
+            y = torch.empty((N, S, S, 1), device=self.dev)
+            for k, (fi, fm) in enumerate(self.files):
+                ops.resize_bilinear_u8(self._decode(fi, "RGB").to(self.dev), rgb[k], 1.0 / 255.0, self.flip_ud)
+                ops.resize_bilinear_u8(self._decode(fm, "L").to(self.dev), y[k], 1.0 / 255.0, self.flip_ud)
+            yuv = torch.empty_like(rgb)
+            acc = torch.zeros(2 * N, dtype=torch.float64, device=self.dev)
+            scale = torch.empty(N, device=self.dev)
+            ops.rgb2yuv_std(rgb, yuv, acc, scale, N, S * S)
+            self._xy = (yuv[..., 0:1].contiguous(), y)
+        return self._xy
+
+    def __iter__(self):
+        x, y = self.tensors()
+        for b0 in range(0, len(self.files), self.B):
+            yield x[b0:b0 + self.B], y[b0:b0 + self.B]
+
+
 def eval_file_lists(test_dir, diffuse_dir=None):
     """File lists of the evaluation loader: the sorted flat `test_dir` and, when given, the sorted flat `diffuse_dir`
     (None otherwise), paired by position.  The reference zips the two datasets (test.py:130), and tf.data's zip stops at the

@@ -859,6 +859,70 @@ def spec_loss(cyc_y, cbcr, ds_ptrs, mask, loss, batch, npix):
           "shm_spec_loss")
 
 
+# ---- SpecSeg training (specseg_train.hip) ------------------------------------------------------------
+SST_MAX_BLOCKS = 256                                      # SHM_SST_MAX_BLOCKS
+SEG_LOSS_NAMES = ("loss", "dice", "focal", "iou", "f1", "tp", "fp", "fn")     # the entries of seg_loss' result (SHM_SEG_LOSS_OUT)
+SEG_LOSS_WS_DOUBLES = SST_MAX_BLOCKS * 7 + 8              # SHM_SEG_LOSS_WS_DOUBLES
+
+
+def bn_train_ws_doubles(c):
+    """SHM_BN_TRAIN_WS_DOUBLES: float64 elements of the workspace of bn_train_fwd / bn_train_bwd / head_logit_bwd."""
+    return SST_MAX_BLOCKS * 2 * c + 2 * c
+
+
+def bn_train_fwd(a, lda, gamma, beta, moving_mean, moving_var, momentum, eps, out, ldo, save, ws, npix, c):
+    """BatchNormalization on batch statistics; save (float64 [2c]) <- mean, inv_std; the moving statistics (or None) are updated."""
+    check(lib().shm_bn_train_fwd(_p(a), lda, _p(gamma), _p(beta), _p(moving_mean), _p(moving_var), momentum, eps, _p(out), ldo, _p(save), _p(ws),
+                                 ws.numel() * ws.element_size(), npix, c, _stream()), "shm_bn_train_fwd")
+
+
+def bn_train_bwd(dy, lddy, a, lda, gamma, save, dx, lddx, dgamma, dbeta, ws, npix, c):
+    check(lib().shm_bn_train_bwd(_p(dy), lddy, _p(a), lda, _p(gamma), _p(save), _p(dx), lddx, _p(dgamma), _p(dbeta), _p(ws),
+                                 ws.numel() * ws.element_size(), npix, c, _stream()), "shm_bn_train_bwd")
+
+
+def maxpool2_bwd(x, ldx, dy, lddy, dx, lddx, batch, h, w, c, accumulate):
+    """The window's gradient to its first maximum in row-major order; accumulate: onto the skip gradient already in dx."""
+    check(lib().shm_maxpool2_bwd(_p(x), ldx, _p(dy), lddy, _p(dx), lddx, batch, h, w, c, int(accumulate), _stream()), "shm_maxpool2_bwd")
+
+
+def conv2d_transpose2x2_dgrad(dy, lddy, w, dx, lddx, batch, hi, wi, cin, cout):
+    flops = 2.0 * batch * hi * wi * 4 * cin * cout
+    _timed("convt2_dgrad_kernel", flops, lambda: check(
+        lib().shm_conv2d_transpose2x2_dgrad(_p(dy), lddy, _p(w), _p(dx), lddx, batch, hi, wi, cin, cout, _stream()),
+        "shm_conv2d_transpose2x2_dgrad"), f"convT2 dgrad n{batch} h{hi} {cin}<-{cout}")
+
+
+def conv2d_transpose2x2_wgrad_workspace(batch, hi, wi, cin, cout):
+    return int(lib().shm_conv2d_transpose2x2_wgrad_workspace(batch, hi, wi, cin, cout))
+
+
+def conv2d_transpose2x2_wgrad(x, ldx, dy, lddy, dw, dbias, ws, batch, hi, wi, cin, cout):
+    flops = 2.0 * batch * hi * wi * 4 * cin * cout
+    _timed("convt2_wgrad_kernel", flops, lambda: check(
+        lib().shm_conv2d_transpose2x2_wgrad(_p(x), ldx, _p(dy), lddy, _p(dw), _p(dbias), _p(ws), ws.numel() * ws.element_size(), batch, hi, wi, cin, cout,
+                                            _stream()), "shm_conv2d_transpose2x2_wgrad"), f"convT2 wgrad n{batch} h{hi} {cin}x{cout}")
+
+
+def head_logit_fwd(x, ldx, w, bias, z, npix, c):
+    check(lib().shm_head_logit_fwd(_p(x), ldx, _p(w), _p(bias), _p(z), npix, c, _stream()), "shm_head_logit_fwd")
+
+
+def head_logit_bwd(x, ldx, w, dz, dx, lddx, dw, db, ws, npix, c):
+    check(lib().shm_head_logit_bwd(_p(x), ldx, _p(w), _p(dz), _p(dx), lddx, _p(dw), _p(db), _p(ws), ws.numel() * ws.element_size(), npix, c, _stream()),
+          "shm_head_logit_bwd")
+
+
+def seg_loss(z, g, dz, out, ws, npix):
+    """Dice + binary focal loss of logits z against target g; out (float64 [8], SEG_LOSS_NAMES); dz (or None) <- dloss/dz."""
+    check(lib().shm_seg_loss(_p(z), _p(g), _p(dz), _p(out), _p(ws), ws.numel() * ws.element_size(), npix, _stream()), "shm_seg_loss")
+
+
+def adam(w, m, v, g, n, alpha, beta1, beta2, eps, gscale=1.0, clip=0.0):
+    """adam_clip with the clip bound as an argument (clip <= 0: none)."""
+    check(lib().shm_adam(_p(w), _p(m), _p(v), _p(g), n, alpha, beta1, beta2, eps, gscale, clip, _stream()), "shm_adam")
+
+
 # ---- live attention branch --------------------------------------------------------------------------
 def mask_pool_pack(mask, dst, batch, s, k):
     """MaxPooling2D(k) of mask [batch,s,s,1] into channel 0 of the activation tensor dst [batch,s/k,s/k,ld]."""

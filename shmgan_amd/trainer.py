@@ -55,7 +55,8 @@ _DEFAULTS = dict(image_size=128, batch_size=1, filter_size=64, g_lr=0.00002, d_l
                  data_dir="", model_save_dir="./models", checkpoint_save_dir="./checkpoints", result_dir="./results",
                  log_dir="./logs/train", log_step=1, checkpoint_save_step=10, calc_metrics=False, test_dir="", diffuse_dir="",
                  save_images=False, image_values="rescale", image_out_size="source", image_dir="", eval_size="model",
-                 loss_log_step=0, histogram_step=0, nonfinite=None, diffuse_source="dir")
+                 loss_log_step=0, histogram_step=0, nonfinite=None, diffuse_source="dir",
+                 specseg_image_dir="", specseg_mask_dir="", specseg_epochs=20, specseg_lr=1e-3, specseg_batch_size=8)
 
 
 class KernelAbortError(RuntimeError):
@@ -266,6 +267,25 @@ class ShmGANwithSSpecSeg:
         checkpoint is not available, so the network starts from the initialisers of SpecSeg.py; load trained
         Keras weights with `self.SpecSeg.set_weights(keras_model.get_weights())`."""
         return SpecSeg(self.image_size, self.device, self.arena).init_random()
+
+    def train_specseg(self, args=None, *, print_fn=print):
+        """Train the mask network in place on a directory of image / mask pairs (data.MaskDataset): args.specseg_image_dir,
+        args.specseg_mask_dir, args.specseg_epochs, args.specseg_lr (and specseg_batch_size), defaults from the trainer's own
+        options.  The reference builds this optimiser (SHM.py:175) and never steps it; its checkpoint is not available, so this is
+        how the weights every Spec_loss, live-attention step and test-mode image depends on are made.  Adam runs on the schedule of
+        optimizer_G with the trainer's beta1 / beta2; the five scalars are logged per epoch through print_fn.  G and D are not
+        touched; the next train_step / infer uses the trained network.  Returns fit()'s history."""
+        from .data import MaskDataset
+        opt = lambda k: getattr(args, k, None) if args is not None and getattr(args, k, None) is not None else getattr(self.args, k)
+        idir, mdir = opt("specseg_image_dir"), opt("specseg_mask_dir")
+        if not idir or not mdir:
+            raise ValueError("train_specseg needs specseg_image_dir and specseg_mask_dir")
+        if self.SpecSeg is None:
+            self.SpecSeg = self.build_specseg()
+        ds = MaskDataset(idir, mdir, self.image_size, int(opt("specseg_batch_size")), device=self.device)
+        x, y = ds.tensors()
+        return self.SpecSeg.fit(x, y, batch_size=ds.B, epochs=int(opt("specseg_epochs")), lr=float(opt("specseg_lr")), beta1=self.beta1,
+                                beta2=self.beta2, shuffle=True, print_fn=print_fn)
 
     def build(self, seed=42, beta_seed=43, attention_seed=45):
         """Build G, D and SpecSeg and give G/D the synthetic init of SURVEY 8(d): weights N(0,0.02) from
@@ -948,6 +968,10 @@ class ShmGANwithSSpecSeg:
         if self.SpecSeg is not None:
             for i, w in enumerate(self.SpecSeg.get_weights()):
                 d[f"SpecSeg/var{i:02d}"] = w
+            opt = self.SpecSeg.optimizer_state()
+            if opt is not None:            # the mask network has been trained here: a resumed fit() continues from its Adam state
+                for k, v in opt.items():
+                    d[f"SpecSeg/{k}"] = v
         # trainer state a resumed run continues from: the step-level draw streams (flags / TARGET_LABELS generator, the
         # Philox counter of the noise and dropout kernels), the epoch, and which graph the variables belong to
         import json
@@ -989,6 +1013,14 @@ class ShmGANwithSSpecSeg:
                     self.SpecSeg = self.build_specseg()
                 for i in range(len(self.SpecSeg.vars)):
                     arrays[f"SpecSeg/var{i:02d}"] = z[f"SpecSeg/var{i:02d}"]
+                if "SpecSeg/adam_m" in z.files:           # absent in files written before the mask network could be trained
+                    for k in ("adam_m", "adam_v"):
+                        a = z[f"SpecSeg/{k}"]
+                        if a.size != self.SpecSeg.n:
+                            raise KeyError(f"checkpoint {path}: SpecSeg/{k} has {a.size} elements, the network's flat buffer {self.SpecSeg.n}")
+                        arrays[f"SpecSeg/{k}"] = a
+                    arrays["SpecSeg/iterations"] = z["SpecSeg/iterations"]
+                    arrays["SpecSeg/train_state"] = z["SpecSeg/train_state"]
         return arrays, state
 
     def _apply_npz(self, z, state):
@@ -1000,6 +1032,8 @@ class ShmGANwithSSpecSeg:
             M.P.iterations = int(z[f"{name}/iterations"])
         if "SpecSeg/var00" in z:
             self.SpecSeg.set_weights([z[f"SpecSeg/var{i:02d}"] for i in range(len(self.SpecSeg.vars))])
+        if "SpecSeg/adam_m" in z:
+            self.SpecSeg.set_optimizer_state(z["SpecSeg/adam_m"], z["SpecSeg/adam_v"], z["SpecSeg/iterations"], z["SpecSeg/train_state"])
         if state is not None:            # continue the draw streams instead of replaying the first run's opening steps
             self.epoch = int(state["epoch"])
             self._draw_count = int(state["draw_count"])

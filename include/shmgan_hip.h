@@ -607,6 +607,30 @@ int shm_load_pad_u8(const unsigned char* src, int h, int w, int c, float* dst, i
 #define SHM_POLAR_STOKES 1
 int shm_polar_views_u8(const unsigned char* const* src_ptrs, int hin, int win, const float* coef, int mode,
                        float* const* dst_ptrs, int ho, int wo, float scale, int flip_ud, void* stream);
+/* Train-time augmentation of ONE sample in the launch that resizes it: shm_polar_views_u8 with a crop window, two mirrors and
+ * an optional re-mix of the four views, or (SHM_AUG_DIR) the same for five sources.  One launch, one thread per output pixel.
+ * src_ptrs: host array of n_src device pointers to uint8 [hin,win,3] images of one size; dst_ptrs: host array of 5 device pointers
+ * to float32 [ho,wo,3] planes; both arrays, coef and mix are read during the call and travel to the kernel by value.
+ *   mode   SHM_AUG_DIR: n_src = 5, plane 4 is source 4 resampled like the views.  SHM_POLAR_MIN / SHM_POLAR_STOKES: n_src = 4,
+ *          plane 4 is the per-tap estimate e(v0..v3) exactly as shm_polar_views_u8 defines it (coef as there).
+ *   sampling   output pixel (oy, ox) samples at sy = flip_ud ? ho-1-oy : oy, sx = flip_lr ? wo-1-ox : ox (the mirrors are on the
+ *          read side); fy = ((sy + 0.5f) * (crop_h / ho) - 0.5f) + crop_y, fx alike with crop_w / wo and crop_x, in fp32; taps and
+ *          weights as shm_resize_bilinear_u8: lower = max(floor(fy), 0), upper = min(ceil(fy), hin-1), ly = fy - floor(fy).  The
+ *          taps are held inside the IMAGE, not the crop: a crop edge interpolates against its real neighbours.
+ *   mix    null, or a host float[16], a row-major 4x4 matrix M: the four view bytes of every tap are replaced by
+ *          v'_i = clamp(((M[i][0] v0 + M[i][1] v1) + M[i][2] v2) + M[i][3] v3, 0, 255) before the lerp (polar.mirror_views: the
+ *          views a polariser at 180 - theta_i would have seen, from the Stokes fit).  The fifth plane is never mixed: a fifth
+ *          source is read as it is, and an estimate is made from the UNMIXED bytes (the unpolarised part is mirror-invariant).
+ * dst[i] = lerp(v'_i) * scale, dst[4] = lerp(source 4 or e) * scale, in the lerp order of shm_polar_views_u8.
+ * Identity parameters -- crop (0, 0, hin, win), flip_lr = 0, mix null -- give bitwise the planes of five shm_resize_bilinear_u8
+ * calls (SHM_AUG_DIR) and of shm_polar_views_u8 (MIN / STOKES) for either flip_ud: the same expressions, then + 0.0f.
+ * SHM_E_SHAPE for a null array or entry, an unknown mode, an n_src that does not fit the mode, a size outside [1, 32768],
+ * crop_h <= 0 or crop_w <= 0, a crop that does not lie inside [0,hin] x [0,win] (a NaN anywhere fails these) or SHM_POLAR_STOKES
+ * without coef; all before any launch. */
+#define SHM_AUG_DIR 2
+int shm_augment_views_u8(const unsigned char* const* src_ptrs, int n_src, int hin, int win, int mode, const float* coef,
+                         const float* mix, float crop_y, float crop_x, float crop_h, float crop_w, int flip_ud, int flip_lr,
+                         float* const* dst_ptrs, int ho, int wo, float scale, void* stream);
 /* Stokes maps of four float32 views of n elements each (any shape: the loaded RGB views or their Y channels).  view_ptrs: host
  * array of 4 device pointers; coef: host float[12], the 3x4 matrix above.  Per element (S0, S1, S2) = C (v0..v3) and
  *   s0 = S0;  dop = sqrt(S1^2 + S2^2) / S0, 0 where S0 == 0 (divide_no_nan, as calcDOP);  aolp = 0.5 atan2f(S2, S1)

@@ -12,6 +12,7 @@
 //                        S0 == 0), aolp = 0.5 atan2(S2, S1).  Grid-stride, float4 when everything is 16-byte aligned.
 // Both are launch- and latency-bound elementwise kernels; nothing here is tuned beyond coalesced access.
 #include "common.h"
+#include "polar_est.h"
 
 #include <math.h>
 
@@ -34,16 +35,6 @@ struct PolarMapArgs {
     float* aolp;
     float coef[12];
 };
-
-template <int MODE>
-__device__ __forceinline__ float estimate(const float* c, float v0, float v1, float v2, float v3) {
-    if (MODE == SHM_POLAR_MIN) return fminf(fminf(v0, v1), fminf(v2, v3));
-    const float s0 = c[0] * v0 + c[1] * v1 + c[2] * v2 + c[3] * v3;
-    const float s1 = c[4] * v0 + c[5] * v1 + c[6] * v2 + c[7] * v3;
-    const float s2 = c[8] * v0 + c[9] * v1 + c[10] * v2 + c[11] * v3;
-    // the fitted intensity minimum over all polariser angles, 0.5 (S0 - P), kept inside the byte range
-    return fminf(fmaxf(0.5f * (s0 - sqrtf(s1 * s1 + s2 * s2)), 0.f), 255.f);
-}
 
 template <int MODE>
 __global__ void __launch_bounds__(PL_NT) polar_views_u8_kernel(const PolarViewArgs a, int hin, int win, int ho, int wo, float hs, float ws,
@@ -77,8 +68,8 @@ __global__ void __launch_bounds__(PL_NT) polar_views_u8_kernel(const PolarViewAr
             const float top = tl[v] + (tr[v] - tl[v]) * lx, bot = bl[v] + (br[v] - bl[v]) * lx;
             a.dst[v][o + k] = (top + (bot - top) * ly) * scale;
         }
-        const float etl = estimate<MODE>(a.coef, tl[0], tl[1], tl[2], tl[3]), etr = estimate<MODE>(a.coef, tr[0], tr[1], tr[2], tr[3]);
-        const float ebl = estimate<MODE>(a.coef, bl[0], bl[1], bl[2], bl[3]), ebr = estimate<MODE>(a.coef, br[0], br[1], br[2], br[3]);
+        const float etl = polar_estimate<MODE>(a.coef, tl[0], tl[1], tl[2], tl[3]), etr = polar_estimate<MODE>(a.coef, tr[0], tr[1], tr[2], tr[3]);
+        const float ebl = polar_estimate<MODE>(a.coef, bl[0], bl[1], bl[2], bl[3]), ebr = polar_estimate<MODE>(a.coef, br[0], br[1], br[2], br[3]);
         const float top = etl + (etr - etl) * lx, bot = ebl + (ebr - ebl) * lx;
         a.dst[4][o + k] = (top + (bot - top) * ly) * scale;
     }

@@ -17,6 +17,12 @@ pre-computed estimated-diffuse images.  "min" / "stokes" need only the four view
 one kernel per SAMPLE (shm_polar_views_u8) writes all five tensors, the diffuse estimate made per source pixel from the four
 decoded views ("Estimated diffuse on the device") -- B launches and 4 B uploads per batch instead of 5 B of each.
 
+`shuffle` and `augment` are the as-intended train-time loader (the reference's --flip, whose per-step draw its traced `map` lambda
+never sees): an epoch-wise shuffle, and per sample one random crop / mirror drawn by the stateless `augment_params`, applied by ONE
+kernel per sample (shm_augment_views_u8) at the decoded bytes for all three `diffuse_source` modes.  A single mirror turns a polariser
+angle theta into 180 - theta, so the four views are permuted or re-mixed with it (polar.mirror_views).  Without
+either option the loader calls exactly the kernels described above.
+
 Under torch.distributed the loader shards by rank: global batch i of rank r is images [(i*world + r)*B, +B), so N ranks
 consume N*B distinct samples per step (the data-parallel identity of shmgan_amd/dist.py) and len() = n // (B*world).
 """
@@ -24,7 +30,9 @@ from __future__ import annotations
 
 import os
 from concurrent.futures import ThreadPoolExecutor
+from dataclasses import dataclass
 from pathlib import Path
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -43,17 +51,93 @@ def list_images(directory):
     return sorted(str(p) for p in d.iterdir() if p.suffix.lower() in _EXT)
 
 
+AUGMENT_VIEWS = ("physical", "keep")
+
+
+@dataclass(frozen=True)
+class Augment:
+    """Per-sample random augmentation of PolarDataset.  flip_lr / flip_ud: probabilities of a left-right / top-bottom mirror (the
+    drawn flip_ud is XOR-ed onto the loader's fixed flip_ud orientation).  crop_min: the crop keeps the source aspect and covers a
+    fraction a ~ U(crop_min, 1) of its area (side fraction sqrt(a)), its origin uniform over the positions that fit; 1.0 = no crop.
+    views: "physical" = when exactly one mirror is drawn the four views follow it (a polariser at theta sees of the mirrored scene
+    what one at 180 - theta saw: polar.mirror_views); "keep" = the reference's plain geometric flip."""
+    flip_lr: float = 0.0
+    flip_ud: float = 0.0
+    crop_min: float = 1.0
+    views: str = "physical"
+
+    def __post_init__(self):
+        for name in ("flip_lr", "flip_ud"):
+            p = getattr(self, name)
+            if not isinstance(p, (int, float)) or not 0.0 <= p <= 1.0:
+                raise ValueError(f"Augment: {name} {p!r} is not a probability in [0, 1]")
+        if not isinstance(self.crop_min, (int, float)) or not 0.0 < self.crop_min <= 1.0:
+            raise ValueError(f"Augment: crop_min {self.crop_min!r} is not an area fraction in (0, 1]")
+        if self.views not in AUGMENT_VIEWS:
+            raise ValueError(f"Augment: views {self.views!r} is not one of {AUGMENT_VIEWS}")
+
+
+class AugmentParams(NamedTuple):
+    crop: tuple          # (y, x, h, w) in source pixels: floats that float32 holds exactly, inside [0,hin] x [0,win]
+    flip_ud: bool        # the DRAWN top-bottom mirror (before the loader's fixed orientation)
+    flip_lr: bool
+    remap: bool          # exactly one mirror drawn: the views stand for other polariser angles
+
+
+def _fit_origin(u, size, extent):
+    """u * (size - extent) as a float32 value with origin + extent <= size in exact arithmetic (what the kernel's host check adds)."""
+    o = np.float32(u * (size - float(extent)))
+    if float(o) + float(extent) > size:
+        o = np.nextafter(o, np.float32(0.0))
+    return o
+
+
+def augment_params(seed, pass_index, position, hin, win, augment):
+    """The draw of the sample at `position` of the sorted file list in pass `pass_index`: a pure function of its arguments, so the
+    worker thread, the rank and a resume do not change what a sample gets.  Five uniforms from default_rng((seed, pass_index,
+    position)), always in this order: crop area, crop row, crop column, flip_ud, flip_lr.  crop_min = 1 and zero probabilities give
+    the identity (0, 0, hin, win), no flips.  Both mirrors together are a rotation by 180 degrees, the identity on polariser
+    angles: `remap` is set when exactly one is drawn."""
+    u = np.random.default_rng((int(seed), int(pass_index), int(position))).random(5)
+    side = np.sqrt(augment.crop_min + (1.0 - augment.crop_min) * u[0])
+    ch, cw = np.float32(min(side * hin, hin)), np.float32(min(side * win, win))
+    cy, cx = _fit_origin(u[1], hin, ch), _fit_origin(u[2], win, cw)
+    fud, flr = bool(u[3] < augment.flip_ud), bool(u[4] < augment.flip_lr)
+    return AugmentParams((float(cy), float(cx), float(ch), float(cw)), fud, flr, fud != flr)
+
+
+def pass_order(n, seed, pass_index, shuffle):
+    """Dataset position of every slot of pass `pass_index`: the sorted order, or with `shuffle` a permutation that depends on (seed,
+    pass_index) alone -- the same on every rank, which then takes its slots by PolarDataset.image_index."""
+    return np.random.default_rng((int(seed), int(pass_index))).permutation(n) if shuffle else np.arange(n)
+
+
 class PolarDataset:
     """Iterable of 5-tuples of [B,S,S,3] float32 device tensors in [0,1].
 
     diffuse_source: "dir" = the fifth of `subdirs` holds the estimated-diffuse images (the reference's loader); "min" = the
     per-channel minimum of the four views (utils.calculate_estimate_diffuse), "stokes" = the fitted minimum over all polariser
     angles, both computed on the device from the first four `subdirs` alone.  angles: the polariser angles in degrees for
-    "stokes" (default: read from the directory names, polar.angles_from_subdirs)."""
+    "stokes" (default: read from the directory names, polar.angles_from_subdirs).
+
+    shuffle: every pass visits the samples in the order pass_order(n, seed, pass) instead of the sorted one.  augment: an Augment,
+    or None; with one, every sample goes through shm_augment_views_u8 with the draw augment_params(seed, pass, position, ...), and
+    views="physical" needs the polariser angles (`angles`, or the directory names).  Passes count from `first_pass` (a resumed run
+    sets it, so that it does not replay pass 0)."""
 
     def __init__(self, data_dir, image_size, batch_size=1, subdirs=PSD_SUBDIRS, flip_ud=True, device=None, epochs=1,
-                 rank=None, world=None, diffuse_source="dir", angles=None):
+                 rank=None, world=None, diffuse_source="dir", angles=None, shuffle=False, augment=None, seed=0, first_pass=0):
         self.S, self.B, self.flip_ud, self.epochs = image_size, batch_size, flip_ud, epochs
+        if augment is not None and not isinstance(augment, Augment):
+            raise ValueError(f"augment must be a data.Augment or None, got {augment!r}")
+        self.shuffle, self.augment, self.seed, self.first_pass = bool(shuffle), augment, int(seed), int(first_pass)
+        self._mirror = ("identity", None)
+        if augment is not None and augment.views == "physical" and (augment.flip_lr > 0 or augment.flip_ud > 0):
+            from . import polar
+            ang = list(angles if angles is not None else polar.angles_from_subdirs(tuple(subdirs)[:4]))
+            if len(ang) != 4:
+                raise ValueError(f"augment views='physical' takes four angles, got {ang}")
+            self._mirror = polar.mirror_views(ang)
         if diffuse_source not in DIFFUSE_SOURCES:
             raise ValueError(f"diffuse_source {diffuse_source!r} is not one of {DIFFUSE_SOURCES}")
         self.diffuse_source, self.coef = diffuse_source, None
@@ -103,6 +187,10 @@ class PolarDataset:
         """Dataset position of sample b of this rank's batch `index`."""
         return (index * self.world + self.rank) * self.B + b
 
+    def position(self, index, b, pass_index=0):
+        """Index in the sorted file lists of sample b of this rank's batch `index` in pass `pass_index`."""
+        return int(pass_order(self.n, self.seed, pass_index, self.shuffle)[self.image_index(index, b)])
+
     def _decode(self, path, key):
         from PIL import Image
         with Image.open(path) as im:
@@ -114,14 +202,31 @@ class PolarDataset:
         buf.numpy()[...] = a
         return buf
 
-    def _prepare_worker(self, index, gen):
+    def _stage(self, index, gen, pass_index, nsrc):
+        """Decode the `nsrc` files of every sample of the batch into this generation's pinned buffers: (staged[v][b], paths[v][b],
+        the samples' positions in the sorted file lists)."""
+        pos = [self.position(index, b, pass_index) for b in range(self.B)]
+        paths = [[self.files[v][p] for p in pos] for v in range(nsrc)]
+        return [[self._decode(paths[v][b], (gen, v, b)) for b in range(self.B)] for v in range(nsrc)], paths, pos
+
+    @staticmethod
+    def _same_size(staged, paths, b):
+        n = len(staged)
+        if any(staged[v][b].shape != staged[0][b].shape for v in range(n)):
+            raise ValueError(("the four views of a sample" if n == 4 else "the four views and the diffuse image of a sample") +
+                             " must have the same decoded size: " +
+                             ", ".join(f"{paths[v][b]} {staged[v][b].shape[0]}x{staged[v][b].shape[1]}" for v in range(n)))
+
+    def _prepare_worker(self, index, gen, pass_index=0):
         """Runs on the loader thread (torch's current stream is per thread): decode into this generation's pinned buffers,
         then enqueue copy + resize per image on the loader stream and record the batch's event."""
         if self._gen_event[gen] is not None:         # the copies that last read this generation's staging buffers
             self._gen_event[gen].synchronize()       # (a host wait, but on the loader thread)
+        if self.augment is not None:
+            return self._prepare_augmented(index, gen, pass_index)
         if self.diffuse_source != "dir":
-            return self._prepare_estimated(index, gen)
-        staged = [[self._decode(self.files[v][self.image_index(index, b)], (gen, v, b)) for b in range(self.B)] for v in range(5)]
+            return self._prepare_estimated(index, gen, pass_index)
+        staged, _, _ = self._stage(index, gen, pass_index, 5)
         with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
             # allocated, filled and consumed on the loader stream: the caching allocator hands a block back to loader-stream
             # allocations only, which are ordered behind the resize kernel that read it
@@ -135,14 +240,12 @@ class PolarDataset:
         self._gen_event[gen] = ev
         return tuple(outs), ev
 
-    def _prepare_estimated(self, index, gen):
+    def _prepare_estimated(self, index, gen, pass_index=0):
         """_prepare_worker for diffuse_source "min" / "stokes": 4 B decodes and uploads, then one shm_polar_views_u8 per sample
         writes that sample's slice of all five tensors."""
-        staged = [[self._decode(self.files[v][self.image_index(index, b)], (gen, v, b)) for b in range(self.B)] for v in range(4)]
+        staged, paths, _ = self._stage(index, gen, pass_index, 4)
         for b in range(self.B):
-            if any(staged[v][b].shape != staged[0][b].shape for v in range(4)):
-                raise ValueError("the four views of a sample must have the same decoded size: " + ", ".join(
-                    f"{self.files[v][self.image_index(index, b)]} {staged[v][b].shape[0]}x{staged[v][b].shape[1]}" for v in range(4)))
+            self._same_size(staged, paths, b)
         with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
             outs = [torch.empty((self.B, self.S, self.S, 3), device=self.dev) for _ in range(5)]       # on the loader stream, as above
             for b in range(self.B):
@@ -153,15 +256,41 @@ class PolarDataset:
         self._gen_event[gen] = ev
         return tuple(outs), ev
 
-    def prepare(self, index):
-        """Start batch `index` (0-based, of this rank) on the loader thread / stream; returns a future of
+    def _prepare_augmented(self, index, gen, pass_index):
+        """_prepare_worker with `augment`, for every diffuse_source: 5 B ("dir") or 4 B decodes and uploads, then one
+        shm_augment_views_u8 per sample writes that sample's slice of all five tensors with the sample's own draw.  A mirror that
+        permutes the views is applied by handing the kernel the view planes in the permuted order (exact); one that does not is the
+        kernel's 4x4 mix."""
+        nsrc = 5 if self.diffuse_source == "dir" else 4
+        staged, paths, pos = self._stage(index, gen, pass_index, nsrc)
+        for b in range(self.B):
+            self._same_size(staged, paths, b)
+        kind, how = self._mirror
+        with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+            outs = [torch.empty((self.B, self.S, self.S, 3), device=self.dev) for _ in range(5)]       # on the loader stream, as above
+            for b in range(self.B):
+                hin, win = staged[0][b].shape[:2]
+                p = augment_params(self.seed, pass_index, pos[b], hin, win, self.augment)
+                srcs = [staged[v][b].to(self.dev, non_blocking=True) for v in range(nsrc)]
+                dsts = [outs[v][b] for v in range(5)]
+                if p.remap and kind == "permute":     # mirrored view i is view how[i]: source how[i] lands in plane i
+                    dsts = [dsts[how.index(v)] for v in range(4)] + dsts[4:]
+                ops.augment_views_u8(srcs, dsts, self.diffuse_source, self.coef, how if p.remap and kind == "mix" else None, p.crop,
+                                     bool(self.flip_ud) != p.flip_ud, p.flip_lr, 1.0 / 255.0)
+            ev = torch.cuda.Event()
+            ev.record(self.stream)
+        self._gen_event[gen] = ev
+        return tuple(outs), ev
+
+    def prepare(self, index, pass_index=0):
+        """Start batch `index` (0-based, of this rank) of pass `pass_index` on the loader thread / stream; returns a future of
         (five [B,S,S,3] tensors, ready event).  The outputs are ALLOCATED on the loader stream: a block the consumer has
         dropped is then only reused after the consumer stream's work recorded by `take()` has finished (train_step is
         fully asynchronous and reads its inputs late in the step, so allocating them on the consumer stream would let the
         next batch's resize kernels overwrite images that queued step kernels still read)."""
         gen = self._prepared & 1
         self._prepared += 1
-        return self._pool.submit(self._prepare_worker, index, gen)
+        return self._pool.submit(self._prepare_worker, index, gen, pass_index)
 
     def take(self, prepared):
         """Hand a prepared batch to the current stream (waits for the loader thread's host work, not for the GPU)."""
@@ -172,26 +301,33 @@ class PolarDataset:
             t.record_stream(cur)
         return outs
 
-    def batch(self, index):
-        """Batch `index` (0-based) as five [B,S,S,3] tensors; prepared on the loader's stream."""
-        return self.take(self.prepare(index))
+    def batch(self, index, pass_index=0):
+        """Batch `index` (0-based) of pass `pass_index` as five [B,S,S,3] tensors; prepared on the loader's stream."""
+        return self.take(self.prepare(index, pass_index))
 
     def __iter__(self):
-        """One batch is always in preparation on the loader thread while the previous one is consumed."""
-        order = [i for _ in range(self.epochs) for i in range(len(self))]
-        nxt = self.prepare(order[0]) if order else None
+        """One batch is always in preparation on the loader thread while the previous one is consumed.  Pass e of the iteration
+        is pass first_pass + e of the shuffle and the augmentation draws."""
+        order = [(i, self.first_pass + e) for e in range(self.epochs) for i in range(len(self))]
+        nxt = self.prepare(*order[0]) if order else None
         for j in range(len(order)):
             cur = nxt
-            nxt = self.prepare(order[j + 1]) if j + 1 < len(order) else None
+            nxt = self.prepare(*order[j + 1]) if j + 1 < len(order) else None
             yield self.take(cur)
 
 
 def datasetLoad(trainer, subdirs=PSD_SUBDIRS, flip_ud=True):
     """Reference signature (datasetLoader.py:19): returns (length_dataset, loadedDataset) and sets the same
     attributes on the trainer object.  The trainer's `diffuse_source` option (default "dir") goes to PolarDataset; it is NOT
-    keyed on the reference's `est_diffuse`, which main.py's parser makes True for every run."""
+    keyed on the reference's `est_diffuse`, which main.py's parser makes True for every run.  `shuffle`, `data_seed`
+    and `aug_flip_lr` / `aug_flip_ud` / `aug_crop_min` / `aug_views` become the loader's shuffle, seed and Augment."""
+    opt = lambda k, dflt: getattr(trainer.args, k, dflt)
+    draws = (float(opt("aug_flip_lr", 0.0)), float(opt("aug_flip_ud", 0.0)), float(opt("aug_crop_min", 1.0)))
+    # no augmentation asked for: the loader's default path, not the augmenting kernel at identity parameters
+    augment = Augment(*draws, views=opt("aug_views", "physical")) if draws != (0.0, 0.0, 1.0) else None
     ds = PolarDataset(trainer.data_dir, trainer.image_size, trainer.batch_size, subdirs, flip_ud, trainer.device,
-                      epochs=trainer.num_epochs, diffuse_source=getattr(trainer.args, "diffuse_source", "dir"))
+                      epochs=trainer.num_epochs, diffuse_source=getattr(trainer.args, "diffuse_source", "dir"),
+                      shuffle=bool(opt("shuffle", False)), augment=augment, seed=int(opt("data_seed", 0)))
     trainer.stddev_arr, trainer.mean_arr, trainer.variance_arr = [], [], []
     # per-rank length: batches_per_epoch = length // batch_size (SHM.py:957) then counts this rank's batches
     trainer.length_dataset, trainer.loadedDataset = ds.n // ds.world, ds

@@ -1011,6 +1011,55 @@ def polar_views_u8(srcs, dsts, mode="min", coef=None, scale=1.0 / 255.0, flip_ud
           "shm_polar_views_u8")
 
 
+AUGMENT_MODES = dict(POLAR_MODES, dir=2)                 # ... and SHM_AUG_DIR
+
+
+def augment_views_u8(srcs, dsts, mode="dir", coef=None, mix=None, crop=None, flip_ud=False, flip_lr=False, scale=1.0 / 255.0):
+    """The decoded images of one sample -> its five training planes, cropped, mirrored and re-mixed in the launch that resizes them
+    (shm_augment_views_u8, include/shmgan_hip.h, states the definitions).  srcs: uint8 [hin,win,3] device tensors of one size, five
+    for mode "dir" (plane 4 is the fifth resampled), four for "min" / "stokes" (plane 4 is the estimate of polar_views_u8, coef as
+    there); dsts: five float32 [ho,wo,3] device tensors.  mix: None or a 4x4 matrix (polar.mirror_views) applied to the four view
+    bytes of every tap.  crop: (y, x, h, w) in source pixels, floats, None for the whole image.  Runs asynchronously on the current
+    stream."""
+    import ctypes as C
+    import numpy as np
+    if mode not in AUGMENT_MODES:
+        raise ValueError(f"augment_views_u8: mode {mode!r} is not 'dir', 'min' or 'stokes'")
+    nsrc = 5 if mode == "dir" else 4
+    if len(srcs) != nsrc or len(dsts) != 5:
+        raise ValueError(f"augment_views_u8 takes {nsrc} sources for mode {mode!r} and 5 destination planes, got {len(srcs)} and {len(dsts)}")
+    if mode == "stokes" and coef is None:
+        raise ValueError("augment_views_u8: mode 'stokes' needs coef (polar.stokes_matrix of the polariser angles)")
+    for s in srcs:
+        if s.dtype != torch.uint8 or not s.is_cuda:
+            raise TypeError(f"augment_views_u8 takes uint8 device images, got {s.dtype} on {s.device}")
+        if s.dim() != 3 or s.shape[2] != 3 or not s.is_contiguous():
+            raise ValueError(f"augment_views_u8 takes contiguous [hin,win,3] images, got {tuple(s.shape)} with strides {s.stride()}")
+    if any(s.shape != srcs[0].shape for s in srcs):
+        raise ValueError(f"augment_views_u8: the sources differ in size: {[tuple(s.shape[:2]) for s in srcs]}")
+    for d in dsts:
+        if d.dtype != torch.float32 or d.device != srcs[0].device:
+            raise TypeError(f"augment_views_u8 writes float32 planes on {srcs[0].device}, got {d.dtype} on {d.device}")
+        if d.dim() != 3 or d.shape[2] != 3 or not d.is_contiguous():
+            raise ValueError(f"augment_views_u8 writes contiguous [ho,wo,3] planes, got {tuple(d.shape)} with strides {d.stride()}")
+    if any(d.shape != dsts[0].shape for d in dsts):
+        raise ValueError(f"augment_views_u8: the five planes differ in size: {[tuple(d.shape[:2]) for d in dsts]}")
+    hin, win, _ = srcs[0].shape
+    ho, wo, _ = dsts[0].shape
+    mx = None
+    if mix is not None:
+        m = np.asarray(mix.cpu() if isinstance(mix, torch.Tensor) else mix, dtype=np.float32)
+        if m.shape != (4, 4):
+            raise ValueError(f"augment_views_u8: mix must be a 4x4 matrix, got shape {m.shape}")
+        mx = (C.c_float * 16)(*[float(v) for v in m.reshape(-1)])
+    cy, cx, ch, cw = (0.0, 0.0, float(hin), float(win)) if crop is None else (float(v) for v in crop)
+    sp = (C.c_void_p * nsrc)(*[s.data_ptr() for s in srcs])
+    dp = (C.c_void_p * 5)(*[d.data_ptr() for d in dsts])
+    cf = _polar_coef(coef, "augment_views_u8") if mode == "stokes" else None
+    check(lib().shm_augment_views_u8(sp, nsrc, hin, win, AUGMENT_MODES[mode], cf, mx, cy, cx, ch, cw, int(bool(flip_ud)), int(bool(flip_lr)),
+                                     dp, ho, wo, scale, _stream()), "shm_augment_views_u8")
+
+
 def polar_maps(views, coef, want=("s0", "dop", "aolp")):
     """Stokes maps of four float32 device views of equal element count (shm_polar_maps): with (S0, S1, S2) = coef . views,
     "s0" = S0, "dop" = sqrt(S1^2 + S2^2) / S0 (0 where S0 == 0), "aolp" = 0.5 atan2(S2, S1).  Returns {name: tensor of views[0]'s

@@ -42,10 +42,15 @@ def angles_from_subdirs(subdirs=("I0", "I60", "I90", "I150")):
     return out
 
 
-def stokes_matrix(angles_deg):
-    """The least-squares 3 x n matrix C with (S0, S1, S2) = C . (I(theta_1) .. I(theta_n)) for the model above: the
-    pseudo-inverse of A, A[i] = 0.5 * (1, cos 2 theta_i, sin 2 theta_i).  Computed in float64, returned as float32.  The fit
-    needs three angles that are distinct modulo 180 degrees (theta and theta + 180 are the same polariser); fewer raise."""
+def _model_rows(angles_deg):
+    """A[i] = 0.5 * (1, cos 2 theta_i, sin 2 theta_i) in float64, cos / sin of multiples of 90 degrees exactly, so that the textbook
+    angle sets give the textbook matrices."""
+    r = np.deg2rad(2.0 * np.asarray(angles_deg, dtype=np.float64).reshape(-1))
+    return 0.5 * np.stack([np.ones_like(r), np.round(np.cos(r), 15), np.round(np.sin(r), 15)], axis=1)
+
+
+def _stokes_f64(angles_deg):
+    """stokes_matrix before the cast to float32."""
     th = np.asarray(angles_deg, dtype=np.float64).reshape(-1)
     distinct = []
     for t in np.mod(th, 180.0):
@@ -54,10 +59,38 @@ def stokes_matrix(angles_deg):
     if len(distinct) < 3:
         raise ValueError(f"a Stokes fit needs at least three polariser angles that are distinct modulo 180 degrees, got "
                          f"{[float(t) for t in th]}")
-    r = np.deg2rad(2.0 * th)
-    # cos / sin of multiples of 90 degrees exactly, so that the textbook angle sets give the textbook matrices
-    A = 0.5 * np.stack([np.ones_like(r), np.round(np.cos(r), 15), np.round(np.sin(r), 15)], axis=1)
-    return np.linalg.solve(A.T @ A, A.T).astype(np.float32)
+    A = _model_rows(th)
+    return np.linalg.solve(A.T @ A, A.T)
+
+
+def stokes_matrix(angles_deg):
+    """The least-squares 3 x n matrix C with (S0, S1, S2) = C . (I(theta_1) .. I(theta_n)) for the model above: the
+    pseudo-inverse of A, A[i] = 0.5 * (1, cos 2 theta_i, sin 2 theta_i).  Computed in float64, returned as float32.  The fit
+    needs three angles that are distinct modulo 180 degrees (theta and theta + 180 are the same polariser); fewer raise."""
+    return _stokes_f64(angles_deg).astype(np.float32)
+
+
+def mirror_views(angles_deg):
+    """What mirroring the scene about one image axis does to views taken at `angles_deg`: a polariser at theta sees of the mirrored
+    scene what a polariser at (180 - theta) mod 180 saw of the original.  Returns
+      ("permute", perm)   every mirrored angle is in the set (within the 1e-9 of stokes_matrix): mirrored view i is view perm[i],
+                          exactly -- [0, 3, 2, 1] for 0/45/90/135
+      ("mix", M)          otherwise: M = A' . pinv(A), A'[i] = 0.5 (1, cos 2 theta'_i, sin 2 theta'_i), the views a polariser at
+                          theta'_i = 180 - theta_i passes of the Stokes fit of the given ones; float64 arithmetic with the exact
+                          multiples of 90 degrees of stokes_matrix, returned as float32 [n, n]
+      ("identity", None)  the permutation is the identity
+    Both mirrors together are a rotation by 180 degrees and leave every angle alone.  Fewer than three distinct angles raise, as
+    stokes_matrix does."""
+    pinv = _stokes_f64(angles_deg)
+    th = np.mod(np.asarray(angles_deg, dtype=np.float64).reshape(-1), 180.0)
+    mirrored = np.mod(180.0 - th, 180.0)
+    perm = []
+    for t in mirrored:
+        hit = [j for j, u in enumerate(th) if min(abs(t - u), 180.0 - abs(t - u)) < 1e-9]
+        if not hit:
+            return "mix", (_model_rows(mirrored) @ pinv).astype(np.float32)
+        perm.append(hit[0])
+    return ("identity", None) if perm == list(range(len(perm))) else ("permute", perm)
 
 
 def polar_maps(views, angles, want=("s0", "dop", "aolp")):

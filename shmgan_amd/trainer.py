@@ -56,6 +56,7 @@ _DEFAULTS = dict(image_size=128, batch_size=1, filter_size=64, g_lr=0.00002, d_l
                  log_dir="./logs/train", log_step=1, checkpoint_save_step=10, calc_metrics=False, test_dir="", diffuse_dir="",
                  save_images=False, image_values="rescale", image_out_size="source", image_dir="", eval_size="model",
                  loss_log_step=0, histogram_step=0, nonfinite=None, diffuse_source="dir",
+                 shuffle=False, data_seed=0, aug_flip_lr=0.0, aug_flip_ud=0.0, aug_crop_min=1.0, aug_views="physical",
                  specseg_image_dir="", specseg_mask_dir="", specseg_epochs=20, specseg_lr=1e-3, specseg_batch_size=8)
 
 
@@ -653,7 +654,9 @@ class ShmGANwithSSpecSeg:
         sign / exponent histograms of every gradient tensor (gradmapD, gradmapG, SHM.py:1085-1091) and of every weight tensor go to
         gradients.jsonl / weights.jsonl, computed on the device and written by a thread of their own (telemetry.py; `nonfinite` says what
         a NaN or Inf gradient does).  Both are off by default; the step counts optimizer updates, so a resumed run appends.  The logs are
-        flushed before every checkpoint.  `max_steps` (tests) stops early.  Returns the number of train_step calls made."""
+        flushed before every checkpoint.  The loader options `shuffle`, `data_seed`, `aug_flip_lr`, `aug_flip_ud`, `aug_crop_min` and
+        `aug_views` (data.datasetLoad; all off by default) give an epoch-wise shuffle and a random crop / mirror per sample;
+        aug_flip_ud=0.5 is the as-intended reading of the per-step draw below.  `max_steps` (tests) stops early.  Returns the number of train_step calls made."""
         import os
         import time
         from .data import datasetLoad
@@ -678,6 +681,9 @@ class ShmGANwithSSpecSeg:
         latest = self._restore_latest()                                        # SHM.py:949-951 (delete_old_checkpoints is False)
         if latest is not None:
             print_fn(f"Latest checkpoint restored!! ({latest})")
+        # the loader's shuffle and augmentation draws are keyed by the pass number: a resumed run goes on from the pass its restored
+        # step counter (the one telemetry uses) lies in instead of replaying pass 0's order and draws
+        dataset.first_pass = self.D.P.iterations // max(len(dataset), 1)
         loss_step, hist_step, _ = telemetry_options(self.args.loss_log_step, self.args.histogram_step, self.args.nonfinite)
         if rank0 and (loss_step or hist_step):
             self.start_telemetry()

@@ -1,12 +1,16 @@
 """Batch preparation of the training loader (shmgan_amd.data.PolarDataset): one batch of B samples at S x S from a synthetic
 capture of HxH PNG files, with the diffuse target read from the ED/ directory (diffuse_source="dir": 5 B decodes, 5 B uploads,
-5 B shm_resize_bilinear_u8 launches) and computed on the device ("min": 4 B decodes, 4 B uploads, B shm_polar_views_u8 launches).
+5 B shm_resize_bilinear_u8 launches) and computed on the device ("min": 4 B decodes, 4 B uploads, B shm_polar_views_u8 launches),
+and the "dir" loader through the augmenting kernel (5 B uploads, B shm_augment_views_u8 launches): "dir/identity" with
+Augment() -- identity parameters, the same numbers as "dir" -- and "dir/augment" with a random crop of at least half the area and
+both mirrors at probability 0.5, another pass (so other draws) every repeat.  On a tree without data.Augment the last two are
+left out, so the same tool gives the first figure on an older commit.
 
-Two figures per source, the two sources alternating within every repeat, median over the repeats after a warm-up:
+Two figures per configuration, the configurations alternating within every repeat, median over the repeats after a warm-up:
   device_ms   HIP events on the loader stream around the uploads and kernels alone: the decoded bytes are already in the pinned
               staging buffers (the decode is replaced by a lookup), so this is what the GPU side of a batch costs
   total_ms    host clock around prepare() -> the batch's event has completed, decode included (PIL, one worker thread)
-Launch and upload counts are counted, not assumed.  Prints one JSON line per source.
+Launch and upload counts are counted, not assumed.  Prints one JSON line per configuration.
 python tools/bench_loader.py [--batch 8] [--size 256] [--source-size 1024] [--repeats 20] [--warmup 3]"""
 import argparse
 import json
@@ -18,7 +22,7 @@ from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import numpy as np
 import torch
-from shmgan_amd import ops
+from shmgan_amd import data, ops
 from shmgan_amd.data import PSD_SUBDIRS, PolarDataset
 
 ap = argparse.ArgumentParser()
@@ -45,6 +49,9 @@ def counted(fn):
 
 ops.resize_bilinear_u8 = counted(ops.resize_bilinear_u8)
 ops.polar_views_u8 = counted(ops.polar_views_u8)
+Augment = getattr(data, "Augment", None)
+if Augment is not None:
+    ops.augment_views_u8 = counted(ops.augment_views_u8)
 
 with tempfile.TemporaryDirectory() as root:
     from PIL import Image
@@ -54,18 +61,30 @@ with tempfile.TemporaryDirectory() as root:
         for i in range(B):
             Image.fromarray(rng.integers(0, 256, (H, H, 3)).astype(np.uint8)).save(Path(root) / sub / f"img_{i:03d}.png", compress_level=1)
     sets = {src: PolarDataset(root, S, batch_size=B, diffuse_source=src, rank=0, world=1) for src in ("dir", "min")}
+    if Augment is not None:
+        sets["dir/identity"] = PolarDataset(root, S, batch_size=B, rank=0, world=1, augment=Augment())
+        sets["dir/augment"] = PolarDataset(root, S, batch_size=B, rank=0, world=1, seed=a.seed,
+                                           augment=Augment(flip_lr=0.5, flip_ud=0.5, crop_min=0.5))
+    passes = {src: 0 for src in sets}
 
-    def run(ds):
+    def prepare(src, ds):
+        """Batch 0; the augmenting configurations take the next pass each time (the identity one draws nothing either way)."""
+        if ds.__dict__.get("augment") is None:
+            return ds.prepare(0)
+        passes[src] += 1
+        return ds.prepare(0, passes[src])
+
+    def run(src, ds):
         """One batch through the loader's own worker; (host seconds until the batch's event completed, its tensors)."""
         t0 = time.perf_counter()
-        outs, ev = ds.prepare(0).result()
+        outs, ev = prepare(src, ds).result()
         ev.synchronize()
         return time.perf_counter() - t0, outs
 
     total = {src: [] for src in sets}
     for r in range(a.warmup + a.repeats):
         for src, ds in sets.items():
-            dt, _ = run(ds)
+            dt, _ = run(src, ds)
             if r >= a.warmup:
                 total[src].append(dt * 1e3)
 
@@ -81,7 +100,7 @@ with tempfile.TemporaryDirectory() as root:
             counts["launches"] = counts["uploads"] = 0
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(ds.stream)
-            ds.prepare(0).result()
+            prepare(src, ds).result()
             e1.record(ds.stream)
             e1.synchronize()
             per_batch[src] = dict(counts)
@@ -89,7 +108,7 @@ with tempfile.TemporaryDirectory() as root:
                 device[src].append(e0.elapsed_time(e1))
     for src in sets:
         d, t = sorted(device[src]), sorted(total[src])
-        print(json.dumps({"tool": "bench_loader", "diffuse_source": src, "B": B, "S": S, "source": f"{H}x{H}",
+        print(json.dumps({"tool": "bench_loader", "diffuse_source": src.split("/")[0], "config": src, "B": B, "S": S, "source": f"{H}x{H}",
                           "launches": per_batch[src]["launches"], "uploads": per_batch[src]["uploads"],
                           "device_ms": round(statistics.median(d), 4), "device_ms_min_max": [round(d[0], 4), round(d[-1], 4)],
                           "total_ms": round(statistics.median(t), 3), "total_ms_min_max": [round(t[0], 3), round(t[-1], 3)],

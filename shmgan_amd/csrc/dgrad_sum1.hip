@@ -260,6 +260,8 @@ extern "C" int shm_conv3x3_dgrad_sum1(const void* dz, int lddz, const float* wef
                                       int accumulate, int dtype, void* stream) {
     SHM_REQUIRE(dz && weff && out, SHM_E_SHAPE, "shm_conv3x3_dgrad_sum1: null pointer");
     SHM_REQUIRE(c % 4 == 0 && pow2_le64(c / 4) && lddz % 4 == 0, SHM_E_SHAPE, "shm_conv3x3_dgrad_sum1: channels %d unsupported", c);
+    // bf16 pitches are multiples of 8 (the header's rule): the bf16 MFMA form loads 16 bytes a lane from dz + pixel * lddz
+    SHM_REQUIRE(dtype != SHM_BF16 || lddz % 8 == 0, SHM_E_SHAPE, "shm_conv3x3_dgrad_sum1: bf16 pitch %d is no multiple of 8", lddz);
     SHM_REQUIRE(stride == 1 || stride == 2, SHM_E_SHAPE, "shm_conv3x3_dgrad_sum1: stride %d not in {1,2}", stride);
     int ho, wo, pt, pl;
     shm_same_pad(hi, 3, stride, &ho, &pt);

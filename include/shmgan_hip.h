@@ -794,7 +794,7 @@ int shm_head_logit_bwd(const float* x, int ldx, const float* w, const float* dz,
 #define SHM_SEG_LOSS_OUT 8
 #define SHM_SEG_LOSS_WS_DOUBLES ((size_t)SHM_SST_MAX_BLOCKS * 7 + 8)
 int shm_seg_loss(const float* z, const float* g, float* dz, double* out, double* ws, size_t ws_bytes, size_t npix, void* stream);
-/* shm_adam_clip with the clip bound as an argument (clip <= 0: no clip) and no abort word; clip = 1 gives shm_adam_clip's bits. */
+/* shm_adam_clip's kernel with the clip bound as an argument (clip <= 0: no clip) and no abort word. */
 int shm_adam(float* w, float* m, float* v, const float* g, size_t n, float alpha, float beta1, float beta2, float eps,
              float gscale, float clip, void* stream);
 

@@ -26,15 +26,6 @@ __device__ __forceinline__ void rgb2yuv(float r, float g, float b, float& y, flo
     v = r * R2Y_02 + g * R2Y_12 + b * R2Y_22;
 }
 
-__device__ __forceinline__ double block_sum_d(double v) {
-    __shared__ double ws[4];
-    v = shm_wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ws[0] + ws[1] + ws[2] + ws[3];
-}
-
 // ---------------------------------------------------------------- rgb -> yuv + standardise
 __global__ __launch_bounds__(256) void yuv_stats_kernel(const float* __restrict__ rgb, double* __restrict__ acc, size_t npix) {
     const int b = blockIdx.y;
@@ -46,8 +37,8 @@ __global__ __launch_bounds__(256) void yuv_stats_kernel(const float* __restrict_
         s += (double)y + (double)u + (double)v;
         q += (double)y * y + (double)u * u + (double)v * v;
     }
-    s = block_sum_d(s);
-    q = block_sum_d(q);
+    s = shm_block_sum<256>(s);
+    q = shm_block_sum<256>(q);
     if (threadIdx.x == 0) {
         atomicAdd(&acc[2 * b], s);
         atomicAdd(&acc[2 * b + 1], q);
@@ -73,22 +64,15 @@ __global__ __launch_bounds__(256) void yuv_scale_kernel(const float* __restrict_
     }
 }
 
-static int grid1d(size_t n, int per_block = 256, int cap = 4096) {
-    long g = (long)((n + per_block - 1) / per_block);
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
 extern "C" int shm_rgb2yuv_std(const float* rgb, float* yuv, double* acc, float* scale_out, int batch, size_t npix, void* stream) {
     if (batch == 0 || npix == 0) return SHM_OK;
     hipStream_t st = (hipStream_t)stream;
     int r = shm_zero(acc, (size_t)batch * 2 * sizeof(double), stream);
     if (r) return r;
-    dim3 grid(grid1d(npix, 256, 512), batch);
+    dim3 grid(shm_grid_cap(npix, 256, 512), batch);
     // statistics pass: every block ends in two f64 atomics on its sample's two sums -- 32 blocks per sample, not 256 (the adds on one
     // address serialize: 39 us per launch for 6 MB of pixels)
-    dim3 grids(grid1d(npix, 256, 32), batch);
+    dim3 grids(shm_grid_cap(npix, 256, 32), batch);
     hipLaunchKernelGGL(yuv_stats_kernel, grids, dim3(256), 0, st, rgb, acc, npix);
     SHM_LAUNCH_CHECK("shm_rgb2yuv_std(stats)");
     hipLaunchKernelGGL(yuv_scale_kernel, grid, dim3(256), 0, st, rgb, yuv, (const double*)acc, scale_out, npix);
@@ -375,14 +359,16 @@ extern "C" int shm_dhead_losses(const float* rf, const float* cls, double* loss,
 }
 
 // ------------------------------------------------------------------------- clip + Adam
+// The one optimiser kernel: shm_adam_clip (clip = 1, the trainer's abort word) and shm_adam (the clip bound an argument, <= 0 for none; no abort word)
 __global__ void adam_clip_kernel(float* __restrict__ w, float* __restrict__ m, float* __restrict__ v, const float* __restrict__ g, size_t n,
-                                 float alpha, float b1, float b2, float eps, float gscale, const unsigned* __restrict__ abort_word) {
+                                 float alpha, float b1, float b2, float eps, float gscale, float clip, const unsigned* __restrict__ abort_word) {
     // a kernel of this step gave up (the caller's abort word, shm_adam_clip): its gradients are built on unfinished sums -- apply nothing
     if (abort_word && __hip_atomic_load(abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) return;
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (; i < n; i += stride) {
-        float gg = fminf(fmaxf(g[i] * gscale, -1.0f), 1.0f);
+        float gg = g[i] * gscale;
+        if (clip > 0.f) gg = fminf(fmaxf(gg, -clip), clip);
         float mm = m[i] + (gg - m[i]) * (1.0f - b1);
         float vv = v[i] + (gg * gg - v[i]) * (1.0f - b2);
         m[i] = mm;
@@ -394,12 +380,21 @@ __global__ void adam_clip_kernel(float* __restrict__ w, float* __restrict__ m, f
 extern "C" int shm_adam_clip(float* w, float* m, float* v, const float* g, size_t n, float alpha, float beta1, float beta2, float eps, float gscale, const unsigned* abort_word,
                              void* stream) {
     if (n == 0) return SHM_OK;
-    hipLaunchKernelGGL(adam_clip_kernel, dim3(grid1d(n, 256, 8192)), dim3(256), 0, (hipStream_t)stream, w, m, v, g, n, alpha, beta1, beta2, eps, gscale,
-                       abort_word);
+    hipLaunchKernelGGL(adam_clip_kernel, dim3(shm_grid_cap(n, 256, 8192)), dim3(256), 0, (hipStream_t)stream, w, m, v, g, n, alpha, beta1, beta2, eps, gscale,
+                       1.0f, abort_word);
     SHM_LAUNCH_CHECK("shm_adam_clip");
     return SHM_OK;
 }
 
+extern "C" int shm_adam(float* w, float* m, float* v, const float* g, size_t n, float alpha, float beta1, float beta2, float eps, float gscale, float clip,
+                        void* stream) {
+    if (n == 0) return SHM_OK;
+    SHM_REQUIRE(w && m && v && g, SHM_E_SHAPE, "shm_adam: null pointer");
+    hipLaunchKernelGGL(adam_clip_kernel, dim3(shm_grid_cap(n, 256, 8192)), dim3(256), 0, (hipStream_t)stream, w, m, v, g, n, alpha, beta1, beta2, eps, gscale,
+                       clip, (const unsigned*)nullptr);
+    SHM_LAUNCH_CHECK("shm_adam");
+    return SHM_OK;
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // Step-level random draws on the device (SHM.py:352 GaussianNoise(0.1), SHM.py:363 Dropout(0.2)): counter-based

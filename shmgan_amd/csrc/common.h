@@ -203,6 +203,13 @@ __device__ __forceinline__ float rnd_as(const bf16_t*, float v) { return (float)
     } while (0)
 
 static inline int shm_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+// blocks of a grid-stride launch over n items, per_block of them to a block: min(max(ceil(n / per_block), 1), cap)
+static inline int shm_grid_cap(size_t n, int per_block, int cap) {
+    size_t g = (n + per_block - 1) / per_block;
+    if (g > (size_t)cap) g = cap;
+    if (g < 1) g = 1;
+    return (int)g;
+}
 
 // TF "SAME": out = ceil(in/s); pad_before = max((out-1)*s + k - in, 0) / 2
 static inline void shm_same_pad(int in, int k, int s, int* out, int* before) {
@@ -260,6 +267,37 @@ __device__ __forceinline__ float shm_wave_sum(float v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
     return v;
 }
+// Sum over a block of NT threads (NT a multiple of 64, every thread calls) in a fixed order: the wave shuffles, then the wave sums
+// added left to right in wave order, ((p0 + p1) + p2) + ...  Every thread gets the result.  The first barrier lets the previous
+// call's readers finish before `part` is written again, so calls may follow each other directly; both barriers also order the
+// caller's own LDS traffic around the call.  V = double or float (deduced: shm_block_sum<256>(v)), one LDS array per (V, NT).
+template <int NT, typename V>
+__device__ __forceinline__ V shm_block_sum(V v) {
+    static_assert(NT % 64 == 0 && NT >= 64 && NT <= 1024, "whole waves");
+    static_assert(__is_same(V, double) || __is_same(V, float), "shm_wave_sum has a double and a float form");
+    __shared__ V part[NT / 64];
+    v = shm_wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    V r = part[0];
+#pragma unroll
+    for (int w = 1; w < NT / 64; ++w) r += part[w];
+    return r;
+}
+
+// The 11-tap window of tf.image.ssim: a gaussian of sigma 1.5, normalised (w: float[SHM_SSIM_WIN]; one thread fills it)
+#define SHM_SSIM_WIN 11
+__device__ __forceinline__ void shm_ssim_gauss1d(float* w) {
+    float s = 0.f;
+    for (int i = 0; i < SHM_SSIM_WIN; ++i) {
+        float c = (float)i - 5.0f;
+        w[i] = expf(-0.5f * c * c / 2.25f);
+        s += w[i];
+    }
+    for (int i = 0; i < SHM_SSIM_WIN; ++i) w[i] /= s;
+}
+
 __device__ __forceinline__ float shm_wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_down(v, o, 64));

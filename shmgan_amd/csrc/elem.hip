@@ -28,9 +28,7 @@ __global__ void cast_f32_kernel(const float* __restrict__ s, T* __restrict__ d, 
 
 extern "C" int shm_cast_f32(const float* src, void* dst, size_t n, int dtype, void* stream) {
     if (n == 0) return SHM_OK;
-    long blocks = (long)((n + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    SHM_DISPATCH(dtype, "shm_cast_f32", hipLaunchKernelGGL(cast_f32_kernel<T>, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, src, (T*)dst, n));
+    SHM_DISPATCH(dtype, "shm_cast_f32", hipLaunchKernelGGL(cast_f32_kernel<T>, dim3(shm_grid_cap(n, 256, 4096)), dim3(256), 0, (hipStream_t)stream, src, (T*)dst, n));
     SHM_LAUNCH_CHECK("shm_cast_f32");
     return SHM_OK;
 }

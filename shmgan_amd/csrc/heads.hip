@@ -41,11 +41,9 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const T* __restrict__ x, 
 extern "C" int shm_head_fwd(const void* x, int ldx, const float* w, const float* bias, float* y, size_t npix, int c, float slope, int dtype, void* stream) {
     SHM_REQUIRE(c % 4 == 0 && pow2_le64(c / 4) && ldx % 4 == 0, SHM_E_SHAPE, "shm_head_fwd: channels %d unsupported", c);
     if (npix == 0) return SHM_OK;
-    int PP = 256 / (c / 4);
-    long blocks = ((long)npix + PP - 1) / PP;
-    if (blocks > 8192) blocks = 8192;
+    const int blocks = shm_grid_cap(npix, 256 / (c / 4), 8192);
     SHM_DISPATCH(dtype, "shm_head_fwd",
-                 hipLaunchKernelGGL((head_fwd_kernel<T, false>), dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, (const T*)x, ldx, w, bias, y, npix, c, slope,
+                 hipLaunchKernelGGL((head_fwd_kernel<T, false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const T*)x, ldx, w, bias, y, npix, c, slope,
                                     (const double*)nullptr, (const float*)nullptr));
     SHM_LAUNCH_CHECK("shm_head_fwd");
     return SHM_OK;
@@ -147,12 +145,9 @@ extern "C" int shm_head_bwd(const void* x, int ldx, const float* w, const float*
     if (npix == 0) return SHM_OK;
     int r = shm_zero(red, (size_t)SHM_LRELU_RED_SLOTS * (c + 1) * sizeof(double), stream);
     if (r) return r;
-    int PP = 256 / (c / 4);
-    long blocks = ((long)npix + (long)PP * 8 - 1) / ((long)PP * 8);
-    if (blocks > 4096) blocks = 4096;
-    if (blocks < 1) blocks = 1;
+    const int blocks = shm_grid_cap(npix, 256 / (c / 4) * 8, 4096);
     SHM_DISPATCH_G(dtype, "shm_head_bwd",
-                 hipLaunchKernelGGL((head_bwd_kernel<T, TG, false>), dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, (const T*)x, ldx, w, y, dy, (TG*)dx, lddx, red,
+                 hipLaunchKernelGGL((head_bwd_kernel<T, TG, false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const T*)x, ldx, w, y, dy, (TG*)dx, lddx, red,
                                     npix, c, slope, (const double*)nullptr, (const float*)nullptr, (float*)nullptr));
     SHM_LAUNCH_CHECK("shm_head_bwd");
     hipLaunchKernelGGL(head_fold_kernel, dim3(shm_cdiv(c + 1, 256)), dim3(256), 0, (hipStream_t)stream, (const double*)red, dw_acc, db_acc, c);
@@ -202,15 +197,6 @@ extern "C" int shm_head_in_bwd(const void* a, int lda, const double* stats, cons
 }
 
 // ------------------------------------------------------------------------ PatchGAN logits
-__device__ __forceinline__ float block_sum_256(float v) {
-    __shared__ float ws[4];
-    v = shm_wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ws[0] + ws[1] + ws[2] + ws[3];
-}
-
 // one block per output pixel
 template <typename T>
 __global__ __launch_bounds__(256) void patch_fwd_kernel(const T* __restrict__ x, int ldx, const float* __restrict__ w, float* __restrict__ y, int h, int wd, int c, float slope) {
@@ -228,7 +214,7 @@ __global__ __launch_bounds__(256) void patch_fwd_kernel(const T* __restrict__ x,
             s += xv[0] * wv[0] + xv[1] * wv[1] + xv[2] * wv[2] + xv[3] * wv[3];
         }
     }
-    s = block_sum_256(s);
+    s = shm_block_sum<256>(s);
     if (threadIdx.x == 0) y[q] = shm_lrelu(s, slope);
 }
 
@@ -364,7 +350,7 @@ __global__ __launch_bounds__(256) void dense_fwd_kernel(const T* __restrict__ x,
         }
     }
     for (int j = 0; j < nout; ++j) {
-        float s = block_sum_256(acc[j]);
+        float s = shm_block_sum<256>(acc[j]);
         if (threadIdx.x == 0) y[(size_t)n * nout + j] = s;
     }
 }

@@ -15,7 +15,7 @@
 #define Y2R_U_B 2.03206185f
 
 constexpr int NSUM = 19;    // 6 L1 + content + 6 gram(cycED) + 6 gram(ds4)
-constexpr int WIN = 11;
+constexpr int WIN = SHM_SSIM_WIN;
 constexpr int TILE = 16;
 constexpr int HALO = TILE + WIN - 1;   // 26
 
@@ -49,15 +49,6 @@ __device__ __forceinline__ unsigned f2ord(float f) {
 }
 __device__ __forceinline__ float ord2f(unsigned u) {
     return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
-}
-
-__device__ __forceinline__ double block_sum_d2(double v) {
-    __shared__ double ws[4];
-    v = shm_wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ws[0] + ws[1] + ws[2] + ws[3];
 }
 
 // ------------------------------------------------------------------- pass A: pixel sums
@@ -119,7 +110,7 @@ __global__ __launch_bounds__(256) void img_pass_a(const ImgArgs a) {
     }
 #pragma unroll
     for (int i = 0; i < NSUM; ++i) {
-        double s = block_sum_d2(sm[i]);
+        double s = shm_block_sum<256>(sm[i]);
         if (threadIdx.x == 0) atomicAdd(&a.sums[(size_t)b * NSUM + i], s);
     }
 #pragma unroll
@@ -164,16 +155,6 @@ __global__ void img_style_grad(const ImgArgs a) {
 }
 
 // ------------------------------------------------------------------------ SSIM forward
-__device__ __forceinline__ void gauss1d(float* w) {   // 11 taps, sigma 1.5, normalised
-    float s = 0.f;
-    for (int i = 0; i < WIN; ++i) {
-        float c = (float)i - 5.0f;
-        w[i] = expf(-0.5f * c * c / 2.25f);
-        s += w[i];
-    }
-    for (int i = 0; i < WIN; ++i) w[i] /= s;
-}
-
 // value of channel c of cyc_yuv_k at (b,p)
 __device__ __forceinline__ float cyc_val(const ImgArgs& a, int b, int k, int c, size_t p, size_t npix) {
     if (c == 0) return a.cyc_y[((size_t)k * a.batch + b) * npix + p];
@@ -193,7 +174,7 @@ __global__ __launch_bounds__(256) void ssim_fwd_kernel(const ImgArgs a) {
     const float xmn = ord2f(a.mm[((size_t)b * 10 + k) * 2]), xmx = ord2f(a.mm[((size_t)b * 10 + k) * 2 + 1]);
     const float ymn = ord2f(a.mm[((size_t)b * 10 + 5 + k) * 2]), ymx = ord2f(a.mm[((size_t)b * 10 + 5 + k) * 2 + 1]);
     const float xr = xmx > xmn ? xmx - xmn : 0.f, yr = ymx > ymn ? ymx - ymn : 0.f;
-    if (threadIdx.x == 0) gauss1d(w1);
+    if (threadIdx.x == 0) shm_ssim_gauss1d(w1);
     const int oy0 = ty * TILE, ox0 = tx * TILE;
     for (int i = threadIdx.x; i < HALO * HALO; i += 256) {
         int r = i / HALO, cc = i % HALO;
@@ -254,7 +235,7 @@ __global__ __launch_bounds__(256) void ssim_fwd_kernel(const ImgArgs a) {
         dm[no] = dexy;
         dm[2 * no] = desq;
     }
-    sval = block_sum_d2(sval);
+    sval = shm_block_sum<256>(sval);
     if (threadIdx.x == 0) atomicAdd(&a.ssim_sum[bk], sval);
 }
 
@@ -291,7 +272,7 @@ __global__ __launch_bounds__(256) void ssim_bwd_kernel(const ImgArgs a) {
     const float xmn = ord2f(a.mm[((size_t)b * 10 + k) * 2]), xmx = ord2f(a.mm[((size_t)b * 10 + k) * 2 + 1]);
     const float ymn = ord2f(a.mm[((size_t)b * 10 + 5 + k) * 2]), ymx = ord2f(a.mm[((size_t)b * 10 + 5 + k) * 2 + 1]);
     const float xr = xmx > xmn ? xmx - xmn : 0.f, yr = ymx > ymn ? ymx - ymn : 0.f;
-    if (threadIdx.x == 0) gauss1d(w1);
+    if (threadIdx.x == 0) shm_ssim_gauss1d(w1);
     const int qy0 = ty * TILE, qx0 = tx * TILE;
     // outputs p in [q-10, q]: LDS tile origin = q0 - 10
     const float* dm = a.dmaps + ((size_t)bk * 3 + c) * 3 * no;
@@ -352,8 +333,8 @@ __global__ __launch_bounds__(256) void ssim_bwd_kernel(const ImgArgs a) {
             if (xraw == xmx) a.argpos[bk * 2 + 1] = (int)p;
         }
     }
-    sdx = block_sum_d2(sdx);
-    sdxr = block_sum_d2(sdxr);
+    sdx = shm_block_sum<256>(sdx);
+    sdxr = shm_block_sum<256>(sdxr);
     if (threadIdx.x == 0) {
         atomicAdd(&a.rsum[bk * 2], sdx);
         atomicAdd(&a.rsum[bk * 2 + 1], sdxr);
@@ -458,8 +439,7 @@ extern "C" int shm_image_losses(const float* gen_rgb, const float* cyc_rgb, cons
     SHM_LAUNCH_CHECK("shm_image_losses(init)");
 
     const size_t npix = (size_t)s * s;
-    int nblk = (int)((npix + 1023) / 1024);
-    if (nblk > 256) nblk = 256;
+    const int nblk = shm_grid_cap(npix, 1024, 256);
     hipLaunchKernelGGL(img_pass_a, dim3(nblk, batch), dim3(256), 0, st, a);
     SHM_LAUNCH_CHECK("shm_image_losses(pass a)");
     hipLaunchKernelGGL(img_pass_b, dim3(1), dim3(64), 0, st, a);

@@ -32,7 +32,7 @@
 
 namespace {
 
-constexpr int MWIN = 11;
+constexpr int MWIN = SHM_SSIM_WIN;
 constexpr int MTILE = 16;
 constexpr int MHALO = MTILE + MWIN - 1;     // 26
 constexpr int NT = 256;                     // threads per block, all three kernels
@@ -66,16 +66,6 @@ MetricWs plan_metric_ws(int batch, int h, int wd) {
     w.ssim = off; off = align256(off + (size_t)batch * 3 * ssim_tiles(h, wd) * sizeof(double));
     w.total = off;
     return w;
-}
-
-// sum over the block's 256 threads in a fixed order (wave shuffles, then the four wave sums in wave order)
-__device__ __forceinline__ double block_sum_fixed(double v) {
-    __shared__ double part[NT / 64];
-    v = shm_wave_sum(v);
-    __syncthreads();                          // the previous call's readers are done
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return part[0] + part[1] + part[2] + part[3];
 }
 
 // ---- tfio rgb_to_lab (D65, 2 degree observer), restated
@@ -142,9 +132,9 @@ __global__ __launch_bounds__(NT) void metrics_pixel_kernel(const float* __restri
         const double e2 = (double)dL * dL + (dC / sc) * (dC / sc) + dH2 / (sh * sh);
         e94 += (float)sqrt(e2 > 0.0 ? e2 : 0.0);
     }
-    const double s0 = block_sum_fixed((double)sq);
-    const double s1 = block_sum_fixed((double)e76);
-    const double s2 = block_sum_fixed((double)e94);
+    const double s0 = shm_block_sum<NT>((double)sq);
+    const double s1 = shm_block_sum<NT>((double)e76);
+    const double s2 = shm_block_sum<NT>((double)e94);
     gmn = shm_wave_min(gmn);
     gmx = shm_wave_max(gmx);
     tmn = shm_wave_min(tmn);
@@ -174,17 +164,6 @@ __global__ __launch_bounds__(NT) void metrics_pixel_kernel(const float* __restri
 }
 
 // ----------------------------------------------------------------------------------- ssim pass
-// 11 taps, sigma 1.5, normalised: the same taps and arithmetic as gauss1d of imgloss.hip
-__device__ __forceinline__ void metrics_gauss1d(float* w) {
-    float s = 0.f;
-    for (int i = 0; i < MWIN; ++i) {
-        float c = (float)i - 5.0f;
-        w[i] = expf(-0.5f * c * c / 2.25f);
-        s += w[i];
-    }
-    for (int i = 0; i < MWIN; ++i) w[i] /= s;
-}
-
 // grid (tiles, B, 3); ssim[b][c][tile] = sum over the tile's valid outputs of luminance * contrast-structure
 __global__ __launch_bounds__(NT) void metrics_ssim_kernel(const float* __restrict__ g, const float* __restrict__ t, const float* __restrict__ mm,
                                                          double* __restrict__ ssim, const MetricWin win, size_t frame, int np) {
@@ -216,7 +195,7 @@ __global__ __launch_bounds__(NT) void metrics_ssim_kernel(const float* __restric
         wmm[threadIdx.x >> 6][2] = r2;
         wmm[threadIdx.x >> 6][3] = r3;
     }
-    if (threadIdx.x == 0) metrics_gauss1d(w1);
+    if (threadIdx.x == 0) shm_ssim_gauss1d(w1);
     __syncthreads();
     float xmn = wmm[0][0], xmx = wmm[0][1], ymn = wmm[0][2], ymx = wmm[0][3];
     for (int w = 1; w < NT / 64; ++w) {
@@ -275,7 +254,7 @@ __global__ __launch_bounds__(NT) void metrics_ssim_kernel(const float* __restric
         const float A2 = 2.f * exy - 2.f * mx_ * my_ + c2, B2 = esq - mx_ * mx_ - my_ * my_ + c2;
         v = (double)((A1 / B1) * (A2 / B2));
     }
-    v = block_sum_fixed(v);
+    v = shm_block_sum<NT>(v);
     if (threadIdx.x == 0) ssim[((size_t)b * 3 + c) * ntiles + blockIdx.x] = v;
 }
 
@@ -292,10 +271,10 @@ __global__ __launch_bounds__(NT) void metrics_finalize_kernel(const double* __re
         a2 += q[2];
     }
     for (int i = threadIdx.x; i < 3 * ntiles; i += NT) a3 += ssim[(size_t)b * 3 * ntiles + i];
-    a0 = block_sum_fixed(a0);
-    a1 = block_sum_fixed(a1);
-    a2 = block_sum_fixed(a2);
-    a3 = block_sum_fixed(a3);
+    a0 = shm_block_sum<NT>(a0);
+    a1 = shm_block_sum<NT>(a1);
+    a2 = shm_block_sum<NT>(a2);
+    a3 = shm_block_sum<NT>(a3);
     if (threadIdx.x == 0) {
         const double npix = (double)h * w, nssim = (double)(h - MWIN + 1) * (double)(w - MWIN + 1);
         const double mse = a0 / (3.0 * npix);

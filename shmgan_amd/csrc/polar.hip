@@ -161,8 +161,7 @@ extern "C" int shm_polar_maps(const float* const* view_ptrs, size_t n, const flo
     for (int i = 0; i < 12; ++i) a.coef[i] = coef[i];
     const bool vec = n % 4 == 0 && (bits & 15) == 0;
     const size_t items = vec ? n / 4 : n;
-    const size_t want = (items + PL_NT - 1) / PL_NT;
-    const dim3 grid((unsigned)(want < (size_t)PL_MAPS_BLOCKS ? want : (size_t)PL_MAPS_BLOCKS)), block(PL_NT);
+    const dim3 grid(shm_grid_cap(items, PL_NT, PL_MAPS_BLOCKS)), block(PL_NT);
     hipStream_t st = (hipStream_t)stream;
     if (vec)
         hipLaunchKernelGGL(polar_maps_kernel<true>, grid, block, 0, st, a, n);

@@ -1,14 +1,7 @@
-// Elementwise kernels of the SpecSeg mask network (inference only; SpecSeg.py:27-98, called at
-// SHM.py:492) and the specular loss it feeds (SHM.py:792-806).  The 3x3 conv + ReLU layers and the
+// Elementwise kernels of the SpecSeg mask network's forward pass (SpecSeg.py:27-98, called at
+// SHM.py:492; training adds specseg_train.hip) and the specular loss it feeds (SHM.py:792-806).  The 3x3 conv + ReLU layers and the
 // 2x2 stride-2 Conv2DTranspose run on the tap GEMM (conv_igemm.hip); everything here is HBM-bound.
 #include "common.h"
-
-static int grid_cap(size_t n, int per_block = 256, int cap = 8192) {
-    long g = (long)((n + per_block - 1) / per_block);
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (int)g;
-}
 
 // ------------------------------------------------------------------ channel pack (1 -> 16 pitch)
 __global__ void pack_channels_kernel(const float* __restrict__ src, int ldsrc, int c0, int nc, float* __restrict__ dst, int lddst4, size_t total) {
@@ -27,7 +20,7 @@ extern "C" int shm_pack_channels(const float* src, int ldsrc, int c0, int nc, fl
     SHM_REQUIRE(lddst % 4 == 0 && nc <= lddst && c0 >= 0 && c0 + nc <= ldsrc, SHM_E_SHAPE, "shm_pack_channels: bad channel window");
     size_t total = npix * (lddst / 4);
     if (total == 0) return SHM_OK;
-    hipLaunchKernelGGL(pack_channels_kernel, dim3(grid_cap(total)), dim3(256), 0, (hipStream_t)stream, src, ldsrc, c0, nc, dst, lddst / 4, total);
+    hipLaunchKernelGGL(pack_channels_kernel, dim3(shm_grid_cap(total, 256, 8192)), dim3(256), 0, (hipStream_t)stream, src, ldsrc, c0, nc, dst, lddst / 4, total);
     SHM_LAUNCH_CHECK("shm_pack_channels");
     return SHM_OK;
 }
@@ -56,7 +49,7 @@ extern "C" int shm_bn_apply(const float* a, int lda, const float* gamma, const f
                             float* out, int ldo, size_t npix, int c, void* stream) {
     SHM_REQUIRE(c % 4 == 0 && lda % 4 == 0 && ldo % 4 == 0, SHM_E_SHAPE, "shm_bn_apply: channels/pitch must be multiples of 4");
     if (npix == 0 || c == 0) return SHM_OK;
-    hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_cap(npix * (c / 4))), dim3(256), 0, (hipStream_t)stream, a, lda, gamma, beta, mean, var, eps, out, ldo,
+    hipLaunchKernelGGL(bn_apply_kernel, dim3(shm_grid_cap(npix * (c / 4), 256, 8192)), dim3(256), 0, (hipStream_t)stream, a, lda, gamma, beta, mean, var, eps, out, ldo,
                        npix, c / 4);
     SHM_LAUNCH_CHECK("shm_bn_apply");
     return SHM_OK;
@@ -86,23 +79,25 @@ extern "C" int shm_maxpool2_fwd(const float* x, int ldx, float* y, int ldy, int 
     SHM_REQUIRE(h % 2 == 0 && w % 2 == 0, SHM_E_SHAPE, "shm_maxpool2_fwd: odd size %dx%d", h, w);
     size_t total = (size_t)batch * (h / 2) * (w / 2) * (c / 4);
     if (total == 0) return SHM_OK;
-    hipLaunchKernelGGL(maxpool2_kernel, dim3(grid_cap(total)), dim3(256), 0, (hipStream_t)stream, x, ldx, y, ldy, h, w, c / 4, total);
+    hipLaunchKernelGGL(maxpool2_kernel, dim3(shm_grid_cap(total, 256, 8192)), dim3(256), 0, (hipStream_t)stream, x, ldx, y, ldy, h, w, c / 4, total);
     SHM_LAUNCH_CHECK("shm_maxpool2_fwd");
     return SHM_OK;
 }
 
-// --------------------------------------------------------- Conv2D(1, 1x1, activation='sigmoid')
+// ------------------------------------------- Conv2D(1, 1x1): activation='sigmoid' (predict) or the logit (training)
+// c / 4 lanes across the channels (a power of two in 1..64), 256 / (c / 4) pixels side by side in a block
+template <bool SIGMOID>
 __global__ __launch_bounds__(256) void head_sigmoid_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ w, const float* __restrict__ bias,
                                                            float* __restrict__ y, size_t npix, int c) {
     const int lanes_c = c >> 2, PP = 256 / lanes_c;
     const int pp = threadIdx.x / lanes_c, cl = threadIdx.x % lanes_c;
-    f32x4 wv = *(const f32x4*)(w + cl * 4);
+    const f32x4 wv = *(const f32x4*)(w + cl * 4);
     const float b = bias ? bias[0] : 0.f;
     for (size_t p = (size_t)blockIdx.x * PP + pp; p < npix; p += (size_t)gridDim.x * PP) {
-        f32x4 xv = *(const f32x4*)(x + p * ldx + cl * 4);
+        const f32x4 xv = *(const f32x4*)(x + p * ldx + cl * 4);
         float s = xv[0] * wv[0] + xv[1] * wv[1] + xv[2] * wv[2] + xv[3] * wv[3];
         for (int o = lanes_c >> 1; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-        if (cl == 0) y[p] = 1.f / (1.f + expf(-(s + b)));
+        if (cl == 0) y[p] = SIGMOID ? 1.f / (1.f + expf(-(s + b))) : s + b;
     }
 }
 
@@ -110,11 +105,18 @@ extern "C" int shm_head_sigmoid_fwd(const float* x, int ldx, const float* w, con
     const int l = c / 4;
     SHM_REQUIRE(c % 4 == 0 && l >= 1 && l <= 64 && (l & (l - 1)) == 0 && ldx % 4 == 0, SHM_E_SHAPE, "shm_head_sigmoid_fwd: channels %d unsupported", c);
     if (npix == 0) return SHM_OK;
-    int PP = 256 / l;
-    long blocks = ((long)npix + PP - 1) / PP;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(head_sigmoid_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, x, ldx, w, bias, y, npix, c);
+    hipLaunchKernelGGL(head_sigmoid_kernel<true>, dim3(shm_grid_cap(npix, 256 / l, 8192)), dim3(256), 0, (hipStream_t)stream, x, ldx, w, bias, y, npix, c);
     SHM_LAUNCH_CHECK("shm_head_sigmoid_fwd");
+    return SHM_OK;
+}
+
+// the same head without its sigmoid, for training (the loss works on the logit)
+extern "C" int shm_head_logit_fwd(const float* x, int ldx, const float* w, const float* bias, float* z, size_t npix, int c, void* stream) {
+    SHM_REQUIRE(x && w && z, SHM_E_SHAPE, "shm_head_logit_fwd: null pointer");
+    SHM_REQUIRE(c >= 16 && c <= 256 && (c & (c - 1)) == 0 && ldx % 4 == 0 && ldx >= c, SHM_E_SHAPE, "shm_head_logit_fwd: channels %d / pitch %d unsupported", c, ldx);
+    if (npix == 0) return SHM_OK;
+    hipLaunchKernelGGL(head_sigmoid_kernel<false>, dim3(shm_grid_cap(npix, 256 / (c / 4), 8192)), dim3(256), 0, (hipStream_t)stream, x, ldx, w, bias, z, npix, c);
+    SHM_LAUNCH_CHECK("shm_head_logit_fwd");
     return SHM_OK;
 }
 
@@ -154,7 +156,7 @@ extern "C" int shm_spec_loss(const float* cyc_y, const float* cbcr, const float*
     if (n == 0) return SHM_OK;
     SpecPtrs P;
     for (int k = 0; k < 5; ++k) P.ds[k] = ds[k];
-    hipLaunchKernelGGL(spec_loss_kernel, dim3(grid_cap(n, 256, 256), 5), dim3(256), 0, (hipStream_t)stream, cyc_y, cbcr, P, mask, loss, n);
+    hipLaunchKernelGGL(spec_loss_kernel, dim3(shm_grid_cap(n, 256, 256), 5), dim3(256), 0, (hipStream_t)stream, cyc_y, cbcr, P, mask, loss, n);
     SHM_LAUNCH_CHECK("shm_spec_loss");
     return SHM_OK;
 }

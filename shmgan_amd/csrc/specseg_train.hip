@@ -5,8 +5,8 @@
 //   BatchNormalization, training mode       shm_bn_train_fwd / shm_bn_train_bwd
 //   MaxPooling2D(2) backward                shm_maxpool2_bwd
 //   Conv2DTranspose(2x2, stride 2) backward shm_conv2d_transpose2x2_dgrad / _wgrad   (MFMA GEMMs, v_mfma_f32_16x16x4_f32, LDS-staged)
-//   head: logit, its backward, the loss     shm_head_logit_fwd / shm_head_logit_bwd / shm_seg_loss
-//   Adam with the clip bound as an argument shm_adam
+//   head: its backward, the loss            shm_head_logit_bwd / shm_seg_loss   (the logit itself, shm_head_logit_fwd, is the predict head's kernel: specseg.hip)
+// The optimiser is shm_adam (color.hip).
 //
 // Reproducibility (the conventions of metrics.hip / telemetry.hip): every reduction keeps f64 partial sums, every block writes its partial
 // into a workspace slot of its own, the slots are summed in a fixed order (slot_sum below), and no kernel uses a global atomic: results are bitwise
@@ -20,24 +20,7 @@ namespace {
 constexpr int NT = 256;              // threads per block, every kernel of this file
 constexpr int MAXB = SHM_SST_MAX_BLOCKS;
 
-int grid_cap(size_t n, int per_block, int cap) {
-    size_t g = (n + per_block - 1) / per_block;
-    if (g > (size_t)cap) g = cap;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
 bool pow2_channels(int c) { return c >= 16 && c <= 256 && (c & (c - 1)) == 0; }
-
-// sum over the block's 256 threads in a fixed order (wave shuffles, then the four wave sums in wave order)
-__device__ __forceinline__ double block_sum_fixed(double v) {
-    __shared__ double part[NT / 64];
-    v = shm_wave_sum(v);
-    __syncthreads();                          // the previous call's readers are done
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return part[0] + part[1] + part[2] + part[3];
-}
 
 // ------------------------------------------------------------------------------------------- per-channel sums
 // One pass over a [npix, c] tensor (pitch lda; c a power of two in 16..256), c / 4 lanes across the channels (16-byte loads) and
@@ -118,7 +101,7 @@ __global__ __launch_bounds__(NT) void chan_sums_kernel(const float* __restrict__
 
 int chan_blocks(size_t npix, int c) {
     const int PP = NT / (c / 4);
-    return grid_cap(npix, PP * 4, MAXB);
+    return shm_grid_cap(npix, PP * 4, MAXB);
 }
 
 // Sum of value v of channel ch over the nblk slots by ONE WAVE (the finish kernels run a block of 64 threads per channel): lane i adds slots
@@ -393,20 +376,6 @@ Convt2WgradPlan plan_convt2_wgrad(int batch, int hi, int wi, int cin, int cout) 
 }
 
 // ------------------------------------------------------------------------------------------- head and loss
-__global__ __launch_bounds__(NT) void head_logit_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ w, const float* __restrict__ bias,
-                                                        float* __restrict__ z, size_t npix, int c) {
-    const int lanes_c = c >> 2, PP = NT / lanes_c;
-    const int pp = threadIdx.x / lanes_c, cl = threadIdx.x % lanes_c;
-    const f32x4 wv = *(const f32x4*)(w + cl * 4);
-    const float b = bias ? bias[0] : 0.f;
-    for (size_t p = (size_t)blockIdx.x * PP + pp; p < npix; p += (size_t)gridDim.x * PP) {
-        const f32x4 xv = *(const f32x4*)(x + p * ldx + cl * 4);
-        float s = xv[0] * wv[0] + xv[1] * wv[1] + xv[2] * wv[2] + xv[3] * wv[3];
-        for (int o = lanes_c >> 1; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-        if (cl == 0) z[p] = s + b;
-    }
-}
-
 // Per pixel, from the logit z and the target g, all in f64: p = sigmoid(z), q = 1 - p = sigmoid(-z), log p = -softplus(-z), log q = -softplus(z)
 // (finite at |z| = 40, where 1 - p rounds to 0 in fp32 and log(1 - p) would be -inf)
 struct SegPix {
@@ -442,7 +411,7 @@ __global__ __launch_bounds__(NT) void seg_loss_sums_kernel(const float* __restri
     }
 #pragma unroll
     for (int k = 0; k < SEG_NV; ++k) {
-        const double t = block_sum_fixed(s[k]);
+        const double t = shm_block_sum<NT>(s[k]);
         if (threadIdx.x == 0) part[(size_t)blockIdx.x * SEG_NV + k] = t;
     }
 }
@@ -455,7 +424,7 @@ __global__ __launch_bounds__(NT) void seg_loss_finish_kernel(const double* __res
     for (int k = 0; k < SEG_NV; ++k) {
         double a = 0.0;
         for (int i = threadIdx.x; i < nblk; i += NT) a += part[(size_t)i * SEG_NV + k];
-        t[k] = block_sum_fixed(a);
+        t[k] = shm_block_sum<NT>(a);
     }
     if (threadIdx.x == 0) {
 #pragma unroll
@@ -487,23 +456,6 @@ __global__ __launch_bounds__(NT) void seg_loss_grad_kernel(const float* __restri
     }
 }
 
-// -------------------------------------------------------------------------------------------------- Adam
-// adam_clip_kernel (color.hip) with the clip bound as an argument: the same expressions, so clip = 1 gives the same bits
-__global__ void adam_kernel(float* __restrict__ w, float* __restrict__ m, float* __restrict__ v, const float* __restrict__ g, size_t n, float alpha, float b1,
-                            float b2, float eps, float gscale, float clip) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (; i < n; i += stride) {
-        float gg = g[i] * gscale;
-        if (clip > 0.f) gg = fminf(fmaxf(gg, -clip), clip);
-        float mm = m[i] + (gg - m[i]) * (1.0f - b1);
-        float vv = v[i] + (gg * gg - v[i]) * (1.0f - b2);
-        m[i] = mm;
-        v[i] = vv;
-        w[i] = w[i] - alpha * mm / (sqrtf(vv) + eps);
-    }
-}
-
 }  // namespace
 
 // ====================================================================================================== entry points
@@ -529,7 +481,7 @@ extern "C" int shm_bn_train_fwd(const float* a, int lda, const float* gamma, con
     SHM_LAUNCH_CHECK("shm_bn_train_fwd");
     hipLaunchKernelGGL(bn_fwd_finish_kernel, dim3(fb), dim3(64), 0, st, ws, nblk, 1, save, moving_mean, moving_var, (double)momentum, (double)eps, (double)npix, c);
     SHM_LAUNCH_CHECK("shm_bn_train_fwd");
-    hipLaunchKernelGGL(bn_train_apply_kernel, dim3(grid_cap(npix * (c / 4), NT, 8192)), dim3(NT), 0, st, a, lda, gamma, beta, (const double*)save, out, ldo, npix, c);
+    hipLaunchKernelGGL(bn_train_apply_kernel, dim3(shm_grid_cap(npix * (c / 4), NT, 8192)), dim3(NT), 0, st, a, lda, gamma, beta, (const double*)save, out, ldo, npix, c);
     SHM_LAUNCH_CHECK("shm_bn_train_fwd");
     return SHM_OK;
 }
@@ -552,7 +504,7 @@ extern "C" int shm_bn_train_bwd(const float* dy, int lddy, const float* a, int l
     SHM_LAUNCH_CHECK("shm_bn_train_bwd");
     hipLaunchKernelGGL(bn_bwd_finish_kernel, dim3(c), dim3(64), 0, st, (const double*)ws, nblk, stat, dgamma, dbeta, c);
     SHM_LAUNCH_CHECK("shm_bn_train_bwd");
-    hipLaunchKernelGGL(bn_train_bwd_apply_kernel, dim3(grid_cap(npix * (c / 4), NT, 8192)), dim3(NT), 0, st, dy, lddy, a, lda, gamma, save, (const double*)stat, dx,
+    hipLaunchKernelGGL(bn_train_bwd_apply_kernel, dim3(shm_grid_cap(npix * (c / 4), NT, 8192)), dim3(NT), 0, st, dy, lddy, a, lda, gamma, save, (const double*)stat, dx,
                        lddx, npix, c);
     SHM_LAUNCH_CHECK("shm_bn_train_bwd");
     return SHM_OK;
@@ -565,7 +517,7 @@ extern "C" int shm_maxpool2_bwd(const float* x, int ldx, const float* dy, int ld
                 "shm_maxpool2_bwd: channels/pitch must be multiples of 4, pitch >= channels");
     SHM_REQUIRE(batch >= 1 && h >= 2 && w >= 2 && h % 2 == 0 && w % 2 == 0, SHM_E_SHAPE, "shm_maxpool2_bwd: bad size %d x %d x %d", batch, h, w);
     const size_t total = (size_t)batch * (h / 2) * (w / 2) * (c / 4);
-    hipLaunchKernelGGL(maxpool2_bwd_kernel, dim3(grid_cap(total, NT, 8192)), dim3(NT), 0, (hipStream_t)stream, x, ldx, dy, lddy, dx, lddx, h, w, c / 4, total,
+    hipLaunchKernelGGL(maxpool2_bwd_kernel, dim3(shm_grid_cap(total, NT, 8192)), dim3(NT), 0, (hipStream_t)stream, x, ldx, dy, lddy, dx, lddx, h, w, c / 4, total,
                        accumulate);
     SHM_LAUNCH_CHECK("shm_maxpool2_bwd");
     return SHM_OK;
@@ -612,7 +564,7 @@ extern "C" int shm_conv2d_transpose2x2_wgrad(const float* x, int ldx, const floa
                        p.cps);
     SHM_LAUNCH_CHECK("shm_conv2d_transpose2x2_wgrad");
     const size_t n = (size_t)4 * cout * cin;
-    hipLaunchKernelGGL(convt2_wgrad_reduce_kernel, dim3(grid_cap(n, NT, 4096)), dim3(NT), 0, st, (const float*)part, dw, n, p.nsplit);
+    hipLaunchKernelGGL(convt2_wgrad_reduce_kernel, dim3(shm_grid_cap(n, NT, 4096)), dim3(NT), 0, st, (const float*)part, dw, n, p.nsplit);
     SHM_LAUNCH_CHECK("shm_conv2d_transpose2x2_wgrad");
     if (dbias) {
         double* bp = (double*)ws;
@@ -625,16 +577,6 @@ extern "C" int shm_conv2d_transpose2x2_wgrad(const float* x, int ldx, const floa
         hipLaunchKernelGGL(chan_finish_kernel, dim3(cout), dim3(64), 0, st, (const double*)bp, nblk, 1, 0, cout, dbias);
         SHM_LAUNCH_CHECK("shm_conv2d_transpose2x2_wgrad");
     }
-    return SHM_OK;
-}
-
-extern "C" int shm_head_logit_fwd(const float* x, int ldx, const float* w, const float* bias, float* z, size_t npix, int c, void* stream) {
-    SHM_REQUIRE(x && w && z, SHM_E_SHAPE, "shm_head_logit_fwd: null pointer");
-    SHM_REQUIRE(pow2_channels(c) && ldx % 4 == 0 && ldx >= c, SHM_E_SHAPE, "shm_head_logit_fwd: channels %d / pitch %d unsupported", c, ldx);
-    if (npix == 0) return SHM_OK;
-    const int PP = NT / (c / 4);
-    hipLaunchKernelGGL(head_logit_kernel, dim3(grid_cap(npix, PP, 8192)), dim3(NT), 0, (hipStream_t)stream, x, ldx, w, bias, z, npix, c);
-    SHM_LAUNCH_CHECK("shm_head_logit_fwd");
     return SHM_OK;
 }
 
@@ -663,24 +605,15 @@ extern "C" int shm_seg_loss(const float* z, const float* g, float* dz, double* o
     SHM_REQUIRE(ws_bytes >= SHM_SEG_LOSS_WS_DOUBLES * sizeof(double), SHM_E_WORKSPACE, "shm_seg_loss: workspace %zu < %zu bytes", ws_bytes,
                 (size_t)SHM_SEG_LOSS_WS_DOUBLES * sizeof(double));
     hipStream_t st = (hipStream_t)stream;
-    const int nblk = grid_cap(npix, NT * 4, MAXB);
+    const int nblk = shm_grid_cap(npix, NT * 4, MAXB);
     double* tot = ws + (size_t)MAXB * SEG_NV;
     hipLaunchKernelGGL(seg_loss_sums_kernel, dim3(nblk), dim3(NT), 0, st, z, g, ws, npix);
     SHM_LAUNCH_CHECK("shm_seg_loss");
     hipLaunchKernelGGL(seg_loss_finish_kernel, dim3(1), dim3(NT), 0, st, (const double*)ws, nblk, tot, out, (double)npix);
     SHM_LAUNCH_CHECK("shm_seg_loss");
     if (dz) {
-        hipLaunchKernelGGL(seg_loss_grad_kernel, dim3(grid_cap(npix, NT, 8192)), dim3(NT), 0, st, z, g, (const double*)tot, dz, npix);
+        hipLaunchKernelGGL(seg_loss_grad_kernel, dim3(shm_grid_cap(npix, NT, 8192)), dim3(NT), 0, st, z, g, (const double*)tot, dz, npix);
         SHM_LAUNCH_CHECK("shm_seg_loss");
     }
-    return SHM_OK;
-}
-
-extern "C" int shm_adam(float* w, float* m, float* v, const float* g, size_t n, float alpha, float beta1, float beta2, float eps, float gscale, float clip,
-                        void* stream) {
-    if (n == 0) return SHM_OK;
-    SHM_REQUIRE(w && m && v && g, SHM_E_SHAPE, "shm_adam: null pointer");
-    hipLaunchKernelGGL(adam_kernel, dim3(grid_cap(n, 256, 8192)), dim3(256), 0, (hipStream_t)stream, w, m, v, g, n, alpha, beta1, beta2, eps, gscale, clip);
-    SHM_LAUNCH_CHECK("shm_adam");
     return SHM_OK;
 }

@@ -188,21 +188,9 @@ __global__ __launch_bounds__(TS_NT) void tensor_stats_chunk_kernel(const TsArgs 
     }
 }
 
-// sum over the block's threads in a fixed order: wave shuffles, then the wave sums in wave order (the convention of metrics.hip)
-__device__ __forceinline__ double ts_block_sum(double v) {
-    __shared__ double part[TS_FNT / 64];
-    v = shm_wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double r = part[0];
-    for (int w = 1; w < TS_FNT / 64; ++w) r += part[w];
-    return r;
-}
-
 // grid (nseg).  The integer words of a slot are read 16 bytes at a time: 24 threads cover a slot, TS_FGROUPS such groups take the
 // segment's chunks round-robin (a 3x3x512x1024 kernel has 576 of them), LDS adds the groups.  Integer sums do not depend on the order;
-// the f64 sums go through ts_block_sum: every thread a fixed stride of slots in chunk order, then the block in thread order.
+// the f64 sums go through shm_block_sum: every thread a fixed stride of slots in chunk order, then the block in thread order.
 __global__ __launch_bounds__(TS_FNT) void tensor_stats_finalize_kernel(const TsArgs a) {
     __shared__ unsigned long long cnt[TS_FGROUPS][TS_SLOT_WORDS];
     __shared__ float gmn[TS_FGROUPS], gmx[TS_FGROUPS];
@@ -238,8 +226,8 @@ __global__ __launch_bounds__(TS_FNT) void tensor_stats_finalize_kernel(const TsA
         sv += sums[(size_t)c * 2];
         qv += sums[(size_t)c * 2 + 1];
     }
-    sv = ts_block_sum(sv);                                   // its barriers also publish cnt / gmn / gmx
-    qv = ts_block_sum(qv);
+    sv = shm_block_sum<TS_FNT>(sv);                             // its barriers also publish cnt / gmn / gmx
+    qv = shm_block_sum<TS_FNT>(qv);
     if (threadIdx.x < TS_BINS + 2) {
         unsigned long long c = 0;
         for (int k = 0; k < TS_FGROUPS; ++k) c += cnt[k][threadIdx.x];

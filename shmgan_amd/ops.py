@@ -6,6 +6,8 @@ their device pointers to libshmgan_hip.so on torch's current stream and returns 
 """
 from __future__ import annotations
 
+import math
+
 import torch
 
 from ._lib import check, lib
@@ -822,6 +824,14 @@ def running_scale_mean(scale, acc, mul):
     return mul
 
 
+def adam_alpha(lr0, beta_1, beta_2, iterations):
+    """The `alpha` of adam_clip / adam after `iterations` updates: Keras Adam's step size on ExponentialDecay(lr0, 10000, 0.95)
+    (SHM.py:169-175)."""
+    t = iterations + 1
+    lr = lr0 * 0.95 ** (iterations / 10000.0)
+    return lr * math.sqrt(1.0 - beta_2 ** t) / (1.0 - beta_1 ** t)
+
+
 def adam_clip(w, m, v, g, n, alpha, beta1, beta2, eps, gscale, abort=None):
     """abort: the step's AbortWords; the kernel applies nothing while their device word is set."""
     _timed_bytes("shm_adam_clip", 7.0 * 4 * n, lambda: check(          # read w, m, v, g; write w, m, v
@@ -919,7 +929,7 @@ def seg_loss(z, g, dz, out, ws, npix):
 
 
 def adam(w, m, v, g, n, alpha, beta1, beta2, eps, gscale=1.0, clip=0.0):
-    """adam_clip with the clip bound as an argument (clip <= 0: none)."""
+    """adam_clip's kernel with the clip bound as an argument (clip <= 0: none) and no abort word."""
     check(lib().shm_adam(_p(w), _p(m), _p(v), _p(g), n, alpha, beta1, beta2, eps, gscale, clip, _stream()), "shm_adam")
 
 

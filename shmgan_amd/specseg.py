@@ -17,8 +17,6 @@ the schedule of SHM.py:169-175.  `predict` / `forward_plane` are untouched by it
 """
 from __future__ import annotations
 
-import math
-
 import numpy as np
 import torch
 
@@ -359,10 +357,7 @@ class SpecSeg:
         return self.grad
 
     def alpha(self, iterations):
-        """Keras Adam's step size on ExponentialDecay(lr0, 10000, 0.95) (SHM.py:169-175; the trainer's _Optimizer)."""
-        t = iterations + 1
-        lr = self.lr0 * 0.95 ** (iterations / 10000.0)
-        return lr * math.sqrt(1.0 - self.beta_2 ** t) / (1.0 - self.beta_1 ** t)
+        return ops.adam_alpha(self.lr0, self.beta_1, self.beta_2, iterations)
 
     def configure_optimizer(self, lr=None, beta1=None, beta2=None):
         if lr is not None:

@@ -18,7 +18,6 @@ the generator backward) and scaled by 1/world inside the clip+Adam kernel.
 from __future__ import annotations
 
 import ctypes as C
-import math
 from types import SimpleNamespace
 
 import numpy as np
@@ -39,9 +38,7 @@ class _Optimizer:
         self.lr0, self.beta_1, self.beta_2, self.epsilon = lr0, beta_1, beta_2, epsilon
 
     def alpha(self, iterations):
-        t = iterations + 1
-        lr = self.lr0 * 0.95 ** (iterations / 10000.0)
-        return lr * math.sqrt(1.0 - self.beta_2 ** t) / (1.0 - self.beta_1 ** t)
+        return ops.adam_alpha(self.lr0, self.beta_1, self.beta_2, iterations)
 
     def apply(self, P, gscale=1.0, abort=None):
         """abort: the ops.AbortWords of the step that made P.grad: no update while their device word is set."""

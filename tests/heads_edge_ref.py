@@ -77,8 +77,8 @@ def _colsum(a):
 # generator head, plain and with InstanceNorm folded in, and SpecSeg's sigmoid head (the same lane mapping)
 
 HEAD_C = (4, 8, 64, 256)
-HEAD_FWD_CAP = 8192          # heads.hip shm_head_fwd / shm_head_in_fwd, specseg.hip shm_head_sigmoid_fwd: "if (blocks > 8192)", "8192 / batch"
-HEAD_BWD_CAP = 4096          # heads.hip shm_head_bwd / shm_head_in_bwd: "if (blocks > 4096)", "4096 / batch"
+HEAD_FWD_CAP = 8192          # heads.hip shm_head_fwd / shm_head_in_fwd, specseg.hip shm_head_sigmoid_fwd: "shm_grid_cap(npix, ..., 8192)", "8192 / batch"
+HEAD_BWD_CAP = 4096          # heads.hip shm_head_bwd / shm_head_in_bwd: "shm_grid_cap(npix, ..., 4096)", "4096 / batch"
 HEAD_BWD_ITERS = 8           # the same two: blocks = cdiv(npix, PP * 8)
 HEAD_BWD_U = 4               # heads.hip head_bwd_kernel: "constexpr int U = 4"
 HEAD_IN_BATCH = 3
@@ -310,8 +310,8 @@ def lrelu_special_ok(dz, k, tol):
 # ---------------------------------------------------------------------------------------------------------------------------------------
 # SpecSeg passes (SpecSeg.py:27-98) and the specular loss (SHM.py:792-806)
 
-SPEC_GRID = 8192 * 256            # specseg.hip grid_cap: "int per_block = 256, int cap = 8192"
-SPEC_LOSS_GRID = 256 * 256        # specseg.hip shm_spec_loss: "grid_cap(n, 256, 256)"
+SPEC_GRID = 8192 * 256            # specseg.hip: "shm_grid_cap(total, 256, 8192)"
+SPEC_LOSS_GRID = 256 * 256        # specseg.hip shm_spec_loss: "shm_grid_cap(n, 256, 256)"
 BN_EPS = float(np.float32(1e-3))
 SPEC_PITCH_MAP = (2, 6, 10, 8)    # batch, h, w, c; lda = c + 4, ldo = c + 8
 # Sixteen channels are four vectors a pixel, so no pixel count gives 8192 * 256 + 77 vectors; this map gives 8192 * 256 + 1000: the
@@ -378,7 +378,7 @@ def spec_loss_ref(k, dtype=torch.float64, pixels=None):
 # ---------------------------------------------------------------------------------------------------------------------------------------
 # casts
 
-CAST_GRID = 4096 * 256            # elem.hip shm_cast_f32: "if (blocks > 4096) blocks = 4096"
+CAST_GRID = 4096 * 256            # elem.hip shm_cast_f32: "shm_grid_cap(n, 256, 4096)"
 CAST_SIZES = (1, 255, CAST_GRID + 77)
 # float32 bit patterns: ties between two bf16 neighbours (to even: down, up) and one bit off them, +-0, subnormals (smallest, largest, a
 # tie), the largest finite float (rounds to Inf) and the largest finite bf16, +-Inf, a quiet NaN and a NaN whose payload sits in the low 16

@@ -28,15 +28,19 @@ def test_constants_are_the_sources():
     kernel file was reformatted or a name changed is no regression of the kernels: re-read the cap at the source line the constant's comment
     names, update heads_edge_ref.py (and the snippet below) to it, and check that the case tables still reach past it."""
     heads, spec, elem, gs, eh = ((CSRC / n).read_text() for n in ("heads.hip", "specseg.hip", "elem.hip", "grad_sums.hip", "elem.h"))
-    assert f"blocks > {R.HEAD_FWD_CAP}" in heads and f"{R.HEAD_FWD_CAP} / batch" in heads and f"blocks > {R.HEAD_FWD_CAP}" in spec
-    assert f"blocks > {R.HEAD_BWD_CAP}" in heads and f"{R.HEAD_BWD_CAP} / batch" in heads and f"(long)PP * {R.HEAD_BWD_ITERS}" in heads
+    assert f"shm_grid_cap(npix, 256 / (c / 4), {R.HEAD_FWD_CAP})" in heads and f"{R.HEAD_FWD_CAP} / batch" in heads
+    assert f"shm_grid_cap(npix, 256 / l, {R.HEAD_FWD_CAP})" in spec
+    assert f"shm_grid_cap(npix, 256 / (c / 4) * {R.HEAD_BWD_ITERS}, {R.HEAD_BWD_CAP})" in heads and f"{R.HEAD_BWD_CAP} / batch" in heads
+    assert f"(long)PP * {R.HEAD_BWD_ITERS}" in heads
     assert f"constexpr int U = {R.HEAD_BWD_U};" in heads and "PP = 256 / lanes_c" in eh and "lanes_c = c >> 2" in eh
     assert f"n += {R.PATCH_SAMPLE_STRIDE})" in heads and f"blockIdx.y * {R.PATCH_CH_PER_BLOCK}" in heads
     assert f"n + {R.DENSE_UNROLL} <= batch" in heads and "48 * 1024" in heads and R.DENSE_LDS_BYTES == 48 * 1024
     assert "nout == 5 && (k & 3) == 0" in heads
     assert f"pix_chunks((long)npix, 1, c, {R.LRELU_BLOCKS})" in gs and "U = sizeof(T) == 2 ? 8 : 4" in gs and "blocks > 4096 ? 8 : 16" in eh
-    assert "int per_block = 256, int cap = 8192" in spec and "grid_cap(n, 256, 256)" in spec and R.SPEC_GRID == 8192 * 256
-    assert "if (blocks > 4096) blocks = 4096;" in elem and R.CAST_GRID == 4096 * 256
+    assert spec.count("shm_grid_cap(total, 256, 8192)") == 2 and "shm_grid_cap(npix * (c / 4), 256, 8192)" in spec and R.SPEC_GRID == 8192 * 256
+    assert "shm_grid_cap(n, 256, 256)" in spec and R.SPEC_LOSS_GRID == 256 * 256
+    assert "shm_grid_cap(n, 256, 4096)" in elem and R.CAST_GRID == 4096 * 256
+    assert "if (g > (size_t)cap) g = cap;" in (CSRC / "common.h").read_text()
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ heads

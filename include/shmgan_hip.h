@@ -631,6 +631,32 @@ int shm_polar_views_u8(const unsigned char* const* src_ptrs, int hin, int win, c
 int shm_augment_views_u8(const unsigned char* const* src_ptrs, int n_src, int hin, int win, int mode, const float* coef,
                          const float* mix, float crop_y, float crop_x, float crop_h, float crop_w, int flip_ud, int flip_lr,
                          float* const* dst_ptrs, int ho, int wo, float scale, void* stream);
+/* shm_augment_views_u8 for a whole batch: sample i of `samples` (a host array of n >= 1 descriptors, read during the call) is
+ * resampled into slice i of five float32 [n,ho,wo,3] tensors, dst_ptrs[p] + i * sample_stride (floats) being its plane p.  One
+ * launch per SHM_AUG_GROUP samples, grid (cdiv(ho*wo, 256), samples of the group): every block row reads its own descriptor, which
+ * travels to the kernel by value; n may exceed the group and is cut into cdiv(n, SHM_AUG_GROUP) launches.
+ *   descriptor   src: n_src device pointers to uint8 [hin,win,3] images (src[4] is read only with SHM_AUG_DIR); hin, win and the crop
+ *          are the sample's own; flip_ud, flip_lr and mix are flags (nonzero = on); plane[v] is the destination plane of view v =
+ *          0..3, a permutation of 0..3 (identity (0,1,2,3); a mirror that exchanges two polariser angles exchanges their planes).
+ *          Plane 4 is always plane 4.
+ *   shared   n_src, mode, coef, scale, ho, wo as shm_augment_views_u8; mix: a host float[16] used by the samples whose mix flag is
+ *          set, and may be null when none is.
+ * The bits written for a sample are those of shm_augment_views_u8 called for that sample alone with dst_ptrs permuted by `plane`
+ * (the same per-pixel code: csrc/augment_px.h), so at identity parameters those of shm_resize_bilinear_u8 / shm_polar_views_u8.
+ * SHM_E_SHAPE for n < 1, a null array or destination, an unknown mode, an n_src that does not fit it, ho or wo outside [1, 32768],
+ * a sample_stride below ho*wo*3 with n > 1, SHM_POLAR_STOKES without coef, and per sample -- the message names its index -- a null
+ * source, hin or win outside [1, 32768], an empty crop or one outside the image (checked in double; a NaN fails), a mix flag
+ * without mix, or planes that are no permutation of 0..3.  Every sample is checked before the first launch. */
+#define SHM_AUG_GROUP 8
+typedef struct shm_aug_sample {
+    const unsigned char* src[5];
+    int hin, win;
+    float crop_y, crop_x, crop_h, crop_w;
+    int flip_ud, flip_lr, mix;
+    int plane[4];
+} shm_aug_sample;
+int shm_augment_batch_u8(const shm_aug_sample* samples, int n, int n_src, int mode, const float* coef, const float* mix,
+                         float* const* dst_ptrs, size_t sample_stride, int ho, int wo, float scale, void* stream);
 /* Stokes maps of four float32 views of n elements each (any shape: the loaded RGB views or their Y channels).  view_ptrs: host
  * array of 4 device pointers; coef: host float[12], the 3x4 matrix above.  Per element (S0, S1, S2) = C (v0..v3) and
  *   s0 = S0;  dop = sqrt(S1^2 + S2^2) / S0, 0 where S0 == 0 (divide_no_nan, as calcDOP);  aolp = 0.5 atan2f(S2, S1)

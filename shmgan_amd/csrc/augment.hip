@@ -11,15 +11,10 @@
 //                          is mirror-invariant) and a fifth source is never mixed.
 // One thread per output pixel, 4 taps x n_src x 3 byte loads; pointers and the two small matrices travel by value.  At identity
 // parameters the arithmetic is that of resize_bilinear_u8_kernel / polar_views_u8_kernel to the bit: the same expressions, + 0.0f.
-#include "common.h"
-#include "polar_est.h"
-
-#include <math.h>
+// The per-pixel body is augment_px.h, which the batched kernel (augment_batch.hip) includes too.
+#include "augment_px.h"
 
 namespace {
-
-constexpr int AU_NT = 256;
-constexpr int AU_DIM_MAX = 32768;               // hin, win, ho, wo
 
 struct AugmentArgs {
     const unsigned char* src[5];                // [4] only for SHM_AUG_DIR
@@ -31,56 +26,9 @@ struct AugmentArgs {
 template <int MODE, bool MIX>
 __global__ void __launch_bounds__(AU_NT) augment_views_u8_kernel(const AugmentArgs a, int hin, int win, int ho, int wo, float hs, float ws,
                                                                  float cy, float cx, float scale, int flip_ud, int flip_lr) {
-    constexpr int NSRC = MODE == SHM_AUG_DIR ? 5 : 4;
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;       // (oy, ox)
     if (idx >= (size_t)ho * wo) return;
-    const int ox = (int)(idx % wo), oy = (int)(idx / wo);
-    const int sy = flip_ud ? ho - 1 - oy : oy, sx = flip_lr ? wo - 1 - ox : ox;
-    // the coordinate of resize_bilinear_u8_kernel (data.hip) inside the crop window, then the window's origin; the taps are held
-    // inside the image on both sides (no-ops for a crop inside the image, kept so that no rounding can index outside it)
-    const float fy = (((float)sy + 0.5f) * hs - 0.5f) + cy, fx = (((float)sx + 0.5f) * ws - 0.5f) + cx;
-    const float fly = floorf(fy), flx = floorf(fx);
-    const int y0 = min(max((int)fly, 0), hin - 1), y1 = min(max((int)ceilf(fy), 0), hin - 1);
-    const int x0 = min(max((int)flx, 0), win - 1), x1 = min(max((int)ceilf(fx), 0), win - 1);
-    const float ly = fy - fly, lx = fx - flx;
-    const size_t itl = ((size_t)y0 * win + x0) * 3, itr = ((size_t)y0 * win + x1) * 3;
-    const size_t ibl = ((size_t)y1 * win + x0) * 3, ibr = ((size_t)y1 * win + x1) * 3;
-    const size_t o = ((size_t)oy * wo + ox) * 3;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        float tl[5], tr[5], bl[5], br[5];
-#pragma unroll
-        for (int v = 0; v < NSRC; ++v) {
-            tl[v] = a.src[v][itl + k];
-            tr[v] = a.src[v][itr + k];
-            bl[v] = a.src[v][ibl + k];
-            br[v] = a.src[v][ibr + k];
-        }
-        if constexpr (MODE != SHM_AUG_DIR) {
-            tl[4] = polar_estimate<MODE>(a.coef, tl[0], tl[1], tl[2], tl[3]);
-            tr[4] = polar_estimate<MODE>(a.coef, tr[0], tr[1], tr[2], tr[3]);
-            bl[4] = polar_estimate<MODE>(a.coef, bl[0], bl[1], bl[2], bl[3]);
-            br[4] = polar_estimate<MODE>(a.coef, br[0], br[1], br[2], br[3]);
-        }
-        if constexpr (MIX) {
-            float* const taps[4] = {tl, tr, bl, br};
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                float* q = taps[t];
-                const float v0 = q[0], v1 = q[1], v2 = q[2], v3 = q[3];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const float* m = a.mix + 4 * i;
-                    q[i] = fminf(fmaxf(((m[0] * v0 + m[1] * v1) + m[2] * v2) + m[3] * v3, 0.f), 255.f);
-                }
-            }
-        }
-#pragma unroll
-        for (int v = 0; v < 5; ++v) {
-            const float top = tl[v] + (tr[v] - tl[v]) * lx, bot = bl[v] + (br[v] - bl[v]) * lx;
-            a.dst[v][o + k] = (top + (bot - top) * ly) * scale;
-        }
-    }
+    augment_pixel<MODE, MIX>(a, idx, hin, win, ho, wo, hs, ws, cy, cx, scale, flip_ud, flip_lr);     // augment_px.h
 }
 
 template <int MODE>

@@ -23,6 +23,13 @@ kernel per sample (shm_augment_views_u8) at the decoded bytes for all three `dif
 angle theta into 180 - theta, so the four views are permuted or re-mixed with it (polar.mirror_views).  Without
 either option the loader calls exactly the kernels described above.
 
+`cache="device"` keeps every sample's decoded bytes on the device after its first decode (shmgan_amd/cache.py: an arena of uint8
+chunks under a byte budget, keyed by the sample's position in the sorted file lists; the reference's `.cache()`), and builds every
+batch -- all three `diffuse_source` modes, with or without `shuffle` and `augment` -- with ONE shm_augment_batch_u8 launch from
+per-sample descriptors: no decode and no upload for a resident sample.  A sample the budget does not hold takes the decode-and-upload
+path every time.  Files that change on disk during a run are not noticed; under data parallelism each rank caches the samples it
+sees (with `shuffle`, eventually the whole set).  `cache="none"` (default) calls exactly the kernels described above.
+
 Under torch.distributed the loader shards by rank: global batch i of rank r is images [(i*world + r)*B, +B), so N ranks
 consume N*B distinct samples per step (the data-parallel identity of shmgan_amd/dist.py) and len() = n // (B*world).
 """
@@ -42,6 +49,7 @@ from . import ops
 PSD_SUBDIRS = ("I0", "I60", "I90", "I150", "ED")          # datasetLoader.py:30-34 (PSD polar dataset)
 SHMGAN_SUBDIRS = ("I0", "I45", "I90", "I135", "ED")       # datasetLoader.py:23-27 (commented alternative)
 DIFFUSE_SOURCES = ("dir", "min", "stokes")                # where the fifth tensor comes from (PolarDataset)
+CACHE_MODES = ("none", "device")                          # where decoded samples are kept between passes (PolarDataset)
 _EXT = (".bmp", ".gif", ".jpeg", ".jpg", ".png")          # Keras' ALLOWLIST_FORMATS
 
 
@@ -123,11 +131,21 @@ class PolarDataset:
     shuffle: every pass visits the samples in the order pass_order(n, seed, pass) instead of the sorted one.  augment: an Augment,
     or None; with one, every sample goes through shm_augment_views_u8 with the draw augment_params(seed, pass, position, ...), and
     views="physical" needs the polariser angles (`angles`, or the directory names).  Passes count from `first_pass` (a resumed run
-    sets it, so that it does not replay pass 0)."""
+    sets it, so that it does not replay pass 0).
+
+    cache: "none", or "device" = decoded samples stay on the device after their first decode (cache.SampleCache) and every batch is
+    one shm_augment_batch_u8 launch; cache_bytes: the device memory the cache may take (default: half of what is free when the first
+    sample is stored).  With "device" the images of a sample must have one decoded size, whatever the other options."""
 
     def __init__(self, data_dir, image_size, batch_size=1, subdirs=PSD_SUBDIRS, flip_ud=True, device=None, epochs=1,
-                 rank=None, world=None, diffuse_source="dir", angles=None, shuffle=False, augment=None, seed=0, first_pass=0):
+                 rank=None, world=None, diffuse_source="dir", angles=None, shuffle=False, augment=None, seed=0, first_pass=0,
+                 cache="none", cache_bytes=None):
         self.S, self.B, self.flip_ud, self.epochs = image_size, batch_size, flip_ud, epochs
+        if cache not in CACHE_MODES:
+            raise ValueError(f"cache {cache!r} is not one of {CACHE_MODES}")
+        if cache_bytes is not None and (not isinstance(cache_bytes, int) or cache_bytes < 0):
+            raise ValueError(f"cache_bytes {cache_bytes!r} is not a byte count")
+        self.cache, self.cache_bytes, self._cache, self._scratch = cache, cache_bytes, None, {}
         if augment is not None and not isinstance(augment, Augment):
             raise ValueError(f"augment must be a data.Augment or None, got {augment!r}")
         self.shuffle, self.augment, self.seed, self.first_pass = bool(shuffle), augment, int(seed), int(first_pass)
@@ -222,6 +240,8 @@ class PolarDataset:
         then enqueue copy + resize per image on the loader stream and record the batch's event."""
         if self._gen_event[gen] is not None:         # the copies that last read this generation's staging buffers
             self._gen_event[gen].synchronize()       # (a host wait, but on the loader thread)
+        if self.cache == "device":
+            return self._prepare_cached(index, gen, pass_index)
         if self.augment is not None:
             return self._prepare_augmented(index, gen, pass_index)
         if self.diffuse_source != "dir":
@@ -282,6 +302,64 @@ class PolarDataset:
         self._gen_event[gen] = ev
         return tuple(outs), ev
 
+    def _sample_cache(self):
+        """The arena, made on first use; its chunks are torch.uint8 tensors allocated where it is called from: the loader stream."""
+        if self._cache is None:
+            from .cache import SampleCache
+            budget = self.cache_bytes if self.cache_bytes is not None else lambda: torch.cuda.mem_get_info(self.dev)[0] // 2
+            self._cache = SampleCache(lambda nbytes: torch.empty(nbytes, dtype=torch.uint8, device=self.dev), budget)
+        return self._cache
+
+    def cache_stats(self):
+        """cache.SampleCache.stats() of this loader: {"resident", "bytes", "chunks", "hits", "misses", "refused"} (zeros before the
+        first batch and with cache="none")."""
+        if self._cache is None:
+            return {"resident": 0, "bytes": 0, "chunks": 0, "hits": 0, "misses": 0, "refused": 0}
+        return self._cache.stats()
+
+    def _prepare_cached(self, index, gen, pass_index):
+        """_prepare_worker with cache="device", for every diffuse_source, with or without `augment`: a resident sample is its arena
+        pointers; any other is decoded into this generation's pinned buffers and copied into its arena slot -- or, refused by the
+        budget, into this generation's scratch -- on the loader stream.  Then ONE shm_augment_batch_u8 writes the batch from the
+        samples' descriptors: identity crop and the fixed flip_ud without `augment` (bitwise the default path's kernels), the
+        sample's draw and the permute / mix logic of _prepare_augmented with it."""
+        from .cache import sample_bytes, sample_descriptor
+        nsrc = 5 if self.diffuse_source == "dir" else 4
+        pos = [self.position(index, b, pass_index) for b in range(self.B)]
+        kind, how = self._mirror
+        with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
+            arena = self._sample_cache()
+            outs = [torch.empty((self.B, self.S, self.S, 3), device=self.dev) for _ in range(5)]       # on the loader stream, as above
+            samples = []
+            for b, p in enumerate(pos):
+                e = arena.lookup(p)
+                if e is not None:
+                    ptrs, hin, win = e.ptrs, e.hin, e.win
+                else:
+                    paths = [[self.files[v][p]] for v in range(nsrc)]
+                    staged = [[self._decode(paths[v][0], (gen, v, b))] for v in range(nsrc)]
+                    self._same_size(staged, paths, 0)
+                    hin, win = staged[0][0].shape[:2]
+                    e = arena.store(p, nsrc, hin, win)
+                    if e is not None:
+                        room, offsets = arena.chunks[e.chunk], e.offsets
+                    else:           # refused: this generation's scratch, free again once the generation's event has completed
+                        need = sample_bytes(nsrc, hin, win)
+                        room = self._scratch.get((gen, b))
+                        if room is None or room.numel() < need:
+                            room = self._scratch[(gen, b)] = torch.empty(need, dtype=torch.uint8, device=self.dev)
+                        offsets = tuple(v * (need // nsrc) for v in range(nsrc))
+                    for v in range(nsrc):
+                        room[offsets[v]:offsets[v] + hin * win * 3].view(hin, win, 3).copy_(staged[v][0], non_blocking=True)
+                    ptrs = tuple(room.data_ptr() + o for o in offsets)
+                params = None if self.augment is None else augment_params(self.seed, pass_index, p, hin, win, self.augment)
+                samples.append(sample_descriptor(ptrs, hin, win, self.flip_ud, params, self._mirror))
+            ops.augment_batch_u8(samples, outs, self.diffuse_source, self.coef, how if kind == "mix" else None, 1.0 / 255.0)
+            ev = torch.cuda.Event()
+            ev.record(self.stream)
+        self._gen_event[gen] = ev
+        return tuple(outs), ev
+
     def prepare(self, index, pass_index=0):
         """Start batch `index` (0-based, of this rank) of pass `pass_index` on the loader thread / stream; returns a future of
         (five [B,S,S,3] tensors, ready event).  The outputs are ALLOCATED on the loader stream: a block the consumer has
@@ -320,14 +398,17 @@ def datasetLoad(trainer, subdirs=PSD_SUBDIRS, flip_ud=True):
     """Reference signature (datasetLoader.py:19): returns (length_dataset, loadedDataset) and sets the same
     attributes on the trainer object.  The trainer's `diffuse_source` option (default "dir") goes to PolarDataset; it is NOT
     keyed on the reference's `est_diffuse`, which main.py's parser makes True for every run.  `shuffle`, `data_seed`
-    and `aug_flip_lr` / `aug_flip_ud` / `aug_crop_min` / `aug_views` become the loader's shuffle, seed and Augment."""
+    and `aug_flip_lr` / `aug_flip_ud` / `aug_crop_min` / `aug_views` become the loader's shuffle, seed and Augment; `cache` ("none" /
+    "device") and `cache_gb` (GiB of device memory the cache may take; None = half of what is free) its cache and cache_bytes."""
     opt = lambda k, dflt: getattr(trainer.args, k, dflt)
     draws = (float(opt("aug_flip_lr", 0.0)), float(opt("aug_flip_ud", 0.0)), float(opt("aug_crop_min", 1.0)))
     # no augmentation asked for: the loader's default path, not the augmenting kernel at identity parameters
     augment = Augment(*draws, views=opt("aug_views", "physical")) if draws != (0.0, 0.0, 1.0) else None
+    cache_gb = opt("cache_gb", None)
     ds = PolarDataset(trainer.data_dir, trainer.image_size, trainer.batch_size, subdirs, flip_ud, trainer.device,
                       epochs=trainer.num_epochs, diffuse_source=getattr(trainer.args, "diffuse_source", "dir"),
-                      shuffle=bool(opt("shuffle", False)), augment=augment, seed=int(opt("data_seed", 0)))
+                      shuffle=bool(opt("shuffle", False)), augment=augment, seed=int(opt("data_seed", 0)),
+                      cache=opt("cache", "none"), cache_bytes=None if cache_gb is None else int(float(cache_gb) * 2 ** 30))
     trainer.stddev_arr, trainer.mean_arr, trainer.variance_arr = [], [], []
     # per-rank length: batches_per_epoch = length // batch_size (SHM.py:957) then counts this rank's batches
     trainer.length_dataset, trainer.loadedDataset = ds.n // ds.world, ds

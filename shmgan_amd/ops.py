@@ -6,6 +6,7 @@ their device pointers to libshmgan_hip.so on torch's current stream and returns 
 """
 from __future__ import annotations
 
+import functools
 import math
 
 import torch
@@ -1068,6 +1069,78 @@ def augment_views_u8(srcs, dsts, mode="dir", coef=None, mix=None, crop=None, fli
     cf = _polar_coef(coef, "augment_views_u8") if mode == "stokes" else None
     check(lib().shm_augment_views_u8(sp, nsrc, hin, win, AUGMENT_MODES[mode], cf, mx, cy, cx, ch, cw, int(bool(flip_ud)), int(bool(flip_lr)),
                                      dp, ho, wo, scale, _stream()), "shm_augment_views_u8")
+
+
+AUG_GROUP = 8                                            # SHM_AUG_GROUP: samples per launch of augment_batch_u8
+
+
+@functools.lru_cache(maxsize=None)
+def _aug_sample_struct():
+    """ctypes mirror of shm_aug_sample (include/shmgan_hip.h)."""
+    import ctypes as C
+
+    class ShmAugSample(C.Structure):
+        _fields_ = [("src", C.c_void_p * 5), ("hin", C.c_int), ("win", C.c_int), ("crop_y", C.c_float), ("crop_x", C.c_float),
+                    ("crop_h", C.c_float), ("crop_w", C.c_float), ("flip_ud", C.c_int), ("flip_lr", C.c_int), ("mix", C.c_int),
+                    ("plane", C.c_int * 4)]
+    return ShmAugSample
+
+
+def augment_batch_u8(samples, dsts, mode="dir", coef=None, mix=None, scale=1.0 / 255.0):
+    """augment_views_u8 for a whole batch in one launch per AUG_GROUP samples (shm_augment_batch_u8, include/shmgan_hip.h, states the
+    definitions): sample i of `samples` is written to dsts[p][i].  samples: a sequence of cache.AugSample (or anything with its
+    fields): srcs are five ("dir") or four uint8 [hin,win,3] device tensors of the sample's own size, or their device addresses (the
+    loader's arena) with hin / win given; crop (y, x, h, w) or None; flip_ud, flip_lr; mix: apply the shared 4x4 `mix` to this sample;
+    planes: the destination plane of view 0..3.  dsts: five float32 [n,ho,wo,3] device tensors, n >= len(samples).  The C entry point
+    checks every sample before it launches anything and names the sample it refuses.  Runs asynchronously on the current stream."""
+    import ctypes as C
+    import numpy as np
+    if mode not in AUGMENT_MODES:
+        raise ValueError(f"augment_batch_u8: mode {mode!r} is not 'dir', 'min' or 'stokes'")
+    nsrc = 5 if mode == "dir" else 4
+    if len(dsts) != 5:
+        raise ValueError(f"augment_batch_u8 takes 5 destination tensors, got {len(dsts)}")
+    if mode == "stokes" and coef is None:
+        raise ValueError("augment_batch_u8: mode 'stokes' needs coef (polar.stokes_matrix of the polariser angles)")
+    for d in dsts:
+        if d.dtype != torch.float32 or not d.is_cuda or d.device != dsts[0].device:
+            raise TypeError(f"augment_batch_u8 writes float32 device tensors on one device, got {d.dtype} on {d.device}")
+        if d.dim() != 4 or d.shape[3] != 3 or not d[0].is_contiguous() or d.shape != dsts[0].shape or d.stride(0) != dsts[0].stride(0):
+            raise ValueError(f"augment_batch_u8 writes five [n,ho,wo,3] tensors of one shape with contiguous samples, got {tuple(d.shape)} "
+                             f"with strides {d.stride()}")
+    nmax, ho, wo, _ = dsts[0].shape
+    if len(samples) > nmax:
+        raise ValueError(f"augment_batch_u8: {len(samples)} samples for destination tensors of {nmax}")
+    arr = (_aug_sample_struct() * max(len(samples), 1))()
+    for i, s in enumerate(samples):
+        if len(s.srcs) != nsrc or len(s.planes) != 4:
+            raise ValueError(f"augment_batch_u8: sample {i} has {len(s.srcs)} sources and {len(s.planes)} planes; mode {mode!r} takes {nsrc} and 4")
+        hin, win = int(s.hin), int(s.win)
+        for v, t in enumerate(s.srcs):
+            if isinstance(t, torch.Tensor):
+                if t.dtype != torch.uint8 or t.device != dsts[0].device:
+                    raise TypeError(f"augment_batch_u8 takes uint8 images on {dsts[0].device}, got {t.dtype} on {t.device} (sample {i})")
+                if tuple(t.shape) != (hin, win, 3) or not t.is_contiguous():
+                    raise ValueError(f"augment_batch_u8: source {v} of sample {i} is not a contiguous [{hin},{win},3] image: "
+                                     f"{tuple(t.shape)} with strides {t.stride()}")
+                arr[i].src[v] = t.data_ptr()
+            else:
+                arr[i].src[v] = int(t) or None
+        arr[i].hin, arr[i].win = hin, win
+        arr[i].crop_y, arr[i].crop_x, arr[i].crop_h, arr[i].crop_w = (0.0, 0.0, float(hin), float(win)) if s.crop is None else (float(c) for c in s.crop)
+        arr[i].flip_ud, arr[i].flip_lr, arr[i].mix = int(bool(s.flip_ud)), int(bool(s.flip_lr)), int(bool(s.mix))
+        for v in range(4):
+            arr[i].plane[v] = int(s.planes[v])
+    mx = None
+    if mix is not None:
+        m = np.asarray(mix.cpu() if isinstance(mix, torch.Tensor) else mix, dtype=np.float32)
+        if m.shape != (4, 4):
+            raise ValueError(f"augment_batch_u8: mix must be a 4x4 matrix, got shape {m.shape}")
+        mx = (C.c_float * 16)(*[float(v) for v in m.reshape(-1)])
+    dp = (C.c_void_p * 5)(*[d.data_ptr() for d in dsts])
+    cf = _polar_coef(coef, "augment_batch_u8") if mode == "stokes" else None
+    check(lib().shm_augment_batch_u8(arr, len(samples), nsrc, AUGMENT_MODES[mode], cf, mx, dp, dsts[0].stride(0), ho, wo, scale, _stream()),
+          "shm_augment_batch_u8")
 
 
 def polar_maps(views, coef, want=("s0", "dop", "aolp")):

@@ -54,6 +54,7 @@ _DEFAULTS = dict(image_size=128, batch_size=1, filter_size=64, g_lr=0.00002, d_l
                  save_images=False, image_values="rescale", image_out_size="source", image_dir="", eval_size="model",
                  loss_log_step=0, histogram_step=0, nonfinite=None, diffuse_source="dir",
                  shuffle=False, data_seed=0, aug_flip_lr=0.0, aug_flip_ud=0.0, aug_crop_min=1.0, aug_views="physical",
+                 cache="none", cache_gb=None,
                  specseg_image_dir="", specseg_mask_dir="", specseg_epochs=20, specseg_lr=1e-3, specseg_batch_size=8)
 
 
@@ -653,7 +654,9 @@ class ShmGANwithSSpecSeg:
         a NaN or Inf gradient does).  Both are off by default; the step counts optimizer updates, so a resumed run appends.  The logs are
         flushed before every checkpoint.  The loader options `shuffle`, `data_seed`, `aug_flip_lr`, `aug_flip_ud`, `aug_crop_min` and
         `aug_views` (data.datasetLoad; all off by default) give an epoch-wise shuffle and a random crop / mirror per sample;
-        aug_flip_ud=0.5 is the as-intended reading of the per-step draw below.  `max_steps` (tests) stops early.  Returns the number of train_step calls made."""
+        aug_flip_ud=0.5 is the as-intended reading of the per-step draw below.  `cache="device"` (with `cache_gb`, GiB; default half of the free
+        device memory) keeps the decoded samples on the device after their first decode, the reference's `.cache()`;
+        `self.loadedDataset.cache_stats()` says what it holds.  `max_steps` (tests) stops early.  Returns the number of train_step calls made."""
         import os
         import time
         from .data import datasetLoad

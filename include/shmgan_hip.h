@@ -15,10 +15,24 @@
  *    accumulation and fp32 arithmetic inside every kernel).  `float*` / `double*` arguments keep
  *    their type in both modes: master weights, biases, IN beta, statistics, weight gradients,
  *    image-space tensors and losses are always fp32 / f64;
- *  - "ld*" arguments are channel pitches in ELEMENTS (>= the channel count).  MFMA operands are
- *    staged as 64-byte rows, so contraction channel counts and concat splits are multiples of
- *    16 (fp32) or 32 (bf16), pitches multiples of 4 (fp32) or 8 (bf16); the 3- and 10-channel
- *    images are stored in a 16-float / 32-bf16 pitch (zero padded);
+ *  - "ld*" arguments are channel pitches in ELEMENTS, at least the channel count of their tensor (its part of a split
+ *    destination, its source of a concat): a tensor may be a channel slice of a wider buffer.  A smaller pitch is refused
+ *    with SHM_E_SHAPE before any launch (rows would overlap); a pitch is looked at only when its tensor is given (pass 0
+ *    with a NULL x2 / dx2 / g2).  The one exception is the compact 3-channel image below.  MFMA operands are staged as
+ *    64-byte rows that travel to LDS in 16-byte pieces, so contraction channel counts and concat splits are multiples of
+ *    16 (fp32) or 32 (bf16), and convolution INPUTS (x, x2, the dy of a gradient product; the aux of a gsum call where
+ *    the epilogue is to take the sums) have pitches that are multiples of 4 (fp32) or 8 (bf16) on 16-byte-aligned bases --
+ *    enforced for x, x2 and dy.  Convolution OUTPUTS take any pitch and any element-aligned base (the statistics pass of
+ *    shm_conv2d_in_fwd on small maps and the gsum reduce pass read them four channels at a time and refuse a pitch that is
+ *    no multiple of 4): bf16 outputs
+ *    whose pitches are multiples of 8 on 16-byte-aligned bases (and whose channel counts are multiples of 8) leave in 16-byte
+ *    stores, others element by element -- same values, slower -- and a bf16 layer then leaves the weights-in-registers
+ *    kernels, and gsum sums their epilogue for the reduce pass.  The InstanceNorm, pooling and LeakyReLU entry points work
+ *    on four channels per thread: channel counts and pitches are multiples of 4 in either type (8-byte-aligned bases in
+ *    bf16), and bf16 calls whose pitches are not multiples of 8 or whose bases are not 16-byte aligned take the four-channel
+ *    forms (shm_in_bwd: two passes; its one-pass form also wants a 16-byte-aligned dz).  The
+ *    3- and 10-channel images are stored in a 16-float / 32-bf16 pitch (zero padded); tests/test_pitch_gpu.py runs every
+ *    entry point on such views;
  *  - "f64 scratch" arguments are small double accumulators; where a comment says "zero on entry" the caller
  *    zeroes them ONCE (at allocation) and every call leaves them zero again -- also when it returns an error
  *    (the entry point clears the scratch itself if a launch after the one that filled it fails); otherwise

@@ -226,6 +226,19 @@ static int finish_args(TapGemmArgs& a, int batch, int nphase, int dtype, bool tw
     SHM_REQUIRE(a.K % bke == 0 && a.K > 0, SHM_E_SHAPE, "%s: contraction channels %d must be a multiple of %d", who, a.K, bke);
     SHM_REQUIRE(a.c1 % bke == 0, SHM_E_SHAPE, "%s: concat split %d must be a multiple of %d", who, a.c1, bke);
     SHM_REQUIRE(a.ldx % che == 0 && (!two_src || a.ldx2 % che == 0), SHM_E_SHAPE, "%s: input pitch must be a multiple of 16 bytes", who);
+    // the A operand travels to LDS in 16-byte pieces, one per lane, addressed as base + a multiple of 16 bytes: the bases are 16-byte aligned
+    // (a shape query has no operands: its null pointers read as aligned)
+    SHM_REQUIRE(((size_t)a.x & 15) == 0 && ((size_t)a.x2 & 15) == 0, SHM_E_SHAPE, "%s: input tensors must be 16-byte aligned", who);
+    // a pitch is at least the channel count of its tensor (rows of a smaller pitch overlap: the result would depend on the store order).  The one
+    // exception is the compact RGB image: one 16-byte chunk per pixel under a 64-byte weight row (include/shmgan_hip.h, conv_rgb.hip)
+    const bool compact_rgb = !two_src && a.ldx * esz == 16 && a.K * esz == 64;
+    SHM_REQUIRE(compact_rgb || a.ldx >= a.c1, SHM_E_SHAPE, "%s: input pitch %d below the source's %d channels", who, a.ldx, a.c1);
+    SHM_REQUIRE(!two_src || a.ldx2 >= a.K - a.c1, SHM_E_SHAPE, "%s: input pitch %d of the second source below its %d channels", who, a.ldx2, a.K - a.c1);
+    SHM_REQUIRE(a.ldy >= a.n1, SHM_E_SHAPE, "%s: output pitch %d below the part's %d channels", who, a.ldy, a.n1);
+    SHM_REQUIRE(a.y2 == nullptr || a.ldy2 >= a.nout - a.n1, SHM_E_SHAPE, "%s: output pitch %d of the second part below its %d channels", who, a.ldy2, a.nout - a.n1);
+    for (int p = 0; p < 2; ++p)
+        SHM_REQUIRE(a.gred[p] == nullptr || a.ldgaux[p] >= (p ? a.nout - a.n1 : a.n1), SHM_E_SHAPE, "%s: aux pitch %d below the part's %d channels", who,
+                    a.ldgaux[p], p ? a.nout - a.n1 : a.n1);
     SHM_REQUIRE((size_t)batch * a.hi * a.wi < (1u << 31) && (size_t)batch * a.ho * a.wo < (1u << 31), SHM_E_SHAPE, "%s: pixel count overflows int32", who);
     a.M = batch * a.hg * a.wg;
     if (a.M == 0 || a.nout == 0) return SHM_OK;

@@ -276,6 +276,13 @@ static int wgrad_check(const WgradShape& s, bool operands_ok, size_t ws_bytes, c
                 "shm_conv2d_wgrad: cin_ld %d / cout %d must be multiples of %d", s.cin_ld, s.cout, vec);
     SHM_REQUIRE(s.ldx % vec == 0 && s.lddy % vec == 0 && (!s.two || (s.ldx2 % vec == 0 && s.c1 % vec == 0)), SHM_E_SHAPE,
                 "shm_conv2d_wgrad: pitches must be multiples of %d", vec);
+    // a pitch is at least the channels read through it; the compact RGB image (one 16-byte chunk per pixel under a 64-byte row, conv_rgb.hip) is the exception
+    const bool compact_rgb = !s.two && s.ldx * esz == 16 && s.cin_ld * esz == 64;
+    SHM_REQUIRE(compact_rgb || s.ldx >= (s.two ? s.c1 : s.cin_ld), SHM_E_SHAPE, "shm_conv2d_wgrad: input pitch %d below the source's %d channels", s.ldx,
+                s.two ? s.c1 : s.cin_ld);
+    SHM_REQUIRE(!s.two || s.ldx2 >= s.cin_ld - s.c1, SHM_E_SHAPE, "shm_conv2d_wgrad: input pitch %d of the second source below its %d channels", s.ldx2,
+                s.cin_ld - s.c1);
+    SHM_REQUIRE(s.lddy >= s.cout, SHM_E_SHAPE, "shm_conv2d_wgrad: gradient pitch %d below %d channels", s.lddy, s.cout);
     SHM_REQUIRE((size_t)s.batch * s.hi * s.wi < (1u << 31), SHM_E_SHAPE, "shm_conv2d_wgrad: pixel count overflows int32");
     *plan = wgrad_plan(s, want_nm, nm.part, nm.c, nm.mode);
     SHM_REQUIRE(ws_bytes >= plan->early_bytes, SHM_E_WORKSPACE, "shm_conv2d_wgrad: workspace %zu < %zu bytes", ws_bytes, plan->early_bytes);
@@ -377,6 +384,8 @@ static int wgrad_partial_impl(const void* x, const void* x2, int c1, int ldx, in
     const WgradShape s{batch, hi, wi, cin, cin_ld, c1, cout, ksize, stride, dtype, x2 != nullptr, ldx, ldx2, lddy};
     WgradPlan p;
     if (const int r = wgrad_check(s, x && dy && workspace, ws_bytes, nm, nm.nt != nullptr, &p)) return r;
+    // both operands travel in 16-byte pieces addressed as base + a multiple of 16 bytes
+    SHM_REQUIRE(((size_t)x & 15) == 0 && ((size_t)x2 & 15) == 0 && ((size_t)dy & 15) == 0, SHM_E_SHAPE, "shm_conv2d_wgrad: x, x2 and dy must be 16-byte aligned");
     SHM_REQUIRE(!nm.nt || p.norm_ok, SHM_E_SHAPE,
                 "shm_conv2d_wgrad_norm: the kernel this shape runs on cannot normalise its source in LDS (unit-stride 3x3, map width a multiple of "
                 "16, concat split a multiple of 64; ask shm_conv2d_wgrad_norm_supported) -- use shm_in_apply");

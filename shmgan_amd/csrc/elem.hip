@@ -52,6 +52,7 @@ __global__ void avgpool2_kernel(const T* __restrict__ x, int ldx, T* __restrict_
 
 extern "C" int shm_avgpool2_fwd(const void* x, int ldx, void* y, int ldy, int batch, int h, int w, int c, int dtype, void* stream) {
     SHM_REQUIRE(c % 4 == 0 && ldx % 4 == 0 && ldy % 4 == 0, SHM_E_SHAPE, "shm_avgpool2_fwd: channels/pitch must be multiples of 4");
+    SHM_REQUIRE(ldx >= c && ldy >= c, SHM_E_SHAPE, "shm_avgpool2_fwd: pitch %d / %d below the %d channels", ldx, ldy, c);
     SHM_REQUIRE(h % 2 == 0 && w % 2 == 0, SHM_E_SHAPE, "shm_avgpool2_fwd: odd size %dx%d", h, w);
     size_t total = (size_t)batch * (h / 2) * (w / 2) * (c / 4);
     if (total == 0) return SHM_OK;

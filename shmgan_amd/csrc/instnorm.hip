@@ -152,7 +152,7 @@ __global__ __launch_bounds__(256) void in_apply_kernel(const T* __restrict__ a, 
 extern "C" int shm_in_apply(const void* a, int lda, const double* stats, const float* beta, void* out, int ldo, int batch, int hw, int c, int dtype,
                             void* stream) {
     SHM_CHECK_C(c, "shm_in_apply");
-    SHM_REQUIRE(lda % 4 == 0 && ldo % 4 == 0, SHM_E_SHAPE, "shm_in_apply: bad pitch");
+    SHM_REQUIRE(lda % 4 == 0 && ldo % 4 == 0 && lda >= c && ldo >= c, SHM_E_SHAPE, "shm_in_apply: bad pitch %d / %d (multiples of 4, at least %d channels)", lda, ldo, c);
     if (batch == 0 || hw == 0) return SHM_OK;
     int nch = pix_chunks(hw, batch, c);
     int chunk = shm_cdiv(hw, nch);
@@ -234,7 +234,8 @@ __global__ __launch_bounds__(256) void in_apply_pool_kernel(const T* __restrict_
 extern "C" int shm_in_apply_pool(const void* a, int lda, const double* stats, const float* beta, void* out, int ldo, void* pooled, int ldp, int batch,
                                  int h, int w, int c, int dtype, void* stream) {
     SHM_CHECK_C(c, "shm_in_apply_pool");
-    SHM_REQUIRE(lda % 4 == 0 && ldo % 4 == 0 && ldp % 4 == 0, SHM_E_SHAPE, "shm_in_apply_pool: bad pitch");
+    SHM_REQUIRE(lda % 4 == 0 && ldo % 4 == 0 && ldp % 4 == 0 && lda >= c && ldo >= c && ldp >= c, SHM_E_SHAPE,
+                "shm_in_apply_pool: bad pitch %d / %d / %d (multiples of 4, at least %d channels)", lda, ldo, ldp, c);
     SHM_REQUIRE(h % 2 == 0 && w % 2 == 0, SHM_E_SHAPE, "shm_in_apply_pool: odd size %dx%d", h, w);
     SHM_REQUIRE(a && stats && beta && out && pooled, SHM_E_SHAPE, "shm_in_apply_pool: null pointer");
     if (batch == 0 || h * w == 0) return SHM_OK;
@@ -251,7 +252,7 @@ extern "C" int shm_in_apply_pool(const void* a, int lda, const double* stats, co
 extern "C" int shm_in_pool(const void* a, int lda, const double* stats, const float* beta, void* pooled, int ldp, int batch, int h, int w, int c, int dtype,
                            void* stream) {
     SHM_CHECK_C(c, "shm_in_pool");
-    SHM_REQUIRE(lda % 4 == 0 && ldp % 4 == 0, SHM_E_SHAPE, "shm_in_pool: bad pitch");
+    SHM_REQUIRE(lda % 4 == 0 && ldp % 4 == 0 && lda >= c && ldp >= c, SHM_E_SHAPE, "shm_in_pool: bad pitch %d / %d (multiples of 4, at least %d channels)", lda, ldp, c);
     SHM_REQUIRE(h % 2 == 0 && w % 2 == 0, SHM_E_SHAPE, "shm_in_pool: odd size %dx%d", h, w);
     SHM_REQUIRE(a && stats && beta && pooled, SHM_E_SHAPE, "shm_in_pool: null pointer");
     if (batch == 0 || h * w == 0) return SHM_OK;

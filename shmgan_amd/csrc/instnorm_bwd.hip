@@ -30,6 +30,7 @@ struct InBwdReq {                // one call, after the argument checks (4 <= c 
     bool g2, r1, keep;           // pooled gradient, rank-1 gradient, the per-sample dz sums are wanted
     bool scratch;                // the one-pass forms' fused_scratch was given, ...
     size_t scratch_n;            // ... of this many doubles
+    bool src_al16, dz_al16;      // the sources (g1, g2, a) / dz start on 16-byte boundaries
 };
 
 // Which form a call takes.  Host only; the only reader of the "elem.*" knobs in this launcher.  `resident(form)`: fused_resident_blocks, asked
@@ -63,9 +64,9 @@ static InBwdPlan in_bwd_plan(const InBwdReq& q, int (*resident)(int form)) {
     p.nt = shm_tune(SHM_TUNE_ELEM_NT);          // the apply pass is the last reader of g1
     p.interleave = shm_tune(SHM_TUNE_ELEM_INTERLEAVE);
     p.fold = q.keep ? 0 : 1;     // (the per-sample sums are wanted too -- SHM_NORM_SCALED's second term: the separate fold kernel copies them out)
-    // 16-byte accesses of the bf16 sources.  c >= 8 and c <= 1024 of the earlier spelling follow from c % 8 == 0 and the argument check, and
+    // 16-byte accesses of the bf16 sources: pitches AND bases (a slice 8 bytes into a 16-byte row takes the four-channel forms).  c >= 8 and c <= 1024 of the earlier spelling follow from c % 8 == 0 and the argument check, and
     // 256 / (c / 8) >= 1 from c <= 1024
-    const bool src16 = (q.r1 || q.ldg1 % 8 == 0) && q.lda % 8 == 0 && (!q.g2 || q.ldg2 % 8 == 0);
+    const bool src16 = (q.r1 || q.ldg1 % 8 == 0) && q.lda % 8 == 0 && (!q.g2 || q.ldg2 % 8 == 0) && q.src_al16;
     p.wide8 = (q.dtype == SHM_BF16 || q.dtype == SHM_BF16_GF32) && c % 8 == 0 && src16;          // eight channels per thread in the reduce pass
     // ---- one pass
     const int cb = c < 64 ? c : 64;
@@ -75,7 +76,7 @@ static InBwdPlan in_bwd_plan(const InBwdReq& q, int (*resident)(int form)) {
     // a power of two up to 128 divides 256 into an even number of rows
     const int wt = q.w < 128 ? q.w : 128;
     const bool g2_tiles = cb == 64 && (wt & (wt - 1)) == 0 && q.w % wt == 0 && q.h % (256 / wt) == 0;
-    const bool base_ok = q.scratch && shm_tune(SHM_TUNE_ELEM_FUSED_BWD) && q.dtype == SHM_BF16 && !q.r1 && groups_ok && src16 && q.lddz % 8 == 0 &&
+    const bool base_ok = q.scratch && shm_tune(SHM_TUNE_ELEM_FUSED_BWD) && q.dtype == SHM_BF16 && !q.r1 && groups_ok && src16 && q.lddz % 8 == 0 && q.dz_al16 &&
                          q.batch <= 65535 && q.scratch_n >= SHM_IN_BWD_FUSED_DOUBLES(q.batch, hw, c);
     const int max_slices = shm_tune(SHM_TUNE_ELEM_FUSED_MAX_SLICES);
     const int hold = shm_tune(SHM_TUNE_ELEM_FUSED_HOLD);          // 0 automatic, 1 the round-5 kernel only (g and a held), 2 the g-held kernel only
@@ -161,10 +162,13 @@ static int in_bwd_impl(const char* who, const void* g1, int ldg1, const void* g2
     SHM_REQUIRE(!keep || dbias, SHM_E_SHAPE, "%s: the per-sample dz sums are staged only with a bias gradient", who);
     SHM_CHECK_C(c, who);
     SHM_REQUIRE((r1 || ldg1 % 4 == 0) && lda % 4 == 0 && lddz % 4 == 0 && (!g2 || ldg2 % 4 == 0), SHM_E_SHAPE, "%s: bad pitch", who);
+    SHM_REQUIRE((r1 || ldg1 >= c) && lda >= c && lddz >= c && (!g2 || ldg2 >= c), SHM_E_SHAPE, "%s: pitch below the %d channels", who, c);
     SHM_REQUIRE(!g2 || (h % 2 == 0 && w % 2 == 0), SHM_E_SHAPE, "%s: pooled gradient needs even h,w", who);
     SHM_REQUIRE(!(r1 && g2), SHM_E_SHAPE, "%s: the rank-1 form takes no pooled gradient", who);
     if (batch == 0 || h * w == 0) return SHM_OK;
-    const InBwdPlan p = in_bwd_plan(InBwdReq{dtype, batch, h, w, c, ldg1, ldg2, lda, lddz, g2 != nullptr, r1, keep != nullptr, fscr != nullptr, fscr_n}, fused_resident_blocks);
+    const InBwdPlan p = in_bwd_plan(InBwdReq{dtype, batch, h, w, c, ldg1, ldg2, lda, lddz, g2 != nullptr, r1, keep != nullptr, fscr != nullptr, fscr_n,
+                                                (((size_t)g1 | (size_t)g2 | (size_t)a) & 15) == 0, ((size_t)dz & 15) == 0},
+                                       fused_resident_blocks);
     InBwdArgs k{g1, g2, a, stats, red, dz, dbias, ldg1, ldg2, lda, lddz, h, w, c, 0, slope, 0, r1_dz, r1_w};
     k.nbatch = batch;
     return launch_plan(who, p, k, keep, fscr, abort_dev, abort_host, (hipStream_t)stream);
@@ -193,6 +197,7 @@ extern "C" int shm_in_bwd_apply(const void* g1, int ldg1, const void* g2, int ld
     SHM_REQUIRE(!dbias || dstage, SHM_E_SHAPE, "%s: the bias gradient needs its staging scratch", who);
     SHM_CHECK_C(c, who);
     SHM_REQUIRE(ldg1 % 4 == 0 && lda % 4 == 0 && lddz % 4 == 0 && (!g2 || ldg2 % 4 == 0), SHM_E_SHAPE, "%s: bad pitch", who);
+    SHM_REQUIRE(ldg1 >= c && lda >= c && lddz >= c && (!g2 || ldg2 >= c), SHM_E_SHAPE, "%s: pitch below the %d channels", who, c);
     SHM_REQUIRE(!g2 || (h % 2 == 0 && w % 2 == 0), SHM_E_SHAPE, "%s: pooled gradient needs even h,w", who);
     if (batch == 0 || h * w == 0) return SHM_OK;
     hipStream_t st = (hipStream_t)stream;

@@ -680,6 +680,44 @@ int shm_augment_batch_u8(const shm_aug_sample* samples, int n, int n_src, int mo
 int shm_polar_maps(const float* const* view_ptrs, size_t n, const float* coef, float* s0, float* dop, float* aolp,
                    void* stream);
 
+/* ---- specular masks from the polarised views (csrc/specmask.hip) ------------------------------------------
+ * Specular reflection is polarised, diffuse reflection is not: the polarised intensity sqrt(S1^2 + S2^2) of the Stokes fit, the part
+ * SHM_POLAR_STOKES subtracts, thresholded and cleaned up, is a highlight mask of ONE sample that needs no label.  Three calls on one
+ * stream make it; none synchronises with the host, the threshold travels in device memory (stats).
+ *   stats   device int[3]: [0] Otsu's t, [1] the threshold applied t_eff, [2] the number of set mask pixels
+ * Strength and histogram.  src_ptrs: host array of 4 device pointers to contiguous uint8 [h,w,3] views; coef: host float[12], the 3x4
+ * Stokes matrix of shm_polar_views_u8 (rows 1 and 2 are read).  Per pixel, with S1_c = ((C10 v0 + C11 v1) + C12 v2) + C13 v3 of channel c
+ * and S2_c alike from row 2, all in fp32:
+ *   e = max_c (S1_c^2 + S2_c^2);  p = sqrtf(e);  q = min(255, (int)p)        q: device uint8 [h,w]
+ * The maximum is taken BEFORE the root: for integer matrices e is an exact integer below 2^24 and q its integer square root.
+ * hist: device unsigned[256], cleared on the stream by the call and then holding exactly the counts of q (integer atomics: the same
+ * on every run).  SHM_E_SHAPE for a null pointer, h or w below 1, or h * w * 3 beyond the 32-bit index range; before any launch. */
+int shm_specmask_strength(const unsigned char* const* src_ptrs, int h, int w, const float* coef, unsigned char* q,
+                          unsigned* hist, void* stream);
+/* Otsu's threshold of a 256-bin histogram (device unsigned[256]; one block).  With bins <= t as class 0: N0(t), M0(t) the exact 64-bit
+ * prefix counts and first moments, N1 = N - N0, M1 = M - M0, and in double
+ *   var(t) = ((N0 * N1) * d) * d,  d = M1 / N1 - M0 / N0;   var(t) = 0 where a class is empty
+ * stats[0] = the lowest t of maximal var(t) (0 for an empty or one-bin histogram); stats[1] = fixed_t when fixed_t >= 0, else
+ * max(stats[0], floor_t): Otsu splits anything, sensor noise included, and the floor keeps such a split from becoming a mask.
+ * SHM_E_SHAPE for a null pointer, floor_t outside [0, 255] or fixed_t outside [-1, 255]. */
+int shm_specmask_otsu(const unsigned* hist, int floor_t, int fixed_t, int* stats, void* stream);
+/* b = q > stats[1] (read on the device), opened with a (2 open_radius + 1)^2 square (erosion, then dilation) and dilated with a
+ * (2 dilate_radius + 1)^2 square; a tap outside the image is skipped (the min / max runs over the taps inside it); radius 0 is the
+ * identity.  Two launches: threshold + erosion into tmp (device uint8 [h,w], 0 / 1, a buffer of its own), then one dilation by
+ * open_radius + dilate_radius into mask (device uint8 [h,w], 0 / 255), which also counts the set pixels into stats[2] (cleared on
+ * the stream by the call).  SHM_E_SHAPE for a null pointer, tmp aliasing q or mask, sizes as above, open_radius outside
+ * [0, SHM_SPECMASK_MAX_OPEN] or dilate_radius outside [0, SHM_SPECMASK_MAX_DILATE]; before any launch. */
+#define SHM_SPECMASK_MAX_OPEN 4
+#define SHM_SPECMASK_MAX_DILATE 8
+int shm_specmask_morph(const unsigned char* q, int h, int w, int open_radius, int dilate_radius, unsigned char* tmp,
+                       unsigned char* mask, int* stats, void* stream);
+/* The chain: shm_specmask_strength, shm_specmask_otsu and shm_specmask_morph on `stream`, with every refusal of the three (and
+ * mask sharing q's buffer) made before the first launch; four launches and two small clears, no host synchronisation.  q, hist and
+ * stats are results like mask; tmp is scratch. */
+int shm_specmask(const unsigned char* const* src_ptrs, int h, int w, const float* coef, int floor_t, int fixed_t,
+                 int open_radius, int dilate_radius, unsigned char* q, unsigned* hist, unsigned char* tmp,
+                 unsigned char* mask, int* stats, void* stream);
+
 /* ---- test-mode image export (the images test.py:305-317 logs; test_plot at test.py:410-425) ----------------------------
  * Batched, ragged float32 -> uint8 export.  One job = one plane of one image: source src[j], float32 [s,s,c] NHWC with channel
  * pitch ld >= c, c in {1,3}; destination [ho,wo,c] uint8, tightly packed, at byte offset dst_off (a multiple of 4) of dst.

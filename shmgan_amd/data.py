@@ -432,6 +432,40 @@ class MaskDataset:
         self.names = sorted(imgs)
         self.files = [(imgs[n], masks[n]) for n in self.names]
         self.S, self.B, self.flip_ud, self._dev, self._xy = int(image_size), int(batch_size), bool(flip_ud), device, None
+        self._polar = None
+
+    @classmethod
+    def from_polar(cls, data_dir, image_size, batch_size=1, subdirs=PSD_SUBDIRS, angles=None, flip_ud=False, device=None, **mask_options):
+        """The same (x, y) tensors from a raw four-directory capture, without a mask anybody drew and without the PNG round trip:
+        the image of sample i is its view subdirs[2] (the one whose Y plane train_step feeds SpecSeg.predict), the mask is
+        polar.specular_mask of its four views (`angles`, or those read from the directory names; `mask_options` = threshold, floor,
+        open_radius, dilate_radius), computed at source size and then resized like a decoded mask file.  Bit-equal to
+        polar.write_specular_masks(data_dir, out) followed by MaskDataset(<data_dir>/<subdirs[2]>, out, ...): PNG is lossless.
+        Same refusals as write_specular_masks: four directories, equal counts, equal sizes."""
+        from . import polar
+        bad = sorted(set(mask_options) - set(polar.MASK_OPTIONS))
+        if bad:
+            raise TypeError(f"MaskDataset.from_polar: unknown option(s) {bad}; polar.specular_mask takes {polar.MASK_OPTIONS}")
+        views, files = polar.polar_sample_files(data_dir, subdirs, "MaskDataset.from_polar")
+        if not files[0]:
+            raise ValueError(f"{data_dir}: the view directories {views} hold no images")
+        self = cls.__new__(cls)
+        self.files = sorted(zip(*files), key=lambda paths: Path(paths[2]).stem)          # the order of the directory form: by name
+        self.names = [Path(paths[2]).stem for paths in self.files]
+        self.S, self.B, self.flip_ud, self._dev, self._xy = int(image_size), int(batch_size), bool(flip_ud), device, None
+        self._polar = dict(coef=polar.stokes_matrix(angles if angles is not None else polar.angles_from_subdirs(views)), options=dict(mask_options))
+        return self
+
+    def _pair(self, k):
+        """Sample k as decoded bytes on the device: (uint8 [h,w,3] image, uint8 [h,w,1] mask)."""
+        if self._polar is None:
+            fi, fm = self.files[k]
+            return self._decode(fi, "RGB").to(self.dev), self._decode(fm, "L").to(self.dev)
+        from . import polar
+        srcs = [torch.from_numpy(a).to(self.dev) for a in polar.decode_sample(self.files[k], k)]
+        with torch.cuda.device(self.dev):
+            mask, _, _ = polar.specular_mask(srcs, matrix=self._polar["coef"], **self._polar["options"])
+        return srcs[2], mask.unsqueeze(2)
 
     @property
     def dev(self):
@@ -455,9 +489,10 @@ class MaskDataset:
             N, S = len(self.files), self.S
             rgb = torch.empty((N, S, S, 3), device=self.dev)
             y = torch.empty((N, S, S, 1), device=self.dev)
-            for k, (fi, fm) in enumerate(self.files):
-                ops.resize_bilinear_u8(self._decode(fi, "RGB").to(self.dev), rgb[k], 1.0 / 255.0, self.flip_ud)
-                ops.resize_bilinear_u8(self._decode(fm, "L").to(self.dev), y[k], 1.0 / 255.0, self.flip_ud)
+            for k in range(N):
+                img, mask = self._pair(k)
+                ops.resize_bilinear_u8(img, rgb[k], 1.0 / 255.0, self.flip_ud)
+                ops.resize_bilinear_u8(mask, y[k], 1.0 / 255.0, self.flip_ud)
             yuv = torch.empty_like(rgb)
             acc = torch.zeros(2 * N, dtype=torch.float64, device=self.dev)
             scale = torch.empty(N, device=self.dev)

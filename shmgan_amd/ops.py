@@ -1168,6 +1168,82 @@ def polar_maps(views, coef, want=("s0", "dop", "aolp")):
     return out
 
 
+# ---- specular masks from the polarised views (specmask.hip) -------------------------------------------
+SPECMASK_MAX_OPEN, SPECMASK_MAX_DILATE = 4, 8            # SHM_SPECMASK_MAX_OPEN / SHM_SPECMASK_MAX_DILATE
+
+
+def _specmask_map(t, who, what, like=None):
+    if t.dtype != torch.uint8 or not t.is_cuda or t.dim() != 2 or not t.is_contiguous():
+        raise ValueError(f"{who}: {what} must be a contiguous uint8 [h,w] device tensor, got {t.dtype} {tuple(t.shape)} with strides {t.stride()} on {t.device}")
+    if like is not None and (t.shape != like.shape or t.device != like.device):
+        raise ValueError(f"{who}: {what} is {tuple(t.shape)} on {t.device}, expected {tuple(like.shape)} on {like.device}")
+
+
+def _specmask_ints(t, who, what, n):
+    if t.dtype != torch.int32 or not t.is_cuda or t.dim() != 1 or t.shape[0] != n or not t.is_contiguous():
+        raise ValueError(f"{who}: {what} must be a contiguous int32 [{n}] device tensor, got {t.dtype} {tuple(t.shape)} on {t.device}")
+
+
+def _specmask_views(srcs, q, who):
+    """The checks of the four source views and the map of their size; returns (host pointer array, h, w)."""
+    import ctypes as C
+    if len(srcs) != 4:
+        raise ValueError(f"{who} takes 4 source views, got {len(srcs)}")
+    for s in srcs:
+        if s.dtype != torch.uint8 or not s.is_cuda:
+            raise TypeError(f"{who} takes uint8 device views, got {s.dtype} on {s.device}")
+        if s.dim() != 3 or s.shape[2] != 3 or not s.is_contiguous():
+            raise ValueError(f"{who} takes contiguous [h,w,3] views, got {tuple(s.shape)} with strides {s.stride()}")
+    if any(s.shape != srcs[0].shape or s.device != srcs[0].device for s in srcs):
+        raise ValueError(f"{who}: the four views differ in size: {[tuple(s.shape[:2]) for s in srcs]}")
+    h, w, _ = srcs[0].shape
+    _specmask_map(q, who, "q")
+    if tuple(q.shape) != (h, w) or q.device != srcs[0].device:
+        raise ValueError(f"{who}: q is {tuple(q.shape)} on {q.device}, the views are {h}x{w} on {srcs[0].device}")
+    return (C.c_void_p * 4)(*[s.data_ptr() for s in srcs]), h, w
+
+
+def specmask_strength(srcs, coef, q, hist):
+    """Polarised-intensity byte map and its histogram of one sample (shm_specmask_strength, include/shmgan_hip.h): srcs = four
+    contiguous uint8 [h,w,3] device views of one size, coef = the 3x4 Stokes matrix, q = uint8 [h,w], hist = int32 [256] (cleared by
+    the call, whatever it held).  Asynchronous on the current stream."""
+    sp, h, w = _specmask_views(srcs, q, "specmask_strength")
+    _specmask_ints(hist, "specmask_strength", "hist", 256)
+    check(lib().shm_specmask_strength(sp, h, w, _polar_coef(coef, "specmask_strength"), _p(q), _p(hist), _stream()), "shm_specmask_strength")
+
+
+def specmask(srcs, coef, q, hist, tmp, mask, stats, floor=16, fixed=None, open_radius=1, dilate_radius=2):
+    """The chain specmask_strength -> specmask_otsu -> specmask_morph in one call (shm_specmask): every argument is checked before the
+    first launch.  q, hist, mask and stats are results, tmp is scratch.  Asynchronous; nothing is read back."""
+    sp, h, w = _specmask_views(srcs, q, "specmask")
+    _specmask_map(tmp, "specmask", "tmp", q)
+    _specmask_map(mask, "specmask", "mask", q)
+    _specmask_ints(hist, "specmask", "hist", 256)
+    _specmask_ints(stats, "specmask", "stats", 3)
+    check(lib().shm_specmask(sp, h, w, _polar_coef(coef, "specmask"), int(floor), -1 if fixed is None else int(fixed), int(open_radius),
+                             int(dilate_radius), _p(q), _p(hist), _p(tmp), _p(mask), _p(stats), _stream()), "shm_specmask")
+
+
+def specmask_otsu(hist, stats, floor=16, fixed=None):
+    """Otsu's threshold of hist (int32 [256] on the device) into stats (int32 [3]: t, t_eff, count): t_eff = max(t, floor), or
+    `fixed` (an integer in [0, 255]) when given (shm_specmask_otsu).  Asynchronous; nothing is read back."""
+    _specmask_ints(hist, "specmask_otsu", "hist", 256)
+    _specmask_ints(stats, "specmask_otsu", "stats", 3)
+    check(lib().shm_specmask_otsu(_p(hist), int(floor), -1 if fixed is None else int(fixed), _p(stats), _stream()), "shm_specmask_otsu")
+
+
+def specmask_morph(q, stats, tmp, mask, open_radius=1, dilate_radius=2):
+    """mask (uint8 [h,w], 0 / 255) = dilate(open(q > stats[1], open_radius), dilate_radius) with square elements and out-of-image taps
+    skipped; stats[2] = the number of set pixels (shm_specmask_morph).  tmp: uint8 [h,w] scratch of its own.  Asynchronous."""
+    _specmask_map(q, "specmask_morph", "q")
+    _specmask_map(tmp, "specmask_morph", "tmp", q)
+    _specmask_map(mask, "specmask_morph", "mask", q)
+    _specmask_ints(stats, "specmask_morph", "stats", 3)
+    h, w = q.shape
+    check(lib().shm_specmask_morph(_p(q), h, w, int(open_radius), int(dilate_radius), _p(tmp), _p(mask), _p(stats), _stream()),
+          "shm_specmask_morph")
+
+
 # ---- first-layer input gradient, summed over input channels -----------------------------------------
 def sum_input_channels(w, cin, cout, mask, weff):
     check(lib().shm_sum_input_channels(_p(w), cin, cout, mask, _p(weff), _stream()), "shm_sum_input_channels")

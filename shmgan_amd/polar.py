@@ -6,7 +6,11 @@ the four views at source size; its imwrite is commented out) and calcDOP (SHM.py
 device implementation (csrc/polar.hip) and this module holds the host side: the least-squares Stokes matrix for any set of
 polariser angles, the reference's own coefficients, and the `imwrite` the reference left out.
 
-Importing this module needs no GPU; `polar_maps` and `write_estimated_diffuse` run on one.
+The same fit gives a label the capture already contains: the polarised intensity sqrt(S1^2 + S2^2) is the specular part, and
+`specular_mask` / `write_specular_masks` (csrc/specmask.hip) threshold it into the highlight masks SpecSeg is trained on
+(data.MaskDataset.from_polar, trainer.train_specseg with specseg_mask_source="polar").
+
+Importing this module needs no GPU; `polar_maps`, `specular_mask`, `write_estimated_diffuse` and `write_specular_masks` run on one.
 
 Model: a linear polariser at angle theta in front of light with Stokes parameters (S0, S1, S2) passes
     I(theta) = 0.5 * (S0 + S1 cos 2 theta + S2 sin 2 theta)
@@ -105,6 +109,110 @@ def _decode(path):
         return np.array(im.convert("RGB"), dtype=np.uint8)
 
 
+MASK_OPTIONS = ("threshold", "floor", "open_radius", "dilate_radius")       # the keyword options of specular_mask
+
+
+def specular_mask(views_u8, angles=None, *, matrix=None, threshold="otsu", floor=16, open_radius=1, dilate_radius=2):
+    """Highlight mask of one sample from its four polarised views (csrc/specmask.hip): specular reflection is
+    polarised, diffuse reflection is not, so the polarised intensity sqrt(S1^2 + S2^2) -- what diffuse_source="stokes" subtracts --
+    marks the highlights without a label.
+
+    views_u8: four contiguous uint8 [h,w,3] device tensors; the Stokes matrix is stokes_matrix(angles) or `matrix` (3x4, e.g.
+    REFERENCE_DOP_MATRIX); exactly one of the two.  strength = min(255, int(sqrt(max over channels of S1^2 + S2^2))); the
+    threshold is Otsu's on the strength histogram, held at `floor` byte units from below (Otsu splits anything, sensor noise
+    included; 16 is 6 % of full scale, a documented default and not a measured constant), or `threshold` itself when it is a number
+    in byte units (pixels with strength > floor(threshold) are set).  The thresholded map is opened with a (2 open_radius + 1)^2
+    square (isolated noise pixels go) and dilated with a (2 dilate_radius + 1)^2 one (the soft rim of a highlight); taps outside the
+    image are skipped.  Radii: open 0..4, dilate 0..8, 0 = identity.
+
+    Returns (mask uint8 [h,w] 0 / 255, strength uint8 [h,w], stats int32 [3] = Otsu's t, the threshold applied, the number of set
+    pixels), all on the device, filled asynchronously on the current stream: nothing is read back here."""
+    import torch
+    from . import ops
+    if (angles is None) == (matrix is None):
+        raise ValueError("specular_mask needs the polariser angles or a 3x4 Stokes matrix (one of `angles`, `matrix`)")
+    coef = stokes_matrix(angles) if matrix is None else matrix
+    if isinstance(threshold, str):
+        if threshold != "otsu":
+            raise ValueError(f"specular_mask: threshold {threshold!r} is not 'otsu' or a number in byte units")
+        fixed = None
+    else:
+        if not 0 <= float(threshold) <= 255:
+            raise ValueError(f"specular_mask: threshold {threshold!r} is outside the byte range [0, 255]")
+        fixed = int(float(threshold))
+    views_u8 = list(views_u8)
+    if len(views_u8) != 4:
+        raise ValueError(f"specular_mask takes four views, got {len(views_u8)}")
+    v0 = views_u8[0]
+    if not isinstance(v0, torch.Tensor) or v0.dim() != 3:
+        raise ValueError("specular_mask takes four uint8 [h,w,3] device tensors")
+    h, w = int(v0.shape[0]), int(v0.shape[1])
+    q, tmp, mask = (torch.empty((h, w), dtype=torch.uint8, device=v0.device) for _ in range(3))
+    hist = torch.empty(256, dtype=torch.int32, device=v0.device)
+    stats = torch.empty(3, dtype=torch.int32, device=v0.device)
+    ops.specmask(views_u8, coef, q, hist, tmp, mask, stats, floor, fixed, open_radius, dilate_radius)
+    return mask, q, stats
+
+
+def polar_sample_files(data_dir, subdirs, who):
+    """The sorted file lists of the first four `subdirs` of `data_dir`, with the refusals of write_estimated_diffuse: four
+    directories, equal counts."""
+    views = tuple(subdirs)[:4]
+    if len(views) != 4:
+        raise ValueError(f"{who} needs four view directories, got {views}")
+    files = [list_images(os.path.join(data_dir, s)) for s in views]
+    if any(len(f) != len(files[0]) for f in files):
+        raise ValueError(f"the four view directories hold different numbers of images: {[len(f) for f in files]}")
+    return views, files
+
+
+def decode_sample(paths, index):
+    """The four decoded views of one sample; views of unequal size raise, naming the files."""
+    imgs = [_decode(p) for p in paths]
+    if any(a.shape != imgs[0].shape for a in imgs):
+        raise ValueError(f"the four views of sample {index} differ in size: " + ", ".join(f"{p} {a.shape[0]}x{a.shape[1]}" for p, a in zip(paths, imgs)))
+    return imgs
+
+
+def write_specular_masks(data_dir, out_dir, subdirs=PSD_SUBDIRS, angles=None, name_from=2, device=None, **mask_options):
+    """Materialise the specular mask of every sample as a one-channel PNG (0 / 255) at the sample's own size: the sibling of
+    write_estimated_diffuse.  The first four `subdirs` of `data_dir` are listed as the loader lists them; sample i's mask is
+    specular_mask of its four views (`angles`, or the angles read from the directory names; `mask_options` = its threshold, floor,
+    open_radius and dilate_radius), written to `out_dir` under the stem of view `name_from` -- by default the third view (I90), the
+    one whose Y plane train_step feeds SpecSeg.predict, so that train_specseg(specseg_image_dir=<data_dir>/I90,
+    specseg_mask_dir=out_dir) pairs them as they are.  `out_dir`/masks.jsonl gets one line per sample: name, t (Otsu's), t_eff
+    (applied), fraction (of the frame that is masked) -- samples whose mask is empty or covers most of the frame show there.
+    Same refusals as write_estimated_diffuse: four directories, equal counts, equal sizes.  Returns the list of PNG files written."""
+    import json
+    import torch
+    from PIL import Image
+    bad = sorted(set(mask_options) - set(MASK_OPTIONS))
+    if bad:
+        raise TypeError(f"write_specular_masks: unknown option(s) {bad}; specular_mask takes {MASK_OPTIONS}")
+    if name_from not in (0, 1, 2, 3):
+        raise ValueError(f"write_specular_masks: name_from {name_from!r} is not a view index 0..3")
+    views, files = polar_sample_files(data_dir, subdirs, "write_specular_masks")
+    coef = stokes_matrix(angles if angles is not None else angles_from_subdirs(views))
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    os.makedirs(out_dir, exist_ok=True)
+    written, rows = [], []
+    for i in range(len(files[0])):
+        paths = [f[i] for f in files]
+        imgs = decode_sample(paths, i)
+        with torch.cuda.device(dev):
+            mask, _, stats = specular_mask([torch.from_numpy(a).to(dev) for a in imgs], matrix=coef, **mask_options)
+        m, st = mask.cpu().numpy(), stats.cpu().numpy()
+        name = Path(paths[name_from]).stem
+        out = os.path.join(out_dir, name + ".png")
+        Image.fromarray(m).save(out)                   # uint8 [h,w]: mode "L"
+        written.append(out)
+        rows.append(dict(name=name, t=int(st[0]), t_eff=int(st[1]), fraction=int(st[2]) / m.size))
+    with open(os.path.join(out_dir, "masks.jsonl"), "w") as f:
+        for r in rows:
+            f.write(json.dumps(r) + "\n")
+    return written
+
+
 def write_estimated_diffuse(data_dir, out_dir, subdirs=PSD_SUBDIRS, mode="min", angles=None, device=None):
     """Materialise the estimated-diffuse image of every sample as a PNG at the sample's own size: the imwrite that
     utils.calculate_estimate_diffuse left commented out.  The first four `subdirs` of `data_dir` are listed as the loader lists
@@ -118,22 +226,14 @@ def write_estimated_diffuse(data_dir, out_dir, subdirs=PSD_SUBDIRS, mode="min", 
     from . import ops
     if mode not in ops.POLAR_MODES:
         raise ValueError(f"write_estimated_diffuse: mode {mode!r} is not 'min' or 'stokes'")
-    views = tuple(subdirs)[:4]
-    if len(views) != 4:
-        raise ValueError(f"write_estimated_diffuse needs four view directories, got {views}")
+    views, files = polar_sample_files(data_dir, subdirs, "write_estimated_diffuse")
     coef = stokes_matrix(angles if angles is not None else angles_from_subdirs(views)) if mode == "stokes" else None
-    files = [list_images(os.path.join(data_dir, s)) for s in views]
-    n = len(files[0])
-    if any(len(f) != n for f in files):
-        raise ValueError(f"the four view directories hold different numbers of images: {[len(f) for f in files]}")
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     os.makedirs(out_dir, exist_ok=True)
     written = []
-    for i in range(n):
+    for i in range(len(files[0])):
         paths = [f[i] for f in files]
-        imgs = [_decode(p) for p in paths]
-        if any(a.shape != imgs[0].shape for a in imgs):
-            raise ValueError(f"the four views of sample {i} differ in size: " + ", ".join(f"{p} {a.shape[0]}x{a.shape[1]}" for p, a in zip(paths, imgs)))
+        imgs = decode_sample(paths, i)
         h, w, _ = imgs[0].shape
         srcs = [torch.from_numpy(a).to(dev) for a in imgs]
         planes = torch.empty((5, h, w, 3), dtype=torch.float32, device=dev)

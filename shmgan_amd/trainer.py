@@ -55,7 +55,11 @@ _DEFAULTS = dict(image_size=128, batch_size=1, filter_size=64, g_lr=0.00002, d_l
                  loss_log_step=0, histogram_step=0, nonfinite=None, diffuse_source="dir",
                  shuffle=False, data_seed=0, aug_flip_lr=0.0, aug_flip_ud=0.0, aug_crop_min=1.0, aug_views="physical",
                  cache="none", cache_gb=None,
-                 specseg_image_dir="", specseg_mask_dir="", specseg_epochs=20, specseg_lr=1e-3, specseg_batch_size=8)
+                 specseg_image_dir="", specseg_mask_dir="", specseg_epochs=20, specseg_lr=1e-3, specseg_batch_size=8,
+                 specseg_mask_source="dir", specseg_mask_threshold="otsu", specseg_mask_floor=16, specseg_mask_open=1,
+                 specseg_mask_dilate=2)
+
+SPECSEG_MASK_SOURCES = ("dir", "polar")                   # where train_specseg's masks come from
 
 
 class KernelAbortError(RuntimeError):
@@ -273,18 +277,51 @@ class ShmGANwithSSpecSeg:
         options.  The reference builds this optimiser (SHM.py:175) and never steps it; its checkpoint is not available, so this is
         how the weights every Spec_loss, live-attention step and test-mode image depends on are made.  Adam runs on the schedule of
         optimizer_G with the trainer's beta1 / beta2; the five scalars are logged per epoch through print_fn.  G and D are not
-        touched; the next train_step / infer uses the trained network.  Returns fit()'s history."""
-        from .data import MaskDataset
-        opt = lambda k: getattr(args, k, None) if args is not None and getattr(args, k, None) is not None else getattr(self.args, k)
-        idir, mdir = opt("specseg_image_dir"), opt("specseg_mask_dir")
-        if not idir or not mdir:
-            raise ValueError("train_specseg needs specseg_image_dir and specseg_mask_dir")
+        touched; the next train_step / infer uses the trained network.  Returns fit()'s history.
+        args.specseg_mask_source = "polar" needs neither directory: the pairs come from the raw capture under data_dir
+        (data.MaskDataset.from_polar: view 2 as the image, polar.specular_mask of the four views as its mask), with
+        args.specseg_mask_threshold / specseg_mask_floor / specseg_mask_open / specseg_mask_dilate as the mask's options."""
+        opt = self._specseg_opt(args)
+        source = opt("specseg_mask_source")
+        if source not in SPECSEG_MASK_SOURCES:
+            raise ValueError(f"train_specseg: specseg_mask_source {source!r} is not one of {SPECSEG_MASK_SOURCES}")
+        if source == "polar":
+            ds = self._polar_mask_dataset(opt)
+        else:
+            from .data import MaskDataset
+            idir, mdir = opt("specseg_image_dir"), opt("specseg_mask_dir")
+            if not idir or not mdir:
+                raise ValueError("train_specseg needs specseg_image_dir and specseg_mask_dir")
+            ds = MaskDataset(idir, mdir, self.image_size, int(opt("specseg_batch_size")), device=self.device)
         if self.SpecSeg is None:
             self.SpecSeg = self.build_specseg()
-        ds = MaskDataset(idir, mdir, self.image_size, int(opt("specseg_batch_size")), device=self.device)
         x, y = ds.tensors()
         return self.SpecSeg.fit(x, y, batch_size=ds.B, epochs=int(opt("specseg_epochs")), lr=float(opt("specseg_lr")), beta1=self.beta1,
                                 beta2=self.beta2, shuffle=True, print_fn=print_fn)
+
+    def _specseg_opt(self, args):
+        """Option lookup of train_specseg / evaluate_specseg: `args` first, then the trainer's own options."""
+        return lambda k: getattr(args, k, None) if args is not None and getattr(args, k, None) is not None else getattr(self.args, k)
+
+    def _polar_mask_dataset(self, opt):
+        from .data import MaskDataset
+        data_dir = opt("data_dir")
+        if not data_dir:
+            raise ValueError("specseg_mask_source='polar' needs data_dir: the capture's four view directories")
+        return MaskDataset.from_polar(data_dir, self.image_size, int(opt("specseg_batch_size")), device=self.device,
+                                      threshold=opt("specseg_mask_threshold"), floor=int(opt("specseg_mask_floor")),
+                                      open_radius=int(opt("specseg_mask_open")), dilate_radius=int(opt("specseg_mask_dilate")))
+
+    def evaluate_specseg(self, args=None):
+        """Score the current mask network against the polar masks of a capture (args.data_dir or the trainer's; the mask options of
+        train_specseg): has the network learnt what the polariser sees?  Inference mode, through SpecSeg.evaluate.  Returns
+        {"loss", "dice", "focal", "iou", "f1"}."""
+        opt = self._specseg_opt(args)
+        ds = self._polar_mask_dataset(opt)
+        if self.SpecSeg is None:
+            self.SpecSeg = self.build_specseg()
+        x, y = ds.tensors()
+        return self.SpecSeg.evaluate(x, y, batch_size=ds.B)
 
     def build(self, seed=42, beta_seed=43, attention_seed=45):
         """Build G, D and SpecSeg and give G/D the synthetic init of SURVEY 8(d): weights N(0,0.02) from

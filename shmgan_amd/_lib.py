@@ -19,7 +19,6 @@ HEADER = _HERE.parent / "include" / "shmgan_hip.h"
 SOURCES = ["runtime.hip", "conv_igemm.hip", "conv_dma.hip", "conv_halo.hip", "conv_wreg.hip", "conv_wreg_f32.hip", "conv_phase4.hip", "conv_wreg16.hip", "conv_pingpong.hip", "conv_wgrad.hip", "conv_wgrad_gen.hip", "conv_wgrad_halo.hip", "conv_wgrad_halo16.hip", "conv_wgrad_halo8.hip", "conv_wgrad_x3.hip", "conv_fwd_x3.hip", "conv_rgb.hip", "elem.hip", "instnorm.hip", "instnorm_bwd.hip", "instnorm_bwd_2pass.hip", "instnorm_bwd_fused8.hip", "instnorm_bwd_fusedg.hip", "grad_sums.hip", "heads.hip", "dgrad_sum1.hip", "color.hip", "imgloss.hip", "metrics.hip", "specseg.hip", "data.hip", "polar.hip", "specmask.hip", "augment.hip", "augment_batch.hip", "export.hip", "telemetry.hip", "specseg_train.hip"]
 # headers every source may include: a change of any of them rebuilds every object (tools/sanitize_host.py goes by the same list)
 SHARED_HEADERS = [CSRC / "common.h", CSRC / "elem.h", CSRC / "ablate.h", CSRC / "tapgemm.h", CSRC / "tapgemm_dev.h", CSRC / "wgrad.h", CSRC / "in_bwd.h", CSRC / "x3split.h", CSRC / "polar_est.h", CSRC / "augment_px.h", HEADER]
-F32, BF16 = 0, 1                 # SHM_F32 / SHM_BF16 of include/shmgan_hip.h
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-munsafe-fp-atomics",
                "-Wall", "-Wno-unused-function", "-Wno-unused-local-typedef"]
 
@@ -27,121 +26,47 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-munsafe-fp-
 # forms (v_pk_add_f32 / v_pk_mul_f32) cost several times their scalar pairs (MI355X guide, cycle constants)
 EXTRA_FLAGS = {"conv_pingpong.hip": ["-fno-slp-vectorize"]}
 
-P, I, Z, F = C.c_void_p, C.c_int, C.c_size_t, C.c_float
+# C scalar types of the header -> ctypes; every pointer or array is c_void_p, except `const char*`
+_C_SCALARS = {"void": None, "int": C.c_int, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t, "unsigned": C.c_uint,
+              "long long": C.c_longlong, "unsigned long long": C.c_ulonglong}
 
-# name -> (restype, argtypes); must mirror include/shmgan_hip.h (tests/test_abi.py checks it)
-SIGNATURES = {
-    "shm_version": (I, []),
-    "shm_last_error": (C.c_char_p, []),
-    "shm_last_kernel": (C.c_char_p, []),
-    "shm_set_tuning": (I, [C.c_char_p, I]),
-    "shm_get_tuning": (I, [C.c_char_p, P]),
-    "shm_transpose_taps": (I, [P, P, I, I, I, I, I, P]),
-    "shm_transpose_taps_multi": (I, [I, P, P, P, P, P, P, I, P]),
-    "shm_cast_f32": (I, [P, P, Z, I, P]),
-    "shm_conv2d_fwd": (I, [P, P, I, I, I, P, P, P, I, I, I, I, I, I, I, I, F, I, P]),
-    "shm_conv2d_in_fwd": (I, [P, P, I, I, I, P, P, P, I, I, I, I, I, I, I, I, F, P, P, F, I, P]),
-    "shm_conv2d_dgrad": (I, [P, I, P, P, P, I, I, I, I, I, I, I, I, I, I, I, P]),
-    "shm_conv2d_transpose_fwd": (I, [P, I, P, P, P, I, I, I, I, I, I, F, I, P]),
-    "shm_conv2d_wgrad_workspace": (Z, [I, I, I, I, I, I]),
-    "shm_conv2d_wgrad_partial": (I, [P, P, I, I, I, P, I, I, I, I, I, I, I, I, I, P, Z, I, P, P]),
-    "shm_conv2d_wgrad_reduce": (I, [P, P, Z, I, I, P]),
-    "shm_conv2d_wgrad": (I, [P, P, I, I, I, P, I, P, I, I, I, I, I, I, I, I, I, P, Z, I, P]),
-    "shm_in_stats": (I, [P, I, P, I, I, I, F, I, P]),
-    "shm_in_apply": (I, [P, I, P, P, P, I, I, I, I, I, P]),
-    "shm_in_apply_pool": (I, [P, I, P, P, P, I, P, I, I, I, I, I, I, P]),
-    "shm_in_norm_table": (I, [P, P, P, I, I, P]),
-    "shm_conv2d_in_fwd_norm": (I, [P, P, I, I, I, P, P, I, P, P, P, I, I, I, I, I, I, I, I, F, P, P, F, P, P, I, P]),
-    "shm_conv2d_norm_prepare": (I, [P, P, P, I, I, P, P, I, I, I, I, I, P]),
-    "shm_conv2d_norm_supported": (I, [I, I, I, I, I, I, I, I, I, I]),
-    "shm_conv2d_wgrad_norm": (I, [P, P, I, I, I, P, P, I, P, I, P, I, I, I, I, I, I, I, I, I, P, Z, I, P]),
-    "shm_conv2d_wgrad_partial_norm": (I, [P, P, I, I, I, P, P, I, P, I, I, I, I, I, I, I, I, I, P, Z, I, P, P]),
-    "shm_conv2d_wgrad_norm_workspace": (Z, [I, I, I, I, I, I, I]),
-    "shm_conv2d_wgrad_norm_finish": (I, [P, P, P, I, I, I, I, I, I, P]),
-    "shm_set_clock_probe": (I, [P]),
-    "shm_conv2d_wgrad_norm_supported": (I, [I, I, I, I, I, I, I, I, I, I, I]),
-    "shm_in_pool": (I, [P, I, P, P, P, I, I, I, I, I, I, P]),
-    "shm_in_bwd": (I, [P, I, P, I, P, I, P, P, P, I, P, P, P, Z, P, P, I, I, I, I, F, I, P]),
-    "shm_conv2d_dgrad_gsum": (I, [P, I, P, P, P, I, I, I, I, I, I, I, I, I, I, P, I, P, P, I, P, I, P]),
-    "shm_conv2d_fwd_gsum": (I, [P, P, I, I, I, P, P, P, I, I, I, I, I, I, I, I, F, P, I, P, I, P]),
-    "shm_in_bwd_apply": (I, [P, I, P, I, P, I, P, P, P, P, P, P, I, P, P, I, I, I, I, F, I, P]),
-    "shm_sum_input_channels": (I, [P, I, I, C.c_uint, P, P]),
-    "shm_conv3x3_dgrad_sum1": (I, [P, I, P, P, I, I, I, I, I, I, I, I, P]),
-    "shm_lrelu_bwd": (I, [P, I, P, I, P, I, P, P, Z, I, F, I, P]),
-    "shm_avgpool2_fwd": (I, [P, I, P, I, I, I, I, I, I, P]),
-    "shm_cvt_f64_f32": (I, [P, P, Z, I, P]),
-    "shm_zero": (I, [P, Z, P]),
-    "shm_head_fwd": (I, [P, I, P, P, P, Z, I, F, I, P]),
-    "shm_head_bwd": (I, [P, I, P, P, P, P, I, P, P, P, Z, I, F, I, P]),
-    "shm_head_in_fwd": (I, [P, I, P, P, P, P, P, I, I, I, F, I, P]),
-    "shm_head_in_bwd": (I, [P, I, P, P, P, P, P, P, I, P, P, P, P, I, I, I, F, I, P]),
-    "shm_in_bwd_rank1": (I, [P, P, P, I, P, P, P, I, P, P, I, I, I, I, F, I, P]),
-    "shm_patch_fwd": (I, [P, I, P, P, I, I, I, I, F, I, P]),
-    "shm_patch_bwd": (I, [P, I, P, P, P, P, P, I, P, I, I, I, I, F, I, P]),
-    "shm_dense_fwd": (I, [P, P, P, I, I, I, I, P]),
-    "shm_dense_bwd": (I, [P, P, P, P, P, I, I, I, I, P]),
-    "shm_mul_mask": (I, [P, P, P, Z, F, I, P]),
-    "shm_rgb2yuv_std": (I, [P, P, P, P, I, Z, P]),
-    "shm_avg_cbcr": (I, [P, P, P, P, P, P, Z, P]),
-    "shm_build_gen_input": (I, [P, P, P, P, P, P, I, I, P, I, I, Z, I, P]),
-    "shm_cyc_input_bwd": (I, [P, I, I, P, I, Z, I, P]),
-    "shm_yuv2rgb": (I, [P, P, P, P, P, I, I, I, Z, I, P]),
-    "shm_pack_rgb16": (I, [P, P, P, I, Z, I, P]),
-    "shm_rgb16_to_dy": (I, [P, I, P, Z, I, I, P]),
-    "shm_randn": (I, [P, Z, F, C.c_ulonglong, C.c_uint, P]),
-    "shm_keep_mask": (I, [P, Z, F, C.c_ulonglong, C.c_uint, P]),
-    "shm_dhead_losses": (I, [P, P, P, P, P, P, I, I, F, I, P]),
-    "shm_image_losses_workspace": (Z, [I, I]),
-    "shm_image_losses": (I, [P, P, P, P, P, P, I, F, P, P, P, P, Z, I, I, P]),
-    "shm_image_metrics_workspace": (Z, [I, I]),
-    "shm_image_metrics": (I, [P, P, P, P, Z, I, I, P]),
-    "shm_image_metrics_hw_workspace": (Z, [I, I, I]),
-    "shm_image_metrics_hw": (I, [P, I, I, I, I, P, I, I, P, P, Z, I, P]),
-    "shm_pack_channels": (I, [P, I, I, I, P, I, Z, P]),
-    "shm_bn_apply": (I, [P, I, P, P, P, P, F, P, I, Z, I, P]),
-    "shm_maxpool2_fwd": (I, [P, I, P, I, I, I, I, I, P]),
-    "shm_conv2d_transpose2x2_fwd": (I, [P, I, P, P, P, I, I, I, I, I, I, F, I, P]),
-    "shm_head_sigmoid_fwd": (I, [P, I, P, P, P, Z, I, P]),
-    "shm_spec_loss": (I, [P, P, P, P, P, I, Z, P]),
-    "shm_mask_pool_pack": (I, [P, P, I, I, I, I, I, P]),
-    "shm_mask_pool_pack_hw": (I, [P, P, I, I, I, I, I, I, P]),
-    "shm_add_bcast": (I, [P, P, P, I, Z, I, I, I, P]),
-    "shm_sum_groups": (I, [P, P, I, Z, I, I, I, I, P]),
-    "shm_resize_bilinear_u8": (I, [P, I, I, I, P, I, I, F, I, P]),
-    "shm_load_pad_u8": (I, [P, I, I, I, P, I, I, I, I, F, P]),
-    "shm_polar_views_u8": (I, [P, I, I, P, I, P, I, I, F, I, P]),
-    "shm_polar_maps": (I, [P, Z, P, P, P, P, P]),
-    "shm_specmask_strength": (I, [P, I, I, P, P, P, P]),
-    "shm_specmask_otsu": (I, [P, I, I, P, P]),
-    "shm_specmask_morph": (I, [P, I, I, I, I, P, P, P, P]),
-    "shm_specmask": (I, [P, I, I, P, I, I, I, I, P, P, P, P, P, P]),
-    "shm_augment_views_u8": (I, [P, I, I, I, I, P, P, F, F, F, F, I, I, P, I, I, F, P]),
-    "shm_augment_batch_u8": (I, [P, I, I, I, P, P, P, Z, I, I, F, P]),
-    "shm_export_u8_workspace": (Z, [I]),
-    "shm_export_u8": (I, [P, P, I, P, I, P, Z, P, Z, P]),
-    "shm_export_u8_hw": (I, [P, P, I, P, I, P, Z, P, Z, P]),
-    "shm_running_scale_mean": (I, [P, I, P, P, P]),
-    "shm_adam_clip": (I, [P, P, P, P, Z, F, F, F, F, F, P, P]),
-    "shm_tensor_stats_workspace": (Z, [I, Z]),
-    "shm_tensor_stats": (I, [P, Z, P, P, I, F, P, P, P, Z, P]),
-    "shm_loss_ring_put": (I, [P, P, P, P, P, I, I, C.c_longlong, P]),
-    "shm_bn_train_fwd": (I, [P, I, P, P, P, P, F, F, P, I, P, P, Z, Z, I, P]),
-    "shm_bn_train_bwd": (I, [P, I, P, I, P, P, P, I, P, P, P, Z, Z, I, P]),
-    "shm_maxpool2_bwd": (I, [P, I, P, I, P, I, I, I, I, I, I, P]),
-    "shm_conv2d_transpose2x2_dgrad": (I, [P, I, P, P, I, I, I, I, I, I, P]),
-    "shm_conv2d_transpose2x2_wgrad_workspace": (Z, [I, I, I, I, I]),
-    "shm_conv2d_transpose2x2_wgrad": (I, [P, I, P, I, P, P, P, Z, I, I, I, I, I, P]),
-    "shm_head_logit_fwd": (I, [P, I, P, P, P, Z, I, P]),
-    "shm_head_logit_bwd": (I, [P, I, P, P, P, I, P, P, P, Z, Z, I, P]),
-    "shm_seg_loss": (I, [P, P, P, P, P, Z, Z, P]),
-    "shm_adam": (I, [P, P, P, P, Z, F, F, F, F, F, F, P]),
-}
+
+def _ctype(decl, fn):
+    """ctypes class of one return type or parameter declaration (its name, if any, included) of function `fn`."""
+    words = re.sub(r"\bconst\b", " ", decl).split()
+    if "*" in decl or "[" in decl:
+        return C.c_char_p if "".join(words).startswith("char*") and decl.count("*") == 1 and "[" not in decl else C.c_void_p
+    for t in (" ".join(words), " ".join(words[:-1])):          # without a parameter name, with one
+        if t in _C_SCALARS:
+            return _C_SCALARS[t]
+    raise ValueError(f"{fn}: no ctypes class for the C type in {decl.strip()!r}")
+
+
+def parse_header(txt):
+    """(SIGNATURES, CONSTANTS) of a C header's text: name -> (restype, argtypes) for every `ret shm_name(args);` in declaration order,
+    and name -> int for every object-like `#define SHM_X <integer>` or `(-<integer>)`.  A type outside _C_SCALARS raises."""
+    txt = re.sub(r"/\*.*?\*/", " ", txt, flags=re.S)
+    consts = {m.group(1): int(m.group(2).strip("()"))
+              for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(SHM_\w+)[ \t]+(\(-\d+\)|\d+)[ \t]*$", txt, flags=re.M)}
+    txt = re.sub(r"^[ \t]*#(?:.*\\\n)*.*$", "", txt, flags=re.M)                  # preprocessor lines and their continuations
+    txt = re.sub(r"\btypedef\s+struct\b[^{};]*\{[^{}]*\}[^;]*;", "", txt)      # struct bodies: their members are no prototypes
+    sigs = {}
+    for m in re.finditer(r"([\w\s*]+?)\b(shm_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", txt):
+        ret, fn, args = m.group(1), m.group(2), m.group(3).strip()
+        if fn in sigs:
+            raise ValueError(f"{fn}: declared twice")
+        sigs[fn] = (_ctype(ret, fn), [] if args in ("", "void") else [_ctype(a, fn) for a in args.split(",")])
+    return sigs, consts
+
+
+# name -> (restype, argtypes), and the header's integer constants: read from include/shmgan_hip.h, which is the one statement of the ABI
+SIGNATURES, CONSTANTS = parse_header(HEADER.read_text())
+F32, BF16 = CONSTANTS["SHM_F32"], CONSTANTS["SHM_BF16"]
+
 
 def header_functions():
-    """Names declared in include/shmgan_hip.h (used by the ABI test)."""
-    txt = HEADER.read_text()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return re.findall(r"\b(shm_[a-z0-9_]+)\s*\(", txt)
+    """Names declared in include/shmgan_hip.h, in its order."""
+    return list(SIGNATURES)
 
 
 def build(force=False, verbose=False, jobs=None):

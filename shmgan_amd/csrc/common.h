@@ -98,8 +98,6 @@ __device__ __forceinline__ unsigned shm_lds_addr(const void* p) {
     return (unsigned)(size_t)(__attribute__((address_space(3))) const void*)p;
 }
 
-#define SHM_TG_COUNT 17           // SHM_TG_* of include/shmgan_hip.h
-
 // 4-channel vector access in either element type; arithmetic is always fp32.
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *(const f32x4*)p; }
 __device__ __forceinline__ f32x4 ld4(const bf16_t* p) {

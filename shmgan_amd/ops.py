@@ -11,7 +11,7 @@ import math
 
 import torch
 
-from ._lib import check, lib
+from ._lib import CONSTANTS, check, lib
 
 
 def _stream():
@@ -49,36 +49,29 @@ class KernelTimer:
             nbytes = nbytes()
         self.brecs.append((name, nbytes, e0, e1))
 
+    @staticmethod
+    def _fold(rows, unit):
+        """{key: dict(launches, ms, <unit>)} of rows (key, amount, start event, end event) -- call after a device synchronize."""
+        out = {}
+        for key, amount, e0, e1 in rows:
+            d = out.setdefault(key, {"launches": 0, "ms": 0.0, unit: 0.0})
+            d["launches"] += 1
+            d["ms"] += e0.elapsed_time(e1)
+            d[unit] += amount
+        return out
+
     def bytes_summary(self):
         """{entry point: dict(launches, ms, bytes)} of the HBM-bound passes (algorithmic bytes: every tensor the pass must read or
         write, once) -- call after a device synchronize."""
-        out = {}
-        for name, nb, e0, e1 in self.brecs:
-            d = out.setdefault(name, dict(launches=0, ms=0.0, bytes=0.0))
-            d["launches"] += 1
-            d["ms"] += e0.elapsed_time(e1)
-            d["bytes"] += nb
-        return out
+        return self._fold(self.brecs, "bytes")
 
     def per_shape(self):
         """{(symbol, label): dict(launches, ms, flops)} for tuning."""
-        out = {}
-        for sym, flops, e0, e1, label in self.recs:
-            d = out.setdefault((sym, label), dict(launches=0, ms=0.0, flops=0.0))
-            d["launches"] += 1
-            d["ms"] += e0.elapsed_time(e1)
-            d["flops"] += flops
-        return out
+        return self._fold((((sym, label), flops, e0, e1) for sym, flops, e0, e1, label in self.recs), "flops")
 
     def summary(self):
         """{symbol: dict(launches, ms, flops)} -- call after a device synchronize."""
-        out = {}
-        for sym, flops, e0, e1, _ in self.recs:
-            d = out.setdefault(sym, dict(launches=0, ms=0.0, flops=0.0))
-            d["launches"] += 1
-            d["ms"] += e0.elapsed_time(e1)
-            d["flops"] += flops
-        return out
+        return self._fold((r[:4] for r in self.recs), "flops")
 
 
 TIMER = None
@@ -102,12 +95,20 @@ def _p(t):
     return 0 if t is None else t.data_ptr()
 
 
+_F32, _BF16, _BF16_GF32 = CONSTANTS["SHM_F32"], CONSTANTS["SHM_BF16"], CONSTANTS["SHM_BF16_GF32"]
+
+
+def _dtc(dtype):
+    """SHM_BF16 for torch.bfloat16, SHM_F32 for any other torch dtype (the shape queries, which see no tensor)."""
+    return _BF16 if dtype == torch.bfloat16 else _F32
+
+
 def _dt(t):
     """SHM_F32 / SHM_BF16 code of an activation tensor."""
     if t.dtype == torch.bfloat16:
-        return 1
+        return _BF16
     if t.dtype == torch.float32:
-        return 0
+        return _F32
     raise TypeError(f"activation tensors are float32 or bfloat16, got {t.dtype}")
 
 
@@ -115,16 +116,17 @@ def _dtg(act, grad):
     """dtype code of a call with activation tensor `act` and gradient-signal ([G]) tensor `grad`:
     SHM_BF16_GF32 when the activations are bf16 and the gradient signal is kept in fp32."""
     d = _dt(act)
-    if d == 1 and grad is not None and grad.dtype == torch.float32:
-        return 2
-    if grad is not None and d != 2 and _dt(grad) != d:
+    if d == _BF16 and grad is not None and grad.dtype == torch.float32:
+        return _BF16_GF32
+    if grad is not None and _dt(grad) != d:
         raise TypeError("gradient-signal tensors are float32, or share the activation dtype")
     return d
 
 
-# SHM_TG_* of include/shmgan_hip.h
-TAPGEMM_VARIANTS = {"auto": 0, "halo128": 1, "halo64": 2, "dma128x128": 3, "dma64x128": 4, "dma128x64": 5, "dma256x64": 6,
-                    "dma256x128": 7, "halo128_ph8": 8, "dma128x128_bk32": 9, "dma128x128_nst4": 10, "wreg": 11, "halo128_st": 12, "halo64_st": 13, "phase4": 14, "dma64x64": 15, "halo128_st_w4": 16}
+# the header's SHM_TG_<NAME> by lower-case name (SHM_TG_DMA_128x64 is "dma128x64")
+TAPGEMM_VARIANTS = {k[len("SHM_TG_"):].lower().replace("dma_", "dma"): v for k, v in CONSTANTS.items()
+                    if k.startswith("SHM_TG_") and k != "SHM_TG_COUNT"}
+assert sorted(TAPGEMM_VARIANTS.values()) == list(range(CONSTANTS["SHM_TG_COUNT"])), TAPGEMM_VARIANTS
 
 
 def set_tuning(key, value):
@@ -195,10 +197,10 @@ def conv2d_fwd(x, x2, c1, ldx, ldx2, wk, bias, y, ldy, batch, hi, wi, cin, cout,
                                   slope, _p(aux), ldaux, _p(red), _dtg(x, y), _stream()), "shm_conv2d_fwd_gsum"), label + " +gsum")
 
 
-STATS_SLOTS = 16            # SHM_STATS_SLOTS
+STATS_SLOTS = CONSTANTS["SHM_STATS_SLOTS"]
 
 
-NORM_EXACT, NORM_SCALED = 0, 1          # SHM_NORM_* of include/shmgan_hip.h
+NORM_EXACT, NORM_SCALED = CONSTANTS["SHM_NORM_EXACT"], CONSTANTS["SHM_NORM_SCALED"]
 
 
 def conv2d_in_fwd(x, x2, c1, ldx, ldx2, wk, bias, y, ldy, batch, hi, wi, cin, cout, ksize, stride, slope, stats, eps,
@@ -230,7 +232,7 @@ def conv2d_norm_prepare(wk, bias, nt, c, part_lo, wk_n, bias_n, batch, cin, cout
 
 
 def conv2d_wgrad_norm_workspace(batch, hi, wi, cin, cout, ksize, dtype):
-    return int(lib().shm_conv2d_wgrad_norm_workspace(batch, hi, wi, cin, cout, ksize, 1 if dtype == torch.bfloat16 else 0))
+    return int(lib().shm_conv2d_wgrad_norm_workspace(batch, hi, wi, cin, cout, ksize, _dtc(dtype)))
 
 
 def conv2d_wgrad_norm_finish(dw, nt, dzsum, batch, c, part_lo, cin, cout, ksize):
@@ -241,20 +243,18 @@ def conv2d_wgrad_norm_finish(dw, nt, dzsum, batch, c, part_lo, cin, cout, ksize)
 def conv2d_norm_supported(batch, hi, wi, cin, c1, cout, ksize, stride, norm_part, dtype):
     """Would conv2d_in_fwd(nt_x= / nt_x2=) run on a kernel that normalises source `norm_part` in LDS?  (c1: channels of x when
     there are two sources, else 0; dtype: torch dtype of the activations.)"""
-    dt = 1 if dtype == torch.bfloat16 else 0
-    return bool(lib().shm_conv2d_norm_supported(batch, hi, wi, cin, c1, cout, ksize, stride, norm_part, dt))
+    return bool(lib().shm_conv2d_norm_supported(batch, hi, wi, cin, c1, cout, ksize, stride, norm_part, _dtc(dtype)))
 
 
 def conv2d_wgrad_norm_supported(batch, hi, wi, cin, cin_ld, c1, cout, ksize, stride, norm_part, dtype):
-    dt = 1 if dtype == torch.bfloat16 else 0
-    return bool(lib().shm_conv2d_wgrad_norm_supported(batch, hi, wi, cin, cin_ld, c1, cout, ksize, stride, norm_part, dt))
+    return bool(lib().shm_conv2d_wgrad_norm_supported(batch, hi, wi, cin, cin_ld, c1, cout, ksize, stride, norm_part, _dtc(dtype)))
 
 
 def in_norm_table(stats, beta, nt, batch, c):
     check(lib().shm_in_norm_table(_p(stats), _p(beta), _p(nt), batch, c, _stream()), "shm_in_norm_table")
 
 
-GSUM_SLOTS = 8              # SHM_GSUM_SLOTS
+GSUM_SLOTS = CONSTANTS["SHM_GSUM_SLOTS"]
 # InstanceNorm-backward sums in the producing epilogue (model.py).  Default by activation dtype: ON in float32 -- the convolutions
 # are MFMA bound there and take the extra aux read in their stride: -3.4 ms of reduce passes for +1.3 ms of epilogues per step at
 # BASELINE configs[1] -- OFF in bfloat16, where the same epilogues sit in latency-bound kernels and cost what the reduce passes
@@ -424,7 +424,7 @@ def in_bwd_apply(g1, ldg1, g2, ldg2, a, lda, stats, beta, red, redp, dstage, dz,
                                _p(dbias), _p(dz_sums), batch, h, w, c, slope, _dtg(a, g1), _stream()), "shm_in_bwd_apply"))
 
 
-LRELU_RED_SLOTS = 64        # SHM_LRELU_RED_SLOTS
+LRELU_RED_SLOTS = CONSTANTS["SHM_LRELU_RED_SLOTS"]
 
 
 def lrelu_bwd(dy, lddy, y, ldy, dz, lddz, dbias, npix, c, slope, red=None):
@@ -537,7 +537,7 @@ def keep_mask(out, rate, seed, stream_id=0):
     check(lib().shm_keep_mask(_p(out), out.numel(), rate, int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream_id), _stream()), "shm_keep_mask")
 
 
-XENT_TF_FUSED, XENT_INTENDED = 0, 1          # SHM_XENT_* of include/shmgan_hip.h
+XENT_TF_FUSED, XENT_INTENDED = CONSTANTS["SHM_XENT_TF_FUSED"], CONSTANTS["SHM_XENT_INTENDED"]
 
 
 def dhead_losses(rf, cls, loss, drf_d, dcls_d, drf_g, batch, np_, target, xent_mode=XENT_TF_FUSED):
@@ -564,6 +564,27 @@ METRIC_NAMES = ("mse", "psnr", "ssim", "de76", "de94")          # the columns of
 _METRIC_ARENAS = {}
 
 
+def _default_arena(device):
+    """This module's own arena of `device` (made at its first use), for the calls that are given none."""
+    arena = _METRIC_ARENAS.get(device)
+    if arena is None:
+        from .model import Arena
+        arena = _METRIC_ARENAS[device] = Arena(device)
+    return arena
+
+
+def _metrics_out_ws(who, pred, out, arena, workspace, *dims):
+    """The checked (or new) float64 [B,5] result tensor of `who` and its workspace of workspace(B, *dims) bytes from `arena`."""
+    B = int(pred.shape[0])
+    if out is None:
+        out = torch.empty((B, 5), dtype=torch.float64, device=pred.device)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (B, 5) or not out.is_contiguous():
+        raise ValueError(f"{who}: out must be a contiguous float64 [{B},5] tensor")
+    if arena is None:
+        arena = _default_arena(pred.device)
+    return out, arena.get("metrics/ws", (max(workspace(B, *dims), 1),), torch.uint8)
+
+
 def image_metrics_workspace(batch, s):
     return int(lib().shm_image_metrics_workspace(batch, s))
 
@@ -580,15 +601,7 @@ def image_metrics(pred, target, out=None, arena=None):
     if not (pred.is_contiguous() and target.is_contiguous()):
         raise ValueError("image_metrics takes contiguous NHWC images")
     B, S = int(pred.shape[0]), int(pred.shape[1])
-    if out is None:
-        out = torch.empty((B, 5), dtype=torch.float64, device=pred.device)
-    elif out.dtype != torch.float64 or tuple(out.shape) != (B, 5) or not out.is_contiguous():
-        raise ValueError(f"image_metrics: out must be a contiguous float64 [{B},5] tensor")
-    if arena is None:
-        from .model import Arena
-        arena = _METRIC_ARENAS.setdefault(pred.device, Arena(pred.device))
-    n = image_metrics_workspace(B, S)
-    ws = arena.get("metrics/ws", (max(n, 1),), torch.uint8)
+    out, ws = _metrics_out_ws("image_metrics", pred, out, arena, image_metrics_workspace, S)
     check(lib().shm_image_metrics(_p(pred), _p(target), _p(out), _p(ws), ws.numel(), B, S, _stream()), "shm_image_metrics")
     return out
 
@@ -608,15 +621,7 @@ def image_metrics_hw(pred, window, target, out=None, arena=None):
     if not (pred.is_contiguous() and target.is_contiguous()):
         raise ValueError("image_metrics_hw takes contiguous NHWC images")
     B, hp, wp = int(pred.shape[0]), int(pred.shape[1]), int(pred.shape[2])
-    if out is None:
-        out = torch.empty((B, 5), dtype=torch.float64, device=pred.device)
-    elif out.dtype != torch.float64 or tuple(out.shape) != (B, 5) or not out.is_contiguous():
-        raise ValueError(f"image_metrics_hw: out must be a contiguous float64 [{B},5] tensor")
-    if arena is None:
-        from .model import Arena
-        arena = _METRIC_ARENAS.setdefault(pred.device, Arena(pred.device))
-    n = image_metrics_hw_workspace(B, h, w)
-    ws = arena.get("metrics/ws", (max(n, 1),), torch.uint8)
+    out, ws = _metrics_out_ws("image_metrics_hw", pred, out, arena, image_metrics_hw_workspace, h, w)
     check(lib().shm_image_metrics_hw(_p(pred), hp, wp, top, left, _p(target), h, w, _p(out), _p(ws), ws.numel(), B, _stream()),
           "shm_image_metrics_hw")
     return out
@@ -624,8 +629,9 @@ def image_metrics_hw(pred, window, target, out=None, arena=None):
 
 # ---- training telemetry (shm_tensor_stats / shm_loss_ring_put, include/shmgan_hip.h) ---------------------------------------
 TSTAT_NAMES = ["finite", "nan", "inf", "min", "max", "sum", "sumsq", "clipped"]     # SHM_TSTAT_* order
-TSTAT_N, THIST_BINS, THIST_EMIN, TSTAT_MAX_SEGS = 8, 44, -40, 128                   # SHM_TSTAT_N, SHM_THIST_BINS, SHM_THIST_EMIN, SHM_TSTAT_MAX_SEGS
-LOSS_ROW_DL, LOSS_ROW_IL, LOSS_ROW_SL, LOSS_ROW_STEP, LOSS_ROW_ABORT, LOSS_ROW = 16, 32, 5, 53, 54, 56     # SHM_LOSS_ROW_*
+TSTAT_N, THIST_BINS, THIST_EMIN, TSTAT_MAX_SEGS = (CONSTANTS["SHM_" + k] for k in ("TSTAT_N", "THIST_BINS", "THIST_EMIN", "TSTAT_MAX_SEGS"))
+LOSS_ROW_DL, LOSS_ROW_IL, LOSS_ROW_SL, LOSS_ROW_STEP, LOSS_ROW_ABORT, LOSS_ROW = (
+    CONSTANTS["SHM_LOSS_ROW" + k] for k in ("_DL", "_IL", "_SL", "_STEP", "_ABORT", ""))
 
 
 def tensor_stats_workspace(nseg, n):
@@ -664,8 +670,7 @@ def tensor_stats(x, offsets, sizes=None, scale=1.0, out=None, arena=None):
             or hist.dtype != torch.int64 or tuple(hist.shape) != (nseg, 2, THIST_BINS) or not hist.is_contiguous()):
         raise ValueError(f"tensor_stats: out must be contiguous (float64 [{nseg},{TSTAT_N}], int64 [{nseg},2,{THIST_BINS}]) tensors")
     if arena is None:
-        from .model import Arena
-        arena = _METRIC_ARENAS.setdefault(x.device, Arena(x.device))
+        arena = _default_arena(x.device)
     nb = tensor_stats_workspace(nseg, n)
     ws = arena.get("tstats/ws", (max((nb + 7) // 8, 1),), torch.int64)
     _timed_bytes("shm_tensor_stats", 4.0 * tab.total, lambda: check(          # read every segment once
@@ -683,8 +688,8 @@ def loss_ring_put(dl, il, sl, abort_word, ring, row, step):
 
 
 # ---- test-mode image export (the images test.py:305-317 logs) ----------------------------------------------------------
-EXPORT_MODES = {"rescale": 0, "scale": 1, "clip": 2}     # SHM_EXPORT_RESCALE / _SCALE / _CLIP
-EXPORT_DESC, EXPORT_MAX_JOBS = 8, 64                      # SHM_EXPORT_DESC, SHM_EXPORT_MAX_JOBS
+EXPORT_MODES = {k: CONSTANTS["SHM_EXPORT_" + k.upper()] for k in ("rescale", "scale", "clip")}
+EXPORT_DESC, EXPORT_HW_DESC, EXPORT_MAX_JOBS = CONSTANTS["SHM_EXPORT_DESC"], CONSTANTS["SHM_EXPORT_HW_DESC"], CONSTANTS["SHM_EXPORT_MAX_JOBS"]
 EXPORT_ALIGN = 16                                         # start of every job's bytes in export_u8's output
 
 
@@ -702,6 +707,65 @@ def export_layout(sizes, channels):
     return offs, n
 
 
+def _export_jobs(who, planes, windows, sizes, modes, mul):
+    """Host side of export_u8 (windows None: square planes, SHM_EXPORT_DESC words per job) and export_u8_hw (SHM_EXPORT_HW_DESC words):
+    every plane, window and mode checked; returns (descriptor rows, destination offsets, total bytes)."""
+    hw = windows is not None
+    shape, rows = ("[Hs,Ws,C]", "Ws") if hw else ("[S,S,C]", "S")
+    desc, chans = [], []
+    for p, win, (ho, wo), m in zip(planes, windows if hw else [None] * len(planes), sizes, modes):
+        if p.dtype != torch.float32 or not p.is_cuda:
+            raise TypeError(f"{who} takes float32 device planes, got {p.dtype} on {p.device}")
+        if p.dim() != 3 or p.shape[2] not in (1, 3) or (not hw and p.shape[0] != p.shape[1]):
+            raise ValueError(f"{who} takes {shape} planes with C in {{1,3}}, got {tuple(p.shape)}")
+        hs, ws_, c = int(p.shape[0]), int(p.shape[1]), int(p.shape[2])
+        ld = int(p.stride(1))
+        if p.stride(2) != 1 or ld < c or p.stride(0) != ws_ * ld:
+            raise ValueError(f"{who}: plane strides {p.stride()} are not [{rows}*ld, ld, 1] with ld >= {c}")
+        if isinstance(m, tuple) and len(m) == 2 and m[0] == "scale":
+            mode, k = EXPORT_MODES["scale"], int(m[1])
+            if mul is None or mul.dtype != torch.float32 or mul.dim() != 1 or not 0 <= k < mul.numel() or not mul.is_contiguous():
+                raise ValueError(f"{who}: mode {m} needs a contiguous float32 mul with more than {k} elements")
+        elif m in ("rescale", "clip"):
+            mode, k = EXPORT_MODES[m], 0
+        else:
+            raise ValueError(f"{who}: mode {m!r} is not 'rescale', 'clip' or ('scale', k)")
+        if hw:
+            y0, x0, hc, wc = (int(v) for v in win)
+            if min(y0, x0) < 0 or min(hc, wc) < 1 or y0 + hc > hs or x0 + wc > ws_:
+                raise ValueError(f"{who}: window {tuple(win)} outside the {hs} x {ws_} plane")
+            desc.append([hs, ws_, c, ld, y0, x0, hc, wc, int(ho), int(wo), mode, k])
+        else:
+            desc.append([hs, c, ld, int(ho), int(wo), mode, k])
+        chans.append(c)
+    offs, total = export_layout(sizes, chans)
+    return [d + [o] for d, o in zip(desc, offs)], offs, total
+
+
+def _export(who, planes, windows, sizes, modes, mul, out, arena):
+    """export_u8 / export_u8_hw behind their own count checks: entry point shm_<who>, one call per EXPORT_MAX_JOBS planes."""
+    import ctypes as C
+    desc, offs, total = _export_jobs(who, planes, windows, sizes, modes, mul)
+    dev = planes[0].device
+    if out is None:
+        out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.numel() < total:
+        raise ValueError(f"{who}: out must be a contiguous flat uint8 tensor of at least {total} bytes")
+    if arena is None:
+        arena = _default_arena(dev)
+    need = export_workspace(EXPORT_MAX_JOBS)
+    ws = arena.get("export/ws", (need,), torch.uint8)
+    width = EXPORT_DESC if windows is None else EXPORT_HW_DESC
+    assert all(len(d) == width for d in desc)
+    for j0 in range(0, len(planes), EXPORT_MAX_JOBS):
+        part = range(j0, min(len(planes), j0 + EXPORT_MAX_JOBS))
+        src = (C.c_void_p * len(part))(*[planes[j].data_ptr() for j in part])
+        dsc = (C.c_size_t * (width * len(part)))(*[v for j in part for v in desc[j]])
+        check(getattr(lib(), "shm_" + who)(src, dsc, len(part), _p(mul), 0 if mul is None else mul.numel(), _p(out), out.numel(),
+                                           _p(ws), need, _stream()), "shm_" + who)
+    return out, offs
+
+
 def export_u8(planes, sizes, modes, mul=None, out=None, arena=None):
     """float32 planes -> uint8 images (shm_export_u8, include/shmgan_hip.h, states the definitions).  planes: [S,S,C] device
     tensors, C in {1,3}, channels innermost with unit stride and a pixel pitch ld >= C (a channel slice of a wider NHWC tensor
@@ -710,53 +774,10 @@ def export_u8(planes, sizes, modes, mul=None, out=None, arena=None):
     given) at the offsets of export_layout.  Returns (out, offsets), filled asynchronously on the current stream.  The
     workspace comes from `arena` (default: one arena per device held by this module).  One shm_export_u8 call per
     EXPORT_MAX_JOBS planes (two launches at most each): a test-mode batch of 8 images with all 8 planes is one call."""
-    import ctypes as C
     n = len(planes)
     if n == 0 or len(sizes) != n or len(modes) != n:
         raise ValueError(f"export_u8: {n} planes, {len(sizes)} sizes, {len(modes)} modes")
-    desc, chans = [], []
-    for p, (ho, wo), m in zip(planes, sizes, modes):
-        if p.dtype != torch.float32 or not p.is_cuda:
-            raise TypeError(f"export_u8 takes float32 device planes, got {p.dtype} on {p.device}")
-        if p.dim() != 3 or p.shape[0] != p.shape[1] or p.shape[2] not in (1, 3):
-            raise ValueError(f"export_u8 takes [S,S,C] planes with C in {{1,3}}, got {tuple(p.shape)}")
-        S, c = int(p.shape[0]), int(p.shape[2])
-        ld = int(p.stride(1))
-        if p.stride(2) != 1 or ld < c or p.stride(0) != S * ld:
-            raise ValueError(f"export_u8: plane strides {p.stride()} are not [S*ld, ld, 1] with ld >= {c}")
-        if isinstance(m, tuple) and len(m) == 2 and m[0] == "scale":
-            mode, k = EXPORT_MODES["scale"], int(m[1])
-            if mul is None or mul.dtype != torch.float32 or mul.dim() != 1 or not 0 <= k < mul.numel() or not mul.is_contiguous():
-                raise ValueError(f"export_u8: mode {m} needs a contiguous float32 mul with more than {k} elements")
-        elif m in ("rescale", "clip"):
-            mode, k = EXPORT_MODES[m], 0
-        else:
-            raise ValueError(f"export_u8: mode {m!r} is not 'rescale', 'clip' or ('scale', k)")
-        desc.append([S, c, ld, int(ho), int(wo), mode, k, 0])
-        chans.append(c)
-    offs, total = export_layout(sizes, chans)
-    dev = planes[0].device
-    if out is None:
-        out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
-    elif out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.numel() < total:
-        raise ValueError(f"export_u8: out must be a contiguous flat uint8 tensor of at least {total} bytes")
-    if arena is None:
-        from .model import Arena
-        arena = _METRIC_ARENAS.setdefault(dev, Arena(dev))
-    need = export_workspace(EXPORT_MAX_JOBS)
-    ws = arena.get("export/ws", (need,), torch.uint8)
-    for d, o in zip(desc, offs):
-        d[7] = o
-    for j0 in range(0, n, EXPORT_MAX_JOBS):
-        part = range(j0, min(n, j0 + EXPORT_MAX_JOBS))
-        src = (C.c_void_p * len(part))(*[planes[j].data_ptr() for j in part])
-        dsc = (C.c_size_t * (EXPORT_DESC * len(part)))(*[v for j in part for v in desc[j]])
-        check(lib().shm_export_u8(src, dsc, len(part), _p(mul), 0 if mul is None else mul.numel(), _p(out), out.numel(),
-                                  _p(ws), need, _stream()), "shm_export_u8")
-    return out, offs
-
-
-EXPORT_HW_DESC = 13                                       # SHM_EXPORT_HW_DESC
+    return _export("export_u8", planes, None, sizes, modes, mul, out, arena)
 
 
 def export_u8_hw(planes, windows, sizes, modes, mul=None, out=None, arena=None):
@@ -764,53 +785,10 @@ def export_u8_hw(planes, windows, sizes, modes, mul=None, out=None, arena=None):
     (C in {1,3}, pixel pitch ld >= C), windows (y0, x0, hc, wc) per plane -- the part that is exported: RESCALE takes its min / max
     there and the resampling maps it to the plane's (ho, wo) of `sizes`.  modes, mul, out, arena, the output layout (export_layout)
     and the return value are export_u8's."""
-    import ctypes as C
     n = len(planes)
     if n == 0 or len(sizes) != n or len(modes) != n or len(windows) != n:
         raise ValueError(f"export_u8_hw: {n} planes, {len(windows)} windows, {len(sizes)} sizes, {len(modes)} modes")
-    desc, chans = [], []
-    for p, win, (ho, wo), m in zip(planes, windows, sizes, modes):
-        if p.dtype != torch.float32 or not p.is_cuda:
-            raise TypeError(f"export_u8_hw takes float32 device planes, got {p.dtype} on {p.device}")
-        if p.dim() != 3 or p.shape[2] not in (1, 3):
-            raise ValueError(f"export_u8_hw takes [Hs,Ws,C] planes with C in {{1,3}}, got {tuple(p.shape)}")
-        hs, ws_, c = int(p.shape[0]), int(p.shape[1]), int(p.shape[2])
-        ld = int(p.stride(1))
-        if p.stride(2) != 1 or ld < c or p.stride(0) != ws_ * ld:
-            raise ValueError(f"export_u8_hw: plane strides {p.stride()} are not [Ws*ld, ld, 1] with ld >= {c}")
-        if isinstance(m, tuple) and len(m) == 2 and m[0] == "scale":
-            mode, k = EXPORT_MODES["scale"], int(m[1])
-            if mul is None or mul.dtype != torch.float32 or mul.dim() != 1 or not 0 <= k < mul.numel() or not mul.is_contiguous():
-                raise ValueError(f"export_u8_hw: mode {m} needs a contiguous float32 mul with more than {k} elements")
-        elif m in ("rescale", "clip"):
-            mode, k = EXPORT_MODES[m], 0
-        else:
-            raise ValueError(f"export_u8_hw: mode {m!r} is not 'rescale', 'clip' or ('scale', k)")
-        y0, x0, hc, wc = (int(v) for v in win)
-        if min(y0, x0) < 0 or min(hc, wc) < 1 or y0 + hc > hs or x0 + wc > ws_:
-            raise ValueError(f"export_u8_hw: window {tuple(win)} outside the {hs} x {ws_} plane")
-        desc.append([hs, ws_, c, ld, y0, x0, hc, wc, int(ho), int(wo), mode, k, 0])
-        chans.append(c)
-    offs, total = export_layout(sizes, chans)
-    dev = planes[0].device
-    if out is None:
-        out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
-    elif out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.numel() < total:
-        raise ValueError(f"export_u8_hw: out must be a contiguous flat uint8 tensor of at least {total} bytes")
-    if arena is None:
-        from .model import Arena
-        arena = _METRIC_ARENAS.setdefault(dev, Arena(dev))
-    need = export_workspace(EXPORT_MAX_JOBS)
-    ws = arena.get("export/ws", (need,), torch.uint8)
-    for d, o in zip(desc, offs):
-        d[12] = o
-    for j0 in range(0, n, EXPORT_MAX_JOBS):
-        part = range(j0, min(n, j0 + EXPORT_MAX_JOBS))
-        src = (C.c_void_p * len(part))(*[planes[j].data_ptr() for j in part])
-        dsc = (C.c_size_t * (EXPORT_HW_DESC * len(part)))(*[v for j in part for v in desc[j]])
-        check(lib().shm_export_u8_hw(src, dsc, len(part), _p(mul), 0 if mul is None else mul.numel(), _p(out), out.numel(),
-                                     _p(ws), need, _stream()), "shm_export_u8_hw")
-    return out, offs
+    return _export("export_u8_hw", planes, windows, sizes, modes, mul, out, arena)
 
 
 def running_scale_mean(scale, acc, mul):
@@ -871,7 +849,7 @@ def spec_loss(cyc_y, cbcr, ds_ptrs, mask, loss, batch, npix):
 
 
 # ---- SpecSeg training (specseg_train.hip) ------------------------------------------------------------
-SST_MAX_BLOCKS = 256                                      # SHM_SST_MAX_BLOCKS
+SST_MAX_BLOCKS = CONSTANTS["SHM_SST_MAX_BLOCKS"]
 SEG_LOSS_NAMES = ("loss", "dice", "focal", "iou", "f1", "tp", "fp", "fn")     # the entries of seg_loss' result (SHM_SEG_LOSS_OUT)
 SEG_LOSS_WS_DOUBLES = SST_MAX_BLOCKS * 7 + 8              # SHM_SEG_LOSS_WS_DOUBLES
 
@@ -974,7 +952,41 @@ def load_pad_u8(src_u8, dst, top, left, scale=1.0 / 255.0):
 
 
 # ---- polarimetry: estimated-diffuse target and Stokes maps ----------------------------------------
-POLAR_MODES = {"min": 0, "stokes": 1}                    # SHM_POLAR_MIN / SHM_POLAR_STOKES
+POLAR_MODES = {"min": CONSTANTS["SHM_POLAR_MIN"], "stokes": CONSTANTS["SHM_POLAR_STOKES"]}
+
+
+def _u8_images(srcs, who, noun, dims, which):
+    """`who`'s check of its uint8 device images of one size: contiguous `dims` (say "[h,w,3]") `noun` ("views" / "images")."""
+    for s in srcs:
+        if s.dtype != torch.uint8 or not s.is_cuda:
+            raise TypeError(f"{who} takes uint8 device {noun}, got {s.dtype} on {s.device}")
+        if s.dim() != 3 or s.shape[2] != 3 or not s.is_contiguous():
+            raise ValueError(f"{who} takes contiguous {dims} {noun}, got {tuple(s.shape)} with strides {s.stride()}")
+    if any(s.shape != srcs[0].shape for s in srcs):
+        raise ValueError(f"{who}: {which} differ in size: {[tuple(s.shape[:2]) for s in srcs]}")
+
+
+def _f32_planes(dsts, who, device):
+    """`who`'s check of its five contiguous float32 [ho,wo,3] destination planes on `device`."""
+    for d in dsts:
+        if d.dtype != torch.float32 or d.device != device:
+            raise TypeError(f"{who} writes float32 planes on {device}, got {d.dtype} on {d.device}")
+        if d.dim() != 3 or d.shape[2] != 3 or not d.is_contiguous():
+            raise ValueError(f"{who} writes contiguous [ho,wo,3] planes, got {tuple(d.shape)} with strides {d.stride()}")
+    if any(d.shape != dsts[0].shape for d in dsts):
+        raise ValueError(f"{who}: the five planes differ in size: {[tuple(d.shape[:2]) for d in dsts]}")
+
+
+def _mat4(mix, who):
+    """None, or a 4x4 matrix (anything numpy takes, or a host tensor) as the C ABI's host float[16]."""
+    import ctypes as C
+    import numpy as np
+    if mix is None:
+        return None
+    m = np.asarray(mix.cpu() if isinstance(mix, torch.Tensor) else mix, dtype=np.float32)
+    if m.shape != (4, 4):
+        raise ValueError(f"{who}: mix must be a 4x4 matrix, got shape {m.shape}")
+    return (C.c_float * 16)(*[float(v) for v in m.reshape(-1)])
 
 
 def _polar_coef(coef, who):
@@ -999,20 +1011,8 @@ def polar_views_u8(srcs, dsts, mode="min", coef=None, scale=1.0 / 255.0, flip_ud
         raise ValueError(f"polar_views_u8: mode {mode!r} is not 'min' or 'stokes'")
     if mode == "stokes" and coef is None:
         raise ValueError("polar_views_u8: mode 'stokes' needs coef (polar.stokes_matrix of the polariser angles)")
-    for s in srcs:
-        if s.dtype != torch.uint8 or not s.is_cuda:
-            raise TypeError(f"polar_views_u8 takes uint8 device views, got {s.dtype} on {s.device}")
-        if s.dim() != 3 or s.shape[2] != 3 or not s.is_contiguous():
-            raise ValueError(f"polar_views_u8 takes contiguous [hin,win,3] views, got {tuple(s.shape)} with strides {s.stride()}")
-    if any(s.shape != srcs[0].shape for s in srcs):
-        raise ValueError(f"polar_views_u8: the four views differ in size: {[tuple(s.shape[:2]) for s in srcs]}")
-    for d in dsts:
-        if d.dtype != torch.float32 or d.device != srcs[0].device:
-            raise TypeError(f"polar_views_u8 writes float32 planes on {srcs[0].device}, got {d.dtype} on {d.device}")
-        if d.dim() != 3 or d.shape[2] != 3 or not d.is_contiguous():
-            raise ValueError(f"polar_views_u8 writes contiguous [ho,wo,3] planes, got {tuple(d.shape)} with strides {d.stride()}")
-    if any(d.shape != dsts[0].shape for d in dsts):
-        raise ValueError(f"polar_views_u8: the five planes differ in size: {[tuple(d.shape[:2]) for d in dsts]}")
+    _u8_images(srcs, "polar_views_u8", "views", "[hin,win,3]", "the four views")
+    _f32_planes(dsts, "polar_views_u8", srcs[0].device)
     hin, win, _ = srcs[0].shape
     ho, wo, _ = dsts[0].shape
     sp = (C.c_void_p * 4)(*[s.data_ptr() for s in srcs])
@@ -1022,7 +1022,7 @@ def polar_views_u8(srcs, dsts, mode="min", coef=None, scale=1.0 / 255.0, flip_ud
           "shm_polar_views_u8")
 
 
-AUGMENT_MODES = dict(POLAR_MODES, dir=2)                 # ... and SHM_AUG_DIR
+AUGMENT_MODES = dict(POLAR_MODES, dir=CONSTANTS["SHM_AUG_DIR"])
 
 
 def augment_views_u8(srcs, dsts, mode="dir", coef=None, mix=None, crop=None, flip_ud=False, flip_lr=False, scale=1.0 / 255.0):
@@ -1033,7 +1033,6 @@ def augment_views_u8(srcs, dsts, mode="dir", coef=None, mix=None, crop=None, fli
     bytes of every tap.  crop: (y, x, h, w) in source pixels, floats, None for the whole image.  Runs asynchronously on the current
     stream."""
     import ctypes as C
-    import numpy as np
     if mode not in AUGMENT_MODES:
         raise ValueError(f"augment_views_u8: mode {mode!r} is not 'dir', 'min' or 'stokes'")
     nsrc = 5 if mode == "dir" else 4
@@ -1041,28 +1040,11 @@ def augment_views_u8(srcs, dsts, mode="dir", coef=None, mix=None, crop=None, fli
         raise ValueError(f"augment_views_u8 takes {nsrc} sources for mode {mode!r} and 5 destination planes, got {len(srcs)} and {len(dsts)}")
     if mode == "stokes" and coef is None:
         raise ValueError("augment_views_u8: mode 'stokes' needs coef (polar.stokes_matrix of the polariser angles)")
-    for s in srcs:
-        if s.dtype != torch.uint8 or not s.is_cuda:
-            raise TypeError(f"augment_views_u8 takes uint8 device images, got {s.dtype} on {s.device}")
-        if s.dim() != 3 or s.shape[2] != 3 or not s.is_contiguous():
-            raise ValueError(f"augment_views_u8 takes contiguous [hin,win,3] images, got {tuple(s.shape)} with strides {s.stride()}")
-    if any(s.shape != srcs[0].shape for s in srcs):
-        raise ValueError(f"augment_views_u8: the sources differ in size: {[tuple(s.shape[:2]) for s in srcs]}")
-    for d in dsts:
-        if d.dtype != torch.float32 or d.device != srcs[0].device:
-            raise TypeError(f"augment_views_u8 writes float32 planes on {srcs[0].device}, got {d.dtype} on {d.device}")
-        if d.dim() != 3 or d.shape[2] != 3 or not d.is_contiguous():
-            raise ValueError(f"augment_views_u8 writes contiguous [ho,wo,3] planes, got {tuple(d.shape)} with strides {d.stride()}")
-    if any(d.shape != dsts[0].shape for d in dsts):
-        raise ValueError(f"augment_views_u8: the five planes differ in size: {[tuple(d.shape[:2]) for d in dsts]}")
+    _u8_images(srcs, "augment_views_u8", "images", "[hin,win,3]", "the sources")
+    _f32_planes(dsts, "augment_views_u8", srcs[0].device)
     hin, win, _ = srcs[0].shape
     ho, wo, _ = dsts[0].shape
-    mx = None
-    if mix is not None:
-        m = np.asarray(mix.cpu() if isinstance(mix, torch.Tensor) else mix, dtype=np.float32)
-        if m.shape != (4, 4):
-            raise ValueError(f"augment_views_u8: mix must be a 4x4 matrix, got shape {m.shape}")
-        mx = (C.c_float * 16)(*[float(v) for v in m.reshape(-1)])
+    mx = _mat4(mix, "augment_views_u8")
     cy, cx, ch, cw = (0.0, 0.0, float(hin), float(win)) if crop is None else (float(v) for v in crop)
     sp = (C.c_void_p * nsrc)(*[s.data_ptr() for s in srcs])
     dp = (C.c_void_p * 5)(*[d.data_ptr() for d in dsts])
@@ -1071,7 +1053,7 @@ def augment_views_u8(srcs, dsts, mode="dir", coef=None, mix=None, crop=None, fli
                                      dp, ho, wo, scale, _stream()), "shm_augment_views_u8")
 
 
-AUG_GROUP = 8                                            # SHM_AUG_GROUP: samples per launch of augment_batch_u8
+AUG_GROUP = CONSTANTS["SHM_AUG_GROUP"]                    # samples per launch of augment_batch_u8
 
 
 @functools.lru_cache(maxsize=None)
@@ -1094,7 +1076,6 @@ def augment_batch_u8(samples, dsts, mode="dir", coef=None, mix=None, scale=1.0 /
     planes: the destination plane of view 0..3.  dsts: five float32 [n,ho,wo,3] device tensors, n >= len(samples).  The C entry point
     checks every sample before it launches anything and names the sample it refuses.  Runs asynchronously on the current stream."""
     import ctypes as C
-    import numpy as np
     if mode not in AUGMENT_MODES:
         raise ValueError(f"augment_batch_u8: mode {mode!r} is not 'dir', 'min' or 'stokes'")
     nsrc = 5 if mode == "dir" else 4
@@ -1131,12 +1112,7 @@ def augment_batch_u8(samples, dsts, mode="dir", coef=None, mix=None, scale=1.0 /
         arr[i].flip_ud, arr[i].flip_lr, arr[i].mix = int(bool(s.flip_ud)), int(bool(s.flip_lr)), int(bool(s.mix))
         for v in range(4):
             arr[i].plane[v] = int(s.planes[v])
-    mx = None
-    if mix is not None:
-        m = np.asarray(mix.cpu() if isinstance(mix, torch.Tensor) else mix, dtype=np.float32)
-        if m.shape != (4, 4):
-            raise ValueError(f"augment_batch_u8: mix must be a 4x4 matrix, got shape {m.shape}")
-        mx = (C.c_float * 16)(*[float(v) for v in m.reshape(-1)])
+    mx = _mat4(mix, "augment_batch_u8")
     dp = (C.c_void_p * 5)(*[d.data_ptr() for d in dsts])
     cf = _polar_coef(coef, "augment_batch_u8") if mode == "stokes" else None
     check(lib().shm_augment_batch_u8(arr, len(samples), nsrc, AUGMENT_MODES[mode], cf, mx, dp, dsts[0].stride(0), ho, wo, scale, _stream()),
@@ -1169,7 +1145,7 @@ def polar_maps(views, coef, want=("s0", "dop", "aolp")):
 
 
 # ---- specular masks from the polarised views (specmask.hip) -------------------------------------------
-SPECMASK_MAX_OPEN, SPECMASK_MAX_DILATE = 4, 8            # SHM_SPECMASK_MAX_OPEN / SHM_SPECMASK_MAX_DILATE
+SPECMASK_MAX_OPEN, SPECMASK_MAX_DILATE = CONSTANTS["SHM_SPECMASK_MAX_OPEN"], CONSTANTS["SHM_SPECMASK_MAX_DILATE"]
 
 
 def _specmask_map(t, who, what, like=None):
@@ -1189,12 +1165,8 @@ def _specmask_views(srcs, q, who):
     import ctypes as C
     if len(srcs) != 4:
         raise ValueError(f"{who} takes 4 source views, got {len(srcs)}")
-    for s in srcs:
-        if s.dtype != torch.uint8 or not s.is_cuda:
-            raise TypeError(f"{who} takes uint8 device views, got {s.dtype} on {s.device}")
-        if s.dim() != 3 or s.shape[2] != 3 or not s.is_contiguous():
-            raise ValueError(f"{who} takes contiguous [h,w,3] views, got {tuple(s.shape)} with strides {s.stride()}")
-    if any(s.shape != srcs[0].shape or s.device != srcs[0].device for s in srcs):
+    _u8_images(srcs, who, "views", "[h,w,3]", "the four views")
+    if any(s.device != srcs[0].device for s in srcs):
         raise ValueError(f"{who}: the four views differ in size: {[tuple(s.shape[:2]) for s in srcs]}")
     h, w, _ = srcs[0].shape
     _specmask_map(q, who, "q")

@@ -1,5 +1,5 @@
 """The C-ABI shared library loads on a CPU-only box and exports exactly what include/shmgan_hip.h
-declares; the ctypes signature table mirrors the header.  No compute call is made here."""
+declares; the ctypes signature table and the constants are read from the header.  No compute call is made here."""
 import ctypes as C
 from pathlib import Path
 import re
@@ -30,12 +30,112 @@ def test_header_table_and_exports_agree():
     assert exports == set(hdr), (exports ^ set(hdr))
 
 
-def test_argument_counts_match_header():
-    txt = re.sub(r"/\*.*?\*/", "", _lib.HEADER.read_text(), flags=re.S)
-    for m in re.finditer(r"\b(shm_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", txt, flags=re.S):
-        name, args = m.group(1), m.group(2).strip()
-        n = 0 if args in ("", "void") else len(args.split(","))
-        assert n == len(_lib.SIGNATURES[name][1]), (name, n, len(_lib.SIGNATURES[name][1]))
+SYNTHETIC_HEADER = r"""
+/* a comment that holds a prototype: int shm_fake(int); */
+#ifndef SHM_GUARD
+#define SHM_GUARD
+#define SHM_EMIN (-40)
+#define SHM_BINS 44            /* a trailing comment
+                                  that goes on */
+#define SHM_RATIO 0.5
+#define SHM_SIZED ((size_t)SHM_BINS * 7 + 8)
+#define SHM_DECLARE(n, c)                        \
+    int shm_in_macro(int n, short c);            \
+    int shm_in_macro_too(int n)
+typedef struct shm_thing {
+    int shm_member(short x);
+    const unsigned char* src[5];
+    int plane[4];
+} shm_thing;
+int shm_three_lines(const void* const* w, const char* key,
+                    unsigned long long seed, long long step, unsigned mask,
+                    float coef[12], double d, const shm_thing* things, int n, void* stream);
+const char* shm_text(void);
+size_t shm_bytes(int n, size_t m, float);
+void shm_nothing();
+#endif
+"""
+
+
+def test_header_parser_on_a_synthetic_header():
+    """_lib.parse_header, which _lib.SIGNATURES and _lib.CONSTANTS are the result of: declarations over several lines, prototypes inside
+    comments, macros and struct bodies, every scalar type it knows, pointers and arrays, and a type it does not know."""
+    P = C.c_void_p
+    sigs, consts = _lib.parse_header(SYNTHETIC_HEADER)
+    assert list(sigs) == ["shm_three_lines", "shm_text", "shm_bytes", "shm_nothing"]
+    assert sigs["shm_three_lines"] == (C.c_int, [P, C.c_char_p, C.c_ulonglong, C.c_longlong, C.c_uint, P, C.c_double, P, C.c_int, P])
+    assert sigs["shm_text"] == (C.c_char_p, [])
+    assert sigs["shm_bytes"] == (C.c_size_t, [C.c_int, C.c_size_t, C.c_float])
+    assert sigs["shm_nothing"] == (None, [])
+    assert consts == {"SHM_EMIN": -40, "SHM_BINS": 44}           # not the guard, the float, the expression or the function-like macro
+    with pytest.raises(ValueError, match=r"shm_bad.*short x"):
+        _lib.parse_header(SYNTHETIC_HEADER + "int shm_bad(int n, short x);\n")
+    with pytest.raises(ValueError, match=r"shm_worse.*long"):
+        _lib.parse_header("long shm_worse(void);\n")
+    with pytest.raises(ValueError, match="shm_text.*twice"):
+        _lib.parse_header(SYNTHETIC_HEADER + "const char* shm_text(void);\n")
+
+
+def test_header_signatures_are_pinned_by_type():
+    """The table is read from the header, so its argument counts agree with it by construction; these entries are written out, restype and
+    every argtype, for the declarations with the types a wrong guess would corrupt silently (tests/test_native_cpu.py pins five more)."""
+    I, P, Z, F = C.c_int, C.c_void_p, C.c_size_t, C.c_float
+    pins = {
+        "shm_randn": (I, [P, Z, F, C.c_ulonglong, C.c_uint, P]),
+        "shm_loss_ring_put": (I, [P, P, P, P, P, I, I, C.c_longlong, P]),
+        "shm_sum_input_channels": (I, [P, I, I, C.c_uint, P, P]),
+        "shm_set_tuning": (I, [C.c_char_p, I]),
+        "shm_get_tuning": (I, [C.c_char_p, P]),
+        "shm_last_error": (C.c_char_p, []),
+        "shm_conv2d_wgrad_workspace": (Z, [I, I, I, I, I, I]),
+        "shm_in_bwd": (I, [P, I, P, I, P, I, P, P, P, I, P, P, P, Z, P, P, I, I, I, I, F, I, P]),
+        "shm_augment_batch_u8": (I, [P, I, I, I, P, P, P, Z, I, I, F, P]),
+    }
+    for name, sig in pins.items():
+        assert _lib.SIGNATURES[name] == sig, name
+    assert _lib.header_functions() == list(_lib.SIGNATURES)
+    assert (_lib.F32, _lib.BF16, _lib.CONSTANTS["SHM_BF16_GF32"], _lib.CONSTANTS["SHM_E_HIP"], _lib.CONSTANTS["SHM_THIST_EMIN"]) == (0, 1, 2, -4, -40)
+    assert not any("(" in k or k.endswith("_DOUBLES") for k in _lib.CONSTANTS)      # the function-like and computed macros stay Python functions
+
+
+def test_default_arena_is_made_once_per_device():
+    import torch
+    from shmgan_amd import ops
+    dev = torch.device("cpu")
+    a = ops._default_arena(dev)
+    assert ops._default_arena(dev) is a and ops._default_arena(torch.device("cpu")) is a and ops._METRIC_ARENAS[dev] is a
+
+
+def test_square_export_descriptor_words():
+    """Host side of ops.export_u8: the SHM_EXPORT_DESC words per job handed to shm_export_u8 are {S, C, ld, ho, wo, mode, k, destination
+    offset} (include/shmgan_hip.h), written out here for a 4x4x3 plane of pixel pitch 5 and a one-channel plane behind it."""
+    import torch
+    from shmgan_amd import ops
+
+    class Plane:            # what _export_jobs reads of a device tensor
+        dtype, is_cuda, device = torch.float32, True, "cuda:0"
+
+        def __init__(self, shape, strides):
+            self.shape, self.strides = shape, strides
+
+        def dim(self):
+            return len(self.shape)
+
+        def stride(self, i=None):
+            return self.strides if i is None else self.strides[i]
+
+    mul = torch.ones(3)
+    desc, offs, total = ops._export_jobs("export_u8", [Plane((4, 4, 3), (20, 5, 1)), Plane((4, 4, 1), (20, 5, 1))], None, [(6, 7), (4, 4)],
+                                         ["clip", ("scale", 2)], mul)
+    assert desc == [[4, 3, 5, 6, 7, 2, 0, 0], [4, 1, 5, 4, 4, 1, 2, 128]]          # 6 * 7 * 3 = 126 bytes, the next job from 128
+    assert offs == [0, 128] and total == 144 and all(len(d) == ops.EXPORT_DESC == 8 for d in desc)
+    # the windowed form's SHM_EXPORT_HW_DESC words: {Hs, Ws, C, ld, y0, x0, hc, wc, ho, wo, mode, k, destination offset}
+    desc, offs, total = ops._export_jobs("export_u8_hw", [Plane((4, 6, 3), (30, 5, 1))], [(1, 2, 3, 4)], [(6, 7)], ["rescale"], None)
+    assert desc == [[4, 6, 3, 5, 1, 2, 3, 4, 6, 7, 0, 0, 0]] and len(desc[0]) == ops.EXPORT_HW_DESC == 13 and (offs, total) == ([0], 128)
+    with pytest.raises(ValueError, match=r"export_u8 takes \[S,S,C\] planes"):
+        ops._export_jobs("export_u8", [Plane((4, 6, 3), (30, 5, 1))], None, [(6, 7)], ["clip"], None)
+    with pytest.raises(ValueError, match=r"export_u8_hw: window \(1, 2, 4, 4\) outside the 4 x 6 plane"):
+        ops._export_jobs("export_u8_hw", [Plane((4, 6, 3), (30, 5, 1))], [(1, 2, 4, 4)], [(6, 7)], ["clip"], None)
 
 
 def test_version_and_error_string_without_gpu():
@@ -170,6 +270,12 @@ def test_fused_in_bwd_scratch_size_and_timeout_report():
     expr = re.sub(r"\(size_t\)", "", m.group(1)).replace("\\\n", " ").replace("/", "//").replace("SHM_IN_BWD_FUSED_CB(c)", "min(c, 64)")
     for batch, hw, c in ((40, 65536, 64), (8, 16384, 128), (3, 1024, 512), (1, 4096, 8)):
         assert ops.in_bwd_fused_doubles(batch, hw, c) == eval(expr, {"batch": batch, "hw": hw, "c": c}), (batch, hw, c)
+    # ... and so are the two workspace sizes of the SpecSeg training kernels
+    bn = re.search(r"#define SHM_BN_TRAIN_WS_DOUBLES\(c\) (.*)", hdr).group(1).replace("(size_t)", "")
+    for c in (1, 16, 256):
+        assert ops.bn_train_ws_doubles(c) == eval(bn, {"c": c, **_lib.CONSTANTS}), c
+    seg = re.search(r"#define SHM_SEG_LOSS_WS_DOUBLES (.*)", hdr).group(1).replace("(size_t)", "")
+    assert ops.SEG_LOSS_WS_DOUBLES == eval(seg, dict(_lib.CONSTANTS)) == 1800
     A = Arena(torch.device("cpu"))
     assert _fused_scratch(A, torch.float32, 2, 4096, 64) is None
     t = _fused_scratch(A, torch.bfloat16, 2, 4096, 64)

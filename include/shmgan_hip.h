@@ -672,6 +672,38 @@ typedef struct shm_aug_sample {
 } shm_aug_sample;
 int shm_augment_batch_u8(const shm_aug_sample* samples, int n, int n_src, int mode, const float* coef, const float* mix,
                          float* const* dst_ptrs, size_t sample_stride, int ho, int wo, float scale, void* stream);
+/* The mask network's training pairs (SpecSeg.train_step's x and y) from decoded bytes, a whole batch in one call: sample i of
+ * `samples` (a host array of n >= 1 descriptors, read during the call; they travel to the kernels by value) is written to
+ * x + i * sample_stride and y + i * sample_stride (floats), each a float32 [ho,wo] plane.  Launches cover SHM_AUG_GROUP samples
+ * each (two per group: resample with partial sums, then finish); n may exceed the group.
+ *   descriptor   image: device uint8 [hin,win,3]; mask: device uint8 [hin,win]; hin, win and the crop (y, x, h, w) are the
+ *          sample's own; flip_ud and flip_lr are flags (nonzero = on).
+ *   sampling   the coordinate, taps and lerp of shm_augment_views_u8 (the same code: csrc/augment_px.h): mirrors on the read side,
+ *          taps held inside the image, not the crop.
+ *   y      lerp(mask bytes) * (1/255): bitwise what shm_resize_bilinear_u8 (c = 1, scale 1/255) writes at identity parameters, and
+ *          for any parameters bitwise the plane shm_augment_views_u8 (SHM_AUG_DIR, scale 1/255) writes for a 3-channel copy of the mask.
+ *   x      r, g, b = lerp(image bytes) * (1/255) per channel; (Y, U, V) = tf.image.rgb_to_yuv with the constants and expression
+ *          order of shm_rgb2yuv_std; x = Y / scale, scale = max(std, 1/256), std over all 3*ho*wo values of Y, U and V of the
+ *          resampled sample from f64 sums (the formulas of shm_rgb2yuv_std).  U and V enter the statistics and are not written;
+ *          no float RGB or YUV tensor goes to memory.
+ *   statistics   no atomics: every block writes its two f64 sums to its own slot of `ws`, and the finish adds a sample's slots in a
+ *          fixed order.  The blocks per sample depend on ho*wo alone, so a sample's bits do not depend on n, on its slot in the
+ *          batch or on its neighbours, and two calls give the same bits.  ws: device f64, shm_augment_pairs_ws_doubles(n, ho, wo)
+ *          doubles (0 for arguments the call would refuse); it needs no initial value and holds nothing of use afterwards.
+ *   scale_out   null, or device float32 [n]: receives every sample's scale.
+ * SHM_E_SHAPE for n < 1, a null array, x, y or ws, ho or wo outside [1, 32768], a sample_stride below ho*wo with n > 1, and per
+ * sample -- the message names its index -- a null image or mask, hin or win outside [1, 32768], an empty crop or one outside the
+ * image (checked in double; a NaN fails).  Every sample is checked before the first launch. */
+typedef struct shm_pair_sample {
+    const unsigned char* image;
+    const unsigned char* mask;
+    int hin, win;
+    float crop_y, crop_x, crop_h, crop_w;
+    int flip_ud, flip_lr;
+} shm_pair_sample;
+size_t shm_augment_pairs_ws_doubles(int n, int ho, int wo);
+int shm_augment_pairs_u8(const shm_pair_sample* samples, int n, float* x, float* y, size_t sample_stride, int ho, int wo,
+                         double* ws, float* scale_out, void* stream);
 /* Stokes maps of four float32 views of n elements each (any shape: the loaded RGB views or their Y channels).  view_ptrs: host
  * array of 4 device pointers; coef: host float[12], the 3x4 matrix above.  Per element (S0, S1, S2) = C (v0..v3) and
  *   s0 = S0;  dop = sqrt(S1^2 + S2^2) / S0, 0 where S0 == 0 (divide_no_nan, as calcDOP);  aolp = 0.5 atan2f(S2, S1)

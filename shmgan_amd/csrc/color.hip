@@ -1,30 +1,15 @@
 // Colour conversion, per-image standardisation, generator/discriminator input assembly,
 // discriminator-head losses and the clip+Adam update.  All HBM-bound, one pass each.
 #include "common.h"
+#include "yuv.h"                                // rgb2yuv and its constants, yuv_std_scale
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-// tf.image.rgb_to_yuv kernel (column j of yuv = sum_i rgb[i] * K[i][j])
-#define R2Y_00 0.299f
-#define R2Y_01 -0.14714119f
-#define R2Y_02 0.61497538f
-#define R2Y_10 0.587f
-#define R2Y_11 -0.28886916f
-#define R2Y_12 -0.51496512f
-#define R2Y_20 0.114f
-#define R2Y_21 0.43601035f
-#define R2Y_22 -0.10001026f
 // tf.image.yuv_to_rgb kernel
 #define Y2R_V_R 1.13988303f
 #define Y2R_U_G -0.394642334f
 #define Y2R_V_G -0.58062185f
 #define Y2R_U_B 2.03206185f
-
-__device__ __forceinline__ void rgb2yuv(float r, float g, float b, float& y, float& u, float& v) {
-    y = r * R2Y_00 + g * R2Y_10 + b * R2Y_20;
-    u = r * R2Y_01 + g * R2Y_11 + b * R2Y_21;
-    v = r * R2Y_02 + g * R2Y_12 + b * R2Y_22;
-}
 
 // ---------------------------------------------------------------- rgb -> yuv + standardise
 __global__ __launch_bounds__(256) void yuv_stats_kernel(const float* __restrict__ rgb, double* __restrict__ acc, size_t npix) {
@@ -47,11 +32,7 @@ __global__ __launch_bounds__(256) void yuv_stats_kernel(const float* __restrict_
 
 __global__ __launch_bounds__(256) void yuv_scale_kernel(const float* __restrict__ rgb, float* __restrict__ yuv, const double* __restrict__ acc, float* __restrict__ scale_out, size_t npix) {
     const int b = blockIdx.y;
-    const double cnt = (double)npix * 3.0;
-    double mean = acc[2 * b] / cnt;
-    double var = acc[2 * b + 1] / cnt - mean * mean;
-    if (var < 0.0) var = 0.0;
-    float scale = fmaxf((float)sqrt(var), 1.0f / 256.0f);   // rsqrt(65536), SHM.py:1280,1293
+    const float scale = yuv_std_scale(acc[2 * b], acc[2 * b + 1], (double)npix * 3.0);
     if (blockIdx.x == 0 && threadIdx.x == 0) scale_out[b] = scale;
     const float* base = rgb + (size_t)b * npix * 3;
     float* ob = yuv + (size_t)b * npix * 3;

@@ -415,15 +415,43 @@ def datasetLoad(trainer, subdirs=PSD_SUBDIRS, flip_ud=True):
     return trainer.length_dataset, ds
 
 
+def split_names(names, val_fraction, seed=0):
+    """(train, val): two sorted, disjoint lists whose union is `names`, a pure function of the sorted names, the fraction and the
+    seed: val is the round(N * val_fraction) names at the first places of default_rng(seed).permutation(N) over the sorted names.
+    A fraction outside (0, 1), or one that would leave either side empty, raises ValueError.  No torch call."""
+    names = sorted(names)
+    n = len(names)
+    if len(set(names)) != n:
+        raise ValueError("split_names: the names are not distinct")
+    if not isinstance(val_fraction, (int, float)) or not 0.0 < float(val_fraction) < 1.0:
+        raise ValueError(f"split: val_fraction {val_fraction!r} is not a fraction in (0, 1)")
+    n_val = int(round(n * float(val_fraction)))
+    if n_val < 1 or n_val >= n:
+        raise ValueError(f"split: val_fraction {val_fraction} of {n} samples leaves {n - n_val} for training and {n_val} for validation; "
+                         f"both sides need at least one")
+    val = set(int(i) for i in np.random.default_rng(int(seed)).permutation(n)[:n_val])
+    return [names[i] for i in range(n) if i not in val], [names[i] for i in range(n) if i in val]
+
+
 class MaskDataset:
     """Image / mask pairs for SpecSeg training (SpecSeg.fit, trainer.train_specseg): the files of `image_dir` and `mask_dir` are
     paired by name (the stem, whatever the extension; a file without its partner raises).  Images are decoded to RGB, resized with
     shm_resize_bilinear_u8 (the training loader's kernel), and go through shm_rgb2yuv_std; the standardised Y plane is kept --
     exactly what train_step feeds `SpecSeg.predict`.  Masks are decoded to one channel, resized the same way and divided by 255:
     soft values at the resized edges, not thresholded.  flip_ud flips image and mask alike.  The whole set is held on the device
-    ([N,S,S,1] each): mask sets are small next to the polarimetric data."""
+    ([N,S,S,1] each): mask sets are small next to the polarimetric data.
 
-    def __init__(self, image_dir, mask_dir, image_size, batch_size=1, flip_ud=False, device=None):
+    augment (a data.Augment) / shuffle / seed: the train-time loader of PolarDataset for pairs.  With either
+    set, `batch(index, pass_index)` makes (x, y) with ONE ops.augment_pairs_u8 call from the pairs' decoded bytes: the order of the
+    pass is pass_order(N, seed, pass_index, shuffle), the draw of the sample at sorted position p is augment_params(seed, pass_index,
+    p, hin, win, augment), and image and mask get the same crop and mirrors.  The bytes (for the polar source: view 2 and the
+    finished mask) stay on the device in a cache.SampleCache arena of at most cache_bytes (default: half of the free device memory
+    when the first pair is stored); a pair that does not fit is decoded -- and its polar mask recomputed -- every time it comes up.
+    Image and mask of a pair must then have one decoded size.  Without both options nothing changes: tensors() and iteration make
+    the calls described above, and batch() slices tensors()."""
+
+    def __init__(self, image_dir, mask_dir, image_size, batch_size=1, flip_ud=False, device=None, augment=None, shuffle=False, seed=0,
+                 cache_bytes=None):
         imgs = {Path(p).stem: p for p in list_images(image_dir)}
         masks = {Path(p).stem: p for p in list_images(mask_dir)}
         if set(imgs) != set(masks) or not imgs:
@@ -433,15 +461,20 @@ class MaskDataset:
         self.files = [(imgs[n], masks[n]) for n in self.names]
         self.S, self.B, self.flip_ud, self._dev, self._xy = int(image_size), int(batch_size), bool(flip_ud), device, None
         self._polar = None
+        self._loader_options(augment, shuffle, seed, cache_bytes, None)
 
     @classmethod
-    def from_polar(cls, data_dir, image_size, batch_size=1, subdirs=PSD_SUBDIRS, angles=None, flip_ud=False, device=None, **mask_options):
+    def from_polar(cls, data_dir, image_size, batch_size=1, subdirs=PSD_SUBDIRS, angles=None, flip_ud=False, device=None, augment=None,
+                   shuffle=False, seed=0, cache_bytes=None, **mask_options):
         """The same (x, y) tensors from a raw four-directory capture, without a mask anybody drew and without the PNG round trip:
         the image of sample i is its view subdirs[2] (the one whose Y plane train_step feeds SpecSeg.predict), the mask is
         polar.specular_mask of its four views (`angles`, or those read from the directory names; `mask_options` = threshold, floor,
         open_radius, dilate_radius), computed at source size and then resized like a decoded mask file.  Bit-equal to
         polar.write_specular_masks(data_dir, out) followed by MaskDataset(<data_dir>/<subdirs[2]>, out, ...): PNG is lossless.
-        Same refusals as write_specular_masks: four directories, equal counts, equal sizes."""
+        Same refusals as write_specular_masks: four directories, equal counts, equal sizes.
+        augment / shuffle / seed / cache_bytes as the directory form.  The mask is mirror-invariant (S2 only changes sign), but the
+        image is view 2: with augment.views == "physical" and a mirror probability above zero, the angles must be such that a
+        mirror leaves view 2 in place (polar.mirror_keeps_view: true for 0/45/90/135 and 0/60/90/150), else ValueError."""
         from . import polar
         bad = sorted(set(mask_options) - set(polar.MASK_OPTIONS))
         if bad:
@@ -453,8 +486,30 @@ class MaskDataset:
         self.files = sorted(zip(*files), key=lambda paths: Path(paths[2]).stem)          # the order of the directory form: by name
         self.names = [Path(paths[2]).stem for paths in self.files]
         self.S, self.B, self.flip_ud, self._dev, self._xy = int(image_size), int(batch_size), bool(flip_ud), device, None
-        self._polar = dict(coef=polar.stokes_matrix(angles if angles is not None else polar.angles_from_subdirs(views)), options=dict(mask_options))
+        ang = list(angles if angles is not None else polar.angles_from_subdirs(views))
+        self._polar = dict(coef=polar.stokes_matrix(ang), options=dict(mask_options))
+        self._loader_options(augment, shuffle, seed, cache_bytes, ang)
         return self
+
+    def _loader_options(self, augment, shuffle, seed, cache_bytes, angles):
+        if augment is not None and not isinstance(augment, Augment):
+            raise ValueError(f"augment must be a data.Augment or None, got {augment!r}")
+        if cache_bytes is not None and (not isinstance(cache_bytes, int) or cache_bytes < 0):
+            raise ValueError(f"cache_bytes {cache_bytes!r} is not a byte count")
+        if angles is not None and augment is not None and augment.views == "physical" and (augment.flip_lr > 0 or augment.flip_ud > 0):
+            from . import polar
+            if not polar.mirror_keeps_view(angles, 2):
+                raise ValueError(f"MaskDataset.from_polar: a mirror does not leave view 2 (the image) of the angles {list(angles)} in place, so a "
+                                 f"mirrored pair is not one this capture could have produced; use Augment(views=\"keep\") for the plain "
+                                 f"geometric flip, or no mirror")
+        self.augment, self.shuffle, self.seed, self.cache_bytes = augment, bool(shuffle), int(seed), cache_bytes
+        self.first_pass = 0
+        self._cache, self._ws = None, None
+
+    @property
+    def active(self):
+        """Whether batches are made from the decoded bytes by ops.augment_pairs_u8 (augment or shuffle set)."""
+        return self.augment is not None or self.shuffle
 
     def _pair(self, k):
         """Sample k as decoded bytes on the device: (uint8 [h,w,3] image, uint8 [h,w,1] mask)."""
@@ -484,7 +539,8 @@ class MaskDataset:
         return torch.from_numpy(np.ascontiguousarray(a.reshape(a.shape[0], a.shape[1], -1)))
 
     def tensors(self):
-        """(x, y): the standardised Y planes and the masks, float32 [N,S,S,1] on the device (loaded once)."""
+        """(x, y): the standardised Y planes and the masks, float32 [N,S,S,1] on the device (loaded once), in sorted order and
+        without augmentation, whatever the loader options."""
         if self._xy is None:
             N, S = len(self.files), self.S
             rgb = torch.empty((N, S, S, 3), device=self.dev)
@@ -500,10 +556,96 @@ class MaskDataset:
             self._xy = (yuv[..., 0:1].contiguous(), y)
         return self._xy
 
+    def cache_stats(self):
+        """cache.SampleCache.stats() of the pair arena: {"resident", "bytes", "chunks", "hits", "misses", "refused"} (zeros before the
+        first batch made from bytes, and always without augment / shuffle)."""
+        if self._cache is None:
+            return {"resident": 0, "bytes": 0, "chunks": 0, "hits": 0, "misses": 0, "refused": 0}
+        return self._cache.stats()
+
+    def _resident(self, p):
+        """The pair at sorted position p as (image address, mask address, hin, win, what keeps the bytes alive): from the arena, or
+        decoded now and -- where the budget holds it -- copied into its arena slot (two images per sample; the mask takes the
+        first hin * win bytes of the second)."""
+        if self._cache is None:
+            from .cache import SampleCache
+            budget = self.cache_bytes if self.cache_bytes is not None else lambda: torch.cuda.mem_get_info(self.dev)[0] // 2
+            self._cache = SampleCache(lambda nbytes: torch.empty(nbytes, dtype=torch.uint8, device=self.dev), budget)
+        e = self._cache.lookup(p)
+        if e is not None:
+            return e.ptrs[0], e.ptrs[1], e.hin, e.win, None
+        img, mask = self._pair(p)
+        hin, win = int(img.shape[0]), int(img.shape[1])
+        if tuple(mask.shape[:2]) != (hin, win):
+            raise ValueError(f"image and mask of a pair must have the same decoded size to be augmented together: {self.files[p][0]} is "
+                             f"{hin}x{win}, {self.files[p][-1]} {mask.shape[0]}x{mask.shape[1]}")
+        img, mask = img.contiguous(), mask.contiguous()
+        e = self._cache.store(p, 2, hin, win)
+        if e is None:                   # refused by the budget: these tensors are the sources, for this batch only
+            return img.data_ptr(), mask.data_ptr(), hin, win, (img, mask)
+        room = self._cache.chunks[e.chunk]
+        room[e.offsets[0]:e.offsets[0] + hin * win * 3].view(hin, win, 3).copy_(img)
+        room[e.offsets[1]:e.offsets[1] + hin * win].view(hin, win).copy_(mask.view(hin, win))
+        return e.ptrs[0], e.ptrs[1], hin, win, None
+
+    def positions(self, index, pass_index=0):
+        """Sorted positions of the samples of batch `index` in pass `pass_index`; the last batch of a pass holds N mod B samples
+        when that is not zero."""
+        order = pass_order(len(self.files), self.seed, pass_index, self.shuffle)
+        return [int(p) for p in order[index * self.B:(index + 1) * self.B]]
+
+    def batch(self, index, pass_index=0):
+        """(x, y) of batch `index` of pass `pass_index`, float32 [b,S,S,1] each.  With augment or shuffle: one ops.augment_pairs_u8
+        call on the current stream.  Without: slices of tensors()."""
+        if not 0 <= index < len(self):
+            raise IndexError(f"batch {index} of {len(self)}")
+        if not self.active:
+            x, y = self.tensors()
+            return x[index * self.B:(index + 1) * self.B], y[index * self.B:(index + 1) * self.B]
+        from .cache import AugSample
+        pos = self.positions(index, pass_index)
+        with torch.cuda.device(self.dev):
+            samples, keep = [], []
+            for p in pos:
+                iptr, mptr, hin, win, alive = self._resident(p)
+                keep.append(alive)
+                if self.augment is None:
+                    samples.append(AugSample((iptr, mptr), hin, win, None, self.flip_ud, False))
+                else:
+                    d = augment_params(self.seed, pass_index, p, hin, win, self.augment)
+                    samples.append(AugSample((iptr, mptr), hin, win, d.crop, self.flip_ud != d.flip_ud, d.flip_lr))
+            x = torch.empty((len(pos), self.S, self.S, 1), device=self.dev)
+            y = torch.empty_like(x)
+            need = ops.augment_pairs_ws_doubles(len(pos), self.S, self.S)
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = torch.empty(ops.augment_pairs_ws_doubles(self.B, self.S, self.S), dtype=torch.float64, device=self.dev)
+            ops.augment_pairs_u8(samples, x, y, self._ws)
+        return x, y
+
     def __iter__(self):
+        if self.active:
+            for i in range(len(self)):
+                yield self.batch(i, self.first_pass)
+            return
         x, y = self.tensors()
         for b0 in range(0, len(self.files), self.B):
             yield x[b0:b0 + self.B], y[b0:b0 + self.B]
+
+    def _subset(self, names, augment, shuffle):
+        import copy
+        want = set(names)
+        sub = copy.copy(self)
+        sub.files = [f for n, f in zip(self.names, self.files) if n in want]
+        sub.names = [n for n in self.names if n in want]
+        sub.augment, sub.shuffle = augment, bool(shuffle)
+        sub._xy = sub._cache = sub._ws = None
+        return sub
+
+    def split(self, val_fraction, seed=0):
+        """(train, val): two datasets over disjoint name sets whose union is this one's (split_names: a pure function of the sorted
+        names, the fraction and the seed).  `train` keeps this dataset's options; `val` has no augmentation and no shuffle."""
+        train, val = split_names(self.names, val_fraction, seed)
+        return self._subset(train, self.augment, self.shuffle), self._subset(val, None, False)
 
 
 def eval_file_lists(test_dir, diffuse_dir=None):

@@ -1119,6 +1119,75 @@ def augment_batch_u8(samples, dsts, mode="dir", coef=None, mix=None, scale=1.0 /
           "shm_augment_batch_u8")
 
 
+@functools.lru_cache(maxsize=None)
+def _pair_sample_struct():
+    """ctypes mirror of shm_pair_sample (include/shmgan_hip.h)."""
+    import ctypes as C
+
+    class ShmPairSample(C.Structure):
+        _fields_ = [("image", C.c_void_p), ("mask", C.c_void_p), ("hin", C.c_int), ("win", C.c_int), ("crop_y", C.c_float),
+                    ("crop_x", C.c_float), ("crop_h", C.c_float), ("crop_w", C.c_float), ("flip_ud", C.c_int), ("flip_lr", C.c_int)]
+    return ShmPairSample
+
+
+def augment_pairs_ws_doubles(n, ho, wo):
+    """float64 elements of augment_pairs_u8's workspace for n samples of ho x wo."""
+    return int(lib().shm_augment_pairs_ws_doubles(int(n), int(ho), int(wo)))
+
+
+def augment_pairs_u8(samples, x, y, ws=None, scale_out=None):
+    """A batch of decoded (image, mask) pairs -> SpecSeg.train_step's two tensors in one call (shm_augment_pairs_u8,
+    include/shmgan_hip.h, states the definitions): sample i of `samples` is written to x[i], the standardised Y plane of its cropped,
+    mirrored and resized image, and y[i], its mask resampled the same way, in [0,1].  samples: a sequence of cache.AugSample (or
+    anything with its fields) whose srcs are (image, mask): a uint8 [hin,win,3] and a uint8 [hin,win] (or [hin,win,1]) device tensor of
+    the sample's own size, or their device addresses with hin / win given; crop (y, x, h, w) or None; flip_ud, flip_lr.  x, y: float32
+    [n,ho,wo,1] device tensors of one shape, n >= len(samples).  ws: float64 device workspace of augment_pairs_ws_doubles elements
+    (allocated when None; no initial value needed).  scale_out: None or float32 [n], receives every sample's max(std, 1/256).  The C
+    entry point checks every sample before it launches anything and names the sample it refuses.  Runs asynchronously on the current
+    stream."""
+    for t in (x, y):
+        if t.dtype != torch.float32 or not t.is_cuda or t.device != x.device:
+            raise TypeError(f"augment_pairs_u8 writes float32 device tensors on one device, got {t.dtype} on {t.device}")
+        if t.dim() != 4 or t.shape[3] != 1 or not t[0].is_contiguous() or t.shape != x.shape or t.stride(0) != x.stride(0):
+            raise ValueError(f"augment_pairs_u8 writes two [n,ho,wo,1] tensors of one shape with contiguous samples, got {tuple(t.shape)} "
+                             f"with strides {t.stride()}")
+    nmax, ho, wo, _ = x.shape
+    n = len(samples)
+    if n > nmax:
+        raise ValueError(f"augment_pairs_u8: {n} samples for destination tensors of {nmax}")
+    arr = (_pair_sample_struct() * max(n, 1))()
+    for i, s in enumerate(samples):
+        if len(s.srcs) != 2:
+            raise ValueError(f"augment_pairs_u8: sample {i} has {len(s.srcs)} sources; a pair is (image, mask)")
+        hin, win = int(s.hin), int(s.win)
+        ptrs = []
+        for t, c in zip(s.srcs, (3, 1)):
+            if isinstance(t, torch.Tensor):
+                if t.dtype != torch.uint8 or t.device != x.device:
+                    raise TypeError(f"augment_pairs_u8 takes uint8 images on {x.device}, got {t.dtype} on {t.device} (sample {i})")
+                if tuple(t.shape) not in (((hin, win, c),) if c == 3 else ((hin, win, 1), (hin, win))) or not t.is_contiguous():
+                    raise ValueError(f"augment_pairs_u8: the {'image' if c == 3 else 'mask'} of sample {i} is not a contiguous "
+                                     f"[{hin},{win},{c}] tensor: {tuple(t.shape)} with strides {t.stride()}")
+                ptrs.append(t.data_ptr())
+            else:
+                ptrs.append(int(t) or None)
+        arr[i].image, arr[i].mask = ptrs
+        arr[i].hin, arr[i].win = hin, win
+        arr[i].crop_y, arr[i].crop_x, arr[i].crop_h, arr[i].crop_w = (0.0, 0.0, float(hin), float(win)) if s.crop is None else (float(c) for c in s.crop)
+        arr[i].flip_ud, arr[i].flip_lr = int(bool(s.flip_ud)), int(bool(s.flip_lr))
+    need = augment_pairs_ws_doubles(max(n, 1), ho, wo)
+    if ws is None:
+        ws = torch.empty(max(need, 1), dtype=torch.float64, device=x.device)
+    elif ws.dtype != torch.float64 or ws.device != x.device or not ws.is_contiguous() or ws.numel() < need:
+        raise ValueError(f"augment_pairs_u8: ws must be a contiguous float64 tensor of at least {need} elements on {x.device}, got "
+                         f"{ws.dtype} {tuple(ws.shape)} on {ws.device}")
+    if scale_out is not None and (scale_out.dtype != torch.float32 or scale_out.device != x.device or not scale_out.is_contiguous()
+                                  or scale_out.numel() < n):
+        raise ValueError(f"augment_pairs_u8: scale_out must be a contiguous float32 tensor of at least {n} elements on {x.device}")
+    check(lib().shm_augment_pairs_u8(arr, n, _p(x), _p(y), x.stride(0), ho, wo, _p(ws), _p(scale_out), _stream()),
+          "shm_augment_pairs_u8")
+
+
 def polar_maps(views, coef, want=("s0", "dop", "aolp")):
     """Stokes maps of four float32 device views of equal element count (shm_polar_maps): with (S0, S1, S2) = coef . views,
     "s0" = S0, "dop" = sqrt(S1^2 + S2^2) / S0 (0 where S0 == 0), "aolp" = 0.5 atan2(S2, S1).  Returns {name: tensor of views[0]'s

@@ -97,6 +97,24 @@ def mirror_views(angles_deg):
     return ("identity", None) if perm == list(range(len(perm))) else ("permute", perm)
 
 
+def mirror_keeps_view(angles_deg, view=2):
+    """Whether mirroring the scene leaves view `view` what it was: then that view of a mirrored capture is the mirrored view, and an
+    (image, mask) pair made from it may take the plain geometric flip (data.MaskDataset.from_polar).  In terms of mirror_views:
+    "identity", a "permute" with perm[view] == view, or a "mix" in which the view's own angle is mirror-invariant ((180 - theta)
+    mod 180 == theta mod 180 within the 1e-9 of stokes_matrix, i.e. 0 or 90 degrees).  The last is decided on the angle and not on
+    the matrix: with four views and three Stokes parameters row `view` of the mix is the least-squares FIT of that view -- for
+    0/60/90/150 row 2 is (-0.25, 0.25, 0.75, 0.25), not the unit row -- although the polariser at 90 degrees sees of the mirrored
+    scene exactly what it saw.  True for view 2 of both 0/45/90/135 and 0/60/90/150; false for 0/30/60/120, where 60 becomes 120."""
+    kind, how = mirror_views(angles_deg)
+    if kind == "identity":
+        return True
+    if kind == "permute":
+        return how[view] == view
+    th = float(np.mod(np.asarray(angles_deg, dtype=np.float64).reshape(-1)[view], 180.0))
+    d = abs(float(np.mod(180.0 - th, 180.0)) - th)
+    return min(d, 180.0 - d) < 1e-9
+
+
 def polar_maps(views, angles, want=("s0", "dop", "aolp")):
     """Stokes maps of four float32 device views taken at `angles` (degrees): ops.polar_maps with the least-squares matrix."""
     from . import ops

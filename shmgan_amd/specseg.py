@@ -398,15 +398,30 @@ class SpecSeg:
         self.weights_dirty = True
         return LossRecord(out)
 
-    def evaluate(self, x, y, batch_size=8):
+    @staticmethod
+    def _is_dataset(x):
+        """A data.MaskDataset (anything with its batch(index, pass_index), len() and B)."""
+        return hasattr(x, "batch") and hasattr(x, "B") and hasattr(x, "__len__") and not isinstance(x, (np.ndarray, torch.Tensor))
+
+    def evaluate(self, x, y=None, batch_size=8):
         """Keras-shaped: the loss and metrics of `predict`'s network (inference mode: moving statistics, no Dropout) on x / y
-        [N,H,W,1], the mean over the batches weighted by their size.  Returns {"loss", "dice", "focal", "iou", "f1"}."""
-        x, y = self._as_dev(x), self._as_dev(y)
-        tot, N = torch.zeros(len(ops.SEG_LOSS_NAMES), dtype=torch.float64, device=self.dev), int(x.shape[0])
-        for b0 in range(0, N, batch_size):
-            xb, yb = x[b0:b0 + batch_size].contiguous(), y[b0:b0 + batch_size].contiguous()
+        [N,H,W,1], the mean over the batches weighted by their size.  x may be a data.MaskDataset (then without y): its batches of
+        pass 0, in its own batch size.  Returns {"loss", "dice", "focal", "iou", "f1"}."""
+        if self._is_dataset(x):
+            if y is not None:
+                raise ValueError("evaluate(dataset): the masks come from the dataset; y must be None")
+            batches = (x.batch(i, 0) for i in range(len(x)))
+        else:
+            if y is None:
+                raise ValueError("evaluate(x, y) on tensors needs y")
+            x, y = self._as_dev(x), self._as_dev(y)
+            batches = ((x[b0:b0 + batch_size], y[b0:b0 + batch_size]) for b0 in range(0, int(x.shape[0]), batch_size))
+        tot, N = torch.zeros(len(ops.SEG_LOSS_NAMES), dtype=torch.float64, device=self.dev), 0
+        for xb, yb in batches:
+            xb, yb = self._as_dev(xb), self._as_dev(yb)
             z = self._eval_logits(xb)
             tot += self._loss(z, yb, None) * xb.shape[0]
+            N += int(xb.shape[0])
         r = (tot / N).cpu().numpy()
         return {k: float(r[j]) for j, k in enumerate(LOSS_KEYS)}
 
@@ -421,30 +436,56 @@ class SpecSeg:
         ops.head_logit_fwd(last, WIDTHS[0], self.vars[i], self.vars[i + 1], z, n * H * W, WIDTHS[0])
         return z
 
-    def fit(self, x, y, batch_size=8, epochs=1, lr=None, beta1=None, beta2=None, shuffle=True, seed=None, print_fn=None):
+    def fit(self, x, y=None, batch_size=8, epochs=1, lr=None, beta1=None, beta2=None, shuffle=True, seed=None, print_fn=None,
+            validation_data=None):
         """Keras-shaped training loop on x / y [N,H,W,1] (host arrays or device tensors).  The optimiser keeps its m, v and iterations
         across calls (save_npz / load_npz carry them).  shuffle draws the epoch's order from default_rng((seed, iterations)).
+        x may be a data.MaskDataset (then without y): batch size, order and augmentation are the dataset's, `shuffle` is not read, and
+        epoch e of the call is the dataset's pass first_pass + e with first_pass = iterations // len(dataset) (PolarDataset.first_pass's
+        rule), so a resumed fit goes on with the next pass's order and draws.
+        validation_data: an (xv, yv) pair or a MaskDataset; `evaluate` runs on it after every epoch (inference mode; the training
+        weights are not touched) and its five values join the history as val_loss, val_dice, val_focal, val_iou and val_f1.
         Returns {"loss": [...], "dice": ..., "focal": ..., "iou": ..., "f1": ...}: per epoch, the mean over its steps."""
-        x, y = self._as_dev(x), self._as_dev(y)
-        assert x.shape == y.shape and x.dim() == 4 and x.shape[3] == 1, (x.shape, y.shape)
+        dataset = x if self._is_dataset(x) else None
+        if dataset is not None:
+            if y is not None:
+                raise ValueError("fit(dataset): the masks come from the dataset; y must be None")
+            batch_size = int(dataset.B)
+        else:
+            if y is None:
+                raise ValueError("fit(x, y) on tensors needs y")
+            x, y = self._as_dev(x), self._as_dev(y)
+            assert x.shape == y.shape and x.dim() == 4 and x.shape[3] == 1, (x.shape, y.shape)
         self.configure_optimizer(lr, beta1, beta2)
         self.trainable = True
         if seed is not None:
             self.train_seed = int(seed)
-        N = int(x.shape[0])
         hist = {k: [] for k in LOSS_KEYS}
+        if validation_data is not None:
+            hist.update({"val_" + k: [] for k in LOSS_KEYS})
+        first_pass = self.iterations // len(dataset) if dataset is not None else 0
         for ep in range(int(epochs)):
-            order = np.random.default_rng((self.train_seed, self.iterations)).permutation(N) if shuffle else np.arange(N)
             recs = []
-            for b0 in range(0, N, batch_size):
-                idx = torch.from_numpy(order[b0:b0 + batch_size]).to(self.dev)
-                recs.append((self.train_step(x.index_select(0, idx), y.index_select(0, idx)), len(idx)))
-            tot = sum(r.out * k for r, k in recs) / N          # on the device; one read-back per epoch
+            if dataset is not None:
+                for i in range(len(dataset)):
+                    xb, yb = dataset.batch(i, first_pass + ep)
+                    recs.append((self.train_step(xb, yb), int(xb.shape[0])))
+            else:
+                N = int(x.shape[0])
+                order = np.random.default_rng((self.train_seed, self.iterations)).permutation(N) if shuffle else np.arange(N)
+                for b0 in range(0, N, batch_size):
+                    idx = torch.from_numpy(order[b0:b0 + batch_size]).to(self.dev)
+                    recs.append((self.train_step(x.index_select(0, idx), y.index_select(0, idx)), len(idx)))
+            tot = sum(r.out * k for r, k in recs) / sum(k for _, k in recs)          # on the device; one read-back per epoch
             row = tot.cpu().numpy()
             for j, k in enumerate(LOSS_KEYS):
                 hist[k].append(float(row[j]))
+            if validation_data is not None:
+                val = self.evaluate(validation_data) if self._is_dataset(validation_data) else self.evaluate(*validation_data, batch_size=batch_size)
+                for k in LOSS_KEYS:
+                    hist["val_" + k].append(val[k])
             if print_fn is not None:
-                print_fn(f"SpecSeg epoch {ep + 1}/{epochs}: " + " ".join(f"{k} {hist[k][-1]:.5f}" for k in LOSS_KEYS))
+                print_fn(f"SpecSeg epoch {ep + 1}/{epochs}: " + " ".join(f"{k} {v[-1]:.5f}" for k, v in hist.items()))
         return hist
 
     def optimizer_state(self):

@@ -57,7 +57,9 @@ _DEFAULTS = dict(image_size=128, batch_size=1, filter_size=64, g_lr=0.00002, d_l
                  cache="none", cache_gb=None,
                  specseg_image_dir="", specseg_mask_dir="", specseg_epochs=20, specseg_lr=1e-3, specseg_batch_size=8,
                  specseg_mask_source="dir", specseg_mask_threshold="otsu", specseg_mask_floor=16, specseg_mask_open=1,
-                 specseg_mask_dilate=2)
+                 specseg_mask_dilate=2,
+                 specseg_aug_flip_lr=0.0, specseg_aug_flip_ud=0.0, specseg_aug_crop_min=1.0, specseg_aug_views="physical",
+                 specseg_shuffle=False, specseg_data_seed=0, specseg_val_fraction=0.0, specseg_cache_gb=None)
 
 SPECSEG_MASK_SOURCES = ("dir", "polar")                   # where train_specseg's masks come from
 
@@ -126,6 +128,7 @@ class ShmGANwithSSpecSeg:
         self._ws = None
         self._lane = None
         self.G = self.D = self.SpecSeg = None
+        self.specseg_datasets = None             # (train, val) of the last train_specseg that ran with loader options or a split
         # zeros at graph-build time (SHM.py:206; the attention convs only ever see this constant, finding 3);
         # train_step overwrites it with SpecSeg.predict(I90_Ych) (SHM.py:492), which feeds Spec_loss only
         self.specular_candidate = None
@@ -280,37 +283,63 @@ class ShmGANwithSSpecSeg:
         touched; the next train_step / infer uses the trained network.  Returns fit()'s history.
         args.specseg_mask_source = "polar" needs neither directory: the pairs come from the raw capture under data_dir
         (data.MaskDataset.from_polar: view 2 as the image, polar.specular_mask of the four views as its mask), with
-        args.specseg_mask_threshold / specseg_mask_floor / specseg_mask_open / specseg_mask_dilate as the mask's options."""
+        args.specseg_mask_threshold / specseg_mask_floor / specseg_mask_open / specseg_mask_dilate as the mask's options.
+        The loader options of specseg_dataset (augmentation, shuffle, seed, cache) and specseg_val_fraction apply to both sources: with
+        any of them set the network is fitted on the dataset itself (SpecSeg.fit(dataset): one ops.augment_pairs_u8 call per
+        batch), and a fraction above 0 holds that part of the names out (MaskDataset.split with specseg_data_seed) and reports
+        val_loss ... val_f1 per epoch; `specseg_datasets` then holds (train, val).  With all of them at their defaults the path is
+        tensors(), then fit(x, y)."""
+        opt = self._specseg_opt(args)
+        ds = self.specseg_dataset(args)
+        if self.SpecSeg is None:
+            self.SpecSeg = self.build_specseg()
+        fit = dict(epochs=int(opt("specseg_epochs")), lr=float(opt("specseg_lr")), beta1=self.beta1, beta2=self.beta2, print_fn=print_fn)
+        val_fraction = float(opt("specseg_val_fraction"))
+        if not ds.active and val_fraction == 0.0:         # no loader option set: the whole set as two tensors, shuffled by fit
+            x, y = ds.tensors()
+            return self.SpecSeg.fit(x, y, batch_size=ds.B, shuffle=True, **fit)
+        train, val = ds.split(val_fraction, seed=int(opt("specseg_data_seed"))) if val_fraction != 0.0 else (ds, None)
+        self.specseg_datasets = (train, val)
+        if not train.active:                              # a split alone: the training side as tensors, as above
+            x, y = train.tensors()
+            return self.SpecSeg.fit(x, y, batch_size=train.B, shuffle=True, validation_data=val, **fit)
+        return self.SpecSeg.fit(train, validation_data=val, **fit)
+
+    def specseg_dataset(self, args=None):
+        """The data.MaskDataset train_specseg trains on, before any split: the source (specseg_mask_source and its directories or
+        mask options) with the loader options specseg_aug_flip_lr / specseg_aug_flip_ud / specseg_aug_crop_min / specseg_aug_views
+        (an Augment when any draw is asked for), specseg_shuffle, specseg_data_seed and specseg_cache_gb (GiB of device memory for
+        the decoded pairs; None = half of what is free).  All at their defaults: a dataset without loader options."""
+        from .data import Augment
         opt = self._specseg_opt(args)
         source = opt("specseg_mask_source")
         if source not in SPECSEG_MASK_SOURCES:
             raise ValueError(f"train_specseg: specseg_mask_source {source!r} is not one of {SPECSEG_MASK_SOURCES}")
+        draws = (float(opt("specseg_aug_flip_lr")), float(opt("specseg_aug_flip_ud")), float(opt("specseg_aug_crop_min")))
+        cache_gb = opt("specseg_cache_gb")
+        loader = dict(augment=Augment(*draws, views=opt("specseg_aug_views")) if draws != (0.0, 0.0, 1.0) else None,
+                      shuffle=bool(opt("specseg_shuffle")), seed=int(opt("specseg_data_seed")),
+                      cache_bytes=None if cache_gb is None else int(float(cache_gb) * 2 ** 30))
         if source == "polar":
-            ds = self._polar_mask_dataset(opt)
-        else:
-            from .data import MaskDataset
-            idir, mdir = opt("specseg_image_dir"), opt("specseg_mask_dir")
-            if not idir or not mdir:
-                raise ValueError("train_specseg needs specseg_image_dir and specseg_mask_dir")
-            ds = MaskDataset(idir, mdir, self.image_size, int(opt("specseg_batch_size")), device=self.device)
-        if self.SpecSeg is None:
-            self.SpecSeg = self.build_specseg()
-        x, y = ds.tensors()
-        return self.SpecSeg.fit(x, y, batch_size=ds.B, epochs=int(opt("specseg_epochs")), lr=float(opt("specseg_lr")), beta1=self.beta1,
-                                beta2=self.beta2, shuffle=True, print_fn=print_fn)
+            return self._polar_mask_dataset(opt, **loader)
+        from .data import MaskDataset
+        idir, mdir = opt("specseg_image_dir"), opt("specseg_mask_dir")
+        if not idir or not mdir:
+            raise ValueError("train_specseg needs specseg_image_dir and specseg_mask_dir")
+        return MaskDataset(idir, mdir, self.image_size, int(opt("specseg_batch_size")), device=self.device, **loader)
 
     def _specseg_opt(self, args):
         """Option lookup of train_specseg / evaluate_specseg: `args` first, then the trainer's own options."""
         return lambda k: getattr(args, k, None) if args is not None and getattr(args, k, None) is not None else getattr(self.args, k)
 
-    def _polar_mask_dataset(self, opt):
+    def _polar_mask_dataset(self, opt, **loader):
         from .data import MaskDataset
         data_dir = opt("data_dir")
         if not data_dir:
             raise ValueError("specseg_mask_source='polar' needs data_dir: the capture's four view directories")
         return MaskDataset.from_polar(data_dir, self.image_size, int(opt("specseg_batch_size")), device=self.device,
                                       threshold=opt("specseg_mask_threshold"), floor=int(opt("specseg_mask_floor")),
-                                      open_radius=int(opt("specseg_mask_open")), dilate_radius=int(opt("specseg_mask_dilate")))
+                                      open_radius=int(opt("specseg_mask_open")), dilate_radius=int(opt("specseg_mask_dilate")), **loader)
 
     def evaluate_specseg(self, args=None):
         """Score the current mask network against the polar masks of a capture (args.data_dir or the trainer's; the mask options of

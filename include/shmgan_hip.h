@@ -799,6 +799,21 @@ int shm_running_scale_mean(const float* scale, int batch, double* acc, float* mu
  * step's shm_in_bwd calls; the kernel checks it first and leaves w, m, v untouched while it is non-zero. */
 int shm_adam_clip(float* w, float* m, float* v, const float* g, size_t n, float alpha, float beta1,
                   float beta2, float eps, float gscale, const unsigned* abort_word, void* stream);
+/* Exponential moving average of a flat fp32 weight buffer (the trainer's `ema_decay`: the generator weights one evaluates with), in
+ * place, one launch.  Per element, all in fp32 and in exactly this form, so that a float64 restatement can bound it:
+ *   om = 1.0f - decay;   t = w[i] - ema[i];   ema[i] = fmaf(om, t, ema[i])          (one rounding of t, one of the fused multiply-add)
+ * decay == 0 is a plain copy, ema[i] = w[i] bit for bit: how the average is initialised.  A non-finite w[i] propagates into ema[i]
+ * and stays there (NaN for good, Inf until decay == 0 copies over it): the kernel does not look for them, the trainer's `nonfinite`
+ * option is the detector.  abort_word (may be NULL) as in shm_adam_clip: one relaxed agent-scope load at kernel entry, nothing is
+ * written while the word is non-zero -- the step whose weights were not updated does not move the average either.
+ * ema and w are device float32 [n], 4-byte aligned (slices of flat buffers) and must not overlap.  With the same misalignment to 16
+ * bytes on both, the (< 4) elements in front of the first boundary and behind the last whole vector go one per lane and the rest 16
+ * bytes per lane; otherwise 4-byte lanes (same values).  256-thread blocks, a grid-stride loop under SHM_EMA_MAX_BLOCKS blocks; no
+ * LDS, no atomics: results are bitwise the same from run to run.  12 bytes of traffic per element (8 for decay == 0).
+ * SHM_E_SHAPE, before any launch, with a message that names the argument: decay NaN, < 0 or >= 1 (for any n); with n > 0 a null ema
+ * or w, overlapping [ema, ema + n) and [w, w + n), or a pointer that is not 4-byte aligned.  n == 0 is SHM_OK without a launch. */
+#define SHM_EMA_MAX_BLOCKS 8192
+int shm_ema_update(float* ema, const float* w, size_t n, float decay, const unsigned* abort_word, void* stream);
 
 /* ---- training telemetry (the reference logs its loss scalars every 25 steps, SHM.py:1035-1053, and a histogram of every clipped
  * gradient tensor every 100, SHM.py:1085-1091) --------------------------------------------------------------------------------

@@ -139,7 +139,11 @@ class PolarDataset:
 
     def __init__(self, data_dir, image_size, batch_size=1, subdirs=PSD_SUBDIRS, flip_ud=True, device=None, epochs=1,
                  rank=None, world=None, diffuse_source="dir", angles=None, shuffle=False, augment=None, seed=0, first_pass=0,
-                 cache="none", cache_bytes=None):
+                 cache="none", cache_bytes=None, select=None):
+        # what split() builds its two parts from: this dataset's own options (rank / world as given: None = torch.distributed's)
+        self._options = dict(data_dir=data_dir, image_size=image_size, batch_size=batch_size, subdirs=tuple(subdirs), flip_ud=flip_ud,
+                             device=device, epochs=epochs, rank=rank, world=world, diffuse_source=diffuse_source, angles=angles,
+                             shuffle=shuffle, augment=augment, seed=seed, first_pass=first_pass, cache=cache, cache_bytes=cache_bytes)
         self.S, self.B, self.flip_ud, self.epochs = image_size, batch_size, flip_ud, epochs
         if cache not in CACHE_MODES:
             raise ValueError(f"cache {cache!r} is not one of {CACHE_MODES}")
@@ -172,6 +176,14 @@ class PolarDataset:
         n = len(self.files[0])
         if any(len(f) != n for f in self.files):
             raise ValueError(f"the {len(self.files)} view directories hold different numbers of images: {[len(f) for f in self.files]}")
+        self.select = None
+        if select is not None:           # a subset: everything below (n, positions, shuffle, augmentation draws, cache keys) counts within it
+            select = [int(i) for i in select]
+            if select != sorted(set(select)) or (select and not 0 <= select[0] <= select[-1] < n):
+                raise ValueError(f"select must be a sorted list of distinct indices into the {n} listed samples, got {select[:8]}...")
+            self.select = select
+            self.files = [[f[i] for i in select] for f in self.files]
+            n = len(select)
         self.n = n
         if rank is None or world is None:
             import torch.distributed as dist
@@ -393,22 +405,79 @@ class PolarDataset:
             nxt = self.prepare(*order[j + 1]) if j + 1 < len(order) else None
             yield self.take(cur)
 
+    def split(self, val_fraction, seed=0):
+        """(train, val): two PolarDatasets over disjoint samples whose union is this one's (split_indices over the first view's stems:
+        a pure function of the names, the fraction and the seed).  `train` keeps this dataset's options; `val` is a held-out set
+        (held_out_options: one pass in sorted order, no augmentation, rank 0 of a world of 1).  Both renumber their samples from 0."""
+        train, val = split_indices(self.files[0], val_fraction, seed)
+        base = self.select if self.select is not None else list(range(self.n))
+        return (PolarDataset(**self._options, select=[base[i] for i in train]),
+                PolarDataset(**held_out_options(self._options), select=[base[i] for i in val]))
+
+
+def split_indices(files, val_fraction, seed=0):
+    """(train, val): the sorted positions in `files` (one view's file list) of the two parts of split_names over the files' stems."""
+    at = {Path(f).stem: i for i, f in enumerate(files)}
+    train, val = split_names([Path(f).stem for f in files], val_fraction, seed)           # two files with one stem raise there
+    return sorted(at[s] for s in train), sorted(at[s] for s in val)
+
+
+def held_out_options(options):
+    """PolarDataset options of a held-out (validation) loader next to a training loader with `options`: the same images, size, batch
+    size, orientation, diffuse source, angles and cache; ONE pass in sorted order without augmentation; and rank 0 of a world of 1
+    EXPLICITLY, whatever torch.distributed says -- every rank scores the whole held-out set (the kernels are deterministic, so all get
+    the same numbers), which needs no collective, so a slow rank cannot hang its peers."""
+    return dict(options, shuffle=False, augment=None, epochs=1, first_pass=0, rank=0, world=1)
+
+
+def validation_loader(data_dir, image_size, batch_size, *, val_dir="", val_fraction=0.0, val_seed=0, val_batch_size=None, subdirs=PSD_SUBDIRS,
+                      flip_ud=True, device=None, diffuse_source="dir", angles=None, cache="none", cache_bytes=None):
+    """The held-out loader of `train()` from plain options (no trainer, no GPU needed to build it), or None with both sources off:
+    `val_dir` = a directory laid out like data_dir, `val_fraction` = that part of data_dir (split_indices with val_seed; datasetLoad
+    then trains on the rest).  Giving both raises ValueError.  The other options are the training loader's (held_out_options says what a
+    held-out loader does with them); val_batch_size defaults to batch_size.  Only full batches are yielded: len() = n // val_batch_size."""
+    if val_dir and val_fraction:
+        raise ValueError(f"val_dir ({val_dir!r}) and val_fraction ({val_fraction}) are two sources of one held-out set: give one of them")
+    if not val_dir and not val_fraction:
+        return None
+    B = int(batch_size if val_batch_size is None else val_batch_size)
+    if B < 1:
+        raise ValueError(f"val_batch_size {val_batch_size!r} < 1")
+    opts = held_out_options(dict(image_size=image_size, batch_size=B, subdirs=tuple(subdirs), flip_ud=flip_ud, device=device,
+                                 diffuse_source=diffuse_source, angles=angles, seed=0, cache=cache, cache_bytes=cache_bytes))
+    if val_dir:
+        return PolarDataset(val_dir, **opts)
+    _, val = split_indices(list_images(os.path.join(data_dir, tuple(subdirs)[0])), val_fraction, val_seed)
+    return PolarDataset(data_dir, **opts, select=val)
+
 
 def datasetLoad(trainer, subdirs=PSD_SUBDIRS, flip_ud=True):
     """Reference signature (datasetLoader.py:19): returns (length_dataset, loadedDataset) and sets the same
     attributes on the trainer object.  The trainer's `diffuse_source` option (default "dir") goes to PolarDataset; it is NOT
     keyed on the reference's `est_diffuse`, which main.py's parser makes True for every run.  `shuffle`, `data_seed`
     and `aug_flip_lr` / `aug_flip_ud` / `aug_crop_min` / `aug_views` become the loader's shuffle, seed and Augment; `cache` ("none" /
-    "device") and `cache_gb` (GiB of device memory the cache may take; None = half of what is free) its cache and cache_bytes."""
+    "device") and `cache_gb` (GiB of device memory the cache may take; None = half of what is free) its cache and cache_bytes.
+    `val_dir` / `val_fraction` (with `val_seed`, `val_batch_size`) set trainer.valDataset (validation_loader; None when both are off);
+    with `val_fraction` the returned loader and length are those of the training part."""
     opt = lambda k, dflt: getattr(trainer.args, k, dflt)
     draws = (float(opt("aug_flip_lr", 0.0)), float(opt("aug_flip_ud", 0.0)), float(opt("aug_crop_min", 1.0)))
     # no augmentation asked for: the loader's default path, not the augmenting kernel at identity parameters
     augment = Augment(*draws, views=opt("aug_views", "physical")) if draws != (0.0, 0.0, 1.0) else None
     cache_gb = opt("cache_gb", None)
+    cache = dict(cache=opt("cache", "none"), cache_bytes=None if cache_gb is None else int(float(cache_gb) * 2 ** 30))
+    source = dict(diffuse_source=getattr(trainer.args, "diffuse_source", "dir"))
+    # held-out validation (`val_dir` / `val_fraction`, both off by default): the loader train() validates on, and with val_fraction
+    # the training loader is the rest of data_dir
+    val_dir, val_fraction, val_seed = opt("val_dir", ""), float(opt("val_fraction", 0.0) or 0.0), int(opt("val_seed", 0))
+    trainer.valDataset = validation_loader(trainer.data_dir, trainer.image_size, trainer.batch_size, val_dir=val_dir, val_fraction=val_fraction,
+                                           val_seed=val_seed, val_batch_size=opt("val_batch_size", None), subdirs=subdirs, flip_ud=flip_ud,
+                                           device=trainer.device, **source, **cache)
+    select = None
+    if val_fraction:
+        select, _ = split_indices(list_images(os.path.join(trainer.data_dir, tuple(subdirs)[0])), val_fraction, val_seed)
     ds = PolarDataset(trainer.data_dir, trainer.image_size, trainer.batch_size, subdirs, flip_ud, trainer.device,
-                      epochs=trainer.num_epochs, diffuse_source=getattr(trainer.args, "diffuse_source", "dir"),
-                      shuffle=bool(opt("shuffle", False)), augment=augment, seed=int(opt("data_seed", 0)),
-                      cache=opt("cache", "none"), cache_bytes=None if cache_gb is None else int(float(cache_gb) * 2 ** 30))
+                      epochs=trainer.num_epochs, shuffle=bool(opt("shuffle", False)), augment=augment, seed=int(opt("data_seed", 0)),
+                      select=select, **source, **cache)
     trainer.stddev_arr, trainer.mean_arr, trainer.variance_arr = [], [], []
     # per-rank length: batches_per_epoch = length // batch_size (SHM.py:957) then counts this rank's batches
     trainer.length_dataset, trainer.loadedDataset = ds.n // ds.world, ds

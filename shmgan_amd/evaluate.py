@@ -6,7 +6,10 @@ kernels (`ops.image_metrics`; include/shmgan_hip.h states the definitions).
 
 Differences from the reference, all outside the arithmetic:
   - checkpoints are the .npz files `train()` writes (the newest `ckpt-*.npz` of `checkpoint_save_dir`, restored through the same
-    path as training); with none there the run warns and goes on with the initial weights, as the reference's restore(None) does;
+    path as training); with none there the run warns and goes on with the initial weights, as the reference's restore(None) does.
+    `eval_checkpoint` = "best" (the best.npz train() keeps with validation on) or a path scores another file, `eval_weights` = "ema" the
+    average of the generator's weights inside it (the whole loop runs under trainer.generator_weights); a missing file or a file
+    without an average raises before any image is processed;
   - the model summaries go to `log_dir` (as in `train()`), and SSIM.txt / MSE.txt / PSNR.txt to `result_dir` rather than the
     working directory; the pickled lists hold Python floats;
   - images are evaluated `eval_batch_size` at a time (default 1, as the reference); every sample is an independent B=1
@@ -127,6 +130,44 @@ def image_options(save, values, out_size):
     if out_size not in IMAGE_OUT_SIZES:
         raise ValueError(f"image_out_size {out_size!r} is not one of {IMAGE_OUT_SIZES}")
     return tags
+
+
+EVAL_WEIGHTS = ("raw", "ema")
+EVAL_CHECKPOINTS = ("latest", "best")                         # or a path
+
+
+def eval_options(eval_weights="raw", eval_checkpoint="latest"):
+    """The two options that say WHAT test mode scores, checked: eval_weights "raw" or "ema" (the average train() keeps with ema_decay),
+    eval_checkpoint "latest" (the newest ckpt-*.npz, as the reference), "best" (the best.npz train() keeps with validation on) or the
+    path of a save_npz file.  Anything else raises ValueError."""
+    if eval_weights not in EVAL_WEIGHTS:
+        raise ValueError(f"eval_weights {eval_weights!r} is not one of {EVAL_WEIGHTS}")
+    if eval_checkpoint not in EVAL_CHECKPOINTS and not (isinstance(eval_checkpoint, (str, os.PathLike)) and str(eval_checkpoint).endswith(".npz")):
+        raise ValueError(f"eval_checkpoint {eval_checkpoint!r} is not one of {EVAL_CHECKPOINTS} or the path of an .npz checkpoint")
+    return eval_weights, eval_checkpoint if eval_checkpoint in EVAL_CHECKPOINTS else os.fspath(eval_checkpoint)
+
+
+def _restore_for_test(shmgan, eval_weights, eval_checkpoint, print_fn):
+    """Load the weights test mode scores and check, before any image is processed, that they are there: the chosen file (a missing
+    best.npz or path raises FileNotFoundError naming eval_checkpoint) and, for "ema", an average inside it (ValueError naming
+    eval_weights)."""
+    shmgan.args.eval_weights = eval_weights               # _apply_npz takes the average out of the file only for a trainer that wants it
+    if eval_checkpoint == "latest":
+        path = shmgan._restore_latest()                                         # test.py:162-169
+        if path is None:
+            warnings.warn(f"no checkpoint in {shmgan.checkpoint_save_dir}: evaluating the initial weights")
+    else:
+        path = os.path.join(shmgan.checkpoint_save_dir, shmgan.BEST_CHECKPOINT) if eval_checkpoint == "best" else eval_checkpoint
+        if not os.path.exists(path):
+            raise FileNotFoundError(f"eval_checkpoint={eval_checkpoint!r}: {path} does not exist" +
+                                    (" (train() writes it with val_dir or val_fraction set)" if eval_checkpoint == "best" else ""))
+        shmgan.load_npz(path)
+    if path is not None:
+        print_fn(f"Latest checkpoint restored!! ({path})" if eval_checkpoint == "latest" else f"Checkpoint restored ({path})")
+    if eval_weights == "ema" and not (path is not None and shmgan._loaded_ema):
+        raise ValueError(f"eval_weights='ema': {path or 'no checkpoint'} holds no average of the generator's weights (G/ema; train() writes "
+                         f"it with ema_decay > 0)")
+    return path
 
 
 def _esz(dtype):
@@ -305,7 +346,8 @@ def test(shmgan, args, *, print_fn=print):
     (default 1), args.eval_size ("model", the default: every image resized to image_size x image_size; "native": every image at
     its own size -- eval_batch_size must then be 1, image_out_size is ignored, and "Time" covers the passes that were run: G1,
     plus the five cyclic passes with save_images="all"; module docstring), and the image export's args.save_images, image_values,
-    image_out_size, image_dir (module docstring); model
+    image_out_size, image_dir (module docstring), and args.eval_weights / args.eval_checkpoint (eval_options: which file and which of its
+    weight sets is scored; defaults "raw" / "latest"); model
     and folder settings come from the trainer (`image_size`, `checkpoint_save_dir`, `log_dir`, `result_dir`).  Returns a
     dict: "index" (1-based image numbers), "time" (seconds per image), "images" and "files" (the exported image paths, in
     batch order; empty without save_images); with calc_metrics also the per-image lists "MSE", "SSIM", "PSNR", "delE76",
@@ -318,6 +360,8 @@ def test(shmgan, args, *, print_fn=print):
     if eval_size not in EVAL_SIZES:
         raise ValueError(f"eval_size {eval_size!r} is not one of {EVAL_SIZES}")
     native = eval_size == "native"
+    eval_weights, eval_checkpoint = eval_options(_arg(shmgan, args, "eval_weights", "raw") or "raw",
+                                                 _arg(shmgan, args, "eval_checkpoint", "latest") or "latest")
     if native and B != 1:
         raise ValueError(f"eval_size='native' evaluates one image at a time (sizes differ per image): eval_batch_size must be 1, got {B}")
     if not test_dir:
@@ -350,11 +394,7 @@ def test(shmgan, args, *, print_fn=print):
     if shmgan.G is None:
         shmgan.build()                                                          # test.py:139-140, 156
     shmgan._write_summaries()                                                   # test.py:142-158
-    latest = shmgan._restore_latest()                                           # test.py:162-169
-    if latest is None:
-        warnings.warn(f"no checkpoint in {shmgan.checkpoint_save_dir}: evaluating the initial weights")
-    else:
-        print_fn(f"Latest checkpoint restored!! ({latest})")
+    _restore_for_test(shmgan, eval_weights, eval_checkpoint, print_fn)
 
     exporter = None
     if tags:
@@ -365,26 +405,27 @@ def test(shmgan, args, *, print_fn=print):
     cols = {k: [] for k in METRIC_KEYS}
     stream = torch.cuda.current_stream()
     try:
-        for bi, item in enumerate(dataset):
-            rgb, diffuse, window = item if native else (*item, None)
-            stream.synchronize()                         # the batch's upload and resize are not part of its time
-            t0 = time.perf_counter()
-            gen_rgb, cyc, m = shmgan.evaluate_frame(rgb, diffuse, window, cyclic) if native else shmgan.evaluate(rgb, diffuse)
-            m = None if m is None else m.cpu().tolist()  # a synchronising copy (without metrics: the synchronize below)
-            stream.synchronize()
-            n = rgb.shape[0]
-            dt = (time.perf_counter() - t0) / n
-            if exporter is not None:                     # after the timing window: the export is not part of "Time"
-                exporter.submit(shmgan, gen_rgb, cyc, dataset.sources(bi), [window] if native else None)
-            lo, _ = dataset.batch_range(bi)
-            for b in range(n):
-                index.append(lo + b + 1)
-                times.append(dt)
-                if m is not None:
-                    for k, v in zip(METRIC_KEYS, m[b]):
-                        cols[k].append(float(v))
-                    rows.append([lo + b + 1, dt, cols["MSE"][-1], cols["SSIM"][-1], cols["PSNR"][-1], cols["delE76"][-1],
-                                 cols["delE94"][-1]])
+        with shmgan.generator_weights(eval_weights):     # "raw": nothing; "ema": the whole loop runs on the average
+            for bi, item in enumerate(dataset):
+                rgb, diffuse, window = item if native else (*item, None)
+                stream.synchronize()                         # the batch's upload and resize are not part of its time
+                t0 = time.perf_counter()
+                gen_rgb, cyc, m = shmgan.evaluate_frame(rgb, diffuse, window, cyclic) if native else shmgan.evaluate(rgb, diffuse)
+                m = None if m is None else m.cpu().tolist()  # a synchronising copy (without metrics: the synchronize below)
+                stream.synchronize()
+                n = rgb.shape[0]
+                dt = (time.perf_counter() - t0) / n
+                if exporter is not None:                     # after the timing window: the export is not part of "Time"
+                    exporter.submit(shmgan, gen_rgb, cyc, dataset.sources(bi), [window] if native else None)
+                lo, _ = dataset.batch_range(bi)
+                for b in range(n):
+                    index.append(lo + b + 1)
+                    times.append(dt)
+                    if m is not None:
+                        for k, v in zip(METRIC_KEYS, m[b]):
+                            cols[k].append(float(v))
+                        rows.append([lo + b + 1, dt, cols["MSE"][-1], cols["SSIM"][-1], cols["PSNR"][-1], cols["delE76"][-1],
+                                     cols["delE94"][-1]])
         files = exporter.finish() if exporter is not None else []
     finally:
         if exporter is not None:

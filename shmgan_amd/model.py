@@ -234,6 +234,9 @@ class _Vars:
         self.iterations = 0
         self._sizes = sizes
         self.op_flat, self.op_vars = self.flat, self.vars       # MFMA operand copy (== master in float32)
+        # exponential moving average of `flat` (the trainer's ema_decay; None = off), its update count, and the buffer that keeps
+        # `flat` while the average stands in for it (trainer.generator_weights)
+        self.ema, self.ema_updates, self.spare = None, 0, None
 
     def operand_copy(self, dtype):
         """bf16 path: the products that read weights 'as stored' (dgrad, Conv2DTranspose) take a bf16

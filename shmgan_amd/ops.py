@@ -817,6 +817,27 @@ def adam_clip(w, m, v, g, n, alpha, beta1, beta2, eps, gscale, abort=None):
         lib().shm_adam_clip(_p(w), _p(m), _p(v), _p(g), n, alpha, beta1, beta2, eps, gscale, _p(abort and abort.dev), _stream()), "shm_adam_clip"))
 
 
+EMA_MAX_BLOCKS = CONSTANTS["SHM_EMA_MAX_BLOCKS"]            # the block cap of ema_update's grid-stride launch
+
+
+def ema_decay_at(ema_decay, updates, warmup=True):
+    """The `decay` of the ema_update call after `updates` earlier ones: ema_decay, or with `warmup` min(ema_decay, (1 + t) / (10 + t)),
+    tf.train.ExponentialMovingAverage's num_updates rule (0.1 at t = 0, so the first steps forget the initial weights quickly).
+    ema_decay outside [0, 1) raises ValueError."""
+    d = float(ema_decay)
+    if not 0.0 <= d < 1.0:
+        raise ValueError(f"ema_decay {ema_decay!r} is not in [0, 1) (0 = off)")
+    t = int(updates)
+    return min(d, (1.0 + t) / (10.0 + t)) if warmup else d
+
+
+def ema_update(ema, w, n, decay, abort=None):
+    """ema += (1 - decay) * (w - ema) over the first n floats of two flat float32 device buffers (shm_ema_update states the arithmetic);
+    decay = 0 copies w into ema bit for bit.  abort: the step's AbortWords; the kernel writes nothing while their device word is set."""
+    _timed_bytes("shm_ema_update", (2.0 if decay == 0 else 3.0) * 4 * n, lambda: check(          # read ema (not for a copy), w; write ema
+        lib().shm_ema_update(_p(ema), _p(w), n, decay, _p(abort and abort.dev), _stream()), "shm_ema_update"))
+
+
 # ---- SpecSeg (inference only) ----------------------------------------------------------------
 def pack_channels(src, ldsrc, c0, nc, dst, lddst, npix):
     check(lib().shm_pack_channels(_p(src), ldsrc, c0, nc, _p(dst), lddst, npix, _stream()), "shm_pack_channels")

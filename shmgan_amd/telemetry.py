@@ -131,6 +131,48 @@ def read_log(log_dir):
     return out
 
 
+VALIDATION_FILE = "validation.jsonl"
+# what `val_monitor` may name (the columns of ops.image_metrics) and the sign that makes a larger value the better one
+VAL_MONITORS = {"mse": -1.0, "psnr": 1.0, "ssim": 1.0, "de76": -1.0, "de94": -1.0}
+WEIGHT_SETS = ("raw", "ema")                               # the generator weights one can infer with (trainer.generator_weights)
+
+
+def validation_options(val_dir="", val_fraction=0.0, val_seed=0, val_step=1, val_batch_size=None, val_monitor="psnr"):
+    """The held-out validation options of train(), checked: (on, val_step, val_monitor).  `on` is whether a held-out set was asked for
+    (val_dir or val_fraction; both together raise ValueError).  An unknown val_monitor, a val_step below 1, a val_batch_size below 1 and
+    a val_fraction outside [0, 1) raise ValueError whether validation is on or not."""
+    val_fraction = float(val_fraction or 0.0)
+    if val_dir and val_fraction:
+        raise ValueError(f"val_dir ({val_dir!r}) and val_fraction ({val_fraction}) are two sources of one held-out set: give one of them")
+    if not 0.0 <= val_fraction < 1.0:
+        raise ValueError(f"val_fraction {val_fraction!r} is not a fraction in [0, 1)")
+    if val_monitor not in VAL_MONITORS:
+        raise ValueError(f"val_monitor {val_monitor!r} is not one of {tuple(VAL_MONITORS)}")
+    if isinstance(val_step, bool) or not isinstance(val_step, (int, np.integer)) or val_step < 1:
+        raise ValueError(f"val_step {val_step!r} is not a number of epochs (at least 1)")
+    if val_batch_size is not None and (isinstance(val_batch_size, bool) or not isinstance(val_batch_size, (int, np.integer)) or val_batch_size < 1):
+        raise ValueError(f"val_batch_size {val_batch_size!r} is not a batch size (at least 1, or None for the training batch size)")
+    int(val_seed)
+    return bool(val_dir or val_fraction), int(val_step), val_monitor
+
+
+def improves(monitor, value, best):
+    """Whether `value` of metric `monitor` beats `best` (None: nothing to beat).  psnr and ssim are maximised, the others minimised; a
+    NaN never improves."""
+    if value != value:
+        return False
+    return best is None or VAL_MONITORS[monitor] * (value - best) > 0.0
+
+
+def read_validation(log_dir):
+    """The rows of `log_dir`/validation.jsonl as a list of dicts, in file order (an absent file: [])."""
+    path = os.path.join(log_dir, VALIDATION_FILE)
+    if not os.path.exists(path):
+        return []
+    with open(path) as f:
+        return [json.loads(line) for line in f if line.strip()]
+
+
 def write_lines(path, records):
     """Append records to a JSON-lines file (float64 values round-trip exactly through repr)."""
     with open(path, "a") as f:

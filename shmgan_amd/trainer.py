@@ -17,6 +17,7 @@ the generator backward) and scaled by 1/world inside the clip+Adam kernel.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from types import SimpleNamespace
 
@@ -28,6 +29,7 @@ from .dist import GradReducer, exchange_active, world_size
 from .model import Arena, Discriminator, Generator, WgradLane, pad_channels
 from .specseg import SpecSeg
 from .telemetry import LOSS_NAMES, NonFiniteGradientError, Telemetry, compose_losses, telemetry_options  # noqa: F401
+from .telemetry import VALIDATION_FILE, WEIGHT_SETS, improves, validation_options, write_lines
 
 
 class _Optimizer:
@@ -59,7 +61,10 @@ _DEFAULTS = dict(image_size=128, batch_size=1, filter_size=64, g_lr=0.00002, d_l
                  specseg_mask_source="dir", specseg_mask_threshold="otsu", specseg_mask_floor=16, specseg_mask_open=1,
                  specseg_mask_dilate=2,
                  specseg_aug_flip_lr=0.0, specseg_aug_flip_ud=0.0, specseg_aug_crop_min=1.0, specseg_aug_views="physical",
-                 specseg_shuffle=False, specseg_data_seed=0, specseg_val_fraction=0.0, specseg_cache_gb=None)
+                 specseg_shuffle=False, specseg_data_seed=0, specseg_val_fraction=0.0, specseg_cache_gb=None,
+                 ema_decay=0.0, ema_warmup=True,
+                 val_dir="", val_fraction=0.0, val_seed=0, val_step=1, val_batch_size=None, val_monitor="psnr",
+                 eval_weights="raw", eval_checkpoint="latest")
 
 SPECSEG_MASK_SOURCES = ("dir", "polar")                   # where train_specseg's masks come from
 
@@ -137,6 +142,10 @@ class ShmGANwithSSpecSeg:
         self._reducer = GradReducer(self.device)
         self._prefetched = None          # _prologue() of the next batch, issued by train_step(next_batch=)
         self._loss_cache = None
+        # held-out validation inside train() (off by default): the loader datasetLoad made, whether train() validates, the best monitored
+        # value so far {"monitor", "weights", "value", "step"} and the step of the last validation; whether the last checkpoint that was
+        # loaded held an average of the generator's weights
+        self.valDataset, self._val_on, self._best, self._last_val_step, self._loaded_ema = None, False, None, None, False
         # test diagnostics: called with no arguments between the last forward pass and the first backward kernel of a step
         # (tests/test_step_gpu.py pins LeakyReLU signs there; never set on the hot path)
         self.before_backward = None
@@ -206,7 +215,7 @@ class ShmGANwithSSpecSeg:
         aborted = self.arena.abort is not None and self.arena.abort.tripped(sync=True)
         self.arena.abort = None
         self.arena.t.clear()
-        self._ws = self._prefetched = self._loss_cache = None
+        self._ws = self._prefetched = self._loss_cache = self.valDataset = None
         self._adhoc_telemetry = None
         self.G = self.D = self.SpecSeg = None
         self.specular_candidate = None
@@ -485,6 +494,64 @@ class ShmGANwithSSpecSeg:
         """Sum `flat` over ranks on the side stream; returns an event to wait on (or None)."""
         return self._reducer.allreduce_async(flat, after, tag)
 
+    # ------------------------------------------------------------------ average of the generator's weights
+    def _ema_on(self):
+        return float(self.args.ema_decay or 0.0) > 0.0
+
+    def _ensure_ema(self):
+        """With `ema_decay` > 0: G.P.ema, a flat fp32 buffer beside G.P.flat that averages every variable optimizer_G updates (the live
+        attention branch's included; the InstanceNorm betas are constants and have none).  Made when the option is first seen on, or
+        after a checkpoint without an average was loaded, as a copy of the current weights (a decay = 0 call) with the counter at 0."""
+        P = self.G.P
+        if P.ema is None:
+            ops.ema_decay_at(self.args.ema_decay, 0)           # the option, checked before anything is allocated
+            P.ema = torch.empty_like(P.flat)
+            ops.ema_update(P.ema, P.flat, P.n, 0.0)
+            P.ema_updates = 0
+        return P.ema
+
+    @contextlib.contextmanager
+    def generator_weights(self, which="raw"):
+        """with shmgan.generator_weights("ema"): infer / evaluate / validate inside run on the average of the generator's weights.  The
+        raw weights move to a spare buffer, the average is copied into G.P.flat and the weights are marked dirty, so that the next
+        prepare_weights redoes the tap transposes and the bf16 operand copy; on exit -- after an exception too -- the raw weights come
+        back bit for bit and are marked dirty again.  Not for use around train_step.  "raw" changes nothing; "ema" without an average
+        (ema_decay off and none loaded) raises ValueError."""
+        if which not in WEIGHT_SETS:
+            raise ValueError(f"generator_weights: {which!r} is not one of {WEIGHT_SETS}")
+        if which == "raw":
+            yield self
+            return
+        if self.G is None:
+            self.build()
+        P = self.G.P
+        if P.ema is None and self._ema_on():
+            self._ensure_ema()
+        if P.ema is None:
+            raise ValueError("generator_weights('ema'): this trainer holds no average of the generator's weights (ema_decay is 0 and no "
+                             "checkpoint with one has been loaded)")
+        if P.spare is None:
+            P.spare = torch.empty_like(P.flat)
+        self._get_lane().join()                      # nothing queued on the second stream may still read the raw weights
+        P.spare.copy_(P.flat)
+        P.flat.copy_(P.ema)
+        self.G.weights_dirty = True
+        try:
+            yield self
+        finally:
+            P.flat.copy_(P.spare)
+            self.G.weights_dirty = True
+
+    def ema_weights(self):
+        """The average of the generator's weights as host arrays in Keras variable order, like G.get_weights().  Synchronises."""
+        if self.G is None or self.G.P.ema is None:
+            raise ValueError("ema_weights: this trainer holds no average of the generator's weights (ema_decay is 0 and no checkpoint "
+                             "with one has been loaded)")
+        P = self.G.P
+        flat = P.ema.cpu().numpy()
+        w = [flat[o:o + int(np.prod(s))].reshape(s).copy() for o, s in zip(P.offsets, P.shapes)]
+        return [w[i] for i in self.G._korder()]
+
     # ------------------------------------------------------------------ the step
     def train_step(self, orig0, orig45, orig90, orig135, origED, *, draws=None, style_factor=None, apply=True, next_batch=None):
         """One SHM.py:467-875 step: D update + G update from a 5-view batch [B,S,S,3] in [0,1].
@@ -499,6 +566,8 @@ class ShmGANwithSSpecSeg:
             self.telemetry.check()       # non-finite gradients in a histogram that has reached the host (nonfinite="raise" / "warn")
         G, D, A = self.G, self.D, self.arena
         S, F = self.image_size, self.filter_size
+        if self._ema_on():
+            self._ensure_ema()           # first step with the option on (or behind a checkpoint without an average): the average starts as these weights
         orig = [self._dev(t) for t in (orig0, orig45, orig90, orig135, origED)]
         B = orig[0].shape[0]
         npix = S * S
@@ -683,6 +752,11 @@ class ShmGANwithSSpecSeg:
                     tel.record_gradients("G", 1.0 / world)
                 self.optimizer_G.apply(G.P, 1.0 / world, abort=self.arena.abort)
                 G.weights_dirty = True
+                if self._ema_on():       # the average follows the update on the same stream, on every rank (the weights are the same on all), under
+                    # the same abort word: a step that did not move the weights does not move the average.  The decay comes from a host counter
+                    ops.ema_update(G.P.ema, G.P.flat, G.P.n, ops.ema_decay_at(self.args.ema_decay, G.P.ema_updates, bool(self.args.ema_warmup)),
+                                   abort=self.arena.abort)
+                    G.P.ema_updates += 1
         elif exchange_active():
             for ev in (ev_d, ev_g):
                 self._reducer.wait_on(ev)
@@ -722,7 +796,11 @@ class ShmGANwithSSpecSeg:
         `aug_views` (data.datasetLoad; all off by default) give an epoch-wise shuffle and a random crop / mirror per sample;
         aug_flip_ud=0.5 is the as-intended reading of the per-step draw below.  `cache="device"` (with `cache_gb`, GiB; default half of the free
         device memory) keeps the decoded samples on the device after their first decode, the reference's `.cache()`;
-        `self.loadedDataset.cache_stats()` says what it holds.  `max_steps` (tests) stops early.  Returns the number of train_step calls made."""
+        `self.loadedDataset.cache_stats()` says what it holds.  `ema_decay` (with `ema_warmup`) keeps an average of the generator's weights
+        (_ensure_ema, generator_weights); `val_dir` or `val_fraction` (with `val_seed`, `val_step`, `val_batch_size`, `val_monitor`) hold captures
+        out: every `val_step` epochs, in front of the checkpoint, and once at the end they are scored (validate), rank 0 appends the means to
+        `log_dir`/validation.jsonl and keeps the best weights as `checkpoint_save_dir`/best.npz (_validate_and_log).  Both are off by default and
+        leave the training trajectory bitwise alone when on.  `max_steps` (tests) stops early.  Returns the number of train_step calls made."""
         import os
         import time
         from .data import datasetLoad
@@ -732,6 +810,10 @@ class ShmGANwithSSpecSeg:
                 if k in self.__dict__:
                     setattr(self, k, v)
         start = time.perf_counter()
+        a = self.args
+        self._val_on, self._val_step, self._val_monitor = validation_options(a.val_dir, a.val_fraction, a.val_seed, a.val_step, a.val_batch_size,
+                                                                             a.val_monitor)
+        ops.ema_decay_at(a.ema_decay, 0)                                       # checked before the data is listed
         self.length_dataset, dataset = datasetLoad(self)                       # SHM.py:904
         if self.G is None:
             self.build()                                                       # SHM.py:911-912, 930-931
@@ -747,6 +829,8 @@ class ShmGANwithSSpecSeg:
         latest = self._restore_latest()                                        # SHM.py:949-951 (delete_old_checkpoints is False)
         if latest is not None:
             print_fn(f"Latest checkpoint restored!! ({latest})")
+        if self._val_on:
+            self._resume_best()
         # the loader's shuffle and augmentation draws are keyed by the pass number: a resumed run goes on from the pass its restored
         # step counter (the one telemetry uses) lies in instead of replaying pass 0's order and draws
         dataset.first_pass = self.D.P.iterations // max(len(dataset), 1)
@@ -795,10 +879,14 @@ class ShmGANwithSSpecSeg:
             if (self.epoch + 1) % self.log_step == 0:                          # SHM.py:1099-1106
                 torch.cuda.current_stream().synchronize()
                 print_fn("Time taken for epoch {} is {} min\n".format(self.epoch + 1, (time.perf_counter() - start) / 60))
+            if self._val_on and (self.epoch + 1) % self._val_step == 0:        # held-out validation, in front of the checkpoint it may beat
+                self._validate_and_log(print_fn)
             if (self.epoch + 1) % self.checkpoint_save_step == 0:              # SHM.py:1125-1128
                 print_fn("Saving checkpoint for epoch {} at {}".format(self.epoch + 1, self._save_checkpoint()))
             if done:
                 break
+        if self._val_on:                                                       # once at the end (unless these weights have just been scored)
+            self._validate_and_log(print_fn)
         print_fn("Saving checkpoint for epoch {} at {}".format(self.epoch + 1, self._save_checkpoint()))   # SHM.py:1133
         return self.batch_step
 
@@ -895,16 +983,114 @@ class ShmGANwithSSpecSeg:
             c = self._checkpoints()
             n = int(os.path.basename(c[-1])[5:-4]) + 1 if c else 1
             path = os.path.join(self.checkpoint_save_dir, f"ckpt-{n}.npz")
-            tmp = path + ".tmp"
-            with open(tmp, "wb") as f:                 # a file object: np.savez would append ".npz" to a name
-                self.save_npz(f)
-                f.flush()
-                os.fsync(f.fileno())
-            os.replace(tmp, path)
+            self._write_npz(path)
             for old in (c + [path])[:-max_to_keep]:
                 os.remove(old)
         self._barrier()
         return path
+
+    def _write_npz(self, path):
+        """save_npz under a temporary name, flushed to disk, then an atomic rename: no half-written file ever has the final name."""
+        import os
+        tmp = path + ".tmp"
+        with open(tmp, "wb") as f:                 # a file object: np.savez would append ".npz" to a name
+            self.save_npz(f)
+            f.flush()
+            os.fsync(f.fileno())
+        os.replace(tmp, path)
+
+    # ------------------------------------------------------------------ held-out validation
+    BEST_CHECKPOINT = "best.npz"          # in checkpoint_save_dir; not a ckpt-*.npz, so neither pruned nor picked by _restore_latest
+
+    def validate(self, dataset=None, weights=("raw",)):
+        """Score the generator on held-out captures with test mode's protocol (evaluate.test): view 0 as the photo, the other views
+        zero, target label ED (infer without the cyclic passes), gen_rgb against the sample's ED image with ops.image_metrics.
+        dataset: a data.PolarDataset (default: the held-out loader of the trainer's val_dir / val_fraction options); only its full
+        batches are scored.  weights: the weight sets to score, each under generator_weights().  Per set every batch's rows go into one
+        [n,5] float64 device buffer; ONE device-to-host copy ends the pass and the means are taken in float64 on the host.
+        Returns {"n": images scored, "held_out": images listed, <set>: {"mse", "psnr", "ssim", "de76", "de94" (means), "rows" ([n,5])}}.
+        Reads no draw stream and writes nothing a training step relies on (its buffers are infer's and its own), so a run that
+        validates takes bitwise the steps of one that does not."""
+        if self.G is None:
+            self.build()
+        if dataset is None:
+            dataset = self.valDataset
+            if dataset is None:
+                from .data import validation_loader
+                a = self.args
+                cache_gb = a.cache_gb
+                dataset = self.valDataset = validation_loader(
+                    self.data_dir, self.image_size, self.batch_size, val_dir=a.val_dir, val_fraction=float(a.val_fraction or 0.0),
+                    val_seed=int(a.val_seed), val_batch_size=a.val_batch_size, device=self.device, diffuse_source=a.diffuse_source,
+                    cache=a.cache, cache_bytes=None if cache_gb is None else int(float(cache_gb) * 2 ** 30))
+            if dataset is None:
+                raise ValueError("validate: no held-out set (give a dataset, or set val_dir or val_fraction)")
+        for w in weights:
+            if w not in WEIGHT_SETS:
+                raise ValueError(f"validate: {w!r} is not one of {WEIGHT_SETS}")
+        B, nb = int(dataset.B), len(dataset)
+        n = nb * B
+        out = {"n": n, "held_out": int(dataset.n)}
+        rows = self.arena.get("val/rows", (max(n, 1), 5), torch.float64)
+        for w in weights:
+            with self.generator_weights(w):
+                for i, batch in enumerate(dataset):
+                    gen_rgb, _ = self.infer(batch[0], cyclic=False)
+                    ops.image_metrics(gen_rgb, batch[4], out=rows[i * B:(i + 1) * B], arena=self.arena)
+                host = rows[:n].cpu().numpy().astype(np.float64, copy=True)           # the pass's one device-to-host copy (it synchronises)
+            means = host.mean(axis=0) if n else np.full(5, np.nan)
+            out[w] = dict({k: float(v) for k, v in zip(ops.METRIC_NAMES, means)}, rows=host)
+        return out
+
+    def _validate_and_log(self, print_fn=print):
+        """One validation of train(): every rank scores the whole held-out set (raw weights, and the average with ema_decay on), rank 0
+        appends one line per weight set to <log_dir>/validation.jsonl, and when the monitored value -- val_monitor of the average
+        with ema_decay on, of the raw weights otherwise -- beats the best so far, rank 0 writes <checkpoint_save_dir>/best.npz.  The
+        step counts optimizer updates; weights that have been scored already (the end of a run right behind an epoch's validation) are
+        not scored again."""
+        import os
+        step = int(self.D.P.iterations)
+        if self._last_val_step == step:
+            return None
+        self._last_val_step = step
+        self._check_abort(sync=True)     # never score (or keep as the best) weights behind a step whose kernels gave up
+        sets = ("raw", "ema") if self._ema_on() else ("raw",)
+        res = self.validate(weights=sets)
+        monitored, mon = sets[-1], self._val_monitor
+        best_now = False
+        if res["n"]:
+            value = res[monitored][mon]
+            if improves(mon, value, None if self._best is None else self._best["value"]):
+                best_now = True
+                self._best = {"monitor": mon, "weights": monitored, "value": value, "step": step}
+        if self._rank() == 0:
+            os.makedirs(self.log_dir, exist_ok=True)
+            write_lines(os.path.join(self.log_dir, VALIDATION_FILE),
+                        [dict({"step": step, "epoch": int(self.epoch), "weights": w, "n": res["n"], "held_out": res["held_out"]},
+                              **{k: res[w][k] for k in ops.METRIC_NAMES}, best=bool(best_now and w == monitored)) for w in sets])
+            if best_now:
+                self._write_npz(os.path.join(self.checkpoint_save_dir, self.BEST_CHECKPOINT))
+            print_fn(f"Validation at step {step} ({res['n']} of {res['held_out']} held-out images): " +
+                     "; ".join(f"{w} {mon} {res[w][mon]:.6g}" for w in sets) + (" -- best so far, saved" if best_now else ""))
+        return res
+
+    def _resume_best(self):
+        """The best monitored value a resumed run has to beat: that of the restored checkpoint's trainer state and that of best.npz
+        itself (written before the checkpoint of its epoch, so it may be the newer of the two), whichever is better; one recorded
+        for another monitor or weight set does not count."""
+        import json
+        import os
+        want = (self._val_monitor, "ema" if self._ema_on() else "raw")
+        cands = [self._best]
+        path = os.path.join(self.checkpoint_save_dir, self.BEST_CHECKPOINT)
+        if os.path.exists(path):
+            with np.load(path) as z:
+                if "trainer/state" in z.files:
+                    cands.append(json.loads(str(z["trainer/state"])).get("best"))
+        self._best = None
+        for b in cands:
+            if b and (b.get("monitor"), b.get("weights")) == want and improves(want[0], b["value"], None if self._best is None else self._best["value"]):
+                self._best = dict(b)
 
     # ------------------------------------------------------------------ inference (test.py:218-297)
     # arena names that hold one frame's worth of inference buffers (dropped when the frame shape changes, _frame_changed)
@@ -1047,9 +1233,17 @@ class ShmGANwithSSpecSeg:
         # trainer state a resumed run continues from: the step-level draw streams (flags / TARGET_LABELS generator, the
         # Philox counter of the noise and dropout kernels), the epoch, and which graph the variables belong to
         import json
-        d["trainer/state"] = np.array(json.dumps({
-            "attention": self.attention, "epoch": int(self.epoch), "draw_count": int(self._draw_count),
-            "rng": self._rng.bit_generator.state, "batch_step": int(getattr(self, "batch_step", 0))}))
+        state = {"attention": self.attention, "epoch": int(self.epoch), "draw_count": int(self._draw_count),
+                 "rng": self._rng.bit_generator.state, "batch_step": int(getattr(self, "batch_step", 0))}
+        # only with their options on (a file written with them off has exactly the keys it always had): the average of the generator's
+        # weights as its flat buffer, like G/adam_m, with its update count; and the best held-out value so far, so that a resumed run
+        # does not replace a better best.npz with a worse one
+        if self._ema_on():
+            d["G/ema"] = self._ensure_ema().cpu().numpy()
+            d["G/ema_updates"] = np.int64(self.G.P.ema_updates)
+        if self._val_on:
+            state["best"] = self._best
+        d["trainer/state"] = np.array(json.dumps(state))
         np.savez(path, **d)
 
     def _read_npz(self, path):
@@ -1080,6 +1274,12 @@ class ShmGANwithSSpecSeg:
                         raise KeyError(f"checkpoint {path}: {name}/{k} has {a.size} elements, this model's flat buffer {M.P.m.numel()}")
                     arrays[f"{name}/{k}"] = a
                 arrays[f"{name}/iterations"] = z[f"{name}/iterations"]
+            if "G/ema" in z.files:                        # written with ema_decay on
+                a = z["G/ema"]
+                if a.size != self.G.P.n:
+                    raise KeyError(f"checkpoint {path}: G/ema has {a.size} elements, this model's flat buffer {self.G.P.n}")
+                arrays["G/ema"] = a
+                arrays["G/ema_updates"] = z["G/ema_updates"]
             if "SpecSeg/var00" in z.files:
                 if self.SpecSeg is None:
                     self.SpecSeg = self.build_specseg()
@@ -1102,6 +1302,18 @@ class ShmGANwithSSpecSeg:
             M.P.m.copy_(torch.from_numpy(z[f"{name}/adam_m"]))
             M.P.v.copy_(torch.from_numpy(z[f"{name}/adam_v"]))
             M.P.iterations = int(z[f"{name}/iterations"])
+        # the average: taken from the file by a trainer that keeps one (ema_decay on) or is to evaluate with one (eval_weights "ema");
+        # a file without one leaves a trainer with ema_decay on with average = the loaded weights and the counter at 0; a trainer with
+        # neither option ignores the keys
+        P = self.G.P
+        self._loaded_ema = "G/ema" in z
+        P.ema = None
+        if self._loaded_ema and (self._ema_on() or self.args.eval_weights == "ema"):
+            P.ema = torch.empty_like(P.flat)
+            P.ema.copy_(torch.from_numpy(np.ascontiguousarray(z["G/ema"], dtype=np.float32).reshape(-1)))
+            P.ema_updates = int(z["G/ema_updates"])
+        elif self._ema_on():
+            self._ensure_ema()
         if "SpecSeg/var00" in z:
             self.SpecSeg.set_weights([z[f"SpecSeg/var{i:02d}"] for i in range(len(self.SpecSeg.vars))])
         if "SpecSeg/adam_m" in z:
@@ -1110,6 +1322,7 @@ class ShmGANwithSSpecSeg:
             self.epoch = int(state["epoch"])
             self._draw_count = int(state["draw_count"])
             self._rng.bit_generator.state = state["rng"]
+            self._best = state.get("best")           # present when the run that wrote the file validated (train() checks it: _resume_best)
 
     def load_npz(self, path):
         """Inverse of save_npz.  The file is read and validated as a whole first (`_read_npz`), so a damaged or mismatching

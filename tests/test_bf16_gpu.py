@@ -320,7 +320,7 @@ def _mk(S, F_, B, grad_dtype=None):
     return m, (g, d, gb, db)
 
 
-@pytest.mark.parametrize("S,F_,B,step,gdt", [(64, 32, 1, 0, None), (64, 32, 2, 1, None), (64, 32, 1, 2, "float32")])
+@pytest.mark.parametrize("S,F_,B,step,gdt", [(64, 32, 1, 0, None), (64, 32, 2, 1, None), (64, 32, 1, 2, "float32"), (64, 32, 2, 1, "float32")])
 def test_train_step_bf16_vs_oracle(S, F_, B, step, gdt):
     """Whole step in bf16 against the float64 oracle at the contract's tolerances: named losses within 2e-2
     (relative, or absolute on O(1) values), gen_Y rel-L2 <= 2e-2, per-tensor weight-gradient cosine >= 0.99.
@@ -400,19 +400,22 @@ def _check_forward_fixture(m, gold, B, sub, loss_tol, y_tol, ssim_tol):
     assert np.abs(np.array(got["ssim"]) - gold["ssim"].mean(axis=1)).max() <= ssim_tol
 
 
-@pytest.mark.parametrize("dt", ["bfloat16", "float32"])
+@pytest.mark.parametrize("dt", ["bfloat16", "float32", "bfloat16-gf32"])
 def test_config3_s512_b4_against_the_oracle_fixture(dt):
     """BASELINE configs[3] -- S=512, F=64, **B=4**, bf16 -- against the committed float64-oracle fixture
     tests/golden/step_S512_F64_B4_fwd.npz (oracle/make_golden.py --s512: forward pass of the whole step, sample by
     sample): every named loss, per-sample gen_Y and the five SSIM values.  bf16 within SURVEY 8(c)'s 2e-2 contract; the
     fp32 run of the same configuration within the fp32 contract (losses 1e-4, gen_Y 1e-4).  The backward of the same step
-    runs too (apply=False) and must leave finite gradients."""
+    runs too (apply=False) and must leave finite gradients.
+    "bfloat16-gf32": the bf16 step with grad_dtype="float32" (SHM_BF16_GF32), held to the bf16 case's tolerances: at this size the real dispatch
+    of that mode runs -- the 128-wide halo blocks, the large DMA tiles and the four-phase kernel with its fused sums."""
     from shmgan_amd import ShmGANwithSSpecSeg
     from oracle import specseg_torch as sp
+    dt, gdt = ("bfloat16", "float32") if dt == "bfloat16-gf32" else (dt, None)
     gold = _fixture("step_S512_F64_B4_fwd.npz")
     S, F, B, step, sub = [int(v) for v in gold["meta"]]
     assert (S, F, B) == (512, 64, 4)
-    m = ShmGANwithSSpecSeg(image_size=S, filter_size=F, batch_size=B, compute_dtype=dt).build()
+    m = ShmGANwithSSpecSeg(image_size=S, filter_size=F, batch_size=B, compute_dtype=dt, grad_dtype=gdt).build()
     m.SpecSeg.set_weights(sp.init_specseg(seed=44 + step))
     assert m.D.count_params() == 6359744 - 81920 + 5 * 16 * 16 * 1024          # Dense grows with S: 1 310 720 weights at 512
     m.train_step(*st.make_inputs(B, S), draws=st.make_draws(step, B, S, F), style_factor=st.style_factor_intended(S), apply=False)

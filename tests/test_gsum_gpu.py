@@ -14,7 +14,8 @@ import numpy as np
 import pytest
 import torch
 
-from util import host, rel_l2
+from oracle import step_torch as st
+from util import SENTINEL, band_untouched, guard_elems, host, rel_l2
 
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
@@ -31,9 +32,28 @@ def _reset_tuning():
     _ops().set_tuning("reset", 0)
 
 
+DTS = ["f32", "bf16", "gf32"]          # "gf32" = SHM_BF16_GF32: bf16 operands and aux, the gradient the launch writes (and sums) in fp32
+
+
 def _t(a, dt):
     t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
-    return t.to(BF) if dt == "bf16" else t
+    return t.to(BF) if dt in ("bf16", "gf32") else t
+
+
+def _out(shape, adt):
+    """An output of `shape` filled with the sentinel, in front of a guard band of one patch row of elements (test_rect_gpu._guarded): an overrun or
+    an unwritten part is a failed assert.  Returns (tensor, band)."""
+    n = int(np.prod(shape))
+    flat = torch.full((n + guard_elems(shape),), SENTINEL, device="cuda", dtype=adt)
+    return flat[:n].view(shape), flat[n:]
+
+
+_last = {}          # "fused": per output part of the latest "gf32" _dgrad_case, whether an epilogue took its sums
+
+
+def _fused_epilogue_ran(red, n, c):
+    """The stand-alone reduce pass adds into slot 0 only; the epilogues spread their atomics over the slot copies."""
+    return bool((red.view(_ops().GSUM_SLOTS, n, c, 2)[1:] != 0).any())
 
 
 def _sums(g, aux):
@@ -58,7 +78,7 @@ def _check_sums(red, g, aux, dt):
 
 def _dgrad_case(variant, dt, n, h, cin, cout, n1, stride=1, k=3, which=(True, True)):
     """conv2d_dgrad under a forced variant: cout -> cin input channels (the GEMM's N), optionally split (n1) into two output
-    tensors with their own aux / sums."""
+    tensors with their own aux / sums.  dt = "gf32": bf16 dy / w / aux, fp32 dx (SHM_BF16_GF32)."""
     ops = _ops()
     rng = np.random.default_rng(7)
     ho = h // stride
@@ -71,8 +91,8 @@ def _dgrad_case(variant, dt, n, h, cin, cout, n1, stride=1, k=3, which=(True, Tr
     aux1 = _t(rng.standard_normal((n, h, h, c1)), dt) if split else None
     outs = []
     for use_gsum in (False, True):
-        dx = torch.full((n, h, h, c0), 7.0, device="cuda", dtype=adt)
-        dx2 = torch.full((n, h, h, c1), 7.0, device="cuda", dtype=adt) if split else None
+        dx, b0 = _out((n, h, h, c0), adt)
+        dx2, b1 = _out((n, h, h, c1), adt) if split else (None, None)
         red0 = torch.zeros(ops.GSUM_SLOTS * n * c0 * 2, dtype=torch.float64, device="cuda")
         red1 = torch.zeros(ops.GSUM_SLOTS * n * c1 * 2, dtype=torch.float64, device="cuda") if split else None
         ops.set_tuning("tapgemm.variant", variant)
@@ -87,21 +107,36 @@ def _dgrad_case(variant, dt, n, h, cin, cout, n1, stride=1, k=3, which=(True, Tr
             g0 = (aux0, c0, red0)
         ops.conv2d_dgrad(dy, cout, w, dx, dx2, n1 if split else 0, c0, c1, n, h, h, cin, cout, k, stride, gsum=g0, gsum2=g1)
         torch.cuda.synchronize()
+        assert band_untouched(b0) and (b1 is None or band_untouched(b1)), ops.last_kernel()
         outs.append((dx, dx2, red0, red1, g0, g1, ops.last_kernel()))
     (dxa, dx2a, *_), (dxb, dx2b, red0, red1, g0, g1, kern) = outs
     assert torch.equal(dxa, dxb) and (not split or torch.equal(dx2a, dx2b)), kern           # the sums do not touch the gradient
+    assert not bool((dxb == SENTINEL).all(-1).any()) and (not split or not bool((dx2b == SENTINEL).all(-1).any())), kern          # no pixel left unwritten
     if g0 is not None:
         _check_sums(red0, dxb, aux0, dt)
     if g1 is not None:
         _check_sums(red1, dx2b, aux1, dt)
+    if dt == "gf32":          # fp32 dx from bf16 operands: float64 on the operands as the device holds them, at test_bf16_gpu.TOL32
+        xt = torch.zeros(n, cin, h, h, dtype=torch.float64, requires_grad=True)
+        ref, = torch.autograd.grad(st.conv2d_same(xt, w.double().cpu(), stride), xt, dy.double().cpu().permute(0, 3, 1, 2))
+        got = host(dxb) if not split else np.concatenate([host(dxb), host(dx2b)], -1)
+        err = rel_l2(got, ref.permute(0, 2, 3, 1).numpy())
+        print(f"{kern}: rel-L2 {err:.2e}")
+        assert err < 1e-4, (kern, err)
+        _last["fused"] = {p: _fused_epilogue_ran(r, n, c) for p, r, c in ((0, red0, c0), (1, red1, c1)) if (g0, g1)[p] is not None}
     return kern
 
 
 HALO = ["halo128", "halo64", "halo128_st", "halo64_st"]
 DMA = ["dma128x128", "dma64x128", "dma128x64", "dma64x64", "dma256x64", "dma256x128", "dma128x128_bk32", "dma128x128_nst4"]
+# shm_last_kernel() of the SHM_BF16_GF32 launches (test_variants_gpu.SYMBOL's template arguments; {gs}: the halo blocks' gsum instantiation)
+GF32_SYMBOL = {v: "tapgemm_halo_kernel<__bf16, float, %d, 16, %s, 2{gs}>" % (128 if "128" in v else 64, "true" if v.endswith("_st") else "false") for v in HALO}
+GF32_SYMBOL.update({v: "tapgemm_dma_kernel<__bf16, float, %s>" % a for v, a in (
+    ("dma128x128", "128, 128, 2, 2, 3, 16"), ("dma64x128", "64, 128, 2, 2, 3, 16"), ("dma128x64", "128, 64, 2, 2, 3, 16"), ("dma64x64", "64, 64, 2, 2, 3, 16"),
+    ("dma256x64", "256, 64, 4, 1, 3, 16"), ("dma256x128", "256, 128, 4, 2, 3, 16"), ("dma128x128_bk32", "128, 128, 2, 2, 2, 32"), ("dma128x128_nst4", "128, 128, 2, 2, 4, 16"))})
 
 
-@pytest.mark.parametrize("dt", ["f32", "bf16"])
+@pytest.mark.parametrize("dt", DTS)
 @pytest.mark.parametrize("variant", HALO + DMA)
 @pytest.mark.parametrize("n,h,cin,cout,n1,which", [
     (3, 16, 64, 64, 0, (True, True)),            # one part
@@ -109,19 +144,29 @@ DMA = ["dma128x128", "dma64x128", "dma128x64", "dma64x64", "dma256x64", "dma256x
     (2, 16, 192, 128, 64, (True, True)),         # both parts, ragged N for the 128-wide tiles
 ])
 def test_dgrad_gsum_forced_variant(variant, dt, n, h, cin, cout, n1, which):
-    _dgrad_case(variant, dt, n, h, cin, cout, n1, which=which)
+    kern = _dgrad_case(variant, dt, n, h, cin, cout, n1, which=which)
+    if dt == "gf32":          # the <__bf16, float> instantiation; the static-tap halo blocks name their gsum form, the DMA tiles take the request as an argument
+        gs = ", true" if variant in ("halo128_st", "halo64_st") else ""
+        assert kern == GF32_SYMBOL[variant].format(gs=gs), kern
+        # the element-store epilogues took the sums themselves (tapgemm_plan: 64-pixel wave tiles per sample for the DMA tiles; the static-tap halo
+        # blocks); the dynamic-tap halo forms are forced-only variants and leave them to the reduce pass
+        want = variant not in ("halo128", "halo64")
+        assert all(f == want for f in _last["fused"].values()), (kern, _last["fused"])
 
 
-@pytest.mark.parametrize("dt", ["f32", "bf16"])
+@pytest.mark.parametrize("dt", DTS)
 @pytest.mark.parametrize("variant", ["dma128x128", "dma64x128", "dma256x128", "halo128_st"])
 def test_dgrad_gsum_with_outputs_beyond_4gib(variant, dt):
     """"tapgemm.flat_epilogue": the DMA tiles keep their sums on the 64-bit-address epilogue, the halo kernels (32-bit aux offsets) hand
     them to the follow-up reduce pass -- same gradient, same sums either way"""
     _ops().set_tuning("tapgemm.flat_epilogue", 1)
-    _dgrad_case(variant, dt, 2, 32, 256, 64, 128, which=(True, True))
+    kern = _dgrad_case(variant, dt, 2, 32, 256, 64, 128, which=(True, True))
+    if dt == "gf32":
+        assert kern == GF32_SYMBOL[variant].format(gs=""), kern
+        assert all(f == variant.startswith("dma") for f in _last["fused"].values()), (kern, _last["fused"])
 
 
-@pytest.mark.parametrize("dt", ["f32", "bf16"])
+@pytest.mark.parametrize("dt", DTS)
 @pytest.mark.parametrize("n,h,cin,cout,n1,which", [
     (3, 16, 64, 64, 0, (True, True)),            # 64 <- 64: the layers in front of the 256 x 256 blocks
     (2, 32, 128, 64, 64, (False, True)),         # 128 <- 64 with the skip half summed
@@ -130,42 +175,60 @@ def test_dgrad_gsum_with_outputs_beyond_4gib(variant, dt):
 ])
 def test_dgrad_gsum_wreg(dt, n, h, cin, cout, n1, which):
     kern = _dgrad_case("wreg", dt, n, h, cin, cout, n1, which=which)
+    if dt == "gf32":
+        # tapgemm_plan fuses on `wreg_ok && oesz == 2`: with fp32 outputs the plain four-wave kernel runs and the reduce pass delivers the sums
+        assert kern == f"tapgemm_wreg_kernel<float, {cout // 32}>", kern
+        assert not any(_last["fused"].values()), _last["fused"]
+        return
     assert kern.startswith("tapgemm_wreg") and kern.endswith("true>"), kern          # the gsum instantiation ran
 
 
-@pytest.mark.parametrize("dt", ["f32", "bf16"])
+@pytest.mark.parametrize("dt", DTS)
 def test_dgrad_gsum_stride2_and_fallback(dt):
-    """Stride-2 input gradients: the fused four-phase kernel has no gsum epilogue (follow-up reduce pass), the DMA tiles take
-    the sums per phase; a 4 x 4 map (16 pixels per sample) has no whole wave tile per sample: reduce pass again."""
+    """Stride-2 input gradients: the fused four-phase kernel has no gsum epilogue for bf16 outputs (follow-up reduce pass; with fp32
+    outputs its element-store epilogue takes the sums), the DMA tiles take the sums per phase; a 4 x 4 map (16 pixels per sample) has no
+    whole wave tile per sample: reduce pass again."""
+    gf = dt == "gf32"
     assert _dgrad_case("phase4", dt, 2, 32, 64, 128, 0, stride=2).startswith("tapgemm_phase4")
-    _dgrad_case("dma128x128", dt, 2, 32, 64, 128, 0, stride=2)
-    _dgrad_case("dma128x64", dt, 3, 16, 64, 64, 0, stride=2)
+    # tapgemm_plan: with fp32 outputs (`oesz == 4`) the four-phase kernel takes the sums in its element-store epilogue -- bf16 aux, fp32 stores
+    assert not gf or (_ops().last_kernel() == "tapgemm_phase4_kernel<__bf16, float>" and _last["fused"] == {0: True})
+    kern = _dgrad_case("dma128x128", dt, 2, 32, 64, 128, 0, stride=2)
+    assert not gf or (kern == GF32_SYMBOL["dma128x128"].format(gs="") and _last["fused"] == {0: True})
+    kern = _dgrad_case("dma128x64", dt, 3, 16, 64, 64, 0, stride=2)          # (64 pixels per sample and phase: one wave tile, every sum in slot 0)
+    assert not gf or kern == GF32_SYMBOL["dma128x64"].format(gs="")
     _dgrad_case("auto", dt, 3, 4, 64, 64, 0)
+    assert not gf or _last["fused"] == {0: False}          # 16 pixels per sample: no whole wave tile, the reduce pass
     _dgrad_case("auto", dt, 2, 8, 128, 128, 0, k=1)                                  # the 1 x 1 bottleneck
 
 
-@pytest.mark.parametrize("dt", ["f32", "bf16"])
+@pytest.mark.parametrize("dt", DTS)
 @pytest.mark.parametrize("variant", ["auto", "dma128x128", "dma256x128", "dma64x64"])
 def test_fwd_gsum_stride2(variant, dt):
     """shm_conv2d_fwd_gsum on the stride-2 forward form (= Conv2DTranspose's input gradient in model.py)."""
     ops = _ops()
     rng = np.random.default_rng(9)
     n, h, cin, cout = 2, 32, 64, 128
-    adt = BF if dt == "bf16" else torch.float32
+    adt = BF if dt == "bf16" else torch.float32          # the outputs; "gf32": bf16 x / wk / aux, fp32 y
     x = _t(rng.standard_normal((n, h, h, cin)), dt)
     w = rng.standard_normal((3, 3, cin, cout)) * 0.1
-    wk = torch.zeros(9 * cout * cin, device="cuda", dtype=adt)
+    wk = torch.zeros(9 * cout * cin, device="cuda", dtype=x.dtype)
     ops.transpose_taps(torch.from_numpy(w.astype(np.float32)).cuda(), wk, 9, cin, cout, cin)
     aux = _t(rng.standard_normal((n, h // 2, h // 2, cout)), dt)
-    ya = torch.empty((n, h // 2, h // 2, cout), device="cuda", dtype=adt)
-    yb = torch.empty_like(ya)
+    ya, ba = _out((n, h // 2, h // 2, cout), adt)
+    yb, bb = _out((n, h // 2, h // 2, cout), adt)
     red = torch.zeros(ops.GSUM_SLOTS * n * cout * 2, dtype=torch.float64, device="cuda")
     ops.set_tuning("tapgemm.variant", variant)
     ops.conv2d_fwd(x, None, 0, cin, 0, wk, None, ya, cout, n, h, h, cin, cout, 3, 2, 1.0)
     ops.conv2d_fwd(x, None, 0, cin, 0, wk, None, yb, cout, n, h, h, cin, cout, 3, 2, 1.0, gsum=(aux, cout, red))
     torch.cuda.synchronize()
-    assert torch.equal(ya, yb)
+    assert torch.equal(ya, yb) and band_untouched(ba) and band_untouched(bb)
     _check_sums(red, yb, aux, dt)
+    if dt == "gf32":
+        kern = ops.last_kernel()
+        assert kern == GF32_SYMBOL["dma64x64" if variant == "auto" else variant].format(gs=""), kern          # (auto: 8 tiles of 64 x 128, "not even one per CU")
+        assert _fused_epilogue_ran(red, n, cout), kern
+        ref = st.conv2d_same(x.double().cpu().permute(0, 3, 1, 2), torch.from_numpy(w.astype(np.float32)).to(BF).double(), 2).permute(0, 2, 3, 1).numpy()
+        assert rel_l2(host(yb), ref) < 1e-4, (kern, rel_l2(host(yb), ref))
 
 
 @pytest.mark.parametrize("dt", ["f32", "bf16"])

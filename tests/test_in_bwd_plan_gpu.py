@@ -9,6 +9,8 @@ The rules the table below is written from (include/shmgan_hip.h at shm_in_bwd's 
     slices per group on, or where "elem.fused_hold" = 2 forces it ("elem.fused_hold" = 1 excludes it); "elem.fused_gvariant" picks <2, 2, 4> or <8, 8, 3>;
   * twice a group's blocks must fit the device (every group here has at most 256 blocks: a whole MI355X holds 768 - 1024);
   * two passes: the reduce pass is in_bwd_reduce8_kernel for bf16 activations with c a multiple of 8, in_bwd_reduce_kernel otherwise.
+  * SHM_BF16_GF32 (bf16 a and dz, fp32 g and g2 -- GF32 below): the one-pass forms require `q.dtype == SHM_BF16`, so every request runs reduce + apply;
+    `wide8` includes the mode, so the reduce pass is in_bwd_reduce8_kernel where c is a multiple of 8.
 Every row also checks the result against float64, that `red` is zero on return and that the scratch is zero behind its partial rows.
 
 Sample chunking: with "elem.chunk_mb" = 1 the two passes run chunk by chunk over samples whose tensors fit 1 MiB; the results are those of one
@@ -21,6 +23,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 BF, F32 = torch.bfloat16, torch.float32
+GF32 = "gf32"               # a row's dtype: bf16 activations (a, dz) with the gradient signal (g, g2) in fp32, SHM_BF16_GF32
 TOL = 1e-5                  # tests/test_ops_gpu.py: one fp32 InstanceNorm op against float64
 TOL_BF16 = 4e-3             # tests/test_in_bwd_fused_gpu.py: bf16 output rounding
 R8 = "in_bwd_reduce8_kernel + in_bwd_apply_kernel"
@@ -43,15 +46,16 @@ def _reset_tuning():
 def _operands(seed, dt, n, h, w, c, pool=False, rank1=False):
     ops = _ops()
     rng = np.random.default_rng(seed)
+    dt, gdt = (BF, F32) if dt == GF32 else (dt, dt)
     a = torch.from_numpy((rng.standard_normal((n, h, w, c)) * rng.uniform(0.5, 2.0, (n, 1, 1, c)) + rng.uniform(-1, 1, (n, 1, 1, c))).astype(np.float32)).cuda().to(dt)
     o = {"a": a, "g": None, "g2": None, "hdz": None, "hw": None}
     if rank1:
         o["hdz"] = torch.from_numpy(rng.standard_normal((n, h, w)).astype(np.float32)).cuda()
         o["hw"] = torch.from_numpy(rng.standard_normal(c).astype(np.float32)).cuda()
     else:
-        o["g"] = torch.from_numpy(rng.standard_normal((n, h, w, c)).astype(np.float32)).cuda().to(dt)
+        o["g"] = torch.from_numpy(rng.standard_normal((n, h, w, c)).astype(np.float32)).cuda().to(gdt)
         if pool:
-            o["g2"] = torch.from_numpy(rng.standard_normal((n, h // 2, w // 2, c)).astype(np.float32)).cuda().to(dt)
+            o["g2"] = torch.from_numpy(rng.standard_normal((n, h // 2, w // 2, c)).astype(np.float32)).cuda().to(gdt)
     o["stats"] = torch.zeros(n * c * 2, dtype=torch.float64, device="cuda")
     ops.in_stats(a, c, o["stats"], n, h * w, c, 1e-6)
     return o
@@ -119,6 +123,16 @@ TABLE = [
     ("two-pass-f32", F32, 2, 16, 16, 64, False, False, {}, "full", R4),
     ("two-pass-f32-pooled", F32, 2, 16, 16, 64, True, False, {}, "full", R4),
     ("two-pass-f32-rank1", F32, 2, 16, 16, 64, False, True, {}, None, R4),
+    # SHM_BF16_GF32 on the requests of "fused8-2048-pixel-slice", "fused8-pooled" and "fusedg-forced-v0" (the smallest of each one-pass form above):
+    # none reaches a one-pass form
+    ("gf32-fused8-request", GF32, 1, 32, 64, 8, False, False, {}, "full", R8),
+    ("gf32-fused8-pooled-request", GF32, 2, 16, 16, 64, True, False, {}, "full", R8),
+    ("gf32-fusedg-request", GF32, 2, 16, 32, 64, False, False, {"elem.fused_hold": 2, "elem.fused_gvariant": 0}, "full", R8),
+    # c = 48 has no whole barrier groups (neither a power of two below 64 nor a multiple of 64): two passes in every mode
+    ("two-pass-bf16-c48", BF, 2, 16, 16, 48, False, False, {}, "full", R8),
+    ("two-pass-f32-c48", F32, 2, 16, 16, 48, False, False, {}, "full", R4),
+    ("gf32-c48", GF32, 2, 16, 16, 48, False, False, {}, "full", R8),
+    ("gf32-c36", GF32, 2, 16, 16, 36, False, False, {}, "full", R4),          # not a multiple of 8: four channels per thread
 ]
 
 
@@ -130,7 +144,7 @@ def test_dispatch_table(dt, n, h, w, c, pool, rank1, knobs, scr, want):
     scratch = None if scr is None else torch.zeros(need - (1 if scr == "short" else 0), dtype=torch.float64, device="cuda")
     for key, val in knobs.items():
         ops.set_tuning(key, val)
-    dz, db, _, kern = _run(o, n, h, w, c, scratch)
+    dz, db, keep, kern = _run(o, n, h, w, c, scratch, sums=dt == GF32)
     assert kern == want, kern
     if scratch is not None:
         # zero on return: behind the per-block partial rows of a one-pass launch (tests/test_in_bwd_fused_gpu.py: _clean); all of it otherwise
@@ -141,11 +155,16 @@ def test_dispatch_table(dt, n, h, w, c, pool, rank1, knobs, scr, want):
     tol = TOL if dt == F32 else TOL_BF16
     assert _rel(dz, zr) < tol, _rel(dz, zr)
     assert float((db - sr.sum(0)).abs().max()) <= tol * float(zr.abs().sum((0, 1, 2)).max())
+    if keep is not None:          # the per-sample dz sums, on the scale of their summands like the bias gradient; and the same call without them (the folding apply pass)
+        assert float((keep - sr).abs().max()) <= tol * float(zr.abs().sum((1, 2)).max())
+        dz1, db1, _, kern1 = _run(o, n, h, w, c, scratch)
+        assert kern1 == want and _rel(dz1, zr) < tol and float((db1 - sr.sum(0)).abs().max()) <= tol * float(zr.abs().sum((0, 1, 2)).max())
 
 
 # 32 x 32 x 64 maps: a plain sample is 512 KiB in fp32 and 256 KiB in bf16, a pooled fp32 sample 576 KiB.  Chunks of 1 MiB: 2 + 1 samples (fp32),
-# 1 + 1 + 1 (fp32 pooled), 3 (bf16: one chunk), 4 + 1 (bf16, n = 5)
-@pytest.mark.parametrize("dt,n,pool", [(F32, 3, False), (F32, 3, True), (BF, 3, False), (BF, 5, False)], ids=["f32-2+1", "f32-pooled-1+1+1", "bf16-3", "bf16-4+1"])
+# 1 + 1 + 1 (fp32 pooled), 3 (bf16: one chunk), 4 + 1 (bf16, n = 5); SHM_BF16_GF32: 128 KiB of a + 256 KiB of g, 2 + 1
+@pytest.mark.parametrize("dt,n,pool", [(F32, 3, False), (F32, 3, True), (BF, 3, False), (BF, 5, False), (GF32, 3, False)],
+                         ids=["f32-2+1", "f32-pooled-1+1+1", "bf16-3", "bf16-4+1", "gf32-2+1"])
 def test_sample_chunks_give_the_results_of_one_chunk(dt, n, pool):
     ops = _ops()
     h = w = 32

@@ -21,17 +21,17 @@ pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
 TOL = {"f32": 1e-5, "bf16": 4e-3}
 SYMBOL = {
-    "halo128": "tapgemm_halo_kernel<{t}, {t}, 128, 16, false, 2>", "halo64": "tapgemm_halo_kernel<{t}, {t}, 64, 16, false, 2>",
-    "halo128_ph8": "tapgemm_halo_kernel<{t}, {t}, 128, 8, false, 2>",
-    "dma128x128": "tapgemm_dma_kernel<{t}, {t}, 128, 128, 2, 2, 3, 16>", "dma64x128": "tapgemm_dma_kernel<{t}, {t}, 64, 128, 2, 2, 3, 16>",
-    "dma128x64": "tapgemm_dma_kernel<{t}, {t}, 128, 64, 2, 2, 3, 16>", "dma64x64": "tapgemm_dma_kernel<{t}, {t}, 64, 64, 2, 2, 3, 16>", "dma256x64": "tapgemm_dma_kernel<{t}, {t}, 256, 64, 4, 1, 3, 16>",
-    "dma256x128": "tapgemm_dma_kernel<{t}, {t}, 256, 128, 4, 2, 3, 16>",
-    "dma128x128_bk32": "tapgemm_dma_kernel<{t}, {t}, 128, 128, 2, 2, 2, 32>",
-    "dma128x128_nst4": "tapgemm_dma_kernel<{t}, {t}, 128, 128, 2, 2, 4, 16>",
+    "halo128": "tapgemm_halo_kernel<{t}, {o}, 128, 16, false, 2>", "halo64": "tapgemm_halo_kernel<{t}, {o}, 64, 16, false, 2>",
+    "halo128_ph8": "tapgemm_halo_kernel<{t}, {o}, 128, 8, false, 2>",
+    "dma128x128": "tapgemm_dma_kernel<{t}, {o}, 128, 128, 2, 2, 3, 16>", "dma64x128": "tapgemm_dma_kernel<{t}, {o}, 64, 128, 2, 2, 3, 16>",
+    "dma128x64": "tapgemm_dma_kernel<{t}, {o}, 128, 64, 2, 2, 3, 16>", "dma64x64": "tapgemm_dma_kernel<{t}, {o}, 64, 64, 2, 2, 3, 16>", "dma256x64": "tapgemm_dma_kernel<{t}, {o}, 256, 64, 4, 1, 3, 16>",
+    "dma256x128": "tapgemm_dma_kernel<{t}, {o}, 256, 128, 4, 2, 3, 16>",
+    "dma128x128_bk32": "tapgemm_dma_kernel<{t}, {o}, 128, 128, 2, 2, 2, 32>",
+    "dma128x128_nst4": "tapgemm_dma_kernel<{t}, {o}, 128, 128, 2, 2, 4, 16>",
     "wreg": "tapgemm_wreg16_bf16_kernel<{nch}, {epi}>",                            # bf16: the eight-wave kernel with line-wide stores ("tapgemm.wreg16", default on)
     "wreg4": "tapgemm_wreg_kernel<{t}, {nch}>",                             # ... and the four-wave form with 32-column wave tiles
-    "halo128_st": "tapgemm_halo_kernel<{t}, {t}, 128, 16, true, 2>", "halo64_st": "tapgemm_halo_kernel<{t}, {t}, 64, 16, true, 2>",
-    "phase4": "tapgemm_phase4_kernel<{t}, {t}>", "halo128_st_w4": "tapgemm_halo_kernel<{t}, {t}, 128, 16, true, 4>",
+    "halo128_st": "tapgemm_halo_kernel<{t}, {o}, 128, 16, true, 2>", "halo64_st": "tapgemm_halo_kernel<{t}, {o}, 64, 16, true, 2>",
+    "phase4": "tapgemm_phase4_kernel<{t}, {o}>", "halo128_st_w4": "tapgemm_halo_kernel<{t}, {o}, 128, 16, true, 4>",
 }
 HALO = ["halo128", "halo64", "halo128_st", "halo64_st", "halo128_st_w4"]
 DMA = ["dma128x128", "dma64x128", "dma128x64", "dma64x64", "dma256x64", "dma256x128", "dma128x128_bk32", "dma128x128_nst4"]
@@ -48,17 +48,22 @@ def _reset_tuning():
     _ops().set_tuning("reset", 0)
 
 
-def _sym(variant, dt, nch=2, epi=True, hw=None):
+def _sym(variant, dt, nch=2, epi=True, hw=None, out=None):
     """epi: the launch has an activation or fused statistics (forward); False = the plain input-gradient form (round 5: tapgemm_wreg16_bf16_kernel<NCH, EPI>).
     hw = (height, width) of the map: under "tapgemm.wreg16" = 2 (the default) a 64-input-channel bf16 layer on a map of whole 8 x 32-pixel
-    patches takes the ping-pong kernel (conv_pingpong.hip)."""
+    patches takes the ping-pong kernel (conv_pingpong.hip).
+    out: element type of the outputs where it is not the operands' -- "f32" with dt = "bf16" is SHM_BF16_GF32, whose weights-in-registers
+    launches all take the four-wave kernel (the eight-wave and ping-pong kernels store 2-byte elements)."""
     if variant == "wreg" and dt == "f32":
         return f"tapgemm_wreg_f32_kernel<{int(2 * nch)}, 4, false>"          # 16-channel chunks, four N waves, one source
     nch = int(nch)
+    o = "float" if (out or dt) == "f32" else "__bf16"
+    if variant == "wreg" and dt == "bf16" and o == "float":
+        return f"tapgemm_wreg_kernel<float, {nch}>"
     if variant == "wreg" and SYMBOL["wreg"].startswith("tapgemm_wreg16") and nch == 2 and hw is not None and hw[0] % 8 == 0 and hw[1] % 32 == 0 \
             and _ops().get_tuning("tapgemm.wreg16") == 2:
         return f"tapgemm_pp_bf16_kernel<{2 if epi else 0}>"          # MODE 2: bias + LeakyReLU + statistics; 0: the plain product
-    return SYMBOL[variant].format(t="float" if dt == "f32" else "__bf16", nch=nch, epi="true" if epi else "false")
+    return SYMBOL[variant].format(t="float" if dt == "f32" else "__bf16", o=o, nch=nch, epi="true" if epi else "false")
 
 
 def _dev(a, dt):

@@ -361,7 +361,8 @@ int shm_in_bwd(const void* g1, int ldg1, const void* g2, int ldg2, const void* a
  *       of Conv2DTranspose).
  *   red = f64 [SHM_GSUM_SLOTS][batch][channels of the part][2], ZERO on entry; the slot copies cut the per-address atomic
  *       chains.  Whether the sums were taken in the epilogue or by a follow-up reduce pass (kernels without a gsum epilogue:
- *       the fused four-phase kernel, odd alignments, tiny maps) is the library's business: red is complete on return.
+ *       the fused four-phase kernel, odd alignments, tiny maps, an output or an aux of 0xfffffff0 bytes or more) is the library's
+ *       business: red is complete on return.  aux may be of any size: unlike the operands it is not bound by the 4 GiB limit.
  *   shm_in_bwd_apply = shm_in_bwd without its reduce pass: d_out = g1 + 0.25 * unpool(g2); red = sums of g1 against a,
  *       redp = sums of g2 against the pooled normalised tensor (NULL iff g2 is NULL; needs beta [c]); dstage = f64 [batch*c]
  *       staging of the bias gradient (required with dbias).  red / redp / dstage are zero again on return.  dz_sums as for shm_in_bwd. */

@@ -140,7 +140,13 @@ static TapGemmPlan tapgemm_plan(const TapGemmArgs& a, int batch, int nphase, int
         for (int p = 0; p < 2; ++p)
             if (a.gred[p]) al = al && (oesz == 4 || (a.ldgaux[p] % 8 == 0 && ((size_t)a.gaux[p] & 15) == 0));
         al = al && (a.y2 == nullptr || a.n1 % 32 == 0);
-        const bool small = a.ybytes != 0 && (a.y2 == nullptr || a.y2bytes != 0);        // 32-bit offsets into aux (it has the output's extent)
+        // the epilogues read aux with 32-bit offsets under a descriptor of 0xfffffff0 bytes.  aux has the output's pixels but a pitch of its own,
+        // so its extent is checked by itself: an aux the offsets cannot reach sends the sums to the reduce pass (64-bit addresses)
+        bool aux32 = true;
+        for (int p = 0; p < 2; ++p)
+            if (a.gred[p]) aux32 = aux32 && (size_t)batch * a.ho * a.wo * a.ldgaux[p] * esz < 0xfffffff0ull;
+        al = al && aux32;
+        const bool small = aux32 && a.ybytes != 0 && (a.y2 == nullptr || a.y2bytes != 0);        // 32-bit offsets into aux and the outputs
         // bf16 outputs: the sums are taken in the LDS-staged 16-byte store path, which has its own alignment conditions
         const bool wide_ok = oesz == 4 || ((a.nout % 8 == 0) && (a.n1 % 8 == 0) && (a.ldy % 8 == 0) && (((size_t)a.y & 15) == 0) &&
                                            (a.y2 == nullptr || ((a.ldy2 % 8 == 0) && (((size_t)a.y2 & 15) == 0))));
@@ -151,6 +157,8 @@ static TapGemmPlan tapgemm_plan(const TapGemmArgs& a, int batch, int nphase, int
             break;
         case SHM_TG_DMA_128x128: case SHM_TG_DMA_64x128: case SHM_TG_DMA_128x64: case SHM_TG_DMA_64x64: case SHM_TG_DMA_256x64:
         case SHM_TG_DMA_256x128: case SHM_TG_DMA_128x128_BK32: case SHM_TG_DMA_128x128_NST4:
+            // (al holds aux32 for the 32-bit aux offsets of the fast element-store epilogue, conv_dma.hip "fastep"; the wide and the plain
+            // element-store epilogues index aux through size_t and would not need it)
             gs_fused = al && (a.hg * a.wg) % 64 == 0;
             break;
         case SHM_TG_WREG:

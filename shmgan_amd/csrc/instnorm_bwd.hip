@@ -82,7 +82,10 @@ static InBwdPlan in_bwd_plan(const InBwdReq& q, int (*resident)(int form)) {
     const int hold = shm_tune(SHM_TUNE_ELEM_FUSED_HOLD);          // 0 automatic, 1 the round-5 kernel only (g and a held), 2 the g-held kernel only
     const int fgv = shm_tune(SHM_TUNE_ELEM_FUSED_GVARIANT);
     const int n8 = hw / slice, n16 = hw / slice16;                // blocks per group of either kernel
-    const bool g_held = base_ok && hold != 1 && !q.g2 && hw % slice16 == 0 && (hold == 2 || n8 >= 256) && n16 <= 2 * max_slices &&
+    // the g-held kernel addresses each tensor through one buffer descriptor per SAMPLE and 32-bit byte offsets: a sample of every pitch below 4 GiB
+    const int ldmax = q.ldg1 > q.lda ? (q.ldg1 > q.lddz ? q.ldg1 : q.lddz) : (q.lda > q.lddz ? q.lda : q.lddz);
+    const bool samp32 = (size_t)hw * ldmax * 2 < 0xfffffff0ull;
+    const bool g_held = base_ok && hold != 1 && !q.g2 && samp32 && hw % slice16 == 0 && (hold == 2 || n8 >= 256) && n16 <= 2 * max_slices &&
                         2 * n16 <= resident(fgv == 1 ? 3 : 2);
     const bool ga_held = !g_held && base_ok && hold != 2 && hw % slice == 0 && n8 <= max_slices && (!q.g2 || g2_tiles) && 2 * n8 <= resident(q.g2 ? 1 : 0);
     if (g_held || ga_held) {

@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 import torch
 
+import far_ref as F
 import pitch_ref as R
 from oracle import step_torch as st
 from test_gsum_gpu import _check_sums, _sums
@@ -55,37 +56,55 @@ def _lrelu(a, slope=0.2):
 
 
 class Alloc:
-    """The tensors of one call in the layouts of one case: inputs in NaN parents, outputs in SENTINEL parents."""
+    """The tensors of one call in the layouts of one case: inputs in NaN parents, outputs in SENTINEL parents.  A case names a layout of
+    pitch_ref.LAYOUTS per pitch argument, or holds a far_ref.Far (test_far_gpu.py; one per case): that tensor's parent has the bands of
+    far_ref.lead_for / trail_for, lies in far_ref.arena() and is filled, written, read and scanned in chunks."""
+
+    last = None          # the tensors of the latest call: a runner that ended in a refusal leaves its parents here for the sentinel check
 
     def __init__(self, case):
         self.case, self.watch, self.pitch = case, [], {}
+        Alloc.last = self
 
     def _view(self, arg, shape, tdt, fill):
-        ld, off = R.layout(self.case.get(arg, "tight"), shape[-1], tdt)
+        kind = self.case.get(arg, "tight")
+        if isinstance(kind, F.Far):
+            lead = F.lead_for(kind.window, shape, kind.ld, torch.empty(0, dtype=tdt).element_size(), kind.W) if kind.lead is None else kind.lead
+            v, parent = F.far_view(fill, shape, kind.ld, 0, lead, F.trail_for(shape), tdt, "cuda", use_arena=True)
+            self.pitch[arg] = kind.ld
+            return v, parent, kind.ld, 0, lead
+        ld, off = R.layout(kind, shape[-1], tdt)
         v, parent = R.view_of(fill, shape, ld, off, None, tdt, "cuda")
         self.pitch[arg] = ld
-        return v, parent, ld, off
+        return v, parent, ld, off, None
 
     def inp(self, arg, vals, tdt, watch=False):
         """vals: float array [..., c].  watch: the call writes this tensor in place, so its parent is checked too."""
-        v, parent, ld, off = self._view(arg, vals.shape, tdt, NAN)
+        v, parent, ld, off, lead = self._view(arg, vals.shape, tdt, NAN)
         assert v.data_ptr() % 16 == 0 or self.case.get(arg) in ("half",), arg          # input bases stay 16-byte aligned
-        v.copy_(torch.from_numpy(np.ascontiguousarray(vals, dtype=np.float32)).to(tdt))
+        src = torch.from_numpy(np.ascontiguousarray(vals, dtype=np.float32)).to(tdt)
+        if lead is None:
+            v.copy_(src)
+        else:
+            F.scatter(v, src)
         if watch:
-            self.watch.append((arg, parent, tuple(vals.shape), ld, off, NAN))
+            self.watch.append((arg, parent, tuple(vals.shape), ld, off, NAN, lead))
         return v, ld
 
     def out(self, arg, shape, tdt):
-        v, parent, ld, off = self._view(arg, shape, tdt, SENTINEL)
-        self.watch.append((arg, parent, tuple(shape), ld, off, SENTINEL))
+        v, parent, ld, off, lead = self._view(arg, shape, tdt, SENTINEL)
+        self.watch.append((arg, parent, tuple(shape), ld, off, SENTINEL, lead))
         return v, ld
 
     def untouched(self):
-        return [arg for arg, parent, shape, ld, off, fill in self.watch if not R.outside_untouched(parent, shape, ld, off, None, fill)]
+        return [arg for arg, parent, shape, ld, off, fill, lead in self.watch
+                if not (R.outside_untouched(parent, shape, ld, off, None, fill) if lead is None else F.far_outside_untouched(parent, shape, ld, off, lead, fill))]
 
 
 def _cpu(t):
-    return None if t is None else t.detach().contiguous().cpu()
+    if t is None:
+        return None
+    return F.gather(t.detach()) if F.is_far(t) else t.detach().contiguous().cpu()
 
 
 def _same_f64(a, b):

@@ -44,13 +44,18 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
-from . import ops
+from . import dist, ops
 
 PSD_SUBDIRS = ("I0", "I60", "I90", "I150", "ED")          # datasetLoader.py:30-34 (PSD polar dataset)
 SHMGAN_SUBDIRS = ("I0", "I45", "I90", "I135", "ED")       # datasetLoader.py:23-27 (commented alternative)
 DIFFUSE_SOURCES = ("dir", "min", "stokes")                # where the fifth tensor comes from (PolarDataset)
 CACHE_MODES = ("none", "device")                          # where decoded samples are kept between passes (PolarDataset)
 _EXT = (".bmp", ".gif", ".jpeg", ".jpg", ".png")          # Keras' ALLOWLIST_FORMATS
+
+
+def gib_to_bytes(cache_gb):
+    """The `cache_gb` / `specseg_cache_gb` option (GiB of device memory; None = half of what is free) as a loader's cache_bytes."""
+    return None if cache_gb is None else int(float(cache_gb) * 2 ** 30)
 
 
 def list_images(directory):
@@ -186,9 +191,7 @@ class PolarDataset:
             n = len(select)
         self.n = n
         if rank is None or world is None:
-            import torch.distributed as dist
-            on = dist.is_available() and dist.is_initialized()
-            rank, world = (dist.get_rank(), dist.get_world_size()) if on else (0, 1)
+            rank, world = dist.rank(), dist.world_size()
         self.rank, self.world = int(rank), int(world)
         self._dev, self._stream = device, None
         self._pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="shm-loader")
@@ -463,8 +466,7 @@ def datasetLoad(trainer, subdirs=PSD_SUBDIRS, flip_ud=True):
     draws = (float(opt("aug_flip_lr", 0.0)), float(opt("aug_flip_ud", 0.0)), float(opt("aug_crop_min", 1.0)))
     # no augmentation asked for: the loader's default path, not the augmenting kernel at identity parameters
     augment = Augment(*draws, views=opt("aug_views", "physical")) if draws != (0.0, 0.0, 1.0) else None
-    cache_gb = opt("cache_gb", None)
-    cache = dict(cache=opt("cache", "none"), cache_bytes=None if cache_gb is None else int(float(cache_gb) * 2 ** 30))
+    cache = dict(cache=opt("cache", "none"), cache_bytes=gib_to_bytes(opt("cache_gb", None)))
     source = dict(diffuse_source=getattr(trainer.args, "diffuse_source", "dir"))
     # held-out validation (`val_dir` / `val_fraction`, both off by default): the loader train() validates on, and with val_fraction
     # the training loader is the rest of data_dir

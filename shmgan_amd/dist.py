@@ -20,6 +20,20 @@ def world_size():
     return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
 
 
+def multi():
+    """Is there a process group with more than one rank?"""
+    return world_size() > 1
+
+
+def rank():
+    return dist.get_rank() if multi() else 0
+
+
+def barrier():
+    if multi():
+        dist.barrier()
+
+
 def exchange_active():
     """Does train_step exchange gradients?  With more than one rank always; with a ONE-rank process group only under SHM_DP_FORCE=1 --
     the rehearsal a 1-GPU box allows: every bucket goes through RCCL's all-reduce on the side stream, behind the same events, as it

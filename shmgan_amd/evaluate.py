@@ -151,7 +151,7 @@ def _restore_for_test(shmgan, eval_weights, eval_checkpoint, print_fn):
     """Load the weights test mode scores and check, before any image is processed, that they are there: the chosen file (a missing
     best.npz or path raises FileNotFoundError naming eval_checkpoint) and, for "ema", an average inside it (ValueError naming
     eval_weights)."""
-    shmgan.args.eval_weights = eval_weights               # _apply_npz takes the average out of the file only for a trainer that wants it
+    shmgan.args.eval_weights = eval_weights               # checkpoint.apply takes the average out of the file only for a trainer that wants it
     if eval_checkpoint == "latest":
         path = shmgan._restore_latest()                                         # test.py:162-169
         if path is None:

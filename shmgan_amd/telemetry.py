@@ -29,7 +29,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from . import ops
+from . import checkpoint, ops
 
 LOSS_NAMES = ["total_Generator_loss", "total_Discriminator_loss", "total_Classification_loss", "G_gan_loss",
               "G_clsf_loss", "D1_RealFake_loss", "D3_RealFake_cyc", "D2_RealFake_target", "D4_RealFake_cyc",
@@ -96,10 +96,10 @@ def telemetry_options(loss_log_step=0, histogram_step=0, nonfinite=None):
 
 
 def variable_table(model, tag):
-    """[(name, offset, size, shape)] of a model's variables in Keras variable order: name = the save_npz key."""
+    """[(name, offset, size, shape)] of a model's variables in Keras variable order: name = the checkpoint key."""
     P = model.P
-    return [(f"{tag}/var{k:02d}", int(P.offsets[i]), int(np.prod(P.shapes[i])), tuple(int(d) for d in P.shapes[i]))
-            for k, i in enumerate(model._korder())]
+    return [(name, int(P.offsets[i]), int(np.prod(P.shapes[i])), tuple(int(d) for d in P.shapes[i]))
+            for name, i in checkpoint.variable_keys(model, tag)]
 
 
 def stats_record(step, model, name, shape, stats, hist):

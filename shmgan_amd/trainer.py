@@ -19,17 +19,20 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import gc
+import os
+import time
 from types import SimpleNamespace
 
 import numpy as np
 import torch
 
-from . import ops
+from . import checkpoint, dist, ops, validation
+from .data import Augment, MaskDataset, datasetLoad, gib_to_bytes
 from .dist import GradReducer, exchange_active, world_size
 from .model import Arena, Discriminator, Generator, WgradLane, pad_channels
 from .specseg import SpecSeg
-from .telemetry import LOSS_NAMES, NonFiniteGradientError, Telemetry, compose_losses, telemetry_options  # noqa: F401
-from .telemetry import VALIDATION_FILE, WEIGHT_SETS, improves, validation_options, write_lines
+from .telemetry import LOSS_NAMES, WEIGHT_SETS, NonFiniteGradientError, Telemetry, compose_losses, telemetry_options, validation_options  # noqa: F401
 
 
 class _Optimizer:
@@ -146,6 +149,10 @@ class ShmGANwithSSpecSeg:
         # value so far {"monitor", "weights", "value", "step"} and the step of the last validation; whether the last checkpoint that was
         # loaded held an average of the generator's weights
         self.valDataset, self._val_on, self._best, self._last_val_step, self._loaded_ema = None, False, None, None, False
+        # train(): the validation options, this rank's dataset length, train_step calls so far, the per-step flip draw (inert, SHM.py:983)
+        self._val_step, self._val_monitor, self.length_dataset, self.batch_step, self.random_flip = None, None, 0, 0, 0.0
+        # the last train_step's loss vectors and inputs (losses()), the frame (H, W) of the last infer(), _stats_now's Telemetry without files
+        self._last = self._inf_frame = self._adhoc_telemetry = None
         # test diagnostics: called with no arguments between the last forward pass and the first backward kernel of a step
         # (tests/test_step_gpu.py pins LeakyReLU signs there; never set on the hot path)
         self.before_backward = None
@@ -155,7 +162,6 @@ class ShmGANwithSSpecSeg:
         # batches on the two streams (samples are independent).  Measured in round 3 and NOT the default: in lockstep the halves
         # gain 0.2 ms of a 121 ms fp32 step (within noise), taking turns convolution by convolution (so that one half's normalisation
         # pass runs under the other's convolution) LOSES 2 ms -- a single stream already fills the launch tails
-        import os
         self.forward_parts = int(os.environ.get("SHM_FORWARD_PARTS", "1"))
         # the D-loss backward on the second stream (train_step): measured on one box, A/B by the variable, bf16 22.48 -> 22.25 ms, S = 512 B = 4
         # 42.79 -> 42.58, B = 32 79.3 -> 78.6; fp32 114.2 -> 114.2 (MFMA bound either way) -- default on in bf16, off in fp32
@@ -215,8 +221,7 @@ class ShmGANwithSSpecSeg:
         aborted = self.arena.abort is not None and self.arena.abort.tripped(sync=True)
         self.arena.abort = None
         self.arena.t.clear()
-        self._ws = self._prefetched = self._loss_cache = self.valDataset = None
-        self._adhoc_telemetry = None
+        self._ws = self._prefetched = self._loss_cache = self.valDataset = self._adhoc_telemetry = None
         self.G = self.D = self.SpecSeg = None
         self.specular_candidate = None
         if aborted:
@@ -246,7 +251,7 @@ class ShmGANwithSSpecSeg:
     def _stats_now(self, kind, scale):
         tel = self.telemetry
         if tel is None:                  # interactive use without logging: a Telemetry with no writer thread and no files
-            tel = self._adhoc_telemetry = getattr(self, "_adhoc_telemetry", None) or Telemetry(self, log_dir=None)
+            tel = self._adhoc_telemetry = self._adhoc_telemetry or Telemetry(self, log_dir=None)
         return tel.stats_now(kind, scale)
 
     def grad_stats(self):
@@ -260,7 +265,6 @@ class ShmGANwithSSpecSeg:
         return self._stats_now("weights", 1.0)
 
     def _get_lane(self):
-        import os
         if self._lane is None:
             self._lane = WgradLane(self.device, enabled=os.environ.get("SHM_NO_WGRAD_LANE") is None)
         return self._lane
@@ -319,19 +323,16 @@ class ShmGANwithSSpecSeg:
         mask options) with the loader options specseg_aug_flip_lr / specseg_aug_flip_ud / specseg_aug_crop_min / specseg_aug_views
         (an Augment when any draw is asked for), specseg_shuffle, specseg_data_seed and specseg_cache_gb (GiB of device memory for
         the decoded pairs; None = half of what is free).  All at their defaults: a dataset without loader options."""
-        from .data import Augment
         opt = self._specseg_opt(args)
         source = opt("specseg_mask_source")
         if source not in SPECSEG_MASK_SOURCES:
             raise ValueError(f"train_specseg: specseg_mask_source {source!r} is not one of {SPECSEG_MASK_SOURCES}")
         draws = (float(opt("specseg_aug_flip_lr")), float(opt("specseg_aug_flip_ud")), float(opt("specseg_aug_crop_min")))
-        cache_gb = opt("specseg_cache_gb")
         loader = dict(augment=Augment(*draws, views=opt("specseg_aug_views")) if draws != (0.0, 0.0, 1.0) else None,
                       shuffle=bool(opt("specseg_shuffle")), seed=int(opt("specseg_data_seed")),
-                      cache_bytes=None if cache_gb is None else int(float(cache_gb) * 2 ** 30))
+                      cache_bytes=gib_to_bytes(opt("specseg_cache_gb")))
         if source == "polar":
             return self._polar_mask_dataset(opt, **loader)
-        from .data import MaskDataset
         idir, mdir = opt("specseg_image_dir"), opt("specseg_mask_dir")
         if not idir or not mdir:
             raise ValueError("train_specseg needs specseg_image_dir and specseg_mask_dir")
@@ -342,7 +343,6 @@ class ShmGANwithSSpecSeg:
         return lambda k: getattr(args, k, None) if args is not None and getattr(args, k, None) is not None else getattr(self.args, k)
 
     def _polar_mask_dataset(self, opt, **loader):
-        from .data import MaskDataset
         data_dir = opt("data_dir")
         if not data_dir:
             raise ValueError("specseg_mask_source='polar' needs data_dir: the capture's four view directories")
@@ -368,7 +368,6 @@ class ShmGANwithSSpecSeg:
         # A trainer is a web of reference cycles (closures over it, records of full-batch tensors), so a dropped trainer keeps its device
         # buffers until Python's cycle collector happens to run.  A process that builds one trainer after another (bench.py's extra
         # configurations, a test session) can pile up hundreds of GiB of dead arenas that way: collect before allocating the next one.
-        import gc
         gc.collect()
         self.G = self.build_generator()
         self.D = self.build_discriminator()
@@ -472,14 +471,9 @@ class ShmGANwithSSpecSeg:
         keep = self.arena.get("draws/keep", (2 * B, s, s, 16 * self.filter_size))
         self._draw_count += 1
         seed = (self.seed << 32) | (self._draw_count & 0xFFFFFFFF)
-        ops.randn(noise, 0.1, seed, 2 * self._rank())
-        ops.keep_mask(keep, self.dropout_amnt, seed, 2 * self._rank() + 1)
+        ops.randn(noise, 0.1, seed, 2 * dist.rank())
+        ops.keep_mask(keep, self.dropout_amnt, seed, 2 * dist.rank() + 1)
         return SimpleNamespace(flags=flags, target_label=float(self.TARGET_LABELS), noise=noise, keep_mask=keep)
-
-    @staticmethod
-    def _rank():
-        import torch.distributed as dist
-        return dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
 
     def _dev(self, t):
         if isinstance(t, np.ndarray):
@@ -609,10 +603,13 @@ class ShmGANwithSSpecSeg:
         # blocks run on the second stream beside the generator's forward passes (round 6); the heads wait for `ev_dreal`
         ev_dreal = None
         d_real_early = self.d_fwd_on_lane and lane.stream is not None and not (self.forward_parts > 1)
-        if d_real_early:
+
+        def pack_real():
             ops.pack_rgb16(orig[4], noise[B:2 * B], xd[6 * B:7 * B], B * npix)                 # D(2) SHM.py:563
             for k in range(5):                                                                 # D(4) SHM.py:638-642
                 ops.pack_rgb16(orig[k], None, xd[(7 + k) * B:(8 + k) * B], B * npix)
+        if d_real_early:
+            pack_real()
             D.start(xd, keep, [(0, B, 0), (6 * B, B, B)], attn_d)
             lane.submit(lambda: D.trunk_rows(6 * B, 12 * B))
             ev_dreal = lane.event()
@@ -632,9 +629,7 @@ class ShmGANwithSSpecSeg:
         cyc_rgb = A.get("cyc/rgb", (5 * B, S, S, 3))
         ops.yuv2rgb(cyc_Y, cbcr, None, cyc_rgb, xd[B:6 * B], 5 * B, B, npix)
         if not d_real_early:
-            ops.pack_rgb16(orig[4], noise[B:2 * B], xd[6 * B:7 * B], B * npix)                 # D(2) SHM.py:563
-            for k in range(5):                                                                 # D(4) SHM.py:638-642
-                ops.pack_rgb16(orig[k], None, xd[(7 + k) * B:(8 + k) * B], B * npix)
+            pack_real()
 
         # ---- image-space losses (L1, SSIM, NST: SHM.py:744-826) and their gradients wrt the two Y planes.  Nothing reads them before the
         # G-loss backward leaves the discriminator (conv3x3_dgrad_sum1 below accumulates into dgen_y / dcyc_y), so in bf16 they run on the second
@@ -737,7 +732,7 @@ class ShmGANwithSSpecSeg:
 
         # ---- clip + Adam  SHM.py:859-872.  On a histogram step (telemetry, rank 0 only: the reduced gradient is the same on every rank) the
         # gradient statistics go beside the Adam launch of the same buffer: both only read the gradient, after its collective
-        tel = self.telemetry if apply and self._rank() == 0 else None
+        tel = self.telemetry if apply and dist.rank() == 0 else None
         step = D.P.iterations + 1
         hist_now = tel is not None and tel.wants_histograms(step)
         if apply:
@@ -799,11 +794,8 @@ class ShmGANwithSSpecSeg:
         `self.loadedDataset.cache_stats()` says what it holds.  `ema_decay` (with `ema_warmup`) keeps an average of the generator's weights
         (_ensure_ema, generator_weights); `val_dir` or `val_fraction` (with `val_seed`, `val_step`, `val_batch_size`, `val_monitor`) hold captures
         out: every `val_step` epochs, in front of the checkpoint, and once at the end they are scored (validate), rank 0 appends the means to
-        `log_dir`/validation.jsonl and keeps the best weights as `checkpoint_save_dir`/best.npz (_validate_and_log).  Both are off by default and
+        `log_dir`/validation.jsonl and keeps the best weights as `checkpoint_save_dir`/best.npz (validation.py).  Both are off by default and
         leave the training trajectory bitwise alone when on.  `max_steps` (tests) stops early.  Returns the number of train_step calls made."""
-        import os
-        import time
-        from .data import datasetLoad
         if args is not None:
             for k, v in vars(args).items():
                 setattr(self.args, k, v)
@@ -811,26 +803,26 @@ class ShmGANwithSSpecSeg:
                     setattr(self, k, v)
         start = time.perf_counter()
         a = self.args
-        self._val_on, self._val_step, self._val_monitor = validation_options(a.val_dir, a.val_fraction, a.val_seed, a.val_step, a.val_batch_size,
-                                                                             a.val_monitor)
+        self._val_on, self._val_step, self._val_monitor = validation_options(a.val_dir, a.val_fraction, a.val_seed, a.val_step, a.val_batch_size, a.val_monitor)
         ops.ema_decay_at(a.ema_decay, 0)                                       # checked before the data is listed
         self.length_dataset, dataset = datasetLoad(self)                       # SHM.py:904
         if self.G is None:
             self.build()                                                       # SHM.py:911-912, 930-931
         # data parallel: every rank trains on its own shard of the dataset (PolarDataset shards by rank) and holds the same
         # weights; files (summaries, checkpoints, log lines) are rank 0's business, the others wait at a barrier
-        rank0 = self._rank() == 0
+        rank0 = dist.rank() == 0
         if not rank0:
             print_fn = lambda *a, **k: None
         if rank0:
             self._write_summaries()                                            # SHM.py:914-919, 933-935
             os.makedirs(self.checkpoint_save_dir, exist_ok=True)
-        self._barrier()
+        dist.barrier()
         latest = self._restore_latest()                                        # SHM.py:949-951 (delete_old_checkpoints is False)
         if latest is not None:
             print_fn(f"Latest checkpoint restored!! ({latest})")
         if self._val_on:
-            self._resume_best()
+            self._best = checkpoint.best_to_beat(self._best, os.path.join(self.checkpoint_save_dir, self.BEST_CHECKPOINT), self._val_monitor,
+                                                 "ema" if self._ema_on() else "raw")
         # the loader's shuffle and augmentation draws are keyed by the pass number: a resumed run goes on from the pass its restored
         # step counter (the one telemetry uses) lies in instead of replaying pass 0's order and draws
         dataset.first_pass = self.D.P.iterations // max(len(dataset), 1)
@@ -848,7 +840,6 @@ class ShmGANwithSSpecSeg:
             raise
 
     def _train_loop(self, dataset, max_steps, print_fn, start):
-        import time
         iterator = iter(dataset)                                               # SHM.py:955
         batches_per_epoch = int(self.length_dataset / self.batch_size)         # SHM.py:957
         self.batch_step = 0
@@ -880,217 +871,35 @@ class ShmGANwithSSpecSeg:
                 torch.cuda.current_stream().synchronize()
                 print_fn("Time taken for epoch {} is {} min\n".format(self.epoch + 1, (time.perf_counter() - start) / 60))
             if self._val_on and (self.epoch + 1) % self._val_step == 0:        # held-out validation, in front of the checkpoint it may beat
-                self._validate_and_log(print_fn)
+                validation.validate_and_log(self, print_fn)
             if (self.epoch + 1) % self.checkpoint_save_step == 0:              # SHM.py:1125-1128
                 print_fn("Saving checkpoint for epoch {} at {}".format(self.epoch + 1, self._save_checkpoint()))
             if done:
                 break
         if self._val_on:                                                       # once at the end (unless these weights have just been scored)
-            self._validate_and_log(print_fn)
+            validation.validate_and_log(self, print_fn)
         print_fn("Saving checkpoint for epoch {} at {}".format(self.epoch + 1, self._save_checkpoint()))   # SHM.py:1133
         return self.batch_step
 
     def _write_summaries(self):
         """Generator / Discriminator / SpecSeg summaries into `log_dir` (SHM.py:914-919, 933-935; test.py:142-158)."""
-        import os
         os.makedirs(self.log_dir, exist_ok=True)
         for mdl, fn in ((self.G, "Generator_summary.txt"), (self.D, "Discriminator_summary.txt"), (self.SpecSeg, "SpecSeg_summary.txt")):
             with open(os.path.join(self.log_dir, fn), "w") as f:
                 mdl.summary(print_fn=lambda x: f.write(x + "\n"))
 
-    def _checkpoints(self):
-        import glob
-        import os
-        return sorted(glob.glob(os.path.join(self.checkpoint_save_dir, "ckpt-*.npz")),
-                      key=lambda p: int(os.path.basename(p)[5:-4]))
+    # ------------------------------------------------------------------ checkpoints and held-out validation
+    # functions of the trainer in checkpoint.py and validation.py, under the names the reference's scripts, bench.py and the tools use;
+    # every read of a checkpoint file goes through _read_npz
+    BEST_CHECKPOINT = checkpoint.BEST_CHECKPOINT
+    save_npz, _read_npz = checkpoint.save, checkpoint.read
+    _save_checkpoint, _restore_latest = checkpoint.save_numbered, checkpoint.restore_latest
+    validate = validation.validate
 
-    def _latest_checkpoint(self):
-        c = self._checkpoints()
-        return c[-1] if c else None
-
-    def _barrier(self):
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-            dist.barrier()
-
-    def _restore_latest(self):
-        """Load the newest checkpoint that reads back.  ONE rank decides: rank 0 reads every candidate completely (every array
-        decoded, i.e. CRC-checked, names and shapes checked against this trainer) WITHOUT touching any state, newest first,
-        skipping only files that are damaged as files (zipfile.BadZipFile / EOFError: a run killed mid-write by an older version,
-        a full disk); the chosen path (or None) is broadcast, every rank loads exactly that file, and the ranks then agree on a
-        success flag -- a rank that could not load what rank 0 chose ends the job (non-zero exit) instead of training on other
-        weights, Adam state and draw streams than its peers.  Anything else (EACCES, EIO, a checkpoint of another model
-        configuration or attention mode) is not a damaged file: rank 0 broadcasts the reason and EVERY rank raises it (round-4 advisor
-        finding: rank 0 used to raise in front of the broadcast and leave its peers waiting in it)."""
-        import zipfile
-        import torch.distributed as dist
-        multi = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
-        if self.G is None:
-            self.build()
-        chosen, payload, fatal = None, None, None
-        if self._rank() == 0:
-            try:
-                for path in reversed(self._checkpoints()):
-                    try:
-                        payload = self._read_npz(path)
-                        chosen = path
-                        break
-                    except (zipfile.BadZipFile, EOFError, ValueError) as e:
-                        # ValueError: np.load / json on an intact zip member with a damaged .npy header or state string -- a damaged file like
-                        # the other two.  _read_npz's own checks (names, shapes, attention mode) raise KeyError, which is not swallowed here
-                        print(f"checkpoint {path} is unreadable ({type(e).__name__}: {e}); trying the previous one")
-            except Exception as e:                      # not a damaged file: every rank must hear about it before rank 0 raises
-                fatal = e                                # (the others would sit in the broadcast until the collective times out)
-        if multi:
-            box = [chosen, None if fatal is None else repr(fatal)]
-            dist.broadcast_object_list(box, src=0)
-            chosen, why = box
-            if why is not None:
-                raise RuntimeError(f"rank {self._rank()}: rank 0 could not choose a checkpoint: {why}") from fatal
-        elif fatal is not None:
-            raise fatal
-        ok, err = 1, None
-        if chosen is not None:
-            try:
-                if payload is None:
-                    payload = self._read_npz(chosen)
-                self._apply_npz(*payload)
-            except Exception as e:                      # reported after the ranks have compared notes, never swallowed
-                ok, err = 0, e
-        if multi:
-            flag = torch.tensor([ok], dtype=torch.int32, device=self.device if dist.get_backend() == "nccl" else "cpu")
-            dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-            if int(flag.item()) == 0:
-                raise RuntimeError(f"rank {self._rank()}: the ranks disagree about checkpoint {chosen} (this rank: "
-                                   f"{'loaded' if ok else repr(err)}); refusing to train on diverged replicas") from err
-        elif err is not None:
-            raise err
-        return chosen
-
-    def _save_checkpoint(self, max_to_keep=3):
-        if self.telemetry is not None:
-            self.telemetry.flush()       # a log never trails a checkpoint
-        return self._save_checkpoint_file(max_to_keep)
-
-    def _save_checkpoint_file(self, max_to_keep=3):
-        """tf.train.CheckpointManager(ckpt, checkpoint_dir, max_to_keep=3).save() (SHM.py:944, 1127).  Rank 0 writes (to a
-        temporary name, then an atomic rename) and prunes; every rank leaves through a barrier, so nobody races ahead into a
-        collective while the file is still being written and nobody deletes a file another rank is about to open."""
-        import os
-        path = None
-        self._check_abort(sync=True)     # never write a checkpoint behind a step whose kernels gave up
-        if self._rank() == 0:
-            c = self._checkpoints()
-            n = int(os.path.basename(c[-1])[5:-4]) + 1 if c else 1
-            path = os.path.join(self.checkpoint_save_dir, f"ckpt-{n}.npz")
-            self._write_npz(path)
-            for old in (c + [path])[:-max_to_keep]:
-                os.remove(old)
-        self._barrier()
-        return path
-
-    def _write_npz(self, path):
-        """save_npz under a temporary name, flushed to disk, then an atomic rename: no half-written file ever has the final name."""
-        import os
-        tmp = path + ".tmp"
-        with open(tmp, "wb") as f:                 # a file object: np.savez would append ".npz" to a name
-            self.save_npz(f)
-            f.flush()
-            os.fsync(f.fileno())
-        os.replace(tmp, path)
-
-    # ------------------------------------------------------------------ held-out validation
-    BEST_CHECKPOINT = "best.npz"          # in checkpoint_save_dir; not a ckpt-*.npz, so neither pruned nor picked by _restore_latest
-
-    def validate(self, dataset=None, weights=("raw",)):
-        """Score the generator on held-out captures with test mode's protocol (evaluate.test): view 0 as the photo, the other views
-        zero, target label ED (infer without the cyclic passes), gen_rgb against the sample's ED image with ops.image_metrics.
-        dataset: a data.PolarDataset (default: the held-out loader of the trainer's val_dir / val_fraction options); only its full
-        batches are scored.  weights: the weight sets to score, each under generator_weights().  Per set every batch's rows go into one
-        [n,5] float64 device buffer; ONE device-to-host copy ends the pass and the means are taken in float64 on the host.
-        Returns {"n": images scored, "held_out": images listed, <set>: {"mse", "psnr", "ssim", "de76", "de94" (means), "rows" ([n,5])}}.
-        Reads no draw stream and writes nothing a training step relies on (its buffers are infer's and its own), so a run that
-        validates takes bitwise the steps of one that does not."""
-        if self.G is None:
-            self.build()
-        if dataset is None:
-            dataset = self.valDataset
-            if dataset is None:
-                from .data import validation_loader
-                a = self.args
-                cache_gb = a.cache_gb
-                dataset = self.valDataset = validation_loader(
-                    self.data_dir, self.image_size, self.batch_size, val_dir=a.val_dir, val_fraction=float(a.val_fraction or 0.0),
-                    val_seed=int(a.val_seed), val_batch_size=a.val_batch_size, device=self.device, diffuse_source=a.diffuse_source,
-                    cache=a.cache, cache_bytes=None if cache_gb is None else int(float(cache_gb) * 2 ** 30))
-            if dataset is None:
-                raise ValueError("validate: no held-out set (give a dataset, or set val_dir or val_fraction)")
-        for w in weights:
-            if w not in WEIGHT_SETS:
-                raise ValueError(f"validate: {w!r} is not one of {WEIGHT_SETS}")
-        B, nb = int(dataset.B), len(dataset)
-        n = nb * B
-        out = {"n": n, "held_out": int(dataset.n)}
-        rows = self.arena.get("val/rows", (max(n, 1), 5), torch.float64)
-        for w in weights:
-            with self.generator_weights(w):
-                for i, batch in enumerate(dataset):
-                    gen_rgb, _ = self.infer(batch[0], cyclic=False)
-                    ops.image_metrics(gen_rgb, batch[4], out=rows[i * B:(i + 1) * B], arena=self.arena)
-                host = rows[:n].cpu().numpy().astype(np.float64, copy=True)           # the pass's one device-to-host copy (it synchronises)
-            means = host.mean(axis=0) if n else np.full(5, np.nan)
-            out[w] = dict({k: float(v) for k, v in zip(ops.METRIC_NAMES, means)}, rows=host)
-        return out
-
-    def _validate_and_log(self, print_fn=print):
-        """One validation of train(): every rank scores the whole held-out set (raw weights, and the average with ema_decay on), rank 0
-        appends one line per weight set to <log_dir>/validation.jsonl, and when the monitored value -- val_monitor of the average
-        with ema_decay on, of the raw weights otherwise -- beats the best so far, rank 0 writes <checkpoint_save_dir>/best.npz.  The
-        step counts optimizer updates; weights that have been scored already (the end of a run right behind an epoch's validation) are
-        not scored again."""
-        import os
-        step = int(self.D.P.iterations)
-        if self._last_val_step == step:
-            return None
-        self._last_val_step = step
-        self._check_abort(sync=True)     # never score (or keep as the best) weights behind a step whose kernels gave up
-        sets = ("raw", "ema") if self._ema_on() else ("raw",)
-        res = self.validate(weights=sets)
-        monitored, mon = sets[-1], self._val_monitor
-        best_now = False
-        if res["n"]:
-            value = res[monitored][mon]
-            if improves(mon, value, None if self._best is None else self._best["value"]):
-                best_now = True
-                self._best = {"monitor": mon, "weights": monitored, "value": value, "step": step}
-        if self._rank() == 0:
-            os.makedirs(self.log_dir, exist_ok=True)
-            write_lines(os.path.join(self.log_dir, VALIDATION_FILE),
-                        [dict({"step": step, "epoch": int(self.epoch), "weights": w, "n": res["n"], "held_out": res["held_out"]},
-                              **{k: res[w][k] for k in ops.METRIC_NAMES}, best=bool(best_now and w == monitored)) for w in sets])
-            if best_now:
-                self._write_npz(os.path.join(self.checkpoint_save_dir, self.BEST_CHECKPOINT))
-            print_fn(f"Validation at step {step} ({res['n']} of {res['held_out']} held-out images): " +
-                     "; ".join(f"{w} {mon} {res[w][mon]:.6g}" for w in sets) + (" -- best so far, saved" if best_now else ""))
-        return res
-
-    def _resume_best(self):
-        """The best monitored value a resumed run has to beat: that of the restored checkpoint's trainer state and that of best.npz
-        itself (written before the checkpoint of its epoch, so it may be the newer of the two), whichever is better; one recorded
-        for another monitor or weight set does not count."""
-        import json
-        import os
-        want = (self._val_monitor, "ema" if self._ema_on() else "raw")
-        cands = [self._best]
-        path = os.path.join(self.checkpoint_save_dir, self.BEST_CHECKPOINT)
-        if os.path.exists(path):
-            with np.load(path) as z:
-                if "trainer/state" in z.files:
-                    cands.append(json.loads(str(z["trainer/state"])).get("best"))
-        self._best = None
-        for b in cands:
-            if b and (b.get("monitor"), b.get("weights")) == want and improves(want[0], b["value"], None if self._best is None else self._best["value"]):
-                self._best = dict(b)
+    def load_npz(self, path):
+        """Inverse of save_npz.  The file is read and validated as a whole first, so a damaged or mismatching file raises before any weight,
+        Adam moment or draw-stream state has been touched."""
+        checkpoint.apply(self, self._read_npz(path))
 
     # ------------------------------------------------------------------ inference (test.py:218-297)
     # arena names that hold one frame's worth of inference buffers (dropped when the frame shape changes, _frame_changed)
@@ -1103,8 +912,7 @@ class ShmGANwithSSpecSeg:
         metrics, and the image exporter's launch over the planes it was handed (evaluate.ImageExporter reads them on this
         stream into a buffer of its own, so nothing outlives the synchronise).  A run that stays at image_size x image_size
         never gets here with a changed shape: its buffers are allocated once, as before."""
-        last = getattr(self, "_inf_frame", None)
-        if last is not None and last != (H, W):
+        if self._inf_frame is not None and self._inf_frame != (H, W):
             torch.cuda.synchronize(self.device)
             for br in self.G.attn:                 # the branches' records hold the old frame's maps
                 br.ctx = None
@@ -1211,124 +1019,6 @@ class ShmGANwithSSpecSeg:
                 metrics = ops.image_metrics_hw(gen_rgb, win, t, out=out, arena=self.arena)
         return gen_rgb, cyc, metrics
 
-    # ------------------------------------------------------------------ weights interchange
-    def save_npz(self, path):
-        """Weights + IN betas + Adam state in a neutral .npz (Keras variable order and layouts)."""
-        d = {}
-        for name, M in (("G", self.G), ("D", self.D)):
-            for i, w in enumerate(M.get_weights()):
-                d[f"{name}/var{i:02d}"] = w
-            for i, b in enumerate(M.betas):
-                d[f"{name}/beta{i:02d}"] = b.cpu().numpy()
-            d[f"{name}/adam_m"] = M.P.m.cpu().numpy()
-            d[f"{name}/adam_v"] = M.P.v.cpu().numpy()
-            d[f"{name}/iterations"] = np.int64(M.P.iterations)
-        if self.SpecSeg is not None:
-            for i, w in enumerate(self.SpecSeg.get_weights()):
-                d[f"SpecSeg/var{i:02d}"] = w
-            opt = self.SpecSeg.optimizer_state()
-            if opt is not None:            # the mask network has been trained here: a resumed fit() continues from its Adam state
-                for k, v in opt.items():
-                    d[f"SpecSeg/{k}"] = v
-        # trainer state a resumed run continues from: the step-level draw streams (flags / TARGET_LABELS generator, the
-        # Philox counter of the noise and dropout kernels), the epoch, and which graph the variables belong to
-        import json
-        state = {"attention": self.attention, "epoch": int(self.epoch), "draw_count": int(self._draw_count),
-                 "rng": self._rng.bit_generator.state, "batch_step": int(getattr(self, "batch_step", 0))}
-        # only with their options on (a file written with them off has exactly the keys it always had): the average of the generator's
-        # weights as its flat buffer, like G/adam_m, with its update count; and the best held-out value so far, so that a resumed run
-        # does not replace a better best.npz with a worse one
-        if self._ema_on():
-            d["G/ema"] = self._ensure_ema().cpu().numpy()
-            d["G/ema_updates"] = np.int64(self.G.P.ema_updates)
-        if self._val_on:
-            state["best"] = self._best
-        d["trainer/state"] = np.array(json.dumps(state))
-        np.savez(path, **d)
-
-    def _read_npz(self, path):
-        """Read and validate a save_npz file completely without mutating anything: every array this trainer's models need is
-        decoded (zipfile checks the CRC of each member as it is read) and shape-checked.  Returns (arrays, trainer state)."""
-        import json
-        if self.G is None:
-            self.build()
-        with np.load(path) as z:
-            state = None
-            if "trainer/state" in z.files:
-                state = json.loads(str(z["trainer/state"]))
-                if state["attention"] != self.attention:
-                    raise KeyError(f"checkpoint {path} holds an attention='{state['attention']}' model, this trainer was built with "
-                                   f"attention='{self.attention}' (the live branch adds 20 + 4 variables)")
-            arrays = {}
-            for name, M in (("G", self.G), ("D", self.D)):
-                for i, shape in enumerate(M.P.shapes[:len(M.P.vars)]):
-                    a = z[f"{name}/var{i:02d}"]
-                    if tuple(a.shape) != tuple(shape):
-                        raise KeyError(f"checkpoint {path}: {name}/var{i:02d} has shape {tuple(a.shape)}, this model's is {tuple(shape)}")
-                    arrays[f"{name}/var{i:02d}"] = a
-                for i in range(len(M.betas)):
-                    arrays[f"{name}/beta{i:02d}"] = z[f"{name}/beta{i:02d}"]
-                for k in ("adam_m", "adam_v"):
-                    a = z[f"{name}/{k}"]
-                    if a.size != M.P.m.numel():
-                        raise KeyError(f"checkpoint {path}: {name}/{k} has {a.size} elements, this model's flat buffer {M.P.m.numel()}")
-                    arrays[f"{name}/{k}"] = a
-                arrays[f"{name}/iterations"] = z[f"{name}/iterations"]
-            if "G/ema" in z.files:                        # written with ema_decay on
-                a = z["G/ema"]
-                if a.size != self.G.P.n:
-                    raise KeyError(f"checkpoint {path}: G/ema has {a.size} elements, this model's flat buffer {self.G.P.n}")
-                arrays["G/ema"] = a
-                arrays["G/ema_updates"] = z["G/ema_updates"]
-            if "SpecSeg/var00" in z.files:
-                if self.SpecSeg is None:
-                    self.SpecSeg = self.build_specseg()
-                for i in range(len(self.SpecSeg.vars)):
-                    arrays[f"SpecSeg/var{i:02d}"] = z[f"SpecSeg/var{i:02d}"]
-                if "SpecSeg/adam_m" in z.files:           # absent in files written before the mask network could be trained
-                    for k in ("adam_m", "adam_v"):
-                        a = z[f"SpecSeg/{k}"]
-                        if a.size != self.SpecSeg.n:
-                            raise KeyError(f"checkpoint {path}: SpecSeg/{k} has {a.size} elements, the network's flat buffer {self.SpecSeg.n}")
-                        arrays[f"SpecSeg/{k}"] = a
-                    arrays["SpecSeg/iterations"] = z["SpecSeg/iterations"]
-                    arrays["SpecSeg/train_state"] = z["SpecSeg/train_state"]
-        return arrays, state
-
-    def _apply_npz(self, z, state):
-        for name, M in (("G", self.G), ("D", self.D)):
-            M.set_weights([z[f"{name}/var{i:02d}"] for i in range(len(M.P.vars))])
-            M.set_betas([z[f"{name}/beta{i:02d}"] for i in range(len(M.betas))])
-            M.P.m.copy_(torch.from_numpy(z[f"{name}/adam_m"]))
-            M.P.v.copy_(torch.from_numpy(z[f"{name}/adam_v"]))
-            M.P.iterations = int(z[f"{name}/iterations"])
-        # the average: taken from the file by a trainer that keeps one (ema_decay on) or is to evaluate with one (eval_weights "ema");
-        # a file without one leaves a trainer with ema_decay on with average = the loaded weights and the counter at 0; a trainer with
-        # neither option ignores the keys
-        P = self.G.P
-        self._loaded_ema = "G/ema" in z
-        P.ema = None
-        if self._loaded_ema and (self._ema_on() or self.args.eval_weights == "ema"):
-            P.ema = torch.empty_like(P.flat)
-            P.ema.copy_(torch.from_numpy(np.ascontiguousarray(z["G/ema"], dtype=np.float32).reshape(-1)))
-            P.ema_updates = int(z["G/ema_updates"])
-        elif self._ema_on():
-            self._ensure_ema()
-        if "SpecSeg/var00" in z:
-            self.SpecSeg.set_weights([z[f"SpecSeg/var{i:02d}"] for i in range(len(self.SpecSeg.vars))])
-        if "SpecSeg/adam_m" in z:
-            self.SpecSeg.set_optimizer_state(z["SpecSeg/adam_m"], z["SpecSeg/adam_v"], z["SpecSeg/iterations"], z["SpecSeg/train_state"])
-        if state is not None:            # continue the draw streams instead of replaying the first run's opening steps
-            self.epoch = int(state["epoch"])
-            self._draw_count = int(state["draw_count"])
-            self._rng.bit_generator.state = state["rng"]
-            self._best = state.get("best")           # present when the run that wrote the file validated (train() checks it: _resume_best)
-
-    def load_npz(self, path):
-        """Inverse of save_npz.  The file is read and validated as a whole first (`_read_npz`), so a damaged or mismatching
-        file raises before any weight, Adam moment or draw-stream state has been touched."""
-        self._apply_npz(*self._read_npz(path))
-
     def _img_ws(self, B):
         n = ops.image_losses_workspace(B, self.image_size)
         return self.arena.get("loss/ws", ((n + 3) // 4,))
@@ -1347,7 +1037,7 @@ class ShmGANwithSSpecSeg:
 
     def __getattr__(self, name):
         # reference attribute names for the loss scalars (self.total_Generator_loss, ...)
-        if name in LOSS_NAMES and self.__dict__.get("_last") is not None:
+        if name in LOSS_NAMES and self._last is not None:
             return self.losses()[name]
         raise AttributeError(name)
 

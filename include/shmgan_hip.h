@@ -542,6 +542,41 @@ size_t shm_image_metrics_hw_workspace(int batch, int h, int w);
 int shm_image_metrics_hw(const float* pred, int hp, int wp, int top, int left, const float* target, int h, int w, double* out,
                          void* ws, size_t ws_bytes, int batch, void* stream);
 
+/* ---- the same metrics split by a region (the highlight, and everything else) ----------------------------------------
+ * shm_highlight_region_hw: one launch writes region [batch,h,w] (uint8, 0 or 1) for the window (top, left, h, w) of a frame.
+ *   SHM_REGION_RESIDUAL  src [batch,hp,wp,3] fp32 (the photo fed to the generator: the padded frame, pitch and window as pred
+ *                        below), target tight [batch,h,w,3] fp32: region = max_c(src_c - target_c) > tau, the subtraction in
+ *                        fp32 first, the maximum over the channels after (specular residue is additive and positive); plane unused
+ *   SHM_REGION_PLANE     plane [batch,hp,wp] fp32 (the SpecSeg output of the inference): region = plane > tau on the window;
+ *                        src and target unused
+ * The comparison is strict and a NaN is outside (RESIDUAL: a NaN difference in any channel).  Nothing outside the window is
+ * read.  SHM_E_SHAPE before any launch for a null pointer among the ones the mode uses, an unknown mode, batch < 1, a window
+ * outside the frame or a window side outside [1, 32768]. */
+#define SHM_REGION_RESIDUAL 0
+#define SHM_REGION_PLANE 1
+int shm_highlight_region_hw(int mode, const float* src, const float* target, const float* plane, int hp, int wp, int top, int left,
+                            int h, int w, float tau, unsigned char* region, int batch, void* stream);
+/* shm_image_metrics_hw split by region (uint8 [batch,h,w] over the window; any non-zero byte is inside).  Per image b,
+ * out[b][0..SHM_REGION_METRICS-1] (f64):
+ *   0..4   {mse, psnr, ssim, de76, de94} over the pixels with region != 0 ("in")
+ *   5..9   the same over the pixels with region == 0 ("out")
+ *   10     n_in, the window's pixels inside; 11: p_in, the SSIM positions inside (exact integers)
+ * For a set R of n_R pixels: mse_R = sum over R and the 3 channels of (pred - target)^2 / (3 n_R); psnr_R = -10 log10(mse_R),
+ * +inf at 0; de76_R / de94_R = means over R, Lab and dE as above.  The SSIM map is the one shm_image_metrics_hw averages
+ * (rescale_01 with the min / max of the WHOLE window, 11-tap gaussian, VALID, (h-10)(w-10) positions per channel); position
+ * (i, j) belongs to R when its centre pixel (i+5, j+5) of the window does, and ssim_R is the mean over those positions and the
+ * 3 channels.  An empty set (no pixels; for ssim no positions) gives NaN.  So n_in mse_in + n_out mse_out = h w mse, the same
+ * for de76 and de94, and p_in ssim_in + p_out ssim_out = (h-10)(w-10) ssim of shm_image_metrics_hw.
+ * The same three kernels, grids and fixed-order reduction as shm_image_metrics_hw with a second set of accumulators:
+ * deterministic and batch-invariant, and with region all ones out[b][0..4] is bit for bit shm_image_metrics_hw's result
+ * (all zeros: out[b][5..9]).  ws: shm_image_metrics_region_hw_workspace(batch, h, w) bytes, no initial contents.  SHM_E_SHAPE
+ * for a window side < 11, a window outside the frame, batch < 1 or a null pointer, SHM_E_WORKSPACE for a short workspace, all
+ * before any launch. */
+#define SHM_REGION_METRICS 12
+size_t shm_image_metrics_region_hw_workspace(int batch, int h, int w);
+int shm_image_metrics_region_hw(const float* pred, int hp, int wp, int top, int left, const float* target, int h, int w,
+                                const unsigned char* region, double* out, void* ws, size_t ws_bytes, int batch, void* stream);
+
 /* ---- SpecSeg mask network, inference only (SpecSeg.py:27-98; SpecSeg.predict at SHM.py:492) --
  * Its Conv2D(3x3, relu) layers are shm_conv2d_fwd with slope 0.  The rest: */
 /* dst[p, 0:nc] = src[p, c0:c0+nc], dst[p, nc:lddst] = 0 (the Y plane into a 16-float pitch). */

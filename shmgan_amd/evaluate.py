@@ -38,6 +38,15 @@ refused with ValueError, before anything is allocated or launched for it, when a
 MAX_TENSOR_BYTES or MAX_FRAME_SIDE, or when native_frame_bytes() of its frame does not fit the free device memory
 (MEMORY_HEADROOM); the message names the file and points to eval_size="model".  InstanceNorm statistics are per whole image,
 so a frame is never tiled.
+
+Region metrics (`metrics_region`: "off", the default, "residual" or "specseg"; needs `calc_metrics`): the five metrics once more, split
+by the highlight -- "residual": where the photo exceeds its diffuse partner by more than `region_threshold` in any channel (default
+16/255, the 16-byte-unit noise floor); "specseg": where the inference's SpecSeg mask exceeds it (default 0.5) -- into the pixels inside
+and the ones outside (include/shmgan_hip.h, shm_image_metrics_region_hw, states the definitions; trainer.eval_region runs it).  The
+returned dict gains "region": per-image lists "in_mse" ... "out_de94" (ops.REGION_METRIC_NAMES; NaN where an image has no such pixels)
+and "fraction" (the part of the photo inside), "means" (per value, over the images whose set is not empty), "n_in_images" and
+"n_out_images"; a second table is printed behind the reference's two, and `<result_dir>/region_metrics.jsonl` gets one line per image:
+{"image": source stem, "fraction", the ten values}, NaN written as null.  Works at both eval sizes; "Time" then includes it.
 """
 from __future__ import annotations
 
@@ -53,6 +62,7 @@ from . import ops
 from .data import EvalDataset, NativeEvalDataset, pad_geometry
 from .model import generator_layers, pad_channels
 from .specseg import WIDTHS as SPECSEG_WIDTHS
+from .telemetry import nan_to_none, region_means, region_options, write_lines
 
 TABLE_HEADERS = ["Image#", "Time", "MSE", "SSIM", "PSNR", "delE76", "delE94"]                  # test.py:371
 MEAN_HEADERS = ["Mean MSE", "Mean SSIM", "Mean PSNR", "Mean dleE76", "Mean delE94"]           # test.py:381 (sic)
@@ -72,6 +82,8 @@ EVAL_SIZES = ("model", "native")
 # A module attribute on purpose: tests lower it instead of allocating a huge image.
 MAX_TENSOR_BYTES = 0xfffffff0
 MAX_FRAME_SIDE = 32768                                        # shm_load_pad_u8, shm_image_metrics_hw, shm_export_u8_hw: sides in [1, 32768]
+REGION_FILE = "region_metrics.jsonl"
+REGION_HEADERS = ["Image#", "Inside"] + [f"{side} {k}" for side in ("in", "out") for k in ("MSE", "PSNR", "SSIM", "delE76", "delE94")]
 MEMORY_HEADROOM = 0.9                                         # fraction of the free device memory a frame's buffers may take
 
 
@@ -351,7 +363,8 @@ def test(shmgan, args, *, print_fn=print):
     and folder settings come from the trainer (`image_size`, `checkpoint_save_dir`, `log_dir`, `result_dir`).  Returns a
     dict: "index" (1-based image numbers), "time" (seconds per image), "images" and "files" (the exported image paths, in
     batch order; empty without save_images); with calc_metrics also the per-image lists "MSE", "SSIM", "PSNR", "delE76",
-    "delE94" and "means" (a dict of their means, None without metrics)."""
+    "delE94" and "means" (a dict of their means, None without metrics).  args.metrics_region / args.region_threshold (module docstring;
+    default "off") add "region", a further table behind the two and region_metrics.jsonl, and nothing when off."""
     test_dir = _arg(shmgan, args, "test_dir", "")
     calc = bool(_arg(shmgan, args, "calc_metrics", False))
     diffuse_dir = _arg(shmgan, args, "diffuse_dir", "") if calc else None
@@ -370,6 +383,9 @@ def test(shmgan, args, *, print_fn=print):
         raise ValueError("calc_metrics needs args.diffuse_dir (the ground-truth diffuse images)")
     tags = image_options(_arg(shmgan, args, "save_images", False), _arg(shmgan, args, "image_values", "rescale"),
                          _arg(shmgan, args, "image_out_size", "source"))
+    region = region_options(_arg(shmgan, args, "metrics_region", "off"), _arg(shmgan, args, "region_threshold", None), "metrics_region")
+    if region is not None and not calc:
+        raise ValueError(f"metrics_region={region[0]!r} splits the image metrics: it needs calc_metrics (and diffuse_dir)")
     shmgan.random_flip, shmgan.TARGET_LABELS = 0.0, 1.0                        # test.py:65-67
     cyclic = not native or len(tags) > 1                                       # native: the cyclic images are only ever exported
 
@@ -403,8 +419,12 @@ def test(shmgan, args, *, print_fn=print):
                                  "native" if native else _arg(shmgan, args, "image_out_size", "source"), shmgan.device)
     index, times, rows = [], [], []
     cols = {k: [] for k in METRIC_KEYS}
+    region_rows, region_size, stems = [], [], []      # per image: the 12 region values, (pixels, SSIM positions) of its window, source stem
     stream = torch.cuda.current_stream()
+    eval_region_before = shmgan.eval_region
     try:
+        if region is not None:
+            shmgan.eval_region = region
         with shmgan.generator_weights(eval_weights):     # "raw": nothing; "ema": the whole loop runs on the average
             for bi, item in enumerate(dataset):
                 rgb, diffuse, window = item if native else (*item, None)
@@ -412,6 +432,11 @@ def test(shmgan, args, *, print_fn=print):
                 t0 = time.perf_counter()
                 gen_rgb, cyc, m = shmgan.evaluate_frame(rgb, diffuse, window, cyclic) if native else shmgan.evaluate(rgb, diffuse)
                 m = None if m is None else m.cpu().tolist()  # a synchronising copy (without metrics: the synchronize below)
+                if region is not None:
+                    region_rows.extend(shmgan.region_metrics.cpu().tolist())
+                    h, w = window[2:] if native else gen_rgb.shape[1:3]
+                    region_size.extend([(int(h) * int(w), (int(h) - 10) * (int(w) - 10))] * rgb.shape[0])
+                    stems.extend(source_stem(path) for path, _ in dataset.sources(bi))
                 stream.synchronize()
                 n = rgb.shape[0]
                 dt = (time.perf_counter() - t0) / n
@@ -428,6 +453,7 @@ def test(shmgan, args, *, print_fn=print):
                                      cols["delE94"][-1]])
         files = exporter.finish() if exporter is not None else []
     finally:
+        shmgan.eval_region = eval_region_before
         if exporter is not None:
             exporter.pool.shutdown(wait=True)       # also after an error: no writer outlives test()
 
@@ -446,4 +472,27 @@ def test(shmgan, args, *, print_fn=print):
     for name, key in (("SSIM.txt", "SSIM"), ("MSE.txt", "MSE"), ("PSNR.txt", "PSNR")):      # test.py:385-392
         with open(os.path.join(shmgan.result_dir, name), "wb+") as f:
             pickle.dump(cols[key], f)
+    if region is not None:
+        out["region"] = _report_regions(shmgan, index, stems, region_rows, region_size, print_fn)
     return out
+
+
+def _report_regions(shmgan, index, stems, rows, sizes, print_fn):
+    """The "region" entry of test()'s result from the per-image rows (ops.REGION_METRIC_NAMES) and (pixels, SSIM positions) of each
+    window; prints its table and writes <result_dir>/region_metrics.jsonl (module docstring)."""
+    names = ops.REGION_METRIC_NAMES[:10]
+    npix, npos = [a for a, _ in sizes], [b for _, b in sizes]
+    means, n_in_images, n_out_images = region_means(rows, npix, npos) if rows else ({k: float("nan") for k in names}, 0, 0)
+    res = {k: [float(r[j]) for r in rows] for j, k in enumerate(names)}
+    res["fraction"] = [float(r[10]) / n for r, n in zip(rows, npix)]
+    res.update(means=means, n_in_images=n_in_images, n_out_images=n_out_images)
+    print_fn(" --- PRINTING METRICS INSIDE / OUTSIDE THE HIGHLIGHT --- ")
+    print_fn(format_table([[i, f] + [float(v) for v in r[:10]] for i, f, r in zip(index, res["fraction"], rows)] +
+                          [["mean", sum(res["fraction"]) / len(rows) if rows else float("nan")] + [means[k] for k in names]], REGION_HEADERS))
+    print_fn("\n\n")
+    path = os.path.join(shmgan.result_dir, REGION_FILE)
+    if os.path.exists(path):
+        os.remove(path)                             # one file per run (write_lines appends)
+    write_lines(path, [dict({"image": stem, "fraction": f}, **{k: nan_to_none(float(r[j])) for j, k in enumerate(names)})
+                       for stem, f, r in zip(stems, res["fraction"], rows)])
+    return res

@@ -627,6 +627,85 @@ def image_metrics_hw(pred, window, target, out=None, arena=None):
     return out
 
 
+# ---- the metrics split by a region: the highlight and everything else (shm_highlight_region_hw / shm_image_metrics_region_hw) ----
+REGION_MODES = {"residual": CONSTANTS["SHM_REGION_RESIDUAL"], "plane": CONSTANTS["SHM_REGION_PLANE"]}
+REGION_METRICS = CONSTANTS["SHM_REGION_METRICS"]
+# the columns of image_metrics_region's result: the five inside, the five outside, the pixels and the SSIM positions inside
+REGION_METRIC_NAMES = tuple(f"{side}_{k}" for side in ("in", "out") for k in METRIC_NAMES) + ("n_in", "p_in")
+assert len(REGION_METRIC_NAMES) == REGION_METRICS
+
+
+def highlight_region(mode, window, *, src=None, target=None, plane=None, tau, out=None):
+    """The highlight of a window as a uint8 [B,h,w] device tensor of 0 / 1 (shm_highlight_region_hw, one launch, asynchronous on the
+    current stream).  window = (top, left, h, w) inside the frame.  mode "residual": src float32 [B,Hp,Wp,3] (the photo fed to the
+    generator, the padded frame) and target tight float32 [B,h,w,3]: max_c(src_c - target_c) > tau; mode "plane": plane float32
+    [B,Hp,Wp] or [B,Hp,Wp,1] (the SpecSeg output): plane > tau.  Strict comparison; a NaN is outside.  Returns `out` (allocated when
+    not given)."""
+    if mode not in REGION_MODES:
+        raise ValueError(f"highlight_region: mode {mode!r} is not one of {tuple(REGION_MODES)}")
+    top, left, h, w = (int(v) for v in window)
+    if mode == "residual":
+        if src is None or target is None or plane is not None:
+            raise ValueError("highlight_region: mode 'residual' takes src and target, and no plane")
+        if src.dtype != torch.float32 or target.dtype != torch.float32:
+            raise TypeError(f"highlight_region takes float32 images, got {src.dtype} / {target.dtype}")
+        if src.dim() != 4 or src.shape[-1] != 3 or tuple(target.shape) != (src.shape[0], h, w, 3):
+            raise ValueError(f"highlight_region takes src [B,Hp,Wp,3] and target [B,{h},{w},3], got {tuple(src.shape)} / {tuple(target.shape)}")
+        if not (src.is_contiguous() and target.is_contiguous()):
+            raise ValueError("highlight_region takes contiguous NHWC images")
+        frame = src
+    else:
+        if plane is None or src is not None or target is not None:
+            raise ValueError("highlight_region: mode 'plane' takes plane, and neither src nor target")
+        if plane.dtype != torch.float32:
+            raise TypeError(f"highlight_region takes a float32 plane, got {plane.dtype}")
+        if plane.dim() not in (3, 4) or (plane.dim() == 4 and plane.shape[-1] != 1):
+            raise ValueError(f"highlight_region takes plane [B,Hp,Wp] or [B,Hp,Wp,1], got {tuple(plane.shape)}")
+        if not plane.is_contiguous():
+            raise ValueError("highlight_region takes a contiguous plane")
+        frame = plane
+    B, hp, wp = int(frame.shape[0]), int(frame.shape[1]), int(frame.shape[2])
+    if out is None:
+        out = torch.empty((B, max(h, 0), max(w, 0)), dtype=torch.uint8, device=frame.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (B, h, w) or not out.is_contiguous():
+        raise ValueError(f"highlight_region: out must be a contiguous uint8 [{B},{h},{w}] tensor")
+    check(lib().shm_highlight_region_hw(REGION_MODES[mode], _p(src), _p(target), _p(plane), hp, wp, top, left, h, w, float(tau), _p(out), B,
+                                        _stream()), "shm_highlight_region_hw")
+    return out
+
+
+def image_metrics_region_workspace(batch, h, w):
+    return int(lib().shm_image_metrics_region_hw_workspace(batch, h, w))
+
+
+def image_metrics_region(pred, window, target, region, out=None, arena=None):
+    """image_metrics_hw split by `region` (uint8 [B,h,w] over the window, non-zero = inside; shm_image_metrics_region_hw): pred float32
+    [B,Hp,Wp,3], window = (top, left, h, w), target tight float32 [B,h,w,3].  Returns `out`, a float64 [B,12] device tensor
+    (REGION_METRIC_NAMES: the five metrics inside, the five outside, n_in, p_in; an empty set gives NaN), filled asynchronously on the
+    current stream.  Workspace rule and ordering as image_metrics (its own arena buffer: both calls may be queued on one stream)."""
+    top, left, h, w = (int(v) for v in window)
+    if pred.dtype != torch.float32 or target.dtype != torch.float32:
+        raise TypeError(f"image_metrics_region takes float32 images, got {pred.dtype} / {target.dtype}")
+    if region.dtype != torch.uint8:
+        raise TypeError(f"image_metrics_region takes a uint8 region, got {region.dtype}")
+    if pred.dim() != 4 or pred.shape[-1] != 3 or tuple(target.shape) != (pred.shape[0], h, w, 3) or tuple(region.shape) != (pred.shape[0], h, w):
+        raise ValueError(f"image_metrics_region takes pred [B,Hp,Wp,3], target [B,{h},{w},3] and region [B,{h},{w}], got {tuple(pred.shape)} / "
+                         f"{tuple(target.shape)} / {tuple(region.shape)}")
+    if not (pred.is_contiguous() and target.is_contiguous() and region.is_contiguous()):
+        raise ValueError("image_metrics_region takes contiguous NHWC images and a contiguous region")
+    B, hp, wp = int(pred.shape[0]), int(pred.shape[1]), int(pred.shape[2])
+    if out is None:
+        out = torch.empty((B, REGION_METRICS), dtype=torch.float64, device=pred.device)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (B, REGION_METRICS) or not out.is_contiguous():
+        raise ValueError(f"image_metrics_region: out must be a contiguous float64 [{B},{REGION_METRICS}] tensor")
+    if arena is None:
+        arena = _default_arena(pred.device)
+    ws = arena.get("metrics/region_ws", (max(image_metrics_region_workspace(B, h, w), 1),), torch.uint8)
+    check(lib().shm_image_metrics_region_hw(_p(pred), hp, wp, top, left, _p(target), h, w, _p(region), _p(out), _p(ws), ws.numel(), B,
+                                            _stream()), "shm_image_metrics_region_hw")
+    return out
+
+
 # ---- training telemetry (shm_tensor_stats / shm_loss_ring_put, include/shmgan_hip.h) ---------------------------------------
 TSTAT_NAMES = ["finite", "nan", "inf", "min", "max", "sum", "sumsq", "clipped"]     # SHM_TSTAT_* order
 TSTAT_N, THIST_BINS, THIST_EMIN, TSTAT_MAX_SEGS = (CONSTANTS["SHM_" + k] for k in ("TSTAT_N", "THIST_BINS", "THIST_EMIN", "TSTAT_MAX_SEGS"))

@@ -134,20 +134,46 @@ def read_log(log_dir):
 VALIDATION_FILE = "validation.jsonl"
 # what `val_monitor` may name (the columns of ops.image_metrics) and the sign that makes a larger value the better one
 VAL_MONITORS = {"mse": -1.0, "psnr": 1.0, "ssim": 1.0, "de76": -1.0, "de94": -1.0}
+# with a region (val_region / metrics_region): where the highlight comes from, each source's default threshold -- 16/255 is the project's
+# 16-byte-unit noise floor of photo - diffuse, 0.5 the middle of SpecSeg's sigmoid -- and what val_monitor may then name as well: a
+# metric inside ("in_") or outside ("out_") the highlight, judged by that metric's own sign
+REGION_SOURCES = ("off", "residual", "specseg")
+REGION_THRESHOLDS = {"residual": 16.0 / 255.0, "specseg": 0.5}
+REGION_MONITORS = {f"{side}_{k}": sign for side in ("in", "out") for k, sign in VAL_MONITORS.items()}
 WEIGHT_SETS = ("raw", "ema")                               # the generator weights one can infer with (trainer.generator_weights)
 
 
-def validation_options(val_dir="", val_fraction=0.0, val_seed=0, val_step=1, val_batch_size=None, val_monitor="psnr"):
+def region_options(source="off", threshold=None, name="metrics_region"):
+    """The option pair `name` / `<name>_threshold` (test mode's metrics_region, validation's val_region), checked: None when off, else
+    (source, threshold) with the source's default threshold (REGION_THRESHOLDS) when none is given.  An unknown source and a threshold
+    that is not a finite number raise ValueError naming the option."""
+    source = "off" if source in (None, False, "") else source
+    if source not in REGION_SOURCES:
+        raise ValueError(f"{name} {source!r} is not one of {REGION_SOURCES}")
+    if source == "off":
+        return None
+    if threshold is None:
+        return source, REGION_THRESHOLDS[source]
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)) or not np.isfinite(threshold):
+        raise ValueError(f"{name}_threshold {threshold!r} is not a finite number")
+    return source, float(threshold)
+
+
+def validation_options(val_dir="", val_fraction=0.0, val_seed=0, val_step=1, val_batch_size=None, val_monitor="psnr", val_region="off"):
     """The held-out validation options of train(), checked: (on, val_step, val_monitor).  `on` is whether a held-out set was asked for
     (val_dir or val_fraction; both together raise ValueError).  An unknown val_monitor, a val_step below 1, a val_batch_size below 1 and
-    a val_fraction outside [0, 1) raise ValueError whether validation is on or not."""
+    a val_fraction outside [0, 1) raise ValueError whether validation is on or not.  With val_region on (region_options checks it),
+    val_monitor may also name one of REGION_MONITORS ("in_psnr", ...)."""
     val_fraction = float(val_fraction or 0.0)
     if val_dir and val_fraction:
         raise ValueError(f"val_dir ({val_dir!r}) and val_fraction ({val_fraction}) are two sources of one held-out set: give one of them")
     if not 0.0 <= val_fraction < 1.0:
         raise ValueError(f"val_fraction {val_fraction!r} is not a fraction in [0, 1)")
-    if val_monitor not in VAL_MONITORS:
-        raise ValueError(f"val_monitor {val_monitor!r} is not one of {tuple(VAL_MONITORS)}")
+    region_on = region_options(val_region, None, "val_region") is not None
+    if val_monitor not in VAL_MONITORS and not (region_on and val_monitor in REGION_MONITORS):
+        if val_monitor in REGION_MONITORS:
+            raise ValueError(f"val_monitor {val_monitor!r} needs val_region ('residual' or 'specseg'): the region metrics are off")
+        raise ValueError(f"val_monitor {val_monitor!r} is not one of {tuple(VAL_MONITORS) + (tuple(REGION_MONITORS) if region_on else ())}")
     if isinstance(val_step, bool) or not isinstance(val_step, (int, np.integer)) or val_step < 1:
         raise ValueError(f"val_step {val_step!r} is not a number of epochs (at least 1)")
     if val_batch_size is not None and (isinstance(val_batch_size, bool) or not isinstance(val_batch_size, (int, np.integer)) or val_batch_size < 1):
@@ -157,11 +183,34 @@ def validation_options(val_dir="", val_fraction=0.0, val_seed=0, val_step=1, val
 
 
 def improves(monitor, value, best):
-    """Whether `value` of metric `monitor` beats `best` (None: nothing to beat).  psnr and ssim are maximised, the others minimised; a
-    NaN never improves."""
+    """Whether `value` of metric `monitor` beats `best` (None: nothing to beat).  psnr and ssim are maximised, the others minimised, inside
+    or outside a region ("in_psnr", "out_de94") as over the whole image; a NaN (a region metric's mean when no image had the set) never
+    improves."""
     if value != value:
         return False
-    return best is None or VAL_MONITORS[monitor] * (value - best) > 0.0
+    sign = VAL_MONITORS[monitor] if monitor in VAL_MONITORS else REGION_MONITORS[monitor]
+    return best is None or sign * (value - best) > 0.0
+
+
+def region_means(rows, npix, npos):
+    """Host side of the region metrics: rows [n,12] (ops.REGION_METRIC_NAMES per image), npix / npos the window's pixels and SSIM
+    positions (one number, or one per image).  Returns (means, n_in_images, n_out_images): for each of the ten in_* / out_* values the
+    float64 mean over the images whose set is not empty -- pixels for mse, psnr and the dE values, SSIM positions for ssim -- NaN when no
+    image has it, and the number of images with pixels inside / outside."""
+    rows = np.asarray(rows, np.float64).reshape(-1, ops.REGION_METRICS)
+    n_in, p_in = rows[:, 10], rows[:, 11]
+    counts = ((n_in, p_in), (np.asarray(npix, np.float64) - n_in, np.asarray(npos, np.float64) - p_in))
+    means = {}
+    for s, (pixels, positions) in enumerate(counts):
+        for j, k in enumerate(ops.METRIC_NAMES):
+            v = rows[(positions if k == "ssim" else pixels) > 0, 5 * s + j]
+            means[ops.REGION_METRIC_NAMES[5 * s + j]] = float(v.mean()) if v.size else float("nan")
+    return means, int((counts[0][0] > 0).sum()), int((counts[1][0] > 0).sum())
+
+
+def nan_to_none(v):
+    """A float for a JSON line: NaN becomes None (null), everything else stays."""
+    return None if isinstance(v, float) and v != v else v
 
 
 def read_validation(log_dir):

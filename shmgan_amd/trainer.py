@@ -32,7 +32,7 @@ from .data import Augment, MaskDataset, datasetLoad, gib_to_bytes
 from .dist import GradReducer, exchange_active, world_size
 from .model import Arena, Discriminator, Generator, WgradLane, pad_channels
 from .specseg import SpecSeg
-from .telemetry import LOSS_NAMES, WEIGHT_SETS, NonFiniteGradientError, Telemetry, compose_losses, telemetry_options, validation_options  # noqa: F401
+from .telemetry import LOSS_NAMES, WEIGHT_SETS, NonFiniteGradientError, Telemetry, compose_losses, region_options, telemetry_options, validation_options  # noqa: F401
 
 
 class _Optimizer:
@@ -67,6 +67,7 @@ _DEFAULTS = dict(image_size=128, batch_size=1, filter_size=64, g_lr=0.00002, d_l
                  specseg_shuffle=False, specseg_data_seed=0, specseg_val_fraction=0.0, specseg_cache_gb=None,
                  ema_decay=0.0, ema_warmup=True,
                  val_dir="", val_fraction=0.0, val_seed=0, val_step=1, val_batch_size=None, val_monitor="psnr",
+                 val_region="off", val_region_threshold=None, metrics_region="off", region_threshold=None,
                  eval_weights="raw", eval_checkpoint="latest")
 
 SPECSEG_MASK_SOURCES = ("dir", "polar")                   # where train_specseg's masks come from
@@ -150,9 +151,14 @@ class ShmGANwithSSpecSeg:
         # loaded held an average of the generator's weights
         self.valDataset, self._val_on, self._best, self._last_val_step, self._loaded_ema = None, False, None, None, False
         # train(): the validation options, this rank's dataset length, train_step calls so far, the per-step flip draw (inert, SHM.py:983)
+        self._val_region = None          # train()'s val_region / val_region_threshold, checked: None or (source, threshold)
         self._val_step, self._val_monitor, self.length_dataset, self.batch_step, self.random_flip = None, None, 0, 0, 0.0
         # the last train_step's loss vectors and inputs (losses()), the frame (H, W) of the last infer(), _stats_now's Telemetry without files
         self._last = self._inf_frame = self._adhoc_telemetry = None
+        # evaluate_frame's split of the metrics by the highlight (off by default): None, ("residual", tau) = photo - diffuse above tau, or
+        # ("specseg", tau) = the inference's SpecSeg mask above tau; with it on and a diffuse target given, evaluate_frame leaves the region
+        # (uint8 [B,h,w]) and the split metrics (float64 [B,12], ops.REGION_METRIC_NAMES) of its last call here
+        self.eval_region = self.highlight_region = self.region_metrics = self._inf_photo = None
         # test diagnostics: called with no arguments between the last forward pass and the first backward kernel of a step
         # (tests/test_step_gpu.py pins LeakyReLU signs there; never set on the hot path)
         self.before_backward = None
@@ -792,7 +798,7 @@ class ShmGANwithSSpecSeg:
         aug_flip_ud=0.5 is the as-intended reading of the per-step draw below.  `cache="device"` (with `cache_gb`, GiB; default half of the free
         device memory) keeps the decoded samples on the device after their first decode, the reference's `.cache()`;
         `self.loadedDataset.cache_stats()` says what it holds.  `ema_decay` (with `ema_warmup`) keeps an average of the generator's weights
-        (_ensure_ema, generator_weights); `val_dir` or `val_fraction` (with `val_seed`, `val_step`, `val_batch_size`, `val_monitor`) hold captures
+        (_ensure_ema, generator_weights); `val_dir` or `val_fraction` (with `val_seed`, `val_step`, `val_batch_size`, `val_monitor`, `val_region`) hold captures
         out: every `val_step` epochs, in front of the checkpoint, and once at the end they are scored (validate), rank 0 appends the means to
         `log_dir`/validation.jsonl and keeps the best weights as `checkpoint_save_dir`/best.npz (validation.py).  Both are off by default and
         leave the training trajectory bitwise alone when on.  `max_steps` (tests) stops early.  Returns the number of train_step calls made."""
@@ -803,7 +809,9 @@ class ShmGANwithSSpecSeg:
                     setattr(self, k, v)
         start = time.perf_counter()
         a = self.args
-        self._val_on, self._val_step, self._val_monitor = validation_options(a.val_dir, a.val_fraction, a.val_seed, a.val_step, a.val_batch_size, a.val_monitor)
+        self._val_on, self._val_step, self._val_monitor = validation_options(a.val_dir, a.val_fraction, a.val_seed, a.val_step, a.val_batch_size, a.val_monitor,
+                                                                             a.val_region)
+        self._val_region = region_options(a.val_region, a.val_region_threshold, "val_region")
         ops.ema_decay_at(a.ema_decay, 0)                                       # checked before the data is listed
         self.length_dataset, dataset = datasetLoad(self)                       # SHM.py:904
         if self.G is None:
@@ -904,7 +912,7 @@ class ShmGANwithSSpecSeg:
     # ------------------------------------------------------------------ inference (test.py:218-297)
     # arena names that hold one frame's worth of inference buffers (dropped when the frame shape changes, _frame_changed)
     # (of the live attention branch only the forward's mask / y1 / y2: its backward buffers belong to training)
-    _FRAME_BUFFERS = ("inf", "specseg/inf", "pre/yuv/inf", "metrics/ws") + tuple(f"g/attn{lvl}/{n}" for lvl in range(4) for n in ("m", "y1", "y2"))
+    _FRAME_BUFFERS = ("inf", "specseg/inf", "pre/yuv/inf", "metrics/ws", "metrics/region_ws", "eval/region") + tuple(f"g/attn{lvl}/{n}" for lvl in range(4) for n in ("m", "y1", "y2"))
 
     def _frame_changed(self, H, W):
         """Inference keeps buffers for ONE frame shape: when (H, W) differs from the frame of the last infer() (square or not),
@@ -916,7 +924,8 @@ class ShmGANwithSSpecSeg:
             torch.cuda.synchronize(self.device)
             for br in self.G.attn:                 # the branches' records hold the old frame's maps
                 br.ctx = None
-            self.gen_input = self.gen_Y = self.gen_rgb = self.specular_candidate = None
+            self.gen_input = self.gen_Y = self.gen_rgb = self.specular_candidate = self._inf_photo = None
+            self.highlight_region = self.region_metrics = None
             self.cyc_gen0_rgb = self.cyc_gen45_rgb = self.cyc_gen90_rgb = self.cyc_gen135_rgb = self.cyc_genED_rgb = None
             self.G.ctx.pop("inf1", None)
             self.G.ctx.pop("inf5", None)
@@ -977,6 +986,7 @@ class ShmGANwithSSpecSeg:
                 G.ctx.pop("inf1", None)                        # it would describe the last cyclic pass, not G1
             outs = [cyc_rgb[k * B:(k + 1) * B] for k in range(5)]
         self.gen_input, self.gen_Y, self.gen_rgb = gen_in, gen_Y, gen_rgb
+        self._inf_photo = x if self.eval_region is not None else None      # the frame as fed (eval_region "residual" reads it)
         self.stddev_arr = [scale]
         (self.cyc_gen0_rgb, self.cyc_gen45_rgb, self.cyc_gen90_rgb, self.cyc_gen135_rgb, self.cyc_genED_rgb) = outs
         return gen_rgb, outs
@@ -1017,7 +1027,33 @@ class ShmGANwithSSpecSeg:
                 if tuple(t.shape) != (B, win[2], win[3], 3):
                     raise ValueError(f"diffuse images {tuple(t.shape)} do not match the window {win[2]} x {win[3]} of the generated ones")
                 metrics = ops.image_metrics_hw(gen_rgb, win, t, out=out, arena=self.arena)
+            if self.eval_region is not None:
+                self._region_metrics(self.eval_region, self._inf_photo, gen_rgb, t, (0, 0, H, W) if window is None else (top, left, h, w))
         return gen_rgb, cyc, metrics
+
+    EVAL_REGIONS = ("residual", "specseg")
+
+    def _region_metrics(self, spec, photo, gen_rgb, t, win, out=None):
+        """The `eval_region` part of evaluate_frame (validation.validate uses it too), after an infer() of this frame: the highlight of
+        the window `win` under spec = (kind, tau) -- from the `photo` infer was fed and the diffuse target t, or from the SpecSeg mask
+        infer computed -- into `highlight_region`, and gen_rgb's metrics against t inside and outside it into `region_metrics` (or
+        `out`).  Two more launch groups on the current stream, arena buffers (the region lives in a frame-sized buffer, so windows of
+        one frame share it)."""
+        kind, tau = spec
+        if kind not in self.EVAL_REGIONS:
+            raise ValueError(f"eval_region {spec!r} is not None or one of {self.EVAL_REGIONS} with a threshold")
+        B, H, W = (int(v) for v in gen_rgb.shape[:3])
+        h, w = win[2], win[3]
+        region = self.arena.get("eval/region", (B * H * W,), torch.uint8)[:B * h * w].view(B, h, w)
+        if kind == "residual":
+            ops.highlight_region("residual", win, src=photo, target=t, tau=tau, out=region)
+        else:
+            ops.highlight_region("plane", win, plane=self.specular_candidate, tau=tau, out=region)
+        if out is None:
+            out = self.arena.get("eval/region_metrics", (B, ops.REGION_METRICS), torch.float64)
+        self.highlight_region = region
+        self.region_metrics = ops.image_metrics_region(gen_rgb, win, t, region, out=out, arena=self.arena)
+        return self.region_metrics
 
     def _img_ws(self, B):
         n = ops.image_losses_workspace(B, self.image_size)

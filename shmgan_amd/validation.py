@@ -7,7 +7,7 @@ import torch
 
 from . import checkpoint, dist, ops
 from .data import gib_to_bytes, validation_loader
-from .telemetry import VALIDATION_FILE, WEIGHT_SETS, improves, write_lines
+from .telemetry import VALIDATION_FILE, WEIGHT_SETS, improves, nan_to_none, region_means, region_options, write_lines
 
 
 def _loader(t):
@@ -20,13 +20,18 @@ def _loader(t):
     return t.valDataset
 
 
-def validate(t, dataset=None, weights=("raw",)):
+def validate(t, dataset=None, weights=("raw",), region="args"):
     """Score the generator on held-out captures with test mode's protocol (evaluate.test): view 0 as the photo, the other views
     zero, target label ED (infer without the cyclic passes), gen_rgb against the sample's ED image with ops.image_metrics.
     dataset: a data.PolarDataset (default: the held-out loader of the trainer's val_dir / val_fraction options); only its full
     batches are scored.  weights: the weight sets to score, each under generator_weights().  Per set every batch's rows go into one
     [n,5] float64 device buffer; ONE device-to-host copy ends the pass and the means are taken in float64 on the host.
     Returns {"n": images scored, "held_out": images listed, <set>: {"mse", "psnr", "ssim", "de76", "de94" (means), "rows" ([n,5])}}.
+    region: None, or (source, threshold) as telemetry.region_options returns it (default: the trainer's val_region / val_region_threshold
+    options) -- every batch's metrics are then also split by the highlight (trainer._region_metrics: the photo is batch[0], the target
+    batch[4]) into the same device buffer, still one copy per pass, and each set also holds "region_rows" ([n,12],
+    ops.REGION_METRIC_NAMES), the ten "in_*" / "out_*" means over the images whose set is not empty (NaN when there is none) and
+    "n_in_images" / "n_out_images".
     Reads no draw stream and writes nothing a training step relies on (its buffers are infer's and its own), so a run that
     validates takes bitwise the steps of one that does not."""
     if t.G is None:
@@ -38,18 +43,34 @@ def validate(t, dataset=None, weights=("raw",)):
     for w in weights:
         if w not in WEIGHT_SETS:
             raise ValueError(f"validate: {w!r} is not one of {WEIGHT_SETS}")
+    if region == "args":
+        region = region_options(getattr(t.args, "val_region", "off"), getattr(t.args, "val_region_threshold", None), "val_region")
     B, nb = int(dataset.B), len(dataset)
     n = nb * B
     out = {"n": n, "held_out": int(dataset.n)}
-    rows = t.arena.get("val/rows", (max(n, 1), 5), torch.float64)
+    if region is None:
+        rows = t.arena.get("val/rows", (max(n, 1), 5), torch.float64)
+    else:                       # one buffer for both tables: [n,5] in front, [n,12] behind it
+        both = t.arena.get("val/rows+region", (max(n, 1) * (5 + ops.REGION_METRICS),), torch.float64)
+        rows, rrows = both[:max(n, 1) * 5].view(-1, 5), both[max(n, 1) * 5:].view(-1, ops.REGION_METRICS)
     for w in weights:
         with t.generator_weights(w):
             for i, batch in enumerate(dataset):
                 gen_rgb, _ = t.infer(batch[0], cyclic=False)
                 ops.image_metrics(gen_rgb, batch[4], out=rows[i * B:(i + 1) * B], arena=t.arena)
-            host = rows[:n].cpu().numpy().astype(np.float64, copy=True)           # the pass's one device-to-host copy (it synchronises)
+                if region is not None:
+                    S = int(gen_rgb.shape[1])
+                    t._region_metrics(region, t._dev(batch[0]), gen_rgb, t._dev(batch[4]), (0, 0, S, S), out=rrows[i * B:(i + 1) * B])
+            # the pass's one device-to-host copy (it synchronises)
+            host = (rows[:n] if region is None else both).cpu().numpy().astype(np.float64, copy=True)
+        if region is not None:
+            host, rhost = host[:max(n, 1) * 5].reshape(-1, 5)[:n], host[max(n, 1) * 5:].reshape(-1, ops.REGION_METRICS)[:n]
         means = host.mean(axis=0) if n else np.full(5, np.nan)
         out[w] = dict({k: float(v) for k, v in zip(ops.METRIC_NAMES, means)}, rows=host)
+        if region is not None:
+            S = int(t.image_size)
+            rmeans, n_in_images, n_out_images = region_means(rhost, S * S, (S - 10) * (S - 10))
+            out[w].update(rmeans, region_rows=rhost, n_in_images=n_in_images, n_out_images=n_out_images)
     return out
 
 
@@ -65,7 +86,7 @@ def validate_and_log(t, print_fn=print):
     t._last_val_step = step
     t._check_abort(sync=True)     # never score (or keep as the best) weights behind a step whose kernels gave up
     sets = ("raw", "ema") if t._ema_on() else ("raw",)
-    res = t.validate(weights=sets)
+    res = t.validate(weights=sets, region=t._val_region)
     monitored, mon = sets[-1], t._val_monitor
     best_now = False
     if res["n"]:
@@ -77,7 +98,10 @@ def validate_and_log(t, print_fn=print):
         os.makedirs(t.log_dir, exist_ok=True)
         write_lines(os.path.join(t.log_dir, VALIDATION_FILE),
                     [dict({"step": step, "epoch": int(t.epoch), "weights": w, "n": res["n"], "held_out": res["held_out"]},
-                          **{k: res[w][k] for k in ops.METRIC_NAMES}, best=bool(best_now and w == monitored)) for w in sets])
+                          **{k: res[w][k] for k in ops.METRIC_NAMES},
+                          **({} if t._val_region is None else dict({k: nan_to_none(res[w][k]) for k in ops.REGION_METRIC_NAMES[:10]},
+                                                                   n_in_images=res[w]["n_in_images"])),
+                          best=bool(best_now and w == monitored)) for w in sets])
         if best_now:
             checkpoint.write_atomic(t, os.path.join(t.checkpoint_save_dir, checkpoint.BEST_CHECKPOINT))
         print_fn(f"Validation at step {step} ({res['n']} of {res['held_out']} held-out images): " +

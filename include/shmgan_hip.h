@@ -511,6 +511,16 @@ int shm_image_losses(const float* gen_rgb, const float* cyc_rgb, const float* cy
                      const float* cbcr, const float* const* orig, const float* const* ds,
                      int flags_mask, float style_factor, double* loss, float* dgen_y, float* dcyc_y,
                      void* ws, size_t ws_bytes, int batch, int s, void* stream);
+/* The same on rectangular frames: every tensor is [.,h,w,c], same arguments, loss slots and gradient definitions.  SSIM is VALID
+ * over (h-10) x (w-10) positions, every mean is taken over h*w pixels and the gram matrices are divided by h*w.  This is the one
+ * implementation: shm_image_losses(s) is this call with h = w = s.  SHM_E_SHAPE for a side below 11 (the SSIM window) or a bad
+ * batch, SHM_E_WORKSPACE for less than shm_image_losses_hw_workspace(batch, h, w) bytes (0 for a side below 11), all before any
+ * launch. */
+size_t shm_image_losses_hw_workspace(int batch, int h, int w);
+int shm_image_losses_hw(const float* gen_rgb, const float* cyc_rgb, const float* cyc_y,
+                        const float* cbcr, const float* const* orig, const float* const* ds,
+                        int flags_mask, float style_factor, double* loss, float* dgen_y, float* dcyc_y,
+                        void* ws, size_t ws_bytes, int batch, int h, int w, void* stream);
 
 /* ---- image-quality metrics of the reference's test mode (test.py:332-392, --calc_metrics True) ----------------------
  * pred = gen_rgb (the G1 output in RGB, not clipped), target = the diffuse image, both [batch,s,s,3] fp32.  Per image b,

@@ -45,10 +45,14 @@ def _tensor(key, buf, size=None, needs=(), owner=None):
 def _state(t):
     """What a resumed run continues from instead of replaying the first run's opening steps: the step-level draw streams (flags / TARGET_LABELS
     generator, the Philox counter of the noise and dropout kernels), the epoch, which graph the variables belong to (`read` checks it) and, only with
-    validation on (other files keep exactly the keys they always had), the best held-out value so far (best_to_beat).  Optional, for old files."""
+    validation on (other files keep exactly the keys they always had), the best held-out value so far (best_to_beat).  Optional, for old files.
+    Only with the image_hw option set: the frame (`read` checks it -- the Dense kernel D/var06 of an H x W and of a W x H frame have one
+    shape and another meaning, its rows follow the NHWC flattening of the (H/32) x (W/32) map)."""
     def get():
         s = {"attention": t.attention, "epoch": int(t.epoch), "draw_count": int(t._draw_count), "rng": t._rng.bit_generator.state,
              "batch_step": int(t.batch_step)}
+        if getattr(t, "_image_hw", None) is not None:
+            s["image_hw"] = list(t._image_hw)
         return np.array(json.dumps(dict(s, best=t._best) if t._val_on else s))
 
     def put(a):
@@ -119,12 +123,27 @@ def read(t, path):
             if mode != t.attention:
                 raise KeyError(f"checkpoint {path} holds an attention='{mode}' model, this trainer was built with "
                                f"attention='{t.attention}' (the live branch adds 20 + 4 variables)")
+            if e.key == "trainer/state":
+                _check_frame(t, path, json.loads(str(a)).get("image_hw"), z["D/var06"] if "D/var06" in z.files else None)
             if isinstance(e.size, tuple) and tuple(a.shape) != e.size:
                 raise KeyError(f"checkpoint {path}: {e.key} has shape {tuple(a.shape)}, this model's is {e.size}")
             if isinstance(e.size, int) and a.size != e.size:
                 whose = "the network's" if e.key.startswith("SpecSeg/") else "this model's"
                 raise KeyError(f"checkpoint {path}: {e.key} has {a.size} elements, {whose} flat buffer {e.size}")
     return arrays
+
+
+def _check_frame(t, path, saved, dense):
+    """The frame a file was trained on against this trainer's: `saved` is the file's image_hw (None: a file of a trainer without the
+    option, whose frame is a square).  Only a trainer that knows its frame as a pair is checked; a mismatch is the Dense kernel's."""
+    mine = getattr(t, "image_hw", None)
+    if mine is None or (saved is None and mine[0] == mine[1]):
+        return
+    if saved is None or tuple(int(v) for v in saved) != tuple(mine):
+        rows = "?" if dense is None else dense.shape[0]
+        was = "a square frame" if saved is None else f"a {saved[0]} x {saved[1]} frame ({saved[0] // 32} x {saved[1] // 32} map)"
+        raise KeyError(f"checkpoint {path}: D/var06 (the Dense kernel, {rows} rows) was trained on {was}, this model's frame is "
+                       f"{mine[0]} x {mine[1]} ({mine[0] // 32} x {mine[1] // 32} map): its rows follow the NHWC flattening of that map")
 
 
 def apply(t, arrays):

@@ -1,7 +1,7 @@
 // Image-space generator losses of SHMGAN's train_step and their gradient wrt the generated
 // Y planes (SHM.py:744-826): L1 cycle loss, tf.image.ssim on rescale_01'd YUV (utils.py:190),
 // content + gram-matrix style loss.  Everything here is tiny next to the convolutions
-// (5B x 3 x S x S values), so the kernels favour clarity: one pixel pass for the sums and
+// (5B x 3 x H x W values), so the kernels favour clarity: one pixel pass for the sums and
 // min/max, a direct 11x11 gaussian from an LDS tile for SSIM forward and backward.
 //
 // loss slots (f64 sums over the batch):
@@ -39,8 +39,8 @@ struct ImgArgs {
     float* gcoef;       // [B][5]  dLoss/dS_p scaling
     double* rsum;       // [B][5][2]  sum dx, sum dx*r
     int* argpos;        // [B][5][2]
-    float* dmaps;       // [B*5*3][3][HO*WO]
-    int batch, s;
+    float* dmaps;       // [B*5*3][3][ho*wo]
+    int batch, h, w, ho, wo;   // the frame and its VALID SSIM map: ho = h - 10, wo = w - 10
 };
 
 __device__ __forceinline__ unsigned f2ord(float f) {
@@ -54,7 +54,7 @@ __device__ __forceinline__ float ord2f(unsigned u) {
 // ------------------------------------------------------------------- pass A: pixel sums
 __global__ __launch_bounds__(256) void img_pass_a(const ImgArgs a) {
     const int b = blockIdx.y, B = a.batch;
-    const size_t npix = (size_t)a.s * a.s;
+    const size_t npix = (size_t)a.h * a.w;
     const float invB = 1.0f / B, inv3n = 1.0f / (3.0f * (float)npix);
     double sm[NSUM];
 #pragma unroll
@@ -126,7 +126,7 @@ __global__ __launch_bounds__(256) void img_pass_a(const ImgArgs a) {
 // ---------------------------------------------------------- pass B: per-sample finalize
 __global__ void img_pass_b(const ImgArgs a) {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    const double npix = (double)a.s * a.s;
+    const double npix = (double)a.h * a.w;
     for (int b = 0; b < a.batch; ++b) {
         const double* sm = a.sums + (size_t)b * NSUM;
         for (int i = 0; i < 6; ++i) a.loss[i] += sm[i] / (3.0 * npix);
@@ -142,9 +142,9 @@ __global__ void img_pass_b(const ImgArgs a) {
     }
 }
 
-// style gradient: d style/dY_p = 4 f / (9 S^2) * (D00*Y + D01*U + D02*V); weight 10*100/B
+// style gradient: d style/dY_p = 4 f / (9 H W) * (D00*Y + D01*U + D02*V); weight 10*100/B
 __global__ void img_style_grad(const ImgArgs a) {
-    const size_t npix = (size_t)a.s * a.s;
+    const size_t npix = (size_t)a.h * a.w;
     size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (size_t)a.batch * npix) return;
     const int b = (int)(idx / npix);
@@ -166,11 +166,11 @@ __global__ __launch_bounds__(256) void ssim_fwd_kernel(const ImgArgs a) {
     __shared__ float xs[HALO][HALO + 1], ys[HALO][HALO + 1];
     __shared__ float hx[HALO][TILE + 1], hy[HALO][TILE + 1], hxy[HALO][TILE + 1], hsq[HALO][TILE + 1];
     __shared__ float w1[WIN];
-    const int S = a.s, HO = S - WIN + 1;
-    const int tiles_x = (HO + TILE - 1) / TILE;
+    const int H = a.h, W = a.w, HO = a.ho, WO = a.wo;
+    const int tiles_x = (WO + TILE - 1) / TILE;            // the grid's x is tiles_y * tiles_x output tiles, row-major
     const int ty = blockIdx.x / tiles_x, tx = blockIdx.x % tiles_x;
     const int bk = blockIdx.y, b = bk / 5, k = bk % 5, c = blockIdx.z;
-    const size_t npix = (size_t)S * S;
+    const size_t npix = (size_t)H * W;
     const float xmn = ord2f(a.mm[((size_t)b * 10 + k) * 2]), xmx = ord2f(a.mm[((size_t)b * 10 + k) * 2 + 1]);
     const float ymn = ord2f(a.mm[((size_t)b * 10 + 5 + k) * 2]), ymx = ord2f(a.mm[((size_t)b * 10 + 5 + k) * 2 + 1]);
     const float xr = xmx > xmn ? xmx - xmn : 0.f, yr = ymx > ymn ? ymx - ymn : 0.f;
@@ -180,8 +180,8 @@ __global__ __launch_bounds__(256) void ssim_fwd_kernel(const ImgArgs a) {
         int r = i / HALO, cc = i % HALO;
         int yy = oy0 + r, xx = ox0 + cc;
         float xv = 0.f, yv = 0.f;
-        if (yy < S && xx < S) {
-            size_t p = (size_t)yy * S + xx;
+        if (yy < H && xx < W) {
+            size_t p = (size_t)yy * W + xx;
             float xraw = cyc_val(a, b, k, c, p, npix);
             float yraw = a.ds[k][((size_t)b * npix + p) * 3 + c];
             xv = xr > 0.f ? (xraw - xmn) / xr : 0.f;       // divide_no_nan
@@ -213,7 +213,7 @@ __global__ __launch_bounds__(256) void ssim_fwd_kernel(const ImgArgs a) {
     const int ly = threadIdx.x / TILE, lx = threadIdx.x % TILE;
     const int oy = oy0 + ly, ox = ox0 + lx;
     double sval = 0.0;
-    if (oy < HO && ox < HO) {
+    if (oy < HO && ox < WO) {
         float mx_ = 0.f, my_ = 0.f, exy = 0.f, esq = 0.f;
         for (int i = 0; i < WIN; ++i) {
             mx_ += w1[i] * hx[ly + i][lx];
@@ -229,8 +229,8 @@ __global__ __launch_bounds__(256) void ssim_fwd_kernel(const ImgArgs a) {
         const float dmx = cs * (2.f * my_ * B1 - A1 * 2.f * mx_) / (B1 * B1) + l * (-2.f * my_ * B2 + A2 * 2.f * mx_) / (B2 * B2);
         const float dexy = l * 2.f / B2;
         const float desq = -l * A2 / (B2 * B2);
-        const size_t no = (size_t)HO * HO;
-        float* dm = a.dmaps + ((size_t)bk * 3 + c) * 3 * no + (size_t)oy * HO + ox;
+        const size_t no = (size_t)HO * WO;
+        float* dm = a.dmaps + ((size_t)bk * 3 + c) * 3 * no + (size_t)oy * WO + ox;
         dm[0] = dmx;
         dm[no] = dexy;
         dm[2 * no] = desq;
@@ -241,8 +241,7 @@ __global__ __launch_bounds__(256) void ssim_fwd_kernel(const ImgArgs a) {
 
 __global__ void ssim_finalize_kernel(const ImgArgs a) {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    const int HO = a.s - WIN + 1;
-    const double cnt = 3.0 * (double)HO * HO;
+    const double cnt = 3.0 * (double)a.ho * a.wo;
     for (int b = 0; b < a.batch; ++b)
         for (int k = 0; k < 5; ++k) {
             double ssim = a.ssim_sum[b * 5 + k] / cnt;
@@ -257,18 +256,18 @@ __global__ void ssim_finalize_kernel(const ImgArgs a) {
 }
 
 // ----------------------------------------------------------------------- SSIM backward
-// grid: (tiles over the S x S input, B*5, 3); block 16x16 input pixels.
+// grid: (tiles_y*tiles_x over the H x W input, B*5, 3); block 16x16 input pixels.
 __global__ __launch_bounds__(256) void ssim_bwd_kernel(const ImgArgs a) {
     __shared__ float d0[HALO][HALO + 1], d1[HALO][HALO + 1], d2[HALO][HALO + 1];
     __shared__ float h0[HALO][TILE + 1], h1[HALO][TILE + 1], h2[HALO][TILE + 1];
     __shared__ float w1[WIN];
-    const int S = a.s, HO = S - WIN + 1;
-    const int tiles_x = (S + TILE - 1) / TILE;
+    const int H = a.h, W = a.w, HO = a.ho, WO = a.wo;
+    const int tiles_x = (W + TILE - 1) / TILE;
     const int ty = blockIdx.x / tiles_x, tx = blockIdx.x % tiles_x;
     const int bk = blockIdx.y, b = bk / 5, k = bk % 5, c = blockIdx.z;
     const float gco = a.gcoef[bk];
     if (gco == 0.f) return;                       // flagged view: no ssim term
-    const size_t npix = (size_t)S * S, no = (size_t)HO * HO;
+    const size_t npix = (size_t)H * W, no = (size_t)HO * WO;
     const float xmn = ord2f(a.mm[((size_t)b * 10 + k) * 2]), xmx = ord2f(a.mm[((size_t)b * 10 + k) * 2 + 1]);
     const float ymn = ord2f(a.mm[((size_t)b * 10 + 5 + k) * 2]), ymx = ord2f(a.mm[((size_t)b * 10 + 5 + k) * 2 + 1]);
     const float xr = xmx > xmn ? xmx - xmn : 0.f, yr = ymx > ymn ? ymx - ymn : 0.f;
@@ -280,8 +279,8 @@ __global__ __launch_bounds__(256) void ssim_bwd_kernel(const ImgArgs a) {
         int r = i / HALO, cc = i % HALO;
         int py = qy0 - (WIN - 1) + r, px = qx0 - (WIN - 1) + cc;
         float v0 = 0.f, v1 = 0.f, v2 = 0.f;
-        if (py >= 0 && py < HO && px >= 0 && px < HO) {
-            size_t o = (size_t)py * HO + px;
+        if (py >= 0 && py < HO && px >= 0 && px < WO) {
+            size_t o = (size_t)py * WO + px;
             v0 = dm[o];
             v1 = dm[no + o];
             v2 = dm[2 * no + o];
@@ -310,7 +309,7 @@ __global__ __launch_bounds__(256) void ssim_bwd_kernel(const ImgArgs a) {
     const int ly = threadIdx.x / TILE, lx = threadIdx.x % TILE;
     const int qy = qy0 + ly, qx = qx0 + lx;
     double sdx = 0.0, sdxr = 0.0;
-    if (qy < S && qx < S) {
+    if (qy < H && qx < W) {
         // input q contributes to output p = q - (i,j) with window weight w[i][j]
         float g0 = 0.f, g1 = 0.f, g2 = 0.f;
         for (int i = 0; i < WIN; ++i) {
@@ -319,7 +318,7 @@ __global__ __launch_bounds__(256) void ssim_bwd_kernel(const ImgArgs a) {
             g1 += w1[i] * h1[rr][lx];
             g2 += w1[i] * h2[rr][lx];
         }
-        const size_t p = (size_t)qy * S + qx;
+        const size_t p = (size_t)qy * W + qx;            // row-major position in the H x W image (argpos)
         const float xraw = cyc_val(a, b, k, c, p, npix);
         const float yraw = a.ds[k][((size_t)b * npix + p) * 3 + c];
         const float xv = xr > 0.f ? (xraw - xmn) / xr : 0.f;
@@ -352,7 +351,7 @@ __global__ void ssim_minmax_kernel(const ImgArgs a) {
     if (!(xmx > xmn)) return;
     const double inv = 1.0 / ((double)xmx - (double)xmn);
     const double sdx = a.rsum[bk * 2], sdxr = a.rsum[bk * 2 + 1];
-    const size_t npix = (size_t)a.s * a.s;
+    const size_t npix = (size_t)a.h * a.w;
     float* dy = a.dcyc_y + ((size_t)k * a.batch + b) * npix;
     const int pmin = a.argpos[bk * 2], pmax = a.argpos[bk * 2 + 1];
     if (pmin >= 0) dy[pmin] += (float)(-(sdx - sdxr) * inv);
@@ -366,7 +365,7 @@ struct WsPlan {
     size_t sums, mm, gd, ssim_sum, gcoef, rsum, argpos, dmaps, total, zero_bytes;
 };
 
-static WsPlan plan_ws(int batch, int s) {
+static WsPlan plan_ws(int batch, int h, int wd) {
     WsPlan w;
     size_t off = 0;
     w.sums = off;     off = align256(off + (size_t)batch * NSUM * 8);
@@ -378,29 +377,34 @@ static WsPlan plan_ws(int batch, int s) {
     w.mm = off;       off = align256(off + (size_t)batch * 20 * 4);
     w.argpos = off;   off = align256(off + (size_t)batch * 10 * 4);
     w.dmaps = off;
-    int ho = s - WIN + 1;
-    off = align256(off + (size_t)batch * 5 * 3 * 3 * ho * ho * 4);
+    const size_t ho = h - WIN + 1, wo = wd - WIN + 1;
+    off = align256(off + (size_t)batch * 5 * 3 * 3 * ho * wo * 4);
     w.total = off;
     return w;
 }
 
-extern "C" size_t shm_image_losses_workspace(int batch, int s) {
-    if (s < WIN) return 0;
-    return plan_ws(batch, s).total;
+extern "C" size_t shm_image_losses_hw_workspace(int batch, int h, int w) {
+    if (h < WIN || w < WIN) return 0;
+    return plan_ws(batch, h, w).total;
 }
+
+extern "C" size_t shm_image_losses_workspace(int batch, int s) { return shm_image_losses_hw_workspace(batch, s, s); }
 
 __global__ void init_mm_kernel(unsigned* mm, int n) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) mm[i] = (i & 1) ? 0u : 0xffffffffu;       // [min, max] pairs
 }
 
-extern "C" int shm_image_losses(const float* gen_rgb, const float* cyc_rgb, const float* cyc_y, const float* cbcr,
-                                const float* const* orig, const float* const* ds, int flags_mask, float style_factor,
-                                double* loss, float* dgen_y, float* dcyc_y, void* ws, size_t ws_bytes, int batch, int s,
-                                void* stream) {
-    SHM_REQUIRE(s >= WIN, SHM_E_SHAPE, "shm_image_losses: image size %d < 11 (ssim window)", s);
+// The one implementation: the square entry below is this one with h = w = s.
+extern "C" int shm_image_losses_hw(const float* gen_rgb, const float* cyc_rgb, const float* cyc_y, const float* cbcr,
+                                   const float* const* orig, const float* const* ds, int flags_mask, float style_factor,
+                                   double* loss, float* dgen_y, float* dcyc_y, void* ws, size_t ws_bytes, int batch, int h, int wd,
+                                   void* stream) {
+    SHM_REQUIRE(h >= WIN && wd >= WIN, SHM_E_SHAPE, "shm_image_losses: image %d x %d has a side < 11 (ssim window)", h, wd);
+    // argpos holds a pixel position as an int
+    SHM_REQUIRE((size_t)h * wd <= 0x7fffffffu, SHM_E_SHAPE, "shm_image_losses: image %d x %d has more than 2^31 - 1 pixels", h, wd);
     SHM_REQUIRE(batch > 0 && batch * 5 <= 65535, SHM_E_SHAPE, "shm_image_losses: bad batch %d", batch);
-    WsPlan w = plan_ws(batch, s);
+    WsPlan w = plan_ws(batch, h, wd);
     SHM_REQUIRE(ws && ws_bytes >= w.total, SHM_E_WORKSPACE, "shm_image_losses: workspace %zu < %zu bytes", ws_bytes, w.total);
     hipStream_t st = (hipStream_t)stream;
     char* base = (char*)ws;
@@ -427,7 +431,10 @@ extern "C" int shm_image_losses(const float* gen_rgb, const float* cyc_rgb, cons
     a.argpos = (int*)(base + w.argpos);
     a.dmaps = (float*)(base + w.dmaps);
     a.batch = batch;
-    a.s = s;
+    a.h = h;
+    a.w = wd;
+    a.ho = h - WIN + 1;
+    a.wo = wd - WIN + 1;
 
     int r = shm_zero(base, w.zero_bytes, stream);
     if (r) return r;
@@ -438,7 +445,7 @@ extern "C" int shm_image_losses(const float* gen_rgb, const float* cyc_rgb, cons
     hipLaunchKernelGGL(init_mm_kernel, dim3(shm_cdiv(batch * 20, 64)), dim3(64), 0, st, a.mm, batch * 20);
     SHM_LAUNCH_CHECK("shm_image_losses(init)");
 
-    const size_t npix = (size_t)s * s;
+    const size_t npix = (size_t)h * wd;
     const int nblk = shm_grid_cap(npix, 1024, 256);
     hipLaunchKernelGGL(img_pass_a, dim3(nblk, batch), dim3(256), 0, st, a);
     SHM_LAUNCH_CHECK("shm_image_losses(pass a)");
@@ -446,15 +453,23 @@ extern "C" int shm_image_losses(const float* gen_rgb, const float* cyc_rgb, cons
     SHM_LAUNCH_CHECK("shm_image_losses(pass b)");
     hipLaunchKernelGGL(img_style_grad, dim3(shm_cdiv((long)(batch * npix), 256)), dim3(256), 0, st, a);
     SHM_LAUNCH_CHECK("shm_image_losses(style)");
-    const int ho = s - WIN + 1;
-    const int tf = shm_cdiv(ho, TILE), tb = shm_cdiv(s, TILE);
-    hipLaunchKernelGGL(ssim_fwd_kernel, dim3(tf * tf, batch * 5, 3), dim3(256), 0, st, a);
+    // tile grids, tiles_y x tiles_x: over the ho x wo outputs in the forward kernel, over the h x w inputs in the backward kernel
+    const int tfy = shm_cdiv(a.ho, TILE), tfx = shm_cdiv(a.wo, TILE), tby = shm_cdiv(h, TILE), tbx = shm_cdiv(wd, TILE);
+    hipLaunchKernelGGL(ssim_fwd_kernel, dim3(tfy * tfx, batch * 5, 3), dim3(256), 0, st, a);
     SHM_LAUNCH_CHECK("shm_image_losses(ssim fwd)");
     hipLaunchKernelGGL(ssim_finalize_kernel, dim3(1), dim3(64), 0, st, a);
     SHM_LAUNCH_CHECK("shm_image_losses(ssim finalize)");
-    hipLaunchKernelGGL(ssim_bwd_kernel, dim3(tb * tb, batch * 5, 3), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(ssim_bwd_kernel, dim3(tby * tbx, batch * 5, 3), dim3(256), 0, st, a);
     SHM_LAUNCH_CHECK("shm_image_losses(ssim bwd)");
     hipLaunchKernelGGL(ssim_minmax_kernel, dim3(shm_cdiv(batch * 5, 64)), dim3(64), 0, st, a);
     SHM_LAUNCH_CHECK("shm_image_losses(minmax)");
     return SHM_OK;
+}
+
+extern "C" int shm_image_losses(const float* gen_rgb, const float* cyc_rgb, const float* cyc_y, const float* cbcr,
+                                const float* const* orig, const float* const* ds, int flags_mask, float style_factor,
+                                double* loss, float* dgen_y, float* dcyc_y, void* ws, size_t ws_bytes, int batch, int s,
+                                void* stream) {
+    return shm_image_losses_hw(gen_rgb, cyc_rgb, cyc_y, cbcr, orig, ds, flags_mask, style_factor, loss, dgen_y, dcyc_y, ws, ws_bytes,
+                               batch, s, s, stream);
 }

@@ -45,6 +45,7 @@ import numpy as np
 import torch
 
 from . import dist, ops
+from .model import frame_hw
 
 PSD_SUBDIRS = ("I0", "I60", "I90", "I150", "ED")          # datasetLoader.py:30-34 (PSD polar dataset)
 SHMGAN_SUBDIRS = ("I0", "I45", "I90", "I135", "ED")       # datasetLoader.py:23-27 (commented alternative)
@@ -126,7 +127,8 @@ def pass_order(n, seed, pass_index, shuffle):
 
 
 class PolarDataset:
-    """Iterable of 5-tuples of [B,S,S,3] float32 device tensors in [0,1].
+    """Iterable of 5-tuples of [B,H,W,3] float32 device tensors in [0,1].  image_size: the output frame, a side S (H = W = S) or a
+    pair (H, W); every image is resized to it whole (a crop drawn by `augment` keeps the source's aspect).
 
     diffuse_source: "dir" = the fifth of `subdirs` holds the estimated-diffuse images (the reference's loader); "min" = the
     per-channel minimum of the four views (utils.calculate_estimate_diffuse), "stokes" = the fitted minimum over all polariser
@@ -150,6 +152,7 @@ class PolarDataset:
                              device=device, epochs=epochs, rank=rank, world=world, diffuse_source=diffuse_source, angles=angles,
                              shuffle=shuffle, augment=augment, seed=seed, first_pass=first_pass, cache=cache, cache_bytes=cache_bytes)
         self.S, self.B, self.flip_ud, self.epochs = image_size, batch_size, flip_ud, epochs
+        self.H, self.W = frame_hw(image_size)
         if cache not in CACHE_MODES:
             raise ValueError(f"cache {cache!r} is not one of {CACHE_MODES}")
         if cache_bytes is not None and (not isinstance(cache_bytes, int) or cache_bytes < 0):
@@ -265,7 +268,7 @@ class PolarDataset:
         with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
             # allocated, filled and consumed on the loader stream: the caching allocator hands a block back to loader-stream
             # allocations only, which are ordered behind the resize kernel that read it
-            outs = [torch.empty((self.B, self.S, self.S, 3), device=self.dev) for _ in range(5)]
+            outs = [torch.empty((self.B, self.H, self.W, 3), device=self.dev) for _ in range(5)]
             for v in range(5):
                 for b in range(self.B):
                     src = staged[v][b].to(self.dev, non_blocking=True)
@@ -282,7 +285,7 @@ class PolarDataset:
         for b in range(self.B):
             self._same_size(staged, paths, b)
         with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
-            outs = [torch.empty((self.B, self.S, self.S, 3), device=self.dev) for _ in range(5)]       # on the loader stream, as above
+            outs = [torch.empty((self.B, self.H, self.W, 3), device=self.dev) for _ in range(5)]       # on the loader stream, as above
             for b in range(self.B):
                 srcs = [staged[v][b].to(self.dev, non_blocking=True) for v in range(4)]
                 ops.polar_views_u8(srcs, [outs[v][b] for v in range(5)], self.diffuse_source, self.coef, 1.0 / 255.0, self.flip_ud)
@@ -302,7 +305,7 @@ class PolarDataset:
             self._same_size(staged, paths, b)
         kind, how = self._mirror
         with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
-            outs = [torch.empty((self.B, self.S, self.S, 3), device=self.dev) for _ in range(5)]       # on the loader stream, as above
+            outs = [torch.empty((self.B, self.H, self.W, 3), device=self.dev) for _ in range(5)]       # on the loader stream, as above
             for b in range(self.B):
                 hin, win = staged[0][b].shape[:2]
                 p = augment_params(self.seed, pass_index, pos[b], hin, win, self.augment)
@@ -344,7 +347,7 @@ class PolarDataset:
         kind, how = self._mirror
         with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
             arena = self._sample_cache()
-            outs = [torch.empty((self.B, self.S, self.S, 3), device=self.dev) for _ in range(5)]       # on the loader stream, as above
+            outs = [torch.empty((self.B, self.H, self.W, 3), device=self.dev) for _ in range(5)]       # on the loader stream, as above
             samples = []
             for b, p in enumerate(pos):
                 e = arena.lookup(p)
@@ -377,7 +380,7 @@ class PolarDataset:
 
     def prepare(self, index, pass_index=0):
         """Start batch `index` (0-based, of this rank) of pass `pass_index` on the loader thread / stream; returns a future of
-        (five [B,S,S,3] tensors, ready event).  The outputs are ALLOCATED on the loader stream: a block the consumer has
+        (five [B,H,W,3] tensors, ready event).  The outputs are ALLOCATED on the loader stream: a block the consumer has
         dropped is then only reused after the consumer stream's work recorded by `take()` has finished (train_step is
         fully asynchronous and reads its inputs late in the step, so allocating them on the consumer stream would let the
         next batch's resize kernels overwrite images that queued step kernels still read)."""
@@ -395,7 +398,7 @@ class PolarDataset:
         return outs
 
     def batch(self, index, pass_index=0):
-        """Batch `index` (0-based) of pass `pass_index` as five [B,S,S,3] tensors; prepared on the loader's stream."""
+        """Batch `index` (0-based) of pass `pass_index` as five [B,H,W,3] tensors; prepared on the loader's stream."""
         return self.take(self.prepare(index, pass_index))
 
     def __iter__(self):
@@ -454,6 +457,13 @@ def validation_loader(data_dir, image_size, batch_size, *, val_dir="", val_fract
     return PolarDataset(data_dir, **opts, select=val)
 
 
+def trainer_frame(trainer):
+    """The frame a trainer's loaders produce: its frame_arg() (the side, or the image_hw pair), or image_size of a plain options
+    object that has no such method."""
+    frame = getattr(trainer, "frame_arg", None)
+    return frame() if callable(frame) else trainer.image_size
+
+
 def datasetLoad(trainer, subdirs=PSD_SUBDIRS, flip_ud=True):
     """Reference signature (datasetLoader.py:19): returns (length_dataset, loadedDataset) and sets the same
     attributes on the trainer object.  The trainer's `diffuse_source` option (default "dir") goes to PolarDataset; it is NOT
@@ -471,13 +481,13 @@ def datasetLoad(trainer, subdirs=PSD_SUBDIRS, flip_ud=True):
     # held-out validation (`val_dir` / `val_fraction`, both off by default): the loader train() validates on, and with val_fraction
     # the training loader is the rest of data_dir
     val_dir, val_fraction, val_seed = opt("val_dir", ""), float(opt("val_fraction", 0.0) or 0.0), int(opt("val_seed", 0))
-    trainer.valDataset = validation_loader(trainer.data_dir, trainer.image_size, trainer.batch_size, val_dir=val_dir, val_fraction=val_fraction,
+    trainer.valDataset = validation_loader(trainer.data_dir, trainer_frame(trainer), trainer.batch_size, val_dir=val_dir, val_fraction=val_fraction,
                                            val_seed=val_seed, val_batch_size=opt("val_batch_size", None), subdirs=subdirs, flip_ud=flip_ud,
                                            device=trainer.device, **source, **cache)
     select = None
     if val_fraction:
         select, _ = split_indices(list_images(os.path.join(trainer.data_dir, tuple(subdirs)[0])), val_fraction, val_seed)
-    ds = PolarDataset(trainer.data_dir, trainer.image_size, trainer.batch_size, subdirs, flip_ud, trainer.device,
+    ds = PolarDataset(trainer.data_dir, trainer_frame(trainer), trainer.batch_size, subdirs, flip_ud, trainer.device,
                       epochs=trainer.num_epochs, shuffle=bool(opt("shuffle", False)), augment=augment, seed=int(opt("data_seed", 0)),
                       select=select, **source, **cache)
     trainer.stddev_arr, trainer.mean_arr, trainer.variance_arr = [], [], []
@@ -745,7 +755,8 @@ class EvalDataset:
     def __init__(self, test_dir, image_size, batch_size=1, diffuse_dir=None, device=None):
         if batch_size < 1:
             raise ValueError(f"batch_size {batch_size} < 1")
-        self.S, self.B = int(image_size), int(batch_size)
+        self.H, self.W = frame_hw(image_size)                # image_size: a side, or a pair (H, W)
+        self.S, self.B = (self.H if self.H == self.W else None), int(batch_size)
         self.test_files, self.diffuse_files = eval_file_lists(test_dir, diffuse_dir)
         self.n = len(self.test_files)
         self.rank, self.world = 0, 1
@@ -782,7 +793,7 @@ class EvalDataset:
         return test, diffuse
 
     def _upload(self, decoded):
-        out = torch.empty((len(decoded), self.S, self.S, 3), dtype=torch.float32, device=self.dev)
+        out = torch.empty((len(decoded), self.H, self.W, 3), dtype=torch.float32, device=self.dev)
         for b, a in enumerate(decoded):
             ops.resize_bilinear_u8(torch.from_numpy(a).to(self.dev), out[b], 1.0 / 255.0, False)
         return out

@@ -24,7 +24,7 @@ IMAGE_TAGS -- G1 RGB, G1 Y, the five cyclic reconstructions and the SpecSeg mask
 user's own input and diffuse files ("g1": G1 only).  `image_values` "rescale" maps each plane with rescale_01 (the reference's
 test_plot display); "output" scales the RGB and Y planes by the running mean of the standardisation scales, the reference's
 gen_rgb_output / 255, and clips.  The mask is always clipped.  `image_out_size` "source" resamples to the photo's own size
-(bilinear, half-pixel centres: the inverse direction of the loader's resize), "model" writes S x S.  `image_dir` defaults to
+(bilinear, half-pixel centres: the inverse direction of the loader's resize), "model" writes the trainer's frame, S x S or the H x W of image_hw.  `image_dir` defaults to
 `<result_dir>/images`.  The bytes come from the library's exporter (ops.export_u8, one call per batch); PNG encoding runs on a
 pool of writer threads while the next batch is evaluated.
 
@@ -59,7 +59,7 @@ from concurrent.futures import ThreadPoolExecutor
 import torch
 
 from . import ops
-from .data import EvalDataset, NativeEvalDataset, pad_geometry
+from .data import EvalDataset, NativeEvalDataset, pad_geometry, trainer_frame
 from .model import generator_layers, pad_channels
 from .specseg import WIDTHS as SPECSEG_WIDTHS
 from .telemetry import nan_to_none, region_means, region_options, write_lines
@@ -291,8 +291,9 @@ class ImageExporter:
     def submit(self, shmgan, gen_rgb, cyc, sources, windows=None):
         """Enqueue batch `sources` ((path, (h, w)) per image, in batch order) of the evaluation just issued.  windows (out_size
         "native"): (top, left, h, w) per image, the photo inside the frame."""
-        B, S = int(gen_rgb.shape[0]), int(gen_rgb.shape[1])
+        B, H, W = (int(v) for v in gen_rgb.shape[:3])
         native = self.out_size == "native"
+        whole = None if native or H == W else (0, 0, H, W)      # a rectangular model frame: the windowed export over the whole plane
         wins = []
         mul = None
         if self.values == "output":
@@ -302,9 +303,9 @@ class ImageExporter:
             ops.running_scale_mean(shmgan.stddev_arr[0], self.acc, mul)
         planes, sizes, modes, jobs = [], [], [], []
         for b, (path, hw) in enumerate(sources):
-            size = tuple(windows[b][2:]) if native else tuple(hw) if self.out_size == "source" else (S, S)
+            size = tuple(windows[b][2:]) if native else tuple(hw) if self.out_size == "source" else (H, W)
             for tag in self.tags:
-                wins.append(tuple(windows[b]) if native else None)
+                wins.append(tuple(windows[b]) if native else whole)
                 p = self._plane(tag, b, gen_rgb, cyc, shmgan.gen_Y, shmgan.specular_candidate)
                 planes.append(p)
                 sizes.append(size)
@@ -315,7 +316,7 @@ class ImageExporter:
             self.buf = torch.empty(total, dtype=torch.uint8, device=self.dev)
         # gen_rgb, the cyclic images, gen_Y and the mask are arena tensors that the next evaluate() overwrites: the export
         # reads them before that only because both are ordered on this one stream.  The same holds for self.buf and the copy.
-        if native:
+        if native or whole is not None:
             ops.export_u8_hw(planes, wins, sizes, modes, mul, self.buf, arena=shmgan.arena)
         else:
             ops.export_u8(planes, sizes, modes, mul, self.buf, arena=shmgan.arena)
@@ -355,7 +356,7 @@ def _write_png(ev, stage, off, size, c, path):
 
 def test(shmgan, args, *, print_fn=print):
     """main.py:110 `test(shmgan, args)`.  Reads args.test_dir, args.diffuse_dir, args.calc_metrics and args.eval_batch_size
-    (default 1), args.eval_size ("model", the default: every image resized to image_size x image_size; "native": every image at
+    (default 1), args.eval_size ("model", the default: every image resized to the trainer's frame, image_size x image_size or image_hw; "native": every image at
     its own size -- eval_batch_size must then be 1, image_out_size is ignored, and "Time" covers the passes that were run: G1,
     plus the five cyclic passes with save_images="all"; module docstring), and the image export's args.save_images, image_values,
     image_out_size, image_dir (module docstring), and args.eval_weights / args.eval_checkpoint (eval_options: which file and which of its
@@ -403,7 +404,7 @@ def test(shmgan, args, *, print_fn=print):
     if native:
         dataset = NativeEvalDataset(test_dir, diffuse_dir, shmgan.device, check=check)
     else:
-        dataset = EvalDataset(test_dir, shmgan.image_size, B, diffuse_dir, shmgan.device)
+        dataset = EvalDataset(test_dir, trainer_frame(shmgan), B, diffuse_dir, shmgan.device)
     if tags:
         check_stems(dataset.test_files)
     shmgan.number_of_test_images = dataset.n                                   # test.py:123

@@ -47,6 +47,35 @@ WGRAD_AFTER_DGRAD = os.environ.get("SHM_WGRAD_AFTER_DGRAD", "0") == "1"
 PAD_C = 16          # channel pitch of 3- and 10-channel images in float32 (one 64-byte MFMA staging row)
 
 
+def frame_hw(image_size):
+    """(H, W) of a model frame given as a side or as a pair (the trainer's image_size / image_hw)."""
+    if isinstance(image_size, (tuple, list)):
+        h, w = image_size
+        return int(h), int(w)
+    return int(image_size), int(image_size)
+
+
+IMAGE_HW_RULE = "image_hw is None or a pair (H, W) of integers, both multiples of 32 and at least 32 (the discriminator has five stride-2 blocks)"
+
+
+def check_image_hw(image_hw):
+    """The trainer's image_hw option, checked: None stays None (the square image_size frame), anything else must be a pair that
+    follows IMAGE_HW_RULE and comes back as a tuple of two ints; ValueError names the rule."""
+    if image_hw is None:
+        return None
+    ok = isinstance(image_hw, (tuple, list)) and len(image_hw) == 2 and all(
+        isinstance(v, (int, np.integer)) and not isinstance(v, bool) and v >= 32 and v % 32 == 0 for v in image_hw)
+    if not ok:
+        raise ValueError(f"image_hw={image_hw!r}: {IMAGE_HW_RULE}")
+    return int(image_hw[0]), int(image_hw[1])
+
+
+def dense_inputs(hw, filter_size):
+    """Inputs of the discriminator's Dense(5): the (H/32) x (W/32) x 16F map of the fifth block, flattened in NHWC order."""
+    h, w = frame_hw(hw)
+    return (h // 32) * (w // 32) * 16 * int(filter_size)
+
+
 def pad_channels(dtype):
     """Channel pitch of the 3- and 10-channel images = contraction granule of the tap GEMM:
     one 64-byte LDS row, i.e. 16 float32 or 32 bfloat16 channels."""
@@ -317,8 +346,7 @@ class AttentionBranch:
             ops.transpose_taps(*it)
 
     def forward(self, mask, B, H, W=None):
-        """mask [B,H,W,1] fp32 (W defaults to H: the square training shape) -> attention map [B, H/pool, W/pool, C] (activation
-        dtype).  The backward pass is the training path's and takes the square shape."""
+        """mask [B,H,W,1] fp32 (W defaults to H) -> attention map [B, H/pool, W/pool, C] (activation dtype)."""
         o, c, A = self.o, self.c, self.o.arena
         W = H if W is None else W
         h, w = H // self.pool, W // self.pool
@@ -335,22 +363,21 @@ class AttentionBranch:
         return y2
 
     def backward(self, dattn):
-        """dattn [B,h,h,C] ([G]-typed): gradient at the attention map, summed over every copy of the sample.  Fills the
+        """dattn [B,h,w,C] ([G]-typed): gradient at the attention map, summed over every copy of the sample.  Fills the
         weight gradients (kernels by the MFMA wgrad, biases through the owner's f64 accumulators)."""
         o, c, A, x = self.o, self.c, self.o.arena, self.ctx
-        B, h = x["B"], x["h"]
-        assert x["w"] == h, "the attention backward is the training path's: square maps only"
-        dz2 = A.get(f"{self.tag}/dz2", (B, h, h, c), o.adt)
-        dz1 = A.get(f"{self.tag}/dz1", (B, h, h, c), o.adt)
-        dy1 = A.get(f"{self.tag}/dy1", (B, h, h, c), o.gdt)
+        B, h, w = x["B"], x["h"], x["w"]
+        dz2 = A.get(f"{self.tag}/dz2", (B, h, w, c), o.adt)
+        dz1 = A.get(f"{self.tag}/dz1", (B, h, w, c), o.adt)
+        dy1 = A.get(f"{self.tag}/dy1", (B, h, w, c), o.gdt)
         red = A.get(f"attn/lred/{c}", (ops.LRELU_RED_SLOTS * c,), torch.float64)
-        ops.lrelu_bwd(dattn, c, x["y2"], c, dz2, c, o._acc_slice(self.vi + 3), B * h * h, c, LRELU, red)
-        ws = o.ws_provider(ops.conv2d_wgrad_workspace(B, h, h, c, c, 3))
-        o.lane.submit(lambda: ops.conv2d_wgrad(x["y1"], None, 0, c, 0, dz2, c, o.P.grads[self.vi + 2], B, h, h, c, c, c, 3, 1, 0, ws))
-        ops.conv2d_dgrad(dz2, c, o.P.op_vars[self.vi + 2], dy1, None, c, c, 0, B, h, h, c, c, 3, 1)
-        ops.lrelu_bwd(dy1, c, x["y1"], c, dz1, c, o._acc_slice(self.vi + 1), B * h * h, c, LRELU, red)
-        ws = o.ws_provider(ops.conv2d_wgrad_workspace(B, h, h, 1, c, 3))
-        o.lane.submit(lambda: ops.conv2d_wgrad(x["m"], None, 0, o.pad, 0, dz1, c, o.P.grads[self.vi], B, h, h, 1, o.pad, c, 3, 1, 0, ws))
+        ops.lrelu_bwd(dattn, c, x["y2"], c, dz2, c, o._acc_slice(self.vi + 3), B * h * w, c, LRELU, red)
+        ws = o.ws_provider(ops.conv2d_wgrad_workspace(B, h, w, c, c, 3))
+        o.lane.submit(lambda: ops.conv2d_wgrad(x["y1"], None, 0, c, 0, dz2, c, o.P.grads[self.vi + 2], B, h, w, c, c, c, 3, 1, 0, ws))
+        ops.conv2d_dgrad(dz2, c, o.P.op_vars[self.vi + 2], dy1, None, c, c, 0, B, h, w, c, c, 3, 1)
+        ops.lrelu_bwd(dy1, c, x["y1"], c, dz1, c, o._acc_slice(self.vi + 1), B * h * w, c, LRELU, red)
+        ws = o.ws_provider(ops.conv2d_wgrad_workspace(B, h, w, 1, c, 3))
+        o.lane.submit(lambda: ops.conv2d_wgrad(x["m"], None, 0, o.pad, 0, dz1, c, o.P.grads[self.vi], B, h, w, 1, o.pad, c, 3, 1, 0, ws))
 
 
 # =============================================================================== Generator
@@ -359,7 +386,9 @@ class Generator(_ModelBase):
 
     def __init__(self, image_size, filter_size, device, arena, ws_provider, lane=None, dtype=torch.float32,
                  grad_dtype=None, attention=False):
-        self.S, self.F, self.dev = image_size, filter_size, device
+        # image_size: the training frame, a side or a pair (H, W); S is the side of a square frame and None otherwise
+        self.H, self.W = frame_hw(image_size)
+        self.S, self.F, self.dev = (self.H if self.H == self.W else None), filter_size, device
         self.attention = bool(attention)
         self.arena, self.ws_provider = arena, ws_provider
         self.lane = lane or WgradLane(device, enabled=False)
@@ -370,7 +399,7 @@ class Generator(_ModelBase):
         self.fold = NORM_FOLD                              # InstanceNorm apply folded into the consumers: False / "auto" / "all" (see NORM_FOLD)
         self.norm_mode = NORM_MODE                         # ... in LDS (exact) or in the operands (scaled)
         self._plans = {}
-        assert image_size % 16 == 0 and filter_size % self.pad == 0, \
+        assert self.H % 16 == 0 and self.W % 16 == 0 and filter_size % self.pad == 0, \
             f"image_size must be a multiple of 16 and filter_size of {self.pad}"
         self.layers = generator_layers(filter_size)
         shapes = []
@@ -500,7 +529,7 @@ class Generator(_ModelBase):
         (its second source); the Concatenate block feeds the decoder level's second block.  That block's own output goes to a
         Conv2DTranspose (or the head, which has normalised on the fly since round 2) and the bottleneck is 1x1: not folded.
         Live attention adds its maps to the normalised skips, which therefore have to exist: nothing is folded."""
-        H, W = self.S if H is None else H, self.S if W is None else W       # the map the pass runs on: (S, S) in training
+        H, W = self.H if H is None else H, self.W if W is None else W       # the map the pass runs on: the model's frame in training
         key = (nb, n, bool(attn), self.fold, H, W)      # nb: samples per forward launch (a part of a two-part forward), n: per backward launch
         plan = self._plans.get(key)
         if plan is not None:
@@ -576,8 +605,8 @@ class Generator(_ModelBase):
         return ahat, rec
 
     def forward(self, x16, tag, attn=None, parts=1):
-        """x16: [N,H,W,pad] (10 real channels, zero padded to the 64-byte pitch), H and W multiples of 16: (S, S) in training, any
-        frame in inference (the network is fully convolutional; backward() takes the square training shape).  Returns gen_Y [N,H,W,1].
+        """x16: [N,H,W,pad] (10 real channels, zero padded to the 64-byte pitch), H and W multiples of 16: the model's frame in training, any
+        frame in inference (the network is fully convolutional; backward() takes the training frame).  Returns gen_Y [N,H,W,1].
         attn: attention_forward()'s maps ([B,...], N a multiple of B: image i is a copy of sample i % B): added to the four
         skip tensors, `down_k + attn_k` (SHM.py:290-293); the pooled path keeps the un-augmented tensor.
         parts = 2 (experiment, not the trainer's default): the batch is evaluated as two halves, the second one on the second
@@ -648,9 +677,9 @@ class Generator(_ModelBase):
             if attn is not None:
                 skip = A.get(f"{tag}/skip{lvl}", (n, h, w, ld), self.adt)
                 ops.add_bcast(cur[r0:r1], attn[lvl], skip[r0:r1], nb, h * w * ld, self._attn_B, r0)
-                downs.append((skip, ld, h, None))
+                downs.append((skip, ld, (h, w), None))
             else:
-                downs.append((cur, ld, h, cur_nt))
+                downs.append((cur, ld, (h, w), cur_nt))
             cur, cur_nt, h, w = pooled, None, h // 2, w // 2
         for _ in range(2):                       # the two 1x1 blocks
             cur, r = self._cnl_fwd(tag, li, bi, cur, None, 0, ld, 0, n, h, w, r0, r1, part, sync=sync)
@@ -669,11 +698,11 @@ class Generator(_ModelBase):
             if sync is not None:
                 sync.after(part)
             yield
-            ups.append(dict(li=li, x=cur, ldx=ld, u=u, h=h))
+            ups.append(dict(li=li, x=cur, ldx=ld, u=u, h=h, w=w))
             li += 1
             h, w = 2 * h, 2 * w
             skip, sld, sh, skip_nt = downs[3 - lvl]
-            assert sh == h
+            assert sh == (h, w)
             cur, r = self._cnl_fwd(tag, li, bi, u, skip, cout, cout, sld, n, h, w, r0, r1, part, sync=sync, ntx2=skip_nt,
                                    fold=plan.get(li, False))                                                  # concat [u, skip]
             cur_nt = r["nt"]
@@ -768,34 +797,35 @@ class Generator(_ModelBase):
         return dz
 
     def backward(self, dy, tag, need_dx=False, on_wgrad=None):
-        """dy: gradient wrt gen_Y [N,S,S,1].  Accumulates into the flat gradient (+ f64 region).
+        """dy: gradient wrt gen_Y [N,H,W,1] on the model's frame.  Accumulates into the flat gradient (+ f64 region).
         on_wgrad(li): called right after the weight gradient of layer li has been issued on the wgrad lane (the
         data-parallel trainer launches the gradient bucket that layer completes).
         need_dx=True: returns the gradient wrt the padded input (channels 0..9 valid).
-        need_dx="dz": returns the first layer's pre-activation gradient dz [N,S,S,F] instead -- the caller only
+        need_dx="dz": returns the first layer's pre-activation gradient dz [N,H,W,F] instead -- the caller only
         needs channel sums of the input gradient and forms them with ops.conv3x3_dgrad_sum1 (no 64->10 dgrad)."""
         c = self.ctx[tag]
         n, recs, ups = c["n"], c["recs"], c["ups"]
         A = self.arena
-        S, F = self.S, self.F
-        assert tuple(c["y"].shape[1:3]) == (S, S), f"backward takes the square training shape {S} x {S}, the forward ran on {tuple(c['y'].shape[1:3])}"
+        H, W, F = self.H, self.W, self.F
+        assert tuple(c["y"].shape[1:3]) == (H, W), \
+            f"backward takes the {'square ' if H == W else ''}training shape {H} x {W}, the forward ran on {tuple(c['y'].shape[1:3])}"
         nl = len(self.layers)
         self._on_wgrad = on_wgrad
         try:
-            return self._backward(dy, c, n, recs, ups, A, S, F, nl, tag, need_dx)
+            return self._backward(dy, c, n, recs, ups, A, H, W, F, nl, tag, need_dx)
         finally:
             self._on_wgrad = None
 
-    def _backward(self, dy, c, n, recs, ups, A, S, F, nl, tag, need_dx):
+    def _backward(self, dy, c, n, recs, ups, A, H, W, F, nl, tag, need_dx):
         # head
         # head: weight / bias gradients and the scalar factor hdz of its input gradient (hdz (x) w is never written: the
         # backward of the block in front of the head forms it on the fly)
         hx = c["head_x"]
-        hdz = A.get(f"bwd/hdz/{n}x{S}", (n, S, S), torch.float32)
+        hdz = A.get(f"bwd/hdz/{n}x{H}x{W}", (n, H, W), torch.float32)
         hred = A.get(f"bwd/hred/{F}", (ops.LRELU_RED_SLOTS * (F + 1),), torch.float64)
         hr = c["head_rec"]
         ops.head_in_bwd(hx, F, hr["stats"], self.betas[hr["bi"]], self.P.vars[2 * (nl - 1)], c["y"], dy, None, 0, self._acc_slice(2 * (nl - 1)),
-                        self._acc_slice(2 * (nl - 1) + 1), n, S * S, F, LRELU, hred, dz_out=hdz)
+                        self._acc_slice(2 * (nl - 1) + 1), n, H * W, F, LRELU, hred, dz_out=hdz)
         dcur = None
         ri = len(recs) - 1
         dskips = [None] * 4
@@ -803,48 +833,48 @@ class Generator(_ModelBase):
             up = ups[lvl]
             r2, r1 = recs[ri], recs[ri - 1]
             ri -= 2
-            h = r2["h"]
+            h, w = r2["h"], r2["w"]
             cout = self.layers[r2["li"]][4]
-            dmid = A.get(f"bwd/dm/{n}x{h}x{cout}", (n, h, h, cout), self.gdt)
+            dmid = A.get(f"bwd/dm/{n}x{h}x{w}x{cout}", (n, h, w, cout), self.gdt)
             self._cnl_bwd(tag, r2, dcur, None, n, True, dmid, None, cout,
                           rank1=(hdz, self.P.vars[2 * (nl - 1)].reshape(-1)) if lvl == 3 else None, gsum=self._gsum(r1))
             # concat block: split gradient into (du, dskip); dskip is the gradient at the encoder block's InstanceNorm output
             # (live attention adds its map to the skip: the same gradient)
             cu = r1["c1"]
             cs = self.layers[r1["li"]][3] - cu
-            du = A.get(f"bwd/du/{n}x{h}x{cu}", (n, h, h, cu), self.gdt)
-            dsk = A.get(f"bwd/dskip{3 - lvl}/{n}x{h}x{cs}", (n, h, h, cs), self.gdt)
+            du = A.get(f"bwd/du/{n}x{h}x{w}x{cu}", (n, h, w, cu), self.gdt)
+            dsk = A.get(f"bwd/dskip{3 - lvl}/{n}x{h}x{w}x{cs}", (n, h, w, cs), self.gdt)
             enc2 = recs[2 * (3 - lvl) + 1]                           # second block of encoder level 3 - lvl
             self._cnl_bwd(tag, r1, dmid, None, n, True, du, dsk, cu, gsum2=self._gsum(enc2))
             dskips[3 - lvl] = dsk
             if c["attn"]:                       # d attn_k = sum of the skip gradient over every copy of the sample
                 B = self._attn_B                # (state reset by zero_grad() at the start of every step)
-                da = A.get(f"bwd/dattn{3 - lvl}/{B}", (B, h, h, cs), self.gdt)
-                ops.sum_groups(dsk, da, n, h * h * cs, B, 0, accumulate=self._dattn[3 - lvl] is not None)
+                da = A.get(f"bwd/dattn{3 - lvl}/{B}", (B, h, w, cs), self.gdt)
+                ops.sum_groups(dsk, da, n, h * w * cs, B, 0, accumulate=self._dattn[3 - lvl] is not None)
                 self._dattn[3 - lvl] = da
             # Conv2DTranspose: LeakyReLU', bias grad, wgrad (roles swapped), dgrad = stride-2 conv
             tli = up["li"]
             _, _, _, tcin, tcout = self.layers[tli]
-            dzu = A.get(f"bwd/dzu/L{tli}/{n}", (n, h, h, cu), self.adt)
+            dzu = A.get(f"bwd/dzu/L{tli}/{n}", (n, h, w, cu), self.adt)
             lred = A.get(f"bwd/lred/{cu}", (ops.LRELU_RED_SLOTS * cu,), torch.float64)
-            ops.lrelu_bwd(du, cu, up["u"], cu, dzu, cu, self._acc_slice(2 * tli + 1), n * h * h, cu, LRELU, lred)
-            ws = self.ws_provider(ops.conv2d_wgrad_workspace(n, h // 2, h // 2, tcout, tcin, 3))
-            self.lane.submit(lambda dzu=dzu, up=up, tli=tli, tcout=tcout, tcin=tcin, h=h, ws=ws: ops.conv2d_wgrad(
-                dzu, None, 0, tcout, 0, up["x"], up["ldx"], self.P.grads[2 * tli], n, h, h, tcout, tcout, tcin, 3, 2, 1, ws))
+            ops.lrelu_bwd(du, cu, up["u"], cu, dzu, cu, self._acc_slice(2 * tli + 1), n * h * w, cu, LRELU, lred)
+            ws = self.ws_provider(ops.conv2d_wgrad_workspace(n, h // 2, w // 2, tcout, tcin, 3))
+            self.lane.submit(lambda dzu=dzu, up=up, tli=tli, tcout=tcout, tcin=tcin, h=h, w=w, ws=ws: ops.conv2d_wgrad(
+                dzu, None, 0, tcout, 0, up["x"], up["ldx"], self.P.grads[2 * tli], n, h, w, tcout, tcout, tcin, 3, 2, 1, ws))
             if self._on_wgrad is not None:
                 self._on_wgrad(tli)
-            hin = up["h"]
-            dcur = A.get(f"bwd/d/{n}x{hin}x{tcin}", (n, hin, hin, tcin), self.gdt)
+            hin, win = up["h"], up["w"]
+            dcur = A.get(f"bwd/d/{n}x{hin}x{win}x{tcin}", (n, hin, win, tcin), self.gdt)
             # input gradient of the Conv2DTranspose = the stride-2 forward form; it writes the gradient at the InstanceNorm output
             # of the block below (recs[ri] after the two decrements above: the previous level's second block, or the bottleneck's)
-            ops.conv2d_fwd(dzu, None, 0, tcout, 0, self.wk[tli], None, dcur, tcin, n, h, h, tcout, tcin, 3, 2, 1.0, gsum=self._gsum(recs[ri]))
+            ops.conv2d_fwd(dzu, None, 0, tcout, 0, self.wk[tli], None, dcur, tcin, n, h, w, tcout, tcin, 3, 2, 1.0, gsum=self._gsum(recs[ri]))
         # bottleneck 1x1 blocks
         for j in range(2):
             r = recs[ri]
             ri -= 1
-            h = r["h"]
+            h, w = r["h"], r["w"]
             cin = self.layers[r["li"]][3]
-            dn = A.get(f"bwd/db{ri}/{n}x{h}x{cin}", (n, h, h, cin), self.gdt)
+            dn = A.get(f"bwd/db{ri}/{n}x{h}x{w}x{cin}", (n, h, w, cin), self.gdt)
             # the first 1x1 block's input gradient is the gradient of pool 4: sums against the pooled tensor of encoder level 3
             self._cnl_bwd(tag, r, dcur, None, n, True, dn, None, cin, gsum=self._gsum(recs[ri]) if j == 0 else self._gsum(recs[ri], pooled=True))
             dcur = dn
@@ -852,17 +882,17 @@ class Generator(_ModelBase):
         for lvl in range(3, -1, -1):
             r2, r1 = recs[ri], recs[ri - 1]
             ri -= 2
-            h = r2["h"]
+            h, w = r2["h"], r2["w"]
             cout = self.layers[r2["li"]][4]
-            dmid = A.get(f"bwd/dm/{n}x{h}x{cout}", (n, h, h, cout), self.gdt)
+            dmid = A.get(f"bwd/dm/{n}x{h}x{w}x{cout}", (n, h, w, cout), self.gdt)
             self._cnl_bwd(tag, r2, dskips[lvl], dpool, n, True, dmid, None, cout, gsum=self._gsum(r1))
             cin = self.layers[r1["li"]][3]
             if lvl > 0:
-                dpool = A.get(f"bwd/dp/{n}x{h}x{cin}", (n, h, h, cin), self.gdt)
+                dpool = A.get(f"bwd/dp/{n}x{h}x{w}x{cin}", (n, h, w, cin), self.gdt)
                 self._cnl_bwd(tag, r1, dmid, None, n, True, dpool, None, cin, gsum=self._gsum(recs[ri], pooled=True))
             else:
                 if need_dx is True:
-                    dx16 = A.get(f"bwd/dx16/{n}", (n, h, h, self.pad), self.gdt)
+                    dx16 = A.get(f"bwd/dx16/{n}", (n, h, w, self.pad), self.gdt)
                     self._cnl_bwd(tag, r1, dmid, None, n, True, dx16, None, cin)
                     return dx16
                 dz0 = self._cnl_bwd(tag, r1, dmid, None, n, False)
@@ -887,18 +917,31 @@ class Generator(_ModelBase):
         return [(t > 0).cpu().numpy() for t in self.lrelu_tensors(tag)]
 
     def __call__(self, x, training=False, tag="call"):
-        """Keras-style call on a [N,S,S,10] tensor (reference: self.G(x, training=...))."""
+        """Keras-style call on a [N,H,W,10] tensor (reference: self.G(x, training=...))."""
         n = x.shape[0]
-        x16 = self.arena.get(f"{tag}/x16", (n, self.S, self.S, self.pad), self.adt)
+        x16 = self.arena.get(f"{tag}/x16", (n, self.H, self.W, self.pad), self.adt)
         x16.zero_()
         x16[..., :10].copy_(x)
         return self.forward(x16, tag)
 
+    def output_shapes(self):
+        """Keras-style output shape (None, h, w, c) of every layer on the model's frame, in layer order: two convolutions per encoder
+        level (a 2x2 pool behind each level), the two 1x1 blocks, then Conv2DTranspose + two convolutions per decoder level, the head."""
+        h, w, out = self.H, self.W, []
+        for i, (_, kind, _, _, cout) in enumerate(self.layers):
+            if kind == "t":
+                h, w = 2 * h, 2 * w
+            out.append((None, h, w, cout))
+            if kind == "c" and i < 8 and i % 2 == 1:
+                h, w = h // 2, w // 2
+        return out
+
     def summary(self, print_fn=print):
         print_fn(f'Model: "{self.name}"')
+        shapes = self.output_shapes()
         for i, (name, kind, k, cin, cout) in enumerate(self.layers):
             cnt = self.P.vars[2 * i].numel() + self.P.vars[2 * i + 1].numel()
-            print_fn(f"{name:24s} {'Conv2DTranspose' if kind == 't' else 'Conv2D':16s} k={k} {cin}->{cout}  {cnt}")
+            print_fn(f"{name:24s} {'Conv2DTranspose' if kind == 't' else 'Conv2D':16s} k={k} {cin}->{cout}  {str(shapes[i]):24s} {cnt}")
         print_fn(f"Total params: {self.P.n:,}")
 
 
@@ -910,7 +953,9 @@ class Discriminator(_ModelBase):
 
     def __init__(self, image_size, filter_size, device, arena, ws_provider, dropout=0.2, lane=None, dtype=torch.float32,
                  grad_dtype=None, attention=False):
-        self.S, self.F, self.dev = image_size, filter_size, device
+        # image_size: the training frame, a side or a pair (H, W); S is the side of a square frame and None otherwise
+        self.H, self.W = frame_hw(image_size)
+        self.S, self.F, self.dev = (self.H if self.H == self.W else None), filter_size, device
         self.attention = bool(attention)
         self.arena, self.ws_provider = arena, ws_provider
         self.lane = lane or WgradLane(device, enabled=False)
@@ -926,12 +971,13 @@ class Discriminator(_ModelBase):
             self.in_pitch = self.pad
         self.gsum = ops.gsum_default(dtype)
         self.dropout = dropout
-        assert image_size % 32 == 0
-        f, s = filter_size, image_size // 32
-        self.s = s
+        assert self.H % 32 == 0 and self.W % 32 == 0, "the discriminator has five stride-2 blocks: the sides are multiples of 32"
+        f = filter_size
+        self.sh, self.sw = self.H // 32, self.W // 32          # the PatchGAN map; s is its side on a square frame
+        self.s = self.sh if self.sh == self.sw else None
         self.chan = [3, f, 2 * f, 4 * f, 8 * f, 16 * f]
         shapes = [(3, 3, self.chan[i], self.chan[i + 1]) for i in range(5)]
-        shapes += [(3, 3, 16 * f, 1), (s * s * 16 * f, 5)]
+        shapes += [(3, 3, 16 * f, 1), (dense_inputs((self.H, self.W), f), 5)]
         self.names = ["conv2d_27", "conv2d_28", "conv2d_29", "conv2d_30", "conv2d_33", "conv2d_34", "dense"]
         order = list(range(7))
         if self.attention:            # attention_layer(8F, pool 16x16) (SHM.py:358): [k 1->8F, b, k 8F->8F, b], biases stored last
@@ -978,13 +1024,13 @@ class Discriminator(_ModelBase):
         return self.acc[o:o + self.P.vars[var_index].numel()]
 
     def attention_forward(self, mask, B):
-        """attn_disc (SHM.py:358) of the step's SpecSeg mask [B,S,S,1]; pass the result to forward(attn=)."""
+        """attn_disc (SHM.py:358) of the step's SpecSeg mask [B,H,W,1]; pass the result to forward(attn=)."""
         self.prepare_weights()
         self._attn_B = B
-        return self.attn.forward(mask, B, self.S)
+        return self.attn.forward(mask, B, self.H, self.W)
 
     def forward(self, xd16, keep_mask=None, mask_rows=(), parts=None, attn=None, join=None):
-        """xd16 [N,S,S,16] (rgb + zeros).  keep_mask [len(mask_rows)...] is the Dropout keep mask of
+        """xd16 [N,H,W,16] (rgb + zeros).  keep_mask [len(mask_rows)...] is the Dropout keep mask of
         the `training=True` samples: mask_rows = list of (row_start, nrows, mask_row_start).
         parts: optional list of (row0, row1, run) -- the conv trunk is evaluated per row range (samples
         are independent: InstanceNorm) through `run(fn)`; the trainer uses it to push the real-image
@@ -1004,39 +1050,39 @@ class Discriminator(_ModelBase):
         """Declare the batch of the next forward (buffers only); follow with trunk_rows(...) over
         every row and heads().  attn: attention_forward()'s map [B,...] (batch a multiple of B, image i = a copy of sample
         i % B): added after the fourth block, `x + attn_disc` (SHM.py:359)."""
-        n, S = xd16.shape[0], self.S
+        n = xd16.shape[0]
         self.prepare_weights()
         A = self.arena
         bufs = []
-        h = S
+        h, w = self.H, self.W
         for i in range(5):
             cout = self.chan[i + 1]
-            ho = h // 2
-            bufs.append((A.get(f"d/a{i}/{n}", (n, ho, ho, cout), self.adt), A.get(f"d/h{i}/{n}", (n, ho, ho, cout), self.adt),
+            ho, wo = h // 2, w // 2
+            bufs.append((A.get(f"d/a{i}/{n}", (n, ho, wo, cout), self.adt), A.get(f"d/h{i}/{n}", (n, ho, wo, cout), self.adt),
                          A.get(f"d/s{i}/{n}", (n * cout * 2,), torch.float64)))
-            h = ho
-        x3p = A.get(f"d/x3p/{n}", (n, S // 16, S // 16, self.chan[4]), self.adt) if attn is not None else None
+            h, w = ho, wo
+        x3p = A.get(f"d/x3p/{n}", (n, self.H // 16, self.W // 16, self.chan[4]), self.adt) if attn is not None else None
         self._pending = dict(n=n, xd16=xd16, bufs=bufs, keep_mask=keep_mask, mask_rows=mask_rows, attn=attn, x3p=x3p)
 
     def trunk_rows(self, r0, r1):
         """The five Conv(3x3, s2) -> LeakyReLU -> InstanceNorm blocks on samples [r0, r1)."""
         xd16, bufs = self._pending["xd16"], self._pending["bufs"]
         nb = r1 - r0
-        cur, ld, h = xd16[r0:r1], xd16.shape[-1], self.S
+        cur, ld, h, w = xd16[r0:r1], xd16.shape[-1], self.H, self.W
         for i in range(5):
             cin, cout = self.chan[i], self.chan[i + 1]
-            ho = h // 2
+            ho, wo = h // 2, w // 2
             a, ahat, stats = bufs[i]
             st = stats[r0 * cout * 2:r1 * cout * 2]
             # keyed by the row range: two parts evaluated on two streams must not share a zero-on-entry scratch
             scr = self.arena.get(f"d/stats_scratch/{r0}:{r1}/{cout}", (ops.STATS_SLOTS * nb * cout * 2,), torch.float64)
-            ops.conv2d_in_fwd(cur, None, 0, ld, 0, self.wk[i], None, a[r0:r1], cout, nb, h, h, _padk(cin, self.pad), cout, 3, 2,
+            ops.conv2d_in_fwd(cur, None, 0, ld, 0, self.wk[i], None, a[r0:r1], cout, nb, h, w, _padk(cin, self.pad), cout, 3, 2,
                               LRELU, st, IN_EPS, cin_real=cin, scratch=scr)
-            ops.in_apply(a[r0:r1], cout, st, self.betas[i], ahat[r0:r1], cout, nb, ho * ho, cout)
-            cur, ld, h = ahat[r0:r1], cout, ho
+            ops.in_apply(a[r0:r1], cout, st, self.betas[i], ahat[r0:r1], cout, nb, ho * wo, cout)
+            cur, ld, h, w = ahat[r0:r1], cout, ho, wo
             if i == 3 and self._pending["attn"] is not None:
                 x3p = self._pending["x3p"]
-                ops.add_bcast(cur, self._pending["attn"], x3p[r0:r1], nb, ho * ho * cout, self._attn_B, r0)
+                ops.add_bcast(cur, self._pending["attn"], x3p[r0:r1], nb, ho * wo * cout, self._attn_B, r0)
                 cur = x3p[r0:r1]
 
     def heads(self):
@@ -1046,21 +1092,21 @@ class Discriminator(_ModelBase):
         keep_mask, mask_rows = pd["keep_mask"], pd["mask_rows"]
         A = self.arena
         recs = []
-        cur, ld, h = xd16, xd16.shape[-1], self.S
+        cur, ld, h, w = xd16, xd16.shape[-1], self.H, self.W
         for i in range(5):
             a, ahat, stats = bufs[i]
-            recs.append(dict(x=cur, ldx=ld, a=a, stats=stats, h=h))
-            cur, ld, h = ahat, self.chan[i + 1], h // 2
+            recs.append(dict(x=cur, ldx=ld, a=a, stats=stats, h=h, w=w))
+            cur, ld, h, w = ahat, self.chan[i + 1], h // 2, w // 2
             if i == 3 and pd["x3p"] is not None:
                 cur = pd["x3p"]
         c5 = self.chan[5]
-        per = h * h * c5
+        per = h * w * c5
         scale = 1.0 / (1.0 - self.dropout)
         for r0, nr, m0 in mask_rows:                 # Dropout on the training=True samples, in place
             ops.mul_mask(cur[r0:r0 + nr], keep_mask[m0:m0 + nr], cur[r0:r0 + nr], nr * per, scale)
-        rf = A.get(f"d/rf/{n}", (n, h, h, 1))
+        rf = A.get(f"d/rf/{n}", (n, h, w, 1))
         cls = A.get(f"d/cls/{n}", (n, 5))
-        ops.patch_fwd(cur, c5, self.P.vars[5], rf, n, h, h, c5, LRELU)
+        ops.patch_fwd(cur, c5, self.P.vars[5], rf, n, h, w, c5, LRELU)
         ops.dense_fwd(cur, self.P.vars[6], cls, n, per, 5)
         self.ctx = dict(n=n, recs=recs, x5=cur, rf=rf, cls=cls, keep_mask=keep_mask, mask_rows=mask_rows, attn=pd["attn"] is not None)
         return rf, cls
@@ -1070,12 +1116,12 @@ class Discriminator(_ModelBase):
         gradients; need_dx: return the gradient wrt the 16-pitch input."""
         c = self.ctx
         A = self.arena
-        s, c5 = self.s, self.chan[5]
-        per = s * s * c5
+        sh, sw, c5 = self.sh, self.sw, self.chan[5]
+        per = sh * sw * c5
         x5 = c["x5"]
-        dz_p = A.get(f"d/bwd/dzp/{n}", (n, s, s, 1))
-        dx5 = A.get(f"d/bwd/dx5/{n}", (n, s, s, c5), self.gdt)
-        ops.patch_bwd(x5, c5, self.P.vars[5], c["rf"], drf, dz_p, dx5, c5, self.P.grads[5] if params else None, n, s, s,
+        dz_p = A.get(f"d/bwd/dzp/{n}", (n, sh, sw, 1))
+        dx5 = A.get(f"d/bwd/dx5/{n}", (n, sh, sw, c5), self.gdt)
+        ops.patch_bwd(x5, c5, self.P.vars[5], c["rf"], drf, dz_p, dx5, c5, self.P.grads[5] if params else None, n, sh, sw,
                       c5, LRELU)
         if dcls is not None:
             ops.dense_bwd(x5, self.P.vars[6], dcls, dx5, self.P.grads[6] if params else None, n, per, 5)
@@ -1088,38 +1134,38 @@ class Discriminator(_ModelBase):
         for i in range(4, -1, -1):
             rec = c["recs"][i]
             cin, cout = self.chan[i], self.chan[i + 1]
-            h = rec["h"]
-            ho = h // 2
-            dz = A.get(f"d/bwd/dz{i}/{n}", (n, ho, ho, cout), self.adt)
+            h, w = rec["h"], rec["w"]
+            ho, wo = h // 2, w // 2
+            dz = A.get(f"d/bwd/dz{i}/{n}", (n, ho, wo, cout), self.adt)
             if gred is not None:           # the stride-2 input gradient below delivered this block's sums: one pass instead of two
-                ops.in_bwd_apply(dcur, cout, None, 0, rec["a"][:n], cout, rec["stats"], self.betas[i], gred, None, None, dz, cout, None, n, ho, ho,
+                ops.in_bwd_apply(dcur, cout, None, 0, rec["a"][:n], cout, rec["stats"], self.betas[i], gred, None, None, dz, cout, None, n, ho, wo,
                                  cout, LRELU)
             else:
                 red = A.get(f"d/bwd/red{i}/{n}", (n * cout * 3,), torch.float64)
-                ops.in_bwd(dcur, cout, None, 0, rec["a"], cout, rec["stats"], red, dz, cout, None, n, ho, ho, cout, LRELU,
-                           fused=_fused_scratch(A, self.adt, n, ho * ho, cout), abort=A.abort)
+                ops.in_bwd(dcur, cout, None, 0, rec["a"], cout, rec["stats"], red, dz, cout, None, n, ho, wo, cout, LRELU,
+                           fused=_fused_scratch(A, self.adt, n, ho * wo, cout), abort=A.abort)
             gred = None
             if params:
-                ws = self.ws_provider(ops.conv2d_wgrad_workspace(n, ho, ho, cin, cout, 3))
-                self.lane.submit(lambda rec=rec, dz=dz, i=i, h=h, cin=cin, cout=cout, ws=ws: ops.conv2d_wgrad(
-                    rec["x"], None, 0, rec["ldx"], 0, dz, cout, self.P.grads[i], n, h, h, cin, _padk(cin, self.pad), cout, 3, 2, 0, ws))
+                ws = self.ws_provider(ops.conv2d_wgrad_workspace(n, ho, wo, cin, cout, 3))
+                self.lane.submit(lambda rec=rec, dz=dz, i=i, h=h, w=w, cin=cin, cout=cout, ws=ws: ops.conv2d_wgrad(
+                    rec["x"], None, 0, rec["ldx"], 0, dz, cout, self.P.grads[i], n, h, w, cin, _padk(cin, self.pad), cout, 3, 2, 0, ws))
             if i == 0 and need_dx == "dz":
                 return dz
             if i > 0 or need_dx:
                 ldx = rec["ldx"]
                 # i == 0: the image gradient in the compact pitch (3 channels in a 4- / 8-element pixel).  The input-gradient kernels write the
                 # real channels only; the pad slot is zero because the buffer is allocated zero-filled, once (advisor finding, round 4)
-                dprev = A.get_slack(f"d/bwd/dx{i}/{n}", (n, h, h, ldx), self.gdt, 0) if i == 0 else A.get(f"d/bwd/dx{i}/{n}", (n, h, h, ldx), self.gdt)
+                dprev = A.get_slack(f"d/bwd/dx{i}/{n}", (n, h, w, ldx), self.gdt, 0) if i == 0 else A.get(f"d/bwd/dx{i}/{n}", (n, h, w, ldx), self.gdt)
                 gs = None
                 if i > 0 and self.gsum:          # dprev is the gradient at block i-1's InstanceNorm output: its sums come with it
                     gred = A.get(f"d/bwd/gred{i - 1}/{n}", (ops.GSUM_SLOTS * n * cin * 2,), torch.float64)
                     gs = (c["recs"][i - 1]["a"], cin, gred)
-                ops.conv2d_dgrad(dz, cout, self.P.op_vars[i], dprev, None, cin, ldx, 0, n, h, h, cin, cout, 3, 2, gsum=gs)
+                ops.conv2d_dgrad(dz, cout, self.P.op_vars[i], dprev, None, cin, ldx, 0, n, h, w, cin, cout, 3, 2, gsum=gs)
                 dcur = dprev
                 if i == 4 and params and c["attn"]:          # d attn_disc = sum over the copies of each sample; then its branch
                     B = self._attn_B
-                    da = A.get(f"d/bwd/dattn/{B}", (B, h, h, cin), self.gdt)
-                    ops.sum_groups(dprev, da, n, h * h * cin, B, 0)
+                    da = A.get(f"d/bwd/dattn/{B}", (B, h, w, cin), self.gdt)
+                    ops.sum_groups(dprev, da, n, h * w * cin, B, 0)
                     self.attn.backward(da)
         return dcur if need_dx else None
 
@@ -1134,7 +1180,7 @@ class Discriminator(_ModelBase):
         return self._backward(n, drf, None, False, True)
 
     def backward_input_dz(self, n, drf):
-        """Same, but stops at the first layer's pre-activation gradient dz [n,S/2,S/2,F]: the step only needs the
+        """Same, but stops at the first layer's pre-activation gradient dz [n,H/2,W/2,F]: the step only needs the
         r+g+b sum of the image gradient, which ops.conv3x3_dgrad_sum1 forms from dz (no 64->3 dgrad)."""
         return self._backward(n, drf, None, False, "dz")
 
@@ -1151,15 +1197,26 @@ class Discriminator(_ModelBase):
         return [(t > 0).cpu().numpy() for t in self.lrelu_tensors()]
 
     def __call__(self, x, training=False, noise=None, keep_mask=None):
-        """Keras-style call on [N,S,S,3] (reference: self.D(x, training=...))."""
+        """Keras-style call on [N,H,W,3] (reference: self.D(x, training=...))."""
         n = x.shape[0]
-        xd = self.arena.get_slack(f"dcall/x16/{n}", (n, self.S, self.S, self.in_pitch), self.adt, self.pad)
-        ops.pack_rgb16(x.contiguous(), noise if training else None, xd, n * self.S * self.S)
+        xd = self.arena.get_slack(f"dcall/x16/{n}", (n, self.H, self.W, self.in_pitch), self.adt, self.pad)
+        ops.pack_rgb16(x.contiguous(), noise if training else None, xd, n * self.H * self.W)
         rows = [(0, n, 0)] if (training and keep_mask is not None) else []
         return self.forward(xd, keep_mask, rows)
 
+    def output_shapes(self):
+        """{layer name: Keras-style output shape} on the model's frame: the five stride-2 blocks, the PatchGAN map, the classifier
+        (and the attention branch's two convolutions on the mask pooled by 16)."""
+        out = {nme: (None, self.H >> (i + 1), self.W >> (i + 1), self.chan[i + 1]) for i, nme in enumerate(self.names[:5])}
+        out[self.names[5]] = (None, self.sh, self.sw, 1)
+        out[self.names[6]] = (None, 5)
+        if self.attention:
+            out["conv2d_31"] = out["conv2d_32"] = (None, self.H // 16, self.W // 16, self.chan[4])
+        return out
+
     def summary(self, print_fn=print):
         print_fn(f'Model: "{self.name}"')
+        shapes = self.output_shapes()
         for nme, v in zip(self.names, self.P.vars):
-            print_fn(f"{nme:24s} {tuple(v.shape)}  {v.numel()}")
+            print_fn(f"{nme:24s} {str(tuple(v.shape)):24s} {str(shapes.get(nme, '')):24s} {v.numel()}")
         print_fn(f"Total params: {self.P.n:,}")

@@ -559,6 +559,18 @@ def image_losses(gen_rgb, cyc_rgb, cyc_y, cbcr, orig_ptrs, ds_ptrs, flags_mask, 
                                  ws.numel() * ws.element_size(), batch, s, _stream()), "shm_image_losses")
 
 
+def image_losses_hw_workspace(batch, h, w):
+    return int(lib().shm_image_losses_hw_workspace(batch, h, w))
+
+
+def image_losses_hw(gen_rgb, cyc_rgb, cyc_y, cbcr, orig_ptrs, ds_ptrs, flags_mask, style_factor, loss, dgen_y, dcyc_y,
+                    ws, batch, h, w):
+    """image_losses on [.,h,w,c] tensors (shm_image_losses_hw; the square call is this one with h = w = s)."""
+    check(lib().shm_image_losses_hw(_p(gen_rgb), _p(cyc_rgb), _p(cyc_y), _p(cbcr), orig_ptrs, ds_ptrs, flags_mask,
+                                    style_factor, _p(loss), _p(dgen_y), _p(dcyc_y), _p(ws),
+                                    ws.numel() * ws.element_size(), batch, h, w, _stream()), "shm_image_losses_hw")
+
+
 # ---- image-quality metrics of the reference's test mode (test.py:332-392) --------------------------------------
 METRIC_NAMES = ("mse", "psnr", "ssim", "de76", "de94")          # the columns of image_metrics' result
 _METRIC_ARENAS = {}

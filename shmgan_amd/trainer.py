@@ -30,7 +30,7 @@ import torch
 from . import checkpoint, dist, ops, validation
 from .data import Augment, MaskDataset, datasetLoad, gib_to_bytes
 from .dist import GradReducer, exchange_active, world_size
-from .model import Arena, Discriminator, Generator, WgradLane, pad_channels
+from .model import Arena, Discriminator, Generator, WgradLane, check_image_hw, pad_channels
 from .specseg import SpecSeg
 from .telemetry import LOSS_NAMES, WEIGHT_SETS, NonFiniteGradientError, Telemetry, compose_losses, region_options, telemetry_options, validation_options  # noqa: F401
 
@@ -52,7 +52,7 @@ class _Optimizer:
         P.iterations += 1
 
 
-_DEFAULTS = dict(image_size=128, batch_size=1, filter_size=64, g_lr=0.00002, d_lr=0.00002, beta1=0.5, beta2=0.99,
+_DEFAULTS = dict(image_size=128, image_hw=None, batch_size=1, filter_size=64, g_lr=0.00002, d_lr=0.00002, beta1=0.5, beta2=0.99,
                  c_dim=5, num_epochs=200, num_iteration_decay=100000, n_critic=5, d_repeat_num=6, mode="train",
                  data_dir="", model_save_dir="./models", checkpoint_save_dir="./checkpoints", result_dir="./results",
                  log_dir="./logs/train", log_step=1, checkpoint_save_step=10, calc_metrics=False, test_dir="", diffuse_dir="",
@@ -92,7 +92,10 @@ class ShmGANwithSSpecSeg:
         attention: "executed" (default) = the graph the reference runs: attention_layer is evaluated once on a constant zero
         mask at build time, so the skips get + 0 (SURVEY finding 3); "live" = the architecture as intended: every step's
         SpecSeg mask goes through attention_layer (MaxPool -> 2 x Conv3x3 + LeakyReLU, SHM.py:404-412) into the four
-        generator skips (SHM.py:290-293) and the discriminator (SHM.py:359), its 10 convolutions are trained."""
+        generator skips (SHM.py:290-293) and the discriminator (SHM.py:359), its 10 convolutions are trained.
+        image_hw = (H, W) (keyword or args.image_hw; default None = (image_size, image_size)): the frame the GAN trains, validates
+        and runs model-size test mode on; H and W multiples of 32, at least 32 (model.check_image_hw).  `image_size` keeps its
+        meaning for what stays square: the mask network's own training."""
         assert attention in ("executed", "live")
         self.attention = attention
         # "executed" (default): the classification-loss gradient as TensorFlow computes it -- the fused
@@ -117,6 +120,7 @@ class ShmGANwithSSpecSeg:
                   "beta1", "beta2", "d_repeat_num", "mode", "data_dir", "model_save_dir", "checkpoint_save_dir",
                   "result_dir", "log_dir", "log_step", "checkpoint_save_step", "filter_size"):
             setattr(self, k, a[k])
+        self._image_hw = check_image_hw(a["image_hw"])       # None, or the checked pair
         # SHM.py:157-212
         self.seed, self.randomness, self.dropout_amnt = 25, 0.50, 0.2
         self.TARGET_LABELS = 0.90
@@ -174,7 +178,19 @@ class ShmGANwithSSpecSeg:
         self.d_fwd_on_lane = os.environ.get("SHM_D_FWD_LANE", "1" if self.compute_dtype != torch.float32 else "0") == "1"
         self.img_loss_on_lane = os.environ.get("SHM_IMG_LOSS_LANE", "1" if self.compute_dtype != torch.float32 else "0") == "1"
         self.d_bwd_on_lane = os.environ.get("SHM_D_BWD_LANE", "1" if self.compute_dtype != torch.float32 else "0") == "1"
-        self.style_factor = 1.0 / float(2 * 9 * self.image_size * self.image_size) ** 2   # as intended (finding 7)
+        self.style_factor = self._default_style_factor()   # as intended (finding 7)
+
+    def _default_style_factor(self):
+        return 1.0 / float(2 * 9 * self.image_hw[0] * self.image_hw[1]) ** 2
+
+    @property
+    def image_hw(self):
+        """The GAN's frame (H, W), always a pair: the image_hw option, or (image_size, image_size) without it."""
+        return self._image_hw if self._image_hw is not None else (self.image_size, self.image_size)
+
+    def frame_arg(self):
+        """What the loaders and the models are given as the frame: the side without the image_hw option, the pair with it."""
+        return self.image_size if self._image_hw is None else self._image_hw
 
     # ------------------------------------------------------------------ workspace
     def _workspace(self, nbytes):
@@ -278,12 +294,12 @@ class ShmGANwithSSpecSeg:
     # ------------------------------------------------------------------ builders
     def build_generator(self):
         """SHM.py:228-327."""
-        return Generator(self.image_size, self.filter_size, self.device, self.arena, self._workspace, self._get_lane(),
+        return Generator(self.frame_arg(), self.filter_size, self.device, self.arena, self._workspace, self._get_lane(),
                          dtype=self.compute_dtype, grad_dtype=self.grad_dtype, attention=self.attention == "live")
 
     def build_discriminator(self):
         """SHM.py:343-380."""
-        return Discriminator(self.image_size, self.filter_size, self.device, self.arena, self._workspace,
+        return Discriminator(self.frame_arg(), self.filter_size, self.device, self.arena, self._workspace,
                              self.dropout_amnt, self._get_lane(), dtype=self.compute_dtype, grad_dtype=self.grad_dtype,
                              attention=self.attention == "live")
 
@@ -429,15 +445,15 @@ class ShmGANwithSSpecSeg:
         reads G's or D's weights, so train_step(next_batch=) issues it for step t+1 while step t's last gradient bucket is
         still being all-reduced ("the next batch's weight-independent prologue"); buffers are double-buffered
         by `slot`."""
-        A, S = self.arena, self.image_size
+        A, (H, W) = self.arena, self.image_hw
         B = orig[0].shape[0]
         ds, scales = [], []
         for k in range(5):
             y, sc = self.preprocess(orig[k], f"{k}/s{slot}")
             ds.append(y)
             scales.append(sc)
-        cbcr = A.get(f"pre/cbcr/s{slot}", (B, S, S, 2))
-        ops.avg_cbcr(ds, cbcr, B * S * S)
+        cbcr = A.get(f"pre/cbcr/s{slot}", (B, H, W, 2))
+        ops.avg_cbcr(ds, cbcr, B * H * W)
         # specular mask: nothing on the gradient path reads it, so it runs on the second stream beside the generator forward
         lane = self._get_lane()
         if self.SpecSeg is None:
@@ -471,10 +487,10 @@ class ShmGANwithSSpecSeg:
         """Fresh draws of a step: the five RNG flags (SHM.py:509-513) on the host; GaussianNoise(0.1) for the D1 / D2 inputs
         (SHM.py:352) and the Dropout keep mask (SHM.py:363) on the device (shm_randn / shm_keep_mask: Philox keyed by the
         trainer's seed, the step counter and the rank, so replicas draw different noise and agree on the flags)."""
-        S, s = self.image_size, self.image_size // 32
+        H, W = self.image_hw
         flags = tuple(bool(u < self.randomness) for u in self._rng.random(5))
-        noise = self.arena.get("draws/noise", (2 * B, S, S, 3))
-        keep = self.arena.get("draws/keep", (2 * B, s, s, 16 * self.filter_size))
+        noise = self.arena.get("draws/noise", (2 * B, H, W, 3))
+        keep = self.arena.get("draws/keep", (2 * B, H // 32, W // 32, 16 * self.filter_size))
         self._draw_count += 1
         seed = (self.seed << 32) | (self._draw_count & 0xFFFFFFFF)
         ops.randn(noise, 0.1, seed, 2 * dist.rank())
@@ -554,7 +570,7 @@ class ShmGANwithSSpecSeg:
 
     # ------------------------------------------------------------------ the step
     def train_step(self, orig0, orig45, orig90, orig135, origED, *, draws=None, style_factor=None, apply=True, next_batch=None):
-        """One SHM.py:467-875 step: D update + G update from a 5-view batch [B,S,S,3] in [0,1].
+        """One SHM.py:467-875 step: D update + G update from a 5-view batch [B,H,W,3] in [0,1] on the trainer's frame (image_hw).
         next_batch: the five tensors of the FOLLOWING step (or a callable returning them, called late in this step's issue
         order; None when it returns None): their weight-independent prologue (_prologue) is issued before this step waits
         for its last gradient collective, and the next train_step on those same tensors (same storage, not modified in
@@ -565,12 +581,14 @@ class ShmGANwithSSpecSeg:
         if self.telemetry is not None:
             self.telemetry.check()       # non-finite gradients in a histogram that has reached the host (nonfinite="raise" / "warn")
         G, D, A = self.G, self.D, self.arena
-        S, F = self.image_size, self.filter_size
+        (H, W), F = self.image_hw, self.filter_size
         if self._ema_on():
             self._ensure_ema()           # first step with the option on (or behind a checkpoint without an average): the average starts as these weights
         orig = [self._dev(t) for t in (orig0, orig45, orig90, orig135, origED)]
         B = orig[0].shape[0]
-        npix = S * S
+        if tuple(orig[0].shape[1:3]) != (H, W):
+            raise ValueError(f"train_step takes [B,{H},{W},3] views (the trainer's frame), got {tuple(orig[0].shape)}")
+        npix = H * W
         if draws is None:
             draws = self._default_draws(B)
         flags = [bool(f) for f in draws.flags]
@@ -604,7 +622,7 @@ class ShmGANwithSSpecSeg:
 
         adt, PAD_C = self.compute_dtype, self.pad
         # D batch layout: [D1: B][D3: 5B][D2: B][D4: 5B]
-        xd = A.get_slack("d/x16", (12 * B, S, S, D.in_pitch), adt, D.pad)          # one 16-byte chunk per pixel (Discriminator.in_pitch) + a K-row of slack
+        xd = A.get_slack("d/x16", (12 * B, H, W, D.in_pitch), adt, D.pad)          # one 16-byte chunk per pixel (Discriminator.in_pitch) + a K-row of slack
         # The REAL half of the discriminator batch (D2, D4: SHM.py:563, 638-642) depends on no generator output: in bf16 its five convolution
         # blocks run on the second stream beside the generator's forward passes (round 6); the heads wait for `ev_dreal`
         ev_dreal = None
@@ -621,18 +639,18 @@ class ShmGANwithSSpecSeg:
             ev_dreal = lane.event()
 
         # ---- G(1)  SHM.py:517-538
-        gen_in = A.get("g1/in", (B, S, S, PAD_C), adt)
+        gen_in = A.get("g1/in", (B, H, W, PAD_C), adt)
         ops.build_gen_input(ds, None, fmask, 0, gen_in, B, npix)
         gen_Y = G.forward(gen_in, "g1", attn=attn_g)
 
-        gen_rgb = A.get("g1/rgb", (B, S, S, 3))
+        gen_rgb = A.get("g1/rgb", (B, H, W, 3))
         ops.yuv2rgb(gen_Y, cbcr, noise[:B], gen_rgb, xd[0:B], B, B, npix)                  # SHM.py:544-559
 
         # ---- G(2): cyclic  SHM.py:576-624
-        cyc_in = A.get("cyc/in", (5 * B, S, S, PAD_C), adt)
+        cyc_in = A.get("cyc/in", (5 * B, H, W, PAD_C), adt)
         ops.build_gen_input(ds, gen_Y, fmask, 1, cyc_in, B, npix)
         cyc_Y = G.forward(cyc_in, "cyc", attn=attn_g, parts=self.forward_parts)
-        cyc_rgb = A.get("cyc/rgb", (5 * B, S, S, 3))
+        cyc_rgb = A.get("cyc/rgb", (5 * B, H, W, 3))
         ops.yuv2rgb(cyc_Y, cbcr, None, cyc_rgb, xd[B:6 * B], 5 * B, B, npix)
         if not d_real_early:
             pack_real()
@@ -642,17 +660,23 @@ class ShmGANwithSSpecSeg:
         # stream beside the discriminator's forward pass and the G-loss backward through it (round 6: ~0.5 / 1.3 / 1.4 ms of SSIM and L1 passes
         # were exposed per step at B = 8 / S = 512 B = 4 / B = 32); the main stream waits for `ev_img` where it needs them
         il = A.get("loss/img", (32,), torch.float64)
-        dgen_y = A.get("loss/dgen_y", (B, S, S, 1))
-        dcyc_y = A.get("loss/dcyc_y", (5 * B, S, S, 1))
+        dgen_y = A.get("loss/dgen_y", (B, H, W, 1))
+        dcyc_y = A.get("loss/dcyc_y", (5 * B, H, W, 1))
         ws = self._img_ws(B)
         optr = (C.c_void_p * 5)(*[t.data_ptr() for t in orig])
         dptr = (C.c_void_p * 5)(*[t.data_ptr() for t in ds])
         ev_img = None
+
+        def image_losses():         # a square frame goes through the square entry, as it always has (one implementation behind both)
+            if H == W:
+                ops.image_losses(gen_rgb, cyc_rgb, cyc_Y, cbcr, optr, dptr, fmask, sf, il, dgen_y, dcyc_y, ws, B, H)
+            else:
+                ops.image_losses_hw(gen_rgb, cyc_rgb, cyc_Y, cbcr, optr, dptr, fmask, sf, il, dgen_y, dcyc_y, ws, B, H, W)
         if self.img_loss_on_lane and lane.stream is not None:
-            lane.submit(lambda: ops.image_losses(gen_rgb, cyc_rgb, cyc_Y, cbcr, optr, dptr, fmask, sf, il, dgen_y, dcyc_y, ws, B, S))
+            lane.submit(image_losses)
             ev_img = lane.event()
         else:
-            ops.image_losses(gen_rgb, cyc_rgb, cyc_Y, cbcr, optr, dptr, fmask, sf, il, dgen_y, dcyc_y, ws, B, S)
+            image_losses()
 
         # ---- D on all 12B images (noise + dropout on the D1 and D2 slices only)
         dparts = None
@@ -664,7 +688,7 @@ class ShmGANwithSSpecSeg:
             rf, cls = D.heads()
         else:
             rf, cls = D.forward(xd, keep, [(0, B, 0), (6 * B, B, B)], parts=dparts, attn=attn_d, join=lane.join if dparts else None)
-        np_ = (S // 32) ** 2
+        np_ = (H // 32) * (W // 32)
 
         # ---- losses  SHM.py:669-844
         dl = A.get("loss/dhead", (16,), torch.float64)
@@ -698,13 +722,13 @@ class ShmGANwithSSpecSeg:
         ops.sum_input_channels(D.P.vars[0], 3, FD, 0b111, weff_d)
         if ev_img is not None:
             torch.cuda.current_stream().wait_event(ev_img)          # dgen_y / dcyc_y of the image losses
-        ops.conv3x3_dgrad_sum1(dzd[0:B], FD, weff_d, dgen_y, 1, B, S, S, FD, 2, 1)
-        ops.conv3x3_dgrad_sum1(dzd[B:6 * B], FD, weff_d, dcyc_y, 1, 5 * B, S, S, FD, 2, 1)
+        ops.conv3x3_dgrad_sum1(dzd[0:B], FD, weff_d, dgen_y, 1, B, H, W, FD, 2, 1)
+        ops.conv3x3_dgrad_sum1(dzd[B:6 * B], FD, weff_d, dcyc_y, 1, 5 * B, H, W, FD, 2, 1)
         dzg = G.backward(dcyc_y, "cyc", need_dx="dz")
         weff_g = A.get("g/weff", (5, 9, F))
         for k in range(5):                                       # G o G chain  SHM.py:576-580
             ops.sum_input_channels(G.P.vars[0], 10, F, sum(1 << j for j in range(5) if j != k and flags[j]), weff_g[k])
-        ops.conv3x3_dgrad_sum1(dzg, F, weff_g, dgen_y, 5, B, S, S, F, 1, 1)
+        ops.conv3x3_dgrad_sum1(dzg, F, weff_g, dgen_y, 5, B, H, W, F, 1, 1)
         update_g = self.epoch >= self.train_G_after
         # no collective for a gradient nobody applies (it would also still be in flight when the next step
         # zeroes the bucket)
@@ -807,6 +831,15 @@ class ShmGANwithSSpecSeg:
                 setattr(self.args, k, v)
                 if k in self.__dict__:
                     setattr(self, k, v)
+            if "image_hw" in vars(args):                                       # the frame cannot change under models that exist
+                hw = check_image_hw(args.image_hw)
+                frame = hw if hw is not None else (self.image_size, self.image_size)
+                if self.G is not None and frame != (self.G.H, self.G.W):
+                    raise ValueError(f"train: image_hw {hw} differs from the frame {(self.G.H, self.G.W)} this trainer's models were built for")
+                default = self.style_factor == self._default_style_factor()
+                self._image_hw = hw
+                if default:                                                    # the default follows the frame; a value set by hand stays
+                    self.style_factor = self._default_style_factor()
         start = time.perf_counter()
         a = self.args
         self._val_on, self._val_step, self._val_monitor = validation_options(a.val_dir, a.val_fraction, a.val_seed, a.val_step, a.val_batch_size, a.val_monitor,
@@ -936,7 +969,7 @@ class ShmGANwithSSpecSeg:
         """Forward-only path of the reference's evaluation script (/root/reference/test.py:218-297):
         standardised YUV of ONE rgb image -> G once with only view 0 populated (target ED) -> the
         generated RGB, whose channel 0 feeds five cyclic G calls.  rgb [B,H,W,3] in [0,1], H and W multiples of 16 and at least 32
-        (the networks are fully convolutional): (H, W) = (image_size, image_size) is the reference's shape and runs the five cyclic
+        (the networks are fully convolutional): (H, W) = image_hw (the reference's image_size x image_size by default) runs the five cyclic
         passes as one batch of 5 B; any other frame runs them one after the other through one set of buffers (samples are
         independent under InstanceNorm: the same arithmetic per sample, a sixth of the activation memory) and keeps arena buffers
         for that one frame shape (_frame_changed).  cyclic=False stops after G1: the cyclic images are then None.
@@ -944,14 +977,13 @@ class ShmGANwithSSpecSeg:
         if self.G is None:
             self.build()
         G, A = self.G, self.arena
-        S = self.image_size
         x = self._dev(rgb)
         if x.dim() != 4 or x.shape[3] != 3:
             raise ValueError(f"infer takes [B,H,W,3] images, got {tuple(x.shape)}")
         B, H, W = (int(v) for v in x.shape[:3])
         if min(H, W) < 32 or H % 16 or W % 16:
             raise ValueError(f"infer takes frames whose sides are multiples of 16 and at least 32, got {H} x {W}")
-        square = (H, W) == (S, S)
+        model_frame = (H, W) == self.image_hw
         self._frame_changed(H, W)
         npix = H * W
         G.prepare_weights()
@@ -974,7 +1006,7 @@ class ShmGANwithSSpecSeg:
             cyc_in = A.get("inf/cyc_in", (5 * B, H, W, PAD_C), adt)
             ops.build_gen_input(ys, orig_Ych, 0b11111, 1, cyc_in, B, npix)      # view k zero, the others = orig_Ych
             cyc_rgb = A.get("inf/cyc_rgb", (5 * B, H, W, 3))
-            if square:
+            if model_frame:
                 cyc_Y = G.forward(cyc_in, "inf5", attn=attn, parts=self.forward_parts)
                 ops.yuv2rgb(cyc_Y, cbcr, None, cyc_rgb, None, 5 * B, B, npix)
             else:
@@ -1056,7 +1088,8 @@ class ShmGANwithSSpecSeg:
         return self.region_metrics
 
     def _img_ws(self, B):
-        n = ops.image_losses_workspace(B, self.image_size)
+        H, W = self.image_hw
+        n = ops.image_losses_workspace(B, H) if H == W else ops.image_losses_hw_workspace(B, H, W)
         return self.arena.get("loss/ws", ((n + 3) // 4,))
 
     # ------------------------------------------------------------------ named losses (lazy D2H)

@@ -6,7 +6,7 @@ import numpy as np
 import torch
 
 from . import checkpoint, dist, ops
-from .data import gib_to_bytes, validation_loader
+from .data import gib_to_bytes, trainer_frame, validation_loader
 from .telemetry import VALIDATION_FILE, WEIGHT_SETS, improves, nan_to_none, region_means, region_options, write_lines
 
 
@@ -15,14 +15,15 @@ def _loader(t):
     if t.valDataset is None:
         a = t.args
         t.valDataset = validation_loader(
-            t.data_dir, t.image_size, t.batch_size, val_dir=a.val_dir, val_fraction=float(a.val_fraction or 0.0), val_seed=int(a.val_seed),
+            t.data_dir, trainer_frame(t), t.batch_size, val_dir=a.val_dir, val_fraction=float(a.val_fraction or 0.0), val_seed=int(a.val_seed),
             val_batch_size=a.val_batch_size, device=t.device, diffuse_source=a.diffuse_source, cache=a.cache, cache_bytes=gib_to_bytes(a.cache_gb))
     return t.valDataset
 
 
 def validate(t, dataset=None, weights=("raw",), region="args"):
     """Score the generator on held-out captures with test mode's protocol (evaluate.test): view 0 as the photo, the other views
-    zero, target label ED (infer without the cyclic passes), gen_rgb against the sample's ED image with ops.image_metrics.
+    zero, target label ED (infer without the cyclic passes), gen_rgb against the sample's ED image with ops.image_metrics (ops.image_metrics_hw on a
+    rectangular model frame).
     dataset: a data.PolarDataset (default: the held-out loader of the trainer's val_dir / val_fraction options); only its full
     batches are scored.  weights: the weight sets to score, each under generator_weights().  Per set every batch's rows go into one
     [n,5] float64 device buffer; ONE device-to-host copy ends the pass and the means are taken in float64 on the host.
@@ -57,10 +58,13 @@ def validate(t, dataset=None, weights=("raw",), region="args"):
         with t.generator_weights(w):
             for i, batch in enumerate(dataset):
                 gen_rgb, _ = t.infer(batch[0], cyclic=False)
-                ops.image_metrics(gen_rgb, batch[4], out=rows[i * B:(i + 1) * B], arena=t.arena)
+                H, W = int(gen_rgb.shape[1]), int(gen_rgb.shape[2])
+                if H == W:
+                    ops.image_metrics(gen_rgb, batch[4], out=rows[i * B:(i + 1) * B], arena=t.arena)
+                else:                   # a rectangular model frame, scored whole
+                    ops.image_metrics_hw(gen_rgb, (0, 0, H, W), t._dev(batch[4]), out=rows[i * B:(i + 1) * B], arena=t.arena)
                 if region is not None:
-                    S = int(gen_rgb.shape[1])
-                    t._region_metrics(region, t._dev(batch[0]), gen_rgb, t._dev(batch[4]), (0, 0, S, S), out=rrows[i * B:(i + 1) * B])
+                    t._region_metrics(region, t._dev(batch[0]), gen_rgb, t._dev(batch[4]), (0, 0, H, W), out=rrows[i * B:(i + 1) * B])
             # the pass's one device-to-host copy (it synchronises)
             host = (rows[:n] if region is None else both).cpu().numpy().astype(np.float64, copy=True)
         if region is not None:
@@ -68,8 +72,8 @@ def validate(t, dataset=None, weights=("raw",), region="args"):
         means = host.mean(axis=0) if n else np.full(5, np.nan)
         out[w] = dict({k: float(v) for k, v in zip(ops.METRIC_NAMES, means)}, rows=host)
         if region is not None:
-            S = int(t.image_size)
-            rmeans, n_in_images, n_out_images = region_means(rhost, S * S, (S - 10) * (S - 10))
+            H, W = t.image_hw
+            rmeans, n_in_images, n_out_images = region_means(rhost, H * W, (H - 10) * (W - 10))
             out[w].update(rmeans, region_rows=rhost, n_in_images=n_in_images, n_out_images=n_out_images)
     return out
 

@@ -43,7 +43,6 @@ NORM_FOLD = _FOLD_VALUES[os.environ.get("SHM_NORM_FOLD", "auto")]
 if os.environ.get("SHM_NORM_MODE", "exact") not in ("exact", "scaled"):
     raise ValueError(f"SHM_NORM_MODE={os.environ['SHM_NORM_MODE']!r}: expected exact or scaled")
 NORM_MODE = ops.NORM_SCALED if os.environ.get("SHM_NORM_MODE", "exact") == "scaled" else ops.NORM_EXACT
-WGRAD_AFTER_DGRAD = os.environ.get("SHM_WGRAD_AFTER_DGRAD", "0") == "1"
 PAD_C = 16          # channel pitch of 3- and 10-channel images in float32 (one 64-byte MFMA staging row)
 
 
@@ -106,8 +105,8 @@ class Arena:
             alloc = torch.zeros if dtype == torch.float64 else torch.empty
             t = alloc(tuple(shape), dtype=dtype, device=self.device)
             if dtype == torch.float64 and torch.device(self.device).type == "cuda":
-                # the zero fill runs on whichever stream is current (a part of a two-stream forward allocates on the second
-                # stream) while slices of the buffer are about to be used on another one: wait for it once, at allocation
+                # the zero fill runs on whichever stream is current (Discriminator.trunk_rows allocates on the second stream when
+                # the trainer runs the real half there) while the buffer may next be used on another one: wait for it once, at allocation
                 torch.cuda.current_stream(self.device).synchronize()
             self.t[key] = t
         return t
@@ -201,26 +200,6 @@ class WgradLane:
             torch.cuda.current_stream().wait_event(ev)
 
 
-class _ConvTurns:
-    """Turn taking of two half-batch passes that run on two streams: before(p) makes part p's stream wait for the other part's
-    most recent convolution, after(p) marks part p's convolution.  The host issues the parts alternately, one convolution (and the
-    elementwise passes behind it) at a time, so an event is always recorded before the other part waits on it."""
-
-    def __init__(self, streams):
-        self.streams = streams
-        self.ev = [None, None]
-
-    def before(self, p):
-        ev = self.ev[1 - p]
-        if ev is not None:
-            self.streams[p].wait_event(ev)
-
-    def after(self, p):
-        ev = torch.cuda.Event()
-        ev.record(self.streams[p])
-        self.ev[p] = ev
-
-
 def generator_layers(f):
     """(keras_name, kind, k, cin, cout) in Keras creation order (Generator_summary.txt)."""
     return [
@@ -292,6 +271,39 @@ class _Vars:
 class _ModelBase:
     trainable = True
 
+    def __init__(self, image_size, filter_size, device, arena, ws_provider, lane, dtype, grad_dtype, attention):
+        """What both models hold before their layers: the frame, the dtypes and the shared plumbing.  The subclass then creates
+        P (_Vars), acc / acc_off (the f64-accumulated gradient region), betas and its K-contiguous weight copies."""
+        self.H, self.W = frame_hw(image_size)              # the training frame, given as a side or a pair (H, W)
+        self.F, self.dev = filter_size, device
+        self.attention = bool(attention)
+        self.arena, self.ws_provider = arena, ws_provider
+        self.lane = lane or WgradLane(device, enabled=False)
+        self.adt = dtype                                   # activation / MFMA operand dtype
+        self.gdt = (grad_dtype or dtype) if dtype != torch.float32 else torch.float32   # gradient-signal tensors ([G] in the header)
+        self.pad = pad_channels(dtype)
+        self.gsum = ops.gsum_default(dtype)                # InstanceNorm-backward sums in the producing epilogues
+        self.weights_dirty = True
+        self._tb = None
+
+    def set_betas(self, arrays):
+        for b, a in zip(self.betas, arrays):
+            b.copy_(torch.as_tensor(np.asarray(a, dtype=np.float32)))
+
+    def _acc_slice(self, var_index):
+        o = self.P.offsets[var_index] - self.acc_off
+        return self.acc[o:o + self.P.vars[var_index].numel()]
+
+    def prepare_weights(self):
+        """Refresh the K-contiguous weight copies after an optimizer step: one launch for all of them (_transpose_items of the model)."""
+        if not self.weights_dirty:
+            return
+        self.P.refresh_operands()
+        if self._tb is None:
+            self._tb = ops.TransposeBatch(self._transpose_items())
+        self._tb.run()
+        self.weights_dirty = False
+
     def count_params(self):
         return self.P.n
 
@@ -353,10 +365,7 @@ class AttentionBranch:
         m = A.get(f"{self.tag}/m", (B, h, w, o.pad), o.adt)
         y1 = A.get(f"{self.tag}/y1", (B, h, w, c), o.adt)
         y2 = A.get(f"{self.tag}/y2", (B, h, w, c), o.adt)
-        if H == W:
-            ops.mask_pool_pack(mask, m, B, H, self.pool)
-        else:
-            ops.mask_pool_pack_hw(mask, m, B, H, W, self.pool)
+        ops.mask_pool_pack_hw(mask, m, B, H, W, self.pool)
         ops.conv2d_fwd(m, None, 0, o.pad, 0, self.wk1, o.P.vars[self.vi + 1], y1, c, B, h, w, o.pad, c, 3, 1, LRELU, cin_real=1)
         ops.conv2d_fwd(y1, None, 0, c, 0, self.wk2, o.P.vars[self.vi + 3], y2, c, B, h, w, c, c, 3, 1, LRELU)
         self.ctx = dict(B=B, h=h, w=w, m=m, y1=y1, y2=y2)
@@ -370,7 +379,9 @@ class AttentionBranch:
         dz2 = A.get(f"{self.tag}/dz2", (B, h, w, c), o.adt)
         dz1 = A.get(f"{self.tag}/dz1", (B, h, w, c), o.adt)
         dy1 = A.get(f"{self.tag}/dy1", (B, h, w, c), o.gdt)
-        red = A.get(f"attn/lred/{c}", (ops.LRELU_RED_SLOTS * c,), torch.float64)
+        # zero-on-entry scratch, keyed by the branch: the discriminator's branch (second stream, d_bwd_on_lane) and the generator's
+        # level-3 branch (main stream) have the same channel count and may run at the same time
+        red = A.get(f"{self.tag}/lred", (ops.LRELU_RED_SLOTS * c,), torch.float64)
         ops.lrelu_bwd(dattn, c, x["y2"], c, dz2, c, o._acc_slice(self.vi + 3), B * h * w, c, LRELU, red)
         ws = o.ws_provider(ops.conv2d_wgrad_workspace(B, h, w, c, c, 3))
         o.lane.submit(lambda: ops.conv2d_wgrad(x["y1"], None, 0, c, 0, dz2, c, o.P.grads[self.vi + 2], B, h, w, c, c, c, 3, 1, 0, ws))
@@ -386,17 +397,8 @@ class Generator(_ModelBase):
 
     def __init__(self, image_size, filter_size, device, arena, ws_provider, lane=None, dtype=torch.float32,
                  grad_dtype=None, attention=False):
-        # image_size: the training frame, a side or a pair (H, W); S is the side of a square frame and None otherwise
-        self.H, self.W = frame_hw(image_size)
-        self.S, self.F, self.dev = (self.H if self.H == self.W else None), filter_size, device
-        self.attention = bool(attention)
-        self.arena, self.ws_provider = arena, ws_provider
-        self.lane = lane or WgradLane(device, enabled=False)
-        self.adt = dtype                                   # activation / MFMA operand dtype
-        self.gdt = (grad_dtype or dtype) if dtype != torch.float32 else torch.float32   # gradient-signal tensors ([G] in the header)
-        self.pad = pad_channels(dtype)
-        self.gsum = ops.gsum_default(dtype)                # InstanceNorm-backward sums in the producing epilogues
-        self.fold = NORM_FOLD                              # InstanceNorm apply folded into the consumers: False / "auto" / "all" (see NORM_FOLD)
+        super().__init__(image_size, filter_size, device, arena, ws_provider, lane, dtype, grad_dtype, attention)
+        self.fold = NORM_FOLD                             # InstanceNorm apply folded into the consumers: False / "auto" / "all" (see NORM_FOLD)
         self.norm_mode = NORM_MODE                         # ... in LDS (exact) or in the operands (scaled)
         self._plans = {}
         assert self.H % 16 == 0 and self.W % 16 == 0 and filter_size % self.pad == 0, \
@@ -440,18 +442,10 @@ class Generator(_ModelBase):
                 self.wk[i] = torch.zeros(9 * cin * cout, dtype=dtype, device=device)
         self.attn = [AttentionBranch(self, nbase + 4 * lvl, filter_size << lvl, 1 << lvl, f"g/attn{lvl}") for lvl in range(4)] \
             if self.attention else []
-        self.weights_dirty = True
-        self._tb = None
         self.ctx = {}
-        self.debug = None
-        self._on_wgrad = None
         self._dattn = [None] * 4           # attention skip gradients of the step in flight (reset by zero_grad)
 
     # -- parameter plumbing ---------------------------------------------------------------
-    def set_betas(self, arrays):
-        for b, a in zip(self.betas, arrays):
-            b.copy_(torch.as_tensor(np.asarray(a, dtype=np.float32)))
-
     def grad_buckets(self):
         """Data-parallel exchange plan of the flat gradient: [(trigger_layer, [(lo, hi), ...]), ...] in the order the
         backward pass completes them.  The kernels are stored in layer order, and a backward pass finishes the layers
@@ -468,28 +462,17 @@ class Generator(_ModelBase):
         out.append((None, [(0, hi), (self.attn_off, self.P.n)]))
         return out
 
-    def _acc_slice(self, var_index):
-        o = self.P.offsets[var_index] - self.acc_off
-        return self.acc[o:o + self.P.vars[var_index].numel()]
-
-    def prepare_weights(self):
-        """Refresh the K-contiguous weight copies after an optimizer step."""
-        if not self.weights_dirty:
-            return
-        self.P.refresh_operands()
-        if self._tb is None:              # one launch for every layer's K-contiguous copy
-            items = []
-            for i, (_, kind, k, cin, cout) in enumerate(self.layers[:-1]):
-                w = self.P.vars[2 * i]
-                if kind == "c":      # HWIO [t][cin][cout] -> [t][cout][cin_pad]
-                    items.append((w, self.wk[i], k * k, cin, cout, _padk(cin, self.pad)))
-                else:                # Keras convT [t][cout][cin] -> [t][cin][cout] (for its dgrad)
-                    items.append((w, self.wk[i], 9, cout, cin, cout))
-            for br in self.attn:
-                items += br.transpose_items()
-            self._tb = ops.TransposeBatch(items)
-        self._tb.run()
-        self.weights_dirty = False
+    def _transpose_items(self):
+        items = []
+        for i, (_, kind, k, cin, cout) in enumerate(self.layers[:-1]):
+            w = self.P.vars[2 * i]
+            if kind == "c":      # HWIO [t][cin][cout] -> [t][cout][cin_pad]
+                items.append((w, self.wk[i], k * k, cin, cout, _padk(cin, self.pad)))
+            else:                # Keras convT [t][cout][cin] -> [t][cin][cout] (for its dgrad)
+                items.append((w, self.wk[i], 9, cout, cin, cout))
+        for br in self.attn:
+            items += br.transpose_items()
+        return items
 
     def zero_grad(self):
         """Start of a step: clear the flat gradient and the f64 accumulators, and forget the attention skip gradients of
@@ -503,7 +486,6 @@ class Generator(_ModelBase):
         """attn_1..attn_4 (SHM.py:248,257,266,275) of the step's SpecSeg mask [B,H,W,1] ((H, W) = (S, S) in training; any frame of
         forward() in inference); pass the result to forward(attn=)."""
         self.prepare_weights()
-        self._attn_B = B
         return [br.forward(mask, B, int(mask.shape[1]), int(mask.shape[2])) for br in self.attn]
 
     def attention_masks(self):
@@ -521,7 +503,7 @@ class Generator(_ModelBase):
         ops.cvt_f64_f32(self.acc, self.P.grad[self.acc_off:], self.acc_n, 0)
 
     # -- forward --------------------------------------------------------------------------
-    def _fold_plan(self, nb, n, attn, H=None, W=None):
+    def _fold_plan(self, n, attn, H=None, W=None):
         """{layer index of an InstanceNorm block: True} for the blocks whose normalisation is applied by their consumers: every
         convolution that reads the block's output, and that convolution's weight gradient, must run on a kernel that normalises its
         operand in LDS for this batch (the launcher's variant choice depends on it: ops.conv2d_norm_supported).  Encoder block 1 of a
@@ -530,7 +512,7 @@ class Generator(_ModelBase):
         Conv2DTranspose (or the head, which has normalised on the fly since round 2) and the bottleneck is 1x1: not folded.
         Live attention adds its maps to the normalised skips, which therefore have to exist: nothing is folded."""
         H, W = self.H if H is None else H, self.W if W is None else W       # the map the pass runs on: the model's frame in training
-        key = (nb, n, bool(attn), self.fold, H, W)      # nb: samples per forward launch (a part of a two-part forward), n: per backward launch
+        key = (n, bool(attn), self.fold, H, W)          # n: samples per launch, forward and backward
         plan = self._plans.get(key)
         if plan is not None:
             return plan
@@ -542,7 +524,7 @@ class Generator(_ModelBase):
                 cin_p = _padk(cin, self.pad)
                 if self.fold != "all" and not (dt == torch.float32 and c1 == 0 and cin_p <= 64):
                     return False                               # "auto": only where it is measured to pay
-                return (ops.conv2d_norm_supported(nb, h, w, cin_p, c1, cout, 3, 1, part, dt) and
+                return (ops.conv2d_norm_supported(n, h, w, cin_p, c1, cout, 3, 1, part, dt) and
                         ops.conv2d_wgrad_norm_supported(n, h, w, cin, cin_p, c1, cout, 3, 1, part, dt))
             for lvl in range(4):
                 h, w = H >> lvl, W >> lvl
@@ -555,10 +537,8 @@ class Generator(_ModelBase):
         self._plans[key] = plan
         return plan
 
-    def _cnl_fwd(self, tag, li, bi, x, x2, c1, ldx, ldx2, n, h, w, r0, r1, part, pooled=None, apply=True, sync=None, ntx=None, ntx2=None,
-                 fold=False):
-        """Conv2D(k, s1, bias, LeakyReLU) -> InstanceNormalization on the samples [r0, r1) of a batch of n.  x, x2, pooled are
-        FULL-batch tensors (the record describes them: the backward pass runs on the whole batch); the launches take row views.
+    def _cnl_fwd(self, tag, li, bi, x, x2, c1, ldx, ldx2, n, h, w, pooled=None, apply=True, ntx=None, ntx2=None, fold=False):
+        """Conv2D(k, s1, bias, LeakyReLU) -> InstanceNormalization on a batch of n.
         Returns (ahat, record).  pooled: AveragePooling2D(2) of the result, written by the same pass as the normalisation.
         apply=False: the consumer normalises on the fly (the head, ops.head_in_fwd): returns the un-normalised tensor.
         ntx / ntx2: x / x2 is the un-normalised output of a folded block and this is its table.  fold: this block's output is
@@ -566,16 +546,11 @@ class Generator(_ModelBase):
         _, _, k, cin, cout = self.layers[li]
         cin_p = _padk(cin, self.pad)
         A = self.arena
-        nb = r1 - r0
         a = A.get(f"{tag}/a{li}", (n, h, w, cout), self.adt)
         ahat = A.get(f"{tag}/h{li}", (n, h, w, cout), self.adt) if apply and not fold else None
         nt = A.get(f"{tag}/nt{li}", (n, 4, cout), torch.float32) if fold else None
         stats = A.get(f"{tag}/s{li}", (n * cout * 2,), torch.float64)
-        st = stats[r0 * cout * 2:r1 * cout * 2]
-        # zero-on-return scratch: one per concurrently running part
-        scr = A.get(f"stats_scratch/{nb * cout}/p{part}", (ops.STATS_SLOTS * nb * cout * 2,), torch.float64)
-        if sync is not None:
-            sync.before(part)
+        scr = A.get(f"stats_scratch/{n * cout}", (ops.STATS_SLOTS * n * cout * 2,), torch.float64)     # zero-on-return scratch
         wk_, bias_, mode = self.wk[li], self.P.vars[2 * li + 1], ops.NORM_EXACT
         folded_in = (ntx is not None or ntx2 is not None)
         if folded_in and self.norm_mode == ops.NORM_SCALED:
@@ -583,80 +558,39 @@ class Generator(_ModelBase):
             src_nt, lo, c = (ntx, 0, ldx) if ntx is not None else (ntx2, c1, ldx2)
             wn = A.get(f"{tag}/wn{li}", (n, k * k * cout * cin_p), self.adt)
             bn = A.get(f"{tag}/bn{li}", (n, cout), torch.float32)
-            ops.conv2d_norm_prepare(wk_, bias_, src_nt[r0:r1], c, lo, wn[r0:r1], bn[r0:r1], nb, cin_p, cout, k)
-            wk_, bias_, mode = wn[r0:r1], bn[r0:r1], ops.NORM_SCALED
-        ops.conv2d_in_fwd(x[r0:r1], None if x2 is None else x2[r0:r1], c1, ldx, ldx2, wk_, bias_, a[r0:r1], cout, nb, h, w,
-                          cin_p, cout, k, 1, LRELU, st, IN_EPS, cin_real=cin, scratch=scr,
-                          nt_x=None if ntx is None else ntx[r0:r1], nt_x2=None if ntx2 is None else ntx2[r0:r1],
-                          nt_out=None if nt is None else nt[r0:r1], beta_out=self.betas[bi] if fold else None, norm_mode=mode)
-        if sync is not None:
-            sync.after(part)
+            ops.conv2d_norm_prepare(wk_, bias_, src_nt, c, lo, wn, bn, n, cin_p, cout, k)
+            wk_, bias_, mode = wn, bn, ops.NORM_SCALED
+        ops.conv2d_in_fwd(x, x2, c1, ldx, ldx2, wk_, bias_, a, cout, n, h, w, cin_p, cout, k, 1, LRELU, stats, IN_EPS, cin_real=cin,
+                          scratch=scr, nt_x=ntx, nt_x2=ntx2, nt_out=nt, beta_out=self.betas[bi] if fold else None, norm_mode=mode)
         rec = dict(li=li, x=x, x2=x2, c1=c1, ldx=ldx, ldx2=ldx2, a=a, stats=stats, h=h, w=w, bi=bi, n=n, cout=cout, ntx=ntx, ntx2=ntx2, nt=nt)
         if not apply:
             return a, rec
         if fold:
             if pooled is not None:
-                ops.in_pool(a[r0:r1], cout, st, self.betas[bi], pooled[r0:r1], cout, nb, h, w, cout)
+                ops.in_pool(a, cout, stats, self.betas[bi], pooled, cout, n, h, w, cout)
             return a, rec
         if pooled is not None:
-            ops.in_apply_pool(a[r0:r1], cout, st, self.betas[bi], ahat[r0:r1], cout, pooled[r0:r1], cout, nb, h, w, cout)
+            ops.in_apply_pool(a, cout, stats, self.betas[bi], ahat, cout, pooled, cout, n, h, w, cout)
         else:
-            ops.in_apply(a[r0:r1], cout, st, self.betas[bi], ahat[r0:r1], cout, nb, h * w, cout)
+            ops.in_apply(a, cout, stats, self.betas[bi], ahat, cout, n, h * w, cout)
         return ahat, rec
 
-    def forward(self, x16, tag, attn=None, parts=1):
+    def forward(self, x16, tag, attn=None):
         """x16: [N,H,W,pad] (10 real channels, zero padded to the 64-byte pitch), H and W multiples of 16: the model's frame in training, any
         frame in inference (the network is fully convolutional; backward() takes the training frame).  Returns gen_Y [N,H,W,1].
         attn: attention_forward()'s maps ([B,...], N a multiple of B: image i is a copy of sample i % B): added to the four
         skip tensors, `down_k + attn_k` (SHM.py:290-293); the pooled path keeps the un-augmented tensor.
-        parts = 2 (experiment, not the trainer's default): the batch is evaluated as two halves, the second one on the second
-        stream, taking turns convolution by convolution (samples are independent: InstanceNorm is per sample, so this is exact).
         A forward pass is a dependency chain conv -> statistics -> normalise -> conv with nothing beside it (rocprofv3 timeline:
-        2 ms of a 121 ms fp32 step are normalisation passes with no MFMA kernel running); the idea was to run one half's
-        normalisation pass under the other half's convolution.  Measured: +2 ms -- the halves' convolutions no longer overlap
-        and the half-size grids are less efficient than the hidden passes are long."""
+        2 ms of a 121 ms fp32 step are normalisation passes with no MFMA kernel running), and stays one: two half batches taking
+        turns on two streams measured slower (LABNOTES.md)."""
         n, H, W = (int(v) for v in x16.shape[:3])
         assert x16.dim() == 4 and x16.shape[3] == self.pad and x16.dtype == self.adt and x16.is_contiguous(), (tuple(x16.shape), x16.dtype)
         assert H >= 16 and W >= 16 and H % 16 == 0 and W % 16 == 0, f"the generator takes maps whose sides are multiples of 16, got {H} x {W}"
         self.prepare_weights()
-        if parts == 2 and self.lane.stream is not None and n >= 4 and (attn is None or (n // 2) % self._attn_B == 0):
-            # two half batches, ALTERNATING: a half launches its next convolution only when the other half's previous one has
-            # finished (events), so the halves do not fall into lockstep (conv beside conv, normalisation beside normalisation):
-            # half A's normalisation pass runs under half B's convolution and vice versa
-            cut = n // 2
-            main, second = torch.cuda.current_stream(), self.lane.stream
-            start = torch.cuda.Event()
-            start.record(main)
-            second.wait_event(start)
-            sync = _ConvTurns((main, second))
-            gens = [self._forward_rows(x16, tag, attn, 0, cut, 0, sync), self._forward_rows(x16, tag, attn, cut, n, 1, sync)]
-            live = [True, True]
-            y = None
-            while live[0] or live[1]:
-                for p in (0, 1):
-                    if live[p]:
-                        with torch.cuda.stream(sync.streams[p]):
-                            try:
-                                next(gens[p])
-                            except StopIteration as e:
-                                live[p] = False
-                                y = e.value if p == 0 else y
-            self.lane.join()
-            return y
-        gen = self._forward_rows(x16, tag, attn, 0, n, 0, None)
-        while True:
-            try:
-                next(gen)
-            except StopIteration as e:
-                return e.value
-
-    def _forward_rows(self, x16, tag, attn, r0, r1, part, sync):
-        """Generator: one step = one convolution of the samples [r0, r1) with the elementwise passes behind it."""
-        n, H, W = (int(v) for v in x16.shape[:3])
-        nb = r1 - r0
+        attn_B = 0 if attn is None else int(attn[0].shape[0])     # samples behind the attention maps (0: none); backward() reads it from ctx
         A = self.arena
         recs = []
-        plan = self._fold_plan(nb, n, attn is not None, H, W)
+        plan = self._fold_plan(n, attn is not None, H, W)
         cur, cur_nt, ld, h, w = x16, None, self.pad, H, W      # cur_nt: cur is the un-normalised output of a folded block, with this table
         li = bi = 0
         downs = []
@@ -665,63 +599,49 @@ class Generator(_ModelBase):
             for j in range(2):
                 if j == 1:            # the level's second block: its normalisation pass also writes the pooled tensor
                     pooled = A.get(f"{tag}/p{lvl}", (n, h // 2, w // 2, self.layers[li][4]), self.adt)
-                cur, r = self._cnl_fwd(tag, li, bi, cur, None, 0, ld, 0, n, h, w, r0, r1, part, pooled=pooled, sync=sync, ntx=cur_nt,
-                                       fold=plan.get(li, False))
+                cur, r = self._cnl_fwd(tag, li, bi, cur, None, 0, ld, 0, n, h, w, pooled=pooled, ntx=cur_nt, fold=plan.get(li, False))
                 cur_nt = r["nt"]
                 r["pooled"] = pooled
                 recs.append(r)
-                yield
                 ld = self.layers[li][4]
                 li += 1
                 bi += 1
             if attn is not None:
                 skip = A.get(f"{tag}/skip{lvl}", (n, h, w, ld), self.adt)
-                ops.add_bcast(cur[r0:r1], attn[lvl], skip[r0:r1], nb, h * w * ld, self._attn_B, r0)
+                ops.add_bcast(cur, attn[lvl], skip, n, h * w * ld, attn_B, 0)
                 downs.append((skip, ld, (h, w), None))
             else:
                 downs.append((cur, ld, (h, w), cur_nt))
             cur, cur_nt, h, w = pooled, None, h // 2, w // 2
         for _ in range(2):                       # the two 1x1 blocks
-            cur, r = self._cnl_fwd(tag, li, bi, cur, None, 0, ld, 0, n, h, w, r0, r1, part, sync=sync)
+            cur, r = self._cnl_fwd(tag, li, bi, cur, None, 0, ld, 0, n, h, w)
             recs.append(r)
             li += 1
             bi += 1
-            yield
         ups = []
         for lvl in range(4):
             _, _, _, cin, cout = self.layers[li]
             u = A.get(f"{tag}/u{lvl}", (n, 2 * h, 2 * w, cout), self.adt)
-            if sync is not None:
-                sync.before(part)
-            ops.conv2d_transpose_fwd(cur[r0:r1], ld, self.P.op_vars[2 * li], self.P.vars[2 * li + 1], u[r0:r1], cout, nb, h, w, cin,
-                                     cout, LRELU)
-            if sync is not None:
-                sync.after(part)
-            yield
+            ops.conv2d_transpose_fwd(cur, ld, self.P.op_vars[2 * li], self.P.vars[2 * li + 1], u, cout, n, h, w, cin, cout, LRELU)
             ups.append(dict(li=li, x=cur, ldx=ld, u=u, h=h, w=w))
             li += 1
             h, w = 2 * h, 2 * w
             skip, sld, sh, skip_nt = downs[3 - lvl]
             assert sh == (h, w)
-            cur, r = self._cnl_fwd(tag, li, bi, u, skip, cout, cout, sld, n, h, w, r0, r1, part, sync=sync, ntx2=skip_nt,
-                                   fold=plan.get(li, False))                                                  # concat [u, skip]
+            cur, r = self._cnl_fwd(tag, li, bi, u, skip, cout, cout, sld, n, h, w, ntx2=skip_nt, fold=plan.get(li, False))      # concat [u, skip]
             cur_nt = r["nt"]
             recs.append(r)
             ld = self.layers[li][4]
             li += 1
             bi += 1
-            yield
             # the last block's InstanceNorm is applied by the head kernels (forward and backward) on the fly
-            cur, r = self._cnl_fwd(tag, li, bi, cur, None, 0, ld, 0, n, h, w, r0, r1, part, apply=lvl < 3, sync=sync, ntx=cur_nt)
+            cur, r = self._cnl_fwd(tag, li, bi, cur, None, 0, ld, 0, n, h, w, apply=lvl < 3, ntx=cur_nt)
             recs.append(r)
             li += 1
             bi += 1
-            yield
         y = A.get(f"{tag}/y", (n, H, W, 1))
-        ops.head_in_fwd(cur[r0:r1], ld, r["stats"][r0 * ld * 2:r1 * ld * 2], self.betas[r["bi"]], self.P.vars[2 * li], self.P.vars[2 * li + 1], y[r0:r1],
-                        nb, H * W, ld, LRELU)
-        if part == 0:                 # the records describe full-batch tensors: identical whichever part builds them
-            self.ctx[tag] = dict(n=n, recs=recs, ups=ups, head_x=cur, head_rec=r, y=y, x16=x16, attn=attn is not None)
+        ops.head_in_fwd(cur, ld, r["stats"], self.betas[r["bi"]], self.P.vars[2 * li], self.P.vars[2 * li + 1], y, n, H * W, ld, LRELU)
+        self.ctx[tag] = dict(n=n, recs=recs, ups=ups, head_x=cur, head_rec=r, y=y, x16=x16, attn=attn_B)
         return y
 
     # -- backward -------------------------------------------------------------------------
@@ -737,12 +657,13 @@ class Generator(_ModelBase):
         rec[key] = red
         return (rec["pooled"] if pooled else rec["a"]), c, red
 
-    def _cnl_bwd(self, tag, rec, g1, g2, n, need_dx, dx=None, dx2=None, n1=0, rank1=None, gsum=None, gsum2=None):
+    def _cnl_bwd(self, tag, rec, g1, g2, n, need_dx, dx=None, dx2=None, n1=0, rank1=None, gsum=None, gsum2=None, on_wgrad=None):
         """Backward of one Conv->LReLU->IN block.  g1: gradient at the IN output (same res),
         g2: optional gradient of the 2x2 average pool that consumed the IN output.
         rank1 = (hdz, w): g1 is the rank-1 tensor hdz (x) w of the head (formed on the fly, g1 = None).
         gsum / gsum2: _gsum() of the block(s) whose output gradient dx / dx2 is.  If the launches that wrote g1 (and g2) were given
         this block's _gsum(), the InstanceNorm backward is the single apply pass (ops.in_bwd_apply), otherwise reduce + apply.
+        on_wgrad(li): backward()'s callback, called once the weight gradient has been issued.
         Accumulates dW / dbias; returns nothing (dx/dx2 are written if need_dx)."""
         li, h, w = rec["li"], rec["h"], rec["w"]
         _, _, k, cin, cout = self.layers[li]
@@ -764,10 +685,6 @@ class Generator(_ModelBase):
             red = A.get(f"bwd/red/{n * cout}", (n * cout * 3,), torch.float64)
             ops.in_bwd(g1, cout, g2, cout, rec["a"], cout, rec["stats"], red, dz, cout, self._acc_slice(2 * li + 1), n,
                        h, w, cout, LRELU, fused=_fused_scratch(A, self.adt, n, h * w, cout), dz_sums=dzsum, abort=A.abort)
-        if self.debug is not None:           # test diagnostics: keep the per-layer gradients
-            if g1 is None:
-                g1 = rank1[0].reshape(n, h, w, 1) * rank1[1].reshape(1, 1, 1, -1)
-            self.debug[li] = (g1.clone(), None if g2 is None else g2.clone(), dz.clone())
         cin_p = _padk(cin, self.pad)
         ws = self.ws_provider(ops.conv2d_wgrad_norm_workspace(n, h, w, cin, cout, k, self.adt) if scaled else ops.conv2d_wgrad_workspace(n, h, w, cin, cout, k))
 
@@ -779,21 +696,13 @@ class Generator(_ModelBase):
                 src_nt, lo, c = (rec["ntx"], 0, rec["ldx"]) if rec["ntx"] is not None else (rec["ntx2"], rec["c1"], rec["ldx2"])
                 ops.conv2d_wgrad_norm_finish(self.P.grads[2 * li], src_nt, dzsum, n, c, lo, cin, cout, k)
 
-        def wgrad():
-            self.lane.submit(wgrad_launches)
-            if self._on_wgrad is not None:
-                self._on_wgrad(li)
-        # WGRAD_AFTER_DGRAD: the weight gradient is released behind the layer's input gradient instead of beside it.  Both are MFMA
-        # bound -- side by side they only share the matrix pipes -- whereas the NEXT thing on the main stream is the InstanceNorm
-        # backward of the layer below, an HBM-bound pass that then runs under this weight gradient instead of alone
-        if not WGRAD_AFTER_DGRAD:
-            wgrad()
+        # the weight gradient is released beside the layer's input gradient, in front of it (behind it measured slower: LABNOTES.md)
+        self.lane.submit(wgrad_launches)
+        if on_wgrad is not None:
+            on_wgrad(li)
         if need_dx:
-            lddx = rec["ldx"]
-            ops.conv2d_dgrad(dz, cout, self.P.op_vars[2 * li], dx, dx2, n1, lddx, rec["ldx2"], n, h, w, cin, cout, k, 1,
+            ops.conv2d_dgrad(dz, cout, self.P.op_vars[2 * li], dx, dx2, n1, rec["ldx"], rec["ldx2"], n, h, w, cin, cout, k, 1,
                              gsum=gsum, gsum2=gsum2)
-        if WGRAD_AFTER_DGRAD:
-            wgrad()
         return dz
 
     def backward(self, dy, tag, need_dx=False, on_wgrad=None):
@@ -810,14 +719,6 @@ class Generator(_ModelBase):
         assert tuple(c["y"].shape[1:3]) == (H, W), \
             f"backward takes the {'square ' if H == W else ''}training shape {H} x {W}, the forward ran on {tuple(c['y'].shape[1:3])}"
         nl = len(self.layers)
-        self._on_wgrad = on_wgrad
-        try:
-            return self._backward(dy, c, n, recs, ups, A, H, W, F, nl, tag, need_dx)
-        finally:
-            self._on_wgrad = None
-
-    def _backward(self, dy, c, n, recs, ups, A, H, W, F, nl, tag, need_dx):
-        # head
         # head: weight / bias gradients and the scalar factor hdz of its input gradient (hdz (x) w is never written: the
         # backward of the block in front of the head forms it on the fly)
         hx = c["head_x"]
@@ -837,7 +738,7 @@ class Generator(_ModelBase):
             cout = self.layers[r2["li"]][4]
             dmid = A.get(f"bwd/dm/{n}x{h}x{w}x{cout}", (n, h, w, cout), self.gdt)
             self._cnl_bwd(tag, r2, dcur, None, n, True, dmid, None, cout,
-                          rank1=(hdz, self.P.vars[2 * (nl - 1)].reshape(-1)) if lvl == 3 else None, gsum=self._gsum(r1))
+                          rank1=(hdz, self.P.vars[2 * (nl - 1)].reshape(-1)) if lvl == 3 else None, gsum=self._gsum(r1), on_wgrad=on_wgrad)
             # concat block: split gradient into (du, dskip); dskip is the gradient at the encoder block's InstanceNorm output
             # (live attention adds its map to the skip: the same gradient)
             cu = r1["c1"]
@@ -845,10 +746,10 @@ class Generator(_ModelBase):
             du = A.get(f"bwd/du/{n}x{h}x{w}x{cu}", (n, h, w, cu), self.gdt)
             dsk = A.get(f"bwd/dskip{3 - lvl}/{n}x{h}x{w}x{cs}", (n, h, w, cs), self.gdt)
             enc2 = recs[2 * (3 - lvl) + 1]                           # second block of encoder level 3 - lvl
-            self._cnl_bwd(tag, r1, dmid, None, n, True, du, dsk, cu, gsum2=self._gsum(enc2))
+            self._cnl_bwd(tag, r1, dmid, None, n, True, du, dsk, cu, gsum2=self._gsum(enc2), on_wgrad=on_wgrad)
             dskips[3 - lvl] = dsk
             if c["attn"]:                       # d attn_k = sum of the skip gradient over every copy of the sample
-                B = self._attn_B                # (state reset by zero_grad() at the start of every step)
+                B = c["attn"]                   # (_dattn is reset by zero_grad() at the start of every step)
                 da = A.get(f"bwd/dattn{3 - lvl}/{B}", (B, h, w, cs), self.gdt)
                 ops.sum_groups(dsk, da, n, h * w * cs, B, 0, accumulate=self._dattn[3 - lvl] is not None)
                 self._dattn[3 - lvl] = da
@@ -861,8 +762,8 @@ class Generator(_ModelBase):
             ws = self.ws_provider(ops.conv2d_wgrad_workspace(n, h // 2, w // 2, tcout, tcin, 3))
             self.lane.submit(lambda dzu=dzu, up=up, tli=tli, tcout=tcout, tcin=tcin, h=h, w=w, ws=ws: ops.conv2d_wgrad(
                 dzu, None, 0, tcout, 0, up["x"], up["ldx"], self.P.grads[2 * tli], n, h, w, tcout, tcout, tcin, 3, 2, 1, ws))
-            if self._on_wgrad is not None:
-                self._on_wgrad(tli)
+            if on_wgrad is not None:
+                on_wgrad(tli)
             hin, win = up["h"], up["w"]
             dcur = A.get(f"bwd/d/{n}x{hin}x{win}x{tcin}", (n, hin, win, tcin), self.gdt)
             # input gradient of the Conv2DTranspose = the stride-2 forward form; it writes the gradient at the InstanceNorm output
@@ -876,7 +777,7 @@ class Generator(_ModelBase):
             cin = self.layers[r["li"]][3]
             dn = A.get(f"bwd/db{ri}/{n}x{h}x{w}x{cin}", (n, h, w, cin), self.gdt)
             # the first 1x1 block's input gradient is the gradient of pool 4: sums against the pooled tensor of encoder level 3
-            self._cnl_bwd(tag, r, dcur, None, n, True, dn, None, cin, gsum=self._gsum(recs[ri]) if j == 0 else self._gsum(recs[ri], pooled=True))
+            self._cnl_bwd(tag, r, dcur, None, n, True, dn, None, cin, gsum=self._gsum(recs[ri]) if j == 0 else self._gsum(recs[ri], pooled=True), on_wgrad=on_wgrad)
             dcur = dn
         dpool = dcur                                   # gradient wrt pool4 output
         for lvl in range(3, -1, -1):
@@ -885,17 +786,17 @@ class Generator(_ModelBase):
             h, w = r2["h"], r2["w"]
             cout = self.layers[r2["li"]][4]
             dmid = A.get(f"bwd/dm/{n}x{h}x{w}x{cout}", (n, h, w, cout), self.gdt)
-            self._cnl_bwd(tag, r2, dskips[lvl], dpool, n, True, dmid, None, cout, gsum=self._gsum(r1))
+            self._cnl_bwd(tag, r2, dskips[lvl], dpool, n, True, dmid, None, cout, gsum=self._gsum(r1), on_wgrad=on_wgrad)
             cin = self.layers[r1["li"]][3]
             if lvl > 0:
                 dpool = A.get(f"bwd/dp/{n}x{h}x{w}x{cin}", (n, h, w, cin), self.gdt)
-                self._cnl_bwd(tag, r1, dmid, None, n, True, dpool, None, cin, gsum=self._gsum(recs[ri], pooled=True))
+                self._cnl_bwd(tag, r1, dmid, None, n, True, dpool, None, cin, gsum=self._gsum(recs[ri], pooled=True), on_wgrad=on_wgrad)
             else:
                 if need_dx is True:
                     dx16 = A.get(f"bwd/dx16/{n}", (n, h, w, self.pad), self.gdt)
-                    self._cnl_bwd(tag, r1, dmid, None, n, True, dx16, None, cin)
+                    self._cnl_bwd(tag, r1, dmid, None, n, True, dx16, None, cin, on_wgrad=on_wgrad)
                     return dx16
-                dz0 = self._cnl_bwd(tag, r1, dmid, None, n, False)
+                dz0 = self._cnl_bwd(tag, r1, dmid, None, n, False, on_wgrad=on_wgrad)
                 return dz0 if need_dx == "dz" else None
         return None
 
@@ -953,15 +854,7 @@ class Discriminator(_ModelBase):
 
     def __init__(self, image_size, filter_size, device, arena, ws_provider, dropout=0.2, lane=None, dtype=torch.float32,
                  grad_dtype=None, attention=False):
-        # image_size: the training frame, a side or a pair (H, W); S is the side of a square frame and None otherwise
-        self.H, self.W = frame_hw(image_size)
-        self.S, self.F, self.dev = (self.H if self.H == self.W else None), filter_size, device
-        self.attention = bool(attention)
-        self.arena, self.ws_provider = arena, ws_provider
-        self.lane = lane or WgradLane(device, enabled=False)
-        self.adt = dtype
-        self.gdt = (grad_dtype or dtype) if dtype != torch.float32 else torch.float32
-        self.pad = pad_channels(dtype)
+        super().__init__(image_size, filter_size, device, arena, ws_provider, lane, dtype, grad_dtype, attention)
         # pitch of the 3-channel input images (elements): ONE 16-byte chunk per pixel -- r, g, b, 0 in float32; r, g, b and five zeros in
         # bfloat16 -- instead of the 64-byte MFMA staging row (round 4: the padded tensor was 403 MB written and read twice per step for
         # 38-75 MB of pixels).  The first layer's forward and weight gradient have kernels for this layout (csrc: conv3x3s2_rgb_*); the
@@ -969,12 +862,10 @@ class Discriminator(_ModelBase):
         self.in_pitch = 4 if dtype == torch.float32 else 8
         if os.environ.get("SHM_D_INPUT") == "staging":       # A/B against the round-3 layout (tools/README.md)
             self.in_pitch = self.pad
-        self.gsum = ops.gsum_default(dtype)
         self.dropout = dropout
         assert self.H % 32 == 0 and self.W % 32 == 0, "the discriminator has five stride-2 blocks: the sides are multiples of 32"
         f = filter_size
-        self.sh, self.sw = self.H // 32, self.W // 32          # the PatchGAN map; s is its side on a square frame
-        self.s = self.sh if self.sh == self.sw else None
+        self.sh, self.sw = self.H // 32, self.W // 32          # the PatchGAN map
         self.chan = [3, f, 2 * f, 4 * f, 8 * f, 16 * f]
         shapes = [(3, 3, self.chan[i], self.chan[i + 1]) for i in range(5)]
         shapes += [(3, 3, 16 * f, 1), (dense_inputs((self.H, self.W), f), 5)]
@@ -994,56 +885,29 @@ class Discriminator(_ModelBase):
         self.betas = [torch.zeros(c, dtype=torch.float32, device=device) for c in self.chan[1:]]
         self.wk = [torch.zeros(9 * self.chan[i + 1] * _padk(self.chan[i], self.pad), dtype=dtype, device=device)
                    for i in range(5)]
-        self.weights_dirty = True
-        self._tb = None
         self.ctx = None
 
-    def set_betas(self, arrays):
-        for b, a in zip(self.betas, arrays):
-            b.copy_(torch.as_tensor(np.asarray(a, dtype=np.float32)))
-
-    def prepare_weights(self):
-        if not self.weights_dirty:
-            return
-        self.P.refresh_operands()
-        if self._tb is None:
-            items = [(self.P.vars[i], self.wk[i], 9, self.chan[i], self.chan[i + 1], _padk(self.chan[i], self.pad)) for i in range(5)]
-            if self.attn is not None:
-                items += self.attn.transpose_items()
-            self._tb = ops.TransposeBatch(items)
-        self._tb.run()
-        self.weights_dirty = False
+    def _transpose_items(self):
+        items = [(self.P.vars[i], self.wk[i], 9, self.chan[i], self.chan[i + 1], _padk(self.chan[i], self.pad)) for i in range(5)]
+        return items + (self.attn.transpose_items() if self.attn is not None else [])
 
     def zero_grad(self):
         ops.zero(self.P.grad)
         if self.attn is not None:
             ops.zero(self.acc)
 
-    def _acc_slice(self, var_index):
-        o = self.P.offsets[var_index] - self.acc_off
-        return self.acc[o:o + self.P.vars[var_index].numel()]
-
     def attention_forward(self, mask, B):
         """attn_disc (SHM.py:358) of the step's SpecSeg mask [B,H,W,1]; pass the result to forward(attn=)."""
         self.prepare_weights()
-        self._attn_B = B
         return self.attn.forward(mask, B, self.H, self.W)
 
-    def forward(self, xd16, keep_mask=None, mask_rows=(), parts=None, attn=None, join=None):
+    def forward(self, xd16, keep_mask=None, mask_rows=(), attn=None):
         """xd16 [N,H,W,16] (rgb + zeros).  keep_mask [len(mask_rows)...] is the Dropout keep mask of
         the `training=True` samples: mask_rows = list of (row_start, nrows, mask_row_start).
-        parts: optional list of (row0, row1, run) -- the conv trunk is evaluated per row range (samples
-        are independent: InstanceNorm) through `run(fn)`; the trainer uses it to push the real-image
-        half onto the second stream while the generator is still producing the fake half; join() is then
-        called before the heads."""
-        n = xd16.shape[0]
+        The three steps below in one go; the trainer calls them itself to push the real-image half of the trunk onto the second
+        stream while the generator is still producing the fake half (samples are independent: InstanceNorm)."""
         self.start(xd16, keep_mask, mask_rows, attn)
-        if parts is None:
-            parts = [(0, n, lambda fn: fn())]
-        for r0, r1, run in parts:
-            run(lambda r0=r0, r1=r1: self.trunk_rows(r0, r1))
-        if join is not None:          # parts that ran on another stream: the heads below read every row
-            join()
+        self.trunk_rows(0, xd16.shape[0])
         return self.heads()
 
     def start(self, xd16, keep_mask=None, mask_rows=(), attn=None):
@@ -1082,7 +946,7 @@ class Discriminator(_ModelBase):
             cur, ld, h, w = ahat[r0:r1], cout, ho, wo
             if i == 3 and self._pending["attn"] is not None:
                 x3p = self._pending["x3p"]
-                ops.add_bcast(cur, self._pending["attn"], x3p[r0:r1], nb, ho * wo * cout, self._attn_B, r0)
+                ops.add_bcast(cur, self._pending["attn"], x3p[r0:r1], nb, ho * wo * cout, self._pending["attn"].shape[0], r0)
                 cur = x3p[r0:r1]
 
     def heads(self):
@@ -1108,7 +972,8 @@ class Discriminator(_ModelBase):
         cls = A.get(f"d/cls/{n}", (n, 5))
         ops.patch_fwd(cur, c5, self.P.vars[5], rf, n, h, w, c5, LRELU)
         ops.dense_fwd(cur, self.P.vars[6], cls, n, per, 5)
-        self.ctx = dict(n=n, recs=recs, x5=cur, rf=rf, cls=cls, keep_mask=keep_mask, mask_rows=mask_rows, attn=pd["attn"] is not None)
+        self.ctx = dict(n=n, recs=recs, x5=cur, rf=rf, cls=cls, keep_mask=keep_mask, mask_rows=mask_rows,
+                        attn=0 if pd["attn"] is None else int(pd["attn"].shape[0]))     # samples behind the attention map (0: none)
         return rf, cls
 
     def _backward(self, n, drf, dcls, params, need_dx):
@@ -1163,7 +1028,7 @@ class Discriminator(_ModelBase):
                 ops.conv2d_dgrad(dz, cout, self.P.op_vars[i], dprev, None, cin, ldx, 0, n, h, w, cin, cout, 3, 2, gsum=gs)
                 dcur = dprev
                 if i == 4 and params and c["attn"]:          # d attn_disc = sum over the copies of each sample; then its branch
-                    B = self._attn_B
+                    B = c["attn"]
                     da = A.get(f"d/bwd/dattn/{B}", (B, h, w, cin), self.gdt)
                     ops.sum_groups(dprev, da, n, h * w * cin, B, 0)
                     self.attn.backward(da)

@@ -168,11 +168,6 @@ class ShmGANwithSSpecSeg:
         self.before_backward = None
         # training telemetry (telemetry.py): None = off, the default; start_telemetry() / train() create it
         self.telemetry = None
-        # SHM_FORWARD_PARTS=2: the two big forward passes (cyclic generator pass on 5B images, discriminator on 12B) as two half
-        # batches on the two streams (samples are independent).  Measured in round 3 and NOT the default: in lockstep the halves
-        # gain 0.2 ms of a 121 ms fp32 step (within noise), taking turns convolution by convolution (so that one half's normalisation
-        # pass runs under the other's convolution) LOSES 2 ms -- a single stream already fills the launch tails
-        self.forward_parts = int(os.environ.get("SHM_FORWARD_PARTS", "1"))
         # the D-loss backward on the second stream (train_step): measured on one box, A/B by the variable, bf16 22.48 -> 22.25 ms, S = 512 B = 4
         # 42.79 -> 42.58, B = 32 79.3 -> 78.6; fp32 114.2 -> 114.2 (MFMA bound either way) -- default on in bf16, off in fp32
         self.d_fwd_on_lane = os.environ.get("SHM_D_FWD_LANE", "1" if self.compute_dtype != torch.float32 else "0") == "1"
@@ -626,7 +621,7 @@ class ShmGANwithSSpecSeg:
         # The REAL half of the discriminator batch (D2, D4: SHM.py:563, 638-642) depends on no generator output: in bf16 its five convolution
         # blocks run on the second stream beside the generator's forward passes (round 6); the heads wait for `ev_dreal`
         ev_dreal = None
-        d_real_early = self.d_fwd_on_lane and lane.stream is not None and not (self.forward_parts > 1)
+        d_real_early = self.d_fwd_on_lane and lane.stream is not None
 
         def pack_real():
             ops.pack_rgb16(orig[4], noise[B:2 * B], xd[6 * B:7 * B], B * npix)                 # D(2) SHM.py:563
@@ -649,7 +644,7 @@ class ShmGANwithSSpecSeg:
         # ---- G(2): cyclic  SHM.py:576-624
         cyc_in = A.get("cyc/in", (5 * B, H, W, PAD_C), adt)
         ops.build_gen_input(ds, gen_Y, fmask, 1, cyc_in, B, npix)
-        cyc_Y = G.forward(cyc_in, "cyc", attn=attn_g, parts=self.forward_parts)
+        cyc_Y = G.forward(cyc_in, "cyc", attn=attn_g)
         cyc_rgb = A.get("cyc/rgb", (5 * B, H, W, 3))
         ops.yuv2rgb(cyc_Y, cbcr, None, cyc_rgb, xd[B:6 * B], 5 * B, B, npix)
         if not d_real_early:
@@ -667,11 +662,8 @@ class ShmGANwithSSpecSeg:
         dptr = (C.c_void_p * 5)(*[t.data_ptr() for t in ds])
         ev_img = None
 
-        def image_losses():         # a square frame goes through the square entry, as it always has (one implementation behind both)
-            if H == W:
-                ops.image_losses(gen_rgb, cyc_rgb, cyc_Y, cbcr, optr, dptr, fmask, sf, il, dgen_y, dcyc_y, ws, B, H)
-            else:
-                ops.image_losses_hw(gen_rgb, cyc_rgb, cyc_Y, cbcr, optr, dptr, fmask, sf, il, dgen_y, dcyc_y, ws, B, H, W)
+        def image_losses():
+            ops.image_losses_hw(gen_rgb, cyc_rgb, cyc_Y, cbcr, optr, dptr, fmask, sf, il, dgen_y, dcyc_y, ws, B, H, W)
         if self.img_loss_on_lane and lane.stream is not None:
             lane.submit(image_losses)
             ev_img = lane.event()
@@ -679,15 +671,12 @@ class ShmGANwithSSpecSeg:
             image_losses()
 
         # ---- D on all 12B images (noise + dropout on the D1 and D2 slices only)
-        dparts = None
-        if self.forward_parts > 1 and lane.stream is not None:     # fake half on the main stream, real half on the second one
-            dparts = [(6 * B, 12 * B, lane.submit), (0, 6 * B, lambda fn: fn())]
         if d_real_early:
             D.trunk_rows(0, 6 * B)                                  # the fake half, here; the real half is already under way on the second stream
             torch.cuda.current_stream().wait_event(ev_dreal)
             rf, cls = D.heads()
         else:
-            rf, cls = D.forward(xd, keep, [(0, B, 0), (6 * B, B, B)], parts=dparts, attn=attn_d, join=lane.join if dparts else None)
+            rf, cls = D.forward(xd, keep, [(0, B, 0), (6 * B, B, B)], attn=attn_d)
         np_ = (H // 32) * (W // 32)
 
         # ---- losses  SHM.py:669-844
@@ -1007,7 +996,7 @@ class ShmGANwithSSpecSeg:
             ops.build_gen_input(ys, orig_Ych, 0b11111, 1, cyc_in, B, npix)      # view k zero, the others = orig_Ych
             cyc_rgb = A.get("inf/cyc_rgb", (5 * B, H, W, 3))
             if model_frame:
-                cyc_Y = G.forward(cyc_in, "inf5", attn=attn, parts=self.forward_parts)
+                cyc_Y = G.forward(cyc_in, "inf5", attn=attn)
                 ops.yuv2rgb(cyc_Y, cbcr, None, cyc_rgb, None, 5 * B, B, npix)
             else:
                 # one pass at a time through the buffers of "inf1", its output plane included: G1's Y moves to a buffer of its own
@@ -1025,9 +1014,8 @@ class ShmGANwithSSpecSeg:
 
     def evaluate(self, rgb, diffuse=None):
         """One batch of the reference's test mode (test.py:218-392): `infer(rgb)` and, when the diffuse targets are given
-        ([B,H,W,3] in [0,1], the shape of rgb), their image-quality metrics against gen_rgb (ops.image_metrics, on the library's
-        kernels; a frame other than a square one is scored whole by ops.image_metrics_hw).  `evaluate_frame` is the same with a
-        window and without the cyclic passes.
+        ([B,H,W,3] in [0,1], the shape of rgb), their image-quality metrics against gen_rgb (ops.image_metrics_hw over the whole
+        frame, on the library's kernels).  `evaluate_frame` is the same with a window and without the cyclic passes.
         Returns (gen_rgb, [5 x cyc_rgb], metrics): metrics is a float64 [B,5] device tensor {mse, psnr, ssim, de76, de94} per
         image (ops.METRIC_NAMES), or None.  Asynchronous like infer; gen_rgb and the metrics live until the next call."""
         return self.evaluate_frame(rgb, diffuse)
@@ -1037,7 +1025,7 @@ class ShmGANwithSSpecSeg:
         (in [0,1]), their image-quality metrics against gen_rgb (on the library's kernels).  window = (top, left, h, w): the part
         of the frame that is the photo (native-resolution test mode pads a photo to multiples of 16, data.pad_geometry); the
         targets are then tight [B,h,w,3] and the metrics are taken on the window only (ops.image_metrics_hw).  Without a window
-        the targets have the frame's shape (ops.image_metrics on a square frame).
+        the targets have the frame's shape and the window is the whole frame.
         Returns (gen_rgb, [5 x cyc_rgb], metrics): metrics is a float64 [B,5] device tensor {mse, psnr, ssim, de76, de94} per
         image (ops.METRIC_NAMES), or None.  Asynchronous like infer; gen_rgb and the metrics live until the next call."""
         gen_rgb, cyc = self.infer(rgb, cyclic)
@@ -1050,17 +1038,13 @@ class ShmGANwithSSpecSeg:
         if diffuse is not None:
             t = self._dev(diffuse)
             out = self.arena.get("eval/metrics", (B, 5), torch.float64)
-            if window is None and H == W:
-                if tuple(t.shape) != tuple(gen_rgb.shape):
-                    raise ValueError(f"diffuse images {tuple(t.shape)} do not match the generated ones {tuple(gen_rgb.shape)}")
-                metrics = ops.image_metrics(gen_rgb, t, out=out, arena=self.arena)
-            else:
-                win = (0, 0, H, W) if window is None else (top, left, h, w)
-                if tuple(t.shape) != (B, win[2], win[3], 3):
-                    raise ValueError(f"diffuse images {tuple(t.shape)} do not match the window {win[2]} x {win[3]} of the generated ones")
-                metrics = ops.image_metrics_hw(gen_rgb, win, t, out=out, arena=self.arena)
+            win = (0, 0, H, W) if window is None else (top, left, h, w)
+            if tuple(t.shape) != (B, win[2], win[3], 3):
+                raise ValueError(f"diffuse images {tuple(t.shape)} do not match the generated ones {tuple(gen_rgb.shape)}" if window is None else
+                                 f"diffuse images {tuple(t.shape)} do not match the window {win[2]} x {win[3]} of the generated ones")
+            metrics = ops.image_metrics_hw(gen_rgb, win, t, out=out, arena=self.arena)
             if self.eval_region is not None:
-                self._region_metrics(self.eval_region, self._inf_photo, gen_rgb, t, (0, 0, H, W) if window is None else (top, left, h, w))
+                self._region_metrics(self.eval_region, self._inf_photo, gen_rgb, t, win)
         return gen_rgb, cyc, metrics
 
     EVAL_REGIONS = ("residual", "specseg")
@@ -1089,7 +1073,7 @@ class ShmGANwithSSpecSeg:
 
     def _img_ws(self, B):
         H, W = self.image_hw
-        n = ops.image_losses_workspace(B, H) if H == W else ops.image_losses_hw_workspace(B, H, W)
+        n = ops.image_losses_hw_workspace(B, H, W)
         return self.arena.get("loss/ws", ((n + 3) // 4,))
 
     # ------------------------------------------------------------------ named losses (lazy D2H)

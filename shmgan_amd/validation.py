@@ -59,10 +59,7 @@ def validate(t, dataset=None, weights=("raw",), region="args"):
             for i, batch in enumerate(dataset):
                 gen_rgb, _ = t.infer(batch[0], cyclic=False)
                 H, W = int(gen_rgb.shape[1]), int(gen_rgb.shape[2])
-                if H == W:
-                    ops.image_metrics(gen_rgb, batch[4], out=rows[i * B:(i + 1) * B], arena=t.arena)
-                else:                   # a rectangular model frame, scored whole
-                    ops.image_metrics_hw(gen_rgb, (0, 0, H, W), t._dev(batch[4]), out=rows[i * B:(i + 1) * B], arena=t.arena)
+                ops.image_metrics_hw(gen_rgb, (0, 0, H, W), t._dev(batch[4]), out=rows[i * B:(i + 1) * B], arena=t.arena)     # the model frame, scored whole
                 if region is not None:
                     t._region_metrics(region, t._dev(batch[0]), gen_rgb, t._dev(batch[4]), (0, 0, H, W), out=rrows[i * B:(i + 1) * B])
             # the pass's one device-to-host copy (it synchronises)

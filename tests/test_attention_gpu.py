@@ -170,3 +170,30 @@ def test_live_attention_bf16_runs_and_tracks_fp32():
     # whole-model cosine against fp32 sits at 0.97-0.99 at this size; the pinned comparison is test_bf16_gpu.py's
     assert cosine(host(res["bfloat16"][1]), host(res["float32"][1])) > 0.95
     assert cosine(host(res["bfloat16"][2]), host(res["float32"][2])) > 0.95
+
+
+def test_live_attention_step_is_the_same_with_the_d_backward_on_either_stream():
+    """bf16 with attention="live" at the smallest frame the discriminator takes and the smallest filter count bf16 takes (S = 64,
+    F = 32, B = 1): the discriminator's attention branch and the generator's level-3 branch both have 8F = 256 channels.  With
+    d_bwd_on_lane the discriminator's branch runs its backward on the second stream while the generator's branches run theirs on
+    the main one; each branch has a LeakyReLU-backward scratch of its own, so one step gives the same flat gradients and named
+    losses whichever stream the D-loss backward is on, to the bound of two runs of one step
+    (test_train_loop_gpu.py::test_full_size_step_is_reproducible_over_many_runs: 1e-6, the float64 atomics)."""
+    S, F, B = 64, 32, 1
+    m, _, _ = _mk_live(S, F, B, dt="bfloat16")
+    assert m._get_lane().stream is not None                 # there is a second stream for the schedule to use
+    inp, dr = st.make_inputs(B, S), st.make_draws(4, B, S, F)
+    res = []
+    for on_lane in (True, False):
+        m.d_bwd_on_lane = on_lane
+        m.train_step(*inp, draws=dr, apply=False)
+        torch.cuda.synchronize()
+        res.append((dict(m.losses()), host(m.G.P.grad).copy(), host(m.D.P.grad).copy()))
+    (l1, g1, d1), (l0, g0, d0) = res
+    assert np.linalg.norm(host(m.G.P.grads[46 + 12])) > 0 and np.linalg.norm(host(m.D.P.grads[7])) > 0      # both 256-channel branches are live
+    eg, ed = rel_l2(g1, g0), rel_l2(d1, d0)
+    print(f"second stream against main stream: G gradient rel-L2 {eg:.3e}, D gradient rel-L2 {ed:.3e}")
+    for k, v in l0.items():
+        a, b = np.asarray(l1[k], np.float64), np.asarray(v, np.float64)
+        assert np.all(np.abs(a - b) <= 1e-6 * np.maximum(1.0, np.abs(b))), (k, v, l1[k])
+    assert eg <= 1e-6 and ed <= 1e-6, (eg, ed)

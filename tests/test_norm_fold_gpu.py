@@ -425,7 +425,7 @@ def test_default_policy_folds_the_float32_wreg_consumers():
     for dt, want in (("float32", [0, 20]), ("bfloat16", [])):
         m = ShmGANwithSSpecSeg(image_size=64, filter_size=64, batch_size=1, compute_dtype=dt).build()
         assert m.G.fold == "auto"
-        plan = m.G._fold_plan(5, 5, False)
+        plan = m.G._fold_plan(5, False)
         assert sorted(li for li, on in plan.items() if on) == want, (dt, plan)
 
 

@@ -9,9 +9,8 @@
 //                          four views per tap (polar_est.h).  With `mix` the four view bytes of a tap become M . v, clamped to
 //                          the byte range, before the lerp; the estimate is made from the unmixed bytes (the unpolarised part
 //                          is mirror-invariant) and a fifth source is never mixed.
-// One thread per output pixel, 4 taps x n_src x 3 byte loads; pointers and the two small matrices travel by value.  At identity
-// parameters the arithmetic is that of resize_bilinear_u8_kernel / polar_views_u8_kernel to the bit: the same expressions, + 0.0f.
-// The per-pixel body is augment_px.h, which the batched kernel (augment_batch.hip) includes too.
+// One thread per output pixel, 4 taps x n_src x 3 byte loads; pointers and the two small matrices travel by value.  The per-pixel
+// body is augment_px.h (the sampler: bilinear.h), which the batched kernel (augment_batch.hip) and polar.hip include too.
 #include "augment_px.h"
 
 namespace {

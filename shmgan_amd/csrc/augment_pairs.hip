@@ -5,7 +5,7 @@
 //   shm_augment_pairs_u8   two launches per group, both with grid (pairs_blocks(ho*wo), samples of the group); block row blockIdx.y
 //                          reads its own descriptor from the kernel arguments (by value, block-uniform: pointers, sizes and crop sit
 //                          in SGPRs), as augment_batch.hip does.
-//     resample   per output pixel the coordinate, taps and lerp of augment_px.h (ONE definition, shared with shm_augment_views_u8):
+//     resample   per output pixel the coordinate, taps and lerp of bilinear.h (ONE definition, shared with shm_augment_views_u8):
 //                the mask's lerp times 1/255 goes to y; the three channels' lerps times 1/255 are converted by rgb2yuv (yuv.h, the
 //                function shm_rgb2yuv_std calls) in registers; the unscaled Y goes to x, and Y, U and V enter the block's two f64
 //                sums, which the block writes to ITS slot of the caller's workspace.  No atomics.
@@ -51,12 +51,13 @@ __global__ void __launch_bounds__(AU_NT) pairs_resample_kernel(const PairArgs a,
     float* const y = a.y + off;
     double s = 0.0, q = 0.0;
     for (size_t p = (size_t)blockIdx.x * AU_NT + threadIdx.x; p < npix; p += (size_t)gridDim.x * AU_NT) {
-        const AugTaps t = augment_taps((int)(p % wo), (int)(p / wo), d.hin, d.win, ho, wo, d.hs, d.ws, d.cy, d.cx, d.flags & 1, d.flags & 2);
-        y[p] = augment_lerp(d.mask[t.tl], d.mask[t.tr], d.mask[t.bl], d.mask[t.br], t.lx, t.ly) * PAIRS_SCALE;
+        const int ox = (int)(p % wo), oy = (int)(p / wo);              // the mirrors on the read side, as augment_pixel
+        const BilinearTaps t = bilinear_taps(d.flags & 2 ? wo - 1 - ox : ox, d.flags & 1 ? ho - 1 - oy : oy, d.hin, d.win, d.win, d.hs, d.ws, d.cy, d.cx);
+        y[p] = bilinear_lerp(d.mask[t.tl], d.mask[t.tr], d.mask[t.bl], d.mask[t.br], t.lx, t.ly) * PAIRS_SCALE;
         float c[3];
 #pragma unroll
         for (int k = 0; k < 3; ++k)
-            c[k] = augment_lerp(d.image[t.tl * 3 + k], d.image[t.tr * 3 + k], d.image[t.bl * 3 + k], d.image[t.br * 3 + k], t.lx, t.ly) * PAIRS_SCALE;
+            c[k] = bilinear_lerp(d.image[t.tl * 3 + k], d.image[t.tr * 3 + k], d.image[t.bl * 3 + k], d.image[t.br * 3 + k], t.lx, t.ly) * PAIRS_SCALE;
         float yy, u, v;
         rgb2yuv(c[0], c[1], c[2], yy, u, v);
         x[p] = yy;

@@ -1,47 +1,14 @@
-// The per-pixel body of the augmenting resize, shared by the kernel of one sample (augment.hip) and the batched one
-// (augment_batch.hip): one definition of the coordinate, the taps, the view mix and the lerp, so that the two agree bit for bit
-// (and, at identity parameters, with resize_bilinear_u8_kernel / polar_views_u8_kernel: the same expressions, + 0.0f).  The
-// coordinate / tap part and the lerp are functions of their own, which the image / mask pair kernel (augment_pairs.hip) calls too.
+// The per-pixel body of the augmenting resize, shared by the kernel of one sample (augment.hip), the batched one (augment_batch.hip)
+// and, at identity parameters, shm_polar_views_u8 (polar.hip): one definition of the mirrors, the view mix and the estimate around
+// the sampler of bilinear.h, so that they agree bit for bit.
 #pragma once
-#include "common.h"
+#include "bilinear.h"
 #include "polar_est.h"
 
 #include <math.h>
 
 constexpr int AU_NT = 256;
 constexpr int AU_DIM_MAX = 32768;               // hin, win, ho, wo
-
-// The coordinate and tap part, for one output pixel (oy, ox) of a plane of ho x wo: the four taps as PIXEL indices y * win + x of the
-// source (times the channel count gives the element) and the two weights.  Every argument but ox / oy is block-uniform.
-struct AugTaps {
-    size_t tl, tr, bl, br;
-    float lx, ly;
-};
-
-__device__ __forceinline__ AugTaps augment_taps(int ox, int oy, int hin, int win, int ho, int wo, float hs, float ws, float cy, float cx, int flip_ud,
-                                                int flip_lr) {
-    const int sy = flip_ud ? ho - 1 - oy : oy, sx = flip_lr ? wo - 1 - ox : ox;
-    // the coordinate of resize_bilinear_u8_kernel (data.hip) inside the crop window, then the window's origin; the taps are held
-    // inside the image on both sides (no-ops for a crop inside the image, kept so that no rounding can index outside it)
-    const float fy = (((float)sy + 0.5f) * hs - 0.5f) + cy, fx = (((float)sx + 0.5f) * ws - 0.5f) + cx;
-    const float fly = floorf(fy), flx = floorf(fx);
-    const int y0 = min(max((int)fly, 0), hin - 1), y1 = min(max((int)ceilf(fy), 0), hin - 1);
-    const int x0 = min(max((int)flx, 0), win - 1), x1 = min(max((int)ceilf(fx), 0), win - 1);
-    AugTaps t;
-    t.ly = fy - fly;
-    t.lx = fx - flx;
-    t.tl = (size_t)y0 * win + x0;
-    t.tr = (size_t)y0 * win + x1;
-    t.bl = (size_t)y1 * win + x0;
-    t.br = (size_t)y1 * win + x1;
-    return t;
-}
-
-// The lerp of the four tap values, before the output scale
-__device__ __forceinline__ float augment_lerp(float tl, float tr, float bl, float br, float lx, float ly) {
-    const float top = tl + (tr - tl) * lx, bot = bl + (br - bl) * lx;
-    return top + (bot - top) * ly;
-}
 
 // Output pixel idx = (oy, ox) of one sample.  ARGS has the members src[5] (uint8 [hin,win,3]; [4] only for SHM_AUG_DIR), dst[5]
 // (float32 [ho,wo,3]), coef (the row-major 3x4 Stokes matrix; STOKES only) and mix (the row-major 4x4 view mix; MIX only), arrays
@@ -51,7 +18,9 @@ __device__ __forceinline__ void augment_pixel(const ARGS& a, size_t idx, int hin
                                               float scale, int flip_ud, int flip_lr) {
     constexpr int NSRC = MODE == SHM_AUG_DIR ? 5 : 4;
     const int ox = (int)(idx % wo), oy = (int)(idx / wo);
-    const AugTaps at = augment_taps(ox, oy, hin, win, ho, wo, hs, ws, cy, cx, flip_ud, flip_lr);
+    // the mirrors on the READ side: (oy, ox) samples at the position of output pixel (sy, sx) of the unmirrored result
+    const int sy = flip_ud ? ho - 1 - oy : oy, sx = flip_lr ? wo - 1 - ox : ox;
+    const BilinearTaps at = bilinear_taps(sx, sy, hin, win, win, hs, ws, cy, cx);
     const float ly = at.ly, lx = at.lx;
     const size_t itl = at.tl * 3, itr = at.tr * 3, ibl = at.bl * 3, ibr = at.br * 3;
     const size_t o = ((size_t)oy * wo + ox) * 3;
@@ -85,6 +54,6 @@ __device__ __forceinline__ void augment_pixel(const ARGS& a, size_t idx, int hin
             }
         }
 #pragma unroll
-        for (int v = 0; v < 5; ++v) a.dst[v][o + k] = augment_lerp(tl[v], tr[v], bl[v], br[v], lx, ly) * scale;
+        for (int v = 0; v < 5; ++v) a.dst[v][o + k] = bilinear_lerp(tl[v], tr[v], bl[v], br[v], lx, ly) * scale;
     }
 }

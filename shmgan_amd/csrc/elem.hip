@@ -101,25 +101,26 @@ __global__ void mask_pool_pack_kernel(const float* __restrict__ m, T* __restrict
     for (int c = 1; c < ld; ++c) o[c] = (T)0.f;
 }
 
+// both entry points behind their own checks: nothing to do for an empty output, else one launch
+static int mask_pool_pack(const char* who, const float* mask, void* dst, int lddst, int batch, int h, int w, int k, int dtype, void* stream) {
+    const size_t total = (size_t)batch * (h / k) * (w / k);
+    if (total == 0) return SHM_OK;
+    SHM_DISPATCH(dtype, who,
+                 hipLaunchKernelGGL(mask_pool_pack_kernel<T>, dim3(shm_cdiv((long)total, 256)), dim3(256), 0, (hipStream_t)stream, mask, (T*)dst, lddst, h, w, k, total));
+    SHM_LAUNCH_CHECK(who);
+    return SHM_OK;
+}
+
+// the square form takes s == 0 (an empty output) and does not look at batch's sign; the _hw form refuses h < 1 and batch < 0
 extern "C" int shm_mask_pool_pack(const float* mask, void* dst, int lddst, int batch, int s, int k, int dtype, void* stream) {
     SHM_REQUIRE(mask && dst && k >= 1 && s % k == 0 && lddst >= 1, SHM_E_SHAPE, "shm_mask_pool_pack: bad shape (s %d, k %d)", s, k);
-    const size_t total = (size_t)batch * (s / k) * (s / k);
-    if (total == 0) return SHM_OK;
-    SHM_DISPATCH(dtype, "shm_mask_pool_pack",
-                 hipLaunchKernelGGL(mask_pool_pack_kernel<T>, dim3(shm_cdiv((long)total, 256)), dim3(256), 0, (hipStream_t)stream, mask, (T*)dst, lddst, s, s, k, total));
-    SHM_LAUNCH_CHECK("shm_mask_pool_pack");
-    return SHM_OK;
+    return mask_pool_pack("shm_mask_pool_pack", mask, dst, lddst, batch, s, s, k, dtype, stream);
 }
 
 extern "C" int shm_mask_pool_pack_hw(const float* mask, void* dst, int lddst, int batch, int h, int w, int k, int dtype, void* stream) {
     SHM_REQUIRE(mask && dst && k >= 1 && h >= 1 && w >= 1 && h % k == 0 && w % k == 0 && lddst >= 1 && batch >= 0, SHM_E_SHAPE,
                 "shm_mask_pool_pack_hw: bad shape (h %d, w %d, k %d)", h, w, k);
-    const size_t total = (size_t)batch * (h / k) * (w / k);
-    if (total == 0) return SHM_OK;
-    SHM_DISPATCH(dtype, "shm_mask_pool_pack_hw",
-                 hipLaunchKernelGGL(mask_pool_pack_kernel<T>, dim3(shm_cdiv((long)total, 256)), dim3(256), 0, (hipStream_t)stream, mask, (T*)dst, lddst, h, w, k, total));
-    SHM_LAUNCH_CHECK("shm_mask_pool_pack_hw");
-    return SHM_OK;
+    return mask_pool_pack("shm_mask_pool_pack_hw", mask, dst, lddst, batch, h, w, k, dtype, stream);
 }
 
 // out[i] = a[i] + b[(i0 + i) % nb]  over images of `per` elements each: the skip tensor plus the attention map of its sample

@@ -1,8 +1,7 @@
 // Image export of the reference's test mode (test.py:305-317 logs these images to Comet; here they become files): float32
 // planes [S,S,C] (C in {1,3}, channel pitch ld) -> uint8 [ho,wo,C], resampled to the source photo's size and mapped to bytes.
 //
-//   resampling  tf.image.resize(bilinear, half-pixel centres, no antialias): the mapping of resize_bilinear_u8_kernel (data.hip),
-//               on the raw float values, in fp32; at (ho,wo) = (S,S) the pixel itself
+//   resampling  the sampler of bilinear.h on the raw float values, in fp32; at (ho,wo) = (S,S) the pixel itself
 //   value maps  RESCALE rescale_01 (utils.py:190-195, test_plot at test.py:410-425): (v - min) / (max - min), min / max over the
 //               whole S*S*C source plane, divide_no_nan;  SCALE v * mul[k];  CLIP v
 //   bytes       rint(clamp(t, 0, 1) * 255) in fp32, round half to even (a NaN becomes 0)
@@ -18,7 +17,7 @@
 // shm_export_u8_hw is the same two kernels on a window (y0, x0, hc, wc) of a rectangular source [hs,ws,C] (native-resolution test
 // mode: the photo inside its padded frame): a job carries the pointer to the window's first pixel, the window's size and the
 // frame's row pitch, so min / max and the resampling see the window only.  The square call is the window (0, 0, s, s) of pitch s.
-#include "common.h"
+#include "bilinear.h"
 
 #include <limits.h>
 #include <math.h>
@@ -152,16 +151,8 @@ __global__ void __launch_bounds__(EX_NT) export_u8_kernel(const ExArgs a) {
         for (int q = 0; q < nq; ++q) {
             float v;
             if (resample) {
-                // ResizeBilinear with half_pixel_centers, as resize_bilinear_u8_kernel (data.hip)
-                const float fy = ((float)oy + 0.5f) * hs - 0.5f, fx = ((float)ox + 0.5f) * ws - 0.5f;
-                const float fly = floorf(fy), flx = floorf(fx);
-                const int y0 = max((int)fly, 0), y1 = min((int)ceilf(fy), hc - 1);
-                const int x0 = max((int)flx, 0), x1 = min((int)ceilf(fx), wc - 1);
-                const float ly = fy - fly, lx = fx - flx;
-                const float tl = src[((size_t)y0 * pitch + x0) * ld + ch], tr = src[((size_t)y0 * pitch + x1) * ld + ch];
-                const float bl = src[((size_t)y1 * pitch + x0) * ld + ch], br = src[((size_t)y1 * pitch + x1) * ld + ch];
-                const float top = tl + (tr - tl) * lx, bot = bl + (br - bl) * lx;
-                v = top + (bot - top) * ly;
+                const BilinearTaps t = bilinear_taps(ox, oy, hc, wc, pitch, hs, ws, 0.f, 0.f);
+                v = bilinear_lerp(src[t.tl * ld + ch], src[t.tr * ld + ch], src[t.bl * ld + ch], src[t.br * ld + ch], t.lx, t.ly);
             } else {
                 v = src[((size_t)oy * pitch + ox) * ld + ch];
             }
@@ -236,12 +227,14 @@ extern "C" size_t shm_export_u8_workspace(int njobs) {
     return njobs > 0 ? (size_t)njobs * EX_MM * 2 * sizeof(float) : 0;
 }
 
-extern "C" int shm_export_u8(const float* const* src, const size_t* desc, int njobs, const float* mul, int nmul,
-                             unsigned char* dst, size_t dst_bytes, void* ws, size_t ws_bytes, void* stream) {
-    SHM_REQUIRE(njobs >= 1 && njobs <= SHM_EXPORT_MAX_JOBS, SHM_E_SHAPE, "shm_export_u8: njobs %d outside [1, %d]", njobs,
-                SHM_EXPORT_MAX_JOBS);
-    SHM_REQUIRE(src && desc && dst, SHM_E_SHAPE, "shm_export_u8: null pointer (src, desc or dst)");
-    SHM_REQUIRE(((uintptr_t)dst & 3) == 0, SHM_E_SHAPE, "shm_export_u8: dst is not 4-byte aligned");
+// Both entry points: a descriptor row of `width` words is {s, c, ld, ho, wo, mode, k, off} (SHM_EXPORT_DESC: the window (0, 0, s, s) of
+// an s x s plane) or {hs, ws, c, ld, y0, x0, hc, wc, ho, wo, mode, k, off} (SHM_EXPORT_HW_DESC)
+static int export_entry(const char* who, int width, const float* const* src, const size_t* desc, int njobs, const float* mul, int nmul,
+                        unsigned char* dst, size_t dst_bytes, void* ws, size_t ws_bytes, void* stream) {
+    const bool sq = width == SHM_EXPORT_DESC;
+    SHM_REQUIRE(njobs >= 1 && njobs <= SHM_EXPORT_MAX_JOBS, SHM_E_SHAPE, "%s: njobs %d outside [1, %d]", who, njobs, SHM_EXPORT_MAX_JOBS);
+    SHM_REQUIRE(src && desc && dst, SHM_E_SHAPE, "%s: null pointer (src, desc or dst)", who);
+    SHM_REQUIRE(((uintptr_t)dst & 3) == 0, SHM_E_SHAPE, "%s: dst is not 4-byte aligned", who);
     ExArgs a;
     a.dst = dst;
     a.mul = mul;
@@ -249,69 +242,44 @@ extern "C" int shm_export_u8(const float* const* src, const size_t* desc, int nj
     a.njobs = njobs;
     int blk = 0, mblk = 0;
     for (int j = 0; j < njobs; ++j) {
-        const size_t* d = desc + (size_t)j * SHM_EXPORT_DESC;
-        const size_t s = d[0], c = d[1], ld = d[2], ho = d[3], wo = d[4], mode = d[5], k = d[6], off = d[7];
-        SHM_REQUIRE(src[j], SHM_E_SHAPE, "shm_export_u8: job %d: null pointer (source plane)", j);
-        SHM_REQUIRE(c == 1 || c == 3, SHM_E_SHAPE, "shm_export_u8: job %d: c %zu not in {1, 3}", j, c);
-        SHM_REQUIRE(s >= 1 && s <= EX_DIM_MAX && ho >= 1 && ho <= EX_DIM_MAX && wo >= 1 && wo <= EX_DIM_MAX, SHM_E_SHAPE,
-                    "shm_export_u8: job %d: sizes s %zu, ho %zu, wo %zu outside [1, %d]", j, s, ho, wo, EX_DIM_MAX);
-        SHM_REQUIRE(ld >= c && ld <= 65536, SHM_E_SHAPE, "shm_export_u8: job %d: ld %zu outside [c, 65536]", j, ld);
-        const size_t nbytes = ho * wo * c;
-        SHM_REQUIRE(nbytes <= (size_t)INT_MAX - EX_BLOCK_BYTES && s * s * c <= (size_t)INT_MAX, SHM_E_SHAPE,
-                    "shm_export_u8: job %d: plane too large", j);
-        SHM_REQUIRE(mode <= SHM_EXPORT_CLIP, SHM_E_SHAPE, "shm_export_u8: job %d: mode %zu unknown", j, mode);
-        SHM_REQUIRE(mode != SHM_EXPORT_SCALE || (mul && nmul > 0 && k < (size_t)nmul), SHM_E_SHAPE,
-                    "shm_export_u8: job %d: SCALE needs mul and k %zu < nmul %d", j, k, nmul);
-        SHM_REQUIRE((off & 3) == 0, SHM_E_SHAPE, "shm_export_u8: job %d: destination offset %zu not a multiple of 4", j, off);
-        SHM_REQUIRE(off <= dst_bytes && nbytes <= dst_bytes - off, SHM_E_SHAPE,
-                    "shm_export_u8: job %d: destination [%zu, %zu) outside dst_bytes %zu", j, off, off + nbytes, dst_bytes);
-        add_job(a, j, src[j], (int)s, (int)s, (int)s, (int)c, (int)ld, (int)ho, (int)wo, (int)mode, (int)k, off, blk, mblk);
-    }
-    const size_t need = shm_export_u8_workspace(njobs);
-    SHM_REQUIRE(ws && ((uintptr_t)ws & 3) == 0 && ws_bytes >= need, SHM_E_WORKSPACE,
-                "shm_export_u8: workspace of %zu bytes (4-byte aligned) needed, %zu given", need, ws ? ws_bytes : 0);
-    return export_launch(a, blk, mblk, stream, "shm_export_u8");
-}
-
-extern "C" int shm_export_u8_hw(const float* const* src, const size_t* desc, int njobs, const float* mul, int nmul, unsigned char* dst,
-                                size_t dst_bytes, void* ws, size_t ws_bytes, void* stream) {
-    SHM_REQUIRE(njobs >= 1 && njobs <= SHM_EXPORT_MAX_JOBS, SHM_E_SHAPE, "shm_export_u8_hw: njobs %d outside [1, %d]", njobs,
-                SHM_EXPORT_MAX_JOBS);
-    SHM_REQUIRE(src && desc && dst, SHM_E_SHAPE, "shm_export_u8_hw: null pointer (src, desc or dst)");
-    SHM_REQUIRE(((uintptr_t)dst & 3) == 0, SHM_E_SHAPE, "shm_export_u8_hw: dst is not 4-byte aligned");
-    ExArgs a;
-    a.dst = dst;
-    a.mul = mul;
-    a.mm = (float*)ws;
-    a.njobs = njobs;
-    int blk = 0, mblk = 0;
-    for (int j = 0; j < njobs; ++j) {
-        const size_t* d = desc + (size_t)j * SHM_EXPORT_HW_DESC;
-        const size_t hs = d[0], wsrc = d[1], c = d[2], ld = d[3], y0 = d[4], x0 = d[5], hc = d[6], wc = d[7], ho = d[8], wo = d[9], mode = d[10],
-                     k = d[11], off = d[12];
-        SHM_REQUIRE(src[j], SHM_E_SHAPE, "shm_export_u8_hw: job %d: null pointer (source plane)", j);
-        SHM_REQUIRE(c == 1 || c == 3, SHM_E_SHAPE, "shm_export_u8_hw: job %d: c %zu not in {1, 3}", j, c);
-        SHM_REQUIRE(hs >= 1 && hs <= EX_DIM_MAX && wsrc >= 1 && wsrc <= EX_DIM_MAX && ho >= 1 && ho <= EX_DIM_MAX && wo >= 1 && wo <= EX_DIM_MAX,
-                    SHM_E_SHAPE, "shm_export_u8_hw: job %d: sizes hs %zu, ws %zu, ho %zu, wo %zu outside [1, %d]", j, hs, wsrc, ho, wo, EX_DIM_MAX);
+        const size_t* d = desc + (size_t)j * width;
+        const size_t hs = d[0], wsrc = sq ? d[0] : d[1], c = sq ? d[1] : d[2], ld = sq ? d[2] : d[3];
+        const size_t y0 = sq ? 0 : d[4], x0 = sq ? 0 : d[5], hc = sq ? hs : d[6], wc = sq ? hs : d[7];
+        const size_t* t = d + (sq ? 3 : 8);
+        const size_t ho = t[0], wo = t[1], mode = t[2], k = t[3], off = t[4];
+        SHM_REQUIRE(src[j], SHM_E_SHAPE, "%s: job %d: null pointer (source plane)", who, j);
+        SHM_REQUIRE(c == 1 || c == 3, SHM_E_SHAPE, "%s: job %d: c %zu not in {1, 3}", who, j, c);
+        const bool sizes = hs >= 1 && hs <= EX_DIM_MAX && wsrc >= 1 && wsrc <= EX_DIM_MAX && ho >= 1 && ho <= EX_DIM_MAX && wo >= 1 && wo <= EX_DIM_MAX;
+        SHM_REQUIRE(sizes || !sq, SHM_E_SHAPE, "%s: job %d: sizes s %zu, ho %zu, wo %zu outside [1, %d]", who, j, hs, ho, wo, EX_DIM_MAX);
+        SHM_REQUIRE(sizes, SHM_E_SHAPE, "%s: job %d: sizes hs %zu, ws %zu, ho %zu, wo %zu outside [1, %d]", who, j, hs, wsrc, ho, wo, EX_DIM_MAX);
         SHM_REQUIRE(hc >= 1 && wc >= 1 && y0 <= hs && hc <= hs - y0 && x0 <= wsrc && wc <= wsrc - x0, SHM_E_SHAPE,
-                    "shm_export_u8_hw: job %d: window (%zu, %zu, %zu, %zu) outside the %zu x %zu source", j, y0, x0, hc, wc, hs, wsrc);
-        SHM_REQUIRE(ld >= c && ld <= 65536, SHM_E_SHAPE, "shm_export_u8_hw: job %d: ld %zu outside [c, 65536]", j, ld);
+                    "%s: job %d: window (%zu, %zu, %zu, %zu) outside the %zu x %zu source", who, j, y0, x0, hc, wc, hs, wsrc);
+        SHM_REQUIRE(ld >= c && ld <= 65536, SHM_E_SHAPE, "%s: job %d: ld %zu outside [c, 65536]", who, j, ld);
         const size_t nbytes = ho * wo * c;
-        SHM_REQUIRE(nbytes <= (size_t)INT_MAX - EX_BLOCK_BYTES && hc * wc * c <= (size_t)INT_MAX, SHM_E_SHAPE,
-                    "shm_export_u8_hw: job %d: plane too large", j);
-        SHM_REQUIRE(mode <= SHM_EXPORT_CLIP, SHM_E_SHAPE, "shm_export_u8_hw: job %d: mode %zu unknown", j, mode);
-        SHM_REQUIRE(mode != SHM_EXPORT_SCALE || (mul && nmul > 0 && k < (size_t)nmul), SHM_E_SHAPE,
-                    "shm_export_u8_hw: job %d: SCALE needs mul and k %zu < nmul %d", j, k, nmul);
-        SHM_REQUIRE((off & 3) == 0, SHM_E_SHAPE, "shm_export_u8_hw: job %d: destination offset %zu not a multiple of 4", j, off);
-        SHM_REQUIRE(off <= dst_bytes && nbytes <= dst_bytes - off, SHM_E_SHAPE,
-                    "shm_export_u8_hw: job %d: destination [%zu, %zu) outside dst_bytes %zu", j, off, off + nbytes, dst_bytes);
+        SHM_REQUIRE(nbytes <= (size_t)INT_MAX - EX_BLOCK_BYTES && hc * wc * c <= (size_t)INT_MAX, SHM_E_SHAPE, "%s: job %d: plane too large", who, j);
+        SHM_REQUIRE(mode <= SHM_EXPORT_CLIP, SHM_E_SHAPE, "%s: job %d: mode %zu unknown", who, j, mode);
+        SHM_REQUIRE(mode != SHM_EXPORT_SCALE || (mul && nmul > 0 && k < (size_t)nmul), SHM_E_SHAPE, "%s: job %d: SCALE needs mul and k %zu < nmul %d",
+                    who, j, k, nmul);
+        SHM_REQUIRE((off & 3) == 0, SHM_E_SHAPE, "%s: job %d: destination offset %zu not a multiple of 4", who, j, off);
+        SHM_REQUIRE(off <= dst_bytes && nbytes <= dst_bytes - off, SHM_E_SHAPE, "%s: job %d: destination [%zu, %zu) outside dst_bytes %zu", who, j,
+                    off, off + nbytes, dst_bytes);
         add_job(a, j, src[j] + (y0 * wsrc + x0) * ld, (int)wsrc, (int)hc, (int)wc, (int)c, (int)ld, (int)ho, (int)wo, (int)mode, (int)k, off, blk,
                 mblk);
     }
     const size_t need = shm_export_u8_workspace(njobs);
-    SHM_REQUIRE(ws && ((uintptr_t)ws & 3) == 0 && ws_bytes >= need, SHM_E_WORKSPACE,
-                "shm_export_u8_hw: workspace of %zu bytes (4-byte aligned) needed, %zu given", need, ws ? ws_bytes : 0);
-    return export_launch(a, blk, mblk, stream, "shm_export_u8_hw");
+    SHM_REQUIRE(ws && ((uintptr_t)ws & 3) == 0 && ws_bytes >= need, SHM_E_WORKSPACE, "%s: workspace of %zu bytes (4-byte aligned) needed, %zu given",
+                who, need, ws ? ws_bytes : 0);
+    return export_launch(a, blk, mblk, stream, who);
+}
+
+extern "C" int shm_export_u8(const float* const* src, const size_t* desc, int njobs, const float* mul, int nmul, unsigned char* dst,
+                             size_t dst_bytes, void* ws, size_t ws_bytes, void* stream) {
+    return export_entry("shm_export_u8", SHM_EXPORT_DESC, src, desc, njobs, mul, nmul, dst, dst_bytes, ws, ws_bytes, stream);
+}
+
+extern "C" int shm_export_u8_hw(const float* const* src, const size_t* desc, int njobs, const float* mul, int nmul, unsigned char* dst,
+                                size_t dst_bytes, void* ws, size_t ws_bytes, void* stream) {
+    return export_entry("shm_export_u8_hw", SHM_EXPORT_HW_DESC, src, desc, njobs, mul, nmul, dst, dst_bytes, ws, ws_bytes, stream);
 }
 
 extern "C" int shm_running_scale_mean(const float* scale, int batch, double* acc, float* mul, void* stream) {

@@ -418,58 +418,52 @@ int metrics_launch(const float* pred, const float* target, const unsigned char* 
     return SHM_OK;
 }
 
+// bytes of workspace of every entry point; 0 for a window or batch the entry point refuses
+template <bool REGION>
+size_t metrics_workspace(int batch, int h, int w) {
+    if (h < MWIN || w < MWIN || batch < 1) return 0;
+    return plan_metric_ws<REGION>(batch, h, w).total;
+}
+
+// The one body of the three entry points: the checks, the plan and the launches.  `square`: shm_image_metrics, the window (0, 0, s, s) of
+// an s x s frame, with its own wording and no limit on the frame's sides
+template <bool REGION>
+int metrics_entry(const char* who, bool square, const float* pred, int hp, int wp, int top, int left, const float* target, int h, int w,
+                  const unsigned char* region, double* out, void* ws, size_t ws_bytes, int batch, void* stream) {
+    SHM_REQUIRE(!square || h >= MWIN, SHM_E_SHAPE, "%s: image size %d < 11 (ssim window)", who, h);
+    SHM_REQUIRE(h >= MWIN && w >= MWIN, SHM_E_SHAPE, "%s: window %d x %d has a side < 11 (ssim window)", who, h, w);
+    SHM_REQUIRE(square || (top >= 0 && left >= 0 && hp >= 1 && wp >= 1 && hp <= 32768 && wp <= 32768 && top <= hp - h && left <= wp - w),
+                SHM_E_SHAPE, "%s: window (%d, %d, %d, %d) outside the %d x %d frame", who, top, left, h, w, hp, wp);
+    SHM_REQUIRE(batch >= 1 && batch <= 65535, SHM_E_SHAPE, "%s: bad batch %d", who, batch);
+    SHM_REQUIRE(pred && target && out && (!REGION || region), SHM_E_SHAPE, "%s: null pointer", who);
+    const MetricWs pl = plan_metric_ws<REGION>(batch, h, w);
+    SHM_REQUIRE(ws && ws_bytes >= pl.total, SHM_E_WORKSPACE, "%s: workspace %zu < %zu bytes", who, ws_bytes, pl.total);
+    const MetricWin win = {wp, top, left, h, w};
+    return metrics_launch<REGION>(pred, target, region, out, ws, pl, batch, win, (size_t)hp * wp, stream, who);
+}
+
 }  // namespace
 
-extern "C" size_t shm_image_metrics_workspace(int batch, int s) {
-    if (s < MWIN || batch < 1) return 0;
-    return plan_metric_ws<false>(batch, s, s).total;
-}
+extern "C" size_t shm_image_metrics_workspace(int batch, int s) { return metrics_workspace<false>(batch, s, s); }
 
 extern "C" int shm_image_metrics(const float* pred, const float* target, double* out, void* ws, size_t ws_bytes, int batch, int s,
                                  void* stream) {
-    SHM_REQUIRE(s >= MWIN, SHM_E_SHAPE, "shm_image_metrics: image size %d < 11 (ssim window)", s);
-    SHM_REQUIRE(batch >= 1 && batch <= 65535, SHM_E_SHAPE, "shm_image_metrics: bad batch %d", batch);
-    SHM_REQUIRE(pred && target && out, SHM_E_SHAPE, "shm_image_metrics: null pointer");
-    const MetricWs w = plan_metric_ws<false>(batch, s, s);
-    SHM_REQUIRE(ws && ws_bytes >= w.total, SHM_E_WORKSPACE, "shm_image_metrics: workspace %zu < %zu bytes", ws_bytes, w.total);
-    const MetricWin win = {s, 0, 0, s, s};
-    return metrics_launch<false>(pred, target, nullptr, out, ws, w, batch, win, (size_t)s * s, stream, "shm_image_metrics");
+    return metrics_entry<false>("shm_image_metrics", true, pred, s, s, 0, 0, target, s, s, nullptr, out, ws, ws_bytes, batch, stream);
 }
 
-extern "C" size_t shm_image_metrics_hw_workspace(int batch, int h, int w) {
-    if (h < MWIN || w < MWIN || batch < 1) return 0;
-    return plan_metric_ws<false>(batch, h, w).total;
-}
+extern "C" size_t shm_image_metrics_hw_workspace(int batch, int h, int w) { return metrics_workspace<false>(batch, h, w); }
 
 extern "C" int shm_image_metrics_hw(const float* pred, int hp, int wp, int top, int left, const float* target, int h, int w, double* out,
                                     void* ws, size_t ws_bytes, int batch, void* stream) {
-    SHM_REQUIRE(h >= MWIN && w >= MWIN, SHM_E_SHAPE, "shm_image_metrics_hw: window %d x %d has a side < 11 (ssim window)", h, w);
-    SHM_REQUIRE(top >= 0 && left >= 0 && hp >= 1 && wp >= 1 && hp <= 32768 && wp <= 32768 && top <= hp - h && left <= wp - w, SHM_E_SHAPE,
-                "shm_image_metrics_hw: window (%d, %d, %d, %d) outside the %d x %d frame", top, left, h, w, hp, wp);
-    SHM_REQUIRE(batch >= 1 && batch <= 65535, SHM_E_SHAPE, "shm_image_metrics_hw: bad batch %d", batch);
-    SHM_REQUIRE(pred && target && out, SHM_E_SHAPE, "shm_image_metrics_hw: null pointer");
-    const MetricWs pl = plan_metric_ws<false>(batch, h, w);
-    SHM_REQUIRE(ws && ws_bytes >= pl.total, SHM_E_WORKSPACE, "shm_image_metrics_hw: workspace %zu < %zu bytes", ws_bytes, pl.total);
-    const MetricWin win = {wp, top, left, h, w};
-    return metrics_launch<false>(pred, target, nullptr, out, ws, pl, batch, win, (size_t)hp * wp, stream, "shm_image_metrics_hw");
+    return metrics_entry<false>("shm_image_metrics_hw", false, pred, hp, wp, top, left, target, h, w, nullptr, out, ws, ws_bytes, batch, stream);
 }
 
-extern "C" size_t shm_image_metrics_region_hw_workspace(int batch, int h, int w) {
-    if (h < MWIN || w < MWIN || batch < 1) return 0;
-    return plan_metric_ws<true>(batch, h, w).total;
-}
+extern "C" size_t shm_image_metrics_region_hw_workspace(int batch, int h, int w) { return metrics_workspace<true>(batch, h, w); }
 
 extern "C" int shm_image_metrics_region_hw(const float* pred, int hp, int wp, int top, int left, const float* target, int h, int w,
                                            const unsigned char* region, double* out, void* ws, size_t ws_bytes, int batch, void* stream) {
-    SHM_REQUIRE(h >= MWIN && w >= MWIN, SHM_E_SHAPE, "shm_image_metrics_region_hw: window %d x %d has a side < 11 (ssim window)", h, w);
-    SHM_REQUIRE(top >= 0 && left >= 0 && hp >= 1 && wp >= 1 && hp <= 32768 && wp <= 32768 && top <= hp - h && left <= wp - w, SHM_E_SHAPE,
-                "shm_image_metrics_region_hw: window (%d, %d, %d, %d) outside the %d x %d frame", top, left, h, w, hp, wp);
-    SHM_REQUIRE(batch >= 1 && batch <= 65535, SHM_E_SHAPE, "shm_image_metrics_region_hw: bad batch %d", batch);
-    SHM_REQUIRE(pred && target && region && out, SHM_E_SHAPE, "shm_image_metrics_region_hw: null pointer");
-    const MetricWs pl = plan_metric_ws<true>(batch, h, w);
-    SHM_REQUIRE(ws && ws_bytes >= pl.total, SHM_E_WORKSPACE, "shm_image_metrics_region_hw: workspace %zu < %zu bytes", ws_bytes, pl.total);
-    const MetricWin win = {wp, top, left, h, w};
-    return metrics_launch<true>(pred, target, region, out, ws, pl, batch, win, (size_t)hp * wp, stream, "shm_image_metrics_region_hw");
+    return metrics_entry<true>("shm_image_metrics_region_hw", false, pred, hp, wp, top, left, target, h, w, region, out, ws, ws_bytes, batch,
+                               stream);
 }
 
 extern "C" int shm_highlight_region_hw(int mode, const float* src, const float* target, const float* plane, int hp, int wp, int top, int left,

@@ -2,17 +2,17 @@
 // (utils.py:68-123 calculate_estimate_diffuse, whose imwrite is commented out), and the Stokes / DoP / AoLP maps of calcDOP
 // (SHM.py:1157-1169).
 //
-//   shm_polar_views_u8   the four decoded uint8 views of ONE sample -> the sample's five training planes: views 0..3 with the
-//                        arithmetic of resize_bilinear_u8_kernel (data.hip), plane 4 the same interpolation of a per-tap estimate
-//                        e(v0..v3).  The estimate is made at SOURCE resolution (per tap) and then resized, which is what the
-//                        reference's helper followed by its loader computes; min and sqrt do not commute with the interpolation.
+//   shm_polar_views_u8   the four decoded uint8 views of ONE sample -> the sample's five training planes: views 0..3 resized by
+//                        the sampler of bilinear.h, plane 4 the same interpolation of a per-tap estimate e(v0..v3): the per-pixel
+//                        body of augment_px.h without crop, horizontal mirror or view mix.  The estimate is made at SOURCE
+//                        resolution (per tap) and then resized, which is what the reference's helper followed by its loader
+//                        computes; min and sqrt do not commute with the interpolation.
 //                        One thread per output pixel, 48 byte loads (3 channels x 4 views x 4 corners), every tap read once and
 //                        used for both its view and the estimate.  The nine pointers travel by value in the argument struct.
 //   shm_polar_maps       (S0, S1, S2) = C v per element of four float32 views; s0, dop = sqrt(S1^2 + S2^2) / S0 (0 where
 //                        S0 == 0), aolp = 0.5 atan2(S2, S1).  Grid-stride, float4 when everything is 16-byte aligned.
 // Both are launch- and latency-bound elementwise kernels; nothing here is tuned beyond coalesced access.
-#include "common.h"
-#include "polar_est.h"
+#include "augment_px.h"
 
 #include <math.h>
 
@@ -41,38 +41,7 @@ __global__ void __launch_bounds__(PL_NT) polar_views_u8_kernel(const PolarViewAr
                                                                float scale, int flip_ud) {
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;       // (oy, ox)
     if (idx >= (size_t)ho * wo) return;
-    const int ox = (int)(idx % wo), oy = (int)(idx / wo);
-    // ResizeBilinear with half_pixel_centers, as resize_bilinear_u8_kernel (data.hip).  The lower taps are also held below the
-    // last row / column: a no-op for every in = (out + 0.5) * scale - 0.5 < size, kept so that no rounding can index past the image
-    const float fy = ((float)oy + 0.5f) * hs - 0.5f, fx = ((float)ox + 0.5f) * ws - 0.5f;
-    const float fly = floorf(fy), flx = floorf(fx);
-    const int y0 = min(max((int)fly, 0), hin - 1), y1 = min((int)ceilf(fy), hin - 1);
-    const int x0 = min(max((int)flx, 0), win - 1), x1 = min((int)ceilf(fx), win - 1);
-    const float ly = fy - fly, lx = fx - flx;
-    const size_t itl = ((size_t)y0 * win + x0) * 3, itr = ((size_t)y0 * win + x1) * 3;
-    const size_t ibl = ((size_t)y1 * win + x0) * 3, ibr = ((size_t)y1 * win + x1) * 3;
-    const int oyy = flip_ud ? ho - 1 - oy : oy;
-    const size_t o = ((size_t)oyy * wo + ox) * 3;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        float tl[4], tr[4], bl[4], br[4];
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            tl[v] = a.src[v][itl + k];
-            tr[v] = a.src[v][itr + k];
-            bl[v] = a.src[v][ibl + k];
-            br[v] = a.src[v][ibr + k];
-        }
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const float top = tl[v] + (tr[v] - tl[v]) * lx, bot = bl[v] + (br[v] - bl[v]) * lx;
-            a.dst[v][o + k] = (top + (bot - top) * ly) * scale;
-        }
-        const float etl = polar_estimate<MODE>(a.coef, tl[0], tl[1], tl[2], tl[3]), etr = polar_estimate<MODE>(a.coef, tr[0], tr[1], tr[2], tr[3]);
-        const float ebl = polar_estimate<MODE>(a.coef, bl[0], bl[1], bl[2], bl[3]), ebr = polar_estimate<MODE>(a.coef, br[0], br[1], br[2], br[3]);
-        const float top = etl + (etr - etl) * lx, bot = ebl + (ebr - ebl) * lx;
-        a.dst[4][o + k] = (top + (bot - top) * ly) * scale;
-    }
+    augment_pixel<MODE, false>(a, idx, hin, win, ho, wo, hs, ws, 0.f, 0.f, scale, flip_ud, 0);      // augment_px.h: no crop, no mix
 }
 
 __device__ __forceinline__ void polar_map_one(const float* c, float v0, float v1, float v2, float v3, float& s0, float& dop, float& aolp) {

@@ -548,15 +548,13 @@ def dhead_losses(rf, cls, loss, drf_d, dcls_d, drf_g, batch, np_, target, xent_m
 
 
 def image_losses_workspace(batch, s):
-    return int(lib().shm_image_losses_workspace(batch, s))
+    return image_losses_hw_workspace(batch, s, s)
 
 
 def image_losses(gen_rgb, cyc_rgb, cyc_y, cbcr, orig_ptrs, ds_ptrs, flags_mask, style_factor, loss, dgen_y, dcyc_y,
                  ws, batch, s):
-    """orig_ptrs / ds_ptrs: ctypes arrays of 5 device pointers (host memory, read at call time)."""
-    check(lib().shm_image_losses(_p(gen_rgb), _p(cyc_rgb), _p(cyc_y), _p(cbcr), orig_ptrs, ds_ptrs, flags_mask,
-                                 style_factor, _p(loss), _p(dgen_y), _p(dcyc_y), _p(ws),
-                                 ws.numel() * ws.element_size(), batch, s, _stream()), "shm_image_losses")
+    """orig_ptrs / ds_ptrs: ctypes arrays of 5 device pointers (host memory, read at call time).  image_losses_hw with h = w = s."""
+    image_losses_hw(gen_rgb, cyc_rgb, cyc_y, cbcr, orig_ptrs, ds_ptrs, flags_mask, style_factor, loss, dgen_y, dcyc_y, ws, batch, s, s)
 
 
 def image_losses_hw_workspace(batch, h, w):
@@ -565,7 +563,7 @@ def image_losses_hw_workspace(batch, h, w):
 
 def image_losses_hw(gen_rgb, cyc_rgb, cyc_y, cbcr, orig_ptrs, ds_ptrs, flags_mask, style_factor, loss, dgen_y, dcyc_y,
                     ws, batch, h, w):
-    """image_losses on [.,h,w,c] tensors (shm_image_losses_hw; the square call is this one with h = w = s)."""
+    """The image losses on [.,h,w,c] tensors (shm_image_losses_hw)."""
     check(lib().shm_image_losses_hw(_p(gen_rgb), _p(cyc_rgb), _p(cyc_y), _p(cbcr), orig_ptrs, ds_ptrs, flags_mask,
                                     style_factor, _p(loss), _p(dgen_y), _p(dcyc_y), _p(ws),
                                     ws.numel() * ws.element_size(), batch, h, w, _stream()), "shm_image_losses_hw")
@@ -585,16 +583,39 @@ def _default_arena(device):
     return arena
 
 
-def _metrics_out_ws(who, pred, out, arena, workspace, *dims):
-    """The checked (or new) float64 [B,5] result tensor of `who` and its workspace of workspace(B, *dims) bytes from `arena`."""
+def _metrics_check(who, pred, target, window=None, region=None):
+    """The dtype, shape and contiguity rules of `who`, one of the image_metrics family (no window: the square form, two [B,S,S,3]
+    images).  Returns (B, Hp, Wp) of pred."""
+    if pred.dtype != torch.float32 or target.dtype != torch.float32:
+        raise TypeError(f"{who} takes float32 images, got {pred.dtype} / {target.dtype}")
+    if region is not None and region.dtype != torch.uint8:
+        raise TypeError(f"{who} takes a uint8 region, got {region.dtype}")
+    images = [pred, target] + ([] if region is None else [region])
+    got = " / ".join(str(tuple(t.shape)) for t in images)
+    nhwc3 = pred.dim() == 4 and pred.shape[-1] == 3
+    if window is None:
+        if not nhwc3 or pred.shape[1] != pred.shape[2] or tuple(target.shape) != tuple(pred.shape):
+            raise ValueError(f"{who} takes two [B,S,S,3] images of one shape, got {got}")
+    else:
+        h, w = window[2:]
+        want = ["pred [B,Hp,Wp,3]", f"target [B,{h},{w},3]"] + ([] if region is None else [f"region [B,{h},{w}]"])
+        if not nhwc3 or tuple(target.shape) != (pred.shape[0], h, w, 3) or (region is not None and tuple(region.shape) != (pred.shape[0], h, w)):
+            raise ValueError(f"{who} takes {', '.join(want[:-1])} and {want[-1]}, got {got}")
+    if not all(t.is_contiguous() for t in images):
+        raise ValueError(f"{who} takes contiguous NHWC images" + ("" if region is None else " and a contiguous region"))
+    return int(pred.shape[0]), int(pred.shape[1]), int(pred.shape[2])
+
+
+def _metrics_out_ws(who, pred, out, arena, workspace, *dims, cols=5, key="metrics/ws"):
+    """The checked (or new) float64 [B,cols] result tensor of `who` and its workspace of workspace(B, *dims) bytes, `key` of `arena`."""
     B = int(pred.shape[0])
     if out is None:
-        out = torch.empty((B, 5), dtype=torch.float64, device=pred.device)
-    elif out.dtype != torch.float64 or tuple(out.shape) != (B, 5) or not out.is_contiguous():
-        raise ValueError(f"{who}: out must be a contiguous float64 [{B},5] tensor")
+        out = torch.empty((B, cols), dtype=torch.float64, device=pred.device)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (B, cols) or not out.is_contiguous():
+        raise ValueError(f"{who}: out must be a contiguous float64 [{B},{cols}] tensor")
     if arena is None:
         arena = _default_arena(pred.device)
-    return out, arena.get("metrics/ws", (max(workspace(B, *dims), 1),), torch.uint8)
+    return out, arena.get(key, (max(workspace(B, *dims), 1),), torch.uint8)
 
 
 def image_metrics_workspace(batch, s):
@@ -606,13 +627,7 @@ def image_metrics(pred, target, out=None, arena=None):
     tensors (shm_image_metrics, include/shmgan_hip.h, states the definitions).  Returns `out`, a float64 [B,5] device tensor
     (allocated when not given), filled asynchronously on the current stream.  The workspace comes from `arena` (default: one
     arena per device held by this module): calls that share an arena must be ordered on one stream."""
-    if pred.dtype != torch.float32 or target.dtype != torch.float32:
-        raise TypeError(f"image_metrics takes float32 images, got {pred.dtype} / {target.dtype}")
-    if pred.dim() != 4 or pred.shape[-1] != 3 or pred.shape[1] != pred.shape[2] or tuple(target.shape) != tuple(pred.shape):
-        raise ValueError(f"image_metrics takes two [B,S,S,3] images of one shape, got {tuple(pred.shape)} / {tuple(target.shape)}")
-    if not (pred.is_contiguous() and target.is_contiguous()):
-        raise ValueError("image_metrics takes contiguous NHWC images")
-    B, S = int(pred.shape[0]), int(pred.shape[1])
+    B, S, _ = _metrics_check("image_metrics", pred, target)
     out, ws = _metrics_out_ws("image_metrics", pred, out, arena, image_metrics_workspace, S)
     check(lib().shm_image_metrics(_p(pred), _p(target), _p(out), _p(ws), ws.numel(), B, S, _stream()), "shm_image_metrics")
     return out
@@ -626,13 +641,7 @@ def image_metrics_hw(pred, window, target, out=None, arena=None):
     """image_metrics on a window of a padded prediction (shm_image_metrics_hw): pred float32 [B,Hp,Wp,3], window = (top, left, h, w)
     the photo inside the frame, target tight float32 [B,h,w,3].  Same result tensor, workspace rule and ordering as image_metrics."""
     top, left, h, w = (int(v) for v in window)
-    if pred.dtype != torch.float32 or target.dtype != torch.float32:
-        raise TypeError(f"image_metrics_hw takes float32 images, got {pred.dtype} / {target.dtype}")
-    if pred.dim() != 4 or pred.shape[-1] != 3 or tuple(target.shape) != (pred.shape[0], h, w, 3):
-        raise ValueError(f"image_metrics_hw takes pred [B,Hp,Wp,3] and target [B,{h},{w},3], got {tuple(pred.shape)} / {tuple(target.shape)}")
-    if not (pred.is_contiguous() and target.is_contiguous()):
-        raise ValueError("image_metrics_hw takes contiguous NHWC images")
-    B, hp, wp = int(pred.shape[0]), int(pred.shape[1]), int(pred.shape[2])
+    B, hp, wp = _metrics_check("image_metrics_hw", pred, target, (top, left, h, w))
     out, ws = _metrics_out_ws("image_metrics_hw", pred, out, arena, image_metrics_hw_workspace, h, w)
     check(lib().shm_image_metrics_hw(_p(pred), hp, wp, top, left, _p(target), h, w, _p(out), _p(ws), ws.numel(), B, _stream()),
           "shm_image_metrics_hw")
@@ -696,23 +705,9 @@ def image_metrics_region(pred, window, target, region, out=None, arena=None):
     (REGION_METRIC_NAMES: the five metrics inside, the five outside, n_in, p_in; an empty set gives NaN), filled asynchronously on the
     current stream.  Workspace rule and ordering as image_metrics (its own arena buffer: both calls may be queued on one stream)."""
     top, left, h, w = (int(v) for v in window)
-    if pred.dtype != torch.float32 or target.dtype != torch.float32:
-        raise TypeError(f"image_metrics_region takes float32 images, got {pred.dtype} / {target.dtype}")
-    if region.dtype != torch.uint8:
-        raise TypeError(f"image_metrics_region takes a uint8 region, got {region.dtype}")
-    if pred.dim() != 4 or pred.shape[-1] != 3 or tuple(target.shape) != (pred.shape[0], h, w, 3) or tuple(region.shape) != (pred.shape[0], h, w):
-        raise ValueError(f"image_metrics_region takes pred [B,Hp,Wp,3], target [B,{h},{w},3] and region [B,{h},{w}], got {tuple(pred.shape)} / "
-                         f"{tuple(target.shape)} / {tuple(region.shape)}")
-    if not (pred.is_contiguous() and target.is_contiguous() and region.is_contiguous()):
-        raise ValueError("image_metrics_region takes contiguous NHWC images and a contiguous region")
-    B, hp, wp = int(pred.shape[0]), int(pred.shape[1]), int(pred.shape[2])
-    if out is None:
-        out = torch.empty((B, REGION_METRICS), dtype=torch.float64, device=pred.device)
-    elif out.dtype != torch.float64 or tuple(out.shape) != (B, REGION_METRICS) or not out.is_contiguous():
-        raise ValueError(f"image_metrics_region: out must be a contiguous float64 [{B},{REGION_METRICS}] tensor")
-    if arena is None:
-        arena = _default_arena(pred.device)
-    ws = arena.get("metrics/region_ws", (max(image_metrics_region_workspace(B, h, w), 1),), torch.uint8)
+    B, hp, wp = _metrics_check("image_metrics_region", pred, target, (top, left, h, w), region)
+    out, ws = _metrics_out_ws("image_metrics_region", pred, out, arena, image_metrics_region_workspace, h, w, cols=REGION_METRICS,
+                              key="metrics/region_ws")
     check(lib().shm_image_metrics_region_hw(_p(pred), hp, wp, top, left, _p(target), h, w, _p(region), _p(out), _p(ws), ws.numel(), B,
                                             _stream()), "shm_image_metrics_region_hw")
     return out
@@ -1025,14 +1020,19 @@ def adam(w, m, v, g, n, alpha, beta1, beta2, eps, gscale=1.0, clip=0.0):
 
 
 # ---- live attention branch --------------------------------------------------------------------------
+def _mask_pool_pack(name, mask, dst, batch, *dims):
+    check(getattr(lib(), name)(_p(mask), _p(dst), dst.shape[-1], batch, *dims, _dt(dst), _stream()), name)
+
+
 def mask_pool_pack(mask, dst, batch, s, k):
-    """MaxPooling2D(k) of mask [batch,s,s,1] into channel 0 of the activation tensor dst [batch,s/k,s/k,ld]."""
-    check(lib().shm_mask_pool_pack(_p(mask), _p(dst), dst.shape[-1], batch, s, k, _dt(dst), _stream()), "shm_mask_pool_pack")
+    """MaxPooling2D(k) of mask [batch,s,s,1] into channel 0 of the activation tensor dst [batch,s/k,s/k,ld].  Its own entry point,
+    not mask_pool_pack_hw(s, s): that one refuses s == 0 and a negative batch, which this one takes."""
+    _mask_pool_pack("shm_mask_pool_pack", mask, dst, batch, s, k)
 
 
 def mask_pool_pack_hw(mask, dst, batch, h, w, k):
     """mask_pool_pack on a rectangular mask [batch,h,w,1] -> dst [batch,h/k,w/k,ld]."""
-    check(lib().shm_mask_pool_pack_hw(_p(mask), _p(dst), dst.shape[-1], batch, h, w, k, _dt(dst), _stream()), "shm_mask_pool_pack_hw")
+    _mask_pool_pack("shm_mask_pool_pack_hw", mask, dst, batch, h, w, k)
 
 
 def add_bcast(a, b, out, nimg, per, nb, i0=0):

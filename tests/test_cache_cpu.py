@@ -255,11 +255,14 @@ def test_shape_errors_name_the_sample_before_any_launch():
 
 
 def test_the_two_kernels_share_one_definition_of_the_arithmetic():
-    """Both kernel sources include csrc/augment_px.h and neither restates the coordinate, the mix or the lerp."""
+    """Both kernel sources include csrc/augment_px.h and neither restates the coordinate, the mix or the lerp; the coordinate and the
+    lerp themselves are the sampler of csrc/bilinear.h, which augment_px.h includes and does not restate either."""
     from pathlib import Path
     from shmgan_amd import _lib
-    body = (_lib.CSRC / "augment_px.h").read_text()
-    assert "augment_pixel" in body and "* hs - 0.5f) + cy" in body and (_lib.CSRC / "augment_px.h") in _lib.SHARED_HEADERS
+    body, sampler = (_lib.CSRC / "augment_px.h").read_text(), (_lib.CSRC / "bilinear.h").read_text()
+    assert "augment_pixel" in body and '#include "bilinear.h"' in body and "floorf" not in body and "* lx" not in body
+    assert "* hs - 0.5f) + cy" in sampler and "bilinear_lerp" in sampler
+    assert (_lib.CSRC / "augment_px.h") in _lib.SHARED_HEADERS and (_lib.CSRC / "bilinear.h") in _lib.SHARED_HEADERS
     for name in ("augment.hip", "augment_batch.hip"):
         src = (_lib.CSRC / name).read_text()
         assert '#include "augment_px.h"' in src and "augment_pixel<MODE" in src, name

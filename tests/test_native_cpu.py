@@ -43,6 +43,60 @@ def test_entry_points_exist_with_the_stated_types():
     assert L.shm_export_u8_hw(src, desc, 1, None, 0, p, 1 << 20, p, 1 << 20, None) == -1 and b"window" in L.shm_last_error()
 
 
+def test_square_entries_refuse_what_their_windowed_twins_refuse():
+    """Every square entry point answers an argument set with the code its _hw twin gives the full window (0, 0, s, s) of an s x s frame,
+    and names itself in the text.  No case reaches a launch: an argument set that passes every shape check is stopped by a missing
+    workspace (SHM_E_WORKSPACE) or an unknown dtype (SHM_E_DTYPE).  The stated exceptions: shm_image_metrics puts no limit on s where the
+    _hw form holds the frame's sides to 32768; shm_mask_pool_pack takes s == 0 (an empty output, SHM_OK) and does not look at the sign
+    of batch, both of which shm_mask_pool_pack_hw refuses."""
+    L = _lib.lib()
+    p = 256                     # a non-null, aligned pointer nobody dereferences
+    seen = set()
+
+    def twins(sq, hw, a, b, want=None):
+        ra, ea = getattr(L, sq)(*a), L.shm_last_error()
+        rb, eb = getattr(L, hw)(*b), L.shm_last_error()
+        assert (ra, rb) == (want or (ra, ra)) and ra != 0, (sq, a, ra, rb, ea, eb)
+        assert ea.startswith(sq.encode() + b":") and eb.startswith(hw.encode() + b":"), (ea, eb)
+        seen.add(ra)
+
+    # ---- metrics: nulls one at a time, sides around the SSIM window, batch limits, no and short workspace; the workspace queries
+    for s in (0, 10, 11, 32768):
+        for batch in (0, -1, 1, 65535, 65536):
+            for pred, target, out, ws, nb in ((p, p, p, None, 0), (None, p, p, p, 0), (p, None, p, p, 0), (p, p, None, p, 0), (p, p, p, p, 8)):
+                twins("shm_image_metrics", "shm_image_metrics_hw", (pred, target, out, ws, nb, batch, s, None),
+                      (pred, s, s, 0, 0, target, s, s, out, ws, nb, batch, None))
+            assert L.shm_image_metrics_workspace(batch, s) == L.shm_image_metrics_hw_workspace(batch, s, s)
+            assert L.shm_image_losses_workspace(batch, min(s, 64)) == L.shm_image_losses_hw_workspace(batch, min(s, 64), min(s, 64))
+    twins("shm_image_metrics", "shm_image_metrics_hw", (p, p, p, None, 0, 1, 32769, None), (p, 32769, 32769, 0, 0, p, 32769, 32769, p, None, 0, 1, None),
+          want=(-3, -1))
+    # ---- export: one job {s, c, ld, ho, wo, mode, k, off} and its windowed spelling
+    K = _lib.CONSTANTS
+    good = dict(s=16, c=3, ld=4, ho=16, wo=16, mode=K["SHM_EXPORT_CLIP"], k=0, off=0)
+    bad_jobs = [dict(c=c) for c in (0, 2, 4)] + [dict(s=s) for s in (0, 32769)] + [dict(ho=0), dict(wo=32769), dict(ld=2), dict(ld=65537),
+                dict(off=2), dict(off=1 << 40), dict(mode=3), dict(mode=K["SHM_EXPORT_SCALE"]), dict(s=32768), dict(ho=32768, wo=32768)]
+    calls = [dict(), dict(s=10, c=1, ld=1), dict(s=11)] + bad_jobs        # the first three pass every shape check
+    for kw in calls:
+        j = dict(good, **kw)
+        dsq = (Z * 8)(j["s"], j["c"], j["ld"], j["ho"], j["wo"], j["mode"], j["k"], j["off"])
+        dhw = (Z * 13)(j["s"], j["s"], j["c"], j["ld"], 0, 0, j["s"], j["s"], j["ho"], j["wo"], j["mode"], j["k"], j["off"])
+        src = (P * 1)(p)
+        for s_, d_, n, dst, ws, nb in ((src, True, 1, p, None, 0), (src, True, 1, p, p, 8), (src, True, 1, p, p + 2, 1 << 20), (None, True, 1, p, p, 0),
+                                       (src, False, 1, p, p, 0), (src, True, 1, None, p, 0), (src, True, 1, p + 2, p, 0), (src, True, 0, p, p, 0),
+                                       (src, True, K["SHM_EXPORT_MAX_JOBS"] + 1, p, p, 0), ((P * 1)(None), True, 1, p, p, 0)):
+            twins("shm_export_u8", "shm_export_u8_hw", (s_, dsq if d_ else None, n, None, 0, dst, 1 << 20, ws, nb, None),
+                  (s_, dhw if d_ else None, n, None, 0, dst, 1 << 20, ws, nb, None))
+    # ---- mask pool pack: dtype 7 stops what passes the shape check
+    for s in (10, 11, 32, 32769):
+        for k in (0, 1, 2, 3, 32, -1):
+            for ld in (0, 1):
+                for mask, dst, batch in ((p, p, 1), (p, p, 65536), (None, p, 1), (p, None, 1)):
+                    twins("shm_mask_pool_pack", "shm_mask_pool_pack_hw", (mask, dst, ld, batch, s, k, 7, None), (mask, dst, ld, batch, s, s, k, 7, None))
+    twins("shm_mask_pool_pack", "shm_mask_pool_pack_hw", (p, p, 1, -1, 32, 2, 7, None), (p, p, 1, -1, 32, 32, 2, 7, None), want=(-2, -1))
+    assert L.shm_mask_pool_pack(p, p, 1, 1, 0, 2, 7, None) == 0 and L.shm_mask_pool_pack_hw(p, p, 1, 1, 0, 0, 2, 7, None) == -1
+    assert seen == {-1, -2, -3}
+
+
 @pytest.mark.parametrize("h,w", SIZES + [(32, 32), (48, 80)])
 def test_pad_geometry_and_reflect_fill(h, w):
     from shmgan_amd.data import pad_geometry

@@ -838,6 +838,41 @@ int shm_export_u8_hw(const float* const* src, const size_t* desc, int njobs, con
  * mul[b] = (float)(sum / count); acc is updated.  One block, deterministic. */
 int shm_running_scale_mean(const float* scale, int batch, double* acc, float* mul, void* stream);
 
+/* ---- full-resolution test output: guided detail transfer (csrc/detail.hip) -------------------------------
+ * The generator changes one plane, the standardised Y, at model resolution.  The change is fitted locally against the Y it was fed
+ * (the fast guided filter of He & Sun with the correction as the target), the fit's two coefficients are upsampled and applied to
+ * the photo's own Y at the photo's own size.
+ * shm_detail_coeffs.  Per image two planes [h,w]: I = guide (pixel pitch ldg: channel 0 of the standardised YUV has pitch 3),
+ * p = target (pitch ldt), images h*w pixels apart; d = p - I.  box_r(x)[y][x] = the mean of x over the part of the
+ * (2 radius + 1)^2 window around (y, x) that lies inside the plane, divided by that part's own count (no padding):
+ *   var = box(I I) - box(I)^2      cov = box(I d) - box(I) box(d)      a = cov / (var + eps)      b = box(d) - a box(I)
+ *   coef[b][y][x] = (box(a), box(b)), interleaved float32 [batch,h,w,2]
+ * all in fp32.  var and cov are formed from I - c, c a block-uniform reference value near I's local mean (both are shift-invariant;
+ * Y is not mean-free), and c is added back in b; d is not shifted, so that radius 0 gives (0, d) with d = p - I bit for bit: the
+ * plain residual transfer is this call at radius 0.  A window that holds a NaN or an Inf (in I or p) gives NaN a and b, whatever c
+ * is.  A window's sum runs over that window's elements alone in a fixed order (rows, then columns; no running sums), so one NaN
+ * spreads to the (4 radius + 1)^2 coefficients whose fit could see it and no further.  One launch, no atomics: an image's
+ * coefficients do not depend on the batch, and are bitwise the same from run to run.  A plane smaller than the window is legal
+ * (every window is then the whole plane).  SHM_E_SHAPE before any launch, with a message that names the argument: a null pointer,
+ * radius outside [0, 8], eps not a positive finite number, batch outside [1, 65535], h or w outside [1, 32768], a pitch below 1,
+ * coef not 8-byte aligned.
+ * shm_detail_apply_u8.  photo uint8 [h,w,3] (any ratio to the coefficients' H x W, larger or smaller), coef float32 [H,W,2] of
+ * one image, scale = device pointer to that image's standardisation scale (shm_rgb2yuv_std's scale_out[b]; read on the device).
+ * Per photo pixel (oy, ox), in fp32:
+ *   (y, u, v) = rgb_to_yuv(byte * (1/255)) * (1 / scale)                           constants and order of shm_rgb2yuv_std (which
+ *               divides by scale: the two agree to an ulp)
+ *   (a', b')  = the sample of coef at (oy, ox): the taps and the lerp of shm_resize_bilinear_u8 (csrc/bilinear.h) with
+ *               scales H/h and W/w, on each of the two coefficients; (h,w) = (H,W) reads the coefficient itself
+ *   Y' = y + (a' y + b');   out[oy][ox] = yuv_to_rgb(Y', u, v) = (Y' + 1.13988303 v, Y' - 0.394642334 u - 0.58062185 v,
+ *   Y' + 2.03206185 u)                                                             float32 [h,w,3], the units of shm_yuv2rgb
+ * One launch over the flat photo, four pixels per lane, 64-bit element offsets; 3 bytes read and 12 written per pixel.
+ * SHM_E_SHAPE before any launch: a null pointer, a side of the photo or of coef outside [1, 32768], photo not 4-byte, coef not
+ * 8-byte or out not 16-byte aligned.  Neither call allocates. */
+int shm_detail_coeffs(const float* guide, int ldg, const float* target, int ldt, float* coef, int batch, int h, int w, int radius,
+                      float eps, void* stream);
+int shm_detail_apply_u8(const unsigned char* photo, int h, int w, const float* coef, int hm, int wm, const float* scale,
+                        float* out, void* stream);
+
 /* ---- optimizer (SHM.py:169-175, 859-872) ------------------------------------------
  * tf.clip_by_value(g,-1,1) + Keras adam_v2.Adam: m += (g-m)(1-b1); v += (g^2-v)(1-b2);
  * w -= alpha * m / (sqrt(v) + eps); alpha = lr_t*sqrt(1-b2^t)/(1-b1^t) computed by the caller.

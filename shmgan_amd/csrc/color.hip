@@ -1,15 +1,9 @@
 // Colour conversion, per-image standardisation, generator/discriminator input assembly,
 // discriminator-head losses and the clip+Adam update.  All HBM-bound, one pass each.
 #include "common.h"
-#include "yuv.h"                                // rgb2yuv and its constants, yuv_std_scale
+#include "yuv.h"                                // rgb2yuv and its constants, the Y2R_* constants of yuv_to_rgb, yuv_std_scale
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-// tf.image.yuv_to_rgb kernel
-#define Y2R_V_R 1.13988303f
-#define Y2R_U_G -0.394642334f
-#define Y2R_V_G -0.58062185f
-#define Y2R_U_B 2.03206185f
 
 // ---------------------------------------------------------------- rgb -> yuv + standardise
 __global__ __launch_bounds__(256) void yuv_stats_kernel(const float* __restrict__ rgb, double* __restrict__ acc, size_t npix) {

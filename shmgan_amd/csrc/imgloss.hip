@@ -8,11 +8,7 @@
 //   0 L1(gen_rgb, origED)   1..5 L1(cyc_rgb_k, orig_k)   6..10 ssim_k   11..15 -log((1+ssim_k)/2)
 //   (0 where flag k)   16 content   17 style (factor applied)
 #include "common.h"
-
-#define Y2R_V_R 1.13988303f
-#define Y2R_U_G -0.394642334f
-#define Y2R_V_G -0.58062185f
-#define Y2R_U_B 2.03206185f
+#include "yuv.h"                                // the Y2R_* constants of yuv_to_rgb
 
 constexpr int NSUM = 19;    // 6 L1 + content + 6 gram(cycED) + 6 gram(ds4)
 constexpr int WIN = SHM_SSIM_WIN;

@@ -1,5 +1,6 @@
 // tf.image.rgb_to_yuv: the constants and the expression order, in one place for the kernels of color.hip (shm_rgb2yuv_std) and the
-// image / mask pair kernel (augment_pairs.hip), which converts in registers what color.hip reads from memory.
+// image / mask pair kernel (augment_pairs.hip), which converts in registers what color.hip reads from memory.  The constants of
+// tf.image.yuv_to_rgb stand beside them for color.hip (shm_yuv2rgb), imgloss.hip and detail.hip (shm_detail_apply_u8).
 #pragma once
 #include "common.h"
 
@@ -15,6 +16,12 @@
 #define R2Y_20 0.114f
 #define R2Y_21 0.43601035f
 #define R2Y_22 -0.10001026f
+
+// tf.image.yuv_to_rgb kernel
+#define Y2R_V_R 1.13988303f
+#define Y2R_U_G -0.394642334f
+#define Y2R_V_G -0.58062185f
+#define Y2R_U_B 2.03206185f
 
 __device__ __forceinline__ void rgb2yuv(float r, float g, float b, float& y, float& u, float& v) {
     y = r * R2Y_00 + g * R2Y_10 + b * R2Y_20;

@@ -750,9 +750,11 @@ class EvalDataset:
     Same decode and resize as PolarDataset (PIL, then shm_resize_bilinear_u8 scaled by 1/255) but NO flip: test.py:93,118 map
     only x / 255.  `sources(index)` gives each test image's path and (h, w) before the resize (the image export writes at that
     size).  Evaluation is not sharded: rank 0 of a world of 1, whatever torch.distributed says.  The next batch is decoded
-    on a worker thread while the current one is consumed; uploads and resizes run on the consumer's current stream."""
+    on a worker thread while the current one is consumed; uploads and resizes run on the consumer's current stream.
+    keep_source=True leaves the last batch's decoded bytes on the device in `last_source` (the full-resolution output of
+    evaluate.test reads the photos there); what the iterator yields is the same either way."""
 
-    def __init__(self, test_dir, image_size, batch_size=1, diffuse_dir=None, device=None):
+    def __init__(self, test_dir, image_size, batch_size=1, diffuse_dir=None, device=None, keep_source=False):
         if batch_size < 1:
             raise ValueError(f"batch_size {batch_size} < 1")
         self.H, self.W = frame_hw(image_size)                # image_size: a side, or a pair (H, W)
@@ -763,6 +765,9 @@ class EvalDataset:
         self._dev = device
         self._pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="shm-eval-loader")
         self._sizes = {}             # dataset position -> (h, w) of the decoded test image, filled by the decode
+        # keep_source: the decoded bytes of the last batch, as uploaded before the resize, stay reachable: (test, diffuse), each a list
+        # of uint8 device tensors [h,w,3] in batch order (diffuse None without a diffuse_dir).  Off: they are temporaries, nothing is kept
+        self.keep_source, self.last_source = bool(keep_source), None
 
     @property
     def dev(self):
@@ -792,10 +797,13 @@ class EvalDataset:
         diffuse = None if self.diffuse_files is None else [self._decode(p) for p in self.diffuse_files[lo:hi]]
         return test, diffuse
 
-    def _upload(self, decoded):
+    def _upload(self, decoded, kept=None):
         out = torch.empty((len(decoded), self.H, self.W, 3), dtype=torch.float32, device=self.dev)
         for b, a in enumerate(decoded):
-            ops.resize_bilinear_u8(torch.from_numpy(a).to(self.dev), out[b], 1.0 / 255.0, False)
+            src = torch.from_numpy(a).to(self.dev)
+            if kept is not None:
+                kept.append(src)
+            ops.resize_bilinear_u8(src, out[b], 1.0 / 255.0, False)
         return out
 
     def sources(self, index):
@@ -813,7 +821,12 @@ class EvalDataset:
 
     def batch(self, index, decoded=None):
         test, diffuse = decoded if decoded is not None else self._decode_batch(index)
-        return self._upload(test), (None if diffuse is None else self._upload(diffuse))
+        if not self.keep_source:
+            return self._upload(test), (None if diffuse is None else self._upload(diffuse))
+        kept = ([], None if diffuse is None else [])
+        out = self._upload(test, kept[0]), (None if diffuse is None else self._upload(diffuse, kept[1]))
+        self.last_source = kept
+        return out
 
     def __iter__(self):
         nxt = self._pool.submit(self._decode_batch, 0) if len(self) else None

@@ -47,6 +47,21 @@ returned dict gains "region": per-image lists "in_mse" ... "out_de94" (ops.REGIO
 and "fraction" (the part of the photo inside), "means" (per value, over the images whose set is not empty), "n_in_images" and
 "n_out_images"; a second table is printed behind the reference's two, and `<result_dir>/region_metrics.jsonl` gets one line per image:
 {"image": source stem, "fraction", the ten values}, NaN written as null.  Works at both eval sizes; "Time" then includes it.
+
+Full-resolution output (`image_detail`: "off", the default, "residual" or "guided"; needs eval_size="model"): with image_out_size="source"
+the G1 image above is a bilinear blow-up of the model-size plane -- a 1024 x 768 photo comes back as a 4x enlargement of 256 x 256.  The
+generator only changes the standardised Y, so with image_detail on that change is transferred to the photo instead: fitted at model
+resolution against the Y the network was fed (the fast guided filter of He & Sun; `detail_radius` 1..8 model pixels, default 2, and
+`detail_eps`, default 1e-2), the fit's two coefficients upsampled with the library's bilinear sampler and applied to the photo's own Y at
+its own size (trainer.refine; include/shmgan_hip.h, shm_detail_coeffs / shm_detail_apply_u8, states the arithmetic).  "residual" is the
+same at radius 0: the upsampled correction added to the photo's Y.  Chroma and fine detail are the camera's, the highlight correction the
+network's.  The `G1` file is then written from that plane (the photo's size, no resampling; image_values keeps its meaning on it), the
+other tags as before; save_images therefore needs image_out_size="source".  With calc_metrics the tables, lists and pickles above are
+computed as ever at model size, and the refined plane is scored in addition against the diffuse image at ITS own size (a partner of another
+size than its photo raises ValueError naming both files): the returned dict gains "detail": {"mode", "radius", "eps", per-image lists
+"MSE", "PSNR", "SSIM", "delE76", "delE94", "means"}, one more table is printed behind the others, and `<result_dir>/detail_metrics.jsonl`
+gets one line per image: {"image": source stem, "size": [h, w], the five values}, NaN written as null.  The refinement runs outside the
+timing window, like the export: "Time" stays what it is.  Off: nothing of this runs and nothing changes.
 """
 from __future__ import annotations
 
@@ -60,7 +75,7 @@ import torch
 
 from . import ops
 from .data import EvalDataset, NativeEvalDataset, pad_geometry, trainer_frame
-from .model import generator_layers, pad_channels
+from .model import Arena, generator_layers, pad_channels
 from .specseg import WIDTHS as SPECSEG_WIDTHS
 from .telemetry import nan_to_none, region_means, region_options, write_lines
 
@@ -84,6 +99,8 @@ MAX_TENSOR_BYTES = 0xfffffff0
 MAX_FRAME_SIDE = 32768                                        # shm_load_pad_u8, shm_image_metrics_hw, shm_export_u8_hw: sides in [1, 32768]
 REGION_FILE = "region_metrics.jsonl"
 REGION_HEADERS = ["Image#", "Inside"] + [f"{side} {k}" for side in ("in", "out") for k in ("MSE", "PSNR", "SSIM", "delE76", "delE94")]
+DETAIL_FILE = "detail_metrics.jsonl"
+IMAGE_DETAILS = ("off", "residual", "guided")
 MEMORY_HEADROOM = 0.9                                         # fraction of the free device memory a frame's buffers may take
 
 
@@ -142,6 +159,23 @@ def image_options(save, values, out_size):
     if out_size not in IMAGE_OUT_SIZES:
         raise ValueError(f"image_out_size {out_size!r} is not one of {IMAGE_OUT_SIZES}")
     return tags
+
+
+def detail_options(image_detail="off", detail_radius=2, detail_eps=1e-2):
+    """The full-resolution output's options, checked: None for "off" (or None / False), else (mode, radius, eps) with mode "residual"
+    (radius 0 whatever detail_radius says) or "guided" (detail_radius an integer in 1..8), detail_eps a positive finite number.
+    Anything else raises ValueError naming the option."""
+    if image_detail in (None, False, "", "off"):
+        return None
+    if image_detail not in IMAGE_DETAILS:
+        raise ValueError(f"image_detail {image_detail!r} is not one of {IMAGE_DETAILS}")
+    radius = 2 if detail_radius is None else detail_radius
+    if image_detail == "guided" and (isinstance(radius, bool) or not isinstance(radius, int) or not 1 <= radius <= ops.DETAIL_MAX_RADIUS):
+        raise ValueError(f"detail_radius {detail_radius!r} is not an integer in 1..{ops.DETAIL_MAX_RADIUS}")
+    eps = 1e-2 if detail_eps is None else detail_eps
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not (eps > 0 and eps < float("inf")):
+        raise ValueError(f"detail_eps {detail_eps!r} is not a positive finite number")
+    return image_detail, (0 if image_detail == "residual" else int(radius)), float(eps)
 
 
 EVAL_WEIGHTS = ("raw", "ema")
@@ -288,12 +322,14 @@ class ImageExporter:
             return mask[b]
         return cyc[IMAGE_TAGS.index(tag) - 2][b]
 
-    def submit(self, shmgan, gen_rgb, cyc, sources, windows=None):
+    def submit(self, shmgan, gen_rgb, cyc, sources, windows=None, refined=None):
         """Enqueue batch `sources` ((path, (h, w)) per image, in batch order) of the evaluation just issued.  windows (out_size
-        "native"): (top, left, h, w) per image, the photo inside the frame."""
+        "native"): (top, left, h, w) per image, the photo inside the frame.  refined (image_detail; out_size "source"): per image the
+        float32 [h,w,3] plane of trainer.refine, which the G1 tag is then written from -- the whole plane at its own size."""
         B, H, W = (int(v) for v in gen_rgb.shape[:3])
         native = self.out_size == "native"
-        whole = None if native or H == W else (0, 0, H, W)      # a rectangular model frame: the windowed export over the whole plane
+        # a rectangular model frame, or refined planes of the photos' sizes: the windowed export over the whole plane
+        whole = None if native or (H == W and refined is None) else (0, 0, H, W)
         wins = []
         mul = None
         if self.values == "output":
@@ -305,8 +341,12 @@ class ImageExporter:
         for b, (path, hw) in enumerate(sources):
             size = tuple(windows[b][2:]) if native else tuple(hw) if self.out_size == "source" else (H, W)
             for tag in self.tags:
-                wins.append(tuple(windows[b]) if native else whole)
-                p = self._plane(tag, b, gen_rgb, cyc, shmgan.gen_Y, shmgan.specular_candidate)
+                if refined is not None and tag == "G1":
+                    p = refined[b]
+                    wins.append((0, 0, int(p.shape[0]), int(p.shape[1])))
+                else:
+                    wins.append(tuple(windows[b]) if native else whole)
+                    p = self._plane(tag, b, gen_rgb, cyc, shmgan.gen_Y, shmgan.specular_candidate)
                 planes.append(p)
                 sizes.append(size)
                 modes.append("clip" if tag == "mask" else ("scale", b) if mul is not None else "rescale")
@@ -365,7 +405,9 @@ def test(shmgan, args, *, print_fn=print):
     dict: "index" (1-based image numbers), "time" (seconds per image), "images" and "files" (the exported image paths, in
     batch order; empty without save_images); with calc_metrics also the per-image lists "MSE", "SSIM", "PSNR", "delE76",
     "delE94" and "means" (a dict of their means, None without metrics).  args.metrics_region / args.region_threshold (module docstring;
-    default "off") add "region", a further table behind the two and region_metrics.jsonl, and nothing when off."""
+    default "off") add "region", a further table behind the two and region_metrics.jsonl, and nothing when off.  args.image_detail /
+    detail_radius / detail_eps (detail_options; module docstring, "Full-resolution output"; default "off") write G1 from the plane
+    trainer.refine makes at the photo's own size and, with calc_metrics, add "detail", one more table and detail_metrics.jsonl."""
     test_dir = _arg(shmgan, args, "test_dir", "")
     calc = bool(_arg(shmgan, args, "calc_metrics", False))
     diffuse_dir = _arg(shmgan, args, "diffuse_dir", "") if calc else None
@@ -384,6 +426,12 @@ def test(shmgan, args, *, print_fn=print):
         raise ValueError("calc_metrics needs args.diffuse_dir (the ground-truth diffuse images)")
     tags = image_options(_arg(shmgan, args, "save_images", False), _arg(shmgan, args, "image_values", "rescale"),
                          _arg(shmgan, args, "image_out_size", "source"))
+    detail = detail_options(_arg(shmgan, args, "image_detail", "off"), _arg(shmgan, args, "detail_radius", 2), _arg(shmgan, args, "detail_eps", 1e-2))
+    if detail is not None and native:
+        raise ValueError(f"image_detail={detail[0]!r} transfers the model-size result to the photo: it needs eval_size='model' (at "
+                         f"eval_size='native' the network already ran at the photo's size and there is nothing to transfer)")
+    if detail is not None and tags and _arg(shmgan, args, "image_out_size", "source") != "source":
+        raise ValueError(f"image_detail={detail[0]!r} writes G1 at the photo's size: save_images needs image_out_size='source'")
     region = region_options(_arg(shmgan, args, "metrics_region", "off"), _arg(shmgan, args, "region_threshold", None), "metrics_region")
     if region is not None and not calc:
         raise ValueError(f"metrics_region={region[0]!r} splits the image metrics: it needs calc_metrics (and diffuse_dir)")
@@ -404,7 +452,7 @@ def test(shmgan, args, *, print_fn=print):
     if native:
         dataset = NativeEvalDataset(test_dir, diffuse_dir, shmgan.device, check=check)
     else:
-        dataset = EvalDataset(test_dir, trainer_frame(shmgan), B, diffuse_dir, shmgan.device)
+        dataset = EvalDataset(test_dir, trainer_frame(shmgan), B, diffuse_dir, shmgan.device, keep_source=detail is not None)
     if tags:
         check_stems(dataset.test_files)
     shmgan.number_of_test_images = dataset.n                                   # test.py:123
@@ -421,6 +469,9 @@ def test(shmgan, args, *, print_fn=print):
     index, times, rows = [], [], []
     cols = {k: [] for k in METRIC_KEYS}
     region_rows, region_size, stems = [], [], []      # per image: the 12 region values, (pixels, SSIM positions) of its window, source stem
+    detail_rows = []                                  # per image: (source stem, (h, w), the five values of the refined plane)
+    refine_on = detail is not None and (bool(tags) or calc)
+    detail_arena = Arena(shmgan.device) if refine_on and calc else None      # the metrics' workspace at the photos' sizes
     stream = torch.cuda.current_stream()
     eval_region_before = shmgan.eval_region
     try:
@@ -441,8 +492,13 @@ def test(shmgan, args, *, print_fn=print):
                 stream.synchronize()
                 n = rgb.shape[0]
                 dt = (time.perf_counter() - t0) / n
+                refined = None
+                if refine_on:                                # after the timing window, like the export
+                    refined = shmgan.refine(dataset.last_source[0], detail[0], detail[1] or 2, detail[2])
+                    if calc:
+                        detail_rows.extend(_score_refined(refined, dataset, bi, detail_arena))
                 if exporter is not None:                     # after the timing window: the export is not part of "Time"
-                    exporter.submit(shmgan, gen_rgb, cyc, dataset.sources(bi), [window] if native else None)
+                    exporter.submit(shmgan, gen_rgb, cyc, dataset.sources(bi), [window] if native else None, refined)
                 lo, _ = dataset.batch_range(bi)
                 for b in range(n):
                     index.append(lo + b + 1)
@@ -460,6 +516,8 @@ def test(shmgan, args, *, print_fn=print):
 
     out = {"images": dataset.n, "index": index, "time": times, "means": None, "files": files}
     if not calc:
+        if detail is not None:                      # what was applied; nothing was scored: empty lists, NaN means, no table, no file
+            out["detail"] = _report_detail(shmgan, detail, index, [], print_fn)
         return out
     out.update(cols)
     means = {k: (sum(v) / len(v) if v else float("nan")) for k, v in cols.items()}
@@ -475,7 +533,51 @@ def test(shmgan, args, *, print_fn=print):
             pickle.dump(cols[key], f)
     if region is not None:
         out["region"] = _report_regions(shmgan, index, stems, region_rows, region_size, print_fn)
+    if detail is not None:
+        out["detail"] = _report_detail(shmgan, detail, index, detail_rows, print_fn)
     return out
+
+
+def _score_refined(refined, dataset, bi, arena):
+    """The five image metrics of each refined plane of batch `bi` against its diffuse partner at the photo's own size: the partner's bytes
+    (dataset.last_source) go to float32 on the device (ops.load_pad_u8 without a pad) and ops.image_metrics_hw scores the whole plane.
+    Returns (source stem, (h, w), [mse, psnr, ssim, de76, de94]) per image; synchronises (the values come to the host), after which the
+    workspace of this image's size leaves `arena`: sizes differ per image."""
+    lo, _ = dataset.batch_range(bi)
+    rows = []
+    for b, (plane, src) in enumerate(zip(refined, dataset.last_source[1])):
+        h, w = (int(v) for v in plane.shape[:2])
+        if tuple(src.shape[:2]) != (h, w):
+            raise ValueError(f"image_detail scores the refined image against its diffuse partner pixel by pixel: {dataset.test_files[lo + b]} is "
+                             f"{h} x {w}, {dataset.diffuse_files[lo + b]} is {int(src.shape[0])} x {int(src.shape[1])}")
+        target = torch.empty((1, h, w, 3), dtype=torch.float32, device=plane.device)
+        ops.load_pad_u8(src, target[0], 0, 0, 1.0 / 255.0)
+        m = ops.image_metrics_hw(plane.unsqueeze(0), (0, 0, h, w), target, arena=arena)
+        rows.append((source_stem(dataset.test_files[lo + b]), (h, w), [float(v) for v in m.cpu()[0].tolist()]))
+        arena.drop("metrics/ws")
+    return rows
+
+
+def _report_detail(shmgan, detail, index, rows, print_fn):
+    """The "detail" entry of test()'s result from the per-image rows of _score_refined (none without calc_metrics: the lists are then
+    empty and the means NaN); prints its table and writes <result_dir>/detail_metrics.jsonl (module docstring)."""
+    mode, radius, eps = detail
+    res = {"mode": mode, "radius": radius, "eps": eps}
+    res.update({k: [r[2][j] for r in rows] for j, k in enumerate(METRIC_KEYS)})
+    res["means"] = {k: (sum(res[k]) / len(res[k]) if res[k] else float("nan")) for k in METRIC_KEYS}
+    if not rows:
+        return res
+    order = [METRIC_KEYS.index(k) for k in ("MSE", "SSIM", "PSNR", "delE76", "delE94")]           # the columns of TABLE_HEADERS
+    print_fn(f" --- PRINTING METRICS AT THE PHOTOS' OWN SIZE (image_detail={mode!r}, radius {radius}, eps {eps:g}) --- ")
+    print_fn(format_table([[i, f"{h}x{w}"] + [v[j] for j in order] for i, (_, (h, w), v) in zip(index, rows)] +
+                          [["mean", ""] + [res["means"][METRIC_KEYS[j]] for j in order]], ["Image#", "Size"] + TABLE_HEADERS[2:]))
+    print_fn("\n\n")
+    os.makedirs(shmgan.result_dir, exist_ok=True)
+    path = os.path.join(shmgan.result_dir, DETAIL_FILE)
+    if os.path.exists(path):
+        os.remove(path)                             # one file per run (write_lines appends)
+    write_lines(path, [dict({"image": stem, "size": [h, w]}, **{k: nan_to_none(v[j]) for j, k in enumerate(METRIC_KEYS)}) for stem, (h, w), v in rows])
+    return res
 
 
 def _report_regions(shmgan, index, stems, rows, sizes, print_fn):

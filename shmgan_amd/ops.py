@@ -1063,6 +1063,75 @@ def load_pad_u8(src_u8, dst, top, left, scale=1.0 / 255.0):
     check(lib().shm_load_pad_u8(_p(src_u8), h, w, c, _p(dst), hp, wp, int(top), int(left), scale, _stream()), "shm_load_pad_u8")
 
 
+# ---- full-resolution test output: guided detail transfer (shm_detail_coeffs / shm_detail_apply_u8) ---------------------------------
+DETAIL_MAX_RADIUS = 8
+
+
+def _detail_plane(t, who, what):
+    """`who`'s check of one of its two model-resolution planes: float32 [B,H,W] (or [B,H,W,1]) on the device, rows and images dense
+    behind a pixel pitch ld >= 1 (channel 0 of an NHWC tensor is fine).  Returns (the [B,H,W] view, ld)."""
+    if t.dtype != torch.float32 or not t.is_cuda:
+        raise TypeError(f"{who} takes float32 device planes, got {what} {t.dtype} on {t.device}")
+    if t.dim() == 4 and t.shape[3] == 1:
+        t = t[..., 0]
+    if t.dim() != 3 or min(t.shape) < 1:
+        raise ValueError(f"{who} takes {what} as [B,H,W] or [B,H,W,1], got {tuple(t.shape)}")
+    B, H, W = (int(v) for v in t.shape)
+    ld = int(t.stride(2)) if W > 1 else int(t.stride(1)) if H > 1 else int(t.stride(0)) if B > 1 else 1
+    if ld < 1 or (W > 1 and t.stride(2) != ld) or (H > 1 and t.stride(1) != W * ld) or (B > 1 and t.stride(0) != H * W * ld):
+        raise ValueError(f"{who}: {what} strides {t.stride()} are not [H*W*ld, W*ld, ld] with ld >= 1")
+    return t, ld
+
+
+def detail_coeffs(guide, target, radius, eps, out=None, arena=None):
+    """The guided filter's coefficients at model resolution (shm_detail_coeffs, include/shmgan_hip.h, states the arithmetic): guide I
+    (the standardised Y the generator was fed) and target p (gen_Y), float32 device planes [B,H,W] or [B,H,W,1] of one shape, each with a
+    pixel pitch of its own; radius in 0..DETAIL_MAX_RADIUS (0: the plain residual, coef = (0, p - I)), eps > 0.  Returns `out`, a
+    contiguous float32 [B,H,W,2] device tensor -- the arena's "detail/coef" when an arena is given, a new tensor otherwise -- filled
+    asynchronously on the current stream."""
+    g, ldg = _detail_plane(guide, "detail_coeffs", "guide")
+    t, ldt = _detail_plane(target, "detail_coeffs", "target")
+    if g.shape != t.shape or g.device != t.device:
+        raise ValueError(f"detail_coeffs: guide {tuple(g.shape)} on {g.device} and target {tuple(t.shape)} on {t.device} differ")
+    radius = int(radius)
+    if not 0 <= radius <= DETAIL_MAX_RADIUS:
+        raise ValueError(f"detail_coeffs: radius {radius} outside [0, {DETAIL_MAX_RADIUS}]")
+    if not (eps > 0 and math.isfinite(eps)):
+        raise ValueError(f"detail_coeffs: eps {eps!r} is not a positive finite number")
+    B, H, W = (int(v) for v in g.shape)
+    if out is None:
+        out = arena.get("detail/coef", (B, H, W, 2)) if arena is not None else torch.empty((B, H, W, 2), dtype=torch.float32, device=g.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, H, W, 2) or not out.is_contiguous() or out.device != g.device:
+        raise ValueError(f"detail_coeffs: out must be a contiguous float32 [{B},{H},{W},2] tensor on {g.device}")
+    check(lib().shm_detail_coeffs(_p(g), ldg, _p(t), ldt, _p(out), B, H, W, radius, float(eps), _stream()), "shm_detail_coeffs")
+    return out
+
+
+def detail_apply_u8(photo_u8, coef, scale, out=None):
+    """The coefficients of ONE image applied to its photo (shm_detail_apply_u8): photo_u8 contiguous uint8 [h,w,3] on the device, any
+    size; coef contiguous float32 [H,W,2] (one image of detail_coeffs' result); scale a float32 device tensor of one element, that image's
+    standardisation scale (a slice of preprocess's scale: no host copy is made).  Returns `out`, contiguous float32 [h,w,3] (allocated
+    when not given): the full-resolution counterpart of gen_rgb, in its units, filled asynchronously on the current stream."""
+    if photo_u8.dtype != torch.uint8 or not photo_u8.is_cuda or photo_u8.dim() != 3 or photo_u8.shape[2] != 3 or not photo_u8.is_contiguous() \
+            or min(photo_u8.shape) < 1:
+        raise ValueError(f"detail_apply_u8 takes a contiguous uint8 [h,w,3] device photo, got {photo_u8.dtype} {tuple(photo_u8.shape)} on "
+                         f"{photo_u8.device}")
+    dev = photo_u8.device
+    if coef.dtype != torch.float32 or coef.device != dev or coef.dim() != 3 or coef.shape[2] != 2 or not coef.is_contiguous() or min(coef.shape) < 1:
+        raise ValueError(f"detail_apply_u8 takes contiguous float32 [H,W,2] coefficients on {dev}, got {coef.dtype} {tuple(coef.shape)} on {coef.device}")
+    if scale.dtype != torch.float32 or scale.device != dev or scale.numel() != 1:
+        raise ValueError(f"detail_apply_u8 takes the image's scale as a float32 tensor of one element on {dev}, got {scale.dtype} "
+                         f"{tuple(scale.shape)} on {scale.device}")
+    h, w = int(photo_u8.shape[0]), int(photo_u8.shape[1])
+    if out is None:
+        out = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (h, w, 3) or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"detail_apply_u8: out must be a contiguous float32 [{h},{w},3] tensor on {dev}")
+    check(lib().shm_detail_apply_u8(_p(photo_u8), h, w, _p(coef), int(coef.shape[0]), int(coef.shape[1]), _p(scale), _p(out), _stream()),
+          "shm_detail_apply_u8")
+    return out
+
+
 # ---- polarimetry: estimated-diffuse target and Stokes maps ----------------------------------------
 POLAR_MODES = {"min": CONSTANTS["SHM_POLAR_MIN"], "stokes": CONSTANTS["SHM_POLAR_STOKES"]}
 

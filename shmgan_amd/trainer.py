@@ -68,7 +68,7 @@ _DEFAULTS = dict(image_size=128, image_hw=None, batch_size=1, filter_size=64, g_
                  ema_decay=0.0, ema_warmup=True,
                  val_dir="", val_fraction=0.0, val_seed=0, val_step=1, val_batch_size=None, val_monitor="psnr",
                  val_region="off", val_region_threshold=None, metrics_region="off", region_threshold=None,
-                 eval_weights="raw", eval_checkpoint="latest")
+                 eval_weights="raw", eval_checkpoint="latest", image_detail="off", detail_radius=2, detail_eps=1e-2)
 
 SPECSEG_MASK_SOURCES = ("dir", "polar")                   # where train_specseg's masks come from
 
@@ -159,6 +159,7 @@ class ShmGANwithSSpecSeg:
         self._val_step, self._val_monitor, self.length_dataset, self.batch_step, self.random_flip = None, None, 0, 0, 0.0
         # the last train_step's loss vectors and inputs (losses()), the frame (H, W) of the last infer(), _stats_now's Telemetry without files
         self._last = self._inf_frame = self._adhoc_telemetry = None
+        self._inf_planes = None          # the last infer()'s (standardised yuv, gen_Y, scale): what refine() fits its coefficients on
         # evaluate_frame's split of the metrics by the highlight (off by default): None, ("residual", tau) = photo - diffuse above tau, or
         # ("specseg", tau) = the inference's SpecSeg mask above tau; with it on and a diffuse target given, evaluate_frame leaves the region
         # (uint8 [B,h,w]) and the split metrics (float64 [B,12], ops.REGION_METRIC_NAMES) of its last call here
@@ -946,7 +947,7 @@ class ShmGANwithSSpecSeg:
             torch.cuda.synchronize(self.device)
             for br in self.G.attn:                 # the branches' records hold the old frame's maps
                 br.ctx = None
-            self.gen_input = self.gen_Y = self.gen_rgb = self.specular_candidate = self._inf_photo = None
+            self.gen_input = self.gen_Y = self.gen_rgb = self.specular_candidate = self._inf_photo = self._inf_planes = None
             self.highlight_region = self.region_metrics = None
             self.cyc_gen0_rgb = self.cyc_gen45_rgb = self.cyc_gen90_rgb = self.cyc_gen135_rgb = self.cyc_genED_rgb = None
             self.G.ctx.pop("inf1", None)
@@ -1008,6 +1009,7 @@ class ShmGANwithSSpecSeg:
             outs = [cyc_rgb[k * B:(k + 1) * B] for k in range(5)]
         self.gen_input, self.gen_Y, self.gen_rgb = gen_in, gen_Y, gen_rgb
         self._inf_photo = x if self.eval_region is not None else None      # the frame as fed (eval_region "residual" reads it)
+        self._inf_planes = (yuv, gen_Y, scale)
         self.stddev_arr = [scale]
         (self.cyc_gen0_rgb, self.cyc_gen45_rgb, self.cyc_gen90_rgb, self.cyc_gen135_rgb, self.cyc_genED_rgb) = outs
         return gen_rgb, outs
@@ -1046,6 +1048,32 @@ class ShmGANwithSSpecSeg:
             if self.eval_region is not None:
                 self._region_metrics(self.eval_region, self._inf_photo, gen_rgb, t, win)
         return gen_rgb, cyc, metrics
+
+    DETAIL_MODES = ("residual", "guided")
+
+    def refine(self, photos_u8, mode="guided", radius=2, eps=1e-2):
+        """Full-resolution output after an infer() or evaluate() of the same batch: the generator only changes the standardised Y, so
+        that change is fitted at model resolution against the Y it was fed (ops.detail_coeffs: the guided filter's two coefficients,
+        one call for the batch, into the arena's "inf/detail_coef") and applied to each photo's own Y at its own size
+        (ops.detail_apply_u8, one call per image; include/shmgan_hip.h states the arithmetic).  photos_u8: B uint8 device tensors
+        [h_b,w_b,3], the decoded photos of the batch in its order (sizes may differ; evaluate.test takes them from
+        EvalDataset(keep_source=True)).  mode "guided" fits windows of `radius` model pixels (1..8) with the regulariser `eps`;
+        "residual" is radius 0, the bilinearly upsampled correction.  Returns B float32 [h_b,w_b,3] tensors in gen_rgb's units, new
+        allocations the caller owns; asynchronous like infer.  ValueError without a preceding infer or for another batch size."""
+        if mode not in self.DETAIL_MODES:
+            raise ValueError(f"refine: mode {mode!r} is not one of {self.DETAIL_MODES}")
+        if self._inf_planes is None:
+            raise ValueError("refine follows an infer() or evaluate() of the same batch: none has run (or its frame was dropped)")
+        yuv, gen_Y, scale = self._inf_planes
+        B, H, W = (int(v) for v in gen_Y.shape[:3])
+        photos = list(photos_u8)
+        if len(photos) != B:
+            raise ValueError(f"refine: {len(photos)} photos for the batch of {B} the last infer() ran")
+        r = 0 if mode == "residual" else int(radius)
+        if mode == "guided" and not 1 <= r <= ops.DETAIL_MAX_RADIUS:
+            raise ValueError(f"refine: radius {radius} outside [1, {ops.DETAIL_MAX_RADIUS}] (mode 'residual' is radius 0)")
+        coef = ops.detail_coeffs(yuv[..., 0], gen_Y, r, eps, out=self.arena.get("inf/detail_coef", (B, H, W, 2)))
+        return [ops.detail_apply_u8(p, coef[b], scale[b:b + 1]) for b, p in enumerate(photos)]
 
     EVAL_REGIONS = ("residual", "specseg")
 

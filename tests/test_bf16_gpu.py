@@ -11,6 +11,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import elem_bound_ref as eb
 from oracle import step_torch as st
 from util import check_grad_fixture, conv_ref, cosine, grad_cosines, host, nchw, nhwc, pad_c, pin_kinks, pin_to_model, rel_l2, t64
 
@@ -34,6 +35,10 @@ def bf(a):
 def rb(a):
     """numpy array rounded through bf16, as float64 (what the device operand holds)."""
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(BF).double().numpy()
+
+
+def _kern():
+    return _ops().last_kernel().split("<")[0]
 
 
 def _wk(w_hwio, cin_pad):
@@ -69,7 +74,9 @@ def test_conv2d_fwd_bf16(n, h, cin, cout, k, s):
     scr = torch.zeros(ops.STATS_SLOTS * n * cout * 2, dtype=torch.float64, device="cuda") if (n + h) % 2 == 0 else None
     ops.conv2d_in_fwd(bf(x), None, 0, cin, 0, _wk(w, cin), torch.from_numpy(b.astype(np.float32)).cuda(), y, cout, n, h, h, cin,
                       cout, k, s, 0.2, stats, 1e-6, scratch=scr)
+    kern = _kern()
     assert rel_l2(host(y.float()), ref) < TOL
+    eb.hold_fwd(host(y.float()), rb(x), rb(w), b, s, ref, "bf16", "fwd default " + kern)
     # the fused InstanceNorm statistics describe the tensor as stored
     yy = host(y.float()).reshape(n, -1, cout)
     st_ = host(stats).reshape(n, cout, 2)
@@ -87,6 +94,7 @@ def test_conv2d_fwd_bf16_padded_cin_and_concat():
     y = torch.empty((n, h, h, cout), device="cuda", dtype=BF)
     ops.conv2d_fwd(bf(pad_c(x, 32)), None, 0, 32, 0, _wk(w, 32), None, y, cout, n, h, h, 32, cout, 3, 1, 1.0)
     assert rel_l2(host(y.float()), ref) < TOL
+    eb.hold_fwd(host(y.float()), rb(x), rb(w), None, 1, ref, "bf16", "fwd default " + _kern())
     c1, c2, cout = 64, 32, 128                      # concat [up, skip], halo kernel
     xa, xb = rng.standard_normal((n, h, h, c1)), rng.standard_normal((n, h, h, c2))
     w = rng.standard_normal((3, 3, c1 + c2, cout)) * 0.1
@@ -94,6 +102,7 @@ def test_conv2d_fwd_bf16_padded_cin_and_concat():
     y = torch.empty((n, h, h, cout), device="cuda", dtype=BF)
     ops.conv2d_fwd(bf(xa), bf(xb), c1, c1, c2, _wk(w, c1 + c2), None, y, cout, n, h, h, c1 + c2, cout, 3, 1, 1.0)
     assert rel_l2(host(y.float()), ref) < TOL
+    eb.hold_fwd(host(y.float()), np.concatenate([rb(xa), rb(xb)], -1), rb(w), None, 1, ref, "bf16", "fwd default " + _kern())
 
 
 @pytest.mark.parametrize("n,h,cin,cout,k,s", [
@@ -113,10 +122,13 @@ def test_conv2d_dgrad_bf16(n, h, cin, cout, k, s):
     dx = torch.full((n, h, h, ld), 7.0, device="cuda", dtype=BF)
     ops.conv2d_dgrad(bf(dy), cout, bf(w), dx, None, cin, ld, 0, n, h, h, cin, cout, k, s)
     assert rel_l2(host(dx.float())[..., :cin], ref) < TOL
+    tol = eb.dgrad_tol(rb(dy), rb(w), s, ref, "bf16")
+    eb.note("dgrad default " + _kern(), "bf16", eb.within(host(dx.float())[..., :cin], ref, tol, eb.CONV, "dgrad"))
     # SHM_BF16_GF32: same bf16 operands, the gradient signal leaves in fp32
     dx32 = torch.full((n, h, h, ld), 7.0, device="cuda")
     ops.conv2d_dgrad(bf(dy), cout, bf(w), dx32, None, cin, ld, 0, n, h, h, cin, cout, k, s)
     assert rel_l2(host(dx32)[..., :cin], ref) < TOL32
+    eb.hold_dgrad(host(dx32)[..., :cin], rb(dy), rb(w), s, ref, "f32", "dgrad gf32 default " + _kern())
 
 
 @pytest.mark.parametrize("n,h,cin,cout", [(2, 8, 64, 64), (1, 16, 128, 64), (3, 4, 32, 32), (1, 2, 512, 512)])
@@ -131,6 +143,7 @@ def test_conv2d_transpose_fwd_bf16(n, h, cin, cout):
     y = torch.empty((n, 2 * h, 2 * h, cout), device="cuda", dtype=BF)
     ops.conv2d_transpose_fwd(bf(x), cin, bf(w), torch.from_numpy(b.astype(np.float32)).cuda(), y, cout, n, h, h, cin, cout, 0.2)
     assert rel_l2(host(y.float()), ref) < TOL
+    eb.hold_transpose(host(y.float()), rb(x), rb(w), b, ref, "bf16", "transpose default " + _kern())
 
 
 @pytest.mark.parametrize("n,h,cin,cout,k,s", [
@@ -151,8 +164,11 @@ def test_conv2d_wgrad_bf16(n, h, cin, cout, k, s):
     ws = _ws(ops.conv2d_wgrad_workspace(n, ho, ho, cin, cout, k))
     ops.conv2d_wgrad(bf(pad_c(x, ld)), None, 0, ld, 0, bf(dy), cout, dw, n, h, h, cin, ld, cout, k, s, 0, ws)
     assert rel_l2(host(dw), ref.numpy()) < TOL32
+    first = host(dw)
+    eb.hold_wgrad(first, rb(x), rb(dy), s, ref.numpy(), "wgrad default " + _kern(), "bf16", k)
     ops.conv2d_wgrad(bf(pad_c(x, ld)), None, 0, ld, 0, bf(dy), cout, dw, n, h, h, cin, ld, cout, k, s, 1, ws)
     assert rel_l2(host(dw), 2 * ref.numpy()) < TOL32
+    eb.hold_wgrad(host(dw), rb(x), rb(dy), s, ref.numpy(), "wgrad default accumulate " + _kern(), "bf16", k, before=first)
 
 
 def test_conv2d_wgrad_bf16_concat_and_transpose_roles():
@@ -168,6 +184,7 @@ def test_conv2d_wgrad_bf16_concat_and_transpose_roles():
         ws = _ws(ops.conv2d_wgrad_workspace(n, h, h, c1 + c2, cout, 3))
         ops.conv2d_wgrad(bf(xa), bf(xb), c1, c1, c2, bf(dy), cout, dw, n, h, h, c1 + c2, c1 + c2, cout, 3, 1, 0, ws)
         assert rel_l2(host(dw), ref.numpy()) < TOL32, (c1, c2)
+        eb.hold_wgrad(host(dw), np.concatenate([rb(xa), rb(xb)], -1), rb(dy), 1, ref.numpy(), "wgrad default " + _kern(), "bf16")
     cin_t, cout_t, hs = 32, 64, 4                  # Conv2DTranspose weight gradient (roles swapped, stride 2)
     xin = rng.standard_normal((n, hs, hs, cin_t))
     dz = rng.standard_normal((n, 2 * hs, 2 * hs, cout_t))
@@ -177,6 +194,7 @@ def test_conv2d_wgrad_bf16_concat_and_transpose_roles():
     ws = _ws(ops.conv2d_wgrad_workspace(n, hs, hs, cout_t, cin_t, 3))
     ops.conv2d_wgrad(bf(dz), None, 0, cout_t, 0, bf(xin), cin_t, dw, n, 2 * hs, 2 * hs, cout_t, cout_t, cin_t, 3, 2, 0, ws)
     assert rel_l2(host(dw), ref.numpy()) < TOL32
+    eb.hold_wgrad(host(dw), rb(dz), rb(xin), 2, ref.numpy(), "wgrad default " + _kern(), "bf16")
 
 
 @pytest.mark.parametrize("n,h,c", [(2, 16, 64), (1, 32, 128), (5, 2, 1024), (2, 4, 48)])
@@ -198,19 +216,26 @@ def test_instance_norm_fwd_bwd_bf16(n, h, c):
     ops.in_stats(ad, c, stats, n, h * h, c, 1e-6)
     ops.in_apply(ad, c, stats, torch.from_numpy(beta.astype(np.float32)).cuda(), out, c, n, h * h, c)
     assert rel_l2(host(out.float()), nhwc(yt.detach())) < TOL
+    where, beta32 = {"kind": "in"}, eb.f32(beta)
+    eb.note("in_apply", "bf16", eb.within(host(out.float()), *eb.in_apply_ref_tol(a, host(stats), beta32, "bf16"), where, "in_apply"))
     red = torch.zeros(n * c * 3, dtype=torch.float64, device="cuda")
     dz = torch.empty((n, h, h, c), device="cuda", dtype=BF)
     db = torch.zeros(c, dtype=torch.float64, device="cuda")
     ops.in_bwd(bf(g1), c, bf(g2), c, ad, c, stats, red, dz, c, db, n, h, h, c, 0.2)
     assert rel_l2(host(dz.float()), ref_dz) < TOL
     assert rel_l2(host(db), ref_dz.sum(axis=(0, 1, 2))) < 1e-3
+    zr, ztol = eb.in_bwd_ref_tol(a, host(stats), g1, g2, slope=0.2, dt="bf16")
+    eb.note("in_bwd " + _kern(), "bf16", eb.within(host(dz.float()), zr, ztol, where, "in_bwd (pooled)"))
+    eb.within(host(db), zr.sum((0, 1, 2)), eb.in_sum_tol(zr, ztol, (0, 1, 2)), None, "in_bwd bias gradient")
     f32 = lambda a_: torch.from_numpy(np.ascontiguousarray(a_, dtype=np.float32)).cuda()
     dz2 = torch.empty((n, h, h, c), device="cuda", dtype=BF)          # fp32 gradient signal in (SHM_BF16_GF32)
     ops.in_bwd(f32(g1), c, f32(g2), c, ad, c, stats, red, dz2, c, None, n, h, h, c, 0.2)
     assert rel_l2(host(dz2.float()), ref_dz) < TOL
+    eb.note("in_bwd gf32 " + _kern(), "bf16", eb.within(host(dz2.float()), zr, ztol, where, "in_bwd (pooled, fp32 gradients)"))
     pl = torch.empty((n, h // 2, h // 2, c), device="cuda", dtype=BF)
     ops.avgpool2_fwd(out, c, pl, c, n, h, h, c)
     assert rel_l2(host(pl.float()), nhwc(F.avg_pool2d(nchw(host(out.float())), 2))) < TOL
+    eb.note("avgpool2_fwd", "bf16", eb.within(host(pl.float()), *eb.in_pool_ref_tol(host(out.float()), "bf16"), where, "avgpool2_fwd"))
 
 
 def test_small_layers_bf16():

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 import torch
 
+import elem_bound_ref as eb
 import gf32_ref as R
 from oracle import step_torch as st
 from test_gsum_gpu import _sums
@@ -96,6 +97,7 @@ def test_dgrad_s1_forced_variant_gf32(case):
     e1, e2 = rel_l2(host(d1), ref[..., :c1]), rel_l2(host(d2), ref[..., c1:])
     print(f"{kern}: rel-L2 {e1:.2e} {e2:.2e}")
     assert e1 < TOL32 and e2 < TOL32, (kern, e1, e2)
+    eb.hold_dgrad([host(d1), host(d2)], _rnd(dy, "bf16"), _rnd(wt, "bf16"), 1, ref, "f32", "dgrad gf32 " + kern.split("<")[0])          # fp32 stores: u_out = u32
 
 
 # =====================================================================================================================
@@ -133,6 +135,7 @@ def test_dgrad_s2_forced_variant_gf32(case):
     assert band_untouched(band) and _written(dx), kern
     print(f"{kern}: rel-L2 {rel_l2(host(dx), ref):.2e}")
     assert rel_l2(host(dx), ref) < TOL32, (kern, rel_l2(host(dx), ref))
+    eb.hold_dgrad(host(dx), _rnd(dy, "bf16"), _rnd(wt, "bf16"), 2, ref, "f32", "dgrad gf32 s2 " + kern.split("<")[0])
 
 
 # =====================================================================================================================
@@ -155,6 +158,7 @@ def test_fwd_s2_fp32_output(case):
     assert band_untouched(band) and _written(y), kern
     print(f"{kern}: rel-L2 {rel_l2(host(y), ref):.2e}")
     assert rel_l2(host(y), ref) < TOL32, (kern, rel_l2(host(y), ref))
+    eb.hold_fwd(host(y), _rnd(x, "bf16"), _rnd(wt, "bf16"), None, 2, ref, "f32", "fwd gf32 s2 " + kern.split("<")[0])
 
 
 def test_in_fwd_refuses_the_mode():
@@ -207,6 +211,9 @@ def test_in_bwd_apply_gf32(pooled, h, w):
     r64 = _in_bwd_ref(host(a.float()), host(g1), None if g2 is None else host(g2))
     e = rel_l2(host(dz_ref.float()), r64)
     assert e < TOL_BF16 and band_untouched(br) and _written(dz_ref), e
+    zr, ztol = eb.in_bwd_ref_tol(host(a.float()), host(stats), host(g1), None if g2 is None else host(g2), slope=0.2, dt="bf16")
+    eb.note("in_bwd gf32 two passes", "bf16", eb.within(host(dz_ref.float()), zr, ztol, {"kind": "in"}, R.R8))
+    eb.within(host(db_ref), zr.sum((0, 1, 2)), eb.in_sum_tol(zr, ztol, (0, 1, 2)), None, "in_bwd gf32 bias gradient")
     assert float(red3.abs().max()) == 0.0
     red = torch.zeros(ops.GSUM_SLOTS * n * c * 2, dtype=torch.float64, device="cuda")
     redp = torch.zeros_like(red) if pooled else None
@@ -219,6 +226,7 @@ def test_in_bwd_apply_gf32(pooled, h, w):
     ops.in_bwd_apply(g1, c, g2, c, a, c, stats, beta, red, redp, dstage, dz, c, db, n, h, w, c, 0.2)
     torch.cuda.synchronize()
     assert band_untouched(bz) and _written(dz)
+    # (no per-element bound for the RAW-sums form, see test_rect_gpu.test_in_bwd_apply_rect: it is held to the two-pass result, which is held element by element above)
     # test_gsum_gpu.test_in_bwd_apply_matches_reduce_plus_apply's bf16 bounds (the pooled form sums g2 against avgpool(normalised a), itself bf16)
     tol = 2e-2 if pooled else TOL_BF16
     assert rel_l2(host(dz.float()), host(dz_ref.float())) < tol, rel_l2(host(dz.float()), host(dz_ref.float()))

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+import elem_bound_ref as eb
 from oracle import step_torch as st
 from util import SENTINEL, band_untouched, guard_elems, host, rel_l2
 
@@ -116,9 +117,12 @@ def _dgrad_case(variant, dt, n, h, cin, cout, n1, stride=1, k=3, which=(True, Tr
         _check_sums(red0, dxb, aux0, dt)
     if g1 is not None:
         _check_sums(red1, dx2b, aux1, dt)
-    if dt == "gf32":          # fp32 dx from bf16 operands: float64 on the operands as the device holds them, at test_bf16_gpu.TOL32
-        xt = torch.zeros(n, cin, h, h, dtype=torch.float64, requires_grad=True)
-        ref, = torch.autograd.grad(st.conv2d_same(xt, w.double().cpu(), stride), xt, dy.double().cpu().permute(0, 3, 1, 2))
+    # the product, element by element (elem_bound_ref.py): float64 on the operands as the device holds them; "gf32" stores fp32
+    xt = torch.zeros(n, cin, h, h, dtype=torch.float64, requires_grad=True)
+    ref, = torch.autograd.grad(st.conv2d_same(xt, w.double().cpu(), stride), xt, dy.double().cpu().permute(0, 3, 1, 2))
+    eb.hold_dgrad([host(dxb.float())] + ([host(dx2b.float())] if split else []), host(dy.float()), host(w.float()), stride, ref.permute(0, 2, 3, 1).numpy(),
+                  "bf16" if dt == "bf16" else "f32", ("dgrad gf32 " if dt == "gf32" else "dgrad gsum ") + kern.split("<")[0])
+    if dt == "gf32":          # fp32 dx from bf16 operands, at test_bf16_gpu.TOL32
         got = host(dxb) if not split else np.concatenate([host(dxb), host(dx2b)], -1)
         err = rel_l2(got, ref.permute(0, 2, 3, 1).numpy())
         print(f"{kern}: rel-L2 {err:.2e}")
@@ -223,11 +227,14 @@ def test_fwd_gsum_stride2(variant, dt):
     torch.cuda.synchronize()
     assert torch.equal(ya, yb) and band_untouched(ba) and band_untouched(bb)
     _check_sums(red, yb, aux, dt)
+    kern = ops.last_kernel()
+    wr = torch.from_numpy(w.astype(np.float32))          # the weights as the device holds them, from the NumPy array (not from the packed buffer)
+    wr = (wr if dt == "f32" else wr.to(BF)).double()
+    ref = st.conv2d_same(x.double().cpu().permute(0, 3, 1, 2), wr, 2).permute(0, 2, 3, 1).numpy()
+    eb.hold_fwd(host(yb.float()), host(x.float()), wr.numpy(), None, 2, ref, "bf16" if dt == "bf16" else "f32", ("fwd gf32 s2 " if dt == "gf32" else "fwd gsum s2 ") + kern.split("<")[0])
     if dt == "gf32":
-        kern = ops.last_kernel()
         assert kern == GF32_SYMBOL["dma64x64" if variant == "auto" else variant].format(gs=""), kern          # (auto: 8 tiles of 64 x 128, "not even one per CU")
         assert _fused_epilogue_ran(red, n, cout), kern
-        ref = st.conv2d_same(x.double().cpu().permute(0, 3, 1, 2), torch.from_numpy(w.astype(np.float32)).to(BF).double(), 2).permute(0, 2, 3, 1).numpy()
         assert rel_l2(host(yb), ref) < 1e-4, (kern, rel_l2(host(yb), ref))
 
 

@@ -15,6 +15,8 @@ import numpy as np
 import pytest
 import torch
 
+import elem_bound_ref as eb
+
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
 
@@ -77,6 +79,14 @@ def _reference(a, g, g2, stats, n, h, c, slope=0.2):
     return dz, dz.sum((0, 1, 2))
 
 
+def _hold(a, g, g2, stats, *results):
+    """elem_bound_ref.py: dz element by element and the bias gradient per channel, against the float64 value of the device's own expression,
+    in channel slices (the 1024 x 1024 map is held with the memory of one channel).  results: (dz, dbias or None, shm_last_kernel())"""
+    worst = eb.hold_in_bwd([(z, b, None, kern) for z, b, kern in results], a, stats, g, g2, dt="bf16" if a.dtype == BF else "f32")
+    for kern, r in worst.items():
+        eb.note("in_bwd " + kern.replace("in_bwd_", "").replace("_kernel", "").split("<")[0], "bf16" if a.dtype == BF else "f32", r)
+
+
 # (n, h, c, pooled): barrier groups of 64 channels with 256-pixel slices (16 / 64 / 256 blocks per group; 128 .. 512 channels: 2 .. 8 groups per
 # sample); 8 / 32 channels -> 2048 / 512-pixel slices; pooled: tiles of 2 x 128, 4 x 64, 16 x 16 pixels
 SHAPES = [(3, 64, 64, False), (2, 128, 64, True), (2, 256, 64, False), (2, 256, 64, True), (2, 128, 128, True), (5, 64, 128, True), (3, 32, 256, False),
@@ -107,6 +117,7 @@ def test_fused_matches_two_passes_and_float64(n, h, c, pool, gshift):
     zr, br = _reference(a, g, g2, stats, n, h, c)
     assert float((z1.double() - zr).norm() / zr.norm()) < 4e-3                          # bf16 output rounding: 2^-9 relative per element
     assert float((b1 - br).abs().max()) <= 4e-3 * float(zr.abs().sum((0, 1, 2)).max())
+    _hold(a, g, g2, stats, (z1, b1, k1), (z0, b0, k0))
     # second call on the same scratch: no float atomics, the rows are added in block order -> the same bits
     z2, b2, _ = _run(a, g, g2, stats, n, h, c, scratch)
     assert torch.equal(z2, z1) and torch.equal(b2, b1)
@@ -123,6 +134,7 @@ def test_fused_without_bias_gradient():
     assert k1 == "in_bwd_fused8_kernel<false>"
     zr, _ = _reference(a, g, None, stats, n, h, c)
     assert float((z1.double() - zr).norm() / zr.norm()) < 4e-3
+    _hold(a, g, None, stats, (z1, None, k1))
     assert _clean(scratch, n, h, c)
 
 
@@ -164,6 +176,7 @@ def test_g_held_kernel_matches_the_other_forms(n, h, c, gshift, variant):
     zr, br = _reference(a, g, None, stats, n, h, c)
     assert float((zg.double() - zr).norm() / zr.norm()) < 4e-3
     assert float((bg - br).abs().max()) <= 4e-3 * float(zr.abs().sum((0, 1, 2)).max())
+    _hold(a, g, None, stats, (zg, bg, kg), (z8, b8, k8), (z0, b0, k0))
     ops.set_tuning("elem.fused_bwd", 1)
     ops.set_tuning("elem.fused_hold", 2)
     z2, b2, _ = _run(a, g, None, stats, n, h, c, scratch)        # bitwise repeatable, also right behind the other kernels on this scratch
@@ -182,6 +195,7 @@ def test_g_held_kernel_is_the_automatic_choice_on_the_largest_maps():
         assert k == want, (n, h, c, k)
         zr, _ = _reference(a, g, None, stats, n, h, c)
         assert float((z.double() - zr).norm() / zr.norm()) < 4e-3 and _clean(scratch, n, h, c)
+        _hold(a, g, None, stats, (z, b, k))
 
 
 @pytest.mark.parametrize("n,h,c,why", [(2, 24, 64, "ragged: 576 pixels are not whole 256-pixel slices"),
@@ -199,6 +213,7 @@ def test_shapes_outside_the_form_run_two_passes(n, h, c, why):
     assert "fused" not in k1, (k1, why)
     zr, br = _reference(a, g, g2, stats, n, h, c)
     assert float((z1.double() - zr).norm() / zr.norm()) < 4e-3
+    _hold(a, g, g2, stats, (z1, b1, k1))
     assert float(scratch.abs().max()) == 0.0
 
 

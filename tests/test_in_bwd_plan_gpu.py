@@ -21,6 +21,8 @@ import numpy as np
 import pytest
 import torch
 
+import elem_bound_ref as eb
+
 pytestmark = pytest.mark.gpu
 BF, F32 = torch.bfloat16, torch.float32
 GF32 = "gf32"               # a row's dtype: bf16 activations (a, dz) with the gradient signal (g, g2) in fp32, SHM_BF16_GF32
@@ -96,6 +98,15 @@ def _run(o, n, h, w, c, scratch=None, sums=False):
     return dz, db, keep, kern
 
 
+def _hold(o, n, c, dz, db, keep, dt, kern):
+    """elem_bound_ref.py: dz element by element, the bias gradient and the per-sample dz sums per channel, against the float64 value of the
+    device's own expression (mean and inv as the kernels read them from `stats`)"""
+    out = "f32" if dt == F32 else "bf16"
+    worst = eb.hold_in_bwd([(dz, db, keep, kern)], o["a"], o["stats"], o["g"], o["g2"], o["hdz"], o["hw"], 0.2, out)
+    fam = "in_bwd " + (GF32 + " " if dt == GF32 else "") + ("rank-1 " if o["hdz"] is not None else "") + kern.replace("in_bwd_", "").replace("_kernel", "").split("<")[0]
+    eb.note(fam, out, worst[kern])
+
+
 def _rel(x, ref):
     return float((x.double() - ref).norm() / ref.norm())
 
@@ -155,10 +166,12 @@ def test_dispatch_table(dt, n, h, w, c, pool, rank1, knobs, scr, want):
     tol = TOL if dt == F32 else TOL_BF16
     assert _rel(dz, zr) < tol, _rel(dz, zr)
     assert float((db - sr.sum(0)).abs().max()) <= tol * float(zr.abs().sum((0, 1, 2)).max())
+    _hold(o, n, c, dz, db, keep, dt, kern)
     if keep is not None:          # the per-sample dz sums, on the scale of their summands like the bias gradient; and the same call without them (the folding apply pass)
         assert float((keep - sr).abs().max()) <= tol * float(zr.abs().sum((1, 2)).max())
         dz1, db1, _, kern1 = _run(o, n, h, w, c, scratch)
         assert kern1 == want and _rel(dz1, zr) < tol and float((db1 - sr.sum(0)).abs().max()) <= tol * float(zr.abs().sum((0, 1, 2)).max())
+        _hold(o, n, c, dz1, db1, None, dt, kern1)
 
 
 # 32 x 32 x 64 maps: a plain sample is 512 KiB in fp32 and 256 KiB in bf16, a pooled fp32 sample 576 KiB.  Chunks of 1 MiB: 2 + 1 samples (fp32),

@@ -7,6 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import elem_bound_ref as eb
 from oracle import step_torch as st
 from oracle import tf_ops_np as tn
 from util import conv_ref, cosine, dev, host, nchw, nhwc, pad_c, rel_l2, t64
@@ -19,6 +20,26 @@ TOL = 1e-5
 def _ops():
     from shmgan_amd import ops
     return ops
+
+
+def _kern():
+    return _ops().last_kernel().split("<")[0]
+
+
+def _hold_fwd(y, x, w, b, s, slope, family):
+    """elem_bound_ref.py's per-element bound: float64 on the operands as the device holds them (dev() rounds them to fp32)"""
+    x, w, b = eb.f32(x), eb.f32(w), None if b is None else eb.f32(b)
+    eb.hold_fwd(host(y), x, w, b, s, eb.fwd_ref(x, w, b, s, slope), "f32", family)
+
+
+def _hold_dgrad(parts, dy, w, s, hw, family):
+    dy, w = eb.f32(dy), eb.f32(w)
+    eb.hold_dgrad(parts, dy, w, s, eb.dgrad_ref(dy, w, s, hw), "f32", family)
+
+
+def _hold_wgrad(dw, x, dy, s, k, family, before=None):
+    x, dy = eb.f32(x), eb.f32(dy)
+    eb.hold_wgrad(host(dw), x, dy, s, eb.wgrad_ref(x, dy, s, k), family, "f32", k, before=before)
 
 
 def _wk(w_hwio, cin_pad):
@@ -47,6 +68,7 @@ def test_conv2d_fwd(n, h, cin, cout, k, s):
     y = torch.empty((n, ho, ho, cout), device="cuda")
     ops.conv2d_fwd(dev(x), None, 0, cin, 0, _wk(w, cin), dev(b), y, cout, n, h, h, cin, cout, k, s, 0.2)
     assert rel_l2(host(y), ref) < TOL
+    _hold_fwd(y, x, w, b, s, 0.2, "fwd default " + _kern())
 
 
 def test_conv2d_fwd_padded_cin_and_concat():
@@ -60,6 +82,7 @@ def test_conv2d_fwd_padded_cin_and_concat():
     y = torch.empty((n, h, h, cout), device="cuda")
     ops.conv2d_fwd(dev(pad_c(x, 16)), None, 0, 16, 0, _wk(w, 16), None, y, cout, n, h, h, 16, cout, 3, 1, 1.0)
     assert rel_l2(host(y), ref) < TOL
+    _hold_fwd(y, x, w, None, 1, 1.0, "fwd default " + _kern())
     # concat of two sources (upsampled first, skip second)
     c1, c2 = 32, 48
     xa, xb = rng.standard_normal((n, h, h, c1)), rng.standard_normal((n, h, h, c2))
@@ -67,6 +90,7 @@ def test_conv2d_fwd_padded_cin_and_concat():
     ref = conv_ref(np.concatenate([xa, xb], -1), w, 1)
     ops.conv2d_fwd(dev(xa), dev(xb), c1, c1, c2, _wk(w, c1 + c2), None, y, cout, n, h, h, c1 + c2, cout, 3, 1, 1.0)
     assert rel_l2(host(y), ref) < TOL
+    _hold_fwd(y, np.concatenate([xa, xb], -1), w, None, 1, 1.0, "fwd default " + _kern())
 
 
 @pytest.mark.parametrize("n,h,cin,cout,k,s", [
@@ -87,6 +111,7 @@ def test_conv2d_dgrad(n, h, cin, cout, k, s):
     dx = torch.full((n, h, h, ld), 7.0, device="cuda")
     ops.conv2d_dgrad(dev(dy), cout, dev(w), dx, None, cin, ld, 0, n, h, h, cin, cout, k, s)
     assert rel_l2(host(dx)[..., :cin], ref) < TOL
+    _hold_dgrad(host(dx)[..., :cin], dy, w, s, (h, h), "dgrad default " + _kern())
 
 
 def test_conv2d_dgrad_split():
@@ -103,6 +128,7 @@ def test_conv2d_dgrad_split():
     ops.conv2d_dgrad(dev(dy), cout, dev(w), d1, d2, c1, c1, c2, n, h, h, c1 + c2, cout, 3, 1)
     assert rel_l2(host(d1), ref[..., :c1]) < TOL
     assert rel_l2(host(d2), ref[..., c1:]) < TOL
+    _hold_dgrad([host(d1), host(d2)], dy, w, 1, (h, h), "dgrad default " + _kern())
 
 
 @pytest.mark.parametrize("n,h,cin,cout", [(2, 8, 64, 64), (1, 16, 128, 64), (3, 4, 32, 16), (1, 2, 512, 512)])
@@ -117,6 +143,8 @@ def test_conv2d_transpose_fwd(n, h, cin, cout):
     y = torch.empty((n, 2 * h, 2 * h, cout), device="cuda")
     ops.conv2d_transpose_fwd(dev(x), cin, dev(w), dev(b), y, cout, n, h, h, cin, cout, 0.2)
     assert rel_l2(host(y), ref) < TOL
+    xr, wr, br = eb.f32(x), eb.f32(w), eb.f32(b)
+    eb.hold_transpose(host(y), xr, wr, br, eb.transpose_ref(xr, wr, br, 0.2), "f32", "transpose default " + _kern())
     # tiny case against the NumPy scatter restatement as well
     if n * h <= 12:
         ref2 = tn.conv2d_transpose_same(x, w) + b
@@ -147,9 +175,12 @@ def test_conv2d_wgrad(n, h, cin, cout, k, s):
     ws = _ws(ops.conv2d_wgrad_workspace(n, ho, ho, cin, cout, k))
     ops.conv2d_wgrad(dev(pad_c(x, ld)), None, 0, ld, 0, dev(dy), cout, dw, n, h, h, cin, ld, cout, k, s, 0, ws)
     assert rel_l2(host(dw), ref.numpy()) < TOL
+    first = host(dw)
+    _hold_wgrad(dw, x, dy, s, k, "wgrad default " + _kern())
     # accumulate
     ops.conv2d_wgrad(dev(pad_c(x, ld)), None, 0, ld, 0, dev(dy), cout, dw, n, h, h, cin, ld, cout, k, s, 1, ws)
     assert rel_l2(host(dw), 2 * ref.numpy()) < TOL
+    _hold_wgrad(dw, x, dy, s, k, "wgrad default accumulate " + _kern(), before=first)
 
 
 def test_conv2d_wgrad_concat_and_transpose_roles():
@@ -164,6 +195,7 @@ def test_conv2d_wgrad_concat_and_transpose_roles():
     ws = _ws(ops.conv2d_wgrad_workspace(n, h, h, c1 + c2, cout, 3))
     ops.conv2d_wgrad(dev(xa), dev(xb), c1, c1, c2, dev(dy), cout, dw, n, h, h, c1 + c2, c1 + c2, cout, 3, 1, 0, ws)
     assert rel_l2(host(dw), ref.numpy()) < TOL
+    _hold_wgrad(dw, np.concatenate([xa, xb], -1), dy, 1, 3, "wgrad default " + _kern())
     # Conv2DTranspose weight gradient: x = dz at 2H, dy = layer input at H, stride 2
     cin_t, cout_t, hs = 32, 64, 4
     xin = rng.standard_normal((n, hs, hs, cin_t))
@@ -174,6 +206,7 @@ def test_conv2d_wgrad_concat_and_transpose_roles():
     ws = _ws(ops.conv2d_wgrad_workspace(n, hs, hs, cout_t, cin_t, 3))
     ops.conv2d_wgrad(dev(dz), None, 0, cout_t, 0, dev(xin), cin_t, dw, n, 2 * hs, 2 * hs, cout_t, cout_t, cin_t, 3, 2, 0, ws)
     assert rel_l2(host(dw), ref.numpy()) < TOL
+    _hold_wgrad(dw, dz, xin, 2, 3, "wgrad default " + _kern())
 
 
 def test_conv2d_transpose_dgrad_via_fwd():
@@ -190,6 +223,7 @@ def test_conv2d_transpose_dgrad_via_fwd():
     dx = torch.empty((n, h, h, cin), device="cuda")
     ops.conv2d_fwd(dev(dz), None, 0, cout, 0, wk, None, dx, cin, n, 2 * h, 2 * h, cout, cin, 3, 2, 1.0)
     assert rel_l2(host(dx), nhwc(ref)) < TOL
+    _hold_fwd(dx, dz, w, None, 2, 1.0, "fwd default " + _kern())
 
 
 @pytest.mark.parametrize("n,h,c", [(2, 16, 64), (3, 8, 16), (1, 32, 128), (5, 2, 1024), (2, 4, 48)])
@@ -212,16 +246,22 @@ def test_instance_norm_fwd_bwd(n, h, c):
     ops.in_stats(ad, c, stats, n, h * h, c, 1e-6)
     ops.in_apply(ad, c, stats, dev(beta), out, c, n, h * h, c)
     assert rel_l2(host(out), nhwc(yt.detach())) < TOL
+    a32, where = eb.f32(a), {"kind": "in"}
+    eb.note("in_apply", "f32", eb.within(host(out), *eb.in_apply_ref_tol(a32, host(stats), eb.f32(beta), "f32"), where, "in_apply"))
     red = torch.zeros(n * c * 3, dtype=torch.float64, device="cuda")
     dz = torch.empty((n, h, h, c), device="cuda")
     db = torch.zeros(c, dtype=torch.float64, device="cuda")
     ops.in_bwd(dev(g1), c, dev(g2), c, ad, c, stats, red, dz, c, db, n, h, h, c, 0.2)
     assert rel_l2(host(dz), nhwc(ref_dz)) < TOL
     assert rel_l2(host(db), nhwc(ref_dz).sum(axis=(0, 1, 2))) < TOL
+    zr, ztol = eb.in_bwd_ref_tol(a32, host(stats), eb.f32(g1), eb.f32(g2), slope=0.2, dt="f32")
+    eb.note("in_bwd two passes", "f32", eb.within(host(dz), zr, ztol, where, "in_bwd (pooled)"))
+    eb.within(host(db), zr.sum((0, 1, 2)), eb.in_sum_tol(zr, ztol, (0, 1, 2)), None, "in_bwd bias gradient")
     # pooling forward
     pl = torch.empty((n, h // 2, h // 2, c), device="cuda")
     ops.avgpool2_fwd(out, c, pl, c, n, h, h, c)
     assert rel_l2(host(pl), nhwc(pooled.detach())) < TOL
+    eb.note("avgpool2_fwd", "f32", eb.within(host(pl), *eb.in_pool_ref_tol(host(out), "f32"), where, "avgpool2_fwd"))
     # the same two results from ONE pass (shm_in_apply_pool): bit-identical, in both dtypes
     for dt in (torch.float32, torch.bfloat16):
         a_t = ad.to(dt)
@@ -231,10 +271,15 @@ def test_instance_norm_fwd_bwd(n, h, c):
         ops.avgpool2_fwd(o1, c, p1, c, n, h, h, c)
         ops.in_apply_pool(a_t, c, stats, dev(beta), o2, c, p2, c, n, h, h, c)
         assert torch.equal(o1, o2) and torch.equal(p1, p2)
+        dn = "bf16" if dt == torch.bfloat16 else "f32"
+        eb.note("in_apply_pool", dn, eb.within(host(o2.float()), *eb.in_apply_ref_tol(host(a_t.float()), host(stats), eb.f32(beta), dn), where, "in_apply_pool"))
+        eb.note("in_apply_pool", dn, eb.within(host(p2.float()), *eb.in_pool_ref_tol(host(o2.float()), dn), where, "in_apply_pool (pooled)"))
     # numpy restatement of the backward (no pooled term)
     ops.in_bwd(dev(g1), c, None, 0, ad, c, stats, red, dz, c, None, n, h, h, c, 0.2)
     ref2 = tn.leaky_relu_grad(z, tn.instance_norm_bwd(a, g1))
     assert rel_l2(host(dz), ref2) < TOL
+    zr, ztol = eb.in_bwd_ref_tol(a32, host(stats), eb.f32(g1), slope=0.2, dt="f32")
+    eb.note("in_bwd two passes", "f32", eb.within(host(dz), zr, ztol, where, "in_bwd"))
 
 
 @pytest.mark.parametrize("n,h,c", [(3, 16, 64), (2, 12, 16), (1, 32, 128)])

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import elem_bound_ref as eb
 from oracle import step_torch as st
 from util import conv_ref, dev, host, nchw, pad_c, rel_l2
 
@@ -38,6 +39,26 @@ def _x(x, dt):
     return dev(pad_c(x, 4 if dt == torch.float32 else 8)).to(dt).contiguous()
 
 
+def _held(a, dt):
+    """the operand as the device holds it (float64)"""
+    return np.asarray(a, np.float32).astype(np.float64) if dt == torch.float32 else rb(a)
+
+
+def _bound_fwd(y, x, w, b, slope, dt, family):
+    """elem_bound_ref.py's per-element bound, against float64 on the operands as the device holds them"""
+    xr, wr = _held(x, dt), _held(w, dt)
+    br = None if b is None else _held(b, torch.float32)
+    ref = conv_ref(xr, wr, 2) + (0.0 if br is None else br)
+    eb.hold_fwd(host(y.float()), xr, wr, br, 2, np.where(ref > 0, ref, slope * ref), "f32" if dt == torch.float32 else "bf16", family)
+
+
+def _bound_wgrad(dw, x, dy, dt, family, before=None):
+    xr, dyr = _held(x, dt), _held(dy, dt)
+    wt = torch.zeros(3, 3, 3, dy.shape[-1], dtype=torch.float64, requires_grad=True)
+    ref, = torch.autograd.grad(st.conv2d_same(nchw(xr), wt, 2), wt, nchw(dyr))
+    eb.hold_wgrad(host(dw), xr, dyr, 2, ref.numpy(), family, "f32" if dt == torch.float32 else "bf16", before=before)
+
+
 # (12 x 256 x 256: a grid that fills the chip -- the size at which a store-data hazard of the first version showed, see tools/check_isa_hazards.py)
 CASES = [(3, 32, 64, True), (2, 64, 32, False), (1, 32, 16, True), (5, 96, 48, False), (7, 32, 64, False), (12, 256, 64, False)]
 
@@ -65,6 +86,7 @@ def test_first_layer_forward_on_the_compact_image(dt, n, h, cout, with_bias):
         ops.conv2d_in_fwd(xd, None, 0, xd.shape[-1], 0, wk, bias, y, cout, n, h, h, kpad, cout, 3, 2, 0.2, stats, 1e-6, scratch=scr)
         assert ops.last_kernel().startswith("conv3x3s2_rgb_fwd_kernel<"), ops.last_kernel()
         assert rel_l2(host(y.float()), ref) < tol
+        _bound_fwd(y, x, w, b, 0.2, dt, "fwd conv3x3s2_rgb_fwd_kernel")
         yy = host(y.float()).astype(np.float64).reshape(n, -1, cout)
         s = host(stats).reshape(n, cout, 2)
         assert np.abs(s[..., 0] - yy.mean(1)).max() < 1e-4
@@ -74,6 +96,7 @@ def test_first_layer_forward_on_the_compact_image(dt, n, h, cout, with_bias):
         ops.conv2d_fwd(xd, None, 0, xd.shape[-1], 0, wk, bias, y1, cout, n, h, h, kpad, cout, 3, 2, 1.0)
         assert ops.last_kernel().startswith("conv3x3s2_rgb_fwd_kernel<")
         assert rel_l2(host(y1.float()), conv_ref(q(x), q(w), 2) + (b if with_bias else 0.0)) < tol
+        _bound_fwd(y1, x, w, b, 1.0, dt, "fwd conv3x3s2_rgb_fwd_kernel")
         # into a wider tensor (output pitch > cout: the kernel's direct stores instead of the linear ones out of LDS)
         yw = torch.full((n, ho, ho, 2 * cout), 7.0, device="cuda", dtype=dt)
         ops.conv2d_in_fwd(xd, None, 0, xd.shape[-1], 0, wk, bias, yw, 2 * cout, n, h, h, kpad, cout, 3, 2, 0.2, stats, 1e-6, scratch=scr)
@@ -86,6 +109,7 @@ def test_first_layer_forward_on_the_compact_image(dt, n, h, cout, with_bias):
         ops.conv2d_in_fwd(xd, None, 0, xd.shape[-1], 0, wk, bias, y2, cout, n, h, h, kpad, cout, 3, 2, 0.2, stats2, 1e-6)
         assert ops.last_kernel().startswith("tapgemm_dma_kernel<"), ops.last_kernel()
         assert rel_l2(host(y2.float()), ref) < tol
+        _bound_fwd(y2, x, w, b, 0.2, dt, "fwd rgb tapgemm_dma_kernel")
         assert np.abs(host(stats2) - host(stats)).max() < 2e-3 * np.abs(host(stats)).max()
     finally:
         ops.set_tuning("reset", 0)
@@ -137,8 +161,10 @@ def test_first_layer_weight_gradient_on_the_compact_image(dt, n, h, cout):
         assert ops.last_kernel().startswith("conv3x3s2_rgb_wgrad_kernel<"), ops.last_kernel()
         assert rel_l2(host(dw), ref.numpy()) < 1e-5           # float32 products and sums of (exactly representable) operands in both dtypes
         first = host(dw).copy()
+        _bound_wgrad(dw, x, dy, dt, "wgrad conv3x3s2_rgb_wgrad_kernel")
         ops.conv2d_wgrad(xd, None, 0, xd.shape[-1], 0, dz, cout, dw, n, h, h, 3, kpad, cout, 3, 2, 1, ws)
         assert rel_l2(host(dw), 2 * ref.numpy()) < 1e-5
+        _bound_wgrad(dw, x, dy, dt, "wgrad accumulate conv3x3s2_rgb_wgrad_kernel", before=first)
         dw2 = torch.empty_like(dw)
         ops.conv2d_wgrad(xd, None, 0, xd.shape[-1], 0, dz, cout, dw2, n, h, h, 3, kpad, cout, 3, 2, 0, ws)
         assert (host(dw2) == first).all()                      # fixed summation order: bitwise repeatable
@@ -148,6 +174,7 @@ def test_first_layer_weight_gradient_on_the_compact_image(dt, n, h, cout):
         ops.conv2d_wgrad(xd, None, 0, xd.shape[-1], 0, dz, cout, dw3, n, h, h, 3, kpad, cout, 3, 2, 0, ws)
         assert not ops.last_kernel().startswith("conv3x3s2_rgb_wgrad_kernel<")
         assert rel_l2(host(dw3), ref.numpy()) < (1e-5 if dt == torch.float32 else 2e-5)
+        _bound_wgrad(dw3, x, dy, dt, "wgrad rgb generic")
     finally:
         ops.set_tuning("reset", 0)
 
@@ -278,6 +305,7 @@ def test_first_layer_on_non_square_images(dt, n, hi, wi, cout):
     ops.conv2d_in_fwd(xd, None, 0, xd.shape[-1], 0, wk, None, y, cout, n, hi, wi, kpad, cout, 3, 2, 0.2, stats, 1e-6)
     assert ops.last_kernel().startswith("conv3x3s2_rgb_fwd_kernel<"), ops.last_kernel()
     assert rel_l2(host(y.float()), ref) < (1e-5 if dt == torch.float32 else 4e-3)
+    _bound_fwd(y, x, w, None, 0.2, dt, "fwd conv3x3s2_rgb_fwd_kernel")
     yy = host(y.float()).astype(np.float64).reshape(n, -1, cout)
     assert np.abs(host(stats).reshape(n, cout, 2)[..., 0] - yy.mean(1)).max() < 1e-4
     ws = torch.empty(ops.conv2d_wgrad_workspace(n, ho, wo, 3, cout, 3) // 4 + 1024, device="cuda")
@@ -285,3 +313,4 @@ def test_first_layer_on_non_square_images(dt, n, hi, wi, cout):
     ops.conv2d_wgrad(xd, None, 0, xd.shape[-1], 0, dev(dy).to(dt), cout, dw, n, hi, wi, 3, kpad, cout, 3, 2, 0, ws)
     assert ops.last_kernel().startswith("conv3x3s2_rgb_wgrad_kernel<"), ops.last_kernel()
     assert rel_l2(host(dw), gref.numpy()) < 1e-5
+    _bound_wgrad(dw, x, dy, dt, "wgrad conv3x3s2_rgb_wgrad_kernel")

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+import elem_bound_ref as eb
 from oracle import step_torch as st
 from util import conv_ref, host, nchw, nhwc, rel_l2, t64
 
@@ -114,9 +115,11 @@ def _fwd_case(variant, dt, n, h, c1, c2, cout, k, s, seed=0):
     ops.conv2d_in_fwd(_dev(xa, dt), None if xb is None else _dev(xb, dt), c1 if c2 else 0, c1, c2, _wk(w, cin, dt),
                       torch.from_numpy(b.astype(np.float32)).cuda(), y, cout, n, h, h, cin, cout, k, s, 0.2, stats, 1e-6, scratch=scr)
     torch.cuda.synchronize()
-    assert ops.last_kernel() == _sym(variant, dt, cin / 32, hw=(h, h)), ops.last_kernel()
+    kern = ops.last_kernel()
+    assert kern == _sym(variant, dt, cin / 32, hw=(h, h)), kern
     got = host(y.float())
     assert rel_l2(got, ref) < TOL[dt], (variant, dt, rel_l2(got, ref))
+    eb.hold_fwd(got, xr, _rnd(w, dt), b, s, ref, dt, "fwd " + kern.split("<")[0])
     if (ho * ho) % 64 == 0:                   # the fused path (smaller maps take a separate statistics pass)
         _check_stats(stats, got, n, cout, dt)
         assert float(scr.abs().max()) == 0.0  # "zero on entry, zero on return"
@@ -163,6 +166,7 @@ def test_flat_epilogue_refuses_the_buffer_store_kernels_and_keeps_results():
     ops.conv2d_fwd(_dev(x, "f32"), None, 0, cin, 0, _wk(w, cin, "f32"), None, y, cout, n, h, h, cin, cout, 3, 1, 0.2)
     assert not ops.last_kernel().startswith("tapgemm_wreg"), ops.last_kernel()
     assert rel_l2(host(y), ref) < 1e-5
+    eb.hold_fwd(host(y), x.astype(np.float64), w.astype(np.float64), None, 1, ref, "f32", "fwd flat " + ops.last_kernel().split("<")[0])
     ops.set_tuning("tapgemm.variant", "wreg")
     with pytest.raises(ShmError):
         ops.conv2d_fwd(_dev(x, "f32"), None, 0, cin, 0, _wk(w, cin, "f32"), None, y, cout, n, h, h, cin, cout, 3, 1, 0.2)
@@ -178,6 +182,7 @@ def test_flat_epilogue_refuses_the_buffer_store_kernels_and_keeps_results():
     ops.conv2d_transpose_fwd(torch.from_numpy(xt).cuda(), ci, torch.from_numpy(wt).cuda(), torch.from_numpy(b).cuda(), yt, co, n, hs, hs, ci, co, 0.2)
     assert ops.last_kernel().startswith("tapgemm_phase4_kernel"), ops.last_kernel()
     assert rel_l2(host(yt), r) < 1e-5
+    eb.hold_transpose(host(yt), xt.astype(np.float64), wt.astype(np.float64), b, r, "f32", "transpose flat tapgemm_phase4_kernel")
 
 
 # ---- weights-in-registers kernels (<= 64 input channels from one tensor): persistent blocks over 8 x 16 patches
@@ -213,7 +218,8 @@ def test_pingpong_forward_with_statistics(n, hi, wi, cout, slope):
     x = rng.standard_normal((n, hi, wi, cin))
     w = rng.standard_normal((3, 3, cin, cout)) * 0.1
     b = rng.standard_normal(cout)
-    ref = conv_ref(_rnd(x, "bf16"), _rnd(w, "bf16"), 1) + b
+    xr, wr = _rnd(x, "bf16"), _rnd(w, "bf16")
+    ref = conv_ref(xr, wr, 1) + b
     ref = np.where(ref > 0, ref, slope * ref)
     y = torch.full((n, hi, wi, cout), 9.0, device="cuda", dtype=BF)
     stats = torch.empty(n * cout * 2, dtype=torch.float64, device="cuda")
@@ -226,6 +232,9 @@ def test_pingpong_forward_with_statistics(n, hi, wi, cout, slope):
         assert ops.last_kernel() == "tapgemm_pp_bf16_kernel<2>", ops.last_kernel()
         got = host(y.float())
         assert rel_l2(got, ref) < TOL["bf16"], rel_l2(got, ref)
+        if rep == 0:
+            tol = eb.fwd_tol(xr, wr, b, 1, ref, "bf16")          # MODE 2 and MODE 1 compute the same function
+        eb.note("fwd tapgemm_pp_bf16_kernel", "bf16", eb.within(got, ref, tol, eb.CONV, "tapgemm_pp_bf16_kernel<2>"))
         if (hi * wi) % 64 == 0:
             _check_stats(stats, got, n, cout, "bf16")
         y.fill_(9.0)
@@ -233,10 +242,13 @@ def test_pingpong_forward_with_statistics(n, hi, wi, cout, slope):
     ops.conv2d_fwd(_dev(x, "bf16"), None, 0, cin, 0, _wk(w, cin, "bf16"), torch.from_numpy(b.astype(np.float32)).cuda(), y, cout, n, hi, wi, cin, cout, 3, 1, slope)
     assert ops.last_kernel() == "tapgemm_pp_bf16_kernel<1>", ops.last_kernel()
     assert rel_l2(host(y.float()), ref) < TOL["bf16"]
+    eb.note("fwd tapgemm_pp_bf16_kernel", "bf16", eb.within(host(y.float()), ref, tol, eb.CONV, "tapgemm_pp_bf16_kernel<1>"))
     # the same product without bias, activation or statistics: MODE 0
     ops.conv2d_fwd(_dev(x, "bf16"), None, 0, cin, 0, _wk(w, cin, "bf16"), None, y, cout, n, hi, wi, cin, cout, 3, 1, 1.0)
     assert ops.last_kernel() == "tapgemm_pp_bf16_kernel<0>", ops.last_kernel()
-    assert rel_l2(host(y.float()), conv_ref(_rnd(x, "bf16"), _rnd(w, "bf16"), 1)) < TOL["bf16"]
+    ref0 = conv_ref(xr, wr, 1)
+    assert rel_l2(host(y.float()), ref0) < TOL["bf16"]
+    eb.hold_fwd(host(y.float()), xr, wr, None, 1, ref0, "bf16", "fwd tapgemm_pp_bf16_kernel")
 
 
 # ---- "tapgemm.wreg16" = 0: the four-wave bf16 form with 32-column wave tiles (the default is the eight-wave form, test_wreg_forced_variant)
@@ -352,6 +364,9 @@ def test_wreg_f32_narrow_and_concat(n, h, c1, c2, cout, sym):
                        torch.from_numpy(b.astype(np.float32)).cuda(), y, cout, n, h, h, cin, cout, 3, 1, 0.0)
         assert ops.last_kernel() == sym, ops.last_kernel()
         assert rel_l2(host(y), ref) < 1e-5
+        if variant == "wreg":
+            tol = eb.fwd_tol(xr.astype(np.float32).astype(np.float64), w.astype(np.float32).astype(np.float64), b, 1, ref, "f32")
+        eb.note("fwd tapgemm_wreg_f32_kernel", "f32", eb.within(host(y), ref, tol, eb.CONV, sym))
         y.fill_(9.0)
 
 
@@ -440,7 +455,9 @@ def test_dgrad_s1_forced_variant(variant, dt):
         ops.conv2d_dgrad(_dev(dy, dt), cout, _dev(w, dt), f1, f2, c1, c1, c2, n, h, h, cin, cout, 3, 1)
         assert ops.last_kernel() == "tapgemm_wreg_kernel<float, 2>"
         assert rel_l2(host(f1), ref[..., :c1]) < 1e-4 and rel_l2(host(f2), ref[..., c1:]) < 1e-4
+        eb.hold_dgrad([host(f1), host(f2)], _rnd(dy, dt), _rnd(w, dt), 1, ref, "f32", "dgrad gf32 tapgemm_wreg_kernel")
     assert rel_l2(host(d1.float()), ref[..., :c1]) < TOL[dt] and rel_l2(host(d2.float()), ref[..., c1:]) < TOL[dt]
+    eb.hold_dgrad([host(d1.float()), host(d2.float())], _rnd(dy, dt), _rnd(w, dt), 1, ref, dt, "dgrad " + _sym(variant, dt, epi=False, hw=(h, h)).split("<")[0])
 
 
 @pytest.mark.parametrize("dt", ["f32", "bf16"])
@@ -460,6 +477,7 @@ def test_dgrad_s2_and_transpose_forced_variant(variant, dt):
     ops.conv2d_dgrad(_dev(dy, dt), cout, _dev(w, dt), dx, None, cin, cin, 0, n, h, h, cin, cout, 3, 2)
     assert ops.last_kernel() == _sym(variant, dt)
     assert rel_l2(host(dx.float()), nhwc(ref)) < TOL[dt]
+    eb.hold_dgrad(host(dx.float()), _rnd(dy, dt), _rnd(w, dt), 2, nhwc(ref), dt, "dgrad s2 tapgemm_dma_kernel")
     # Conv2DTranspose(3x3, s2) + bias + LeakyReLU
     hi, ci, co = 8, 64, 96
     x = rng.standard_normal((n, hi, hi, ci))
@@ -471,6 +489,7 @@ def test_dgrad_s2_and_transpose_forced_variant(variant, dt):
     ops.conv2d_transpose_fwd(_dev(x, dt), ci, _dev(wt, dt), torch.from_numpy(b.astype(np.float32)).cuda(), y, co, n, hi, hi, ci, co, 0.2)
     assert ops.last_kernel() == _sym(variant, dt)
     assert rel_l2(host(y.float()), r) < TOL[dt]
+    eb.hold_transpose(host(y.float()), _rnd(x, dt), _rnd(wt, dt), b, r, dt, "transpose tapgemm_dma_kernel")
 
 
 # ---- the four phases fused in one block (tapgemm_phase4_kernel): 16 x 16 input patches, 64-channel output slices
@@ -493,6 +512,7 @@ def test_dgrad_s2_phase4(dt, n, h, cin, cout):
     ops.conv2d_dgrad(_dev(dy, dt), cout, _dev(w, dt), dx, None, cin, cin, 0, n, h, h, cin, cout, 3, 2)
     assert ops.last_kernel() == _sym("phase4", dt)
     assert rel_l2(host(dx.float()), nhwc(ref)) < TOL[dt]
+    eb.hold_dgrad(host(dx.float()), _rnd(dy, dt), _rnd(w, dt), 2, nhwc(ref), dt, "dgrad s2 tapgemm_phase4_kernel")
 
 
 @pytest.mark.parametrize("dt", ["f32", "bf16"])
@@ -513,6 +533,7 @@ def test_conv2d_transpose_phase4(dt, n, hi, ci, co):
     ops.conv2d_transpose_fwd(_dev(x, dt), ci, _dev(wt, dt), torch.from_numpy(b.astype(np.float32)).cuda(), y, co, n, hi, hi, ci, co, 0.2)
     assert ops.last_kernel() == _sym("phase4", dt)
     assert rel_l2(host(y.float()), r) < TOL[dt]
+    eb.hold_transpose(host(y.float()), _rnd(x, dt), _rnd(wt, dt), b, r, dt, "transpose tapgemm_phase4_kernel")
     y8 = torch.empty((1, 16, 16, 64), device="cuda", dtype=adt)
     with pytest.raises(ShmError):             # 8 x 8 input map: not a whole 16 x 16 patch
         ops.conv2d_transpose_fwd(torch.zeros((1, 8, 8, 64), device="cuda", dtype=adt), 64, torch.zeros((3, 3, 64, 64), device="cuda", dtype=adt), None,
@@ -573,12 +594,14 @@ def test_wgrad_forced_variant(dt, wv, expect, n, h, cin, cout, blocks):
             wide = dt == "bf16" and cout >= 128 and rows == 0
             assert k == ("wgrad_halo8_bf16_kernel<0>" if wide else "wgrad_halo_kernel" if dt == "f32" else f"wgrad_halo_bf16_kernel<{rows or 4}>"), k
         assert rel_l2(host(dw), ref.numpy()) < (1e-4 if dt == "bf16" else 1e-5), (k, rel_l2(host(dw), ref.numpy()))
+        eb.hold_wgrad(host(dw), _rnd(x[..., :cin], dt), _rnd(dy, dt), 1, ref.numpy(), "wgrad " + k.split("<")[0], dt)
         if dt == "bf16" and wv == 2 and rows == 0 and cout >= 128:       # ... and the four-wave kernel on the same shape ("wgrad.bf16_wide" = 1)
             ops.set_tuning("wgrad.bf16_wide", 1)
             dw4 = torch.full((3, 3, cin, cout), 3.0, device="cuda")
             ops.conv2d_wgrad(_dev(x, dt), None, 0, ld, 0, _dev(dy, dt), cout, dw4, n, h, h, cin, ld, cout, 3, 1, 0, ws)
             assert ops.last_kernel() == "wgrad_halo_bf16_kernel<4>", ops.last_kernel()
             assert rel_l2(host(dw4), ref.numpy()) < 1e-4
+            eb.hold_wgrad(host(dw4), _rnd(x[..., :cin], dt), _rnd(dy, dt), 1, ref.numpy(), "wgrad wgrad_halo_bf16_kernel", dt)
             ops.set_tuning("wgrad.bf16_wide", 4)
 
 
@@ -608,9 +631,11 @@ def test_wgrad_stride2_halo(n, h, cin, cout, c1, blocks):
         assert k == ("wgrad_halo_kernel<0, true>" if wv == 0 else "wgrad_kernel<9, false>"), k
         got[wv] = host(dw)
         assert rel_l2(got[wv], ref.numpy()) < 1e-5, (k, rel_l2(got[wv], ref.numpy()))
+        eb.hold_wgrad(got[wv], x.astype(np.float64), dy.astype(np.float64), 2, ref.numpy(), "wgrad s2 " + k.split("<")[0], "f32")
         # accumulate into the result
         ops.conv2d_wgrad(xa, xb, c1, c1 if c1 else cin, cin - c1 if c1 else 0, dyd, cout, dw, n, h, h, cin, cin, cout, 3, 2, 1, ws)
         assert rel_l2(host(dw), 2 * ref.numpy()) < 1e-5
+        eb.hold_wgrad(host(dw), x.astype(np.float64), dy.astype(np.float64), 2, ref.numpy(), "wgrad s2 accumulate " + k.split("<")[0], "f32", before=got[wv])
     ops.set_tuning("reset", 0)
     assert rel_l2(got[0], got[3]) < 1e-5
 
@@ -648,8 +673,10 @@ def test_wgrad_stride2_bf16_wide(n, h, cin, cout, c1, blocks):
         assert k == (f"wgrad_halo8_bf16_kernel<{1 if (h // 2) % 16 == 0 else 2}>" if wide == 0 else "wgrad_bf16_kernel<9, false>"), k
         got[wide] = host(dw)
         assert rel_l2(got[wide], ref.numpy()) < 1e-4, (k, rel_l2(got[wide], ref.numpy()))
+        eb.hold_wgrad(got[wide], _rnd(x, "bf16"), _rnd(dy, "bf16"), 2, ref.numpy(), "wgrad s2 " + k.split("<")[0], "bf16")
         ops.conv2d_wgrad(xa, xb, c1, c1 if c1 else cin, cin - c1 if c1 else 0, dyd, cout, dw, n, h, h, cin, cin, cout, 3, 2, 1, ws)     # accumulate
         assert rel_l2(host(dw), 2 * ref.numpy()) < 1e-4
+        eb.hold_wgrad(host(dw), _rnd(x, "bf16"), _rnd(dy, "bf16"), 2, ref.numpy(), "wgrad s2 accumulate " + k.split("<")[0], "bf16", before=got[wide])
     ops.set_tuning("reset", 0)
     assert rel_l2(got[0], got[1]) < 1e-5          # both accumulate in fp32 from the same bf16 products: only the summation order differs
 
@@ -669,6 +696,7 @@ def test_wgrad_stride2_bf16_wide_leaves_what_it_cannot_tile():
         ops.conv2d_wgrad(_dev(x, "bf16"), None, 0, cin, 0, _dev(dy, "bf16"), cout, dw, n, h, h, cin, cin, cout, 3, 2, 0, ws)
         assert ops.last_kernel() == "wgrad_bf16_kernel<9, false>", ops.last_kernel()
         assert rel_l2(host(dw), ref.numpy()) < 1e-4
+        eb.hold_wgrad(host(dw), _rnd(x, "bf16"), _rnd(dy, "bf16"), 2, ref.numpy(), "wgrad s2 wgrad_bf16_kernel", "bf16")
 
 
 def test_wgrad_stride2_halo_refuses_what_it_cannot_tile():
@@ -687,6 +715,7 @@ def test_wgrad_stride2_halo_refuses_what_it_cannot_tile():
         ops.conv2d_wgrad(xa, xb, c1, c1 if c1 else cin, cin - c1 if c1 else 0, torch.from_numpy(dy).cuda(), cout, dw, n, h, h, cin, cin, cout, 3, 2, 0, ws)
         assert ops.last_kernel().startswith("wgrad_kernel<9"), ops.last_kernel()
         assert rel_l2(host(dw), ref.numpy()) < 1e-5
+        eb.hold_wgrad(host(dw), x.astype(np.float64), dy.astype(np.float64), 2, ref.numpy(), "wgrad s2 wgrad_kernel", "f32")
 
 
 # ======================================================================================================

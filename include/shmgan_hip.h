@@ -759,6 +759,42 @@ int shm_augment_pairs_u8(const shm_pair_sample* samples, int n, float* x, float*
 int shm_polar_maps(const float* const* view_ptrs, size_t n, const float* coef, float* s0, float* dop, float* aolp,
                    void* stream);
 
+/* ---- division-of-focal-plane (DoFP) polarisation sensors: one raw mosaic -> the four views (csrc/dofp.hip) --
+ * On such a sensor (Sony IMX250MZR / MYR and relatives) every 2 x 2 quad of pixels sits behind four micro-polarisers, and on the
+ * colour parts every quad sits behind one Bayer filter.  The period P is 2 for SHM_DOFP_MONO and 4 for the Bayer patterns.
+ *   src       the mosaic on the device: uint8 when bits == 8, uint16 when 9 <= bits <= 16, the significant bits LSB-aligned (a 12-bit
+ *             value stored in 16 bits is bits = 12, an MSB-aligned file is bits = 16); h rows of w samples, consecutive rows
+ *             src_pitch >= w ELEMENTS apart.  A 16-bit sample above 2^bits - 1 is not masked: the clamp below handles it.
+ *   quad      host int[4], read during the call: the view index 0..3 at quad positions (0,0), (0,1), (1,0), (1,1), a permutation
+ *             of 0..3.  Sony's 90 / 45 / 135 / 0 with the views in ascending angle is {2, 1, 3, 0}.
+ *   dst_ptrs  host array of 4 device pointers to uint8 [ho,wo,3] planes, read during the call; total: null, or a fifth such plane.
+ * Lattices: the sample at quad position (ay, ax) under colour block (by, bx) of the Bayer tile lies on the lattice with offsets
+ * dy = 2 by + ay, dx = 2 bx + ax and period P (SHM_DOFP_MONO: by = bx = 0).  A view's channel has one lattice for R, one for B and
+ * two for G; SHM_DOFP_MONO gives the view's single lattice to all three channels.  All arithmetic is integer and exact:
+ *   SHM_DOFP_BILINEAR   (ho, wo) = (h, w).  Per axis of length N a lattice with offset d has n = (N - 1 - d) / P + 1 samples; for the
+ *             output coordinate y: q = y - d, i0 = floor(q / P), f = q - P i0, taps clamp(i0, 0, n - 1) with weight P - f and
+ *             clamp(i0 + 1, 0, n - 1) with weight f.  A lattice's numerator is the product-weighted sum of its 2 x 2 taps (total
+ *             weight P^2); a channel's numerator N is the sum over its lattices, and k = 2 log2 P, plus 1 for G.
+ *   SHM_DOFP_BIN        (ho, wo) = (h / P, w / P), remainder rows and columns dropped: N is the lattice's own sample of that
+ *             super-pixel, summed over the channel's lattices; k = 0, or 1 for G.  No interpolation.
+ *   finish    with s = bits - 8:  view = min(255, (N + (1 << (k + s) >> 1)) >> (k + s));
+ *             total = min(255, (sum of the four views' N + (1 << (k + s + 2) >> 1)) >> (k + s + 2)): the round-half-up of the
+ *             UNROUNDED mean of the four views, S0 / 2.
+ * In bilinear mode the mono, R and B channels return the sample itself at its own site; G is half the own sample plus half the mean of
+ * the diagonal neighbours.  One launch, no atomics, no host synchronisation; four consecutive pixels of a plane are three dword stores
+ * when they start 4-byte aligned, byte stores otherwise (same values).  SHM_E_SHAPE before any launch for a null src, quad or
+ * dst_ptrs or a null entry of dst_ptrs, bits outside [8, 16], an unknown pattern or mode, h or w outside [P, 32768], src_pitch < w, or
+ * a quad that is not a permutation of 0..3. */
+#define SHM_DOFP_MONO 0
+#define SHM_DOFP_RGGB 1
+#define SHM_DOFP_BGGR 2
+#define SHM_DOFP_GRBG 3
+#define SHM_DOFP_GBRG 4
+#define SHM_DOFP_BILINEAR 0
+#define SHM_DOFP_BIN 1
+int shm_dofp_views(const void* src, int bits, int h, int w, size_t src_pitch, int pattern, const int* quad, int mode,
+                   unsigned char* const* dst_ptrs, unsigned char* total, void* stream);
+
 /* ---- specular masks from the polarised views (csrc/specmask.hip) ------------------------------------------
  * Specular reflection is polarised, diffuse reflection is not: the polarised intensity sqrt(S1^2 + S2^2) of the Stokes fit, the part
  * SHM_POLAR_STOKES subtracts, thresholded and cleaned up, is a highlight mask of ONE sample that needs no label.  Three calls on one

@@ -30,6 +30,11 @@ per-sample descriptors: no decode and no upload for a resident sample.  A sample
 path every time.  Files that change on disk during a run are not noticed; under data parallelism each rank caches the samples it
 sees (with `shuffle`, eventually the whole set).  `cache="none"` (default) calls exactly the kernels described above.
 
+`capture="dofp"` reads a polariser-mosaic (division-of-focal-plane) sensor: ONE raw frame per sample instead of four view files.  The
+worker decodes it once, the loader stream uploads it once and demosaics it once (shm_dofp_views, csrc/dofp.hip) into the four uint8
+views, which then stand where the uploaded files stood in every path above (`PolarDataset._sources` is that one place; the device cache
+stores the demosaiced views).  DESIGN.md section 6m.
+
 Under torch.distributed the loader shards by rank: global batch i of rank r is images [(i*world + r)*B, +B), so N ranks
 consume N*B distinct samples per step (the data-parallel identity of shmgan_amd/dist.py) and len() = n // (B*world).
 """
@@ -142,15 +147,28 @@ class PolarDataset:
 
     cache: "none", or "device" = decoded samples stay on the device after their first decode (cache.SampleCache) and every batch is
     one shm_augment_batch_u8 launch; cache_bytes: the device memory the cache may take (default: half of what is free when the first
-    sample is stored).  With "device" the images of a sample must have one decoded size, whatever the other options."""
+    sample is stored).  With "device" the images of a sample must have one decoded size, whatever the other options.
+
+    capture: "views" = one file per polariser angle (the above); "dofp" = a polariser-mosaic sensor: the FIRST of `subdirs` holds one
+    raw mosaic per sample (8-bit "L" or 16-bit "I;16" files, polar.decode_mosaic), laid out as `dofp` (a polar.DofpLayout) says, and
+    the second -- read only for diffuse_source "dir" -- the diffuse images, which must have the demosaiced size.  Every sample is
+    decoded once, uploaded once and demosaiced once on the loader stream (shm_dofp_views, `dofp_demosaic` = "bilinear" or "bin");
+    its four views, in ascending angle, then take every path above unchanged, and the device cache stores them as it stores
+    decoded views.  `angles` defaults to dofp.angles."""
 
     def __init__(self, data_dir, image_size, batch_size=1, subdirs=PSD_SUBDIRS, flip_ud=True, device=None, epochs=1,
                  rank=None, world=None, diffuse_source="dir", angles=None, shuffle=False, augment=None, seed=0, first_pass=0,
-                 cache="none", cache_bytes=None, select=None):
+                 cache="none", cache_bytes=None, select=None, capture="views", dofp=None, dofp_demosaic="bilinear"):
+        from . import polar
+        polar.check_capture(capture, dofp, dofp_demosaic, "PolarDataset")
+        self.capture, self.dofp, self.dofp_demosaic = capture, dofp, dofp_demosaic
         # what split() builds its two parts from: this dataset's own options (rank / world as given: None = torch.distributed's)
         self._options = dict(data_dir=data_dir, image_size=image_size, batch_size=batch_size, subdirs=tuple(subdirs), flip_ud=flip_ud,
                              device=device, epochs=epochs, rank=rank, world=world, diffuse_source=diffuse_source, angles=angles,
-                             shuffle=shuffle, augment=augment, seed=seed, first_pass=first_pass, cache=cache, cache_bytes=cache_bytes)
+                             shuffle=shuffle, augment=augment, seed=seed, first_pass=first_pass, cache=cache, cache_bytes=cache_bytes,
+                             capture=capture, dofp=dofp, dofp_demosaic=dofp_demosaic)
+        if capture == "dofp" and angles is None:          # the views come out in ascending angle
+            angles = dofp.angles
         self.S, self.B, self.flip_ud, self.epochs = image_size, batch_size, flip_ud, epochs
         self.H, self.W = frame_hw(image_size)
         if cache not in CACHE_MODES:
@@ -163,7 +181,6 @@ class PolarDataset:
         self.shuffle, self.augment, self.seed, self.first_pass = bool(shuffle), augment, int(seed), int(first_pass)
         self._mirror = ("identity", None)
         if augment is not None and augment.views == "physical" and (augment.flip_lr > 0 or augment.flip_ud > 0):
-            from . import polar
             ang = list(angles if angles is not None else polar.angles_from_subdirs(tuple(subdirs)[:4]))
             if len(ang) != 4:
                 raise ValueError(f"augment views='physical' takes four angles, got {ang}")
@@ -171,19 +188,28 @@ class PolarDataset:
         if diffuse_source not in DIFFUSE_SOURCES:
             raise ValueError(f"diffuse_source {diffuse_source!r} is not one of {DIFFUSE_SOURCES}")
         self.diffuse_source, self.coef = diffuse_source, None
-        if diffuse_source != "dir":
+        if capture == "dofp":          # the first of subdirs holds the mosaics, the second (read for "dir" only) the diffuse images
+            subdirs = tuple(subdirs)[:2 if diffuse_source == "dir" else 1]
+            if len(subdirs) != (2 if diffuse_source == "dir" else 1):
+                raise ValueError(f"capture 'dofp' with diffuse_source {diffuse_source!r} needs the mosaic directory" +
+                                 (" and the diffuse directory" if diffuse_source == "dir" else "") + f" in subdirs, got {subdirs}")
+            if diffuse_source == "stokes":
+                self.coef = polar.stokes_matrix(angles)
+                if self.coef.shape != (3, 4):
+                    raise ValueError(f"diffuse_source 'stokes' takes four angles, got {angles}")
+        elif diffuse_source != "dir":
             subdirs = tuple(subdirs)[:4]
             if len(subdirs) != 4:
                 raise ValueError(f"diffuse_source {diffuse_source!r} needs four view directories, got {subdirs}")
             if diffuse_source == "stokes":
-                from . import polar
                 self.coef = polar.stokes_matrix(angles if angles is not None else polar.angles_from_subdirs(subdirs))
                 if self.coef.shape != (3, 4):
                     raise ValueError(f"diffuse_source 'stokes' takes four angles, got {angles}")
         self.files = [list_images(os.path.join(data_dir, s)) for s in subdirs]
         n = len(self.files[0])
         if any(len(f) != n for f in self.files):
-            raise ValueError(f"the {len(self.files)} view directories hold different numbers of images: {[len(f) for f in self.files]}")
+            raise ValueError(f"the {len(self.files)} {'sample' if capture == 'dofp' else 'view'} directories hold different numbers of images: "
+                             f"{[len(f) for f in self.files]}")
         self.select = None
         if select is not None:           # a subset: everything below (n, positions, shuffle, augmentation draws, cache keys) counts within it
             select = [int(i) for i in select]
@@ -238,12 +264,49 @@ class PolarDataset:
         buf.numpy()[...] = a
         return buf
 
+    def _decode_mosaic(self, path, key):
+        """_decode for a polariser mosaic: a pinned uint8 or uint16 [h,w] buffer (polar.decode_mosaic)."""
+        from . import polar
+        a = polar.decode_mosaic(path, self.dofp)
+        buf = self._pin.get(key)
+        if buf is None or tuple(buf.shape) != a.shape or buf.numpy().dtype != a.dtype:
+            buf = torch.empty(a.shape, dtype=torch.uint8 if a.dtype == np.uint8 else torch.uint16).pin_memory()
+            self._pin[key] = buf
+        buf.numpy()[...] = a
+        return buf
+
+    def _decode_files(self, paths, gen, b):
+        """One sample's files, paths[f], decoded into this generation's pinned buffers: its four or five images, or with
+        capture="dofp" its mosaic (file 0) and, for diffuse_source "dir", its diffuse image."""
+        mosaic = self.capture == "dofp"
+        return [self._decode_mosaic(p, (gen, f, b)) if mosaic and f == 0 else self._decode(p, (gen, f, b)) for f, p in enumerate(paths)]
+
+    def _nfiles(self, nsrc):
+        """Files behind a sample's `nsrc` (4 or 5) source images: one each, or a mosaic for the four views."""
+        return nsrc - 3 if self.capture == "dofp" else nsrc
+
     def _stage(self, index, gen, pass_index, nsrc):
-        """Decode the `nsrc` files of every sample of the batch into this generation's pinned buffers: (staged[v][b], paths[v][b],
-        the samples' positions in the sorted file lists)."""
+        """Decode the files behind the `nsrc` source images of every sample of the batch into this generation's pinned buffers:
+        (staged[f][b], paths[f][b], the samples' positions in the sorted file lists)."""
         pos = [self.position(index, b, pass_index) for b in range(self.B)]
-        paths = [[self.files[v][p] for p in pos] for v in range(nsrc)]
-        return [[self._decode(paths[v][b], (gen, v, b)) for b in range(self.B)] for v in range(nsrc)], paths, pos
+        paths = [[self.files[f][p] for p in pos] for f in range(self._nfiles(nsrc))]
+        per_sample = [self._decode_files([paths[f][b] for f in range(len(paths))], gen, b) for b in range(self.B)]
+        return [[per_sample[b][f] for b in range(self.B)] for f in range(len(paths))], paths, pos
+
+    def _sources(self, staged, paths, b, nsrc):
+        """The choke point "sample b -> its `nsrc` uint8 [h,w,3] device images", on the current (loader) stream: the decoded files
+        uploaded -- or, with capture="dofp", the mosaic uploaded once and demosaiced once (shm_dofp_views: the four views in
+        ascending angle), with the diffuse image behind them, which must have the demosaiced size."""
+        if self.capture != "dofp":
+            return [staged[v][b].to(self.dev, non_blocking=True) for v in range(nsrc)]
+        srcs = list(ops.dofp_views(staged[0][b].to(self.dev, non_blocking=True), self.dofp, self.dofp_demosaic))
+        if nsrc == 5:
+            if tuple(staged[1][b].shape) != tuple(srcs[0].shape):
+                raise ValueError("the demosaiced views and the diffuse image of a sample must have the same size: "
+                                 f"{paths[0][b]} {srcs[0].shape[0]}x{srcs[0].shape[1]} ({self.dofp_demosaic}), "
+                                 f"{paths[1][b]} {staged[1][b].shape[0]}x{staged[1][b].shape[1]}")
+            srcs.append(staged[1][b].to(self.dev, non_blocking=True))
+        return srcs
 
     @staticmethod
     def _same_size(staged, paths, b):
@@ -264,14 +327,13 @@ class PolarDataset:
             return self._prepare_augmented(index, gen, pass_index)
         if self.diffuse_source != "dir":
             return self._prepare_estimated(index, gen, pass_index)
-        staged, _, _ = self._stage(index, gen, pass_index, 5)
+        staged, paths, _ = self._stage(index, gen, pass_index, 5)
         with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
             # allocated, filled and consumed on the loader stream: the caching allocator hands a block back to loader-stream
             # allocations only, which are ordered behind the resize kernel that read it
             outs = [torch.empty((self.B, self.H, self.W, 3), device=self.dev) for _ in range(5)]
-            for v in range(5):
-                for b in range(self.B):
-                    src = staged[v][b].to(self.dev, non_blocking=True)
+            for b in range(self.B):
+                for v, src in enumerate(self._sources(staged, paths, b, 5)):
                     ops.resize_bilinear_u8(src, outs[v][b], 1.0 / 255.0, self.flip_ud)
             ev = torch.cuda.Event()
             ev.record(self.stream)
@@ -282,12 +344,13 @@ class PolarDataset:
         """_prepare_worker for diffuse_source "min" / "stokes": 4 B decodes and uploads, then one shm_polar_views_u8 per sample
         writes that sample's slice of all five tensors."""
         staged, paths, _ = self._stage(index, gen, pass_index, 4)
-        for b in range(self.B):
-            self._same_size(staged, paths, b)
+        if self.capture == "views":          # a mosaic's four views have one size by construction
+            for b in range(self.B):
+                self._same_size(staged, paths, b)
         with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
             outs = [torch.empty((self.B, self.H, self.W, 3), device=self.dev) for _ in range(5)]       # on the loader stream, as above
             for b in range(self.B):
-                srcs = [staged[v][b].to(self.dev, non_blocking=True) for v in range(4)]
+                srcs = self._sources(staged, paths, b, 4)
                 ops.polar_views_u8(srcs, [outs[v][b] for v in range(5)], self.diffuse_source, self.coef, 1.0 / 255.0, self.flip_ud)
             ev = torch.cuda.Event()
             ev.record(self.stream)
@@ -301,15 +364,16 @@ class PolarDataset:
         kernel's 4x4 mix."""
         nsrc = 5 if self.diffuse_source == "dir" else 4
         staged, paths, pos = self._stage(index, gen, pass_index, nsrc)
-        for b in range(self.B):
-            self._same_size(staged, paths, b)
+        if self.capture == "views":          # a mosaic: _sources compares the diffuse image with the demosaiced size
+            for b in range(self.B):
+                self._same_size(staged, paths, b)
         kind, how = self._mirror
         with torch.cuda.device(self.dev), torch.cuda.stream(self.stream):
             outs = [torch.empty((self.B, self.H, self.W, 3), device=self.dev) for _ in range(5)]       # on the loader stream, as above
             for b in range(self.B):
-                hin, win = staged[0][b].shape[:2]
+                srcs = self._sources(staged, paths, b, nsrc)
+                hin, win = srcs[0].shape[:2]
                 p = augment_params(self.seed, pass_index, pos[b], hin, win, self.augment)
-                srcs = [staged[v][b].to(self.dev, non_blocking=True) for v in range(nsrc)]
                 dsts = [outs[v][b] for v in range(5)]
                 if p.remap and kind == "permute":     # mirrored view i is view how[i]: source how[i] lands in plane i
                     dsts = [dsts[how.index(v)] for v in range(4)] + dsts[4:]
@@ -354,9 +418,12 @@ class PolarDataset:
                 if e is not None:
                     ptrs, hin, win = e.ptrs, e.hin, e.win
                 else:
-                    paths = [[self.files[v][p]] for v in range(nsrc)]
-                    staged = [[self._decode(paths[v][0], (gen, v, b))] for v in range(nsrc)]
-                    self._same_size(staged, paths, 0)
+                    paths = [[self.files[f][p]] for f in range(self._nfiles(nsrc))]
+                    staged = [[a] for a in self._decode_files([q[0] for q in paths], gen, b)]
+                    if self.capture == "dofp":          # the cache holds the DEMOSAICED views: one demosaic per sample per run
+                        staged = [[a] for a in self._sources(staged, paths, 0, nsrc)]
+                    else:
+                        self._same_size(staged, paths, 0)
                     hin, win = staged[0][0].shape[:2]
                     e = arena.store(p, nsrc, hin, win)
                     if e is not None:
@@ -437,7 +504,8 @@ def held_out_options(options):
 
 
 def validation_loader(data_dir, image_size, batch_size, *, val_dir="", val_fraction=0.0, val_seed=0, val_batch_size=None, subdirs=PSD_SUBDIRS,
-                      flip_ud=True, device=None, diffuse_source="dir", angles=None, cache="none", cache_bytes=None):
+                      flip_ud=True, device=None, diffuse_source="dir", angles=None, cache="none", cache_bytes=None, capture="views", dofp=None,
+                      dofp_demosaic="bilinear"):
     """The held-out loader of `train()` from plain options (no trainer, no GPU needed to build it), or None with both sources off:
     `val_dir` = a directory laid out like data_dir, `val_fraction` = that part of data_dir (split_indices with val_seed; datasetLoad
     then trains on the rest).  Giving both raises ValueError.  The other options are the training loader's (held_out_options says what a
@@ -450,7 +518,8 @@ def validation_loader(data_dir, image_size, batch_size, *, val_dir="", val_fract
     if B < 1:
         raise ValueError(f"val_batch_size {val_batch_size!r} < 1")
     opts = held_out_options(dict(image_size=image_size, batch_size=B, subdirs=tuple(subdirs), flip_ud=flip_ud, device=device,
-                                 diffuse_source=diffuse_source, angles=angles, seed=0, cache=cache, cache_bytes=cache_bytes))
+                                 diffuse_source=diffuse_source, angles=angles, seed=0, cache=cache, cache_bytes=cache_bytes,
+                                 capture=capture, dofp=dofp, dofp_demosaic=dofp_demosaic))
     if val_dir:
         return PolarDataset(val_dir, **opts)
     _, val = split_indices(list_images(os.path.join(data_dir, tuple(subdirs)[0])), val_fraction, val_seed)
@@ -464,6 +533,33 @@ def trainer_frame(trainer):
     return frame() if callable(frame) else trainer.image_size
 
 
+CAPTURE_OPTIONS = ("capture_format", "dofp_dir", "dofp_pattern", "dofp_quad_angles", "dofp_bits", "dofp_demosaic")
+
+
+def capture_options(args, subdirs=PSD_SUBDIRS):
+    """The capture options of a trainer's `args` as (subdirs, loader keywords): capture_format "views" (default: `subdirs` and
+    today's loader) or "dofp" = a polariser-mosaic sensor, whose frames lie in dofp_dir ("DOFP") next to the diffuse directory
+    (the last of `subdirs`) and are laid out as polar.DofpLayout(dofp_pattern, dofp_quad_angles, dofp_bits) says; dofp_demosaic
+    "bilinear" / "bin".  An unknown value raises ValueError naming the option, before anything is listed or allocated."""
+    from . import polar
+    opt = lambda k, dflt: getattr(args, k, dflt)
+    capture, demosaic = opt("capture_format", "views"), opt("dofp_demosaic", "bilinear")
+    if capture not in polar.CAPTURES:
+        raise ValueError(f"capture_format {capture!r} is not one of {polar.CAPTURES}")
+    if demosaic not in polar.DOFP_DEMOSAIC:
+        raise ValueError(f"dofp_demosaic {demosaic!r} is not one of {polar.DOFP_DEMOSAIC}")
+    if capture == "views":
+        return tuple(subdirs), dict(capture="views", dofp=None, dofp_demosaic=demosaic)
+    try:
+        layout = polar.DofpLayout(opt("dofp_pattern", "mono"), opt("dofp_quad_angles", (90, 45, 135, 0)), opt("dofp_bits", 8))
+    except ValueError as e:
+        raise ValueError(str(e).replace("DofpLayout: ", "dofp_", 1)) from None
+    dofp_dir = opt("dofp_dir", "DOFP")
+    if not isinstance(dofp_dir, str) or not dofp_dir:
+        raise ValueError(f"dofp_dir {dofp_dir!r} is not a directory name")
+    return (dofp_dir, tuple(subdirs)[-1]), dict(capture="dofp", dofp=layout, dofp_demosaic=demosaic)
+
+
 def datasetLoad(trainer, subdirs=PSD_SUBDIRS, flip_ud=True):
     """Reference signature (datasetLoader.py:19): returns (length_dataset, loadedDataset) and sets the same
     attributes on the trainer object.  The trainer's `diffuse_source` option (default "dir") goes to PolarDataset; it is NOT
@@ -471,13 +567,15 @@ def datasetLoad(trainer, subdirs=PSD_SUBDIRS, flip_ud=True):
     and `aug_flip_lr` / `aug_flip_ud` / `aug_crop_min` / `aug_views` become the loader's shuffle, seed and Augment; `cache` ("none" /
     "device") and `cache_gb` (GiB of device memory the cache may take; None = half of what is free) its cache and cache_bytes.
     `val_dir` / `val_fraction` (with `val_seed`, `val_batch_size`) set trainer.valDataset (validation_loader; None when both are off);
-    with `val_fraction` the returned loader and length are those of the training part."""
+    with `val_fraction` the returned loader and length are those of the training part.  `capture_format` = "dofp" with `dofp_dir`,
+    `dofp_pattern`, `dofp_quad_angles`, `dofp_bits` and `dofp_demosaic` (capture_options) reads a polariser-mosaic capture instead."""
     opt = lambda k, dflt: getattr(trainer.args, k, dflt)
+    subdirs, capture = capture_options(trainer.args, subdirs)
     draws = (float(opt("aug_flip_lr", 0.0)), float(opt("aug_flip_ud", 0.0)), float(opt("aug_crop_min", 1.0)))
     # no augmentation asked for: the loader's default path, not the augmenting kernel at identity parameters
     augment = Augment(*draws, views=opt("aug_views", "physical")) if draws != (0.0, 0.0, 1.0) else None
     cache = dict(cache=opt("cache", "none"), cache_bytes=gib_to_bytes(opt("cache_gb", None)))
-    source = dict(diffuse_source=getattr(trainer.args, "diffuse_source", "dir"))
+    source = dict(capture, diffuse_source=getattr(trainer.args, "diffuse_source", "dir"))
     # held-out validation (`val_dir` / `val_fraction`, both off by default): the loader train() validates on, and with val_fraction
     # the training loader is the rest of data_dir
     val_dir, val_fraction, val_seed = opt("val_dir", ""), float(opt("val_fraction", 0.0) or 0.0), int(opt("val_seed", 0))
@@ -546,7 +644,7 @@ class MaskDataset:
 
     @classmethod
     def from_polar(cls, data_dir, image_size, batch_size=1, subdirs=PSD_SUBDIRS, angles=None, flip_ud=False, device=None, augment=None,
-                   shuffle=False, seed=0, cache_bytes=None, **mask_options):
+                   shuffle=False, seed=0, cache_bytes=None, capture="views", dofp=None, dofp_demosaic="bilinear", **mask_options):
         """The same (x, y) tensors from a raw four-directory capture, without a mask anybody drew and without the PNG round trip:
         the image of sample i is its view subdirs[2] (the one whose Y plane train_step feeds SpecSeg.predict), the mask is
         polar.specular_mask of its four views (`angles`, or those read from the directory names; `mask_options` = threshold, floor,
@@ -555,20 +653,25 @@ class MaskDataset:
         Same refusals as write_specular_masks: four directories, equal counts, equal sizes.
         augment / shuffle / seed / cache_bytes as the directory form.  The mask is mirror-invariant (S2 only changes sign), but the
         image is view 2: with augment.views == "physical" and a mirror probability above zero, the angles must be such that a
-        mirror leaves view 2 in place (polar.mirror_keeps_view: true for 0/45/90/135 and 0/60/90/150), else ValueError."""
+        mirror leaves view 2 in place (polar.mirror_keeps_view: true for 0/45/90/135 and 0/60/90/150), else ValueError.
+        capture="dofp" (with dofp = a polar.DofpLayout and dofp_demosaic): the first of `subdirs` holds one polariser mosaic per
+        sample; its four demosaiced views (polar.sample_views, in ascending angle) take the place of the four files, the angles
+        default to the layout's and the names are the mosaics' stems."""
         from . import polar
+        polar.check_capture(capture, dofp, dofp_demosaic, "MaskDataset.from_polar")
         bad = sorted(set(mask_options) - set(polar.MASK_OPTIONS))
         if bad:
             raise TypeError(f"MaskDataset.from_polar: unknown option(s) {bad}; polar.specular_mask takes {polar.MASK_OPTIONS}")
-        views, files = polar.polar_sample_files(data_dir, subdirs, "MaskDataset.from_polar")
+        views, files = polar.polar_sample_files(data_dir, subdirs, "MaskDataset.from_polar", capture)
         if not files[0]:
             raise ValueError(f"{data_dir}: the view directories {views} hold no images")
         self = cls.__new__(cls)
-        self.files = sorted(zip(*files), key=lambda paths: Path(paths[2]).stem)          # the order of the directory form: by name
-        self.names = [Path(paths[2]).stem for paths in self.files]
+        named = 2 if capture == "views" else 0          # the file a sample is named after: its image (view 2), or its mosaic
+        self.files = sorted(zip(*files), key=lambda paths: Path(paths[named]).stem)      # the order of the directory form: by name
+        self.names = [Path(paths[named]).stem for paths in self.files]
         self.S, self.B, self.flip_ud, self._dev, self._xy = int(image_size), int(batch_size), bool(flip_ud), device, None
-        ang = list(angles if angles is not None else polar.angles_from_subdirs(views))
-        self._polar = dict(coef=polar.stokes_matrix(ang), options=dict(mask_options))
+        ang = list(angles if angles is not None else dofp.angles if capture == "dofp" else polar.angles_from_subdirs(views))
+        self._polar = dict(coef=polar.stokes_matrix(ang), options=dict(mask_options), capture=(capture, dofp, dofp_demosaic))
         self._loader_options(augment, shuffle, seed, cache_bytes, ang)
         return self
 
@@ -598,7 +701,7 @@ class MaskDataset:
             fi, fm = self.files[k]
             return self._decode(fi, "RGB").to(self.dev), self._decode(fm, "L").to(self.dev)
         from . import polar
-        srcs = [torch.from_numpy(a).to(self.dev) for a in polar.decode_sample(self.files[k], k)]
+        srcs = polar.sample_views(self.files[k], k, self.dev, *self._polar["capture"])
         with torch.cuda.device(self.dev):
             mask, _, _ = polar.specular_mask(srcs, matrix=self._polar["coef"], **self._polar["options"])
         return srcs[2], mask.unsqueeze(2)
@@ -729,6 +832,45 @@ class MaskDataset:
         return self._subset(train, self.augment, self.shuffle), self._subset(val, None, False)
 
 
+DOFP_TEST_VIEWS = ("total", 0, 1, 2, 3)       # the demosaiced plane test mode reads of a mosaic: the reference feeds "I0 (or Itot)"
+
+
+class _EvalCapture:
+    """What test mode reads as a photo's decoded bytes (the capture options of EvalDataset and NativeEvalDataset): the RGB file, or
+    with capture="dofp" one plane of a polariser mosaic -- dofp_test_view "total" (the rounded mean of the four views, default) or
+    the view 0..3 in ascending angle -- which then stands wherever the decoded photo stands.  The host side (decode, size) runs on
+    the worker thread; `photo` uploads, and demosaics on the current stream."""
+
+    def __init__(self, capture, dofp, dofp_demosaic, dofp_test_view, who):
+        from . import polar
+        polar.check_capture(capture, dofp, dofp_demosaic, who)
+        if dofp_test_view not in DOFP_TEST_VIEWS or isinstance(dofp_test_view, bool):
+            raise ValueError(f"{who}: dofp_test_view {dofp_test_view!r} is not one of {DOFP_TEST_VIEWS}")
+        self.mosaic, self.dofp, self.demosaic, self.view = capture == "dofp", dofp, dofp_demosaic, dofp_test_view
+
+    def decode(self, path):
+        """(decoded array, (h, w) of the photo it stands for)."""
+        if not self.mosaic:
+            a = EvalDataset._decode(path)
+            return a, a.shape[:2]
+        from . import polar
+        a = polar.decode_mosaic(path, self.dofp)
+        return a, self.dofp.view_shape(a.shape[0], a.shape[1], self.demosaic)
+
+    def size(self, h, w):
+        """(h, w) of the photo a file of h x w pixels stands for."""
+        return self.dofp.view_shape(h, w, self.demosaic) if self.mosaic else (h, w)
+
+    def photo(self, a, dev):
+        """The uint8 [h,w,3] device image of a decoded test file."""
+        if a.ndim == 3:
+            return torch.from_numpy(a).to(dev)
+        from . import polar
+        with torch.cuda.device(dev):
+            out = polar.demosaic(a, self.dofp, self.demosaic, total=self.view == "total", device=dev)
+        return out[4 if self.view == "total" else self.view]
+
+
 def eval_file_lists(test_dir, diffuse_dir=None):
     """File lists of the evaluation loader: the sorted flat `test_dir` and, when given, the sorted flat `diffuse_dir`
     (None otherwise), paired by position.  The reference zips the two datasets (test.py:130), and tf.data's zip stops at the
@@ -752,9 +894,14 @@ class EvalDataset:
     size).  Evaluation is not sharded: rank 0 of a world of 1, whatever torch.distributed says.  The next batch is decoded
     on a worker thread while the current one is consumed; uploads and resizes run on the consumer's current stream.
     keep_source=True leaves the last batch's decoded bytes on the device in `last_source` (the full-resolution output of
-    evaluate.test reads the photos there); what the iterator yields is the same either way."""
+    evaluate.test reads the photos there); what the iterator yields is the same either way.
+    capture="dofp" (with dofp = a polar.DofpLayout, dofp_demosaic, dofp_test_view = "total" | 0..3): test_dir holds polariser
+    mosaics, and the chosen demosaiced plane (_EvalCapture) stands wherever the decoded photo stands: the resize, the sizes of
+    sources() and last_source."""
 
-    def __init__(self, test_dir, image_size, batch_size=1, diffuse_dir=None, device=None, keep_source=False):
+    def __init__(self, test_dir, image_size, batch_size=1, diffuse_dir=None, device=None, keep_source=False, capture="views", dofp=None,
+                 dofp_demosaic="bilinear", dofp_test_view="total"):
+        self._capture = _EvalCapture(capture, dofp, dofp_demosaic, dofp_test_view, "EvalDataset")
         if batch_size < 1:
             raise ValueError(f"batch_size {batch_size} < 1")
         self.H, self.W = frame_hw(image_size)                # image_size: a side, or a pair (H, W)
@@ -791,16 +938,17 @@ class EvalDataset:
 
     def _decode_batch(self, index):
         lo, hi = self.batch_range(index)
-        test = [self._decode(p) for p in self.test_files[lo:hi]]
-        for i, a in enumerate(test):
-            self._sizes[lo + i] = a.shape[:2]
+        test = []
+        for i, p in enumerate(self.test_files[lo:hi]):
+            a, self._sizes[lo + i] = self._capture.decode(p)
+            test.append(a)
         diffuse = None if self.diffuse_files is None else [self._decode(p) for p in self.diffuse_files[lo:hi]]
         return test, diffuse
 
     def _upload(self, decoded, kept=None):
         out = torch.empty((len(decoded), self.H, self.W, 3), dtype=torch.float32, device=self.dev)
         for b, a in enumerate(decoded):
-            src = torch.from_numpy(a).to(self.dev)
+            src = self._capture.photo(a, self.dev)
             if kept is not None:
                 kept.append(src)
             ops.resize_bilinear_u8(src, out[b], 1.0 / 255.0, False)
@@ -815,7 +963,7 @@ class EvalDataset:
             if i not in self._sizes:
                 from PIL import Image
                 with Image.open(self.test_files[i]) as im:
-                    self._sizes[i] = (im.size[1], im.size[0])
+                    self._sizes[i] = self._capture.size(im.size[1], im.size[0])
             out.append((self.test_files[i], tuple(int(v) for v in self._sizes[i])))
         return out
 
@@ -862,9 +1010,12 @@ class NativeEvalDataset:
     decode (PIL on a worker thread, one image ahead); the frame is ONE shm_load_pad_u8 call on the decoded bytes (pad_geometry),
     the diffuse target is uploaded tight (the same call without a pad).  Batch size is 1: sizes differ per image.
     check(path, h, w): called after the decode and before anything is allocated or launched for the image (evaluate.test refuses
-    images over its limits there).  A diffuse partner of another size than its test image raises ValueError naming both files."""
+    images over its limits there).  A diffuse partner of another size than its test image raises ValueError naming both files.
+    capture="dofp": as EvalDataset; the photo's size, the one the diffuse partner must have, is the demosaiced plane's."""
 
-    def __init__(self, test_dir, diffuse_dir=None, device=None, check=None):
+    def __init__(self, test_dir, diffuse_dir=None, device=None, check=None, capture="views", dofp=None, dofp_demosaic="bilinear",
+                 dofp_test_view="total"):
+        self._capture = _EvalCapture(capture, dofp, dofp_demosaic, dofp_test_view, "NativeEvalDataset")
         self.B = 1
         self.test_files, self.diffuse_files = eval_file_lists(test_dir, diffuse_dir)
         self.n = len(self.test_files)
@@ -883,8 +1034,7 @@ class NativeEvalDataset:
         return index, index + 1
 
     def _decode_pair(self, index):
-        test = self._decode(self.test_files[index])
-        self._sizes[index] = test.shape[:2]
+        test, self._sizes[index] = self._capture.decode(self.test_files[index])
         diffuse = None if self.diffuse_files is None else self._decode(self.diffuse_files[index])
         return test, diffuse
 
@@ -893,17 +1043,17 @@ class NativeEvalDataset:
         if index not in self._sizes:
             from PIL import Image
             with Image.open(self.test_files[index]) as im:
-                self._sizes[index] = (im.size[1], im.size[0])
+                self._sizes[index] = self._capture.size(im.size[1], im.size[0])
         return [(self.test_files[index], tuple(int(v) for v in self._sizes[index]))]
 
     def _upload(self, a, hp, wp, top, left):
         out = torch.empty((1, hp, wp, 3), dtype=torch.float32, device=self.dev)
-        ops.load_pad_u8(torch.from_numpy(a).to(self.dev), out[0], top, left, 1.0 / 255.0)
+        ops.load_pad_u8(self._capture.photo(a, self.dev), out[0], top, left, 1.0 / 255.0)
         return out
 
     def batch(self, index, decoded=None):
         test, diffuse = decoded if decoded is not None else self._decode_pair(index)
-        h, w = (int(v) for v in test.shape[:2])
+        h, w = (int(v) for v in self._capture.size(*test.shape[:2]))
         if diffuse is not None and tuple(diffuse.shape[:2]) != (h, w):
             raise ValueError(f"native-resolution evaluation compares a test image with its diffuse partner pixel by pixel: "
                              f"{self.test_files[index]} is {h} x {w}, {self.diffuse_files[index]} is {diffuse.shape[0]} x {diffuse.shape[1]}")

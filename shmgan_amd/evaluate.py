@@ -70,11 +70,12 @@ import pickle
 import time
 import warnings
 from concurrent.futures import ThreadPoolExecutor
+from types import SimpleNamespace
 
 import torch
 
 from . import ops
-from .data import EvalDataset, NativeEvalDataset, pad_geometry, trainer_frame
+from .data import CAPTURE_OPTIONS, EvalDataset, NativeEvalDataset, capture_options, pad_geometry, trainer_frame
 from .model import Arena, generator_layers, pad_channels
 from .specseg import WIDTHS as SPECSEG_WIDTHS
 from .telemetry import nan_to_none, region_means, region_options, write_lines
@@ -449,10 +450,13 @@ def test(shmgan, args, *, print_fn=print):
         check_native_limits(path, h, w, shmgan.filter_size, shmgan.compute_dtype, cyclic, shmgan.attention == "live",
                             free_bytes=free + cached + held)
 
+    # a polariser-mosaic test set (capture_format="dofp"): test_dir holds mosaics, dofp_test_view says which demosaiced plane is the photo
+    _, capture = capture_options(SimpleNamespace(**{k: v for k in CAPTURE_OPTIONS if (v := _arg(shmgan, args, k)) is not None}))
+    capture["dofp_test_view"] = _arg(shmgan, args, "dofp_test_view", "total")
     if native:
-        dataset = NativeEvalDataset(test_dir, diffuse_dir, shmgan.device, check=check)
+        dataset = NativeEvalDataset(test_dir, diffuse_dir, shmgan.device, check=check, **capture)
     else:
-        dataset = EvalDataset(test_dir, trainer_frame(shmgan), B, diffuse_dir, shmgan.device, keep_source=detail is not None)
+        dataset = EvalDataset(test_dir, trainer_frame(shmgan), B, diffuse_dir, shmgan.device, keep_source=detail is not None, **capture)
     if tags:
         check_stems(dataset.test_files)
     shmgan.number_of_test_images = dataset.n                                   # test.py:123

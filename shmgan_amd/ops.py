@@ -1394,6 +1394,54 @@ def polar_maps(views, coef, want=("s0", "dop", "aolp")):
     return out
 
 
+# ---- polariser-mosaic (DoFP) sensors: one raw frame -> the four views (dofp.hip) -----------------------------
+DOFP_PATTERNS = {n: CONSTANTS["SHM_DOFP_" + n.upper()] for n in ("mono", "rggb", "bggr", "grbg", "gbrg")}
+DOFP_MODES = {"bilinear": CONSTANTS["SHM_DOFP_BILINEAR"], "bin": CONSTANTS["SHM_DOFP_BIN"]}
+
+
+def dofp_period(pattern):
+    """The mosaic's period P: 2 for "mono", 4 for the Bayer patterns."""
+    if pattern not in DOFP_PATTERNS:
+        raise ValueError(f"dofp: pattern {pattern!r} is not one of {tuple(DOFP_PATTERNS)}")
+    return 2 if pattern == "mono" else 4
+
+
+def dofp_shape(h, w, pattern, mode):
+    """(ho, wo) of the views shm_dofp_views makes of an [h,w] mosaic: the mosaic's size for "bilinear", (h // P, w // P) for "bin"."""
+    if mode not in DOFP_MODES:
+        raise ValueError(f"dofp: mode {mode!r} is not one of {tuple(DOFP_MODES)}")
+    P = dofp_period(pattern)
+    return (int(h), int(w)) if mode == "bilinear" else (int(h) // P, int(w) // P)
+
+
+def dofp_views(mosaic, layout, mode="bilinear", total=False):
+    """One polariser-mosaic frame -> its four views in one launch (shm_dofp_views, include/shmgan_hip.h, states the arithmetic).
+    mosaic: a uint8 or uint16 2-D device tensor with unit stride along a row; its stride 0 is the pitch.  layout: a
+    polar.DofpLayout (anything with .pattern, .quad and .bits); a uint8 mosaic needs bits == 8, a uint16 one bits 9..16.  Returns
+    four new uint8 [ho,wo,3] tensors in ascending polariser angle, and with `total` a fifth: the rounded mean of the four.
+    Asynchronous on the current stream."""
+    import ctypes as C
+    if not isinstance(mosaic, torch.Tensor) or not mosaic.is_cuda or mosaic.dtype not in (torch.uint8, torch.uint16):
+        raise TypeError(f"dofp_views takes a uint8 or uint16 device tensor, got {getattr(mosaic, 'dtype', type(mosaic))} on "
+                        f"{getattr(mosaic, 'device', 'the host')}")
+    if mosaic.dim() != 2 or (mosaic.shape[1] > 1 and mosaic.stride(1) != 1):
+        raise ValueError(f"dofp_views takes a 2-D mosaic with unit stride along a row, got {tuple(mosaic.shape)} with strides {mosaic.stride()}")
+    bits = int(layout.bits)
+    if (mosaic.dtype == torch.uint8) != (bits == 8):
+        raise ValueError(f"dofp_views: a {mosaic.dtype} mosaic does not hold {bits}-bit samples (uint8 is bits = 8, uint16 is bits 9..16)")
+    h, w = (int(d) for d in mosaic.shape)
+    ho, wo = dofp_shape(h, w, layout.pattern, mode)
+    if ho < 1 or wo < 1:
+        raise ValueError(f"dofp_views: a {h} x {w} mosaic is smaller than one period of pattern {layout.pattern!r}")
+    out = torch.empty((5 if total else 4, ho, wo, 3), dtype=torch.uint8, device=mosaic.device)
+    quad = (C.c_int * 4)(*[int(q) for q in layout.quad])
+    dp = (C.c_void_p * 4)(*[out[v].data_ptr() for v in range(4)])
+    pitch = int(mosaic.stride(0)) if h > 1 else w
+    check(lib().shm_dofp_views(mosaic.data_ptr(), bits, h, w, pitch, DOFP_PATTERNS[layout.pattern], quad, DOFP_MODES[mode], dp,
+                               out[4].data_ptr() if total else None, _stream()), "shm_dofp_views")
+    return tuple(out[v] for v in range(out.shape[0]))
+
+
 # ---- specular masks from the polarised views (specmask.hip) -------------------------------------------
 SPECMASK_MAX_OPEN, SPECMASK_MAX_DILATE = CONSTANTS["SHM_SPECMASK_MAX_OPEN"], CONSTANTS["SHM_SPECMASK_MAX_DILATE"]
 

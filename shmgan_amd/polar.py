@@ -10,7 +10,11 @@ The same fit gives a label the capture already contains: the polarised intensity
 `specular_mask` / `write_specular_masks` (csrc/specmask.hip) threshold it into the highlight masks SpecSeg is trained on
 (data.MaskDataset.from_polar, trainer.train_specseg with specseg_mask_source="polar").
 
-Importing this module needs no GPU; `polar_maps`, `specular_mask`, `write_estimated_diffuse` and `write_specular_masks` run on one.
+A polariser-mosaic sensor records the four views in one raw frame: `DofpLayout` describes such a sensor, `decode_mosaic` reads a frame
+file, `demosaic` (csrc/dofp.hip) splits it into the four views in ascending angle, and `sample_views` is the one place where "a sample's
+files" become "its four uint8 device views" for either kind of capture.
+
+Importing this module needs no GPU; `polar_maps`, `specular_mask`, `demosaic`, `write_estimated_diffuse` and `write_specular_masks` run on one.
 
 Model: a linear polariser at angle theta in front of light with Stokes parameters (S0, S1, S2) passes
     I(theta) = 0.5 * (S0 + S1 cos 2 theta + S2 sin 2 theta)
@@ -21,6 +25,7 @@ from __future__ import annotations
 
 import os
 import re
+from dataclasses import dataclass
 from pathlib import Path
 
 import numpy as np
@@ -127,6 +132,108 @@ def _decode(path):
         return np.array(im.convert("RGB"), dtype=np.uint8)
 
 
+# ---- polariser-mosaic (division-of-focal-plane) sensors: one raw frame per sample (csrc/dofp.hip) ----------
+DOFP_PATTERNS = ("mono", "rggb", "bggr", "grbg", "gbrg")       # no colour filter, or the Bayer tile that lies over the 2 x 2 quads
+DOFP_DEMOSAIC = ("bilinear", "bin")                            # views at the mosaic's size / one pixel per super-pixel
+CAPTURES = ("views", "dofp")                                   # one file per polariser angle / one mosaic per sample
+
+
+@dataclass(frozen=True)
+class DofpLayout:
+    """How a polariser-mosaic sensor lays its samples out.  pattern: "mono", or the Bayer tile over the quads ("rggb", "bggr",
+    "grbg", "gbrg": period 4).  quad_angles: the micro-polariser angles in degrees at quad positions (0,0), (0,1), (1,0), (1,1); Sony's
+    IMX250MZR / MYR is (90, 45, 135, 0).  bits: the significant bits of a sample, LSB-aligned, 8..16 (8 = a uint8 mosaic; a
+    12-bit value stored in 16 bits is 12, an MSB-aligned 16-bit file is 16).
+    Views are always delivered in ASCENDING angle (`angles`), whatever the quad's order, so stokes_matrix(layout.angles) and the
+    exact 45 / 135 exchange of mirror_views apply as they are; `quad` is the kernel's table, the view index at each quad position."""
+    pattern: str = "mono"
+    quad_angles: tuple = (90, 45, 135, 0)
+    bits: int = 8
+
+    def __post_init__(self):
+        if self.pattern not in DOFP_PATTERNS:
+            raise ValueError(f"DofpLayout: pattern {self.pattern!r} is not one of {DOFP_PATTERNS}")
+        try:
+            ang = tuple(float(a) for a in self.quad_angles)
+        except (TypeError, ValueError):
+            raise ValueError(f"DofpLayout: quad_angles {self.quad_angles!r} are not four angles in degrees") from None
+        if len(ang) != 4 or not all(np.isfinite(a) for a in ang):
+            raise ValueError(f"DofpLayout: quad_angles {self.quad_angles!r} are not four angles in degrees")
+        mod = sorted(a % 180.0 for a in ang)
+        if any(min(b - a, 180.0 - (b - a)) < 1e-9 for i, a in enumerate(mod) for b in mod[i + 1:]):
+            raise ValueError(f"DofpLayout: quad_angles {self.quad_angles!r} are not distinct modulo 180 degrees")
+        if isinstance(self.bits, bool) or not isinstance(self.bits, (int, np.integer)) or not 8 <= int(self.bits) <= 16:
+            raise ValueError(f"DofpLayout: bits {self.bits!r} is not an integer in 8..16")
+        object.__setattr__(self, "quad_angles", ang)
+        object.__setattr__(self, "bits", int(self.bits))
+
+    @property
+    def angles(self):
+        """The four angles in ascending order: the order of the delivered views."""
+        return sorted(self.quad_angles)
+
+    @property
+    def quad(self):
+        """View index (into `angles`) at quad positions (0,0), (0,1), (1,0), (1,1): (2, 1, 3, 0) for Sony's layout."""
+        order = self.angles
+        return tuple(order.index(a) for a in self.quad_angles)
+
+    @property
+    def period(self):
+        return 2 if self.pattern == "mono" else 4
+
+    def view_shape(self, h, w, mode="bilinear"):
+        """(ho, wo) of the views of an [h,w] mosaic."""
+        if mode not in DOFP_DEMOSAIC:
+            raise ValueError(f"dofp_demosaic {mode!r} is not one of {DOFP_DEMOSAIC}")
+        return (int(h), int(w)) if mode == "bilinear" else (int(h) // self.period, int(w) // self.period)
+
+
+def check_capture(capture, dofp, dofp_demosaic="bilinear", who="PolarDataset"):
+    """The refusals every entry point that takes the capture options shares, by name and before anything is listed or allocated."""
+    if capture not in CAPTURES:
+        raise ValueError(f"{who}: capture {capture!r} is not one of {CAPTURES}")
+    if dofp_demosaic not in DOFP_DEMOSAIC:
+        raise ValueError(f"{who}: dofp_demosaic {dofp_demosaic!r} is not one of {DOFP_DEMOSAIC}")
+    if capture == "dofp" and not isinstance(dofp, DofpLayout):
+        raise ValueError(f"{who}: capture 'dofp' needs dofp=polar.DofpLayout(...), got {dofp!r}")
+    if capture == "views" and dofp is not None and not isinstance(dofp, DofpLayout):
+        raise ValueError(f"{who}: dofp must be a polar.DofpLayout or None, got {dofp!r}")
+
+
+def decode_mosaic(path, layout):
+    """One raw mosaic file as a 2-D array: PIL mode "L" gives uint8 and needs layout.bits == 8; "I;16" / "I;16B" give uint16 (native
+    byte order) and need bits 9..16.  Anything else -- an RGB file is not a mosaic -- raises ValueError naming the file and its mode."""
+    from PIL import Image
+    with Image.open(path) as im:
+        mode = im.mode
+        if mode == "L":
+            a = np.array(im, dtype=np.uint8)
+        elif mode in ("I;16", "I;16B", "I;16L"):
+            a = np.ascontiguousarray(np.array(im).astype(np.uint16, copy=False))
+        else:
+            raise ValueError(f"{path} is not a polariser mosaic: PIL mode {mode!r} (a mosaic is one channel: 'L' for 8 bits, 'I;16' for 9..16)")
+    if (a.dtype == np.uint8) != (layout.bits == 8):
+        raise ValueError(f"{path} holds {8 * a.dtype.itemsize}-bit samples (PIL mode {mode!r}), the layout says bits = {layout.bits}")
+    return a
+
+
+def demosaic(mosaic, layout, mode="bilinear", total=False, device=None):
+    """The four views (and with `total` their rounded mean) of one mosaic: ops.dofp_views.  mosaic: a uint8 / uint16 2-D device
+    tensor, or a NumPy array, which is uploaded first (to `device`, default the current one).  Returns uint8 [ho,wo,3] device
+    tensors in ascending polariser angle (layout.angles).  Asynchronous on the current stream."""
+    import torch
+    from . import ops
+    if not isinstance(layout, DofpLayout):
+        raise ValueError(f"demosaic: layout must be a polar.DofpLayout, got {layout!r}")
+    if isinstance(mosaic, np.ndarray):
+        if mosaic.dtype not in (np.uint8, np.uint16) or mosaic.ndim != 2:
+            raise ValueError(f"demosaic takes a 2-D uint8 or uint16 mosaic, got {mosaic.dtype} {mosaic.shape}")
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        mosaic = torch.from_numpy(np.ascontiguousarray(mosaic)).to(dev)
+    return ops.dofp_views(mosaic, layout, mode, total)
+
+
 MASK_OPTIONS = ("threshold", "floor", "open_radius", "dilate_radius")       # the keyword options of specular_mask
 
 
@@ -172,9 +279,14 @@ def specular_mask(views_u8, angles=None, *, matrix=None, threshold="otsu", floor
     return mask, q, stats
 
 
-def polar_sample_files(data_dir, subdirs, who):
+def polar_sample_files(data_dir, subdirs, who, capture="views"):
     """The sorted file lists of the first four `subdirs` of `data_dir`, with the refusals of write_estimated_diffuse: four
-    directories, equal counts."""
+    directories, equal counts.  capture="dofp": the one list of the first of `subdirs`, which holds a mosaic per sample."""
+    if capture == "dofp":
+        views = tuple(subdirs)[:1]
+        if len(views) != 1:
+            raise ValueError(f"{who} needs the mosaic directory as the first of subdirs, got {tuple(subdirs)}")
+        return views, [list_images(os.path.join(data_dir, views[0]))]
     views = tuple(subdirs)[:4]
     if len(views) != 4:
         raise ValueError(f"{who} needs four view directories, got {views}")
@@ -192,7 +304,25 @@ def decode_sample(paths, index):
     return imgs
 
 
-def write_specular_masks(data_dir, out_dir, subdirs=PSD_SUBDIRS, angles=None, name_from=2, device=None, **mask_options):
+def sample_views(paths, index, dev, capture="views", dofp=None, dofp_demosaic="bilinear"):
+    """The four uint8 [h,w,3] device views of one sample: its four files decoded and uploaded (decode_sample), or with
+    capture="dofp" its one mosaic decoded once, uploaded once and demosaiced once on the current stream."""
+    import torch
+    if capture == "dofp":
+        with torch.cuda.device(dev):
+            return list(demosaic(decode_mosaic(paths[0], dofp), dofp, dofp_demosaic, device=dev))
+    return [torch.from_numpy(a).to(dev) for a in decode_sample(paths, index)]
+
+
+def _view_angles(angles, views, capture, dofp):
+    """The polariser angles of the four delivered views: `angles` when given, the layout's for a mosaic, else the directory names'."""
+    if angles is not None:
+        return angles
+    return dofp.angles if capture == "dofp" else angles_from_subdirs(views)
+
+
+def write_specular_masks(data_dir, out_dir, subdirs=PSD_SUBDIRS, angles=None, name_from=2, device=None, capture="views", dofp=None,
+                         dofp_demosaic="bilinear", **mask_options):
     """Materialise the specular mask of every sample as a one-channel PNG (0 / 255) at the sample's own size: the sibling of
     write_estimated_diffuse.  The first four `subdirs` of `data_dir` are listed as the loader lists them; sample i's mask is
     specular_mask of its four views (`angles`, or the angles read from the directory names; `mask_options` = its threshold, floor,
@@ -200,7 +330,9 @@ def write_specular_masks(data_dir, out_dir, subdirs=PSD_SUBDIRS, angles=None, na
     one whose Y plane train_step feeds SpecSeg.predict, so that train_specseg(specseg_image_dir=<data_dir>/I90,
     specseg_mask_dir=out_dir) pairs them as they are.  `out_dir`/masks.jsonl gets one line per sample: name, t (Otsu's), t_eff
     (applied), fraction (of the frame that is masked) -- samples whose mask is empty or covers most of the frame show there.
-    Same refusals as write_estimated_diffuse: four directories, equal counts, equal sizes.  Returns the list of PNG files written."""
+    Same refusals as write_estimated_diffuse: four directories, equal counts, equal sizes.  capture="dofp" (with dofp = a DofpLayout
+    and dofp_demosaic): the first of `subdirs` holds one polariser mosaic per sample, the four views are its demosaiced planes
+    (sample_views), the angles default to the layout's and the mask is named after the mosaic.  Returns the list of PNG files written."""
     import json
     import torch
     from PIL import Image
@@ -209,18 +341,18 @@ def write_specular_masks(data_dir, out_dir, subdirs=PSD_SUBDIRS, angles=None, na
         raise TypeError(f"write_specular_masks: unknown option(s) {bad}; specular_mask takes {MASK_OPTIONS}")
     if name_from not in (0, 1, 2, 3):
         raise ValueError(f"write_specular_masks: name_from {name_from!r} is not a view index 0..3")
-    views, files = polar_sample_files(data_dir, subdirs, "write_specular_masks")
-    coef = stokes_matrix(angles if angles is not None else angles_from_subdirs(views))
+    check_capture(capture, dofp, dofp_demosaic, "write_specular_masks")
+    views, files = polar_sample_files(data_dir, subdirs, "write_specular_masks", capture)
+    coef = stokes_matrix(_view_angles(angles, views, capture, dofp))
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     os.makedirs(out_dir, exist_ok=True)
     written, rows = [], []
     for i in range(len(files[0])):
         paths = [f[i] for f in files]
-        imgs = decode_sample(paths, i)
         with torch.cuda.device(dev):
-            mask, _, stats = specular_mask([torch.from_numpy(a).to(dev) for a in imgs], matrix=coef, **mask_options)
+            mask, _, stats = specular_mask(sample_views(paths, i, dev, capture, dofp, dofp_demosaic), matrix=coef, **mask_options)
         m, st = mask.cpu().numpy(), stats.cpu().numpy()
-        name = Path(paths[name_from]).stem
+        name = Path(paths[name_from if capture == "views" else 0]).stem
         out = os.path.join(out_dir, name + ".png")
         Image.fromarray(m).save(out)                   # uint8 [h,w]: mode "L"
         written.append(out)
@@ -231,29 +363,32 @@ def write_specular_masks(data_dir, out_dir, subdirs=PSD_SUBDIRS, angles=None, na
     return written
 
 
-def write_estimated_diffuse(data_dir, out_dir, subdirs=PSD_SUBDIRS, mode="min", angles=None, device=None):
+def write_estimated_diffuse(data_dir, out_dir, subdirs=PSD_SUBDIRS, mode="min", angles=None, device=None, capture="views", dofp=None,
+                            dofp_demosaic="bilinear"):
     """Materialise the estimated-diffuse image of every sample as a PNG at the sample's own size: the imwrite that
     utils.calculate_estimate_diffuse left commented out.  The first four `subdirs` of `data_dir` are listed as the loader lists
     them; sample i's estimate (mode "min": per pixel and channel the minimum of the four views, the reference's definition;
     "stokes": the fitted minimum, with `angles` or the angles read from the directory names) is computed by shm_polar_views_u8 at
     (ho, wo) = (hin, win), scale 1, no flip, rounded to the nearest byte and written to `out_dir` under the first view's file
     name (with the extension .png).  The result can go to any other tool, or back to PolarDataset as its ED/ directory.
+    capture="dofp" (with dofp = a DofpLayout and dofp_demosaic): the first of `subdirs` holds one polariser mosaic per sample, whose
+    demosaiced views (sample_views) take the place of the four files; the image is named after the mosaic.
     Returns the list of files written."""
     import torch
     from PIL import Image
     from . import ops
     if mode not in ops.POLAR_MODES:
         raise ValueError(f"write_estimated_diffuse: mode {mode!r} is not 'min' or 'stokes'")
-    views, files = polar_sample_files(data_dir, subdirs, "write_estimated_diffuse")
-    coef = stokes_matrix(angles if angles is not None else angles_from_subdirs(views)) if mode == "stokes" else None
+    check_capture(capture, dofp, dofp_demosaic, "write_estimated_diffuse")
+    views, files = polar_sample_files(data_dir, subdirs, "write_estimated_diffuse", capture)
+    coef = stokes_matrix(_view_angles(angles, views, capture, dofp)) if mode == "stokes" else None
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     os.makedirs(out_dir, exist_ok=True)
     written = []
     for i in range(len(files[0])):
         paths = [f[i] for f in files]
-        imgs = decode_sample(paths, i)
-        h, w, _ = imgs[0].shape
-        srcs = [torch.from_numpy(a).to(dev) for a in imgs]
+        srcs = sample_views(paths, i, dev, capture, dofp, dofp_demosaic)
+        h, w, _ = srcs[0].shape
         planes = torch.empty((5, h, w, 3), dtype=torch.float32, device=dev)
         ops.polar_views_u8(srcs, list(planes), mode, coef, 1.0, False)
         ed = torch.round(planes[4]).clamp_(0, 255).to(torch.uint8).cpu().numpy()

@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from . import checkpoint, dist, ops, validation
-from .data import Augment, MaskDataset, datasetLoad, gib_to_bytes
+from .data import CAPTURE_OPTIONS, Augment, MaskDataset, capture_options, datasetLoad, gib_to_bytes
 from .dist import GradReducer, exchange_active, world_size
 from .model import Arena, Discriminator, Generator, WgradLane, check_image_hw, pad_channels
 from .specseg import SpecSeg
@@ -60,6 +60,8 @@ _DEFAULTS = dict(image_size=128, image_hw=None, batch_size=1, filter_size=64, g_
                  loss_log_step=0, histogram_step=0, nonfinite=None, diffuse_source="dir",
                  shuffle=False, data_seed=0, aug_flip_lr=0.0, aug_flip_ud=0.0, aug_crop_min=1.0, aug_views="physical",
                  cache="none", cache_gb=None,
+                 capture_format="views", dofp_dir="DOFP", dofp_pattern="mono", dofp_quad_angles=(90, 45, 135, 0), dofp_bits=8,
+                 dofp_demosaic="bilinear", dofp_test_view="total",
                  specseg_image_dir="", specseg_mask_dir="", specseg_epochs=20, specseg_lr=1e-3, specseg_batch_size=8,
                  specseg_mask_source="dir", specseg_mask_threshold="otsu", specseg_mask_floor=16, specseg_mask_open=1,
                  specseg_mask_dilate=2,
@@ -364,7 +366,8 @@ class ShmGANwithSSpecSeg:
         data_dir = opt("data_dir")
         if not data_dir:
             raise ValueError("specseg_mask_source='polar' needs data_dir: the capture's four view directories")
-        return MaskDataset.from_polar(data_dir, self.image_size, int(opt("specseg_batch_size")), device=self.device,
+        subdirs, capture = capture_options(SimpleNamespace(**{k: opt(k) for k in CAPTURE_OPTIONS}))
+        return MaskDataset.from_polar(data_dir, self.image_size, int(opt("specseg_batch_size")), subdirs=subdirs, device=self.device, **capture,
                                       threshold=opt("specseg_mask_threshold"), floor=int(opt("specseg_mask_floor")),
                                       open_radius=int(opt("specseg_mask_open")), dilate_radius=int(opt("specseg_mask_dilate")), **loader)
 
@@ -811,7 +814,8 @@ class ShmGANwithSSpecSeg:
         `aug_views` (data.datasetLoad; all off by default) give an epoch-wise shuffle and a random crop / mirror per sample;
         aug_flip_ud=0.5 is the as-intended reading of the per-step draw below.  `cache="device"` (with `cache_gb`, GiB; default half of the free
         device memory) keeps the decoded samples on the device after their first decode, the reference's `.cache()`;
-        `self.loadedDataset.cache_stats()` says what it holds.  `ema_decay` (with `ema_warmup`) keeps an average of the generator's weights
+        `self.loadedDataset.cache_stats()` says what it holds.  `capture_format="dofp"` (with `dofp_dir`, `dofp_pattern`, `dofp_quad_angles`,
+        `dofp_bits`, `dofp_demosaic`: data.capture_options) trains from one polariser-mosaic frame per sample instead of four view files.  `ema_decay` (with `ema_warmup`) keeps an average of the generator's weights
         (_ensure_ema, generator_weights); `val_dir` or `val_fraction` (with `val_seed`, `val_step`, `val_batch_size`, `val_monitor`, `val_region`) hold captures
         out: every `val_step` epochs, in front of the checkpoint, and once at the end they are scored (validate), rank 0 appends the means to
         `log_dir`/validation.jsonl and keeps the best weights as `checkpoint_save_dir`/best.npz (validation.py).  Both are off by default and

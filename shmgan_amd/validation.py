@@ -6,7 +6,7 @@ import numpy as np
 import torch
 
 from . import checkpoint, dist, ops
-from .data import gib_to_bytes, trainer_frame, validation_loader
+from .data import capture_options, gib_to_bytes, trainer_frame, validation_loader
 from .telemetry import VALIDATION_FILE, WEIGHT_SETS, improves, nan_to_none, region_means, region_options, write_lines
 
 
@@ -14,9 +14,11 @@ def _loader(t):
     """The held-out loader of the trainer's val_dir / val_fraction options (None with both off), made once."""
     if t.valDataset is None:
         a = t.args
+        subdirs, capture = capture_options(a)
         t.valDataset = validation_loader(
             t.data_dir, trainer_frame(t), t.batch_size, val_dir=a.val_dir, val_fraction=float(a.val_fraction or 0.0), val_seed=int(a.val_seed),
-            val_batch_size=a.val_batch_size, device=t.device, diffuse_source=a.diffuse_source, cache=a.cache, cache_bytes=gib_to_bytes(a.cache_gb))
+            val_batch_size=a.val_batch_size, subdirs=subdirs, device=t.device, diffuse_source=a.diffuse_source, cache=a.cache,
+            cache_bytes=gib_to_bytes(a.cache_gb), **capture)
     return t.valDataset
 
 

@@ -1,0 +1,102 @@
+"""shm_dofp_views (csrc/dofp.hip) on 2448 x 2048 frames, the Sony IMX250MZR / MYR's: microseconds per frame, achieved bytes/s and the
+share of the HBM peak, for 8-bit mono, 12-bit mono, 12-bit RGGB bilinear and 12-bit RGGB bin, with and without the total plane;
+and the host time PIL takes to decode the four view PNGs the one mosaic replaces.  A record for kernel work, not an acceptance number.
+
+Bytes are algorithmic and computed from the shapes here: the mosaic read once plus the planes written.  Device events around
+LAUNCHES launches, 2 warm-ups and 5 timed iterations, seeded data.  The launches rotate over SETS source / destination sets (more
+than the 256 MiB Infinity Cache together), so that a frame comes from and goes to HBM as a camera's next frame would.
+python tools/bench_dofp.py [--launches N] [--no-decode]"""
+import argparse
+import ctypes as C
+import io
+import sys
+import time
+from pathlib import Path
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+import numpy as np
+import torch
+from shmgan_amd import _lib, ops
+
+W, H = 2448, 2048
+HBM_PEAK = 8.0e12            # bytes/s, the MI355X's specification; ~6.3e12 is what a float4 copy achieves
+HBM_COPY = 6.29e12
+SETS = 6
+CONFIGS = [("8-bit mono bilinear", "mono", 8, "bilinear"), ("12-bit mono bilinear", "mono", 12, "bilinear"),
+           ("12-bit RGGB bilinear", "rggb", 12, "bilinear"), ("12-bit RGGB bin", "rggb", 12, "bin")]
+QUAD = (2, 1, 3, 0)          # Sony: 90 / 45 / 135 / 0
+
+
+def launcher(pattern, bits, mode, total, rng):
+    """(fn that launches on set i, bytes per launch)."""
+    L = _lib.lib()
+    ho, wo = ops.dofp_shape(H, W, pattern, mode)
+    dt = np.uint8 if bits == 8 else np.uint16
+    nplanes = 5 if total else 4
+    quad = (C.c_int * 4)(*QUAD)
+    sets = []
+    for _ in range(SETS):
+        src = torch.from_numpy(rng.integers(0, 1 << bits, (H, W)).astype(dt)).cuda()
+        out = torch.empty((nplanes, ho, wo, 3), dtype=torch.uint8, device="cuda")
+        sets.append((src, out, (C.c_void_p * 4)(*[out[v].data_ptr() for v in range(4)]), out[4].data_ptr() if total else None))
+    st = torch.cuda.current_stream().cuda_stream
+    pc, mc = ops.DOFP_PATTERNS[pattern], ops.DOFP_MODES[mode]
+
+    def fn(i):
+        src, _, dp, tp = sets[i % SETS]
+        _lib.check(L.shm_dofp_views(src.data_ptr(), bits, H, W, W, pc, quad, mc, dp, tp, st), "shm_dofp_views")
+    return fn, H * W * np.dtype(dt).itemsize + nplanes * ho * wo * 3
+
+
+def timed(fn, launches, warm=2, n=5):
+    """Median microseconds per launch over n timed iterations of `launches` launches (device events)."""
+    us = []
+    for it in range(warm + n):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for i in range(launches):
+            fn(i)
+        e1.record()
+        e1.synchronize()
+        if it >= warm:
+            us.append(e0.elapsed_time(e1) * 1e3 / launches)
+    return float(np.median(us)), us
+
+
+def decode_time(rng, n=3):
+    """Host milliseconds PIL takes to decode the four 8-bit RGB view PNGs of one frame (the mosaic's own demosaiced views)."""
+    from PIL import Image
+    from shmgan_amd.polar import DofpLayout, demosaic
+    views = [v.cpu().numpy() for v in demosaic(rng.integers(0, 256, (H, W)).astype(np.uint8), DofpLayout())]
+    files = []
+    for v in views:
+        b = io.BytesIO()
+        Image.fromarray(v).save(b, format="PNG", compress_level=1)
+        files.append(b.getvalue())
+    best = []
+    for _ in range(n):
+        t0 = time.perf_counter()
+        for f in files:
+            np.asarray(Image.open(io.BytesIO(f)).convert("RGB"))
+        best.append((time.perf_counter() - t0) * 1e3)
+    return min(best), sum(len(f) for f in files)
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--launches", type=int, default=1000)
+    ap.add_argument("--no-decode", action="store_true")
+    a = ap.parse_args()
+    rng = np.random.default_rng(0)
+    print(f"shm_dofp_views, {W} x {H} frames, {SETS} buffer sets in rotation, {a.launches} launches per timed iteration")
+    for name, pattern, bits, mode in CONFIGS:
+        for total in (False, True):
+            fn, nbytes = launcher(pattern, bits, mode, total, rng)
+            us, all_us = timed(fn, a.launches)
+            bw = nbytes / (us * 1e-6)
+            print(f"  {name:22s} {'+ total' if total else '       '}: {us:8.2f} us  ({min(all_us):.2f} .. {max(all_us):.2f})  {nbytes / 1e6:7.2f} MB  "
+                  f"{bw / 1e12:5.2f} TB/s = {100 * bw / HBM_PEAK:4.1f} % of the {HBM_PEAK / 1e12:.1f} TB/s peak, "
+                  f"{100 * bw / HBM_COPY:4.1f} % of a copy's {HBM_COPY / 1e12:.2f} TB/s", flush=True)
+    if not a.no_decode:
+        ms, nb = decode_time(rng)
+        print(f"  PIL decode of the four {W} x {H} RGB view PNGs one mosaic replaces: {ms:.1f} ms on the host ({nb / 1e6:.1f} MB of files; noise "
+              f"images at compress_level 1)")

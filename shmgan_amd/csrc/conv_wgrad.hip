@@ -18,6 +18,7 @@
 // kernel.  The kernels live one family per translation unit, each behind a launch function of wgrad.h: conv_wgrad_gen.hip (wgrad_kernel,
 // wgrad_bf16_kernel: described above), conv_wgrad_halo.hip (wgrad_halo_kernel, wgrad_halo_thin_kernel), conv_wgrad_halo16.hip
 // (wgrad_halo_bf16_kernel), conv_wgrad_halo8.hip (wgrad_halo8_bf16_kernel), beside conv_wgrad_x3.hip and conv_rgb.hip's first-layer kernel.
+// The halo-staged ones share their patch order, edge bits and stage ring through wgrad_halo_dev.h; the plan below counts patches in that order.
 #include "wgrad.h"
 
 #include <stdint.h>

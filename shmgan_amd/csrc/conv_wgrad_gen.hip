@@ -184,16 +184,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const WgradArgs a) {
     }
 
     // partial slab [split][tap][cin][cout]
-    float* out = a.part + (size_t)blk.z * NT * a.cin * a.cout;
-    const int con = co0 + ni * 32 + l31;
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int ci = ci0 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-            if (ci < a.cin && con < a.cout) out[((size_t)t * a.cin + ci) * a.cout + con] = acc[t][r];
-        }
-    }
+    wgrad_store_slab<NT, false>(acc, a.part + (size_t)blk.z * NT * a.cin * a.cout, a.cin, a.cout, ci0, mi, h, co0 + ni * 32 + l31, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -364,16 +355,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_bf16_kernel(const WgradArgs a) {
         }
     }
 
-    float* out = a.part + (size_t)blk.z * NT * a.cin * a.cout;
-    const int con = co0 + ni * 32 + l31;
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int ci = ci0 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-            if (ci < a.cin && con < a.cout) out[((size_t)t * a.cin + ci) * a.cout + con] = acc[t][r];
-        }
-    }
+    wgrad_store_slab<NT, false>(acc, a.part + (size_t)blk.z * NT * a.cin * a.cout, a.cin, a.cout, ci0, mi, h, co0 + ni * 32 + l31, nullptr);
 }
 
 template <int NT, bool STRADDLE>

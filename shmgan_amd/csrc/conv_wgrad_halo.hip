@@ -1,5 +1,5 @@
 // wgrad_halo_kernel and wgrad_halo_thin_kernel: the fp32 3x3 weight gradient with an LDS halo patch (see conv_wgrad.hip's header comment).
-#include "wgrad.h"
+#include "wgrad_halo_dev.h"
 
 // ------------------------------------------------------------------------------------------
 // 3x3 / stride-1 weight gradient with an LDS halo patch.
@@ -74,19 +74,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo_kernel(const WgradHaloArgs 
 
     // running patch coordinate (block-uniform), in OUTPUT pixels (ho x wo = h / IS x w / IS)
     const int ho = a.h / IS, wo = a.w / IS;
-    int n, pr, pc;
-    {
-        // Patches are numbered DOWN the columns of an image (round 4; until then along the rows): a block walks a contiguous range, and the
-        // halos of vertically adjacent patches share two of their four rows (half the halo) where horizontally adjacent ones share two of
-        // eighteen columns -- walking down, the shared rows were fetched one stage ago (L2 / L1 hits), walking along, 16 stages and a few
-        // hundred KiB per resident block ago, i.e. from beyond L2 (r03: 1291 MB HBM-side per launch for 805 MB of operands, L2 hit 0.19)
-        const int ppc = ho / 2, ppi = ppc * (wo / PW);
-        const int p = pid0 < a.npatch ? pid0 : 0;
-        n = p / ppi;
-        const int r = p - n * ppi;
-        pc = (r / ppc) * PW;
-        pr = (r % ppc) * 2;
-    }
+    PatchWalk<2, PW> pw;
+    pw.start(pid0, a.npatch, ho, wo);
     // DMA addressing, one v_add and one masked select per instruction: a lane's byte offset in item j is a per-lane constant plus the
     // patch origin, and whether its halo pixel lies outside the image depends only on which edges of the image the patch touches
     // (block-uniform, four bits) and on which edges of the halo the lane's pixel sits (per-lane constant, four bits per item; a fifth
@@ -103,7 +92,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo_kernel(const WgradHaloArgs 
             const int hp = 4 * item + dpx;
             const int r = hp / HC, c = hp - r * HC;
             off0[j] = (unsigned)((r * a.w + c) * ldX + ccX) * 4u;
-            bits = !(xvalid && hp < NHP) ? 16u : ((PAD && r == 0) ? 1u : 0u) | (r == HR - 1 ? 2u : 0u) | ((PAD && c == 0) ? 4u : 0u) | (c == HC - 1 ? 8u : 0u);
+            bits = !(xvalid && hp < NHP) ? 16u : halo_pixel_bits(r, c, HR - 1, HC - 1, PAD);
         } else {
             const int q = 4 * (item - NXI) + dpx;
             off0[j] = (unsigned)(((q / PW) * (a.w / IS) + q % PW) * a.lddy + coD) * 4u;
@@ -116,9 +105,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo_kernel(const WgradHaloArgs 
     }
     auto dma = [&](int stage) {
         float* sx = smem + stage * STAGE;
-        const int org = (n * a.h + IS * pr - PAD) * a.w + (IS * pc - PAD);       // pixel index of halo (0,0)
-        const unsigned edges = 16u | ((PAD && pr == 0) ? 1u : 0u) | (pr + 2 == ho ? 2u : 0u) | ((PAD && pc == 0) ? 4u : 0u) | (pc + PW == wo ? 8u : 0u);
-        const unsigned xb = (unsigned)(org * ldX) * 4u, db = (unsigned)(((n * ho + pr) * wo + pc) * a.lddy) * 4u;
+        const int org = (pw.n * a.h + IS * pw.pr - PAD) * a.w + (IS * pw.pc - PAD);       // pixel index of halo (0,0)
+        const unsigned edges = pw.template edges<PAD != 0>(ho, wo);
+        const unsigned xb = (unsigned)(org * ldX) * 4u, db = (unsigned)(((pw.n * ho + pw.pr) * wo + pw.pc) * a.lddy) * 4u;
 #pragma unroll
         for (int j = 0; j < 7; ++j) {
             const int item = wave + 4 * j;
@@ -129,28 +118,21 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo_kernel(const WgradHaloArgs 
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(isx ? rsx : rsd, (lds_ptr)(sx + item * 256), 16, (int)off, 0, 0, 0);
             }
         }
-        pr += 2;
-        if (pr == ho) {
-            pr = 0;
-            pc += PW;
-            if (pc == wo) {
-                pc = 0;
-                ++n;
-            }
-        }
+        pw.next(ho, wo);
     };
 
     // NM: coordinates of the next stage to normalise (they run one stage behind dma()'s), the lane's table entries and their image
     const bool nm_on = NM && a.nt != nullptr && (int)second == a.ntpart;        // block-uniform
-    [[maybe_unused]] int n2 = n, pr2 = pr, pc2 = pc, nimg = -1;
+    [[maybe_unused]] PatchWalk<2, PW> pw2 = pw;
+    [[maybe_unused]] int nimg = -1;
     [[maybe_unused]] f32x4 nmean = {0.f, 0.f, 0.f, 0.f}, ninv = nmean, nbeta = nmean;
     // One straight-line piece per stage (interior patches: no per-lane tests).
-    const int n_blk = n;                                    // NM = 2: the sample of this block's patches
+    const int n_blk = pw.n;                                    // NM = 2: the sample of this block's patches
     [[maybe_unused]] auto norm_x = [&](int stage) {
-        if (n2 != nimg) {                                   // block-uniform
-            nimg = n2;
+        if (pw2.n != nimg) {                                   // block-uniform
+            nimg = pw2.n;
             if (xvalid) {
-                const float* t = a.nt + (size_t)n2 * SHM_NT_PLANES * a.ntc + ccX;
+                const float* t = a.nt + (size_t)pw2.n * SHM_NT_PLANES * a.ntc + ccX;
                 if constexpr (NM == 2) {
                     nbeta = load16_drained(t + 3 * a.ntc);              // ring
                 } else {
@@ -163,12 +145,12 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo_kernel(const WgradHaloArgs 
         float* sx = smem + stage * STAGE + lane * 4;
         if constexpr (NM == 2) {
             // SHM_NORM_SCALED: `ring` over the out-of-image halo entries of a border patch; nothing to do inside the image
-            if (!(pr2 > 0 && pr2 + 2 < a.h && pc2 > 0 && pc2 + PW < a.w)) {
+            if (!pw2.interior(a.h, a.w)) {
 #pragma unroll
                 for (int j = 0; j < 5; ++j) {
                     const int item = wave + 4 * j;
                     if (item < 18) {
-                        const int iy = pr2 - 1 + hr[j], ix = pc2 - 1 + hc[j];
+                        const int iy = pw2.pr - 1 + hr[j], ix = pw2.pc - 1 + hc[j];
                         if (xvalid && !((unsigned)iy < (unsigned)a.h && (unsigned)ix < (unsigned)a.w)) *(f32x4*)(sx + item * 256) = nbeta;
                     }
                 }
@@ -176,7 +158,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo_kernel(const WgradHaloArgs 
         } else
         // interior patch (the whole 4 x 18 halo inside the image) of a full 64-channel tile: every lane of every item normalises, no
         // per-lane tests -- block-uniform, 7 of 8 patches of a 256 x 256 map
-        if (pr2 > 0 && pr2 + 2 < a.h && pc2 > 0 && pc2 + PW < a.w && ci0 + 64 <= a.cin_ld) {
+        if (pw2.interior(a.h, a.w) && ci0 + 64 <= a.cin_ld) {
             f32x4 x[5];
 #pragma unroll
             for (int j = 0; j < 4; ++j) x[j] = *(const f32x4*)(sx + (wave + 4 * j) * 256);
@@ -197,7 +179,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo_kernel(const WgradHaloArgs 
             for (int j = 0; j < 5; ++j) {
                 const int item = wave + 4 * j;
                 if (item < 18) {
-                    const int iy = pr2 - 1 + hr[j], ix = pc2 - 1 + hc[j];
+                    const int iy = pw2.pr - 1 + hr[j], ix = pw2.pc - 1 + hc[j];
                     if (xvalid && (unsigned)iy < (unsigned)a.h && (unsigned)ix < (unsigned)a.w) {
                         f32x4 x = *(const f32x4*)(sx + item * 256);
 #pragma unroll
@@ -207,15 +189,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo_kernel(const WgradHaloArgs 
                 }
             }
         }
-        pr2 += 2;
-        if (pr2 == a.h) {
-            pr2 = 0;
-            pc2 += PW;
-            if (pc2 == a.w) {
-                pc2 = 0;
-                ++n2;
-            }
-        }
+        pw2.next(a.h, a.w);
     };
 
     f32x16 acc[9];
@@ -252,65 +226,15 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo_kernel(const WgradHaloArgs 
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
     };
-    if (nstages > 0) {
-        dma(0);
-        if (nstages > 1) dma(1);
-        if constexpr (NM)
-            if (nm_on) {
-                wait_older(nstages > 1);
-                norm_x(0);
-            }
-        int cur = 0, nxt2 = 2;
-        for (int s = 0; s < nstages; ++s) {
-            wait_older(s + 1 < nstages);
-            SHM_LDS_BARRIER();
-            asm volatile("" ::: "memory");
-            if (s + 2 < nstages) dma(nxt2);
-            compute(cur);
-            asm volatile("" ::: "memory");
-            cur = (cur == NST - 1) ? 0 : cur + 1;
-            nxt2 = (nxt2 == NST - 1) ? 0 : nxt2 + 1;
-            // NM: stage s + 1 (issued before the stage in flight): every wave normalises its own items of it behind this stage's last
-            // MFMA (issued, not finished: they and the partner block's keep the matrix pipe busy); the barrier of step s + 1 publishes
-            // them.  The MFMA loop itself stays the plain kernel's: with the normalisation inside it (one piece at K step 8, or an
-            // item per K step) the loop falls into basic blocks -- 47-63 s_waitcnt instead of 20, +5-7 % on the kernel even for
-            // blocks that normalise nothing.  Timing-only builds: with the normalisation removed and the wait kept the kernel is as
-            // fast as the plain one (+0.2-0.5 %); the pass itself costs 3-6 % -- its read / fma / write chain (~500 cycles per
-            // 9216-cycle stage) is serial in every wave at the same time, and the two blocks of a CU run in lockstep.
-            if constexpr (NM)
-                if (nm_on && s + 1 < nstages) {
-                    wait_older(s + 2 < nstages);
-                    norm_x(cur);
-                    asm volatile("" ::: "memory");
-                }
-        }
-    }
+    wgrad_stage_ring<NST, NM != 0>(nstages, nm_on, dma, compute, wait_older, norm_x);
 
-    // NM = 2: the slab's rows times inv of the block's sample (row r of a lane: channel ci0 + 32 mi + (r & 3) + 8 (r >> 2) + 4 hh),
-    // applied on the way out (scaling the accumulators in place made hipcc spill 100 registers)
+    // NM = 2: the slab's rows times inv of the block's sample
     float sc[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) sc[r] = 1.f;
     if constexpr (NM == 2)
-        if (nm_on) {
-            const float* iv = a.nt + ((size_t)n_blk * SHM_NT_PLANES + 1) * a.ntc + (ci0 - (second ? a.c1 : 0)) + mi * 32 + 4 * hh;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x4 s4 = *(const f32x4*)(iv + 8 * g);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) sc[4 * g + e] = s4[e];
-            }
-        }
-    float* out = a.part + (size_t)blk.z * 9 * a.cin * a.cout;
-    const int con = co0 + ni * 32 + l31;
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int ci = ci0 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-            if (ci < a.cin && con < a.cout) out[((size_t)t * a.cin + ci) * a.cout + con] = NM == 2 ? acc[t][r] * sc[r] : acc[t][r];
-        }
-    }
+        if (nm_on) wgrad_row_scale(sc, a.nt + ((size_t)n_blk * SHM_NT_PLANES + 1) * a.ntc + (ci0 - (second ? a.c1 : 0)) + mi * 32 + 4 * hh);
+    wgrad_store_slab<9, NM == 2>(acc, a.part + (size_t)blk.z * 9 * a.cin * a.cout, a.cin, a.cout, ci0, mi, hh, co0 + ni * 32 + l31, sc);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -353,7 +277,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo_thin_kernel(const WgradHalo
     const int coD = co0 + dch * 4;
     const bool dvalid = coD < a.cout;
 
-    int n, pr, pc;                                       // patch origin in OUTPUT pixels
+    int n, pr, pc;                                       // patch origin in OUTPUT pixels; the one kernel that walks ALONG the rows (not PatchWalk's order)
     {
         const int ppr = wo / PW, ppi = (ho / 2) * ppr;
         const int p = pid0 < a.npatch ? pid0 : 0;
@@ -426,28 +350,17 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo_thin_kernel(const WgradHalo
         }
     };
 
-    if (nstages > 0) {
-        dma(0);
-        if (nstages > 1) dma(1);
-        int cur = 0, nxt2 = 2;
-        for (int s = 0; s < nstages; ++s) {
-            if (s + 1 < nstages) {                 // one younger stage in flight: CHI or CLO DMA instructions of this wave
-                if (NHI != 0 && wave < NHI)
-                    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CHI) : "memory");
-                else
-                    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CLO) : "memory");
-            } else {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-            SHM_LDS_BARRIER();
-            asm volatile("" ::: "memory");
-            if (s + 2 < nstages) dma(nxt2);
-            compute(cur);
-            asm volatile("" ::: "memory");
-            cur = (cur == NST - 1) ? 0 : cur + 1;
-            nxt2 = (nxt2 == NST - 1) ? 0 : nxt2 + 1;
+    auto wait_older = [&](bool younger_in_flight) {
+        if (younger_in_flight) {                   // one younger stage in flight: CHI or CLO DMA instructions of this wave
+            if (NHI != 0 && wave < NHI)
+                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CHI) : "memory");
+            else
+                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CLO) : "memory");
+        } else {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
-    }
+    };
+    wgrad_stage_ring<NST, false>(nstages, false, dma, compute, wait_older, [](int) {});
 
     float* out = a.part + ((size_t)blockIdx.z * 2 + qr) * 9 * a.cin * a.cout;
     const int con = co0 + ni * 32 + l31;

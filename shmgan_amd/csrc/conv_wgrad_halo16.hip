@@ -1,5 +1,5 @@
 // wgrad_halo_bf16_kernel: the four-wave bf16 3x3 unit-stride weight gradient with an LDS halo patch (see conv_wgrad.hip's header comment).
-#include "wgrad.h"
+#include "wgrad_halo_dev.h"
 
 // ------------------------------------------------------------------------------------------
 // bf16 version of the halo-patch weight gradient (3x3, stride 1): the LDS image of wgrad_halo_kernel in
@@ -12,15 +12,24 @@
 // q + kh, so a stage of R rows needs (R + 2) x 3 fragment reads for 9 R MFMAs (hipcc keeps the shared ones in registers):
 // R = 4 reads 22 fragments per 36 MFMAs where two R = 2 stages read 28, with half the barriers and 3/4 of the halo bytes.
 // NM: as in wgrad_halo_kernel (a lane's eight channels are the same for every item and patch: 24 table registers).
+
+// Stage geometry of wgrad_halo_bf16_kernel<R, *>: the kernel and its launcher read it
+template <int R>
+struct Halo16Shape {
+    static constexpr int PW = 16, HP = 20;                     // patch R x 16; halo R + 2 rows, LDS pitch 20 (18 valid)
+    static constexpr int NHR = (R + 2) * HP, NPX = R * PW;     // R = 2: 80 halo rows, 32 dY rows (14 KiB); R = 4: 120 + 64 (23 KiB)
+    static constexpr int STAGE = (NHR + NPX) * 64;             // bf16 elements per stage
+    static constexpr int NST = 3;
+    static constexpr int NXI = NHR / 8, NDI = NPX / 8;         // DMA items (8 rows of 128 B each): 10 + 4 / 15 + 8
+    static constexpr int NIT = NXI + NDI, NJ = (NIT + 3) / 4;  // items per wave: waves below NIT % 4 (or all) take NJ, the others NJ - 1
+    static constexpr int NXJ = (NXI + 3) / 4;                  // halo items per wave (at most)
+    static constexpr unsigned lds_bytes = NST * STAGE * 2u;    // R = 2: 42 KiB, R = 4: 69 KiB
+};
+
 template <int R, int NM = 0>
 __global__ __launch_bounds__(256, 2) void wgrad_halo_bf16_kernel(const WgradHaloArgs a) {
-    constexpr int PW = 16, HP = 20;                     // patch R x 16; halo R + 2 rows, LDS pitch 20 (18 valid)
-    constexpr int NHR = (R + 2) * HP, NPX = R * PW;     // R = 2: 80 halo rows, 32 dY rows (14 KiB); R = 4: 120 + 64 (23 KiB)
-    constexpr int STAGE = (NHR + NPX) * 64;             // bf16 elements per stage
-    constexpr int NST = 3;
-    constexpr int NXI = NHR / 8, NDI = NPX / 8;         // DMA items (8 rows of 128 B each): 10 + 4 / 15 + 8
-    constexpr int NIT = NXI + NDI, NJ = (NIT + 3) / 4;  // items per wave: waves below NIT % 4 (or all) take NJ, the others NJ - 1
-    constexpr int NXJ = (NXI + 3) / 4;                  // halo items per wave (at most)
+    typedef Halo16Shape<R> SH;
+    constexpr int PW = SH::PW, HP = SH::HP, NHR = SH::NHR, STAGE = SH::STAGE, NST = SH::NST, NXI = SH::NXI, NIT = SH::NIT, NJ = SH::NJ, NXJ = SH::NXJ;
     extern __shared__ __attribute__((aligned(1024))) unsigned short smem[];
     typedef __attribute__((address_space(3))) void* lds_ptr;
 
@@ -57,15 +66,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo_bf16_kernel(const WgradHalo
         hc[j] = hp - hr[j] * HP;
     }
 
-    int n, pr, pc;
-    {
-        const int ppc = a.h / R, ppi = ppc * (a.w / PW);           // patches numbered down the columns of an image, see wgrad_halo_kernel
-        const int p = pid0 < a.npatch ? pid0 : 0;
-        n = p / ppi;
-        const int r = p - n * ppi;
-        pc = (r / ppc) * PW;
-        pr = (r % ppc) * R;
-    }
+    PatchWalk<R, PW> pw;
+    pw.start(pid0, a.npatch, a.h, a.w);
     // DMA addressing as in wgrad_halo_kernel: per-lane constant offset + patch origin, edge bits (five per item, one register)
     static_assert(NJ <= 6, "five mask bits per item in one register");
     unsigned off0[NJ], bm = 0;
@@ -77,7 +79,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo_bf16_kernel(const WgradHalo
             const int hp = 8 * item + drow;
             const int r_ = hp / HP, c_ = hp - r_ * HP;
             off0[j] = (unsigned)((r_ * a.w + c_) * ldX + ccX) * 2u;
-            bits = !(xvalid && c_ < PW + 2) ? 16u : (r_ == 0 ? 1u : 0u) | (r_ == R + 1 ? 2u : 0u) | (c_ == 0 ? 4u : 0u) | (c_ == PW + 1 ? 8u : 0u);
+            bits = !(xvalid && c_ < PW + 2) ? 16u : halo_pixel_bits(r_, c_, R + 1, PW + 1, true);
         } else {
             const int q = 8 * (item - NXI) + drow;
             off0[j] = (unsigned)(((q >> 4) * a.w + (q & 15)) * a.lddy + coD) * 2u;
@@ -87,9 +89,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo_bf16_kernel(const WgradHalo
     }
     auto dma = [&](int stage) {
         unsigned short* sx = smem + stage * STAGE;
-        const int org = (n * a.h + pr - 1) * a.w + (pc - 1);       // pixel index of halo (0,0)
-        const unsigned edges = 16u | (pr == 0 ? 1u : 0u) | (pr + R == a.h ? 2u : 0u) | (pc == 0 ? 4u : 0u) | (pc + PW == a.w ? 8u : 0u);
-        const unsigned xb = (unsigned)(org * ldX) * 2u, db = (unsigned)(((n * a.h + pr) * a.w + pc) * a.lddy) * 2u;
+        const int org = (pw.n * a.h + pw.pr - 1) * a.w + (pw.pc - 1);       // pixel index of halo (0,0)
+        const unsigned edges = pw.template edges<true>(a.h, a.w);
+        const unsigned xb = (unsigned)(org * ldX) * 2u, db = (unsigned)(((pw.n * a.h + pw.pr) * a.w + pw.pc) * a.lddy) * 2u;
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
             const int item = wave + 4 * j;
@@ -99,26 +101,19 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo_bf16_kernel(const WgradHalo
                 shm_dma16(isx ? rsx : rsd, shm_lds_addr(sx + item * 512), off);
             }
         }
-        pr += R;
-        if (pr == a.h) {
-            pr = 0;
-            pc += PW;
-            if (pc == a.w) {
-                pc = 0;
-                ++n;
-            }
-        }
+        pw.next(a.h, a.w);
     };
 
     const bool nm_on = NM && a.nt != nullptr && (int)second == a.ntpart;        // block-uniform
-    [[maybe_unused]] int n2 = n, pr2 = pr, pc2 = pc, nimg = -1;
+    [[maybe_unused]] PatchWalk<R, PW> pw2 = pw;              // the next stage to normalise: one stage behind dma()'s
+    [[maybe_unused]] int nimg = -1;
     [[maybe_unused]] f32x4 nmean[2] = {}, ninv[2] = {}, nbeta[2] = {};
-    const int n_blk = n;                                    // NM = 2: the sample of this block's patches
+    const int n_blk = pw.n;                                    // NM = 2: the sample of this block's patches
     [[maybe_unused]] auto norm_x = [&](int stage) {
-        if (n2 != nimg) {                                   // block-uniform
-            nimg = n2;
+        if (pw2.n != nimg) {                                   // block-uniform
+            nimg = pw2.n;
             if (xvalid) {
-                const float* t = a.nt + (size_t)n2 * SHM_NT_PLANES * a.ntc + ccX;
+                const float* t = a.nt + (size_t)pw2.n * SHM_NT_PLANES * a.ntc + ccX;
 #pragma unroll
                 for (int hf = 0; hf < 2; ++hf) {
                     if constexpr (NM == 2) {
@@ -135,7 +130,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo_bf16_kernel(const WgradHalo
         unsigned short* sx = smem + stage * STAGE + lane * 8;
         if constexpr (NM == 2) {
             // SHM_NORM_SCALED: `ring` over the out-of-image halo entries of a border patch (the two dummy columns of the pitch stay zero)
-            if (!(pr2 > 0 && pr2 + R < a.h && pc2 > 0 && pc2 + PW < a.w)) {
+            if (!pw2.interior(a.h, a.w)) {
                 u32x4_t rg;
 #pragma unroll
                 for (int hf = 0; hf < 2; ++hf)
@@ -147,7 +142,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo_bf16_kernel(const WgradHalo
                 for (int j = 0; j < NXJ; ++j) {
                     const int item = wave + 4 * j;
                     if (item < NXI) {
-                        const int iy = pr2 - 1 + hr[j], ix = pc2 - 1 + hc[j];
+                        const int iy = pw2.pr - 1 + hr[j], ix = pw2.pc - 1 + hc[j];
                         if (xvalid && hc[j] < PW + 2 && !((unsigned)iy < (unsigned)a.h && (unsigned)ix < (unsigned)a.w)) *(u32x4_t*)(sx + item * 512) = rg;
                     }
                 }
@@ -157,7 +152,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo_bf16_kernel(const WgradHalo
         for (int j = 0; j < NXJ; ++j) {
             const int item = wave + 4 * j;
             if (item < NXI) {
-                const int iy = pr2 - 1 + hr[j], ix = pc2 - 1 + hc[j];
+                const int iy = pw2.pr - 1 + hr[j], ix = pw2.pc - 1 + hc[j];
                 if (xvalid && hc[j] < PW + 2 && (unsigned)iy < (unsigned)a.h && (unsigned)ix < (unsigned)a.w) {
                     u32x4_t x = *(const u32x4_t*)(sx + item * 512);
 #pragma unroll
@@ -174,15 +169,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo_bf16_kernel(const WgradHalo
             }
         }
         }
-        pr2 += R;
-        if (pr2 == a.h) {
-            pr2 = 0;
-            pc2 += PW;
-            if (pc2 == a.w) {
-                pc2 = 0;
-                ++n2;
-            }
-        }
+        pw2.next(a.h, a.w);
     };
 
     f32x16 acc[9];
@@ -191,18 +178,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo_bf16_kernel(const WgradHalo
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
 
-    // transposed-read addresses (elements): lane supplies row 8hh + (i>>2) [+4 for the second read] and channels
-    // [32*tile + 16*(g&1) + 4*(i&3), +4); tap (kh,kw) and K step qr enter as immediates, except that kw shifts
-    // the row and with it bit 1 of the row index -> one address per kw
-    const int fq = 8 * hh + ((lane & 15) >> 2);
-    const int fcol = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
-    int fa[3];
-#pragma unroll
-    for (int kw = 0; kw < 3; ++kw) {
-        const int row = fq + kw;
-        fa[kw] = row * 64 + ((mi * 32 + fcol) ^ (((row >> 1) & 1) << 5));
-    }
-    const int fb = fq * 64 + ((ni * 32 + fcol) ^ (((fq >> 1) & 1) << 5));
+    int fa[3], fb;                                          // transposed-read addresses: one per kw, and the dY fragment's
+    wgrad_tr_addrs<false, HP, HP>(lane, mi, ni, 0, fa, fb);
     auto compute = [&](int stage) {
         const unsigned short* X = smem + stage * STAGE;
         const unsigned short* D = X + NHR * 64;
@@ -228,68 +205,25 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo_bf16_kernel(const WgradHalo
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
     };
-    if (nstages > 0) {
-        dma(0);
-        if (nstages > 1) dma(1);
-        if constexpr (NM)
-            if (nm_on) {
-                wait_older(nstages > 1);
-                norm_x(0);
-            }
-        int cur = 0, nxt2 = 2;
-        for (int s = 0; s < nstages; ++s) {
-            wait_older(s + 1 < nstages);
-            SHM_LDS_BARRIER();
-            asm volatile("" ::: "memory");
-            if (s + 2 < nstages) dma(nxt2);
-            compute(cur);
-            asm volatile("" ::: "memory");
-            cur = (cur == NST - 1) ? 0 : cur + 1;
-            nxt2 = (nxt2 == NST - 1) ? 0 : nxt2 + 1;
-            // NM: see wgrad_halo_kernel
-            if constexpr (NM)
-                if (nm_on && s + 1 < nstages) {
-                    wait_older(s + 2 < nstages);
-                    norm_x(cur);
-                    asm volatile("" ::: "memory");
-                }
-        }
-    }
+    wgrad_stage_ring<NST, NM != 0>(nstages, nm_on, dma, compute, wait_older, norm_x);
 
-    // NM = 2: the slab's rows times inv of the block's sample (see wgrad_halo_kernel)
+    // NM = 2: the slab's rows times inv of the block's sample
     float sc[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) sc[r] = 1.f;
     if constexpr (NM == 2)
-        if (nm_on) {
-            const float* iv = a.nt + ((size_t)n_blk * SHM_NT_PLANES + 1) * a.ntc + (ci0 - (second ? a.c1 : 0)) + mi * 32 + 4 * hh;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x4 s4 = *(const f32x4*)(iv + 8 * g);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) sc[4 * g + e] = s4[e];
-            }
-        }
-    float* out = a.part + (size_t)blk.z * 9 * a.cin * a.cout;
-    const int con = co0 + ni * 32 + l31;
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int ci = ci0 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-            if (ci < a.cin && con < a.cout) out[((size_t)t * a.cin + ci) * a.cout + con] = NM == 2 ? acc[t][r] * sc[r] : acc[t][r];
-        }
-    }
+        if (nm_on) wgrad_row_scale(sc, a.nt + ((size_t)n_blk * SHM_NT_PLANES + 1) * a.ntc + (ci0 - (second ? a.c1 : 0)) + mi * 32 + 4 * hh);
+    wgrad_store_slab<9, NM == 2>(acc, a.part + (size_t)blk.z * 9 * a.cin * a.cout, a.cin, a.cout, ci0, mi, hh, co0 + ni * 32 + l31, sc);
 }
 
 template <int R, int NM>
 static int halo16_launch(const WgradHaloArgs& a, const WgradPlan& p, hipStream_t st) {
-    constexpr unsigned kLds = 3u * ((R + 2) * 20 + R * 16) * 128u;      // R = 4: 69 KiB, R = 2: 42 KiB
-    if constexpr (R == 4) {
-        static const hipError_t attr = hipFuncSetAttribute((const void*)wgrad_halo_bf16_kernel<R, NM>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
-        SHM_REQUIRE(attr == hipSuccess, SHM_E_HIP, "shm_conv2d_wgrad: cannot reserve 69 KiB of LDS: %s", hipGetErrorString(attr));
+    constexpr unsigned lds = Halo16Shape<R>::lds_bytes;
+    if constexpr (R == 4) {                              // above the 64 KiB a kernel gets unasked
+        static const hipError_t attr = hipFuncSetAttribute((const void*)wgrad_halo_bf16_kernel<R, NM>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        SHM_REQUIRE(attr == hipSuccess, SHM_E_HIP, "shm_conv2d_wgrad: cannot reserve %g KiB of LDS: %s", lds / 1024.0, hipGetErrorString(attr));
     }
-    hipLaunchKernelGGL((wgrad_halo_bf16_kernel<R, NM>), dim3(shm_cdiv(a.cin, 64), shm_cdiv(a.cout, 64), p.splits), dim3(256), kLds, st, a);
+    hipLaunchKernelGGL((wgrad_halo_bf16_kernel<R, NM>), dim3(shm_cdiv(a.cin, 64), shm_cdiv(a.cout, 64), p.splits), dim3(256), lds, st, a);
     if (NM)
         shm_set_last_kernel("wgrad_halo_bf16_kernel<%d, %d>", R, NM);
     else

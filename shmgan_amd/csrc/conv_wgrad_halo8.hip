@@ -1,5 +1,5 @@
 // wgrad_halo8_bf16_kernel: the eight-wave bf16 3x3 weight gradient, unit stride and stride 2 (see conv_wgrad.hip's header comment).
-#include "wgrad.h"
+#include "wgrad_halo_dev.h"
 
 // ------------------------------------------------------------------------------------------
 // Round 4: the bf16 halo weight gradient as an EIGHT-wave block that owns 64 input channels x 128 output channels -- two
@@ -27,23 +27,33 @@
 // whose output width is only a multiple of 8 (the discriminator's last layer, 16 x 16 -> 8 x 8): stages of 4 x 8 output pixels, 9 x 17 halo
 // stored as [9 even | 3 unused | 8 odd] = 20 LDS rows per halo row -- the same 180 rows; a K step is two output rows of eight pixels, so the
 // lane half hh of a fragment sits two halo rows (40 LDS rows) further down instead of eight plane entries further on.
+// Stage geometry of wgrad_halo8_bf16_kernel<MODE>: the kernel and its launcher read it
+template <int MODE>
+struct Halo8Shape {
+    static constexpr bool S2 = MODE != 0;
+    static constexpr int R = MODE == 1 ? 2 : 4;                // output rows per stage
+    static constexpr int PW = MODE == 2 ? 8 : 16;
+    static constexpr int HP = MODE == 2 ? 12 : 20;             // S1: LDS pitch of a halo row (18 valid); S2: pitch of the even run
+    static constexpr int HRP = MODE == 1 ? 36 : 20;            // LDS rows per halo row
+    static constexpr int NHROW = S2 ? 2 * R + 1 : R + 2;       // halo rows: 6 | 5 | 9
+    static constexpr int NHR = NHROW * HRP;                    // 120 | 180 | 180
+    static constexpr int KSTEPS = R * PW / 16;                 // K steps (16 output pixels) per stage
+    static constexpr int NXI = (NHR + 7) / 8, NDT = R * PW / 8;       // x items 15 | 23 | 23, dY items per co tile 8 | 4 | 4
+    static constexpr int NIT = NXI + 2 * NDT;                  // 31 | 31 | 31
+    static_assert(NIT == 31, "31 items per stage: waves 0-6 issue four, wave 7 three");
+    static constexpr int NJ = 4;
+    static constexpr int XROWS = NXI * 8, DROWS = NDT * 8;     // LDS rows of the x region, of one dY tile
+    static constexpr int STAGE = (XROWS + 2 * DROWS) * 64;     // bf16 elements: 248 rows of 128 B
+    static constexpr int NST = 3;
+    static constexpr unsigned lds_bytes = NST * STAGE * 2u;    // 93 KiB
+};
+
 template <int MODE>
 __global__ __launch_bounds__(512, 2) void wgrad_halo8_bf16_kernel(const WgradHaloArgs a) {
-    constexpr bool S2 = MODE != 0;
-    constexpr int R = MODE == 1 ? 2 : 4;                // output rows per stage
-    constexpr int PW = MODE == 2 ? 8 : 16;
-    constexpr int HP = MODE == 2 ? 12 : 20;             // S1: LDS pitch of a halo row (18 valid); S2: pitch of the even run
-    constexpr int HRP = MODE == 1 ? 36 : 20;            // LDS rows per halo row
-    constexpr int NHROW = S2 ? 2 * R + 1 : R + 2;       // halo rows: 6 | 5 | 9
-    constexpr int NHR = NHROW * HRP;                    // 120 | 180 | 180
-    constexpr int KSTEPS = R * PW / 16;                 // K steps (16 output pixels) per stage
-    constexpr int NXI = (NHR + 7) / 8, NDT = R * PW / 8;       // x items 23 | 15, dY items per co tile 4 | 8
-    constexpr int NIT = NXI + 2 * NDT;                  // 31 | 31
-    static_assert(NIT == 31, "31 items per stage: waves 0-6 issue four, wave 7 three");
-    constexpr int NJ = 4;
-    constexpr int XROWS = NXI * 8, DROWS = NDT * 8;     // LDS rows of the x region, of one dY tile
-    constexpr int STAGE = (XROWS + 2 * DROWS) * 64;     // bf16 elements: 248 rows of 128 B
-    constexpr int NST = 3;
+    typedef Halo8Shape<MODE> SH;
+    constexpr bool S2 = SH::S2;
+    constexpr int R = SH::R, PW = SH::PW, HP = SH::HP, HRP = SH::HRP, NHROW = SH::NHROW, NHR = SH::NHR, KSTEPS = SH::KSTEPS;
+    constexpr int NXI = SH::NXI, NDT = SH::NDT, NIT = SH::NIT, NJ = SH::NJ, XROWS = SH::XROWS, DROWS = SH::DROWS, STAGE = SH::STAGE, NST = SH::NST;
     extern __shared__ __attribute__((aligned(1024))) unsigned short smem[];
     typedef __attribute__((address_space(3))) void* lds_ptr;
 
@@ -70,15 +80,8 @@ __global__ __launch_bounds__(512, 2) void wgrad_halo8_bf16_kernel(const WgradHal
     const shm_u32x4 rsx = second ? shm_rsrc_words(a.x2, a.x2bytes) : shm_rsrc_words(a.x, a.xbytes);
     const shm_u32x4 rsd = shm_rsrc_words(a.dy, a.dybytes);
 
-    int n, pr, pc;                                      // patch origin in OUTPUT pixels
-    {
-        const int ppc = ho / R, ppi = ppc * (wo / PW);             // patches numbered down the columns of an image, see wgrad_halo_kernel
-        const int p = pid0 < a.npatch ? pid0 : 0;
-        n = p / ppi;
-        const int r = p - n * ppi;
-        pc = (r / ppc) * PW;
-        pr = (r % ppc) * R;
-    }
+    PatchWalk<R, PW> pw;                                // patch origin in OUTPUT pixels
+    pw.start(pid0, a.npatch, ho, wo);
     // per-lane constants of this wave's items (item = wave + 8 j): byte offset inside the halo / patch, and five mask bits -- which
     // edges of the halo the lane's pixel sits on (1 top, 2 bottom, 4 left, 8 right) and 16 for lanes with nothing to fetch
     unsigned off0[NJ], bm = 0;
@@ -91,16 +94,16 @@ __global__ __launch_bounds__(512, 2) void wgrad_halo8_bf16_kernel(const WgradHal
             int r_, c_;
             bool ok;
             if constexpr (S2) {
-                r_ = row / HRP;
-                const int t = row - r_ * HRP;
-                c_ = t < HP ? 2 * t : 2 * (t - HP) + 1;
-                ok = row < NHR && (t < HP ? t <= PW : true);
-                bits = (r_ == NHROW - 1 ? 2u : 0u) | (c_ == 2 * PW ? 8u : 0u);
+                const S2RunPixel px = s2_run_pixel<HRP, HP, PW>(row);
+                r_ = px.r;
+                c_ = px.c;
+                ok = row < NHR && px.ok;
+                bits = halo_pixel_bits(r_, c_, NHROW - 1, 2 * PW, false);
             } else {
                 r_ = row / HP;
                 c_ = row - r_ * HP;
                 ok = c_ < PW + 2;
-                bits = (r_ == 0 ? 1u : 0u) | (r_ == R + 1 ? 2u : 0u) | (c_ == 0 ? 4u : 0u) | (c_ == PW + 1 ? 8u : 0u);
+                bits = halo_pixel_bits(r_, c_, R + 1, PW + 1, true);
             }
             off0[j] = (unsigned)((r_ * a.w + c_) * ldX + ccX) * 2u;
             if (!(xvalid && ok)) bits = 16u;
@@ -115,9 +118,9 @@ __global__ __launch_bounds__(512, 2) void wgrad_halo8_bf16_kernel(const WgradHal
     }
     auto dma = [&](int stage) {
         unsigned short* sx = smem + stage * STAGE;
-        const int org = S2 ? (n * a.h + 2 * pr) * a.w + 2 * pc : (n * a.h + pr - 1) * a.w + (pc - 1);       // input pixel of halo (0, 0)
-        const unsigned edges = 16u | ((!S2 && pr == 0) ? 1u : 0u) | (pr + R == ho ? 2u : 0u) | ((!S2 && pc == 0) ? 4u : 0u) | (pc + PW == wo ? 8u : 0u);
-        const unsigned xb = (unsigned)(org * ldX) * 2u, db = (unsigned)(((n * ho + pr) * wo + pc) * a.lddy) * 2u;
+        const int org = S2 ? (pw.n * a.h + 2 * pw.pr) * a.w + 2 * pw.pc : (pw.n * a.h + pw.pr - 1) * a.w + (pw.pc - 1);       // input pixel of halo (0, 0)
+        const unsigned edges = pw.template edges<!S2>(ho, wo);
+        const unsigned xb = (unsigned)(org * ldX) * 2u, db = (unsigned)(((pw.n * ho + pw.pr) * wo + pw.pc) * a.lddy) * 2u;
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
             const int item = wave + 8 * j;
@@ -127,15 +130,7 @@ __global__ __launch_bounds__(512, 2) void wgrad_halo8_bf16_kernel(const WgradHal
                 shm_dma16(isx ? rsx : rsd, shm_lds_addr(sx + item * 512), off);
             }
         }
-        pr += R;
-        if (pr == ho) {
-            pr = 0;
-            pc += PW;
-            if (pc == wo) {
-                pc = 0;
-                ++n;
-            }
-        }
+        pw.next(ho, wo);
     };
 
     f32x16 acc[9];
@@ -144,19 +139,8 @@ __global__ __launch_bounds__(512, 2) void wgrad_halo8_bf16_kernel(const WgradHal
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
 
-    // transposed-read addresses (elements), as in wgrad_halo_bf16_kernel: the lane supplies row fq [+4 for the second read] and four
-    // channels of its 16-channel block.  S1: one address per kw (kw shifts the row, and with it bit 1 of the row index); S2: kw = 0 and
-    // kw = 1 are 20 rows apart (same bit 1: an immediate), kw = 2 is one row on
-    const int fq = 8 * hh + ((lane & 15) >> 2);                          // pixel of the K step this lane supplies (dY rows are in pixel order)
-    const int fqx = (MODE == 2 ? 2 * HRP * hh : 8 * hh) + ((lane & 15) >> 2);     // ... and its row in the x image (every term but the last is 0 mod 4)
-    const int fcol = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
-    int fa[3];
-#pragma unroll
-    for (int kw = 0; kw < 3; ++kw) {
-        const int row = fqx + (S2 ? (kw == 2 ? 1 : 0) : kw);
-        fa[kw] = row * 64 + ((mi * 32 + fcol) ^ (((row >> 1) & 1) << 5)) + ((S2 && kw == 1) ? HP * 64 : 0);
-    }
-    const int fb = fq * 64 + ((ni * 32 + fcol) ^ (((fq >> 1) & 1) << 5)) + (XROWS + cot * DROWS) * 64;
+    int fa[3], fb;                                      // transposed-read addresses: one per kw, and the dY fragment's in this wave's co tile
+    wgrad_tr_addrs<S2, HP, HRP, MODE == 2>(lane, mi, ni, (XROWS + cot * DROWS) * 64, fa, fb);
     auto compute = [&](int stage) {
         const unsigned short* X = smem + stage * STAGE;
 #pragma unroll
@@ -182,6 +166,8 @@ __global__ __launch_bounds__(512, 2) void wgrad_halo8_bf16_kernel(const WgradHal
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
     };
+    // The ring of wgrad_stage_ring (wgrad_halo_dev.h), written out: through the helper hipcc lays the loop out as wait / barrier / DMA / MFMA
+    // instead of MFMA-first -- the same instructions per stage, +0.2 to 0.6 % on n40 h32 1024x512 (311.5 -> 312.2 us) in three A/B runs, none this way
     if (nstages > 0) {
         dma(0);
         if (nstages > 1) dma(1);
@@ -198,24 +184,15 @@ __global__ __launch_bounds__(512, 2) void wgrad_halo8_bf16_kernel(const WgradHal
         }
     }
 
-    float* out = a.part + (size_t)blk.z * 9 * a.cin * a.cout;
-    const int con = co0 + 64 * cot + ni * 32 + l31;
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int ci = ci0 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-            if (ci < a.cin && con < a.cout) out[((size_t)t * a.cin + ci) * a.cout + con] = acc[t][r];
-        }
-    }
+    wgrad_store_slab<9, false>(acc, a.part + (size_t)blk.z * 9 * a.cin * a.cout, a.cin, a.cout, ci0, mi, hh, co0 + 64 * cot + ni * 32 + l31, nullptr);
 }
 
 template <int MODE>
 static int halo8_launch(const WgradHaloArgs& a, const WgradPlan& p, hipStream_t st) {
-    constexpr unsigned kLds8 = 3u * 248u * 128u;    // 93 KiB
-    static const hipError_t attr = hipFuncSetAttribute((const void*)wgrad_halo8_bf16_kernel<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds8);
-    SHM_REQUIRE(attr == hipSuccess, SHM_E_HIP, "shm_conv2d_wgrad: cannot reserve 93 KiB of LDS: %s", hipGetErrorString(attr));
-    hipLaunchKernelGGL((wgrad_halo8_bf16_kernel<MODE>), dim3(shm_cdiv(a.cin, 64), shm_cdiv(a.cout, 64 * kWgradHalo8CoTiles), p.splits), dim3(512), kLds8, st, a);
+    constexpr unsigned lds = Halo8Shape<MODE>::lds_bytes;
+    static const hipError_t attr = hipFuncSetAttribute((const void*)wgrad_halo8_bf16_kernel<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    SHM_REQUIRE(attr == hipSuccess, SHM_E_HIP, "shm_conv2d_wgrad: cannot reserve %g KiB of LDS: %s", lds / 1024.0, hipGetErrorString(attr));
+    hipLaunchKernelGGL((wgrad_halo8_bf16_kernel<MODE>), dim3(shm_cdiv(a.cin, 64), shm_cdiv(a.cout, 64 * kWgradHalo8CoTiles), p.splits), dim3(512), lds, st, a);
     shm_set_last_kernel("wgrad_halo8_bf16_kernel<%d>", MODE);
     return SHM_OK;
 }

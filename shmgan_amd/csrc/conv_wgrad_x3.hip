@@ -20,7 +20,7 @@
 // kernel costs ~150 vector instructions per lane and stage beside 3 456 matrix-pipe cycles; as a pass of its own it would write and
 // re-read 6 bytes per element of every activation and gradient tensor (~20 ms per step).  Per (K step of 16 pixels, tap): one x fragment per
 // plane meets the K step's three dY fragments: x0 three MFMAs, x1 two, x2 one.
-#include "wgrad.h"
+#include "wgrad_halo_dev.h"
 #include "x3split.h"
 
 
@@ -31,16 +31,26 @@
 // (columns 0, 2, .., 32 at LDS rows 0 .. 16) and an odd run (columns 1, 3, .., 31 at rows 20 .. 35), so that the sixteen pixels of a K step are sixteen
 // consecutive LDS rows for every kw (kw = 1: the odd run, kw = 2: the even run one row on).  TF SAME padding of an even map: nothing before the first
 // row / column, one zero row / column behind the last (out-of-image = out-of-range offset = zeros).
+// Stage geometry of wgrad_halo_x3_kernel<R, *, S2>: the kernel and its launcher read it
+template <int R, bool S2>
+struct WgradX3Shape {
+    static constexpr int PW = 16, HP = 20;                     // patch R x 16; S1: halo R + 2 rows, LDS pitch 20 (18 valid); S2: pitch of the even run
+    static constexpr int HRP = S2 ? 36 : HP;                   // LDS rows per halo row
+    static constexpr int NHROW = S2 ? 2 * R + 1 : R + 2;
+    static constexpr int NHR = NHROW * HRP, NPX = R * PW;      // S1, R = 2: 80 halo rows, 32 dY rows; S2: 180 halo rows
+    static constexpr int XP = NHR * 64, DP = NPX * 64;         // bf16 elements per x plane / dY plane
+    static constexpr int NXI = (NHR + 7) / 8, NDI = NPX / 8;   // items of 8 rows x 64 channels: 10 + 4 (S2: 23 + 4; the last x item's rows 180 .. 183 are not written)
+    static constexpr int NIT = NXI + NDI, NJ = (NIT + 3) / 4;  // items per wave: waves below NIT % 4 (or all) take NJ, the others NJ - 1
+    static constexpr unsigned tab_bytes = S2 ? 0u : 3u * 64u * 4u;     // (mean, inv, beta) x 64 of the normalising form; every unit-stride form reserves it
+    // R = 2: 42 KiB; R = 4: 69 KiB, two blocks per CU; S2: 79.5 KiB, two blocks per CU, just
+    static constexpr unsigned lds_bytes = (3u * XP + 3u * DP) * 2u + tab_bytes;
+};
+
 template <int R, bool NM = false, bool S2 = false>
 __global__ __launch_bounds__(256, 2) void wgrad_halo_x3_kernel(const WgradHaloArgs a) {
     static_assert(!S2 || (R == 2 && !NM), "stride 2: stages of two output rows, plain sources");
-    constexpr int PW = 16, HP = 20;                     // patch R x 16; S1: halo R + 2 rows, LDS pitch 20 (18 valid); S2: pitch of the even run
-    constexpr int HRP = S2 ? 36 : HP;                   // LDS rows per halo row
-    constexpr int NHROW = S2 ? 2 * R + 1 : R + 2;
-    constexpr int NHR = NHROW * HRP, NPX = R * PW;      // S1, R = 2: 80 halo rows, 32 dY rows; S2: 180 halo rows
-    constexpr int XP = NHR * 64, DP = NPX * 64;         // bf16 elements per x plane / dY plane
-    constexpr int NXI = (NHR + 7) / 8, NDI = NPX / 8;   // items of 8 rows x 64 channels: 10 + 4 (S2: 23 + 4; the last x item's rows 180 .. 183 are not written)
-    constexpr int NIT = NXI + NDI, NJ = (NIT + 3) / 4;  // items per wave: waves below NIT % 4 (or all) take NJ, the others NJ - 1
+    typedef WgradX3Shape<R, S2> SH;
+    constexpr int PW = SH::PW, HP = SH::HP, HRP = SH::HRP, NHROW = SH::NHROW, NHR = SH::NHR, XP = SH::XP, DP = SH::DP, NXI = SH::NXI, NIT = SH::NIT, NJ = SH::NJ;
     extern __shared__ __attribute__((aligned(1024))) unsigned short smem[];       // [x plane 0..2][dY plane 0..2][NM: mean, inv, beta x 64]
     [[maybe_unused]] float* const tab = (float*)(smem + 3 * XP + 3 * DP);
 
@@ -70,15 +80,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo_x3_kernel(const WgradHaloAr
     const __amdgpu_buffer_rsrc_t rsd = __builtin_amdgcn_make_buffer_rsrc((void*)a.dy, 0, a.dybytes, 0x00020000);
 
     const int ho = S2 ? a.h / 2 : a.h, wo = S2 ? a.w / 2 : a.w;
-    int n, pr, pc;                                      // patch origin in OUTPUT pixels
-    {
-        const int ppc = ho / R, ppi = ppc * (wo / PW);             // patches numbered down the columns of an image, see wgrad_halo_kernel
-        const int p = pid0 < a.npatch ? pid0 : 0;
-        n = p / ppi;
-        const int r = p - n * ppi;
-        pc = (r / ppc) * PW;
-        pr = (r % ppc) * R;
-    }
+    PatchWalk<R, PW> pw;                                // patch origin in OUTPUT pixels
+    pw.start(pid0, a.npatch, ho, wo);
     // per-lane constant byte offset + patch origin, edge bits (five per item, one register), as in wgrad_halo_bf16_kernel -- fp32 elements here
     unsigned off0[NJ], bm = 0;
 #pragma unroll
@@ -88,15 +91,13 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo_x3_kernel(const WgradHaloAr
         if (item < NXI) {
             const int hp = 8 * item + drow;
             if constexpr (S2) {
-                const int r_ = hp / HRP, t_ = hp - r_ * HRP;
-                const int c_ = t_ < HP ? 2 * t_ : 2 * (t_ - HP) + 1;
-                const bool ok = hp < NHR && (t_ < HP ? t_ <= PW : true);
-                off0[j] = (unsigned)((r_ * a.w + c_) * ldX + ccX) * 4u;
-                bits = !(xvalid && ok) ? 16u : (r_ == NHROW - 1 ? 2u : 0u) | (c_ == 2 * PW ? 8u : 0u);
+                const S2RunPixel px = s2_run_pixel<HRP, HP, PW>(hp);
+                off0[j] = (unsigned)((px.r * a.w + px.c) * ldX + ccX) * 4u;
+                bits = !(xvalid && hp < NHR && px.ok) ? 16u : halo_pixel_bits(px.r, px.c, NHROW - 1, 2 * PW, false);
             } else {
                 const int r_ = hp / HP, c_ = hp - r_ * HP;
                 off0[j] = (unsigned)((r_ * a.w + c_) * ldX + ccX) * 4u;
-                bits = !(xvalid && c_ < PW + 2) ? 16u : (r_ == 0 ? 1u : 0u) | (r_ == R + 1 ? 2u : 0u) | (c_ == 0 ? 4u : 0u) | (c_ == PW + 1 ? 8u : 0u);
+                bits = !(xvalid && c_ < PW + 2) ? 16u : halo_pixel_bits(r_, c_, R + 1, PW + 1, true);
             }
         } else {
             const int q = 8 * (item - NXI) + drow;
@@ -110,13 +111,13 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo_x3_kernel(const WgradHaloAr
     [[maybe_unused]] int sn = 0, spr = 0, spc = 0;             // (NM) sample and origin of the patch the stage registers hold
     auto load = [&]() {
         if constexpr (NM) {
-            sn = n;
-            spr = pr;
-            spc = pc;
+            sn = pw.n;
+            spr = pw.pr;
+            spc = pw.pc;
         }
-        const int org = S2 ? (n * a.h + 2 * pr) * a.w + 2 * pc : (n * a.h + pr - 1) * a.w + (pc - 1);       // input pixel index of halo (0,0)
-        const unsigned edges = 16u | ((!S2 && pr == 0) ? 1u : 0u) | (pr + R == ho ? 2u : 0u) | ((!S2 && pc == 0) ? 4u : 0u) | (pc + PW == wo ? 8u : 0u);
-        const unsigned xb = (unsigned)(org * ldX) * 4u, db = (unsigned)(((n * ho + pr) * wo + pc) * a.lddy) * 4u;
+        const int org = S2 ? (pw.n * a.h + 2 * pw.pr) * a.w + 2 * pw.pc : (pw.n * a.h + pw.pr - 1) * a.w + (pw.pc - 1);       // input pixel index of halo (0,0)
+        const unsigned edges = pw.template edges<!S2>(ho, wo);
+        const unsigned xb = (unsigned)(org * ldX) * 4u, db = (unsigned)(((pw.n * ho + pw.pr) * wo + pw.pc) * a.lddy) * 4u;
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
             const int item = wave + 4 * j;
@@ -127,15 +128,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo_x3_kernel(const WgradHaloAr
                 sr[j][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(isx ? rsx : rsd, off == 0xffffffffu ? off : off + 16u, 0, 0));
             }
         }
-        pr += R;
-        if (pr == ho) {
-            pr = 0;
-            pc += PW;
-            if (pc == wo) {
-                pc = 0;
-                ++n;
-            }
-        }
+        pw.next(ho, wo);
     };
     // split the stage registers and write the six plane images
     const bool nm_on = NM && a.nt != nullptr && (int)second == a.ntpart;        // block-uniform
@@ -201,18 +194,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo_x3_kernel(const WgradHaloAr
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
 
-    // transposed-read addresses (elements), as in wgrad_halo_bf16_kernel: the lane supplies row 8 hh + (i >> 2) [+ 4 for the second read] and
-    // channels [32 tile + 16 (g & 1) + 4 (i & 3), + 4); tap and K step enter as immediates, kw shifts the row and with it bit 1 of the row index
-    const int fq = 8 * hh + ((lane & 15) >> 2);
-    const int fcol = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
-    int fa[3];
-#pragma unroll
-    for (int kw = 0; kw < 3; ++kw) {
-        // S1: kw shifts the row; S2: kw = 0 / 2 read the even run (2 = one row on), kw = 1 the odd run HP rows further (same bit 1: HP % 4 == 0)
-        const int row = fq + (S2 ? (kw == 2 ? 1 : 0) : kw);
-        fa[kw] = row * 64 + ((mi * 32 + fcol) ^ (((row >> 1) & 1) << 5)) + ((S2 && kw == 1) ? HP * 64 : 0);
-    }
-    const int fb = 3 * XP + fq * 64 + ((ni * 32 + fcol) ^ (((fq >> 1) & 1) << 5));
+    int fa[3], fb;                                      // transposed-read addresses: one per kw in an x plane, and the dY fragment's behind the x planes
+    wgrad_tr_addrs<S2, HP, HRP>(lane, mi, ni, 3 * XP, fa, fb);
     auto compute = [&]() {
 #pragma unroll
         for (int qr = 0; qr < R; ++qr) {
@@ -259,16 +242,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_halo_x3_kernel(const WgradHaloAr
         }
     }
 
-    float* out = a.part + (size_t)blk.z * 9 * a.cin * a.cout;
-    const int con = co0 + ni * 32 + l31;
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int ci = ci0 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-            if (ci < a.cin && con < a.cout) out[((size_t)t * a.cin + ci) * a.cout + con] = acc[t][r];
-        }
-    }
+    wgrad_store_slab<9, false>(acc, a.part + (size_t)blk.z * 9 * a.cin * a.cout, a.cin, a.cout, ci0, mi, hh, co0 + ni * 32 + l31, nullptr);
 }
 
 int shm_wgrad_x3_launch(const WgradHaloArgs& hgs, const WgradPlan& p, hipStream_t st) {
@@ -276,22 +250,22 @@ int shm_wgrad_x3_launch(const WgradHaloArgs& hgs, const WgradPlan& p, hipStream_
     const int rows = p.rows;
     const bool nm = hgs.nt != nullptr;               // SHM_NORM_EXACT source
     if (p.stride2) {
-        constexpr unsigned kLds = (3u * 180 + 3u * 32) * 128u;       // 79.5 KiB: two blocks per CU, just
+        constexpr unsigned kLds = WgradX3Shape<2, true>::lds_bytes;
         SHM_REQUIRE(!nm && rows == 2, SHM_E_SHAPE, "shm_conv2d_wgrad: the stride-2 x3 form takes plain sources and stages of two rows");
         static const hipError_t attr = hipFuncSetAttribute((const void*)wgrad_halo_x3_kernel<2, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
-        SHM_REQUIRE(attr == hipSuccess, SHM_E_HIP, "shm_conv2d_wgrad: cannot reserve 79.5 KiB of LDS: %s", hipGetErrorString(attr));
+        SHM_REQUIRE(attr == hipSuccess, SHM_E_HIP, "shm_conv2d_wgrad: cannot reserve %g KiB of LDS: %s", kLds / 1024.0, hipGetErrorString(attr));
         hipLaunchKernelGGL((wgrad_halo_x3_kernel<2, false, true>), grid, dim3(256), kLds, st, hgs);
         shm_set_last_kernel("wgrad_halo_x3_kernel<2, false, true>");
         return SHM_OK;
     }
     if (rows == 4) {
-        constexpr unsigned kLds = (3u * (6 * 20) + 3u * (4 * 16)) * 128u + 768u;      // 69 KiB: two blocks per CU
+        constexpr unsigned kLds = WgradX3Shape<4, false>::lds_bytes;
         SHM_REQUIRE(!nm, SHM_E_SHAPE, "shm_conv2d_wgrad: the normalising x3 form runs stages of two rows");
         static const hipError_t attr = hipFuncSetAttribute((const void*)wgrad_halo_x3_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
-        SHM_REQUIRE(attr == hipSuccess, SHM_E_HIP, "shm_conv2d_wgrad: cannot reserve 69 KiB of LDS: %s", hipGetErrorString(attr));
+        SHM_REQUIRE(attr == hipSuccess, SHM_E_HIP, "shm_conv2d_wgrad: cannot reserve %g KiB of LDS: %s", kLds / 1024.0, hipGetErrorString(attr));
         hipLaunchKernelGGL((wgrad_halo_x3_kernel<4>), grid, dim3(256), kLds, st, hgs);
     } else {
-        constexpr unsigned kLds = (3u * (4 * 20) + 3u * (2 * 16)) * 128u + 768u;      // 42 KiB
+        constexpr unsigned kLds = WgradX3Shape<2, false>::lds_bytes;
         if (nm) hipLaunchKernelGGL((wgrad_halo_x3_kernel<2, true>), grid, dim3(256), kLds, st, hgs);
         else hipLaunchKernelGGL((wgrad_halo_x3_kernel<2>), grid, dim3(256), kLds, st, hgs);
     }

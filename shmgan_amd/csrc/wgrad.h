@@ -1,6 +1,7 @@
-// Shared pieces of the weight-gradient kernels: block order, the argument blocks, the transposed bf16 fragment read, the launcher's plan, and
-// the launch function each kernel family's translation unit sits behind (conv_wgrad_gen.hip, conv_wgrad_halo.hip, conv_wgrad_halo16.hip,
-// conv_wgrad_halo8.hip, conv_wgrad_x3.hip).  conv_wgrad.hip has the entry points, the plan (wgrad_plan) and the launcher: see its header comment.
+// Shared pieces of the weight-gradient kernels: block order, the argument blocks, the transposed bf16 fragment read, the slab epilogue, the
+// launcher's plan, and the launch function each kernel family's translation unit sits behind (conv_wgrad_gen.hip, conv_wgrad_halo.hip,
+// conv_wgrad_halo16.hip, conv_wgrad_halo8.hip, conv_wgrad_x3.hip).  wgrad_halo_dev.h has what only the halo-staged kernels share (patch walk, edge
+// bits, stage ring).  conv_wgrad.hip has the entry points, the plan (wgrad_plan) and the launcher: see its header comment.
 #pragma once
 #include "common.h"
 #include "ablate.h"
@@ -84,6 +85,32 @@ __device__ __forceinline__ f32x4 load16_drained(const float* p) {
     f32x4 v;
     asm volatile("global_load_dwordx4 %0, %1, off\n\ts_waitcnt vmcnt(0)" : "=&v"(v) : "v"(p) : "memory");
     return v;
+}
+
+// A wave's 32 x 32 sub-tile (mi, column con) of all NT taps of the partial slab `out` = [tap][cin][cout] of this block's split.  Row r of lane
+// half hh of an MFMA accumulator is channel ci0 + 32 mi + (r & 3) + 8 (r >> 2) + 4 hh.  SCALED (SHM_NORM_SCALED): row r times sc[r] on the way
+// out (scaling the accumulators in place made hipcc spill 100 registers).
+template <int NT, bool SCALED>
+__device__ __forceinline__ void wgrad_store_slab(const f32x16 (&acc)[NT], float* out, int cin, int cout, int ci0, int mi, int hh, int con, const float* sc) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int ci = ci0 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+            if (ci < cin && con < cout) out[((size_t)t * cin + ci) * cout + con] = SCALED ? acc[t][r] * sc[r] : acc[t][r];
+        }
+    }
+}
+
+// SHM_NORM_SCALED: the slab's row scales = inv of the block's sample; iv points at the table entry of the lane's row 0 (channel ci0 + 32 mi + 4 hh
+// of its source), rows 4 g .. 4 g + 3 are eight channels on per g
+__device__ __forceinline__ void wgrad_row_scale(float (&sc)[16], const float* iv) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const f32x4 s4 = *(const f32x4*)(iv + 8 * g);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) sc[4 * g + e] = s4[e];
+    }
 }
 
 // What the shape-only sizing of shm_conv2d_wgrad_workspace allows for beside the split-K target (the plan uses the same constants)

@@ -178,7 +178,9 @@ def test_live_attention_step_is_the_same_with_the_d_backward_on_either_stream():
     d_bwd_on_lane the discriminator's branch runs its backward on the second stream while the generator's branches run theirs on
     the main one; each branch has a LeakyReLU-backward scratch of its own, so one step gives the same flat gradients and named
     losses whichever stream the D-loss backward is on, to the bound of two runs of one step
-    (test_train_loop_gpu.py::test_full_size_step_is_reproducible_over_many_runs: 1e-6, the float64 atomics)."""
+    (test_train_loop_gpu.py::test_full_size_step_is_reproducible_over_many_runs: 1e-6, the float64 atomics).
+    This run leaves the timing of the two streams to chance; test_sched_gpu.py::test_bf16_live_attention (case 6) is its forced-timing
+    form: the same step with the second stream serialised and delayed."""
     S, F, B = 64, 32, 1
     m, _, _ = _mk_live(S, F, B, dt="bfloat16")
     assert m._get_lane().stream is not None                 # there is a second stream for the schedule to use

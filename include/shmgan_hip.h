@@ -795,6 +795,64 @@ int shm_polar_maps(const float* const* view_ptrs, size_t n, const float* coef, f
 int shm_dofp_views(const void* src, int bits, int h, int w, size_t src_pitch, int pattern, const int* quad, int mode,
                    unsigned char* const* dst_ptrs, unsigned char* total, void* stream);
 
+/* ---- developing a polariser mosaic: black level, white balance, colour matrix, tone curve (csrc/dofp_develop.hip) ----
+ * shm_dofp_develop is shm_dofp_views with another finish: the same arguments, lattices, taps and numerators, and then, instead of the cut
+ * to 8 bits, a development of the UNROUNDED numerator.  Two more device arrays and one host array:
+ *   params       device int[SHM_DOFP_PARAMS], read by the kernel (so a balance estimated on the device needs no round trip):
+ *                [SHM_DOFP_P_BLACK + c]  black_c, the sensor's count for darkness, 0 .. 65535 - 16, c = 0 R, 1 G, 2 B
+ *                [SHM_DOFP_P_MUL + c]    mul_c, a uint32 in Q16 (its bit pattern), 65536 <= mul_c < 2^32: the host's round-half-up of
+ *                                        65535 * 65536 * wb_c / (white - black_c), wb normalised to a smallest entry of 1, every wb_c <= 16,
+ *                                        white - black_c >= 16
+ *                [SHM_DOFP_P_GAIN + c]   gain_c in Q10, 1024 = 1, 1 .. 16383: 1024 from the host, shm_dofp_wb_gray's estimate otherwise
+ *                [SHM_DOFP_P_FLAGS]      bit 0: apply the matrix
+ *                [SHM_DOFP_P_CCM + 3c + j]  ccm[c][j], signed Q10, |ccm| <= 8191 (row-major: output channel c from linear channel j)
+ *                [SHM_DOFP_P_WHITE]      white, the count of a saturated sample: not read by shm_dofp_develop, shm_dofp_wb_gray's
+ *                                        callers take their default `sat` from it
+ *   lut          device uint8[4096], 16-byte aligned: the tone table, indexed by the top 12 of 16 bits
+ *   params_host  host int[SHM_DOFP_PARAMS]: the caller's mirror of `params`; the refusals below are made from it (its gains are not read)
+ * Arithmetic, all integer.  N is a view's channel numerator exactly as above, with total weight 2^k (k as in `finish`, the 1 for G
+ * included); for `total`, N is the sum of the four views' numerators and k is 2 larger -- the UNROUNDED mean is developed, not the rounded
+ * views.  With c in {R, G, B}:
+ *   1. D = max(0, N - (black_c << k))                                   the pedestal, removed at numerator scale: no rounding
+ *   2. M_c = (mul_c * gain_c + 512) >> 10                               in 64 bits; M_c < 2^36
+ *   3. lin_c = min(65535, (D * M_c + (1 << (15 + k))) >> (16 + k))      in 64 bits: D < 2^23
+ *   4. with the matrix: lin'_c = clamp((sum_j ccm[c][j] * lin_j + 512) >> 10, 0, 65535)     arithmetic shift; the sum fits 32 bits because
+ *      of the clamp in 3, which is also what keeps a saturated highlight from wrapping.  Without: lin'_c = lin_c
+ *   5. out_c = lut[lin'_c >> 4]
+ * lin is within 1 unit of 65535 of the real-valued (N / 2^k - black_c) * 65535 wb_c gain_c / (white - black_c): 0.5 from its own rounding, at
+ * most 0.5 from mul_c, which is within 2^-17 relative of the real factor.  Gains of at least 1 and the clamp make an all-saturated pixel
+ * (255, 255, 255) under every balance.  SHM_DOFP_MONO develops its one numerator with channel 0's parameters and writes it to R, G and B.
+ * One launch, no atomics, no host synchronisation; the stores are shm_dofp_views'.  SHM_E_SHAPE before any launch for everything
+ * shm_dofp_views refuses, and for a null params, lut or params_host, a lut that is not 16-byte aligned, a mirror with black outside
+ * [0, 65519], mul below 65536, |ccm| above 8191 or unknown flag bits, and SHM_DOFP_MONO with a mirror whose three channels differ (black or
+ * mul) or whose matrix flag is set. */
+#define SHM_DOFP_P_BLACK 0
+#define SHM_DOFP_P_MUL 3
+#define SHM_DOFP_P_GAIN 6
+#define SHM_DOFP_P_FLAGS 9
+#define SHM_DOFP_P_CCM 10
+#define SHM_DOFP_P_WHITE 19
+#define SHM_DOFP_PARAMS 20
+#define SHM_DOFP_LUT 4096
+int shm_dofp_develop(const void* src, int bits, int h, int w, size_t src_pitch, int pattern, const int* quad, int mode,
+                     unsigned char* const* dst_ptrs, unsigned char* total, const int* params, const unsigned char* lut,
+                     const int* params_host, void* stream);
+/* Grey-world gains of one frame, left on the device (Bayer patterns only).  Over the COMPLETE 4 x 4 periods of the mosaic in which all 16
+ * samples are below `sat` (a clipped highlight must not pull the estimate), for every sample v of colour c:
+ *   S_c += max(0, v - black_c);  n_c += 1                               uint64, black_c from params_in
+ * and then  mean_c = (S_c << 8) / n_c, 0 when n_c == 0;  if any mean is 0 all three gains are 1024, otherwise
+ *   gain_c = min(16383, (max_j mean_j << 10) / mean_c)
+ * params_out (device int[SHM_DOFP_PARAMS]; may be params_in) becomes params_in with the three gains replaced: shm_dofp_develop on the
+ * same stream reads it.  ws: device unsigned long long[SHM_DOFP_WB_WS]; after the call ws[0..2] = S_c, ws[3..5] = n_c, ws[6..8] = the
+ * gains; it needs no clearing.  Integer sums: every reduction order gives the same bits.  Two launches (per-block sums of a
+ * grid-stride walk over the periods, then one block that adds them and finishes), no atomics, no host synchronisation.  SHM_E_SHAPE
+ * before any launch for a null pointer, bits outside [8, 16], a pattern that is not one of the four Bayer ones, h or w outside
+ * [4, 32768], src_pitch < w, or sat outside [1, 65536]. */
+#define SHM_DOFP_WB_BLOCKS 512
+#define SHM_DOFP_WB_WS 3088 /* 16 + 6 * SHM_DOFP_WB_BLOCKS */
+int shm_dofp_wb_gray(const void* src, int bits, int h, int w, size_t src_pitch, int pattern, const int* params_in, int sat,
+                     int* params_out, unsigned long long* ws, void* stream);
+
 /* ---- specular masks from the polarised views (csrc/specmask.hip) ------------------------------------------
  * Specular reflection is polarised, diffuse reflection is not: the polarised intensity sqrt(S1^2 + S2^2) of the Stokes fit, the part
  * SHM_POLAR_STOKES subtracts, thresholded and cleaned up, is a highlight mask of ONE sample that needs no label.  Three calls on one

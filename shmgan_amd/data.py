@@ -533,14 +533,19 @@ def trainer_frame(trainer):
     return frame() if callable(frame) else trainer.image_size
 
 
-CAPTURE_OPTIONS = ("capture_format", "dofp_dir", "dofp_pattern", "dofp_quad_angles", "dofp_bits", "dofp_demosaic")
+DEVELOP_OPTIONS = ("dofp_black", "dofp_white", "dofp_wb", "dofp_ccm", "dofp_tone", "dofp_sat")       # polar.DofpDevelop's fields; all None = no development
+CAPTURE_OPTIONS = ("capture_format", "dofp_dir", "dofp_pattern", "dofp_quad_angles", "dofp_bits", "dofp_demosaic") + DEVELOP_OPTIONS
 
 
 def capture_options(args, subdirs=PSD_SUBDIRS):
     """The capture options of a trainer's `args` as (subdirs, loader keywords): capture_format "views" (default: `subdirs` and
     today's loader) or "dofp" = a polariser-mosaic sensor, whose frames lie in dofp_dir ("DOFP") next to the diffuse directory
     (the last of `subdirs`) and are laid out as polar.DofpLayout(dofp_pattern, dofp_quad_angles, dofp_bits) says; dofp_demosaic
-    "bilinear" / "bin".  An unknown value raises ValueError naming the option, before anything is listed or allocated."""
+    "bilinear" / "bin".  dofp_black, dofp_white, dofp_wb, dofp_ccm, dofp_tone, dofp_sat: when at least one of them is given (not
+    None) the layout carries polar.DofpDevelop(black, white, wb, ccm, tone, sat) and the frames are developed inside the demosaic
+    launch; the development rides on the layout, so the loader keywords stay the three they were (given with capture_format "views",
+    where nothing could carry it, it is refused).  An unknown value raises ValueError
+    naming the option, before anything is listed or allocated."""
     from . import polar
     opt = lambda k, dflt: getattr(args, k, dflt)
     capture, demosaic = opt("capture_format", "views"), opt("dofp_demosaic", "bilinear")
@@ -548,12 +553,16 @@ def capture_options(args, subdirs=PSD_SUBDIRS):
         raise ValueError(f"capture_format {capture!r} is not one of {polar.CAPTURES}")
     if demosaic not in polar.DOFP_DEMOSAIC:
         raise ValueError(f"dofp_demosaic {demosaic!r} is not one of {polar.DOFP_DEMOSAIC}")
+    given = {k[5:]: opt(k, None) for k in DEVELOP_OPTIONS if opt(k, None) is not None}
     if capture == "views":
+        for k, v in given.items():          # it would be ignored: a development is a property of a mosaic's layout
+            raise ValueError(f"dofp_{k} {v!r} needs capture_format 'dofp', got 'views'")
         return tuple(subdirs), dict(capture="views", dofp=None, dofp_demosaic=demosaic)
     try:
-        layout = polar.DofpLayout(opt("dofp_pattern", "mono"), opt("dofp_quad_angles", (90, 45, 135, 0)), opt("dofp_bits", 8))
+        develop = polar.DofpDevelop(**given) if given else None
+        layout = polar.DofpLayout(opt("dofp_pattern", "mono"), opt("dofp_quad_angles", (90, 45, 135, 0)), opt("dofp_bits", 8), develop)
     except ValueError as e:
-        raise ValueError(str(e).replace("DofpLayout: ", "dofp_", 1)) from None
+        raise ValueError(str(e).replace("DofpLayout: ", "dofp_", 1).replace("DofpDevelop: ", "dofp_", 1)) from None
     dofp_dir = opt("dofp_dir", "DOFP")
     if not isinstance(dofp_dir, str) or not dofp_dir:
         raise ValueError(f"dofp_dir {dofp_dir!r} is not a directory name")

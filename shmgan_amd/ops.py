@@ -1419,7 +1419,9 @@ def dofp_views(mosaic, layout, mode="bilinear", total=False):
     mosaic: a uint8 or uint16 2-D device tensor with unit stride along a row; its stride 0 is the pitch.  layout: a
     polar.DofpLayout (anything with .pattern, .quad and .bits); a uint8 mosaic needs bits == 8, a uint16 one bits 9..16.  Returns
     four new uint8 [ho,wo,3] tensors in ascending polariser angle, and with `total` a fifth: the rounded mean of the four.
-    Asynchronous on the current stream."""
+    With layout.develop (a polar.DofpDevelop) the planes are developed instead -- black level, white balance, matrix, tone curve, in
+    the same single launch (shm_dofp_develop), after the two grey-world launches when its wb is "gray".  Asynchronous on the current
+    stream."""
     import ctypes as C
     if not isinstance(mosaic, torch.Tensor) or not mosaic.is_cuda or mosaic.dtype not in (torch.uint8, torch.uint16):
         raise TypeError(f"dofp_views takes a uint8 or uint16 device tensor, got {getattr(mosaic, 'dtype', type(mosaic))} on "
@@ -1437,9 +1439,69 @@ def dofp_views(mosaic, layout, mode="bilinear", total=False):
     quad = (C.c_int * 4)(*[int(q) for q in layout.quad])
     dp = (C.c_void_p * 4)(*[out[v].data_ptr() for v in range(4)])
     pitch = int(mosaic.stride(0)) if h > 1 else w
-    check(lib().shm_dofp_views(mosaic.data_ptr(), bits, h, w, pitch, DOFP_PATTERNS[layout.pattern], quad, DOFP_MODES[mode], dp,
-                               out[4].data_ptr() if total else None, _stream()), "shm_dofp_views")
+    develop = getattr(layout, "develop", None)
+    if develop is None:
+        check(lib().shm_dofp_views(mosaic.data_ptr(), bits, h, w, pitch, DOFP_PATTERNS[layout.pattern], quad, DOFP_MODES[mode], dp,
+                                   out[4].data_ptr() if total else None, _stream()), "shm_dofp_views")
+        return tuple(out[v] for v in range(out.shape[0]))
+    # developed views (shm_dofp_develop): the tables are on the device already; with wb "gray" the frame's own gains are estimated into a
+    # parameter block of this call's, which the development reads on the same stream -- nothing here waits for the device
+    params, lut, mirror = _dofp_tables(layout, mosaic.device)
+    if develop.wb == "gray":
+        params = _dofp_wb_gray(mosaic, layout, develop.saturation(layout), params)[1]
+    check(lib().shm_dofp_develop(mosaic.data_ptr(), bits, h, w, pitch, DOFP_PATTERNS[layout.pattern], quad, DOFP_MODES[mode], dp,
+                                 out[4].data_ptr() if total else None, params.data_ptr(), lut.data_ptr(), mirror, _stream()), "shm_dofp_develop")
     return tuple(out[v] for v in range(out.shape[0]))
+
+
+DOFP_PARAMS, DOFP_WB_WS = CONSTANTS["SHM_DOFP_PARAMS"], CONSTANTS["SHM_DOFP_WB_WS"]
+_DOFP_TABLES = {}          # (layout, device) -> (params int32 [DOFP_PARAMS], lut uint8 [4096]) on the device and the host mirror as a ctypes array
+
+
+def _dofp_tables(layout, device):
+    """The development tables of `layout` (layout.develop.table(layout)) on `device`: uploaded once, kept."""
+    import ctypes as C
+    key = (layout, torch.device(device))
+    if key not in _DOFP_TABLES:
+        params, lut, mirror = layout.develop.table(layout)
+        _DOFP_TABLES[key] = (torch.from_numpy(params.copy()).to(device), torch.from_numpy(lut.copy()).to(device),
+                             (C.c_int * DOFP_PARAMS)(*[int(v) for v in mirror]))
+    return _DOFP_TABLES[key]
+
+
+def _dofp_wb_gray(mosaic, layout, sat, params):
+    """shm_dofp_wb_gray on the current stream: (ws int64 [DOFP_WB_WS], params_out int32 [DOFP_PARAMS]), both new."""
+    h, w = (int(d) for d in mosaic.shape)
+    ws = torch.empty(DOFP_WB_WS, dtype=torch.int64, device=mosaic.device)
+    params_out = torch.empty(DOFP_PARAMS, dtype=torch.int32, device=mosaic.device)
+    check(lib().shm_dofp_wb_gray(mosaic.data_ptr(), int(layout.bits), h, w, int(mosaic.stride(0)) if h > 1 else w, DOFP_PATTERNS[layout.pattern],
+                                 params.data_ptr(), int(sat), params_out.data_ptr(), ws.data_ptr(), _stream()), "shm_dofp_wb_gray")
+    return ws, params_out
+
+
+def dofp_wb_gray(mosaic, layout, sat=None):
+    """Grey-world sums and gains of one Bayer polariser-mosaic frame (shm_dofp_wb_gray, include/shmgan_hip.h): (sums int64 [6] = S_r, S_g,
+    S_b, n_r, n_g, n_b over the complete 4 x 4 periods without a sample at or above `sat`, gains int64 [3] in Q10), device tensors filled
+    asynchronously on the current stream.  The black level is layout.develop's (0 without one); `sat` defaults to its saturation count, or
+    2^bits - 1 without one."""
+    if not isinstance(mosaic, torch.Tensor) or not mosaic.is_cuda or mosaic.dtype not in (torch.uint8, torch.uint16):
+        raise TypeError(f"dofp_wb_gray takes a uint8 or uint16 device tensor, got {getattr(mosaic, 'dtype', type(mosaic))} on "
+                        f"{getattr(mosaic, 'device', 'the host')}")
+    if mosaic.dim() != 2 or (mosaic.shape[1] > 1 and mosaic.stride(1) != 1):
+        raise ValueError(f"dofp_wb_gray takes a 2-D mosaic with unit stride along a row, got {tuple(mosaic.shape)} with strides {mosaic.stride()}")
+    if (mosaic.dtype == torch.uint8) != (int(layout.bits) == 8):
+        raise ValueError(f"dofp_wb_gray: a {mosaic.dtype} mosaic does not hold {layout.bits}-bit samples (uint8 is bits = 8, uint16 is bits 9..16)")
+    if dofp_period(layout.pattern) != 4:
+        raise ValueError(f"dofp_wb_gray needs a Bayer pattern, the layout is {layout.pattern!r}")
+    develop = getattr(layout, "develop", None)
+    if develop is None:
+        params = torch.zeros(DOFP_PARAMS, dtype=torch.int32, device=mosaic.device)
+        sat = (1 << int(layout.bits)) - 1 if sat is None else sat
+    else:
+        params = _dofp_tables(layout, mosaic.device)[0]
+        sat = develop.saturation(layout) if sat is None else sat
+    ws = _dofp_wb_gray(mosaic, layout, sat, params)[0]
+    return ws[:6], ws[6:9]
 
 
 # ---- specular masks from the polarised views (specmask.hip) -------------------------------------------

@@ -12,9 +12,12 @@ The same fit gives a label the capture already contains: the polarised intensity
 
 A polariser-mosaic sensor records the four views in one raw frame: `DofpLayout` describes such a sensor, `decode_mosaic` reads a frame
 file, `demosaic` (csrc/dofp.hip) splits it into the four views in ascending angle, and `sample_views` is the one place where "a sample's
-files" become "its four uint8 device views" for either kind of capture.
+files" become "its four uint8 device views" for either kind of capture.  A layout with a `DofpDevelop` has its
+frames developed inside that launch -- black level, white balance, colour matrix, tone curve (csrc/dofp_develop.hip; DESIGN.md section
+6o); `estimate_white_balance` gives the one grey-world balance of a whole capture.
 
-Importing this module needs no GPU; `polar_maps`, `specular_mask`, `demosaic`, `write_estimated_diffuse` and `write_specular_masks` run on one.
+Importing this module needs no GPU; `polar_maps`, `specular_mask`, `demosaic`, `estimate_white_balance`, `write_estimated_diffuse` and
+`write_specular_masks` run on one.
 
 Model: a linear polariser at angle theta in front of light with Stokes parameters (S0, S1, S2) passes
     I(theta) = 0.5 * (S0 + S1 cos 2 theta + S2 sin 2 theta)
@@ -23,6 +26,7 @@ sampled angles is an upper bound of it (exact only when one polariser happens to
 """
 from __future__ import annotations
 
+import functools
 import os
 import re
 from dataclasses import dataclass
@@ -30,6 +34,7 @@ from pathlib import Path
 
 import numpy as np
 
+from ._lib import CONSTANTS
 from .data import PSD_SUBDIRS, list_images
 
 # S0 = I0 + I90, S1 = I0 - I90, S2 = I45 - I135: the coefficients calcDOP hard-codes (SHM.py:1158-1160).  Its S0 uses two of the
@@ -138,17 +143,184 @@ DOFP_DEMOSAIC = ("bilinear", "bin")                            # views at the mo
 CAPTURES = ("views", "dofp")                                   # one file per polariser angle / one mosaic per sample
 
 
+DOFP_TONES = ("linear", "srgb")                                # or a gamma g in [1, 4]: x^(1/g)
+# the parameter block of shm_dofp_develop: offsets into its int32 words, from include/shmgan_hip.h
+DEVELOP_BLACK, DEVELOP_MUL, DEVELOP_GAIN, DEVELOP_FLAGS, DEVELOP_CCM, DEVELOP_WHITE, DEVELOP_PARAMS = (
+    CONSTANTS["SHM_DOFP_" + k] for k in ("P_BLACK", "P_MUL", "P_GAIN", "P_FLAGS", "P_CCM", "P_WHITE", "PARAMS"))
+
+
+def _triple(v, kind):
+    """v as a 3-tuple of `kind`: a scalar is repeated; anything else must hold three."""
+    if isinstance(v, (str, bytes, bool)):
+        raise TypeError
+    if isinstance(v, (int, float, np.integer, np.floating)):
+        v = (v, v, v)
+    v = tuple(v)
+    if len(v) != 3 or any(isinstance(x, (str, bytes, bool)) for x in v):
+        raise TypeError
+    return tuple(kind(x) for x in v)
+
+
+def _whole(x):
+    if isinstance(x, (float, np.floating)) and float(x) != int(x):
+        raise ValueError
+    return int(x)
+
+
+def tone_table(tone):
+    """The 4096 uint8 entries of a tone curve, indexed by the top 12 of 16 linear bits: round-to-nearest of 255 f(i / 4095), f the
+    identity ("linear"), the piecewise sRGB encoding ("srgb") or x^(1/g) for a gamma g."""
+    x = np.arange(4096, dtype=np.float64) / 4095.0
+    if tone == "linear":
+        f = x
+    elif tone == "srgb":
+        f = np.where(x <= 0.0031308, 12.92 * x, 1.055 * np.power(x, 1.0 / 2.4) - 0.055)
+    else:
+        f = np.power(x, 1.0 / float(tone))
+    return np.floor(255.0 * f + 0.5).astype(np.uint8)
+
+
+@dataclass(frozen=True)
+class DofpDevelop:
+    """How a polariser-mosaic frame is developed inside the demosaic launch (shm_dofp_develop, include/shmgan_hip.h): the sensor's
+    black level is removed, the colours are balanced, optionally mixed by a 3 x 3 matrix, and the 16-bit linear result is encoded
+    to 8 bits by a tone table.  black: the count for darkness, a scalar or an (R, G, B) triple.  white: the count of a saturated
+    sample, default 2^bits - 1 of the layout.  wb: the (R, G, B) balance, normalised so that its smallest entry is 1 (every entry
+    then at most 16), or "gray": grey-world gains estimated from every frame on the device (shm_dofp_wb_gray; Bayer patterns only;
+    estimate_white_balance gives ONE triple for a whole capture, which is what a rig under one illuminant should use).  ccm: a 3 x 3
+    row-major matrix applied to the balanced linear values (entries within +-7.99; Bayer patterns only).  tone: "srgb", "linear"
+    or a gamma in [1, 4].  sat: samples at or above it exclude their 4 x 4 period from the "gray" estimate, default `white`.
+    `table(layout)` is the one quantisation of these options: the kernel and the tests read nothing else."""
+    black: object = 0
+    white: object = None
+    wb: object = (1, 1, 1)
+    ccm: object = None
+    tone: object = "srgb"
+    sat: object = None
+
+    def __post_init__(self):
+        put = lambda k, v: object.__setattr__(self, k, v)
+        try:
+            black = _triple(self.black, _whole)
+        except (TypeError, ValueError, OverflowError):
+            raise ValueError(f"DofpDevelop: black {self.black!r} is not a count or three counts") from None
+        if not all(0 <= b <= 65535 - 16 for b in black):
+            raise ValueError(f"DofpDevelop: black {self.black!r} outside [0, 65519]")
+        put("black", black)
+        if self.white is not None:
+            try:
+                if isinstance(self.white, (bool, str)):
+                    raise TypeError
+                white = _whole(self.white)
+            except (TypeError, ValueError, OverflowError):
+                raise ValueError(f"DofpDevelop: white {self.white!r} is not a count") from None
+            if not 16 <= white <= 65535 or any(white - b < 16 for b in black):
+                raise ValueError(f"DofpDevelop: white {self.white!r} is not in [16, 65535] and at least 16 above black {black}")
+            put("white", white)
+        if isinstance(self.wb, str):
+            if self.wb != "gray":
+                raise ValueError(f"DofpDevelop: wb {self.wb!r} is not three gains or 'gray'")
+        else:
+            try:
+                wb = _triple(self.wb, float)
+            except (TypeError, ValueError):
+                raise ValueError(f"DofpDevelop: wb {self.wb!r} is not three gains or 'gray'") from None
+            if not all(np.isfinite(g) and g > 0 for g in wb):
+                raise ValueError(f"DofpDevelop: wb {self.wb!r} is not three positive gains")
+            if max(wb) > 16 * min(wb):
+                raise ValueError(f"DofpDevelop: wb {self.wb!r} spans more than a factor of 16")
+            put("wb", wb)
+        if self.ccm is not None:
+            try:
+                ccm = tuple(float(x) for x in np.asarray(self.ccm, dtype=np.float64).reshape(-1))
+            except (TypeError, ValueError):
+                raise ValueError(f"DofpDevelop: ccm {self.ccm!r} is not a 3 x 3 matrix") from None
+            if len(ccm) != 9 or not all(np.isfinite(x) for x in ccm):
+                raise ValueError(f"DofpDevelop: ccm {self.ccm!r} is not a 3 x 3 matrix")
+            if any(abs(int(np.floor(x * 1024 + 0.5))) > 8191 for x in ccm):
+                raise ValueError(f"DofpDevelop: ccm {self.ccm!r} has an entry outside +-8191 / 1024")
+            put("ccm", ccm)
+        if isinstance(self.tone, str):
+            if self.tone not in DOFP_TONES:
+                raise ValueError(f"DofpDevelop: tone {self.tone!r} is not one of {DOFP_TONES} or a gamma in [1, 4]")
+        else:
+            try:
+                if isinstance(self.tone, bool):
+                    raise TypeError
+                g = float(self.tone)
+            except (TypeError, ValueError):
+                raise ValueError(f"DofpDevelop: tone {self.tone!r} is not one of {DOFP_TONES} or a gamma in [1, 4]") from None
+            if not 1.0 <= g <= 4.0:
+                raise ValueError(f"DofpDevelop: tone {self.tone!r} is not one of {DOFP_TONES} or a gamma in [1, 4]")
+            put("tone", g)
+        if self.sat is not None:
+            try:
+                if isinstance(self.sat, (bool, str)):
+                    raise TypeError
+                sat = _whole(self.sat)
+            except (TypeError, ValueError, OverflowError):
+                raise ValueError(f"DofpDevelop: sat {self.sat!r} is not a count") from None
+            if not 1 <= sat <= 65536:
+                raise ValueError(f"DofpDevelop: sat {self.sat!r} outside [1, 65536]")
+            put("sat", sat)
+
+    def table(self, layout):
+        """(params int32 [20], lut uint8 [4096], mirror): the parameter block and tone table shm_dofp_develop reads for a sensor laid
+        out as `layout` (its pattern and bits), and the host copy of the block the entry point makes its refusals from.  Gains are
+        1024; wb "gray" leaves the balance to the device.  Arrays are read-only and shared between calls."""
+        return _develop_table(self, layout.pattern, layout.bits)
+
+    def saturation(self, layout):
+        """The count from which a sample excludes its period from the grey-world sums: `sat`, or the white level."""
+        return self.sat if self.sat is not None else int(self.table(layout)[0][DEVELOP_WHITE])
+
+
+@functools.lru_cache(maxsize=None)
+def _develop_table(dev, pattern, bits):
+    from fractions import Fraction
+    white = dev.white if dev.white is not None else (1 << bits) - 1
+    if any(white - b < 16 for b in dev.black):
+        raise ValueError(f"DofpDevelop: white {white} ({bits} bits) is not at least 16 above black {dev.black}")
+    wb = (1.0, 1.0, 1.0) if dev.wb == "gray" else dev.wb
+    if pattern == "mono":
+        if dev.wb == "gray":
+            raise ValueError("DofpDevelop: wb 'gray' needs a Bayer pattern, the layout is 'mono'")
+        if dev.ccm is not None:
+            raise ValueError("DofpDevelop: ccm needs a Bayer pattern, the layout is 'mono'")
+        if len(set(dev.black)) != 1 or len(set(wb)) != 1:
+            raise ValueError(f"DofpDevelop: black {dev.black} and wb {wb} must be the same for all channels of a 'mono' layout")
+    low = min(Fraction(g) for g in wb)
+    p = np.zeros(DEVELOP_PARAMS, dtype=np.int64)
+    for c in range(3):
+        mul = Fraction(65535 * 65536) * (Fraction(wb[c]) / low) / (white - dev.black[c])
+        p[DEVELOP_BLACK + c] = dev.black[c]
+        p[DEVELOP_MUL + c] = int(mul + Fraction(1, 2))              # floor(x + 1/2): round half up; 65536 <= mul < 2^32
+        p[DEVELOP_GAIN + c] = 1024
+    if dev.ccm is not None:
+        p[DEVELOP_FLAGS] = 1
+        p[DEVELOP_CCM:DEVELOP_CCM + 9] = [int(np.floor(x * 1024 + 0.5)) for x in dev.ccm]
+    p[DEVELOP_WHITE] = white
+    params = p.astype(np.uint32).view(np.int32)                     # mul travels as its bit pattern
+    lut = tone_table(dev.tone)
+    mirror = params.copy()
+    for a in (params, lut, mirror):
+        a.setflags(write=False)
+    return params, lut, mirror
+
+
 @dataclass(frozen=True)
 class DofpLayout:
     """How a polariser-mosaic sensor lays its samples out.  pattern: "mono", or the Bayer tile over the quads ("rggb", "bggr",
     "grbg", "gbrg": period 4).  quad_angles: the micro-polariser angles in degrees at quad positions (0,0), (0,1), (1,0), (1,1); Sony's
     IMX250MZR / MYR is (90, 45, 135, 0).  bits: the significant bits of a sample, LSB-aligned, 8..16 (8 = a uint8 mosaic; a
-    12-bit value stored in 16 bits is 12, an MSB-aligned 16-bit file is 16).
+    12-bit value stored in 16 bits is 12, an MSB-aligned 16-bit file is 16).  develop: None = the views are the raw counts cut to 8
+    bits (shm_dofp_views), or a DofpDevelop: black level, white balance, matrix and tone curve inside the demosaic launch.
     Views are always delivered in ASCENDING angle (`angles`), whatever the quad's order, so stokes_matrix(layout.angles) and the
     exact 45 / 135 exchange of mirror_views apply as they are; `quad` is the kernel's table, the view index at each quad position."""
     pattern: str = "mono"
     quad_angles: tuple = (90, 45, 135, 0)
     bits: int = 8
+    develop: DofpDevelop | None = None
 
     def __post_init__(self):
         if self.pattern not in DOFP_PATTERNS:
@@ -166,6 +338,10 @@ class DofpLayout:
             raise ValueError(f"DofpLayout: bits {self.bits!r} is not an integer in 8..16")
         object.__setattr__(self, "quad_angles", ang)
         object.__setattr__(self, "bits", int(self.bits))
+        if self.develop is not None:
+            if not isinstance(self.develop, DofpDevelop):
+                raise ValueError(f"DofpLayout: develop {self.develop!r} is not a polar.DofpDevelop or None")
+            self.develop.table(self)          # what this sensor cannot be developed with is refused here, by name
 
     @property
     def angles(self):
@@ -219,7 +395,8 @@ def decode_mosaic(path, layout):
 
 
 def demosaic(mosaic, layout, mode="bilinear", total=False, device=None):
-    """The four views (and with `total` their rounded mean) of one mosaic: ops.dofp_views.  mosaic: a uint8 / uint16 2-D device
+    """The four views (and with `total` their rounded mean) of one mosaic: ops.dofp_views, which develops them when the layout has
+    a `develop`.  mosaic: a uint8 / uint16 2-D device
     tensor, or a NumPy array, which is uploaded first (to `device`, default the current one).  Returns uint8 [ho,wo,3] device
     tensors in ascending polariser angle (layout.angles).  Asynchronous on the current stream."""
     import torch
@@ -232,6 +409,41 @@ def demosaic(mosaic, layout, mode="bilinear", total=False, device=None):
         dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         mosaic = torch.from_numpy(np.ascontiguousarray(mosaic)).to(dev)
     return ops.dofp_views(mosaic, layout, mode, total)
+
+
+def gray_gains(sums):
+    """The grey-world gains (Q10, 1024 = 1) of the six sums S_r, S_g, S_b, n_r, n_g, n_b of shm_dofp_wb_gray, by its own integer
+    arithmetic: mean_c = (S_c << 8) // n_c (0 for n_c == 0); identity gains if any mean is 0, else min(16383, (max mean << 10) // mean_c)."""
+    S, n = [int(x) for x in sums[:3]], [int(x) for x in sums[3:6]]
+    mean = [(S[c] << 8) // n[c] if n[c] else 0 for c in range(3)]
+    if not all(mean):
+        return (1024, 1024, 1024)
+    return tuple(min(16383, (max(mean) << 10) // m) for m in mean)
+
+
+def estimate_white_balance(data_dir, layout, dofp_dir="DOFP", sat=None, device=None):
+    """The grey-world balance of a WHOLE capture: the sums of shm_dofp_wb_gray (every complete 4 x 4 period without a sample at or
+    above `sat`, black level removed) added over all mosaics of data_dir/dofp_dir and finished on the host.  Returns the (R, G, B)
+    triple for DofpDevelop(wb=...), smallest entry 1.  One device round trip per frame: a one-off, not a loader path.  `sat`
+    defaults to the layout's development's (its white level), or 2^bits - 1 without one."""
+    import torch
+    from . import ops
+    if not isinstance(layout, DofpLayout):
+        raise ValueError(f"estimate_white_balance: layout must be a polar.DofpLayout, got {layout!r}")
+    if layout.pattern == "mono":
+        raise ValueError("estimate_white_balance needs a Bayer pattern, the layout is 'mono'")
+    files = list_images(os.path.join(data_dir, dofp_dir))
+    if not files:
+        raise ValueError(f"estimate_white_balance: no mosaics in {os.path.join(data_dir, dofp_dir)}")
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    total = [0] * 6
+    with torch.cuda.device(dev):
+        for f in files:
+            m = torch.from_numpy(decode_mosaic(f, layout)).to(dev)
+            sums, _ = ops.dofp_wb_gray(m, layout, sat)
+            total = [a + int(b) for a, b in zip(total, sums.cpu().tolist())]
+    gains = gray_gains(total)
+    return tuple(g / min(gains) for g in gains)
 
 
 MASK_OPTIONS = ("threshold", "floor", "open_radius", "dilate_radius")       # the keyword options of specular_mask

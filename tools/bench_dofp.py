@@ -1,11 +1,13 @@
 """shm_dofp_views (csrc/dofp.hip) on 2448 x 2048 frames, the Sony IMX250MZR / MYR's: microseconds per frame, achieved bytes/s and the
 share of the HBM peak, for 8-bit mono, 12-bit mono, 12-bit RGGB bilinear and 12-bit RGGB bin, with and without the total plane;
-and the host time PIL takes to decode the four view PNGs the one mosaic replaces.  A record for kernel work, not an acceptance number.
+and the host time PIL takes to decode the four view PNGs the one mosaic replaces; then shm_dofp_develop (csrc/dofp_develop.hip) on the
+same frames by the same protocol, beside the plain launch in the same run: 12-bit mono and RGGB, bilinear and bin, and 8-bit bilinear, without and with the
+colour matrix, and with wb "gray" including its two estimation launches.  A record for kernel work, not an acceptance number.
 
 Bytes are algorithmic and computed from the shapes here: the mosaic read once plus the planes written.  Device events around
 LAUNCHES launches, 2 warm-ups and 5 timed iterations, seeded data.  The launches rotate over SETS source / destination sets (more
 than the 256 MiB Infinity Cache together), so that a frame comes from and goes to HBM as a camera's next frame would.
-python tools/bench_dofp.py [--launches N] [--no-decode]"""
+python tools/bench_dofp.py [--launches N] [--no-decode] [--no-develop]"""
 import argparse
 import ctypes as C
 import io
@@ -47,6 +49,48 @@ def launcher(pattern, bits, mode, total, rng):
     return fn, H * W * np.dtype(dt).itemsize + nplanes * ho * wo * 3
 
 
+# the 8-bit rows: an 8-bit sensor's multiplier never fits 24 bits, so its product takes three multiplies where a 12-bit one takes two
+DEVELOP_CONFIGS = [("12-bit mono bilinear", "mono", 12, "bilinear"), ("12-bit mono bin", "mono", 12, "bin"),
+                   ("12-bit RGGB bilinear", "rggb", 12, "bilinear"), ("12-bit RGGB bin", "rggb", 12, "bin"),
+                   ("8-bit mono bilinear", "mono", 8, "bilinear"), ("8-bit RGGB bilinear", "rggb", 8, "bilinear")]
+CCM = ((1.6, -0.4, -0.2), (-0.3, 1.5, -0.2), (0.1, -0.6, 1.5))
+
+
+def develop_launcher(pattern, bits, mode, total, rng, what):
+    """(fn that launches on set i, bytes per launch) for what = "views" (the plain launch), "develop", "matrix" or "gray" (the two
+    grey-world launches and the development that reads their gains)."""
+    from shmgan_amd.polar import DofpDevelop, DofpLayout
+    L = _lib.lib()
+    ho, wo = ops.dofp_shape(H, W, pattern, mode)
+    nplanes = 5 if total else 4
+    quad = (C.c_int * 4)(*QUAD)
+    mono = pattern == "mono"
+    dt = np.uint8 if bits == 8 else np.uint16
+    lay = DofpLayout(pattern, bits=bits, develop=DofpDevelop(black=240 >> (12 - bits) if bits < 12 else 240, wb="gray" if what == "gray" else (1, 1, 1) if mono else (1.9, 1, 1.6),
+                                                             ccm=CCM if what == "matrix" else None, tone="srgb"))
+    params, lut, mirror = ops._dofp_tables(lay, torch.device("cuda", torch.cuda.current_device()))
+    sets = []
+    for _ in range(SETS):
+        src = torch.from_numpy(rng.integers(0, 1 << bits, (H, W)).astype(dt)).cuda()
+        out = torch.empty((nplanes, ho, wo, 3), dtype=torch.uint8, device="cuda")
+        sets.append((src, out, (C.c_void_p * 4)(*[out[v].data_ptr() for v in range(4)]), out[4].data_ptr() if total else None,
+                     torch.empty(ops.DOFP_WB_WS, dtype=torch.int64, device="cuda"), torch.empty(ops.DOFP_PARAMS, dtype=torch.int32, device="cuda")))
+    st = torch.cuda.current_stream().cuda_stream
+    pc, mc = ops.DOFP_PATTERNS[pattern], ops.DOFP_MODES[mode]
+
+    def fn(i):
+        src, _, dp, tp, ws, pout = sets[i % SETS]
+        if what == "views":
+            _lib.check(L.shm_dofp_views(src.data_ptr(), bits, H, W, W, pc, quad, mc, dp, tp, st), "shm_dofp_views")
+            return
+        p = params
+        if what == "gray":
+            _lib.check(L.shm_dofp_wb_gray(src.data_ptr(), bits, H, W, W, pc, params.data_ptr(), (1 << bits) - 1, pout.data_ptr(), ws.data_ptr(), st), "shm_dofp_wb_gray")
+            p = pout
+        _lib.check(L.shm_dofp_develop(src.data_ptr(), bits, H, W, W, pc, quad, mc, dp, tp, p.data_ptr(), lut.data_ptr(), mirror, st), "shm_dofp_develop")
+    return fn, H * W * np.dtype(dt).itemsize + nplanes * ho * wo * 3 + (4096 if what != "views" else 0)
+
+
 def timed(fn, launches, warm=2, n=5):
     """Median microseconds per launch over n timed iterations of `launches` launches (device events)."""
     us = []
@@ -85,6 +129,7 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--launches", type=int, default=1000)
     ap.add_argument("--no-decode", action="store_true")
+    ap.add_argument("--no-develop", action="store_true")
     a = ap.parse_args()
     rng = np.random.default_rng(0)
     print(f"shm_dofp_views, {W} x {H} frames, {SETS} buffer sets in rotation, {a.launches} launches per timed iteration")
@@ -100,3 +145,14 @@ if __name__ == "__main__":
         ms, nb = decode_time(rng)
         print(f"  PIL decode of the four {W} x {H} RGB view PNGs one mosaic replaces: {ms:.1f} ms on the host ({nb / 1e6:.1f} MB of files; noise "
               f"images at compress_level 1)")
+    if not a.no_develop:
+        print(f"shm_dofp_develop beside shm_dofp_views, same frames and protocol (black 240 of 4095, sRGB table; \"gray\" = the two estimation launches + the development)")
+        for name, pattern, bits, mode in DEVELOP_CONFIGS:
+            for total in (False, True):
+                row = {}
+                for what in ("views", "develop") + (() if pattern == "mono" else ("matrix", "gray")):
+                    fn, nbytes = develop_launcher(pattern, bits, mode, total, rng, what)
+                    row[what] = timed(fn, a.launches)[0]
+                    bw = nbytes / (row[what] * 1e-6)
+                    print(f"  {name:22s} {'+ total' if total else '       '} {what:8s}: {row[what]:8.2f} us  {bw / 1e12:5.2f} TB/s = {100 * bw / HBM_PEAK:4.1f} % of peak"
+                          f"   x{row[what] / row['views']:.2f} of the plain launch", flush=True)

@@ -853,6 +853,39 @@ int shm_dofp_develop(const void* src, int bits, int h, int w, size_t src_pitch, 
 int shm_dofp_wb_gray(const void* src, int bits, int h, int w, size_t src_pitch, int pattern, const int* params_in, int sat,
                      int* params_out, unsigned long long* ws, void* stream);
 
+/* ---- calibrating a polariser mosaic: dark frame, flat field, defect map (csrc/dofp_calibrate.hip) ---------------
+ * Runs on the raw mosaic, in front of shm_dofp_views / shm_dofp_develop / shm_dofp_wb_gray: each view is built from one photosite per quad,
+ * so a hot sample or a gain difference inside a quad exists in one view only and reads as polarisation once it is interpolated.
+ *   src, dst   uint8 when bits == 8, uint16 otherwise, as shm_dofp_views takes its src; h rows of w samples, rows src_pitch / dst_pitch
+ *              ELEMENTS apart.  dst must not overlap src (a defective site reads its neighbours from src); dst == src is refused.
+ *   dark       device uint16 [h,w], tight: the master dark frame, pedestal included.  Null: `pedestal` everywhere.
+ *   gain       device uint16 [h,w], tight, Q12 (4096 = 1), every entry in [SHM_DOFP_GAIN_MIN, SHM_DOFP_GAIN_MAX].  Null: 4096 everywhere.
+ *   defect     device uint8 [h,w], tight: non-zero marks a photosite to be replaced.  Null: none.
+ *   pedestal   the count the corrected dark level is put back to, 0 .. 65519: it is kept, not removed, so that the black level of
+ *              shm_dofp_develop and the grey-world estimate go on meaning what they mean and noise around black is not clipped at zero.
+ *   white      samples at or above it are saturated and pass through untouched, 1 .. 65536 (65536: none is).
+ * P = 2 for SHM_DOFP_MONO and 4 for the Bayer patterns (the pattern is read for nothing else); maxv = 2^bits - 1.  All integer, exact:
+ *   corr(y,x):  v = src[y,x]
+ *               if v >= white: return v                                    a saturated sample stays saturated
+ *               e = ((v - dark[y,x]) * gain[y,x] + 2048) >> 12             signed, arithmetic shift (floor); fits int32: |v - dark| <= 65535,
+ *                                                                          gain <= 16383
+ *               return clamp(pedestal + e, 0, maxv)
+ *   dst[y,x] = corr(y,x)                    where defect is null or defect[y,x] == 0
+ *            = (2 S + n) / (2 n)  (floor)   otherwise: S, n = sum and count of corr over those of the four same-lattice neighbours
+ *                                           (y-P,x) (y+P,x) (y,x-P) (y,x+P) that lie inside the image and are not themselves defective:
+ *                                           the round-half-up of their mean
+ *            = corr(y,x)                    if n == 0
+ * With dark == pedestal, gain == 4096 and no defects dst equals src for every sample <= maxv.  One launch, no atomics, no host
+ * synchronisation; a thread makes 8 consecutive samples of a row with one 8- or 16-byte access per array where base, pitch (tables: w)
+ * are multiples of 8 elements, single-element accesses otherwise (same values).  SHM_E_SHAPE before any launch, dst untouched, for
+ * everything shm_dofp_views refuses about src, bits, h, w, src_pitch and pattern, a null dst, dst_pitch < w, dst == src, pedestal outside
+ * [0, 65519] or white outside [1, 65536]. */
+#define SHM_DOFP_GAIN_MIN 1024
+#define SHM_DOFP_GAIN_MAX 16383
+int shm_dofp_calibrate(const void* src, int bits, int h, int w, size_t src_pitch, int pattern, const unsigned short* dark,
+                       const unsigned short* gain, const unsigned char* defect, int pedestal, int white, void* dst, size_t dst_pitch,
+                       void* stream);
+
 /* ---- specular masks from the polarised views (csrc/specmask.hip) ------------------------------------------
  * Specular reflection is polarised, diffuse reflection is not: the polarised intensity sqrt(S1^2 + S2^2) of the Stokes fit, the part
  * SHM_POLAR_STOKES subtracts, thresholded and cleaned up, is a highlight mask of ONE sample that needs no label.  Three calls on one

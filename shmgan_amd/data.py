@@ -534,7 +534,8 @@ def trainer_frame(trainer):
 
 
 DEVELOP_OPTIONS = ("dofp_black", "dofp_white", "dofp_wb", "dofp_ccm", "dofp_tone", "dofp_sat")       # polar.DofpDevelop's fields; all None = no development
-CAPTURE_OPTIONS = ("capture_format", "dofp_dir", "dofp_pattern", "dofp_quad_angles", "dofp_bits", "dofp_demosaic") + DEVELOP_OPTIONS
+CALIBRATION_OPTIONS = ("dofp_calibration",)       # the path of a saved polar.DofpCalibration; None = the frames are read as they are
+CAPTURE_OPTIONS = ("capture_format", "dofp_dir", "dofp_pattern", "dofp_quad_angles", "dofp_bits", "dofp_demosaic") + DEVELOP_OPTIONS + CALIBRATION_OPTIONS
 
 
 def capture_options(args, subdirs=PSD_SUBDIRS):
@@ -544,8 +545,10 @@ def capture_options(args, subdirs=PSD_SUBDIRS):
     "bilinear" / "bin".  dofp_black, dofp_white, dofp_wb, dofp_ccm, dofp_tone, dofp_sat: when at least one of them is given (not
     None) the layout carries polar.DofpDevelop(black, white, wb, ccm, tone, sat) and the frames are developed inside the demosaic
     launch; the development rides on the layout, so the loader keywords stay the three they were (given with capture_format "views",
-    where nothing could carry it, it is refused).  An unknown value raises ValueError
-    naming the option, before anything is listed or allocated."""
+    where nothing could carry it, it is refused).  dofp_calibration: the path of the sensor's calibration (polar.build_calibration(...)
+    .save(path); a polar.DofpCalibration itself is taken too): it is loaded here and rides on the layout in the same way, so every
+    frame is corrected on the device before it is demosaiced; refused with capture_format "views" like the development.  An unknown
+    value raises ValueError naming the option, before anything is listed or allocated."""
     from . import polar
     opt = lambda k, dflt: getattr(args, k, dflt)
     capture, demosaic = opt("capture_format", "views"), opt("dofp_demosaic", "bilinear")
@@ -554,15 +557,22 @@ def capture_options(args, subdirs=PSD_SUBDIRS):
     if demosaic not in polar.DOFP_DEMOSAIC:
         raise ValueError(f"dofp_demosaic {demosaic!r} is not one of {polar.DOFP_DEMOSAIC}")
     given = {k[5:]: opt(k, None) for k in DEVELOP_OPTIONS if opt(k, None) is not None}
+    calibration = opt("dofp_calibration", None)
     if capture == "views":
+        if calibration is not None:
+            raise ValueError(f"dofp_calibration {calibration!r} needs capture_format 'dofp', got 'views'")
         for k, v in given.items():          # it would be ignored: a development is a property of a mosaic's layout
             raise ValueError(f"dofp_{k} {v!r} needs capture_format 'dofp', got 'views'")
         return tuple(subdirs), dict(capture="views", dofp=None, dofp_demosaic=demosaic)
     try:
         develop = polar.DofpDevelop(**given) if given else None
-        layout = polar.DofpLayout(opt("dofp_pattern", "mono"), opt("dofp_quad_angles", (90, 45, 135, 0)), opt("dofp_bits", 8), develop)
+        if calibration is not None and not isinstance(calibration, polar.DofpCalibration):
+            if not isinstance(calibration, (str, os.PathLike)):
+                raise ValueError(f"DofpLayout: calibration {calibration!r} is not the path of a saved polar.DofpCalibration")
+            calibration = polar.DofpCalibration.load(calibration)
+        layout = polar.DofpLayout(opt("dofp_pattern", "mono"), opt("dofp_quad_angles", (90, 45, 135, 0)), opt("dofp_bits", 8), develop, calibration)
     except ValueError as e:
-        raise ValueError(str(e).replace("DofpLayout: ", "dofp_", 1).replace("DofpDevelop: ", "dofp_", 1)) from None
+        raise ValueError(str(e).replace("DofpLayout: ", "dofp_", 1).replace("DofpDevelop: ", "dofp_", 1).replace("DofpCalibration: ", "dofp_calibration: ", 1)) from None
     dofp_dir = opt("dofp_dir", "DOFP")
     if not isinstance(dofp_dir, str) or not dofp_dir:
         raise ValueError(f"dofp_dir {dofp_dir!r} is not a directory name")

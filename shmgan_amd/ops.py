@@ -1414,23 +1414,68 @@ def dofp_shape(h, w, pattern, mode):
     return (int(h), int(w)) if mode == "bilinear" else (int(h) // P, int(w) // P)
 
 
+def _dofp_check_mosaic(who, mosaic, bits):
+    """What every mosaic entry point refuses about its frame, by `who`; returns bits as an int."""
+    if not isinstance(mosaic, torch.Tensor) or not mosaic.is_cuda or mosaic.dtype not in (torch.uint8, torch.uint16):
+        raise TypeError(f"{who} takes a uint8 or uint16 device tensor, got {getattr(mosaic, 'dtype', type(mosaic))} on "
+                        f"{getattr(mosaic, 'device', 'the host')}")
+    if mosaic.dim() != 2 or (mosaic.shape[1] > 1 and mosaic.stride(1) != 1):
+        raise ValueError(f"{who} takes a 2-D mosaic with unit stride along a row, got {tuple(mosaic.shape)} with strides {mosaic.stride()}")
+    if (mosaic.dtype == torch.uint8) != (int(bits) == 8):
+        raise ValueError(f"{who}: a {mosaic.dtype} mosaic does not hold {bits}-bit samples (uint8 is bits = 8, uint16 is bits 9..16)")
+    return int(bits)
+
+
+_DOFP_CALIBRATIONS = {}          # (calibration, device) -> (dark uint16 [h,w] | None, gain uint16 [h,w] | None, defect uint8 [h,w] | None) on the device
+
+
+def _dofp_calibration_tables(cal, device):
+    """The tables of a polar.DofpCalibration on `device`: uploaded once, kept (the calibration's equality and hash go by its contents)."""
+    key = (cal, torch.device(device))
+    if key not in _DOFP_CALIBRATIONS:
+        _DOFP_CALIBRATIONS[key] = tuple(None if a is None else torch.from_numpy(a.copy()).to(device) for a in (cal.dark, cal.gain, cal.defect))
+    return _DOFP_CALIBRATIONS[key]
+
+
+def _dofp_calibrated(who, mosaic, cal):
+    """shm_dofp_calibrate of a checked mosaic into a new contiguous tensor, on the current stream."""
+    h, w = (int(d) for d in mosaic.shape)
+    if cal.shape is not None and (h, w) != cal.shape:
+        raise ValueError(f"{who}: the mosaic is {h} x {w}, the calibration tables are {cal.shape[0]} x {cal.shape[1]}")
+    if h < cal.period or w < cal.period:
+        raise ValueError(f"{who}: a {h} x {w} mosaic is smaller than one period of pattern {cal.pattern!r}")
+    dark, gain, defect = _dofp_calibration_tables(cal, mosaic.device)
+    out = torch.empty((h, w), dtype=mosaic.dtype, device=mosaic.device)
+    check(lib().shm_dofp_calibrate(mosaic.data_ptr(), cal.bits, h, w, int(mosaic.stride(0)) if h > 1 else w, DOFP_PATTERNS[cal.pattern],
+                                   _p(dark), _p(gain), _p(defect), cal.pedestal, cal.white_level, out.data_ptr(), w, _stream()),
+          "shm_dofp_calibrate")
+    return out
+
+
+def dofp_calibrate(mosaic, calibration):
+    """One polariser-mosaic frame corrected by its sensor's calibration (shm_dofp_calibrate, include/shmgan_hip.h, states the arithmetic):
+    dark frame removed around the pedestal, flat-field gain applied, defective photosites replaced by the rounded mean of their good
+    same-lattice neighbours; saturated samples pass through.  mosaic: as dofp_views takes it.  calibration: a polar.DofpCalibration, or a
+    polar.DofpLayout that carries one.  Returns a new contiguous tensor of the mosaic's dtype and size; the mosaic is not written.
+    dofp_views and dofp_wb_gray make this call themselves for a layout with a calibration.  Asynchronous on the current stream."""
+    cal = getattr(calibration, "calibration", calibration)
+    if cal is None or not all(hasattr(cal, k) for k in ("dark", "gain", "defect", "pedestal", "white_level")):
+        raise ValueError(f"dofp_calibrate takes a polar.DofpCalibration or a polar.DofpLayout that has one, got {calibration!r}")
+    _dofp_check_mosaic("dofp_calibrate", mosaic, cal.bits)
+    return _dofp_calibrated("dofp_calibrate", mosaic, cal)
+
+
 def dofp_views(mosaic, layout, mode="bilinear", total=False):
     """One polariser-mosaic frame -> its four views in one launch (shm_dofp_views, include/shmgan_hip.h, states the arithmetic).
     mosaic: a uint8 or uint16 2-D device tensor with unit stride along a row; its stride 0 is the pitch.  layout: a
     polar.DofpLayout (anything with .pattern, .quad and .bits); a uint8 mosaic needs bits == 8, a uint16 one bits 9..16.  Returns
     four new uint8 [ho,wo,3] tensors in ascending polariser angle, and with `total` a fifth: the rounded mean of the four.
     With layout.develop (a polar.DofpDevelop) the planes are developed instead -- black level, white balance, matrix, tone curve, in
-    the same single launch (shm_dofp_develop), after the two grey-world launches when its wb is "gray".  Asynchronous on the current
-    stream."""
+    the same single launch (shm_dofp_develop), after the two grey-world launches when its wb is "gray".  With layout.calibration (a
+    polar.DofpCalibration) the frame is corrected first (dofp_calibrate, one more launch into a new tensor) and all of that reads the
+    corrected mosaic.  Asynchronous on the current stream."""
     import ctypes as C
-    if not isinstance(mosaic, torch.Tensor) or not mosaic.is_cuda or mosaic.dtype not in (torch.uint8, torch.uint16):
-        raise TypeError(f"dofp_views takes a uint8 or uint16 device tensor, got {getattr(mosaic, 'dtype', type(mosaic))} on "
-                        f"{getattr(mosaic, 'device', 'the host')}")
-    if mosaic.dim() != 2 or (mosaic.shape[1] > 1 and mosaic.stride(1) != 1):
-        raise ValueError(f"dofp_views takes a 2-D mosaic with unit stride along a row, got {tuple(mosaic.shape)} with strides {mosaic.stride()}")
-    bits = int(layout.bits)
-    if (mosaic.dtype == torch.uint8) != (bits == 8):
-        raise ValueError(f"dofp_views: a {mosaic.dtype} mosaic does not hold {bits}-bit samples (uint8 is bits = 8, uint16 is bits 9..16)")
+    bits = _dofp_check_mosaic("dofp_views", mosaic, layout.bits)
     h, w = (int(d) for d in mosaic.shape)
     ho, wo = dofp_shape(h, w, layout.pattern, mode)
     if ho < 1 or wo < 1:
@@ -1438,6 +1483,8 @@ def dofp_views(mosaic, layout, mode="bilinear", total=False):
     out = torch.empty((5 if total else 4, ho, wo, 3), dtype=torch.uint8, device=mosaic.device)
     quad = (C.c_int * 4)(*[int(q) for q in layout.quad])
     dp = (C.c_void_p * 4)(*[out[v].data_ptr() for v in range(4)])
+    if getattr(layout, "calibration", None) is not None:          # everything below reads the corrected mosaic
+        mosaic = _dofp_calibrated("dofp_views", mosaic, layout.calibration)
     pitch = int(mosaic.stride(0)) if h > 1 else w
     develop = getattr(layout, "develop", None)
     if develop is None:
@@ -1483,16 +1530,12 @@ def dofp_wb_gray(mosaic, layout, sat=None):
     """Grey-world sums and gains of one Bayer polariser-mosaic frame (shm_dofp_wb_gray, include/shmgan_hip.h): (sums int64 [6] = S_r, S_g,
     S_b, n_r, n_g, n_b over the complete 4 x 4 periods without a sample at or above `sat`, gains int64 [3] in Q10), device tensors filled
     asynchronously on the current stream.  The black level is layout.develop's (0 without one); `sat` defaults to its saturation count, or
-    2^bits - 1 without one."""
-    if not isinstance(mosaic, torch.Tensor) or not mosaic.is_cuda or mosaic.dtype not in (torch.uint8, torch.uint16):
-        raise TypeError(f"dofp_wb_gray takes a uint8 or uint16 device tensor, got {getattr(mosaic, 'dtype', type(mosaic))} on "
-                        f"{getattr(mosaic, 'device', 'the host')}")
-    if mosaic.dim() != 2 or (mosaic.shape[1] > 1 and mosaic.stride(1) != 1):
-        raise ValueError(f"dofp_wb_gray takes a 2-D mosaic with unit stride along a row, got {tuple(mosaic.shape)} with strides {mosaic.stride()}")
-    if (mosaic.dtype == torch.uint8) != (int(layout.bits) == 8):
-        raise ValueError(f"dofp_wb_gray: a {mosaic.dtype} mosaic does not hold {layout.bits}-bit samples (uint8 is bits = 8, uint16 is bits 9..16)")
+    2^bits - 1 without one.  A layout with a calibration has the frame corrected first, as dofp_views does."""
+    _dofp_check_mosaic("dofp_wb_gray", mosaic, layout.bits)
     if dofp_period(layout.pattern) != 4:
         raise ValueError(f"dofp_wb_gray needs a Bayer pattern, the layout is {layout.pattern!r}")
+    if getattr(layout, "calibration", None) is not None:
+        mosaic = _dofp_calibrated("dofp_wb_gray", mosaic, layout.calibration)
     develop = getattr(layout, "develop", None)
     if develop is None:
         params = torch.zeros(DOFP_PARAMS, dtype=torch.int32, device=mosaic.device)

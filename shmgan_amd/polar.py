@@ -14,7 +14,9 @@ A polariser-mosaic sensor records the four views in one raw frame: `DofpLayout` 
 file, `demosaic` (csrc/dofp.hip) splits it into the four views in ascending angle, and `sample_views` is the one place where "a sample's
 files" become "its four uint8 device views" for either kind of capture.  A layout with a `DofpDevelop` has its
 frames developed inside that launch -- black level, white balance, colour matrix, tone curve (csrc/dofp_develop.hip; DESIGN.md section
-6o); `estimate_white_balance` gives the one grey-world balance of a whole capture.
+6o); `estimate_white_balance` gives the one grey-world balance of a whole capture.  A layout with a `DofpCalibration` has every frame
+corrected on the device first -- master dark, flat-field gain, defective photosites (csrc/dofp_calibrate.hip; DESIGN.md section 6p);
+`build_calibration` makes one from a stack of dark frames and a stack of flats.
 
 Importing this module needs no GPU; `polar_maps`, `specular_mask`, `demosaic`, `estimate_white_balance`, `write_estimated_diffuse` and
 `write_specular_masks` run on one.
@@ -308,6 +310,225 @@ def _develop_table(dev, pattern, bits):
     return params, lut, mirror
 
 
+# ---- calibrating the sensor: master dark, flat field, defect map (csrc/dofp_calibrate.hip) -------------------
+GAIN_MIN, GAIN_MAX = CONSTANTS["SHM_DOFP_GAIN_MIN"], CONSTANTS["SHM_DOFP_GAIN_MAX"]       # Q12, 4096 = 1
+DEFECT_HOT, DEFECT_UNUSABLE, DEFECT_RANGE = 1, 2, 4       # why build_calibration marked a site; the kernel reads non-zero
+
+
+def pattern_channels(pattern, h, w):
+    """The colour class of every photosite of an [h,w] mosaic under `pattern`, int [h,w]: 0 everywhere for "mono"; 0 R, 1 G, 2 B for a
+    Bayer tile, whose letter at colour block (by, bx) = ((y % 4) // 2, (x % 4) // 2) is pattern[2 by + bx]."""
+    if pattern not in DOFP_PATTERNS:
+        raise ValueError(f"pattern {pattern!r} is not one of {DOFP_PATTERNS}")
+    if pattern == "mono":
+        return np.zeros((h, w), dtype=np.int64)
+    blk = ((np.arange(h) % 4) // 2)[:, None] * 2 + ((np.arange(w) % 4) // 2)[None, :]
+    return np.array(["rgb".index(c) for c in pattern], dtype=np.int64)[blk]
+
+
+class DofpCalibration:
+    """What shm_dofp_calibrate (include/shmgan_hip.h states the arithmetic) corrects a polariser-mosaic frame with, before it is
+    demosaiced: dark = the master dark frame (uint16 [h,w], pedestal included; None = `pedestal` everywhere), gain = the flat-field gain
+    in Q12 (uint16 [h,w], 4096 = 1, every entry in [1024, 16383]; None = 1 everywhere), defect = the map of photosites to replace by the
+    mean of their good same-lattice neighbours (uint8 [h,w], non-zero = defective; build_calibration sets DEFECT_HOT, DEFECT_UNUSABLE or
+    DEFECT_RANGE; None = none).  pedestal: the count the corrected dark level is put back to (it is kept, so DofpDevelop.black goes on
+    meaning the sensor's black level).  white: samples at or above it are saturated and pass through untouched, default 2^bits - 1.
+    pattern, bits: the sensor's, as DofpLayout's; a layout takes only a calibration of its own pattern and bits.  reference: the
+    per-colour (S_c, n_c) build_calibration equalised the flat to, or None.
+
+    The arrays are copied and read-only.  Equality and hash go by a digest of the contents computed once here, so two loads of one file
+    are equal and a layout that carries a calibration stays hashable.  Refusals are ValueErrors by name."""
+
+    def __init__(self, dark=None, gain=None, defect=None, pedestal=0, white=None, pattern="mono", bits=8, reference=None):
+        import hashlib
+        if pattern not in DOFP_PATTERNS:
+            raise ValueError(f"DofpCalibration: pattern {pattern!r} is not one of {DOFP_PATTERNS}")
+        if isinstance(bits, bool) or not isinstance(bits, (int, np.integer)) or not 8 <= int(bits) <= 16:
+            raise ValueError(f"DofpCalibration: bits {bits!r} is not an integer in 8..16")
+        if isinstance(pedestal, (bool, str)) or not isinstance(pedestal, (int, np.integer)) or not 0 <= int(pedestal) <= 65535 - 16:
+            raise ValueError(f"DofpCalibration: pedestal {pedestal!r} is not a count in [0, 65519]")
+        if white is not None and (isinstance(white, (bool, str)) or not isinstance(white, (int, np.integer)) or not 1 <= int(white) <= 65536):
+            raise ValueError(f"DofpCalibration: white {white!r} is not a count in [1, 65536]")
+        shape, arrays = None, {}
+        for name, a, dtype in (("dark", dark, np.uint16), ("gain", gain, np.uint16), ("defect", defect, np.uint8)):
+            if a is not None:
+                if not isinstance(a, np.ndarray) or a.dtype != dtype:
+                    raise ValueError(f"DofpCalibration: {name} must be a {np.dtype(dtype).name} array, got "
+                                     f"{a.dtype if isinstance(a, np.ndarray) else type(a).__name__}")
+                if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] < 1 or (shape is not None and a.shape != shape):
+                    raise ValueError(f"DofpCalibration: {name} has shape {a.shape}, " + ("the tables are 2-D [h,w]" if shape is None or a.ndim != 2 else
+                                                                                        f"the other tables have {shape}"))
+                shape = a.shape
+                a = np.array(a, dtype=dtype, order="C", copy=True)
+                a.setflags(write=False)
+            arrays[name] = a
+        if arrays["gain"] is not None and (int(arrays["gain"].min()) < GAIN_MIN or int(arrays["gain"].max()) > GAIN_MAX):
+            raise ValueError(f"DofpCalibration: gain spans [{int(arrays['gain'].min())}, {int(arrays['gain'].max())}], outside the Q12 range "
+                             f"[{GAIN_MIN}, {GAIN_MAX}]")
+        if reference is not None:
+            try:
+                reference = tuple((int(s), int(n)) for s, n in reference)
+            except (TypeError, ValueError):
+                raise ValueError(f"DofpCalibration: reference {reference!r} is not a (S, n) pair per colour") from None
+            if len(reference) != (1 if pattern == "mono" else 3):
+                raise ValueError(f"DofpCalibration: reference {reference!r} is not a (S, n) pair per colour of pattern {pattern!r}")
+        self.dark, self.gain, self.defect = arrays["dark"], arrays["gain"], arrays["defect"]
+        self.pedestal, self.white, self.pattern, self.bits = int(pedestal), None if white is None else int(white), pattern, int(bits)
+        self.shape = None if shape is None else (int(shape[0]), int(shape[1]))
+        self._reference = reference
+        m = hashlib.sha256(repr((self.pedestal, self.white, self.pattern, self.bits, self.shape, reference)).encode())
+        for a in (self.dark, self.gain, self.defect):
+            m.update(b"-" if a is None else a.tobytes())
+        self.digest = m.hexdigest()
+        self._frozen = True
+
+    def __setattr__(self, k, v):
+        if getattr(self, "_frozen", False):
+            raise AttributeError(f"DofpCalibration is read-only (cannot set {k})")
+        object.__setattr__(self, k, v)
+
+    def __eq__(self, other):
+        return isinstance(other, DofpCalibration) and other.digest == self.digest
+
+    def __hash__(self):
+        return hash(self.digest)
+
+    def __repr__(self):
+        return (f"DofpCalibration({self.pattern!r}, bits={self.bits}, shape={self.shape}, pedestal={self.pedestal}, white={self.white}, "
+                f"digest={self.digest[:12]})")
+
+    @property
+    def period(self):
+        return 2 if self.pattern == "mono" else 4
+
+    @property
+    def white_level(self):
+        """The count from which a sample passes through untouched: `white`, or 2^bits - 1."""
+        return self.white if self.white is not None else (1 << self.bits) - 1
+
+    @property
+    def reference(self):
+        """The per-colour (S_c, n_c) of build_calibration: the sum and count of the dark-subtracted flat over the usable sites of colour
+        c (one class for "mono"; R, G, B otherwise); every good site's corrected flat is pedestal + S_c / n_c within the rounding.
+        None for a calibration without a flat field."""
+        return self._reference
+
+    def summary(self):
+        """dict(sites, hot, unusable, out_of_range, defective, gain_min, gain_max): the counts of the defect map's three reasons (a site may
+        have more than one), of its non-zero entries, and the gain's range in Q12 (4096, 4096 without a gain table)."""
+        d = self.defect if self.defect is not None else np.zeros((0, 0), dtype=np.uint8)
+        g = self.gain
+        return dict(sites=0 if self.shape is None else self.shape[0] * self.shape[1],
+                    hot=int(np.count_nonzero(d & DEFECT_HOT)), unusable=int(np.count_nonzero(d & DEFECT_UNUSABLE)),
+                    out_of_range=int(np.count_nonzero(d & DEFECT_RANGE)), defective=int(np.count_nonzero(d)),
+                    gain_min=4096 if g is None else int(g.min()), gain_max=4096 if g is None else int(g.max()))
+
+    def save(self, path):
+        """Write the calibration as an .npz (no pickle): the arrays that are not None, the scalars, and the reference as int64 [n, 2]."""
+        out = {k: getattr(self, k) for k in ("dark", "gain", "defect") if getattr(self, k) is not None}
+        out.update(pedestal=np.int64(self.pedestal), white=np.int64(-1 if self.white is None else self.white), bits=np.int64(self.bits),
+                   pattern=np.array(self.pattern))
+        if self._reference is not None:
+            out["reference"] = np.array(self._reference, dtype=np.int64).reshape(-1, 2)
+        with open(path, "wb") as f:
+            np.savez(f, **out)
+
+    @classmethod
+    def load(cls, path):
+        """The calibration `save` wrote; a file that is not one raises ValueError naming it."""
+        try:
+            with np.load(path, allow_pickle=False) as z:
+                white = int(z["white"])
+                return cls(*(z[k] if k in z.files else None for k in ("dark", "gain", "defect")), pedestal=int(z["pedestal"]),
+                           white=None if white < 0 else white, pattern=str(z["pattern"]), bits=int(z["bits"]),
+                           reference=[tuple(r) for r in z["reference"].tolist()] if "reference" in z.files else None)
+        except (KeyError, OSError, TypeError) as e:
+            raise ValueError(f"DofpCalibration: {path} is not a saved calibration ({type(e).__name__}: {e})") from None
+        except ValueError as e:
+            raise ValueError(f"{e} (loading {path})" if str(e).startswith("DofpCalibration: ") else
+                             f"DofpCalibration: {path} is not a saved calibration ({e})") from None
+
+
+def _stack_mean(files, layout, shape, who):
+    """(2 sum + N) // (2 N) of the decoded frames, int64 [h,w], and their shape: the round-half-up mean of a stack."""
+    total = None
+    for f in files:
+        a = decode_mosaic(f, layout)
+        if shape is not None and a.shape != shape:
+            raise ValueError(f"{who}: {f} is {a.shape[0]} x {a.shape[1]}, the frames before it are {shape[0]} x {shape[1]}")
+        shape = a.shape
+        total = a.astype(np.int64) if total is None else total + a
+    n = len(files)
+    return (2 * total + n) // (2 * n), shape
+
+
+def build_calibration(layout, dark_dir, flat_dir=None, hot_threshold=None, gain_limits=(0.5, 2.0), white=None):
+    """A DofpCalibration from a stack of dark frames and, optionally, a stack of flat frames of the sensor `layout` describes (its pattern
+    and bits; files as decode_mosaic reads them).  Exact integer NumPy on the host: a one-off, not a loader path.
+
+    The dark frames are taken with the lens capped, at the exposure and gain of the capture.  The FLAT FRAMES NEED UNPOLARISED, UNIFORM
+    ILLUMINATION -- an integrating sphere or a diffuser in front of the lens, and no polarising surface in the path: the reference level
+    is taken per colour over all four orientations, which is what equalises the four micro-polarisers, so any polarisation of the flat
+    light is calibrated INTO the gains and then out of every capture.  They should be well exposed and below saturation.
+
+      dark      = (2 sum D_i + N) // (2 N)                            the rounded mean of the dark stack
+      pedestal  = the lower median of dark
+      hot       = dark > pedestal + hot_threshold                     default 8 << (bits - 8): 8 byte units
+    Without flats: defect = hot, no gain table.  With flats:
+      fm        = the same rounded mean of the flat stack;  f = fm - dark
+      usable    = ~hot & (f > 0) & (fm < white)                       white: default 2^bits - 1
+      S_c, n_c  = sum and count of f over the usable sites of colour c (one class for "mono")
+      g         = (8192 S_c + n_c f) // (2 n_c f)                     the round-half-up of 4096 (S_c / n_c) / f
+      defect    = ~usable | g outside the Q12 images of gain_limits;  gain = g, 4096 at defects
+    The defect map holds the reason (DEFECT_HOT | DEFECT_UNUSABLE | DEFECT_RANGE).  ValueError naming the directory or file for an empty
+    directory, a frame of another size, or a colour without a usable site."""
+    if not isinstance(layout, DofpLayout):
+        raise ValueError(f"build_calibration: layout must be a polar.DofpLayout, got {layout!r}")
+    bits = layout.bits
+    thr = 8 << (bits - 8) if hot_threshold is None else int(hot_threshold)
+    if thr < 0:
+        raise ValueError(f"build_calibration: hot_threshold {hot_threshold!r} is negative")
+    try:
+        lo, hi = (int(np.floor(float(x) * 4096 + 0.5)) for x in gain_limits)
+    except (TypeError, ValueError):
+        raise ValueError(f"build_calibration: gain_limits {gain_limits!r} are not two factors") from None
+    if not GAIN_MIN <= lo <= 4096 <= hi <= GAIN_MAX:
+        raise ValueError(f"build_calibration: gain_limits {gain_limits!r} must enclose 1 inside [{GAIN_MIN / 4096}, {GAIN_MAX / 4096:.4f}]")
+    white_level = (1 << bits) - 1 if white is None else int(white)
+    plain = DofpLayout(layout.pattern, layout.quad_angles, bits)          # decode only: no size check against an older calibration
+    files = list_images(str(dark_dir))
+    if not files:
+        raise ValueError(f"build_calibration: no dark frames in {dark_dir}")
+    dark, shape = _stack_mean(files, plain, None, "build_calibration")
+    pedestal = int(np.sort(dark, axis=None)[(dark.size - 1) // 2])
+    hot = dark > pedestal + thr
+    defect = np.where(hot, DEFECT_HOT, 0).astype(np.uint8)
+    if flat_dir is None:
+        return DofpCalibration(dark.astype(np.uint16), None, defect, pedestal, white, layout.pattern, bits)
+    files = list_images(str(flat_dir))
+    if not files:
+        raise ValueError(f"build_calibration: no flat frames in {flat_dir}")
+    fm, _ = _stack_mean(files, plain, shape, "build_calibration")
+    f = fm - dark
+    usable = ~hot & (f > 0) & (fm < white_level)
+    chan = pattern_channels(layout.pattern, *shape)
+    gain = np.full(shape, 4096, dtype=np.int64)
+    reference = []
+    for c in range(1 if layout.pattern == "mono" else 3):
+        sel = usable & (chan == c)
+        S, n = int(f[sel].sum()), int(np.count_nonzero(sel))
+        if n == 0:
+            raise ValueError(f"build_calibration: no usable {'site' if layout.pattern == 'mono' else 'RGB'[c] + ' site'} in the flat frames of "
+                             f"{flat_dir} (hot, not above the dark frame, or at the white level {white_level})")
+        reference.append((S, n))
+        fc = f[sel]
+        gain[sel] = (8192 * S + n * fc) // (2 * n * fc)
+    out = usable & ((gain < lo) | (gain > hi))
+    defect |= np.where(~usable, DEFECT_UNUSABLE, 0).astype(np.uint8) | np.where(out, DEFECT_RANGE, 0).astype(np.uint8)
+    gain[defect != 0] = 4096
+    return DofpCalibration(dark.astype(np.uint16), gain.astype(np.uint16), defect, pedestal, white, layout.pattern, bits, reference)
+
+
 @dataclass(frozen=True)
 class DofpLayout:
     """How a polariser-mosaic sensor lays its samples out.  pattern: "mono", or the Bayer tile over the quads ("rggb", "bggr",
@@ -315,12 +536,15 @@ class DofpLayout:
     IMX250MZR / MYR is (90, 45, 135, 0).  bits: the significant bits of a sample, LSB-aligned, 8..16 (8 = a uint8 mosaic; a
     12-bit value stored in 16 bits is 12, an MSB-aligned 16-bit file is 16).  develop: None = the views are the raw counts cut to 8
     bits (shm_dofp_views), or a DofpDevelop: black level, white balance, matrix and tone curve inside the demosaic launch.
+    calibration: None, or the sensor's DofpCalibration (of this pattern and these bits): every frame is corrected on the device --
+    dark frame, flat field, defect map (shm_dofp_calibrate) -- before anything else reads it.
     Views are always delivered in ASCENDING angle (`angles`), whatever the quad's order, so stokes_matrix(layout.angles) and the
     exact 45 / 135 exchange of mirror_views apply as they are; `quad` is the kernel's table, the view index at each quad position."""
     pattern: str = "mono"
     quad_angles: tuple = (90, 45, 135, 0)
     bits: int = 8
     develop: DofpDevelop | None = None
+    calibration: DofpCalibration | None = None
 
     def __post_init__(self):
         if self.pattern not in DOFP_PATTERNS:
@@ -342,6 +566,14 @@ class DofpLayout:
             if not isinstance(self.develop, DofpDevelop):
                 raise ValueError(f"DofpLayout: develop {self.develop!r} is not a polar.DofpDevelop or None")
             self.develop.table(self)          # what this sensor cannot be developed with is refused here, by name
+        if self.calibration is not None:
+            cal = self.calibration
+            if not isinstance(cal, DofpCalibration):
+                raise ValueError(f"DofpLayout: calibration {cal!r} is not a polar.DofpCalibration or None")
+            if cal.pattern != self.pattern:
+                raise ValueError(f"DofpLayout: calibration is of pattern {cal.pattern!r}, the layout is {self.pattern!r}")
+            if cal.bits != self.bits:
+                raise ValueError(f"DofpLayout: calibration is of bits = {cal.bits}, the layout says bits = {self.bits}")
 
     @property
     def angles(self):
@@ -379,7 +611,8 @@ def check_capture(capture, dofp, dofp_demosaic="bilinear", who="PolarDataset"):
 
 def decode_mosaic(path, layout):
     """One raw mosaic file as a 2-D array: PIL mode "L" gives uint8 and needs layout.bits == 8; "I;16" / "I;16B" give uint16 (native
-    byte order) and need bits 9..16.  Anything else -- an RGB file is not a mosaic -- raises ValueError naming the file and its mode."""
+    byte order) and need bits 9..16.  Anything else -- an RGB file is not a mosaic -- raises ValueError naming the file and its mode, and
+    so does a frame whose size is not that of the layout's calibration tables, naming both sizes."""
     from PIL import Image
     with Image.open(path) as im:
         mode = im.mode
@@ -391,6 +624,9 @@ def decode_mosaic(path, layout):
             raise ValueError(f"{path} is not a polariser mosaic: PIL mode {mode!r} (a mosaic is one channel: 'L' for 8 bits, 'I;16' for 9..16)")
     if (a.dtype == np.uint8) != (layout.bits == 8):
         raise ValueError(f"{path} holds {8 * a.dtype.itemsize}-bit samples (PIL mode {mode!r}), the layout says bits = {layout.bits}")
+    cal = getattr(layout, "calibration", None)
+    if cal is not None and cal.shape is not None and tuple(a.shape) != cal.shape:          # here, where the file still has a name
+        raise ValueError(f"{path} is {a.shape[0]} x {a.shape[1]}, the layout's calibration tables are {cal.shape[0]} x {cal.shape[1]}")
     return a
 
 

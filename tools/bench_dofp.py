@@ -2,12 +2,14 @@
 share of the HBM peak, for 8-bit mono, 12-bit mono, 12-bit RGGB bilinear and 12-bit RGGB bin, with and without the total plane;
 and the host time PIL takes to decode the four view PNGs the one mosaic replaces; then shm_dofp_develop (csrc/dofp_develop.hip) on the
 same frames by the same protocol, beside the plain launch in the same run: 12-bit mono and RGGB, bilinear and bin, and 8-bit bilinear, without and with the
-colour matrix, and with wb "gray" including its two estimation launches.  A record for kernel work, not an acceptance number.
+colour matrix, and with wb "gray" including its two estimation launches; then shm_dofp_calibrate (csrc/dofp_calibrate.hip) at 8 and 12 bits, with
+all three tables and with the dark frame alone, beside a device copy of the same bytes and the plain RGGB demosaic launch of the same frame.
+A record for kernel work, not an acceptance number.
 
 Bytes are algorithmic and computed from the shapes here: the mosaic read once plus the planes written.  Device events around
 LAUNCHES launches, 2 warm-ups and 5 timed iterations, seeded data.  The launches rotate over SETS source / destination sets (more
 than the 256 MiB Infinity Cache together), so that a frame comes from and goes to HBM as a camera's next frame would.
-python tools/bench_dofp.py [--launches N] [--no-decode] [--no-develop]"""
+python tools/bench_dofp.py [--launches N] [--no-views] [--no-decode] [--no-develop] [--no-calibrate]"""
 import argparse
 import ctypes as C
 import io
@@ -91,6 +93,46 @@ def develop_launcher(pattern, bits, mode, total, rng, what):
     return fn, H * W * np.dtype(dt).itemsize + nplanes * ho * wo * 3 + (4096 if what != "views" else 0)
 
 
+def calibrate_launcher(bits, tables, rng, what):
+    """(fn that launches on set i, bytes per launch) for what = "calibrate", "copy" (one device-to-device copy that moves the same bytes:
+    half of them read, half written) or "views" (the plain RGGB bilinear demosaic of the same frame).  tables: which of dark, gain, defect
+    are given.  Every set has its own tables (0.1 % of the sites defective): the worst case -- a sensor's one calibration would stay in
+    the Infinity Cache between frames."""
+    L = _lib.lib()
+    dt = np.uint8 if bits == 8 else np.uint16
+    size = np.dtype(dt).itemsize
+    nbytes = 2 * H * W * size + H * W * sum(b for b, use in zip((2, 2, 1), tables) if use)
+    st = torch.cuda.current_stream().cuda_stream
+    pc = ops.DOFP_PATTERNS["rggb"]
+    quad = (C.c_int * 4)(*QUAD)
+    ped = ((1 << bits) - 1) // 16
+    sets = []
+    for _ in range(SETS):
+        src = torch.from_numpy(rng.integers(0, 1 << bits, (H, W)).astype(dt)).cuda()
+        if what == "copy":
+            sets.append((torch.empty(nbytes // 2, dtype=torch.uint8, device="cuda"), torch.empty(nbytes // 2, dtype=torch.uint8, device="cuda")))
+        elif what == "views":
+            out = torch.empty((4, H, W, 3), dtype=torch.uint8, device="cuda")
+            sets.append((src, out, (C.c_void_p * 4)(*[out[v].data_ptr() for v in range(4)])))
+        else:
+            dark = torch.from_numpy(rng.integers(ped // 2, 2 * ped, (H, W)).astype(np.uint16)).cuda() if tables[0] else None
+            gain = torch.from_numpy(rng.integers(3600, 4700, (H, W)).astype(np.uint16)).cuda() if tables[1] else None
+            defect = torch.from_numpy((rng.random((H, W)) < 1e-3).astype(np.uint8)).cuda() if tables[2] else None
+            sets.append((src, torch.empty_like(src), dark, gain, defect))
+    ptr = lambda t: None if t is None else t.data_ptr()
+
+    def fn(i):
+        s = sets[i % SETS]
+        if what == "copy":
+            s[1].copy_(s[0], non_blocking=True)
+        elif what == "views":
+            _lib.check(L.shm_dofp_views(s[0].data_ptr(), bits, H, W, W, pc, quad, 0, s[2], None, st), "shm_dofp_views")
+        else:
+            _lib.check(L.shm_dofp_calibrate(s[0].data_ptr(), bits, H, W, W, pc, ptr(s[2]), ptr(s[3]), ptr(s[4]), ped, (1 << bits) - 1, s[1].data_ptr(), W, st),
+                       "shm_dofp_calibrate")
+    return fn, (H * W * size + 4 * H * W * 3 if what == "views" else nbytes)
+
+
 def timed(fn, launches, warm=2, n=5):
     """Median microseconds per launch over n timed iterations of `launches` launches (device events)."""
     us = []
@@ -130,10 +172,12 @@ if __name__ == "__main__":
     ap.add_argument("--launches", type=int, default=1000)
     ap.add_argument("--no-decode", action="store_true")
     ap.add_argument("--no-develop", action="store_true")
+    ap.add_argument("--no-views", action="store_true")
+    ap.add_argument("--no-calibrate", action="store_true")
     a = ap.parse_args()
     rng = np.random.default_rng(0)
     print(f"shm_dofp_views, {W} x {H} frames, {SETS} buffer sets in rotation, {a.launches} launches per timed iteration")
-    for name, pattern, bits, mode in CONFIGS:
+    for name, pattern, bits, mode in ([] if a.no_views else CONFIGS):
         for total in (False, True):
             fn, nbytes = launcher(pattern, bits, mode, total, rng)
             us, all_us = timed(fn, a.launches)
@@ -156,3 +200,14 @@ if __name__ == "__main__":
                     bw = nbytes / (row[what] * 1e-6)
                     print(f"  {name:22s} {'+ total' if total else '       '} {what:8s}: {row[what]:8.2f} us  {bw / 1e12:5.2f} TB/s = {100 * bw / HBM_PEAK:4.1f} % of peak"
                           f"   x{row[what] / row['views']:.2f} of the plain launch", flush=True)
+    if not a.no_calibrate:
+        print("shm_dofp_calibrate beside a device copy of the same bytes and the plain RGGB bilinear demosaic of the same frame (every set has its own tables)")
+        for bits in (8, 12):
+            for name, tables in (("dark + gain + defect", (True, True, True)), ("dark only", (True, False, False))):
+                row = {}
+                for what in ("calibrate", "copy", "views"):
+                    fn, nbytes = calibrate_launcher(bits, tables, rng, what)
+                    row[what] = timed(fn, a.launches)[0]
+                    bw = nbytes / (row[what] * 1e-6)
+                    print(f"  {bits:2d}-bit {name:22s} {what:9s}: {row[what]:8.2f} us  {nbytes / 1e6:7.2f} MB  {bw / 1e12:5.2f} TB/s = {100 * bw / HBM_PEAK:4.1f} % of peak", flush=True)
+                print(f"  {bits:2d}-bit {name:22s} calibrate = x{row['calibrate'] / row['copy']:.2f} of the copy, x{row['calibrate'] / row['views']:.2f} of the demosaic launch", flush=True)

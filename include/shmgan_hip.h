@@ -886,6 +886,47 @@ int shm_dofp_calibrate(const void* src, int bits, int h, int w, size_t src_pitch
                        const unsigned short* gain, const unsigned char* defect, int pedestal, int white, void* dst, size_t dst_pitch,
                        void* stream);
 
+/* ---- merging an exposure bracket of polariser mosaics (csrc/dofp_merge.hip) ----------------------------------------
+ * A highlight is the part of a scene one exposure cannot hold: where all four photosites of a quad sit at the white level the four views are
+ * equal and the Stokes fit reads no polarisation exactly where the highlight is strongest.  A bracket of n exposures of a static scene is
+ * merged per photosite, on the raw mosaic, in front of shm_dofp_views / shm_dofp_develop / shm_dofp_wb_gray (and behind shm_dofp_calibrate
+ * of every page).
+ *   src_ptrs    HOST array of n DEVICE pointers, 2 <= n <= SHM_DOFP_MERGE_MAX: the pages, each uint8 when bits == 8 and uint16 otherwise, h
+ *               rows of w samples, rows src_pitch ELEMENTS apart (one pitch for all pages).  Read during the call; the pointers travel to the
+ *               kernel by value.  Page k was taken with exposure e_k, a positive integer <= 65535 in any unit (only ratios matter); e_min is
+ *               the smallest.
+ *   table       DEVICE uint32 [SHM_DOFP_MERGE_TABLE], indexed by the mask m of valid pages (bit k = page k), 1 <= m <= 2^n - 1:
+ *                 T_m    = sum of e_k over the set bits k of m
+ *                 mul[m] = floor((2 * (e_min << (f + SHM_DOFP_MERGE_Q)) + T_m) / (2 * T_m)),  f = 16 - bits
+ *               the round-half-up of e_min * 2^f * 2^20 / T_m, in [1, 2^(f+20)].  mul[0] and the entries from 2^n on are not read.
+ *   table_host  the caller's HOST mirror of table: the refusals are made from it (as shm_dofp_develop does with params_host).
+ *   black       the count for darkness.   white: the count from which a sample is saturated, 1 .. 2^bits (2^bits: none is).
+ *   dst         device uint16, rows dst_pitch elements apart; not one of the pages.
+ *   counts      device unsigned [SHM_DOFP_MERGE_MAX + 1] or null: counts[j] = the number of photosites with exactly j valid pages, so
+ *               counts[0] is what is still clipped in every page.  Cleared on the stream by this call and filled with integer atomics (the
+ *               same bits on every run); null: nothing is counted.
+ * Per photosite, all integer, exact:
+ *   page k is valid when v_k < white;  m = the mask of valid pages
+ *   E   = sum over the valid pages of (v_k - black)                        signed; |E| < 2^19
+ *   R   = (E * mul[m] + 2^19) >> 20                                        in int64, arithmetic shift (floor)
+ *   dst = clamp((black << f) + R, 0, 65535)                                m != 0
+ *       = min(65535, white << f)                                           m == 0
+ * Every unsaturated page votes, weighted by its exposure time (the maximum-likelihood estimate under photon noise, so no lower threshold is
+ * needed); the result is a 16-bit mosaic on the scale of the SHORTEST exposure with f fractional bits.  A site valid in the shortest page
+ * only comes out as exactly v << f; a valid site is always strictly below white << f.  mul is within 1/2 of the real factor and |E| < 2^19,
+ * so dst is within 0.75 of the real-valued quotient (0.5 from its own rounding, at most 0.25 from mul).
+ * One launch; the clear of counts is a second action on the stream; no host synchronisation.  A thread makes 8 consecutive samples of a row
+ * with one 16-byte (uint16) or 8-byte (uint8) access per page and one 16-byte store where base and pitch are multiples of 8 elements (each
+ * page and dst judged separately), single-element accesses otherwise (same values).  SHM_E_SHAPE before any launch, dst and counts untouched,
+ * for: a null src_ptrs, entry, table, table_host or dst; n outside [2, 8]; bits outside [8, 16]; h or w outside [1, 32768]; a pitch below w;
+ * dst equal to a page; black below 0 or black << f above 65519 (shm_dofp_develop's limit for a black level); white outside [1, 2^bits] or
+ * not above black; a table_host entry m in 1 .. 2^n - 1 outside [1, 2^(f+20)]. */
+#define SHM_DOFP_MERGE_MAX 8
+#define SHM_DOFP_MERGE_TABLE 256
+#define SHM_DOFP_MERGE_Q 20
+int shm_dofp_merge(const void* const* src_ptrs, int n, int bits, int h, int w, size_t src_pitch, const unsigned* table,
+                   const unsigned* table_host, int black, int white, unsigned short* dst, size_t dst_pitch, unsigned* counts, void* stream);
+
 /* ---- specular masks from the polarised views (csrc/specmask.hip) ------------------------------------------
  * Specular reflection is polarised, diffuse reflection is not: the polarised intensity sqrt(S1^2 + S2^2) of the Stokes fit, the part
  * SHM_POLAR_STOKES subtracts, thresholded and cleaned up, is a highlight mask of ONE sample that needs no label.  Three calls on one

@@ -16,7 +16,7 @@ _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ["SHM_LIB_PATH"]) if os.environ.get("SHM_LIB_PATH") else _HERE / "libshmgan_hip.so"
 CSRC = _HERE / "csrc"
 HEADER = _HERE.parent / "include" / "shmgan_hip.h"
-SOURCES = ["runtime.hip", "conv_igemm.hip", "conv_dma.hip", "conv_halo.hip", "conv_wreg.hip", "conv_wreg_f32.hip", "conv_phase4.hip", "conv_wreg16.hip", "conv_pingpong.hip", "conv_wgrad.hip", "conv_wgrad_gen.hip", "conv_wgrad_halo.hip", "conv_wgrad_halo16.hip", "conv_wgrad_halo8.hip", "conv_wgrad_x3.hip", "conv_fwd_x3.hip", "conv_rgb.hip", "elem.hip", "instnorm.hip", "instnorm_bwd.hip", "instnorm_bwd_2pass.hip", "instnorm_bwd_fused8.hip", "instnorm_bwd_fusedg.hip", "grad_sums.hip", "heads.hip", "dgrad_sum1.hip", "color.hip", "ema.hip", "imgloss.hip", "metrics.hip", "specseg.hip", "data.hip", "polar.hip", "dofp.hip", "dofp_develop.hip", "dofp_calibrate.hip", "specmask.hip", "augment.hip", "augment_batch.hip", "augment_pairs.hip", "export.hip", "detail.hip", "telemetry.hip", "specseg_train.hip"]
+SOURCES = ["runtime.hip", "conv_igemm.hip", "conv_dma.hip", "conv_halo.hip", "conv_wreg.hip", "conv_wreg_f32.hip", "conv_phase4.hip", "conv_wreg16.hip", "conv_pingpong.hip", "conv_wgrad.hip", "conv_wgrad_gen.hip", "conv_wgrad_halo.hip", "conv_wgrad_halo16.hip", "conv_wgrad_halo8.hip", "conv_wgrad_x3.hip", "conv_fwd_x3.hip", "conv_rgb.hip", "elem.hip", "instnorm.hip", "instnorm_bwd.hip", "instnorm_bwd_2pass.hip", "instnorm_bwd_fused8.hip", "instnorm_bwd_fusedg.hip", "grad_sums.hip", "heads.hip", "dgrad_sum1.hip", "color.hip", "ema.hip", "imgloss.hip", "metrics.hip", "specseg.hip", "data.hip", "polar.hip", "dofp.hip", "dofp_develop.hip", "dofp_calibrate.hip", "dofp_merge.hip", "specmask.hip", "augment.hip", "augment_batch.hip", "augment_pairs.hip", "export.hip", "detail.hip", "telemetry.hip", "specseg_train.hip"]
 # headers every source may include: a change of any of them rebuilds every object (tools/sanitize_host.py goes by the same list)
 SHARED_HEADERS = [CSRC / "common.h", CSRC / "elem.h", CSRC / "ablate.h", CSRC / "tapgemm.h", CSRC / "tapgemm_dev.h", CSRC / "wgrad.h", CSRC / "wgrad_halo_dev.h", CSRC / "in_bwd.h", CSRC / "x3split.h", CSRC / "polar_est.h", CSRC / "dofp_dev.h", CSRC / "augment_px.h", CSRC / "bilinear.h", CSRC / "yuv.h", HEADER]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-munsafe-fp-atomics",

@@ -17,7 +17,7 @@
 
 namespace {
 
-constexpr int CAL_N = 8;                        // samples per thread
+constexpr int CAL_N = DF_GROUP;                 // samples per thread (dofp_dev.h: df_load8, df_store8)
 constexpr int CAL_BX = 64;                      // threads along a row: 512 samples
 constexpr int CAL_BY = 4;                       // rows per block
 
@@ -28,46 +28,6 @@ struct CalArgs {
     int pedestal, white, maxv;
     int vsrc, vdst, vtab;                       // groups of CAL_N start aligned in the source / the destination / the tables
 };
-
-// CAL_N consecutive elements from p; `vec`: p is aligned to them and all of them lie inside the row
-__device__ __forceinline__ void cal_load(const unsigned short* p, bool vec, int nvalid, unsigned (&o)[CAL_N]) {
-    if (vec) {
-        const uint4 u = *(const uint4*)p;
-        o[0] = u.x & 0xffffu, o[1] = u.x >> 16, o[2] = u.y & 0xffffu, o[3] = u.y >> 16;
-        o[4] = u.z & 0xffffu, o[5] = u.z >> 16, o[6] = u.w & 0xffffu, o[7] = u.w >> 16;
-    } else {
-#pragma unroll
-        for (int j = 0; j < CAL_N; ++j) o[j] = j < nvalid ? (unsigned)p[j] : 0u;
-    }
-}
-__device__ __forceinline__ void cal_load(const unsigned char* p, bool vec, int nvalid, unsigned (&o)[CAL_N]) {
-    if (vec) {
-        const uint2 u = *(const uint2*)p;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = (u.x >> (8 * j)) & 0xffu, o[4 + j] = (u.y >> (8 * j)) & 0xffu;
-    } else {
-#pragma unroll
-        for (int j = 0; j < CAL_N; ++j) o[j] = j < nvalid ? (unsigned)p[j] : 0u;
-    }
-}
-__device__ __forceinline__ void cal_store(unsigned short* p, bool vec, int nvalid, const unsigned (&o)[CAL_N]) {
-    if (vec) {
-        *(uint4*)p = make_uint4(o[0] | o[1] << 16, o[2] | o[3] << 16, o[4] | o[5] << 16, o[6] | o[7] << 16);
-    } else {
-#pragma unroll
-        for (int j = 0; j < CAL_N; ++j)
-            if (j < nvalid) p[j] = (unsigned short)o[j];
-    }
-}
-__device__ __forceinline__ void cal_store(unsigned char* p, bool vec, int nvalid, const unsigned (&o)[CAL_N]) {
-    if (vec) {
-        *(uint2*)p = make_uint2(o[0] | o[1] << 8 | o[2] << 16 | o[3] << 24, o[4] | o[5] << 8 | o[6] << 16 | o[7] << 24);
-    } else {
-#pragma unroll
-        for (int j = 0; j < CAL_N; ++j)
-            if (j < nvalid) p[j] = (unsigned char)o[j];
-    }
-}
 
 // corr of the header: |v - dark| <= 65535 and gain <= 16383 keep the product inside int32; >> of a negative int is arithmetic here
 __device__ __forceinline__ unsigned cal_corr(unsigned v, unsigned dark, unsigned gain, const CalArgs& a) {
@@ -87,22 +47,22 @@ __global__ void __launch_bounds__(CAL_BX* CAL_BY) dofp_calibrate_kernel(const Ca
     const bool full = nvalid == CAL_N;
     const size_t t0 = (size_t)y * w + xg;                                  // the group's first element in the tight tables
     unsigned v[CAL_N], d[CAL_N], g[CAL_N], bad[CAL_N], o[CAL_N];
-    cal_load(src + (size_t)y * spitch + xg, full && a.vsrc, nvalid, v);
+    df_load8(src + (size_t)y * spitch + xg, full && a.vsrc, nvalid, v);
     if (a.dark) {
-        cal_load(a.dark + t0, full && a.vtab, nvalid, d);
+        df_load8(a.dark + t0, full && a.vtab, nvalid, d);
     } else {
 #pragma unroll
         for (int j = 0; j < CAL_N; ++j) d[j] = (unsigned)a.pedestal;
     }
     if (a.gain) {
-        cal_load(a.gain + t0, full && a.vtab, nvalid, g);
+        df_load8(a.gain + t0, full && a.vtab, nvalid, g);
     } else {
 #pragma unroll
         for (int j = 0; j < CAL_N; ++j) g[j] = 4096u;
     }
     unsigned any = 0u;
     if (a.defect) {
-        cal_load(a.defect + t0, full && a.vtab, nvalid, bad);
+        df_load8(a.defect + t0, full && a.vtab, nvalid, bad);
 #pragma unroll
         for (int j = 0; j < CAL_N; ++j) any |= bad[j];
     }
@@ -138,7 +98,7 @@ __global__ void __launch_bounds__(CAL_BX* CAL_BY) dofp_calibrate_kernel(const Ca
             if (n) o[j] = (2u * S + n) / (2u * n);
         }
     }
-    cal_store(dst + (size_t)y * dpitch + xg, full && a.vdst, nvalid, o);
+    df_store8(dst + (size_t)y * dpitch + xg, full && a.vdst, nvalid, o);
 }
 
 template <typename T>

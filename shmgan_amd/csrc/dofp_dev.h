@@ -1,6 +1,7 @@
 // The tap walk of the polariser-mosaic kernels (dofp.hip: shm_dofp_views; dofp_develop.hip: shm_dofp_develop): launch geometry, the
 // Bayer tile's channel table, the sample loads, the plane store and df_numerators, which leaves a thread's four pixels' channel numerators
-// of all four views in registers.  What a kernel makes of the numerators (the 8-bit cut, or the development) is its own.  Everything
+// of all four views in registers.  What a kernel makes of the numerators (the 8-bit cut, or the development) is its own.  Also the
+// eight-sample group accesses of the passes over the mosaic itself (dofp_calibrate.hip, dofp_merge.hip).  Everything
 // here has internal linkage: each source that includes it gets its own copy.
 #pragma once
 #include "common.h"
@@ -63,6 +64,50 @@ __device__ __forceinline__ void df_load4(const unsigned char* p, unsigned* out) 
     out[1] = (u >> 8) & 0xffu;
     out[2] = (u >> 16) & 0xffu;
     out[3] = u >> 24;
+}
+
+// The bandwidth passes over a mosaic (dofp_calibrate.hip, dofp_merge.hip) give a thread DF_GROUP consecutive samples of a row.  `vec`: p is
+// aligned to the group and all of it lies inside the row: one 16-byte (uint16) or 8-byte (uint8) access; otherwise one access per element
+// for the first nvalid, the same values.
+constexpr int DF_GROUP = 8;
+
+__device__ __forceinline__ void df_load8(const unsigned short* p, bool vec, int nvalid, unsigned (&o)[DF_GROUP]) {
+    if (vec) {
+        const uint4 u = *(const uint4*)p;
+        o[0] = u.x & 0xffffu, o[1] = u.x >> 16, o[2] = u.y & 0xffffu, o[3] = u.y >> 16;
+        o[4] = u.z & 0xffffu, o[5] = u.z >> 16, o[6] = u.w & 0xffffu, o[7] = u.w >> 16;
+    } else {
+#pragma unroll
+        for (int j = 0; j < DF_GROUP; ++j) o[j] = j < nvalid ? (unsigned)p[j] : 0u;
+    }
+}
+__device__ __forceinline__ void df_load8(const unsigned char* p, bool vec, int nvalid, unsigned (&o)[DF_GROUP]) {
+    if (vec) {
+        const uint2 u = *(const uint2*)p;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = (u.x >> (8 * j)) & 0xffu, o[4 + j] = (u.y >> (8 * j)) & 0xffu;
+    } else {
+#pragma unroll
+        for (int j = 0; j < DF_GROUP; ++j) o[j] = j < nvalid ? (unsigned)p[j] : 0u;
+    }
+}
+__device__ __forceinline__ void df_store8(unsigned short* p, bool vec, int nvalid, const unsigned (&o)[DF_GROUP]) {
+    if (vec) {
+        *(uint4*)p = make_uint4(o[0] | o[1] << 16, o[2] | o[3] << 16, o[4] | o[5] << 16, o[6] | o[7] << 16);
+    } else {
+#pragma unroll
+        for (int j = 0; j < DF_GROUP; ++j)
+            if (j < nvalid) p[j] = (unsigned short)o[j];
+    }
+}
+__device__ __forceinline__ void df_store8(unsigned char* p, bool vec, int nvalid, const unsigned (&o)[DF_GROUP]) {
+    if (vec) {
+        *(uint2*)p = make_uint2(o[0] | o[1] << 8 | o[2] << 16 | o[3] << 24, o[4] | o[5] << 8 | o[6] << 16 | o[7] << 24);
+    } else {
+#pragma unroll
+        for (int j = 0; j < DF_GROUP; ++j)
+            if (j < nvalid) p[j] = (unsigned char)o[j];
+    }
 }
 
 // The numerators acc[quad position][channel][pixel] of the thread's four pixels (y, xg .. xg + 3).  FAST: every sample the thread needs lies in

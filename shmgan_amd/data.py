@@ -57,6 +57,7 @@ SHMGAN_SUBDIRS = ("I0", "I45", "I90", "I135", "ED")       # datasetLoader.py:23-
 DIFFUSE_SOURCES = ("dir", "min", "stokes")                # where the fifth tensor comes from (PolarDataset)
 CACHE_MODES = ("none", "device")                          # where decoded samples are kept between passes (PolarDataset)
 _EXT = (".bmp", ".gif", ".jpeg", ".jpg", ".png")          # Keras' ALLOWLIST_FORMATS
+BRACKET_EXT = (".tif", ".tiff")       # a bracketed sample is one multi-page TIFF: listed for the mosaic directory of a bracketed layout only
 
 
 def gib_to_bytes(cache_gb):
@@ -64,10 +65,16 @@ def gib_to_bytes(cache_gb):
     return None if cache_gb is None else int(float(cache_gb) * 2 ** 30)
 
 
-def list_images(directory):
-    """Sorted file list as image_dataset_from_directory(shuffle=False) yields it."""
+def list_images(directory, also=()):
+    """Sorted file list as image_dataset_from_directory(shuffle=False) yields it; `also`: further extensions to list (mosaic_extensions)."""
     d = Path(directory)
-    return sorted(str(p) for p in d.iterdir() if p.suffix.lower() in _EXT)
+    ext = _EXT + tuple(also)
+    return sorted(str(p) for p in d.iterdir() if p.suffix.lower() in ext)
+
+
+def mosaic_extensions(dofp):
+    """What list_images lists `also` in the mosaic directory of layout `dofp`: the TIFFs of a bracketed layout, nothing otherwise."""
+    return BRACKET_EXT if getattr(dofp, "bracket", None) is not None else ()
 
 
 AUGMENT_VIEWS = ("physical", "keep")
@@ -205,7 +212,8 @@ class PolarDataset:
                 self.coef = polar.stokes_matrix(angles if angles is not None else polar.angles_from_subdirs(subdirs))
                 if self.coef.shape != (3, 4):
                     raise ValueError(f"diffuse_source 'stokes' takes four angles, got {angles}")
-        self.files = [list_images(os.path.join(data_dir, s)) for s in subdirs]
+        self.files = [list_images(os.path.join(data_dir, s), also=mosaic_extensions(dofp) if capture == "dofp" and i == 0 else ())
+                      for i, s in enumerate(subdirs)]
         n = len(self.files[0])
         if any(len(f) != n for f in self.files):
             raise ValueError(f"the {len(self.files)} {'sample' if capture == 'dofp' else 'view'} directories hold different numbers of images: "
@@ -522,7 +530,8 @@ def validation_loader(data_dir, image_size, batch_size, *, val_dir="", val_fract
                                  capture=capture, dofp=dofp, dofp_demosaic=dofp_demosaic))
     if val_dir:
         return PolarDataset(val_dir, **opts)
-    _, val = split_indices(list_images(os.path.join(data_dir, tuple(subdirs)[0])), val_fraction, val_seed)
+    _, val = split_indices(list_images(os.path.join(data_dir, tuple(subdirs)[0]), also=mosaic_extensions(dofp) if capture == "dofp" else ()),
+                           val_fraction, val_seed)
     return PolarDataset(data_dir, **opts, select=val)
 
 
@@ -535,7 +544,8 @@ def trainer_frame(trainer):
 
 DEVELOP_OPTIONS = ("dofp_black", "dofp_white", "dofp_wb", "dofp_ccm", "dofp_tone", "dofp_sat")       # polar.DofpDevelop's fields; all None = no development
 CALIBRATION_OPTIONS = ("dofp_calibration",)       # the path of a saved polar.DofpCalibration; None = the frames are read as they are
-CAPTURE_OPTIONS = ("capture_format", "dofp_dir", "dofp_pattern", "dofp_quad_angles", "dofp_bits", "dofp_demosaic") + DEVELOP_OPTIONS + CALIBRATION_OPTIONS
+BRACKET_OPTIONS = ("dofp_exposures", "dofp_bracket_black", "dofp_bracket_white")       # polar.DofpBracket's fields; dofp_exposures None = one exposure per sample
+CAPTURE_OPTIONS = ("capture_format", "dofp_dir", "dofp_pattern", "dofp_quad_angles", "dofp_bits", "dofp_demosaic") + DEVELOP_OPTIONS + BRACKET_OPTIONS + CALIBRATION_OPTIONS
 
 
 def capture_options(args, subdirs=PSD_SUBDIRS):
@@ -547,7 +557,10 @@ def capture_options(args, subdirs=PSD_SUBDIRS):
     launch; the development rides on the layout, so the loader keywords stay the three they were (given with capture_format "views",
     where nothing could carry it, it is refused).  dofp_calibration: the path of the sensor's calibration (polar.build_calibration(...)
     .save(path); a polar.DofpCalibration itself is taken too): it is loaded here and rides on the layout in the same way, so every
-    frame is corrected on the device before it is demosaiced; refused with capture_format "views" like the development.  An unknown
+    frame is corrected on the device before it is demosaiced; refused with capture_format "views" like the development.
+    dofp_exposures (with dofp_bracket_black, dofp_bracket_white): the layout carries polar.DofpBracket(exposures, black, white): a sample
+    is one multi-page TIFF of that many exposures, merged on the device before it is demosaiced; refused with capture_format "views",
+    and the two levels are refused without dofp_exposures.  An unknown
     value raises ValueError naming the option, before anything is listed or allocated."""
     from . import polar
     opt = lambda k, dflt: getattr(args, k, dflt)
@@ -558,9 +571,12 @@ def capture_options(args, subdirs=PSD_SUBDIRS):
         raise ValueError(f"dofp_demosaic {demosaic!r} is not one of {polar.DOFP_DEMOSAIC}")
     given = {k[5:]: opt(k, None) for k in DEVELOP_OPTIONS if opt(k, None) is not None}
     calibration = opt("dofp_calibration", None)
+    bracket = {k: opt(k, None) for k in BRACKET_OPTIONS if opt(k, None) is not None}
     if capture == "views":
         if calibration is not None:
             raise ValueError(f"dofp_calibration {calibration!r} needs capture_format 'dofp', got 'views'")
+        for k, v in bracket.items():
+            raise ValueError(f"{k} {v!r} needs capture_format 'dofp', got 'views'")
         for k, v in given.items():          # it would be ignored: a development is a property of a mosaic's layout
             raise ValueError(f"dofp_{k} {v!r} needs capture_format 'dofp', got 'views'")
         return tuple(subdirs), dict(capture="views", dofp=None, dofp_demosaic=demosaic)
@@ -570,9 +586,17 @@ def capture_options(args, subdirs=PSD_SUBDIRS):
             if not isinstance(calibration, (str, os.PathLike)):
                 raise ValueError(f"DofpLayout: calibration {calibration!r} is not the path of a saved polar.DofpCalibration")
             calibration = polar.DofpCalibration.load(calibration)
-        layout = polar.DofpLayout(opt("dofp_pattern", "mono"), opt("dofp_quad_angles", (90, 45, 135, 0)), opt("dofp_bits", 8), develop, calibration)
+        for k, v in bracket.items():
+            if "dofp_exposures" not in bracket:
+                raise ValueError(f"{k} {v!r} needs dofp_exposures: it is a level of the bracket's merge")
+        if bracket:
+            bracket = polar.DofpBracket(bracket["dofp_exposures"], bracket.get("dofp_bracket_black"), bracket.get("dofp_bracket_white"))
+        layout = polar.DofpLayout(opt("dofp_pattern", "mono"), opt("dofp_quad_angles", (90, 45, 135, 0)), opt("dofp_bits", 8), develop, calibration,
+                                  bracket or None)
     except ValueError as e:
-        raise ValueError(str(e).replace("DofpLayout: ", "dofp_", 1).replace("DofpDevelop: ", "dofp_", 1).replace("DofpCalibration: ", "dofp_calibration: ", 1)) from None
+        msg = str(e).replace("DofpLayout: bracket ", "dofp_bracket_", 1).replace("DofpBracket: exposures", "dofp_exposures", 1)
+        msg = msg.replace("DofpBracket: ", "dofp_bracket_", 1)
+        raise ValueError(msg.replace("DofpLayout: ", "dofp_", 1).replace("DofpDevelop: ", "dofp_", 1).replace("DofpCalibration: ", "dofp_calibration: ", 1)) from None
     dofp_dir = opt("dofp_dir", "DOFP")
     if not isinstance(dofp_dir, str) or not dofp_dir:
         raise ValueError(f"dofp_dir {dofp_dir!r} is not a directory name")
@@ -603,7 +627,8 @@ def datasetLoad(trainer, subdirs=PSD_SUBDIRS, flip_ud=True):
                                            device=trainer.device, **source, **cache)
     select = None
     if val_fraction:
-        select, _ = split_indices(list_images(os.path.join(trainer.data_dir, tuple(subdirs)[0])), val_fraction, val_seed)
+        select, _ = split_indices(list_images(os.path.join(trainer.data_dir, tuple(subdirs)[0]),
+                                              also=mosaic_extensions(capture["dofp"]) if capture["capture"] == "dofp" else ()), val_fraction, val_seed)
     ds = PolarDataset(trainer.data_dir, trainer_frame(trainer), trainer.batch_size, subdirs, flip_ud, trainer.device,
                       epochs=trainer.num_epochs, shuffle=bool(opt("shuffle", False)), augment=augment, seed=int(opt("data_seed", 0)),
                       select=select, **source, **cache)
@@ -681,7 +706,7 @@ class MaskDataset:
         bad = sorted(set(mask_options) - set(polar.MASK_OPTIONS))
         if bad:
             raise TypeError(f"MaskDataset.from_polar: unknown option(s) {bad}; polar.specular_mask takes {polar.MASK_OPTIONS}")
-        views, files = polar.polar_sample_files(data_dir, subdirs, "MaskDataset.from_polar", capture)
+        views, files = polar.polar_sample_files(data_dir, subdirs, "MaskDataset.from_polar", capture, dofp)
         if not files[0]:
             raise ValueError(f"{data_dir}: the view directories {views} hold no images")
         self = cls.__new__(cls)
@@ -854,6 +879,11 @@ class MaskDataset:
 DOFP_TEST_VIEWS = ("total", 0, 1, 2, 3)       # the demosaiced plane test mode reads of a mosaic: the reference feeds "I0 (or Itot)"
 
 
+class _MosaicArray(np.ndarray):
+    """A decoded mosaic as _EvalCapture hands it on: the [n,h,w] pages of a bracket are three-dimensional like an RGB photo, so the class
+    and not the rank says which of the two an array is."""
+
+
 class _EvalCapture:
     """What test mode reads as a photo's decoded bytes (the capture options of EvalDataset and NativeEvalDataset): the RGB file, or
     with capture="dofp" one plane of a polariser mosaic -- dofp_test_view "total" (the rounded mean of the four views, default) or
@@ -873,8 +903,8 @@ class _EvalCapture:
             a = EvalDataset._decode(path)
             return a, a.shape[:2]
         from . import polar
-        a = polar.decode_mosaic(path, self.dofp)
-        return a, self.dofp.view_shape(a.shape[0], a.shape[1], self.demosaic)
+        a = polar.decode_mosaic(path, self.dofp).view(_MosaicArray)          # [h,w], or the [n,h,w] pages of a bracketed layout
+        return a, self.dofp.view_shape(a.shape[-2], a.shape[-1], self.demosaic)
 
     def size(self, h, w):
         """(h, w) of the photo a file of h x w pixels stands for."""
@@ -882,19 +912,19 @@ class _EvalCapture:
 
     def photo(self, a, dev):
         """The uint8 [h,w,3] device image of a decoded test file."""
-        if a.ndim == 3:
+        if a.ndim == 3 and not isinstance(a, _MosaicArray):
             return torch.from_numpy(a).to(dev)
         from . import polar
         with torch.cuda.device(dev):
-            out = polar.demosaic(a, self.dofp, self.demosaic, total=self.view == "total", device=dev)
+            out = polar.demosaic(np.asarray(a), self.dofp, self.demosaic, total=self.view == "total", device=dev)
         return out[4 if self.view == "total" else self.view]
 
 
-def eval_file_lists(test_dir, diffuse_dir=None):
-    """File lists of the evaluation loader: the sorted flat `test_dir` and, when given, the sorted flat `diffuse_dir`
-    (None otherwise), paired by position.  The reference zips the two datasets (test.py:130), and tf.data's zip stops at the
+def eval_file_lists(test_dir, diffuse_dir=None, also=()):
+    """File lists of the evaluation loader: the sorted flat `test_dir` (with the extensions `also`: mosaic_extensions of a bracketed
+    layout) and, when given, the sorted flat `diffuse_dir` (None otherwise), paired by position.  The reference zips the two datasets (test.py:130), and tf.data's zip stops at the
     shorter one without a word; a count mismatch here raises instead, since it means the pairs are not what was meant."""
-    test = list_images(test_dir)
+    test = list_images(test_dir, also=also)
     if not diffuse_dir:
         return test, None
     diffuse = list_images(diffuse_dir)
@@ -925,7 +955,7 @@ class EvalDataset:
             raise ValueError(f"batch_size {batch_size} < 1")
         self.H, self.W = frame_hw(image_size)                # image_size: a side, or a pair (H, W)
         self.S, self.B = (self.H if self.H == self.W else None), int(batch_size)
-        self.test_files, self.diffuse_files = eval_file_lists(test_dir, diffuse_dir)
+        self.test_files, self.diffuse_files = eval_file_lists(test_dir, diffuse_dir, mosaic_extensions(dofp) if capture == "dofp" else ())
         self.n = len(self.test_files)
         self.rank, self.world = 0, 1
         self._dev = device
@@ -1036,7 +1066,7 @@ class NativeEvalDataset:
                  dofp_test_view="total"):
         self._capture = _EvalCapture(capture, dofp, dofp_demosaic, dofp_test_view, "NativeEvalDataset")
         self.B = 1
-        self.test_files, self.diffuse_files = eval_file_lists(test_dir, diffuse_dir)
+        self.test_files, self.diffuse_files = eval_file_lists(test_dir, diffuse_dir, mosaic_extensions(dofp) if capture == "dofp" else ())
         self.n = len(self.test_files)
         self.rank, self.world = 0, 1
         self._dev, self._check = device, check
@@ -1072,7 +1102,7 @@ class NativeEvalDataset:
 
     def batch(self, index, decoded=None):
         test, diffuse = decoded if decoded is not None else self._decode_pair(index)
-        h, w = (int(v) for v in self._capture.size(*test.shape[:2]))
+        h, w = (int(v) for v in self._capture.size(*(test.shape[-2:] if isinstance(test, _MosaicArray) else test.shape[:2])))
         if diffuse is not None and tuple(diffuse.shape[:2]) != (h, w):
             raise ValueError(f"native-resolution evaluation compares a test image with its diffuse partner pixel by pixel: "
                              f"{self.test_files[index]} is {h} x {w}, {self.diffuse_files[index]} is {diffuse.shape[0]} x {diffuse.shape[1]}")

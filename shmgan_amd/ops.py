@@ -1465,6 +1465,91 @@ def dofp_calibrate(mosaic, calibration):
     return _dofp_calibrated("dofp_calibrate", mosaic, cal)
 
 
+DOFP_MERGE_MAX, DOFP_MERGE_TABLE = CONSTANTS["SHM_DOFP_MERGE_MAX"], CONSTANTS["SHM_DOFP_MERGE_TABLE"]
+_DOFP_MERGE_TABLES = {}          # (exposures, bits, device) -> (mul uint32 [DOFP_MERGE_TABLE] on the device, its host mirror as a ctypes array)
+
+
+def _dofp_merge_table(bracket, bits, device):
+    """bracket.table(bits) on `device`: uploaded once, kept."""
+    import ctypes as C
+    key = (bracket.exposures, int(bits), torch.device(device))
+    if key not in _DOFP_MERGE_TABLES:
+        mul = bracket.table(bits)
+        _DOFP_MERGE_TABLES[key] = (torch.from_numpy(mul.copy()).to(device), (C.c_uint * DOFP_MERGE_TABLE)(*[int(v) for v in mul]))
+    return _DOFP_MERGE_TABLES[key]
+
+
+def _dofp_pages(who, pages, n, bits):
+    """The n checked 2-D pages of a bracket, of one size, dtype, device and pitch."""
+    if isinstance(pages, torch.Tensor):
+        if pages.dim() != 3:
+            raise ValueError(f"{who} takes the pages as one [n,h,w] tensor or a list of 2-D tensors, got shape {tuple(pages.shape)}")
+        pages = list(pages.unbind(0))
+    pages = list(pages)
+    if len(pages) != n:
+        raise ValueError(f"{who}: {len(pages)} page(s) for a bracket of {n} exposures")
+    for p in pages:
+        _dofp_check_mosaic(who, p, bits)
+    first = pages[0]
+    h, w = (int(d) for d in first.shape)
+    pitch = lambda p: int(p.stride(0)) if h > 1 else w
+    for k, p in enumerate(pages):
+        if tuple(p.shape) != (h, w) or p.dtype != first.dtype or p.device != first.device:
+            raise ValueError(f"{who}: page {k} is {tuple(p.shape)} {p.dtype} on {p.device}, page 0 is {(h, w)} {first.dtype} on {first.device}")
+        if pitch(p) != pitch(first):
+            raise ValueError(f"{who}: page {k} has a row pitch of {pitch(p)} elements, page 0 of {pitch(first)}: the pages share one pitch")
+    return pages, h, w, pitch(first)
+
+
+def _dofp_merged(who, pages, bracket, bits, black, white, counts=False, calibration=None):
+    """shm_dofp_merge of the checked pages (each through shm_dofp_calibrate first when there is a calibration) into a new contiguous uint16
+    tensor, on the current stream: (merged, counts tensor or None)."""
+    import ctypes as C
+    pages, h, w, pitch = _dofp_pages(who, pages, bracket.pages, bits)
+    if calibration is not None:
+        pages, pitch = [_dofp_calibrated(who, p, calibration) for p in pages], w
+    table, mirror = _dofp_merge_table(bracket, bits, pages[0].device)
+    out = torch.empty((h, w), dtype=torch.uint16, device=pages[0].device)
+    cnt = torch.empty(DOFP_MERGE_MAX + 1, dtype=torch.int32, device=pages[0].device) if counts else None
+    sp = (C.c_void_p * len(pages))(*[p.data_ptr() for p in pages])
+    check(lib().shm_dofp_merge(sp, len(pages), bits, h, w, pitch, table.data_ptr(), mirror, black, white, out.data_ptr(), w, _p(cnt), _stream()),
+          "shm_dofp_merge")
+    return out, cnt
+
+
+def dofp_merge(pages, bracket_or_layout, counts=False, bits=None):
+    """The pages of one exposure bracket merged into one uint16 [h,w] mosaic on the scale of the shortest exposure (shm_dofp_merge,
+    include/shmgan_hip.h, states the arithmetic): every unsaturated page votes, weighted by its exposure time.  pages: a [n,h,w] device
+    tensor or a list of n 2-D ones with unit stride along a row and one row pitch, uint8 (bits = 8) or uint16.  bracket_or_layout: a
+    polar.DofpLayout with a bracket -- its bits, its levels (layout.bracket_levels), and its calibration applied to every page first --
+    or a polar.DofpBracket alone, with `bits` (default 8 for uint8 pages, 16 for uint16) and the bracket's own levels (0 and 2^bits - 1
+    where it gives none).  With `counts` also an int32 [9] device tensor: counts[j] = the photosites with exactly j valid pages.  The
+    table goes to the device once per (bracket, bits, device).  Asynchronous on the current stream: nothing waits for the device."""
+    bracket = getattr(bracket_or_layout, "bracket", None)
+    if bracket is not None:
+        layout = bracket_or_layout
+        if bits is not None and int(bits) != layout.bits:
+            raise ValueError(f"dofp_merge: bits {bits!r} is not the layout's {layout.bits}")
+        black, white = layout.bracket_levels
+        out, cnt = _dofp_merged("dofp_merge", pages, bracket, layout.bits, black, white, counts, layout.calibration)
+    else:
+        bracket = bracket_or_layout
+        if not all(hasattr(bracket, k) for k in ("exposures", "table", "levels")):
+            raise ValueError(f"dofp_merge takes a polar.DofpBracket or a polar.DofpLayout that has one, got {bracket_or_layout!r}")
+        if bits is None:
+            first = pages[0] if len(pages) else None
+            bits = 8 if getattr(first, "dtype", None) == torch.uint8 else 16
+        black, white = bracket.levels(int(bits))
+        out, cnt = _dofp_merged("dofp_merge", pages, bracket, int(bits), black, white, counts)
+    return (out, cnt) if counts else out
+
+
+def _dofp_merge_layout(who, pages, layout):
+    """The merged mosaic of a bracketed layout's pages: what dofp_views and dofp_wb_gray then read under layout.merged."""
+    black, white = layout.bracket_levels
+    return _dofp_merged(who, pages, layout.bracket, int(layout.bits), black, white, False, layout.calibration)[0]
+
+
 def dofp_views(mosaic, layout, mode="bilinear", total=False):
     """One polariser-mosaic frame -> its four views in one launch (shm_dofp_views, include/shmgan_hip.h, states the arithmetic).
     mosaic: a uint8 or uint16 2-D device tensor with unit stride along a row; its stride 0 is the pitch.  layout: a
@@ -1473,8 +1558,12 @@ def dofp_views(mosaic, layout, mode="bilinear", total=False):
     With layout.develop (a polar.DofpDevelop) the planes are developed instead -- black level, white balance, matrix, tone curve, in
     the same single launch (shm_dofp_develop), after the two grey-world launches when its wb is "gray".  With layout.calibration (a
     polar.DofpCalibration) the frame is corrected first (dofp_calibrate, one more launch into a new tensor) and all of that reads the
-    corrected mosaic.  Asynchronous on the current stream."""
+    corrected mosaic.  With layout.bracket (a polar.DofpBracket) `mosaic` is the [n,h,w] pages of one sample: each is corrected, they are
+    merged (dofp_merge, one more launch) and the views are those of the merged 16-bit mosaic under layout.merged.  Asynchronous on the
+    current stream."""
     import ctypes as C
+    if getattr(layout, "bracket", None) is not None:
+        return dofp_views(_dofp_merge_layout("dofp_views", mosaic, layout), layout.merged, mode, total)
     bits = _dofp_check_mosaic("dofp_views", mosaic, layout.bits)
     h, w = (int(d) for d in mosaic.shape)
     ho, wo = dofp_shape(h, w, layout.pattern, mode)
@@ -1530,7 +1619,14 @@ def dofp_wb_gray(mosaic, layout, sat=None):
     """Grey-world sums and gains of one Bayer polariser-mosaic frame (shm_dofp_wb_gray, include/shmgan_hip.h): (sums int64 [6] = S_r, S_g,
     S_b, n_r, n_g, n_b over the complete 4 x 4 periods without a sample at or above `sat`, gains int64 [3] in Q10), device tensors filled
     asynchronously on the current stream.  The black level is layout.develop's (0 without one); `sat` defaults to its saturation count, or
-    2^bits - 1 without one.  A layout with a calibration has the frame corrected first, as dofp_views does."""
+    2^bits - 1 without one.  A layout with a calibration has the frame corrected first, as dofp_views does; one with a bracket takes the
+    [n,h,w] pages, merges them and sums the merged mosaic under layout.merged (a `sat` given here is in counts of one page, like the
+    development's, and is moved onto the merged scale)."""
+    if getattr(layout, "bracket", None) is not None:
+        if dofp_period(layout.pattern) != 4:
+            raise ValueError(f"dofp_wb_gray needs a Bayer pattern, the layout is {layout.pattern!r}")
+        sat = None if sat is None else min(65536, int(sat) << (16 - int(layout.bits)))
+        return dofp_wb_gray(_dofp_merge_layout("dofp_wb_gray", mosaic, layout), layout.merged, sat)
     _dofp_check_mosaic("dofp_wb_gray", mosaic, layout.bits)
     if dofp_period(layout.pattern) != 4:
         raise ValueError(f"dofp_wb_gray needs a Bayer pattern, the layout is {layout.pattern!r}")

@@ -16,7 +16,9 @@ files" become "its four uint8 device views" for either kind of capture (DESIGN.m
 frames developed inside that launch -- black level, white balance, colour matrix, tone curve (csrc/dofp_develop.hip; DESIGN.md section
 6o); `estimate_white_balance` gives the one grey-world balance of a whole capture.  A layout with a `DofpCalibration` has every frame
 corrected on the device first -- master dark, flat-field gain, defective photosites (csrc/dofp_calibrate.hip; DESIGN.md section 6p);
-`build_calibration` makes one from a stack of dark frames and a stack of flats.
+`build_calibration` makes one from a stack of dark frames and a stack of flats.  A layout with a `DofpBracket` reads an exposure bracket
+per sample -- one multi-page TIFF (`write_bracket`, `pack_brackets`) -- and merges its pages on the device into a 16-bit mosaic
+(`merge_bracket`; csrc/dofp_merge.hip) that everything else reads under `layout.merged`.
 
 Importing this module needs no GPU; `polar_maps`, `specular_mask`, `demosaic`, `estimate_white_balance`, `write_estimated_diffuse` and
 `write_specular_masks` run on one.
@@ -37,7 +39,7 @@ from pathlib import Path
 import numpy as np
 
 from ._lib import CONSTANTS
-from .data import PSD_SUBDIRS, list_images
+from .data import BRACKET_EXT, PSD_SUBDIRS, list_images, mosaic_extensions
 
 # S0 = I0 + I90, S1 = I0 - I90, S2 = I45 - I135: the coefficients calcDOP hard-codes (SHM.py:1158-1160).  Its S0 uses two of the
 # four views; stokes_matrix([0, 45, 90, 135]) gives the least-squares S0 = (I0 + I45 + I90 + I135) / 2 with the same S1, S2.
@@ -529,6 +531,85 @@ def build_calibration(layout, dark_dir, flat_dir=None, hot_threshold=None, gain_
     return DofpCalibration(dark.astype(np.uint16), gain.astype(np.uint16), defect, pedestal, white, layout.pattern, bits, reference)
 
 
+# ---- exposure brackets: n pages of one mosaic merged into a 16-bit one (csrc/dofp_merge.hip) -------------------
+MERGE_MAX, MERGE_TABLE, MERGE_Q = CONSTANTS["SHM_DOFP_MERGE_MAX"], CONSTANTS["SHM_DOFP_MERGE_TABLE"], CONSTANTS["SHM_DOFP_MERGE_Q"]
+
+
+def _count_or_none(who, name, v, lo, hi):
+    if v is None:
+        return None
+    if isinstance(v, (bool, str)) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+        raise ValueError(f"{who}: {name} {v!r} is not a count in [{lo}, {hi}]")
+    return int(v)
+
+
+@dataclass(frozen=True)
+class DofpBracket:
+    """An exposure bracket of a static scene: shm_dofp_merge (include/shmgan_hip.h states the arithmetic) merges its pages into one 16-bit
+    mosaic on the scale of the shortest exposure, every unsaturated page voting with its exposure time.  exposures: 2 to 8 positive
+    integers of at most 65535 in PAGE order, in any unit (only the ratios matter; they need not be sorted).  black: the count for
+    darkness; None = the pedestal of the layout's calibration when it has one, else 0.  white: the count from which a sample is
+    saturated; None = the calibration's white level when there is one, else 2^bits - 1.  `table(bits)` is the one quantisation of the
+    exposures: the kernel and the tests read nothing else.  Refusals are ValueErrors by name."""
+    exposures: tuple
+    black: object = None
+    white: object = None
+
+    def __post_init__(self):
+        try:
+            if isinstance(self.exposures, (str, bytes)):
+                raise TypeError
+            raw = tuple(self.exposures)
+        except TypeError:
+            raise ValueError(f"DofpBracket: exposures {self.exposures!r} are not 2 to {MERGE_MAX} positive integers") from None
+        if not 2 <= len(raw) <= MERGE_MAX or any(isinstance(e, bool) or not isinstance(e, (int, np.integer)) for e in raw):
+            raise ValueError(f"DofpBracket: exposures {self.exposures!r} are not 2 to {MERGE_MAX} positive integers")
+        if not all(1 <= int(e) <= 65535 for e in raw):
+            raise ValueError(f"DofpBracket: exposures {self.exposures!r} are not all in [1, 65535]")
+        object.__setattr__(self, "exposures", tuple(int(e) for e in raw))
+        object.__setattr__(self, "black", _count_or_none("DofpBracket", "black", self.black, 0, 65535 - 16))
+        object.__setattr__(self, "white", _count_or_none("DofpBracket", "white", self.white, 1, 65536))
+        if self.black is not None and self.white is not None and self.white <= self.black:
+            raise ValueError(f"DofpBracket: white {self.white} is not above black {self.black}")
+
+    @property
+    def pages(self):
+        return len(self.exposures)
+
+    def table(self, bits):
+        """mul of shm_dofp_merge for samples of `bits` bits: uint32 [256], read-only and shared between calls; entry m, the mask of the
+        valid pages, is the round-half-up of e_min * 2^(16 - bits) * 2^20 / (the sum of the valid pages' exposures)."""
+        if isinstance(bits, bool) or not isinstance(bits, (int, np.integer)) or not 8 <= int(bits) <= 16:
+            raise ValueError(f"DofpBracket: bits {bits!r} is not an integer in 8..16")
+        return _merge_table(self.exposures, int(bits))
+
+    def levels(self, bits, calibration=None):
+        """(black, white) as the merge takes them for samples of `bits` bits: the given counts, else the calibration's pedestal and
+        white level, else 0 and 2^bits - 1.  What shm_dofp_merge would refuse is refused here, by name."""
+        f = 16 - int(bits)
+        black = self.black if self.black is not None else calibration.pedestal if calibration is not None else 0
+        white = self.white if self.white is not None else calibration.white_level if calibration is not None else (1 << bits) - 1
+        if (black << f) > 65535 - 16:
+            raise ValueError(f"DofpBracket: black {black} << {f} is above 65519, the merged mosaic's limit for a black level")
+        if not 1 <= white <= 1 << bits:
+            raise ValueError(f"DofpBracket: white {white} outside [1, {1 << bits}] for {bits}-bit samples")
+        if white <= black:
+            raise ValueError(f"DofpBracket: white {white} is not above black {black}")
+        return black, white
+
+
+@functools.lru_cache(maxsize=None)
+def _merge_table(exposures, bits):
+    f, n = 16 - bits, len(exposures)
+    top = min(exposures) << (f + MERGE_Q)
+    mul = np.zeros(MERGE_TABLE, dtype=np.uint32)
+    for m in range(1, 1 << n):
+        T = sum(e for k, e in enumerate(exposures) if m >> k & 1)
+        mul[m] = (2 * top + T) // (2 * T)
+    mul.setflags(write=False)
+    return mul
+
+
 @dataclass(frozen=True)
 class DofpLayout:
     """How a polariser-mosaic sensor lays its samples out.  pattern: "mono", or the Bayer tile over the quads ("rggb", "bggr",
@@ -538,6 +619,9 @@ class DofpLayout:
     bits (shm_dofp_views), or a DofpDevelop: black level, white balance, matrix and tone curve inside the demosaic launch.
     calibration: None, or the sensor's DofpCalibration (of this pattern and these bits): every frame is corrected on the device --
     dark frame, flat field, defect map (shm_dofp_calibrate) -- before anything else reads it.
+    bracket: None, or a DofpBracket: a sample is then n pages [n,h,w] of one mosaic (one multi-page TIFF), each page is calibrated, the
+    pages are merged on the device (shm_dofp_merge) into a 16-bit mosaic on the scale of the shortest exposure, and everything after
+    that reads it as `merged` says.
     Views are always delivered in ASCENDING angle (`angles`), whatever the quad's order, so stokes_matrix(layout.angles) and the
     exact 45 / 135 exchange of mirror_views apply as they are; `quad` is the kernel's table, the view index at each quad position."""
     pattern: str = "mono"
@@ -545,6 +629,7 @@ class DofpLayout:
     bits: int = 8
     develop: DofpDevelop | None = None
     calibration: DofpCalibration | None = None
+    bracket: DofpBracket | None = None
 
     def __post_init__(self):
         if self.pattern not in DOFP_PATTERNS:
@@ -574,6 +659,30 @@ class DofpLayout:
                 raise ValueError(f"DofpLayout: calibration is of pattern {cal.pattern!r}, the layout is {self.pattern!r}")
             if cal.bits != self.bits:
                 raise ValueError(f"DofpLayout: calibration is of bits = {cal.bits}, the layout says bits = {self.bits}")
+        if self.bracket is not None:
+            if not isinstance(self.bracket, DofpBracket):
+                raise ValueError(f"DofpLayout: bracket {self.bracket!r} is not a polar.DofpBracket or None")
+            self.merged          # a level the 16-bit mosaic cannot hold is refused here, by name
+
+    @property
+    def bracket_levels(self):
+        """(black, white) of the merge in counts of one page: the bracket's, else the calibration's pedestal and white level, else 0 and
+        2^bits - 1."""
+        try:
+            return self.bracket.levels(self.bits, self.calibration)
+        except ValueError as e:
+            raise ValueError(str(e).replace("DofpBracket: ", "DofpLayout: bracket ", 1)) from None
+
+    @property
+    def merged(self):
+        """The layout of the mosaic shm_dofp_merge makes of this layout's pages (the layout itself without a bracket): the same pattern
+        and quad, bits = 16, no calibration and no bracket, and the development moved onto the merged scale, f = 16 - bits: its blacks
+        << f, its white min(65535, W << f) with W the development's white when given, else the bracket's, its sat min(65536, sat << f)
+        when given.  So dofp_black / dofp_white stay in counts of the shortest exposure, and without a development the views are the top
+        8 bits of the merged frame."""
+        if self.bracket is None:
+            return self
+        return _merged_layout(self)
 
     @property
     def angles(self):
@@ -597,6 +706,23 @@ class DofpLayout:
         return (int(h), int(w)) if mode == "bilinear" else (int(h) // self.period, int(w) // self.period)
 
 
+@functools.lru_cache(maxsize=None)
+def _merged_layout(layout):
+    f = 16 - layout.bits
+    _, white = layout.bracket_levels
+    dev = layout.develop
+    if dev is not None:
+        if any((b << f) > 65535 - 16 for b in dev.black):
+            raise ValueError(f"DofpLayout: develop black {dev.black} << {f} is above 65519, the merged mosaic's limit for a black level")
+        try:
+            dev = DofpDevelop(tuple(b << f for b in dev.black), min(65535, (dev.white if dev.white is not None else white) << f), dev.wb, dev.ccm,
+                              dev.tone, None if dev.sat is None else min(65536, dev.sat << f))
+            return DofpLayout(layout.pattern, layout.quad_angles, 16, dev)
+        except ValueError as e:
+            raise ValueError(f"DofpLayout: the development of the merged mosaic (levels << {f}): {e}") from None
+    return DofpLayout(layout.pattern, layout.quad_angles, 16)
+
+
 def check_capture(capture, dofp, dofp_demosaic="bilinear", who="PolarDataset"):
     """The refusals every entry point that takes the capture options shares, by name and before anything is listed or allocated."""
     if capture not in CAPTURES:
@@ -612,39 +738,129 @@ def check_capture(capture, dofp, dofp_demosaic="bilinear", who="PolarDataset"):
 def decode_mosaic(path, layout):
     """One raw mosaic file as a 2-D array: PIL mode "L" gives uint8 and needs layout.bits == 8; "I;16" / "I;16B" give uint16 (native
     byte order) and need bits 9..16.  Anything else -- an RGB file is not a mosaic -- raises ValueError naming the file and its mode, and
-    so does a frame whose size is not that of the layout's calibration tables, naming both sizes."""
+    so does a frame whose size is not that of the layout's calibration tables, naming both sizes.  With a bracketed layout the file is one
+    multi-page TIFF, pages in the order of the bracket's exposures, and the result is [n,h,w]; a page count other than n, or pages of
+    unequal size or mode, raise ValueError naming the file."""
     from PIL import Image
+
+    def page(im):
+        if im.mode == "L":
+            return np.array(im, dtype=np.uint8)
+        if im.mode in ("I;16", "I;16B", "I;16L"):
+            return np.ascontiguousarray(np.array(im).astype(np.uint16, copy=False))
+        raise ValueError(f"{path} is not a polariser mosaic: PIL mode {im.mode!r} (a mosaic is one channel: 'L' for 8 bits, 'I;16' for 9..16)")
+    bracket = getattr(layout, "bracket", None)
     with Image.open(path) as im:
         mode = im.mode
-        if mode == "L":
-            a = np.array(im, dtype=np.uint8)
-        elif mode in ("I;16", "I;16B", "I;16L"):
-            a = np.ascontiguousarray(np.array(im).astype(np.uint16, copy=False))
+        if bracket is None:
+            a = page(im)
         else:
-            raise ValueError(f"{path} is not a polariser mosaic: PIL mode {mode!r} (a mosaic is one channel: 'L' for 8 bits, 'I;16' for 9..16)")
+            n = int(getattr(im, "n_frames", 1))
+            if n != bracket.pages:
+                raise ValueError(f"{path} holds {n} page(s), the layout's bracket has {bracket.pages} exposures {bracket.exposures}")
+            pages = []
+            for k in range(n):
+                im.seek(k)
+                if im.mode != mode or (pages and (im.size[1], im.size[0]) != pages[0].shape):
+                    raise ValueError(f"{path}: page {k} is {im.size[1]} x {im.size[0]} of PIL mode {im.mode!r}, page 0 is "
+                                     f"{pages[0].shape[0]} x {pages[0].shape[1]} of mode {mode!r}: the pages of a bracket are one mosaic")
+                pages.append(page(im))
+            a = np.stack(pages)
     if (a.dtype == np.uint8) != (layout.bits == 8):
         raise ValueError(f"{path} holds {8 * a.dtype.itemsize}-bit samples (PIL mode {mode!r}), the layout says bits = {layout.bits}")
     cal = getattr(layout, "calibration", None)
-    if cal is not None and cal.shape is not None and tuple(a.shape) != cal.shape:          # here, where the file still has a name
-        raise ValueError(f"{path} is {a.shape[0]} x {a.shape[1]}, the layout's calibration tables are {cal.shape[0]} x {cal.shape[1]}")
+    if cal is not None and cal.shape is not None and tuple(a.shape[-2:]) != cal.shape:          # here, where the file still has a name
+        raise ValueError(f"{path} is {a.shape[-2]} x {a.shape[-1]}, the layout's calibration tables are {cal.shape[0]} x {cal.shape[1]}")
     return a
 
 
 def demosaic(mosaic, layout, mode="bilinear", total=False, device=None):
     """The four views (and with `total` their rounded mean) of one mosaic: ops.dofp_views, which develops them when the layout has
     a `develop`.  mosaic: a uint8 / uint16 2-D device
-    tensor, or a NumPy array, which is uploaded first (to `device`, default the current one).  Returns uint8 [ho,wo,3] device
+    tensor, or a NumPy array, which is uploaded first (to `device`, default the current one); with a bracketed layout the [n,h,w] pages,
+    which ops.dofp_views merges first.  Returns uint8 [ho,wo,3] device
     tensors in ascending polariser angle (layout.angles).  Asynchronous on the current stream."""
     import torch
     from . import ops
     if not isinstance(layout, DofpLayout):
         raise ValueError(f"demosaic: layout must be a polar.DofpLayout, got {layout!r}")
     if isinstance(mosaic, np.ndarray):
-        if mosaic.dtype not in (np.uint8, np.uint16) or mosaic.ndim != 2:
-            raise ValueError(f"demosaic takes a 2-D uint8 or uint16 mosaic, got {mosaic.dtype} {mosaic.shape}")
-        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        mosaic = torch.from_numpy(np.ascontiguousarray(mosaic)).to(dev)
+        mosaic = _upload_mosaic("demosaic", mosaic, layout, device)
     return ops.dofp_views(mosaic, layout, mode, total)
+
+
+def _upload_mosaic(who, mosaic, layout, device):
+    """A decoded mosaic ([h,w], or the [n,h,w] pages of a bracketed layout) on `device` (default the current one)."""
+    import torch
+    ndim = 2 if layout.bracket is None else 3
+    if mosaic.dtype not in (np.uint8, np.uint16) or mosaic.ndim != ndim:
+        raise ValueError(f"{who} takes a {'2-D' if ndim == 2 else '3-D [n,h,w]'} uint8 or uint16 mosaic, got {mosaic.dtype} {mosaic.shape}")
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    return torch.from_numpy(np.ascontiguousarray(mosaic)).to(dev)
+
+
+def merge_bracket(pages, layout, counts=False, device=None):
+    """The merged 16-bit mosaic of one bracketed sample, uint16 [h,w] on the device (ops.dofp_merge: each page calibrated first when the
+    layout has a calibration), and with `counts` the tensor of how many photosites have 0 .. 8 valid pages -- counts[0] is what is
+    still clipped in every page, which tells whether the bracket goes deep enough.  pages: [n,h,w] as decode_mosaic gives them, or a
+    device tensor.  layout.merged is the layout of the result.  Asynchronous on the current stream."""
+    from . import ops
+    if not isinstance(layout, DofpLayout) or layout.bracket is None:
+        raise ValueError(f"merge_bracket: layout must be a polar.DofpLayout with a bracket, got {layout!r}")
+    if isinstance(pages, np.ndarray):
+        pages = _upload_mosaic("merge_bracket", pages, layout, device)
+    return ops.dofp_merge(pages, layout, counts)
+
+
+def write_bracket(path, pages):
+    """One bracketed sample as ONE multi-page TIFF, pages in the given (exposure) order: uint8 pages as mode "L", uint16 as "I;16" --
+    what decode_mosaic reads with a bracketed layout, and what scientific camera SDKs write.  pages: [n,h,w] or a list of [h,w]."""
+    from PIL import Image
+    pages = [np.asarray(a) for a in pages]
+    if len(pages) < 2 or any(a.ndim != 2 or a.dtype != pages[0].dtype or a.shape != pages[0].shape for a in pages) or \
+            pages[0].dtype not in (np.uint8, np.uint16):
+        raise ValueError(f"write_bracket takes two or more uint8 or uint16 [h,w] pages of one size, got "
+                         f"{[(str(a.dtype), a.shape) for a in pages]}")
+    if Path(path).suffix.lower() not in BRACKET_EXT:
+        raise ValueError(f"write_bracket: {path} is not a TIFF name (one of {BRACKET_EXT})")
+    ims = [Image.fromarray(np.ascontiguousarray(a)) for a in pages]          # uint8 -> "L", uint16 -> "I;16"
+    ims[0].save(path, format="TIFF", save_all=True, append_images=ims[1:])
+    return str(path)
+
+
+def pack_brackets(dirs, out_dir):
+    """One directory of single-frame mosaics per exposure (in exposure order; files as decode_mosaic reads them) -> one multi-page
+    TIFF per sample in out_dir, named after the sample.  The directories must hold the same file names (by stem): unequal counts or
+    names raise ValueError.  Returns the files written."""
+    from PIL import Image
+    dirs = [str(d) for d in dirs]
+    if not 2 <= len(dirs) <= MERGE_MAX:
+        raise ValueError(f"pack_brackets takes 2 to {MERGE_MAX} directories, one per exposure, got {len(dirs)}")
+    lists = [list_images(d, also=BRACKET_EXT) for d in dirs]
+    if any(len(f) != len(lists[0]) for f in lists):
+        raise ValueError(f"pack_brackets: the directories hold different numbers of frames: {dict(zip(dirs, (len(f) for f in lists)))}")
+    stems = [[Path(p).stem for p in f] for f in lists]
+    for d, st in zip(dirs[1:], stems[1:]):
+        if st != stems[0]:
+            odd = sorted(set(st) ^ set(stems[0]))
+            raise ValueError(f"pack_brackets: {d} and {dirs[0]} do not hold the same names (e.g. {odd[:3]})")
+    if len(set(stems[0])) != len(stems[0]):
+        raise ValueError(f"pack_brackets: {dirs[0]} holds two files of one name")
+    os.makedirs(out_dir, exist_ok=True)
+    written = []
+    for i, stem in enumerate(stems[0]):
+        pages = []
+        for f in lists:
+            with Image.open(f[i]) as im:
+                if im.mode not in ("L", "I;16", "I;16B", "I;16L"):
+                    raise ValueError(f"{f[i]} is not a polariser mosaic: PIL mode {im.mode!r}")
+                pages.append(np.array(im, dtype=np.uint8) if im.mode == "L" else np.array(im).astype(np.uint16, copy=False))
+        try:
+            written.append(write_bracket(os.path.join(out_dir, stem + ".tif"), pages))
+        except ValueError:
+            raise ValueError(f"pack_brackets: the frames of sample {stem!r} differ in size or depth: "
+                             f"{[(p[i], str(a.dtype), a.shape) for p, a in zip(lists, pages)]}") from None
+    return written
 
 
 def gray_gains(sums):
@@ -661,14 +877,15 @@ def estimate_white_balance(data_dir, layout, dofp_dir="DOFP", sat=None, device=N
     """The grey-world balance of a WHOLE capture: the sums of shm_dofp_wb_gray (every complete 4 x 4 period without a sample at or
     above `sat`, black level removed) added over all mosaics of data_dir/dofp_dir and finished on the host.  Returns the (R, G, B)
     triple for DofpDevelop(wb=...), smallest entry 1.  One device round trip per frame: a one-off, not a loader path.  `sat`
-    defaults to the layout's development's (its white level), or 2^bits - 1 without one."""
+    defaults to the layout's development's (its white level), or 2^bits - 1 without one.  A bracketed layout has every sample merged
+    first: the sums are those of the merged mosaics, under layout.merged."""
     import torch
     from . import ops
     if not isinstance(layout, DofpLayout):
         raise ValueError(f"estimate_white_balance: layout must be a polar.DofpLayout, got {layout!r}")
     if layout.pattern == "mono":
         raise ValueError("estimate_white_balance needs a Bayer pattern, the layout is 'mono'")
-    files = list_images(os.path.join(data_dir, dofp_dir))
+    files = list_images(os.path.join(data_dir, dofp_dir), also=mosaic_extensions(layout))
     if not files:
         raise ValueError(f"estimate_white_balance: no mosaics in {os.path.join(data_dir, dofp_dir)}")
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -727,14 +944,15 @@ def specular_mask(views_u8, angles=None, *, matrix=None, threshold="otsu", floor
     return mask, q, stats
 
 
-def polar_sample_files(data_dir, subdirs, who, capture="views"):
+def polar_sample_files(data_dir, subdirs, who, capture="views", dofp=None):
     """The sorted file lists of the first four `subdirs` of `data_dir`, with the refusals of write_estimated_diffuse: four
-    directories, equal counts.  capture="dofp": the one list of the first of `subdirs`, which holds a mosaic per sample."""
+    directories, equal counts.  capture="dofp": the one list of the first of `subdirs`, which holds a mosaic per sample (a multi-page
+    TIFF per sample when the layout `dofp` has a bracket)."""
     if capture == "dofp":
         views = tuple(subdirs)[:1]
         if len(views) != 1:
             raise ValueError(f"{who} needs the mosaic directory as the first of subdirs, got {tuple(subdirs)}")
-        return views, [list_images(os.path.join(data_dir, views[0]))]
+        return views, [list_images(os.path.join(data_dir, views[0]), also=mosaic_extensions(dofp))]
     views = tuple(subdirs)[:4]
     if len(views) != 4:
         raise ValueError(f"{who} needs four view directories, got {views}")
@@ -790,7 +1008,7 @@ def write_specular_masks(data_dir, out_dir, subdirs=PSD_SUBDIRS, angles=None, na
     if name_from not in (0, 1, 2, 3):
         raise ValueError(f"write_specular_masks: name_from {name_from!r} is not a view index 0..3")
     check_capture(capture, dofp, dofp_demosaic, "write_specular_masks")
-    views, files = polar_sample_files(data_dir, subdirs, "write_specular_masks", capture)
+    views, files = polar_sample_files(data_dir, subdirs, "write_specular_masks", capture, dofp)
     coef = stokes_matrix(_view_angles(angles, views, capture, dofp))
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     os.makedirs(out_dir, exist_ok=True)
@@ -828,7 +1046,7 @@ def write_estimated_diffuse(data_dir, out_dir, subdirs=PSD_SUBDIRS, mode="min", 
     if mode not in ops.POLAR_MODES:
         raise ValueError(f"write_estimated_diffuse: mode {mode!r} is not 'min' or 'stokes'")
     check_capture(capture, dofp, dofp_demosaic, "write_estimated_diffuse")
-    views, files = polar_sample_files(data_dir, subdirs, "write_estimated_diffuse", capture)
+    views, files = polar_sample_files(data_dir, subdirs, "write_estimated_diffuse", capture, dofp)
     coef = stokes_matrix(_view_angles(angles, views, capture, dofp)) if mode == "stokes" else None
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     os.makedirs(out_dir, exist_ok=True)

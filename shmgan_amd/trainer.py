@@ -63,6 +63,7 @@ _DEFAULTS = dict(image_size=128, image_hw=None, batch_size=1, filter_size=64, g_
                  capture_format="views", dofp_dir="DOFP", dofp_pattern="mono", dofp_quad_angles=(90, 45, 135, 0), dofp_bits=8,
                  dofp_demosaic="bilinear", dofp_test_view="total",
                  dofp_black=None, dofp_white=None, dofp_wb=None, dofp_ccm=None, dofp_tone=None, dofp_sat=None, dofp_calibration=None,
+                 dofp_exposures=None, dofp_bracket_black=None, dofp_bracket_white=None,
                  specseg_image_dir="", specseg_mask_dir="", specseg_epochs=20, specseg_lr=1e-3, specseg_batch_size=8,
                  specseg_mask_source="dir", specseg_mask_threshold="otsu", specseg_mask_floor=16, specseg_mask_open=1,
                  specseg_mask_dilate=2,
@@ -816,7 +817,7 @@ class ShmGANwithSSpecSeg:
         aug_flip_ud=0.5 is the as-intended reading of the per-step draw below.  `cache="device"` (with `cache_gb`, GiB; default half of the free
         device memory) keeps the decoded samples on the device after their first decode, the reference's `.cache()`;
         `self.loadedDataset.cache_stats()` says what it holds.  `capture_format="dofp"` (with `dofp_dir`, `dofp_pattern`, `dofp_quad_angles`,
-        `dofp_bits`, `dofp_demosaic`, and `dofp_black` / `dofp_white` / `dofp_wb` / `dofp_ccm` / `dofp_tone` / `dofp_sat` to develop the frames and `dofp_calibration`, the path of a saved polar.DofpCalibration, to correct them first: data.capture_options) trains from one polariser-mosaic frame per sample instead of four view files.  `ema_decay` (with `ema_warmup`) keeps an average of the generator's weights
+        `dofp_bits`, `dofp_demosaic`, and `dofp_black` / `dofp_white` / `dofp_wb` / `dofp_ccm` / `dofp_tone` / `dofp_sat` to develop the frames and `dofp_calibration`, the path of a saved polar.DofpCalibration, to correct them first, and `dofp_exposures` (with `dofp_bracket_black` / `dofp_bracket_white`) to read an exposure bracket per sample, one multi-page TIFF, merged on the device: data.capture_options) trains from one polariser-mosaic frame per sample instead of four view files.  `ema_decay` (with `ema_warmup`) keeps an average of the generator's weights
         (_ensure_ema, generator_weights); `val_dir` or `val_fraction` (with `val_seed`, `val_step`, `val_batch_size`, `val_monitor`, `val_region`) hold captures
         out: every `val_step` epochs, in front of the checkpoint, and once at the end they are scored (validate), rank 0 appends the means to
         `log_dir`/validation.jsonl and keeps the best weights as `checkpoint_save_dir`/best.npz (validation.py).  Both are off by default and

@@ -3,13 +3,15 @@ share of the HBM peak, for 8-bit mono, 12-bit mono, 12-bit RGGB bilinear and 12-
 and the host time PIL takes to decode the four view PNGs the one mosaic replaces; then shm_dofp_develop (csrc/dofp_develop.hip) on the
 same frames by the same protocol, beside the plain launch in the same run: 12-bit mono and RGGB, bilinear and bin, and 8-bit bilinear, without and with the
 colour matrix, and with wb "gray" including its two estimation launches; then shm_dofp_calibrate (csrc/dofp_calibrate.hip) at 8 and 12 bits, with
-all three tables and with the dark frame alone, beside a device copy of the same bytes and the plain RGGB demosaic launch of the same frame.
+all three tables and with the dark frame alone, beside a device copy of the same bytes and the plain RGGB demosaic launch of the same frame;
+then shm_dofp_merge (csrc/dofp_merge.hip) of a bracket of three pages at 8 and 12 bits, with and without counts, beside a device copy of the
+same bytes (three pages read, one 16-bit page written) and the calibrate launch (dark frame alone) of one page.
 A record for kernel work, not an acceptance number.
 
 Bytes are algorithmic and computed from the shapes here: the mosaic read once plus the planes written.  Device events around
 LAUNCHES launches, 2 warm-ups and 5 timed iterations, seeded data.  The launches rotate over SETS source / destination sets (more
 than the 256 MiB Infinity Cache together), so that a frame comes from and goes to HBM as a camera's next frame would.
-python tools/bench_dofp.py [--launches N] [--no-views] [--no-decode] [--no-develop] [--no-calibrate]"""
+python tools/bench_dofp.py [--launches N] [--no-views] [--no-decode] [--no-develop] [--no-calibrate] [--no-merge]"""
 import argparse
 import ctypes as C
 import io
@@ -133,6 +135,51 @@ def calibrate_launcher(bits, tables, rng, what):
     return fn, (H * W * size + 4 * H * W * 3 if what == "views" else nbytes)
 
 
+MERGE_EXPOSURES = (1, 4, 16)
+
+
+def merge_launcher(bits, counts, rng, what):
+    """(fn that launches on set i, bytes per launch) for what = "merge", "copy" (one device-to-device copy that moves the same bytes: n
+    pages read, one 16-bit page written) or "calibrate" (shm_dofp_calibrate of ONE page with the dark frame alone: the launch a bracketed
+    layout with a calibration makes n times in front of the merge).  The pages are a radiance ramp through the three exposures, so that
+    every number of valid pages occurs."""
+    from shmgan_amd import polar
+    L = _lib.lib()
+    n = len(MERGE_EXPOSURES)
+    dt = np.uint8 if bits == 8 else np.uint16
+    size = np.dtype(dt).itemsize
+    maxv = (1 << bits) - 1
+    black, white = maxv // 16, maxv - maxv // 8
+    nbytes = n * H * W * size + H * W * 2
+    st = torch.cuda.current_stream().cuda_stream
+    mul = polar.DofpBracket(MERGE_EXPOSURES).table(bits)
+    table, mirror = torch.from_numpy(mul.copy()).cuda(), (C.c_uint * 256)(*[int(v) for v in mul])
+    sets = []
+    for _ in range(SETS):
+        if what == "copy":
+            sets.append((torch.empty(nbytes // 2, dtype=torch.uint8, device="cuda"), torch.empty(nbytes // 2, dtype=torch.uint8, device="cuda")))
+            continue
+        light = rng.random((H, W)) ** 2 * 1.3 * (white - black)
+        pages = torch.from_numpy(np.stack([np.clip(black + light * e + rng.normal(0, 2, (H, W)), 0, maxv) for e in MERGE_EXPOSURES]).astype(dt)).cuda()
+        if what == "calibrate":
+            sets.append((pages[0], torch.empty_like(pages[0]), torch.from_numpy(rng.integers(black // 2, 2 * black, (H, W)).astype(np.uint16)).cuda()))
+        else:
+            sets.append((pages, (C.c_void_p * n)(*[pages[k].data_ptr() for k in range(n)]), torch.empty((H, W), dtype=torch.uint16, device="cuda"),
+                         torch.empty(9, dtype=torch.int32, device="cuda") if counts else None))
+
+    def fn(i):
+        s = sets[i % SETS]
+        if what == "copy":
+            s[1].copy_(s[0], non_blocking=True)
+        elif what == "calibrate":
+            _lib.check(L.shm_dofp_calibrate(s[0].data_ptr(), bits, H, W, W, ops.DOFP_PATTERNS["rggb"], s[2].data_ptr(), None, None, black, white,
+                                            s[1].data_ptr(), W, st), "shm_dofp_calibrate")
+        else:
+            _lib.check(L.shm_dofp_merge(s[1], n, bits, H, W, W, table.data_ptr(), mirror, black, white, s[2].data_ptr(), W,
+                                        None if s[3] is None else s[3].data_ptr(), st), "shm_dofp_merge")
+    return fn, (2 * H * W * size + 2 * H * W if what == "calibrate" else nbytes)
+
+
 def timed(fn, launches, warm=2, n=5):
     """Median microseconds per launch over n timed iterations of `launches` launches (device events)."""
     us = []
@@ -174,6 +221,7 @@ if __name__ == "__main__":
     ap.add_argument("--no-develop", action="store_true")
     ap.add_argument("--no-views", action="store_true")
     ap.add_argument("--no-calibrate", action="store_true")
+    ap.add_argument("--no-merge", action="store_true")
     a = ap.parse_args()
     rng = np.random.default_rng(0)
     print(f"shm_dofp_views, {W} x {H} frames, {SETS} buffer sets in rotation, {a.launches} launches per timed iteration")
@@ -211,3 +259,14 @@ if __name__ == "__main__":
                     bw = nbytes / (row[what] * 1e-6)
                     print(f"  {bits:2d}-bit {name:22s} {what:9s}: {row[what]:8.2f} us  {nbytes / 1e6:7.2f} MB  {bw / 1e12:5.2f} TB/s = {100 * bw / HBM_PEAK:4.1f} % of peak", flush=True)
                 print(f"  {bits:2d}-bit {name:22s} calibrate = x{row['calibrate'] / row['copy']:.2f} of the copy, x{row['calibrate'] / row['views']:.2f} of the demosaic launch", flush=True)
+    if not a.no_merge:
+        print(f"shm_dofp_merge of {len(MERGE_EXPOSURES)} pages (exposures {MERGE_EXPOSURES}) beside a device copy of the same bytes and the calibrate launch (dark frame alone) of one page")
+        for bits in (8, 12):
+            for counts in (False, True):
+                row = {}
+                for what in ("merge", "copy", "calibrate"):
+                    fn, nbytes = merge_launcher(bits, counts, rng, what)
+                    row[what] = timed(fn, a.launches)[0]
+                    bw = nbytes / (row[what] * 1e-6)
+                    print(f"  {bits:2d}-bit {'with counts' if counts else 'no counts  '} {what:9s}: {row[what]:8.2f} us  {nbytes / 1e6:7.2f} MB  {bw / 1e12:5.2f} TB/s = {100 * bw / HBM_PEAK:4.1f} % of peak", flush=True)
+                print(f"  {bits:2d}-bit {'with counts' if counts else 'no counts  '} merge = x{row['merge'] / row['copy']:.2f} of the copy, x{row['merge'] / row['calibrate']:.2f} of one calibrate launch", flush=True)
